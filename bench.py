@@ -11,9 +11,16 @@ A "step" = one such pass over one batch of synthetic inputs that are already res
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` (dominant kernel =
-the bf16 MFMA projection GEMM, timed live with HIP events on its launch stream) and `cpu_baseline`
-(the oracle's joint step timed on the host cores on a bounded sample; N=1 only).
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times the K steps and
+prints the headline (`metric`, `value`, `unit`, `ms_per_step`, `loss`, `param_checksum`, `comm`, ...), nothing more.
+`--full` adds what takes runs or passes of its own: `roofline` (dominant kernel = the bf16 MFMA projection GEMM, timed
+live with HIP events on its launch stream inside the timed region), `attention` and the HBM-bound families (a separate
+pass of events after it), `cpu_baseline` (the oracle's joint step timed on the host cores on a bounded sample; N=1 only)
+and, for the default shapes, the per-stage lines (`stages`: C1, C2, C3, C5).
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32 / float64, a few tens of MB at
+most): the loss, the user embeddings and a fixed, seeded sample of the trainable parameters after the optimizer step and
+of their gradients.  The inputs are seeded, so equal arguments give equal inputs from run to run.
 """
 import argparse
 import json
@@ -71,6 +78,11 @@ def parse():
     ap.add_argument("--comm-bf16", action="store_true",
                     help="multi-GPU, opt-in: the item Q-Former's gradient buckets cross xGMI as bf16 (dp.GradBuckets wire_dtype); default f32")
     ap.add_argument("--lora-dropout", type=float, default=0.1, help="LoRA adapter dropout (reference lora_dropout=0.1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / attention / HBM-family events, the CPU oracle "
+                         "baseline and the per-stage lines (the --no-* switches above act on these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -461,6 +473,26 @@ def measure_stage(args, rank, world, device):
     t_host = time.perf_counter() - t0          # the host has issued every launch of the timed steps (nothing synchronises inside a step)
     sync()
     dt = time.perf_counter() - t0
+    if dist_on:
+        t = torch.tensor([dt], device=device, dtype=torch.float64)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        dt = float(t.item())
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "params_sample": pack_sample(pack.master), "grad_sample": pack_sample(pack.grad)})
+
+    def line(**full):
+        """The stage's line (rank 0), with the --full measurements (`full`) inside."""
+        return {"metric": metric, "value": round(world * B * args.steps / dt, 2), "unit": unit, "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "host_issue_ms_per_step": round(t_host / args.steps * 1e3, 2),
+                "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+                "config": {"workload": args.workload, "per_gpu_batch": B, "global_batch": B * world, "dropout": "off" if args.no_dropout else "on",
+                           "parallelism": f"dp{world}"},
+                "step_tflops_per_gpu": round(flops / (dt / args.steps) / 1e12, 1), "loss": round(float(loss.detach()), 5),
+                "max_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 1), **full, "comm": _comm_info(world)}
+
+    if not args.full:
+        return line() if rank == 0 else None
     # roofline leg: HIP events around every GEMM launch, in a SEPARATE pass of the same step right after the timed region -- a stage step
     # is ~270 GEMM launches of 20-100 us, and two event objects + records per launch cost the timed loop 5-20 % on a slow host core
     # (the C4 line keeps its events inside the timed region: 1190 launches per 430 ms)
@@ -477,10 +509,6 @@ def measure_stage(args, rank, world, device):
         step()
     sync()
     aprof, hip.PROFILE_ATTN = hip.PROFILE_ATTN, None
-    if dist_on:
-        t = torch.tensor([dt], device=device, dtype=torch.float64)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        dt = float(t.item())
     if rank == 0:
         # roofline of the dominant kernel family of the stage: every MFMA GEMM launch of the timed region (projections,
         # dX, token-reduction dW), HIP events on the launching stream
@@ -516,14 +544,7 @@ def measure_stage(args, rank, world, device):
                 attn_shapes[f"{kind}_q{aSq}_k{aSk}"].update({"GB_per_s_swept": round(nbytes * swept_frac / (ms / n) / 1e6, 1), "swept_frac": round(swept_frac, 4),
                                                            "hbm_fraction_swept": round(nbytes * swept_frac / (ms / n) / 1e6 / 8000.0, 4)})
         roof["attention_by_shape"] = attn_shapes
-        out = {"metric": metric, "value": round(world * B * args.steps / dt, 2), "unit": unit, "n_gpus": world, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "host_issue_ms_per_step": round(t_host / args.steps * 1e3, 2),
-               "higher_is_better": True, "scaling": "weak",
-               "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-               "config": {"workload": args.workload, "per_gpu_batch": B, "global_batch": B * world, "dropout": "off" if args.no_dropout else "on",
-                          "parallelism": f"dp{world}"},
-               "step_tflops_per_gpu": round(flops / (dt / args.steps) / 1e12, 1), "loss": round(float(loss.detach()), 5),
-               "max_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 1), "roofline": roof, "comm": _comm_info(world)}
+        out = line(roofline=roof)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_subprocess(args)
         else:
@@ -586,6 +607,8 @@ def measure_item_c1(args, rank, world, device, g):
         graph = {"captured": False, "error": f"{type(e).__name__}: {str(e)[:160]}"}
     if rank != 0:
         return None
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"recon_stats": sums.double()})
     sums = sums.float().cpu().tolist()
     # bytes one call has to move: the live bf16 weights once + the field embeddings + the reconstruction read back by the metric kernel
     live = sum(p_.numel() for n_, p_ in m.named_parameters() if n_ in m._ensure_pack(device).params)
@@ -599,7 +622,7 @@ def measure_item_c1(args, rank, world, device, g):
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
            "config": {"workload": "item_c1", "per_gpu_batch": B, "mode": "eval (dropout off)", "eval_mse": round(sums[0] / max(sums[1], 1.0), 6), "eval_cos_mean": round(sums[2] / max(sums[1], 1.0), 6)},
            "max_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 2), "roofline": roof}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_subprocess(args)
     return out
 
@@ -623,6 +646,34 @@ def _comm_info(world):
             return {"backend": "rccl (native ur_comm_*; rendezvous over torch.distributed " + be + ")", "ranks": c.world, "allreduce_launches": c.launches}
         return {"backend": "rccl (torch.distributed nccl)" if be == "nccl" else be, "ranks": d.get_world_size()}
     return {"backend": None, "ranks": 1}
+
+
+# ---- --dump-outputs: what the last timed step computed, for an output-for-output comparison of two builds ----------------
+DUMP_SAMPLE = 1 << 20          # elements kept of a flat parameter / gradient pack larger than this (a fixed, seeded sample)
+DUMP_LIMIT = 64 << 20          # bytes one dump may write
+
+
+def pack_sample(t, seed=0):
+    """The flat tensor t whole when it holds at most DUMP_SAMPLE elements, else DUMP_SAMPLE of its elements at sorted indices
+    drawn (with replacement) from a CPU generator seeded with `seed`: a pack of the same size is sampled at the same indices."""
+    t = t.detach().reshape(-1)
+    if t.numel() <= DUMP_SAMPLE:
+        return t
+    idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return t[idx.to(t.device)]
+
+
+def dump_outputs(path, arrays):
+    """name -> tensor, written as path/<name>.npy: float64 for scalars and float64 tensors, float32 for everything else."""
+    import numpy as np
+    host = {k: (t.detach().double() if t.numel() == 1 or t.dtype == torch.float64 else t.detach().float()).cpu().numpy()
+            for k, t in arrays.items()}
+    nbytes = sum(a.nbytes for a in host.values())
+    if nbytes > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {nbytes} bytes (limit {DUMP_LIMIT})")
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def main():
@@ -653,12 +704,13 @@ def main():
     dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
     import gc
     # ---- per-stage lines (BASELINE configs[0], [1], [2], [4]), measured in this same process after the headline; every rank
-    # takes part (the stages all-reduce their gradient packs like the joint step)
+    # takes part (the stages all-reduce their gradient packs like the joint step); --full only
     stages = {}
-    if args.stages and args.batch == 64 and args.hist == 50 and args.seq == 2048 and not args.user_tokens and args.layers == 28:
+    if args.full and args.stages and args.batch == 64 and args.hist == 50 and args.seq == 2048 and not args.user_tokens and args.layers == 28:
         gc.collect(); torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
         for wl, key in (("item_c1", "item_c1"), ("item", "item_c2"), ("user", "user_c3")):
-            sa = argparse.Namespace(**{**vars(args), "workload": wl, "steps": args.stage_steps, "warmup": 3, "cpu_budget": args.stage_cpu_budget})
+            sa = argparse.Namespace(**{**vars(args), "workload": wl, "steps": args.stage_steps, "warmup": 3, "cpu_budget": args.stage_cpu_budget,
+                                       "dump_outputs": None})
             so = measure_stage(sa, rank, world, device)
             if rank == 0:
                 stages[key] = {k: so[k] for k in ("metric", "value", "unit", "steps", "ms_per_step", "latency_us", "host_issue_ms_per_step", "step_tflops_per_gpu", "max_mem_gb", "config", "roofline", "hip_graph") if k in so}
@@ -672,7 +724,7 @@ def main():
             # gate|up / act of the LAST 14 layers are kept (4.8 GB each at 262144 tokens: ~262 GB of 288), the first 14 rebuilt in the backward;
             # should the allocator refuse, the line falls back to rebuilding all 28 (201.8 GB) and says so in config.recompute_mlp
             ca = argparse.Namespace(**{**vars(args), "hist": 100, "seq": 4096, "pool": 10000, "user_tokens": True, "recompute_mlp": False, "recompute_mlp_layers": int(os.environ.get("UNIREC_BENCH_C5_REBUILD_LAYERS", "14" if world == 1 else "20")),      # (multi-rank: room for the communicator's buffers; no fallback there)
-                                       "steps": 2, "warmup": 1, "micro_batches": 1, "cpu_budget": args.c5_cpu_budget, "cpu_runs": 1})
+                                       "steps": 2, "warmup": 1, "micro_batches": 1, "cpu_budget": args.c5_cpu_budget, "cpu_runs": 1, "dump_outputs": None})
             refused = False
             try:
                 so = measure_joint(ca, rank, world, device, side_steps=1)
@@ -717,7 +769,7 @@ def measure_joint(args, rank, world, device, side_steps=3):
     dp.set_dp_rank(rank, model, qf)                # dropout / LoRA-dropout masks keyed on the global sample index (same seeds on every rank)
     qpack, lpack = qf._ensure_pack(device), qw._ensure_pack(device)
     packs = [qpack, lpack]
-    ubk = None
+    ubk = upack = None
     if model.user_qformer is not None:
         upack = model.user_qformer._ensure_pack(device)
         packs.append(upack)
@@ -739,10 +791,13 @@ def measure_joint(args, rank, world, device, side_steps=3):
     if B % nmb:
         raise SystemExit(f"--batch {B} is not a multiple of --micro-batches {nmb}")
     mb = B // nmb
+    dump = getattr(args, "dump_outputs", None)
+    users = []                  # --dump-outputs: the user embeddings of the latest step, one entry per micro-batch
 
     def step():
         opt.zero_grad()
         total = None
+        del users[:]
         for k in range(nmb):
             sl = slice(k * mb, (k + 1) * mb)
             last = k == nmb - 1
@@ -754,6 +809,8 @@ def measure_joint(args, rank, world, device, side_steps=3):
             ut, um = batch["user_sequence_tokens"], batch["user_attention_mask"]
             user = model(batch["input_ids"][sl], batch["attention_mask"][sl], batch["history_field_embeddings"][sl],
                          batch["history_attention_mask"][sl], None if ut is None else ut[sl], None if um is None else um[sl])
+            if dump:
+                users.append(user.detach())
             nm = batch["negative_masks"]
             loss = loss_fn(user, batch["positive_item_embeddings"][sl], batch["negative_item_embeddings"][sl], None if nm is None else nm[sl])
             if nmb > 1:
@@ -786,11 +843,12 @@ def measure_joint(args, rank, world, device, side_steps=3):
     for _ in range(args.warmup):
         step()
     sync()
-    # Inside the timed region: HIP events around the launches of the DOMINANT family only (the projection GEMMs: `roofline`).  The events
-    # of the attention launches and of the HBM-bound families (1000+ more per step; every timed record is a barrier packet, together
+    # --full, inside the timed region: HIP events around the launches of the DOMINANT family only (the projection GEMMs: `roofline`).  The
+    # events of the attention launches and of the HBM-bound families (1000+ more per step; every timed record is a barrier packet, together
     # 4-6 ms of a 425 ms step: same-box A/B with UNIREC_BENCH_EVENTS=0) run in a separate pass of the same step after the timed region.
+    # A plain run records no events at all.
     ev_in_loop = os.environ.get("UNIREC_BENCH_EVENTS", "1") != "0"      # lab: 0 = no HIP events inside the timed region at all
-    if ev_in_loop:
+    if ev_in_loop and args.full:
         hip.PROFILE = []
     del waits[:]
     t0 = time.perf_counter()
@@ -821,6 +879,33 @@ def measure_joint(args, rank, world, device, side_steps=3):
     # what the timed steps left in the trainable parameters (f64 sums of the flat fp32 masters): equal runs give equal digits,
     # and under data parallelism every rank must print the same ones (tests/test_gpu_dp_rccl.py)
     checksum = {"lora": float(lpack.master.double().abs().sum().item()), "qformer": float(qpack.master.double().abs().sum().item())}
+    if dump and rank == 0:      # before the side pass below steps the model again
+        arrays = {"loss": loss, "user_embeddings": torch.cat(users)}
+        for name, pack in (("lora", lpack), ("qformer", qpack), ("user_qformer", upack)):
+            if pack is not None:
+                arrays[f"{name}_params_sample"] = pack_sample(pack.master)
+                arrays[f"{name}_grad_sample"] = pack_sample(pack.grad)
+        dump_outputs(dump, arrays)
+
+    def headline(**full):
+        """The line's object (rank 0): the headline and what the timed steps left, with the --full measurements (`full`) inside."""
+        return {"metric": f"user-sequences/sec joint fwd+bwd (Qwen3-0.6B+LoRA, hist={args.hist})", "value": round(world * B * args.steps / dt, 3),
+                "unit": "user-sequences/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                "dtype": "bf16", "data": "synthetic",
+                "config": {"workload": ("C5-shaped joint step with the User Q-Former's 64 tokens (U4): " if n_user else "C4 joint step: ") +
+                                       f"item Q-Former(L12,H1024,Q2,F14) on {B}x{args.hist} items -> inject -> "
+                                       f"Qwen3-0.6B-shaped({cfg.num_hidden_layers}L)+LoRA r16 -> mean-pool -> InfoNCE pool {args.pool}; "
+                                       f"fwd+bwd+allreduce+AdamW", "per_gpu_batch": B, "global_batch": B * world, "seq_len": args.seq,
+                           "hist": args.hist, "pool": args.pool, "dropout": 0.0 if args.no_dropout else 0.2, "lora_dropout": 0.0 if args.no_dropout else args.lora_dropout,
+                           "micro_batches": nmb, "recompute_mlp": (qw.recompute_mlp if isinstance(qw.recompute_mlp, bool) else f"layers 0..{int(qw.recompute_mlp) - 1}"), "parallelism": f"dp{world}", "random_init": True},
+                "step_tflops_per_gpu": round(flops_per_step(args, B, cfg, dims) / (dt / args.steps) / 1e12, 1), "loss": round(lossv, 4),
+                "max_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 1), **full, "comm": {**_comm_info(world), **comm_extra}, "param_checksum": checksum}
+
+    if not args.full:
+        qw.grad_ready_hook = None             # (the hooks hold the buckets: drop the cycle so the packs can be freed)
+        qf.qformer.grad_ready_hook = None
+        return headline() if rank == 0 else None
     # the side pass: attention and HBM-bound family events (all ranks run it: the step holds collectives)
     nside = max(1, min(args.steps, side_steps))
     hip.PROFILE_ATTN, hip.PROFILE_STREAM = [], []
@@ -922,19 +1007,7 @@ def measure_joint(args, rank, world, device, side_steps=3):
         attn["kernels"] = ("attn_fwd_c128_kernel; attn_bwd_dq_c128_kernel + attn_bwd_dkv_c128_kernel (one ur_attn_bwd call): main loops "
                            "generated by tools/asmgen (one wave per SIMD, hand-scheduled); executed_over_algorithmic counts the MFMAs they issue: "
                            "forward incl. the row-sum products, backward 7 contractions for the 5 algorithmic ones (S and dP in both kernels)")
-        fl = flops_per_step(args, B, cfg, dims)
-        out = {"metric": f"user-sequences/sec joint fwd+bwd (Qwen3-0.6B+LoRA, hist={args.hist})", "value": round(world * B * args.steps / dt, 3),
-               "unit": "user-sequences/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "bf16", "data": "synthetic",
-               "config": {"workload": ("C5-shaped joint step with the User Q-Former's 64 tokens (U4): " if n_user else "C4 joint step: ") +
-                                      f"item Q-Former(L12,H1024,Q2,F14) on {B}x{args.hist} items -> inject -> "
-                                      f"Qwen3-0.6B-shaped({cfg.num_hidden_layers}L)+LoRA r16 -> mean-pool -> InfoNCE pool {args.pool}; "
-                                      f"fwd+bwd+allreduce+AdamW", "per_gpu_batch": B, "global_batch": B * world, "seq_len": args.seq,
-                          "hist": args.hist, "pool": args.pool, "dropout": 0.0 if args.no_dropout else 0.2, "lora_dropout": 0.0 if args.no_dropout else args.lora_dropout,
-                          "micro_batches": nmb, "recompute_mlp": (qw.recompute_mlp if isinstance(qw.recompute_mlp, bool) else f"layers 0..{int(qw.recompute_mlp) - 1}"), "parallelism": f"dp{world}", "random_init": True},
-               "step_tflops_per_gpu": round(fl / (dt / args.steps) / 1e12, 1), "loss": round(lossv, 4),
-               "max_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 1), "roofline": roof, "attention": attn, "comm": {**_comm_info(world), **comm_extra}, "param_checksum": checksum}
+        out = headline(roofline=roof, attention=attn)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_subprocess(args)
         elif world > 1:

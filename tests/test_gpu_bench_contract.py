@@ -1,11 +1,13 @@
-"""GPU: the bench.py contract -- ONE JSON line with the keys the driver reads, a `roofline` object whose numbers are
-self-consistent, a `cpu_baseline` timed by the oracle, and the per-stage lines.  Reduced sizes (2 decoder layers, 8 sequences of
+"""GPU: the bench.py contract -- ONE JSON line with the keys the driver reads; under --full a `roofline` object whose numbers
+are self-consistent, a `cpu_baseline` timed by the oracle, and the per-stage lines; without it the headline alone, and
+--dump-outputs writes what the last timed step computed.  Reduced sizes (2 decoder layers, 8 sequences of
 512 tokens): this checks the plumbing, not the numbers."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -33,7 +35,7 @@ def _common(d, n_gpus=1):
 
 
 def test_joint_line_contract():
-    d = _run(["--steps", "2", "--warmup", "1", "--layers", "2", "--batch", "8", "--seq", "512", "--hist", "10", "--pool", "64", "--cpu-budget", "20"])
+    d = _run(["--full", "--steps", "2", "--warmup", "1", "--layers", "2", "--batch", "8", "--seq", "512", "--hist", "10", "--pool", "64", "--cpu-budget", "20"])
     _common(d)
     assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "user-sequences/sec"
     assert abs(d["value"] - 8 * 1000.0 / d["ms_per_step"]) <= 0.02 * d["value"]          # value = sequences / measured time
@@ -46,7 +48,7 @@ def test_joint_line_contract():
 
 @pytest.mark.parametrize("workload,unit", [("item", "items/sec"), ("user", "user-sequences/sec")])
 def test_stage_line_contract(workload, unit):
-    d = _run(["--workload", workload, "--steps", "2", "--warmup", "1", "--batch", "16", "--hist", "4", "--cpu-budget", "20"])
+    d = _run(["--full", "--workload", workload, "--steps", "2", "--warmup", "1", "--batch", "16", "--hist", "4", "--cpu-budget", "20"])
     _common(d)
     assert d["unit"] == unit and d["config"]["workload"] == workload
     assert d["cpu_baseline"]["unit"] == unit and d["cpu_baseline"]["value"] > 0
@@ -55,7 +57,7 @@ def test_stage_line_contract(workload, unit):
 def test_item_c1_line_contract():
     """BASELINE configs[0] (C1): eval forward + reconstruction metrics on the GPU, launch by launch and as one hipGraph replay, beside the
     oracle's CPU figure (round 6: every BASELINE config has a number in the driver's line -- `stages.item_c1`)."""
-    d = _run(["--workload", "item_c1", "--cpu-budget", "10"])
+    d = _run(["--full", "--workload", "item_c1", "--cpu-budget", "10"])
     assert d["unit"] == "items/sec" and d["value"] > 0 and d["config"]["workload"] == "item_c1" and d["config"]["per_gpu_batch"] == 16
     r = d["roofline"]
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-4
@@ -67,3 +69,29 @@ def test_item_c1_line_contract():
     assert 0.0 < d["config"]["eval_mse"] < 1e4          # (random-init heads: the value only has to be a finite masked MSE)
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["unit"] == "items/sec" and c["value"] > 0
+
+
+def test_plain_joint_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline and what the timed steps left, none of the separate measurements; --dump-outputs
+    writes the last timed step's loss, user embeddings and parameter / gradient samples, and equal arguments give equal inputs."""
+    args = ["--steps", "2", "--warmup", "1", "--layers", "2", "--batch", "8", "--seq", "512", "--hist", "10", "--pool", "64"]
+    runs = []
+    for tag in ("a", "b"):
+        d = _run(args + ["--dump-outputs", str(tmp_path / tag)])
+        for k, t in (("metric", str), ("value", float), ("unit", str), ("higher_is_better", bool), ("dtype", str), ("ms_per_step", float)):
+            assert isinstance(d[k], t), (k, d.get(k))
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "user-sequences/sec" and d["dtype"] == "bf16"
+        assert abs(d["value"] - 8 * 1000.0 / d["ms_per_step"]) <= 0.02 * d["value"]
+        assert not {"roofline", "attention", "cpu_baseline", "stages"} & set(d), sorted(d)
+        files = sorted(os.listdir(tmp_path / tag))
+        assert files == sorted(f"{n}.npy" for n in ("loss", "user_embeddings", "lora_params_sample", "lora_grad_sample",
+                                                    "qformer_params_sample", "qformer_grad_sample"))
+        arrs = {f[:-4]: np.load(tmp_path / tag / f) for f in files}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["user_embeddings"].shape == (8, 1024) and round(float(arrs["loss"]), 4) == d["loss"]
+        runs.append((d, arrs))
+    (da, a), (db, b) = runs
+    assert da["loss"] == db["loss"] and da["param_checksum"] == db["param_checksum"]
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-7, err_msg=k)

@@ -3,8 +3,8 @@
 # usage (on the GPU box): bash tools/lab/bench_ab.sh <lib name> <out tag>
 OUT=gpurun_out/$2; mkdir -p $OUT
 for r in 1 2; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-stages --steps 4 > $OUT/new_$r.json 2>> $OUT/err.txt || exit 1
-  UNIREC_HIP_LIB=tools/lab/libs/$1.so timeout -k 10 300 python bench.py --no-cpu-baseline --no-stages --steps 4 > $OUT/old_$r.json 2>> $OUT/err.txt || exit 1
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-stages --steps 4 > $OUT/new_$r.json 2>> $OUT/err.txt || exit 1
+  UNIREC_HIP_LIB=tools/lab/libs/$1.so timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-stages --steps 4 > $OUT/old_$r.json 2>> $OUT/err.txt || exit 1
 done
 python - <<PY
 import json
