@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 12
+#define UR_ABI_VERSION 13
 
 int ur_version(void);
 const char* ur_last_error(void);
@@ -474,6 +474,30 @@ int ur_swiglu_bwd(const void* dact, const void* gu, void* dgu, int32_t M, int32_
 int ur_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                   float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale,
                   void* stream);
+/* = ur_adamw_step with the gradient scaled by grad_scale * (*coef): coef is a DEVICE scalar, the clip coefficient
+ * ur_grad_norm_clip wrote earlier on the same stream (no host read).  *coef == 1.0f gives ur_adamw_step's bits. */
+int ur_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                      float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale,
+                      const float* coef, void* stream);
+
+/* Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, L2, as HF Trainer runs it with max_grad_norm,
+ * training/train_item_individual_token_joint.py:755-773) over several f32 ranges (HOST array of device pointer + length; each
+ * start 16-byte aligned, any length):
+ *   norm = sqrt(sum over the ranges of x^2) * grad_scale        -> *out_norm (device)
+ *   coef = min(max_norm / (norm + 1e-6), 1)                      -> *out_coef (device; a NaN norm gives NaN, an Inf norm 0)
+ * Deterministic: each range is cut into UR_NORM_BLOCK_ELEMS-element pieces, one workgroup and one f32 partial per piece, in
+ * range order (UR_NORM_MAX_RANGES ranges per launch, by value), then one workgroup sums the partials in a fixed order.  The
+ * split depends on the ranges only: two calls give the same bits.  partials (device, n_partials floats) needs
+ * sum_i ceil(n_i / UR_NORM_BLOCK_ELEMS) slots.  No float atomics, no host synchronisation. */
+typedef struct {
+  const float* ptr;
+  int64_t n;
+} ur_f32_range;
+#define UR_NORM_BLOCK_ELEMS 16384
+#define UR_NORM_MAX_RANGES 64
+#define UR_NORM_MAX_RANGES_TOTAL (1 << 20)
+int ur_grad_norm_clip(const ur_f32_range* ranges, int32_t n_ranges, float* partials, int32_t n_partials, float grad_scale,
+                      float max_norm, float* out_norm, float* out_coef, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Gradient all-reduce of the data-parallel step (SURVEY 8(b) communicator calls, 8(e)).

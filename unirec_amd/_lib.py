@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -72,6 +72,14 @@ class AttnBwdArgs(ctypes.Structure):
                 ("rope_k", c_void_p), ("rope_ldk", c_i64), ("rope_k_weight", c_void_p), ("rope_rstd_hk0", c_int),
                 ("rope_dk_raw", c_void_p), ("rope_lddkraw", c_i64),
                 ("kv_colsum", c_void_p), ("kv_colsum_ws", c_void_p)]
+
+
+class F32Range(ctypes.Structure):
+    """Mirror of ur_f32_range."""
+    _fields_ = [("ptr", c_void_p), ("n", c_i64)]
+
+
+NORM_BLOCK_ELEMS = 16384      # UR_NORM_BLOCK_ELEMS: a range of n elements takes ceil(n / NORM_BLOCK_ELEMS) partial slots
 
 
 # name -> (restype, argtypes).  Every symbol include/unirec_hip.h declares must appear here
@@ -167,6 +175,9 @@ SIGNATURES = {
     "ur_swiglu_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ur_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_float, c_float, c_float, c_float, c_float,
                               c_int, c_float, c_void_p]),
+    "ur_adamw_step_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_float, c_float, c_float, c_float, c_float,
+                                  c_int, c_float, c_void_p, c_void_p]),
+    "ur_grad_norm_clip": (c_int, [ctypes.POINTER(F32Range), c_int, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-// HBM-bound element-wise kernels: casts, adds, SwiGLU, fused AdamW.  16-byte accesses, grid-stride.
+// HBM-bound element-wise kernels: casts, adds, SwiGLU, fused AdamW, the global gradient norm.  16-byte accesses, grid-stride.
 #include "common.hip.h"
 #include "unirec_hip.h"
 
@@ -147,9 +147,13 @@ __global__ void transpose_batched_kernel(const TransposeDesc* __restrict__ desc,
   }
 }
 
+// DEV_COEF: the gradient scale is grad_scale * (*coef), a clip coefficient a previous kernel wrote on the same stream
+// (ur_adamw_step_dev).  coef == 1.0f leaves gscale's bits unchanged, so an unclipped step equals ur_adamw_step's bit for bit.
+template <bool DEV_COEF>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                              long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                             float gscale) {
+                             float gscale, const float* __restrict__ coef) {
+  if constexpr (DEV_COEF) gscale *= *coef;
   const long n4 = n / 4, stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
@@ -177,6 +181,88 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   }
 }
 
+
+// ---- global L2 norm of several f32 ranges + clip coefficient (ur_grad_norm_clip) ---------------------------------------------
+// Stage 1: every workgroup owns UR_NORM_BLOCK_ELEMS consecutive elements of ONE range (a range of n elements owns
+// ceil(n / UR_NORM_BLOCK_ELEMS) workgroups, in range order) and writes the f32 sum of their squares to its own partial slot.  Stage 2: one workgroup sums the
+// partials in a fixed order (f64) and writes norm / coef.  The grid and the split depend on the ranges only -- not on the CU count,
+// occupancy or the stream -- and there are no atomics: two runs give the same bits.
+constexpr int NORM_THREADS = 256;
+constexpr int NORM_ITERS = UR_NORM_BLOCK_ELEMS / (NORM_THREADS * 4);     // float4 loads per lane
+static_assert(NORM_ITERS * NORM_THREADS * 4 == UR_NORM_BLOCK_ELEMS, "UR_NORM_BLOCK_ELEMS must be a multiple of 1024");
+
+struct NormRanges {
+  const float* p[UR_NORM_MAX_RANGES];
+  int blk0[UR_NORM_MAX_RANGES];     // first workgroup of range i (relative to this launch)
+  int last[UR_NORM_MAX_RANGES];     // its last workgroup
+  int last_len[UR_NORM_MAX_RANGES]; // elements of that last piece, 1 .. UR_NORM_BLOCK_ELEMS
+  int count;
+};
+
+__device__ __forceinline__ float sq4(float4 x) { return (x.x * x.x + x.y * x.y) + (x.z * x.z + x.w * x.w); }
+
+__global__ __launch_bounds__(NORM_THREADS) void sqnorm_partial_kernel(NormRanges rs, float* __restrict__ partials) {
+  __shared__ float red[NORM_THREADS / UR_WAVE];
+  int lo = 0, hi = rs.count - 1;
+  const int blk = blockIdx.x;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (rs.blk0[mid] <= blk) lo = mid; else hi = mid - 1; }
+  // (the piece length is precomputed on the host as a 32-bit value: hipcc 7.x selected a 64-bit min() of two kernel-argument values
+  // through SCC after a VALU compare -- a wrong length that read past the range)
+  const long start = (long)(blk - rs.blk0[lo]) * UR_NORM_BLOCK_ELEMS;
+  const int len = blk == rs.last[lo] ? rs.last_len[lo] : UR_NORM_BLOCK_ELEMS;
+  const float* x = rs.p[lo] + start;              // 16-byte aligned: range starts are, UR_NORM_BLOCK_ELEMS is a multiple of 4
+  const float4* x4 = reinterpret_cast<const float4*>(x);
+  const int t = threadIdx.x;
+  float acc = 0.f;
+  if (len == UR_NORM_BLOCK_ELEMS) {
+    float a[NORM_ITERS];
+#pragma unroll
+    for (int i = 0; i < NORM_ITERS; ++i) a[i] = sq4(x4[i * NORM_THREADS + t]);
+#pragma unroll
+    for (int i = 0; i < NORM_ITERS; ++i) acc += a[i];
+  } else {
+    const int n4 = len / 4;
+    for (int i = t; i < n4; i += NORM_THREADS) acc += sq4(x4[i]);
+    for (int i = n4 * 4 + t; i < len; i += NORM_THREADS) acc += x[i] * x[i];
+  }
+  acc = wave_sum(acc);
+  if ((t & (UR_WAVE - 1)) == 0) red[t / UR_WAVE] = acc;
+  __syncthreads();
+  if (t == 0) {
+    float s = red[0];
+#pragma unroll
+    for (int w = 1; w < NORM_THREADS / UR_WAVE; ++w) s += red[w];
+    partials[blk] = s;
+  }
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// norm = sqrt(sum partials) * grad_scale; coef = max_norm / (norm + 1e-6) clamped to <= 1 as torch.nn.utils.clip_grad_norm_ does:
+// a NaN norm gives a NaN coef (the comparison is false, the NaN stays), an Inf norm gives 0.
+__global__ __launch_bounds__(1024) void norm_finish_kernel(const float* __restrict__ partials, int n, float grad_scale, float max_norm,
+                                                           float* __restrict__ out_norm, float* __restrict__ out_coef) {
+  __shared__ double red[1024 / UR_WAVE];
+  const int t = threadIdx.x;
+  double acc = 0.0;
+  for (int i = t; i < n; i += 1024) acc += (double)partials[i];
+  acc = wave_sum_f64(acc);
+  if ((t & (UR_WAVE - 1)) == 0) red[t / UR_WAVE] = acc;
+  __syncthreads();
+  if (t == 0) {
+    double s = red[0];
+    for (int w = 1; w < 1024 / UR_WAVE; ++w) s += red[w];
+    const float norm = (float)sqrt(s) * grad_scale;
+    float coef = max_norm / (norm + 1e-6f);
+    if (coef > 1.0f) coef = 1.0f;
+    out_norm[0] = norm;
+    out_coef[0] = coef;
+  }
+}
 }  // namespace
 
 extern "C" int ur_cast_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream) {
@@ -254,9 +340,70 @@ extern "C" int ur_adamw_step(float* param, const float* grad, float* exp_avg, fl
              UR_ALIGNED16(exp_avg_sq), "ur_adamw_step: null / misaligned");
   const float bc1 = 1.0f - powf(beta1, (float)step);
   const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
-  hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                     exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);
+  hipLaunchKernelGGL(adamw_kernel<false>, dim3(ew_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, nullptr);
   UR_CHECK_LAUNCH("ur_adamw_step");
+  return 0;
+}
+extern "C" int ur_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                                 float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale,
+                                 const float* coef, void* stream) {
+  UR_REQUIRE(n >= 0 && step >= 1, "ur_adamw_step_dev: need n >= 0 and step >= 1");
+  UR_REQUIRE(coef != nullptr && (((uintptr_t)coef) & 3) == 0, "ur_adamw_step_dev: null / misaligned coef");
+  if (n == 0) return 0;
+  UR_REQUIRE(param && grad && exp_avg && exp_avg_sq && UR_ALIGNED16(param) && UR_ALIGNED16(grad) && UR_ALIGNED16(exp_avg) &&
+             UR_ALIGNED16(exp_avg_sq), "ur_adamw_step_dev: null / misaligned");
+  const float bc1 = 1.0f - powf(beta1, (float)step);
+  const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+  hipLaunchKernelGGL(adamw_kernel<true>, dim3(ew_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, coef);
+  UR_CHECK_LAUNCH("ur_adamw_step_dev");
+  return 0;
+}
+
+extern "C" int ur_grad_norm_clip(const ur_f32_range* ranges, int32_t n_ranges, float* partials, int32_t n_partials, float grad_scale,
+                                 float max_norm, float* out_norm, float* out_coef, void* stream) {
+  UR_REQUIRE(n_ranges >= 0 && n_ranges <= UR_NORM_MAX_RANGES_TOTAL, "ur_grad_norm_clip: n_ranges must be in [0, %d] (got %d)",
+             UR_NORM_MAX_RANGES_TOTAL, (int)n_ranges);
+  UR_REQUIRE(n_ranges == 0 || ranges != nullptr, "ur_grad_norm_clip: null ranges");
+  UR_REQUIRE(max_norm > 0.f, "ur_grad_norm_clip: max_norm must be > 0");
+  UR_REQUIRE(out_norm && out_coef && (((uintptr_t)out_norm) & 3) == 0 && (((uintptr_t)out_coef) & 3) == 0,
+             "ur_grad_norm_clip: null / misaligned out_norm / out_coef");
+  long blocks = 0;
+  for (int i = 0; i < n_ranges; ++i) {
+    UR_REQUIRE(ranges[i].n >= 0, "ur_grad_norm_clip: range %d: negative n", i);
+    if (ranges[i].n == 0) continue;
+    UR_REQUIRE(ranges[i].ptr && UR_ALIGNED16(ranges[i].ptr), "ur_grad_norm_clip: range %d: null / misaligned (16 bytes)", i);
+    blocks += (ranges[i].n + UR_NORM_BLOCK_ELEMS - 1) / UR_NORM_BLOCK_ELEMS;
+    UR_REQUIRE(blocks <= 0x7fffffffL, "ur_grad_norm_clip: too many elements");
+  }
+  UR_REQUIRE(n_partials >= blocks, "ur_grad_norm_clip: %d partial slots, the ranges need %ld (ur_grad_norm_partials rule)",
+             (int)n_partials, blocks);
+  UR_REQUIRE(blocks == 0 || (partials && (((uintptr_t)partials) & 3) == 0), "ur_grad_norm_clip: null / misaligned partials");
+  // ranges go to the device by value, UR_NORM_MAX_RANGES per launch; launch k writes the partial slots after launch k - 1's, so
+  // the order of the partials (and of their sum) is the order of the ranges whatever the split into launches
+  int slot = 0;
+  for (int i = 0; i < n_ranges;) {
+    NormRanges rs = {};
+    int nb = 0;
+    while (i < n_ranges && rs.count < UR_NORM_MAX_RANGES) {
+      if (ranges[i].n > 0) {
+        const int pieces = (int)((ranges[i].n + UR_NORM_BLOCK_ELEMS - 1) / UR_NORM_BLOCK_ELEMS);
+        rs.p[rs.count] = ranges[i].ptr; rs.blk0[rs.count] = nb; rs.last[rs.count] = nb + pieces - 1;
+        rs.last_len[rs.count] = (int)(ranges[i].n - (int64_t)(pieces - 1) * UR_NORM_BLOCK_ELEMS);
+        nb += pieces;
+        ++rs.count;
+      }
+      ++i;
+    }
+    if (nb == 0) continue;
+    hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, rs, partials + slot);
+    UR_CHECK_LAUNCH("ur_grad_norm_clip(partials)");
+    slot += nb;
+  }
+  hipLaunchKernelGGL(norm_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)partials, slot, grad_scale, max_norm,
+                     out_norm, out_coef);
+  UR_CHECK_LAUNCH("ur_grad_norm_clip(finish)");
   return 0;
 }
 

@@ -816,10 +816,41 @@ def swiglu_bwd(dact, gu, I):
 
 
 @_stream_family("adamw", lambda r, param, grad, exp_avg, exp_avg_sq, *a, **k: 2 * _nb(param, exp_avg, exp_avg_sq) + _nb(grad))
-def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
+def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, coef=None):
+    """coef: None (ur_adamw_step) or a 0-d f32 device tensor, the clip coefficient of grad_norm_clip: the gradient is scaled by
+    grad_scale * coef on the device (ur_adamw_step_dev, no host read)."""
     lib = _lib.load()
-    check(lib.ur_adamw_step(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), param.numel(), lr,
-                            beta1, beta2, eps, weight_decay, step, grad_scale, _stream()), "ur_adamw_step")
+    if coef is None:
+        check(lib.ur_adamw_step(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), param.numel(), lr,
+                                beta1, beta2, eps, weight_decay, step, grad_scale, _stream()), "ur_adamw_step")
+    else:
+        _need(coef, F32, "adamw_step(coef)")
+        check(lib.ur_adamw_step_dev(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), param.numel(), lr,
+                                    beta1, beta2, eps, weight_decay, step, grad_scale, coef.data_ptr(), _stream()), "ur_adamw_step_dev")
+
+
+def grad_norm_partials(ranges):
+    """partial slots ur_grad_norm_clip needs for these ranges (UR_NORM_BLOCK_ELEMS elements per slot)"""
+    return sum(-(-r.numel() // _lib.NORM_BLOCK_ELEMS) for r in ranges)
+
+
+@_stream_family("grad_norm", lambda r, ranges, *a, **k: _nb(*ranges))
+def grad_norm_clip(ranges, grad_scale, max_norm, out_norm, out_coef):
+    """torch.nn.utils.clip_grad_norm_'s global L2 norm and clip coefficient over a list of contiguous f32 device tensors (the live
+    gradient spans), without touching them: out_norm = ||all ranges|| * grad_scale, out_coef = min(max_norm / (norm + 1e-6), 1),
+    both 0-d f32 device tensors written on the current stream (no host sync).  Deterministic (fixed split, no atomics)."""
+    lib = _lib.load()
+    _need(out_norm, F32, "grad_norm_clip(out_norm)")
+    _need(out_coef, F32, "grad_norm_clip(out_coef)")
+    for r in ranges:
+        _need(r, F32, "grad_norm_clip(range)")
+    arr = (_lib.F32Range * max(1, len(ranges)))()
+    for i, r in enumerate(ranges):
+        arr[i].ptr, arr[i].n = r.data_ptr(), r.numel()
+    nparts = grad_norm_partials(ranges)
+    ws = workspace(4 * max(1, nparts), out_norm.device, tag="grad_norm")
+    check(lib.ur_grad_norm_clip(arr, len(ranges), ws.data_ptr(), nparts, grad_scale, max_norm, out_norm.data_ptr(), out_coef.data_ptr(),
+                                _stream()), "ur_grad_norm_clip")
 
 
 # ---- Qwen3-side ops ------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Drop-in for the model/loss part of ``training/train_item_individual_token_joint.py``:
 ``MultiModalQwenEmbedding`` (:88-212), ``InfoNCELoss`` (:326-352), MRR (:392-419) and
-``MultiModalTrainer.compute_loss`` (:482-498), all on the HIP path.
+``MultiModalTrainer.compute_loss`` (:482-498), all on the HIP path; ``JointTrainer`` is the optimisation step HF Trainer runs
+around that loss with the reference's ``TrainingArguments`` (:755-773): gradient-norm clipping, AdamW, the warm-up schedule.
 
 Differences that are deliberate and documented:
   * no network here: the Qwen3 backbone is built from a ``Qwen3Config`` (random init or weights the
@@ -11,7 +12,9 @@ Differences that are deliberate and documented:
   * the python triple loop with one host sync per (item, query, sample) (:160-171) is one kernel.
 """
 import json
+import math
 import os
+import re
 
 import torch
 import torch.nn as nn
@@ -193,3 +196,161 @@ class MultiModalTrainer:
         loss = self.infonce_loss(user_embeddings, inputs["positive_item_embeddings"], inputs["negative_item_embeddings"],
                                  inputs.get("negative_masks", None))
         return (loss, user_embeddings) if return_outputs else loss
+
+
+# ---- the reference's optimisation step (HF Trainer with TrainingArguments, :755-773) -------------------------------------------------
+# Trainer.get_decay_parameter_names: every parameter outside nn.LayerNorm modules whose dotted name (lower case) matches none of these
+_NO_DECAY_PATTERNS = [re.compile(p) for p in (r"bias", r"layernorm", r"rmsnorm", r"(?:^|\.)norm(?:$|\.)", r"_norm(?:$|\.)")]
+
+
+def decay_parameter_names(module):
+    """Names of the parameters HF Trainer applies weight decay to (transformers' get_parameter_names(model, [nn.LayerNorm],
+    patterns) rule, re-stated so the product path does not import transformers)."""
+    out = []
+    for name, child in module.named_children():
+        out += [f"{name}.{n}" for n in decay_parameter_names(child)
+                if not isinstance(child, nn.LayerNorm) and not any(p.search(f"{name}.{n}".lower()) for p in _NO_DECAY_PATTERNS)]
+    out += [k for k in module._parameters if not any(p.search(k.lower()) for p in _NO_DECAY_PATTERNS)]
+    return out
+
+
+def no_decay_pack_names(model, packs):
+    """Pack tensor names HF would step without weight decay (bias / LayerNorm / norm tensors), matched by parameter identity."""
+    decay = set(decay_parameter_names(model))
+    decay_ids = {id(p) for n, p in model.named_parameters() if n in decay}
+    out, seen = set(), {}
+    for pack in packs:
+        for n in pack.names:
+            exempt = id(pack.params[n]) not in decay_ids
+            if seen.setdefault(n, exempt) != exempt:
+                raise ValueError(f"{n}: one pack name with two weight-decay rules (FusedAdamW.no_decay is keyed on names)")
+            if exempt:
+                out.add(n)
+    return out
+
+
+class TrainingConfig:
+    """What JointTrainer takes from a transformers.TrainingArguments (or any object with its attribute names)."""
+
+    def __init__(self, args, num_training_steps=None):
+        g = lambda name, dflt: dflt if getattr(args, name, None) is None else getattr(args, name)
+        gas = int(g("gradient_accumulation_steps", 1))
+        if gas != 1:
+            raise ValueError(f"JointTrainer: gradient_accumulation_steps={gas} is not supported (one backward per optimizer step)")
+        optim = str(getattr(g("optim", "adamw_torch"), "value", g("optim", "adamw_torch")))
+        if not optim.startswith("adamw"):
+            raise ValueError(f"JointTrainer: optim={optim!r}; the fused step is AdamW (torch.optim.AdamW semantics)")
+        self.learning_rate = float(g("learning_rate", 5e-5))
+        self.betas = (float(g("adam_beta1", 0.9)), float(g("adam_beta2", 0.999)))
+        self.eps = float(g("adam_epsilon", 1e-8))
+        self.weight_decay = float(g("weight_decay", 0.0))
+        mgn = getattr(args, "max_grad_norm", 1.0)
+        self.max_grad_norm = float(mgn) if mgn is not None and mgn > 0 else None      # HF: None or <= 0 turns clipping off
+        self.lr_scheduler_type = str(getattr(g("lr_scheduler_type", "linear"), "value", g("lr_scheduler_type", "linear")))
+        max_steps = g("max_steps", -1)
+        self.num_training_steps = int(max_steps) if max_steps > 0 else (None if num_training_steps is None else int(num_training_steps))
+        ws = g("warmup_steps", 0)
+        if hasattr(args, "get_warmup_steps") and (self.num_training_steps is not None or ws >= 1 or ws == 0):
+            self.warmup_steps = int(args.get_warmup_steps(self.num_training_steps if self.num_training_steps is not None else 0))
+        elif ws >= 1 or ws == 0:
+            self.warmup_steps = int(ws)
+        else:
+            raise ValueError("JointTrainer: a fractional warmup_steps needs max_steps or num_training_steps")
+        ls = g("logging_steps", 500)
+        if 0 < ls < 1:                  # HF: a ratio of the total steps
+            if self.num_training_steps is None:
+                raise ValueError("JointTrainer: a fractional logging_steps needs max_steps or num_training_steps")
+            ls = math.ceil(self.num_training_steps * ls)
+        self.logging_steps = int(ls)
+
+
+class JointTrainerState:
+    def __init__(self):
+        self.global_step = 0
+        self.log_history = []
+
+
+class JointTrainer:
+    """The step HF Trainer runs for the reference's joint model (:755-773) after ``compute_loss``, on the HIP path and nothing more
+    (no dataloader, callbacks, evaluation loop or checkpoint directory -- DESIGN §8 keeps those with the caller):
+    zero_grad -> MultiModalTrainer.compute_loss -> backward -> (bucket all-reduce waits) -> global gradient-norm clip + AdamW in
+    one deterministic norm launch and the AdamW launches reading its coefficient on the device -> scheduler step.
+    Under torch.distributed the gradient buckets are wired as bench.py wires them and 1/world is folded into the gradient scale:
+    the norm is the norm of the averaged gradient (DDP + clip_grad_norm_), the same on every rank.  ``state.log_history`` gets
+    {step, loss, grad_norm, learning_rate} every ``logging_steps`` -- the only host read (rank-local loss)."""
+
+    def __init__(self, model, args, num_training_steps=None, temperature: float = 0.07):
+        from . import dp
+        from .optim import FusedAdamW, get_scheduler
+        self.model, self.args = model, args
+        self.config = cfg = TrainingConfig(args, num_training_steps)
+        self.loss_fn = MultiModalTrainer(temperature)
+        dev = model.base_model.embed_tokens.weight.device
+        qf, qw, uq = model.qformer_model, model.base_model, model.user_qformer
+        self.qpack = None if qf is None else qf._ensure_pack(dev)
+        self.lpack = qw._ensure_pack(dev)
+        self.upack = None if uq is None else uq._ensure_pack(dev)
+        self.packs = [p for p in (self.qpack, self.lpack, self.upack) if p is not None]
+        self.no_decay = no_decay_pack_names(model, self.packs)
+        self.optimizer = FusedAdamW(self.packs, lr=cfg.learning_rate, betas=cfg.betas, eps=cfg.eps, weight_decay=cfg.weight_decay,
+                                    max_grad_norm=cfg.max_grad_norm, no_decay=self.no_decay if cfg.weight_decay > 0 else ())
+        self.lr_scheduler = get_scheduler(cfg.lr_scheduler_type, self.optimizer, cfg.warmup_steps, cfg.num_training_steps)
+        self.state = JointTrainerState()
+        self._tr_loss, self._since_log = None, 0
+        # data parallel: the buckets and hooks of bench.py's joint step (LoRA: groups of 7 layers; Q-Former: one bucket per layer)
+        self.grad_scale, self.buckets, self.tail_buckets = 1.0, [], []
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
+            dp.set_dp_rank(rank, model)
+            self.grad_scale = 1.0 / world
+            if self.lpack is not None:
+                l_pre = [f"layers.{i}." for i in range(qw.config.num_hidden_layers)]
+                lbk = dp.GradBuckets(self.lpack.grad, dp.layer_boundaries(self.lpack, l_pre, 7))
+                qw.grad_ready_hook = dp.bucket_hook(self.lpack, lbk, l_pre, 7)
+                self.buckets.append(lbk)
+            if self.qpack is not None:
+                q_pre = [f"qformer.encoder.layer.{i}." for i in range(qf.qformer.config.num_hidden_layers)]
+                qbk = dp.GradBuckets(self.qpack.grad, dp.layer_boundaries(self.qpack, q_pre, 1))
+                qf.qformer.grad_ready_hook = dp.bucket_hook(self.qpack, qbk, q_pre, 1)
+                self.buckets.append(qbk)
+            if self.upack is not None:
+                self.tail_buckets.append(dp.GradBuckets(self.upack.grad, [0, self.upack.numel]))
+
+    def compute_loss(self, model, inputs, return_outputs=False, **kwargs):
+        return self.loss_fn.compute_loss(model, inputs, return_outputs=return_outputs, **kwargs)
+
+    def training_step(self, inputs):
+        """One optimizer step on `inputs` (the batch dict of the reference's collator); returns the loss as a device tensor."""
+        opt = self.optimizer
+        self.model.train()
+        opt.zero_grad()
+        loss = self.compute_loss(self.model, inputs)
+        loss.backward()
+        for bk in self.tail_buckets:
+            bk.ready_all()
+        for bk in self.tail_buckets + self.buckets:
+            bk.wait()
+        lr = opt.lr                       # the scheduled rate of this step (HF logs it before the scheduler moves on)
+        opt.step(grad_scale=self.grad_scale)
+        self.lr_scheduler.step()
+        self.state.global_step += 1
+        loss = loss.detach()
+        self._tr_loss = loss.clone() if self._tr_loss is None else self._tr_loss + loss
+        self._since_log += 1
+        ls = self.config.logging_steps
+        if ls > 0 and self.state.global_step % ls == 0:
+            self._log(lr)
+        return loss
+
+    def _log(self, lr):
+        vals = [self._tr_loss.float()]
+        norm = self.optimizer.last_grad_norm
+        if norm is not None:
+            vals.append(norm)
+        host = torch.stack(vals).tolist()
+        rec = {"step": self.state.global_step, "loss": host[0] / self._since_log}
+        if norm is not None:
+            rec["grad_norm"] = host[1]
+        rec["learning_rate"] = lr
+        self.state.log_history.append(rec)
+        self._tr_loss, self._since_log = None, 0

@@ -166,6 +166,21 @@ class ParamPack:
             cnt *= d
         return lo, lo + (cnt + ALIGN - 1) // ALIGN * ALIGN
 
+    def live_spans(self):
+        """Maximal contiguous [lo, hi) extents of the live tensors (exact sizes, padding excluded; tensors whose sizes are multiples of
+        ALIGN join into one span): the elements a global gradient norm covers -- what torch sees through param.grad."""
+        spans = []
+        for n in self.names:
+            if n not in self.live:
+                continue
+            lo = self.offsets[n]
+            hi = lo + self.params[n].numel()
+            if spans and spans[-1][1] == lo:
+                spans[-1][1] = hi
+            else:
+                spans.append([lo, hi])
+        return [(lo, hi) for lo, hi in spans]
+
     def live_ranges(self, key=None):
         """Maximal contiguous [lo, hi) runs of live tensors (in pack order); `key(name)` splits runs whose tensors must
         not share a launch (different optimizer step counts)."""
