@@ -326,7 +326,8 @@ int ur_attn_dropout_keep(uint64_t seed, float p, uint64_t row0, int64_t nrows, i
  * cos/sin tables are [S][head_dim/2] f32 (ur_rope_table).  qkv_raw [M, (nq+2nkv)*hd] bf16 is the
  * fused projection output (q heads | k heads | v heads); token m has position m % S.
  * fwd: q_out [M,nq*hd], k_out [M,nkv*hd] bf16.  bwd: dqkv_raw q and k sections are written (the v
- * section is written by ur_attn_bwd). */
+ * section is written by ur_attn_bwd).  nq == 0 runs the k heads alone: q_out / dq_out are then never
+ * touched and may be NULL (q_norm_w must still be a valid pointer). */
 int ur_rope_table(float* cos_out, float* sin_out, int32_t S, int32_t head_dim, float theta, void* stream);
 int ur_qknorm_rope_fwd(const void* qkv_raw, int64_t ldraw, const float* q_norm_w, const float* k_norm_w,
                        const float* cos_tab, const float* sin_tab, void* q_out, void* k_out, int64_t M, int32_t S,

@@ -1,0 +1,352 @@
+"""Float64 restatements of the head, RoPE, pool and data primitives of include/unirec_hip.h, and the element-wise criteria the
+GPU tests hold the kernels to (tests/test_gpu_head_primitives.py).  Plain torch on the CPU: no fixtures, no device code.
+
+Every reference is written from the formula in the header comment of its entry point and is itself checked against an
+independent implementation in tests/test_ref64.py.  All functions take / return CPU tensors; inputs of any float dtype are
+promoted to float64 first (``dtype=torch.float32`` re-evaluates the SAME formula in float32: the yardstick of assert_f32_close).
+"""
+import math
+
+import torch
+
+F64 = torch.float64
+BF16_MAX = float(torch.finfo(torch.bfloat16).max)
+_BF16_MIN_NORMAL_EXP = -126
+
+
+# ---- criteria --------------------------------------------------------------------------------------------------------------
+def bf16_ulp(ref64):
+    """2 ** (floor(log2 |ref|) - 7): the spacing of bfloat16 (8 significant bits) at |ref|, floored at the smallest normal."""
+    a = torch.as_tensor(ref64, dtype=F64).abs()
+    _, e = torch.frexp(a)                                        # a = m * 2^e, m in [0.5, 1): floor(log2 a) = e - 1
+    e = torch.where(a == 0, torch.full_like(e, _BF16_MIN_NORMAL_EXP), e - 1).clamp_min(_BF16_MIN_NORMAL_EXP)
+    return torch.ldexp(torch.ones_like(a), e - 7)
+
+
+def f32_ulp(x):
+    """Spacing of float32 at |x| (floored at the smallest normal)."""
+    a = torch.as_tensor(x, dtype=F64).abs()
+    _, e = torch.frexp(a)
+    e = torch.where(a == 0, torch.full_like(e, -126), e - 1).clamp_min(-126)
+    return torch.ldexp(torch.ones_like(a), e - 23)
+
+
+def _cpu64(t):
+    return torch.as_tensor(t).detach().to("cpu").to(F64)
+
+
+def assert_within_ulps(got, ref64, ulps, floor=0.0, what=""):
+    """EVERY element: |got - ref| <= ulps * bf16_ulp(ref) + floor (floor broadcasts against ref: a per-row scale), everything finite.
+    Returns the worst |err| / bound (for the lab-note table)."""
+    g, r = _cpu64(got), _cpu64(ref64)
+    assert g.shape == r.shape, f"{what}: shape {tuple(g.shape)} vs reference {tuple(r.shape)}"
+    assert torch.isfinite(r).all(), f"{what}: the reference itself is not finite"
+    if g.numel() == 0:
+        return 0.0
+    bad = ~torch.isfinite(g)
+    if bad.any():
+        i = tuple(int(v) for v in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} non-finite outputs, first at {i}: got {g[i].item()}, reference {r[i].item()}")
+    fl = torch.as_tensor(floor, dtype=F64)
+    ulp = bf16_ulp(r)
+    err = (g - r).abs()
+    bound = (ulps * ulp + fl).expand_as(err)
+    off = err > bound
+    if off.any():
+        ratio = torch.where(off, err / ulp, torch.zeros_like(err))
+        flat = int(ratio.argmax())
+        i = tuple(int(v) for v in torch.unravel_index(torch.tensor(flat), err.shape))
+        raise AssertionError(f"{what}: {int(off.sum())} of {err.numel()} elements exceed {ulps} bf16 ulp + floor; worst at index {i}: "
+                             f"got {g[i].item()!r}, reference {r[i].item()!r}, error {err[i].item():.3e} = {ratio[i].item():.2f} ulp "
+                             f"(allowed {bound[i].item():.3e})")
+    return float((err / bound.clamp_min(1e-300)).max())
+
+
+def assert_f32_close(got, ref64, ref32, scale=None, what=""):
+    """f32 outputs.  ref32 is the SAME reference formula evaluated in float32 torch on the CPU; e32 = per-row max |ref32 - ref64|
+    is what plain f32 arithmetic costs on this input.  Per row (last axis; a 0-d / 1-element tensor is one row):
+        max |got - ref64| <= 8 * e32 + 2 ** -20 * scale,      scale = row max |ref64| unless given (|loss| + 1 for scalars).
+    Returns the worst row's error / bound."""
+    g, r, r32 = _cpu64(got), _cpu64(ref64), _cpu64(ref32)
+    assert g.shape == r.shape == r32.shape, f"{what}: shapes {tuple(g.shape)} / {tuple(r.shape)} / {tuple(r32.shape)}"
+    assert torch.isfinite(r).all(), f"{what}: the reference itself is not finite"
+    if g.numel() == 0:
+        return 0.0
+    bad = ~torch.isfinite(g)
+    if bad.any():
+        i = tuple(int(v) for v in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} non-finite outputs, first at {i}: got {g[i].item()}, reference {r[i].item()}")
+    if g.dim() == 0:
+        g, r, r32 = g.reshape(1), r.reshape(1), r32.reshape(1)
+    e32 = (r32 - r).abs().amax(dim=-1)
+    sc = r.abs().amax(dim=-1) if scale is None else torch.as_tensor(scale, dtype=F64).expand_as(e32)
+    bound = 8.0 * e32 + 2.0 ** -20 * sc
+    err = (g - r).abs()
+    rowerr = err.amax(dim=-1)
+    off = rowerr > bound
+    if off.any():
+        excess = torch.where(off, rowerr - bound, torch.zeros_like(rowerr))
+        row = tuple(int(v) for v in torch.unravel_index(excess.argmax(), rowerr.shape))
+        col = int(err[row].argmax())
+        i = row + (col,)
+        raise AssertionError(f"{what}: {int(off.sum())} of {rowerr.numel()} rows exceed 8 * e32 + 2^-20 * scale; worst at index {i}: "
+                             f"got {g[i].item()!r}, reference {r[i].item()!r}, error {err[i].item():.3e}, allowed {bound[row].item():.3e} "
+                             f"(e32 {e32[row].item():.3e}, scale {sc[row].item():.3e})")
+    ok = bound > 0
+    return float((rowerr[ok] / bound[ok]).max()) if ok.any() else 0.0
+
+
+def rowmax(ref64, dim=-1):
+    return _cpu64(ref64).abs().amax(dim=dim, keepdim=True)
+
+
+# ---- Qwen3 q/k RMSNorm + RoPE (modeling_qwen3.py:59-64, 107-170) -----------------------------------------------------------
+def rope_table(S, head_dim, theta, dtype=F64):
+    """cos / sin [S, head_dim / 2]: inv_freq_i = theta ** (-2 i / head_dim), angle = pos * inv_freq_i."""
+    i = torch.arange(head_dim // 2, dtype=dtype)
+    inv = torch.as_tensor(theta, dtype=dtype) ** (-(2.0 * i) / head_dim)
+    ang = torch.arange(S, dtype=dtype)[:, None] * inv[None, :]
+    return torch.cos(ang), torch.sin(ang)
+
+
+def _rotate_half(x):
+    h = x.shape[-1] // 2
+    return torch.cat([-x[..., h:], x[..., :h]], dim=-1)
+
+
+def _unrotate(y, c, s):
+    """R^T y of the rotation R x = x c + rotate_half(x) s (c, s duplicated over both halves)."""
+    return y * c - _rotate_half(y) * s
+
+
+def _cs_rows(cos_tab, sin_tab, M, S, dtype):
+    pos = torch.arange(M) % S
+    c = cos_tab.to(dtype)[pos]
+    s = sin_tab.to(dtype)[pos]
+    return torch.cat([c, c], -1)[:, None, :], torch.cat([s, s], -1)[:, None, :]
+
+
+def _head_weights(qw, kw, nq, nkv, dtype):
+    return torch.cat([qw.to(dtype)[None].expand(nq, -1), kw.to(dtype)[None].expand(nkv, -1)], 0)      # [nq + nkv, hd]
+
+
+def qknorm_rope_fwd(raw, qw, kw, cos_tab, sin_tab, S, nq, nkv, hd, eps, dtype=F64):
+    """raw [M, >= (nq + nkv) * hd] (q heads | k heads | ...), token m at position m % S, the TABLES AS GIVEN (the kernel's f32 ones, so
+    table error is not rope error): out[m, h] = RoPE(w_h * x / sqrt(mean(x^2) + eps)).  Returns [M, nq + nkv, hd]."""
+    M = raw.shape[0]
+    x = raw[:, :(nq + nkv) * hd].to(dtype).reshape(M, nq + nkv, hd)
+    w = _head_weights(qw, kw, nq, nkv, dtype)
+    xn = x * torch.rsqrt((x * x).mean(-1, keepdim=True) + eps) * w
+    c, s = _cs_rows(cos_tab, sin_tab, M, S, dtype)
+    return xn * c + _rotate_half(xn) * s
+
+
+def qknorm_rope_rstd(raw, nq, nkv, hd, eps):
+    M = raw.shape[0]
+    x = raw[:, :(nq + nkv) * hd].to(F64).reshape(M, nq + nkv, hd)
+    return torch.rsqrt((x * x).mean(-1) + eps)                    # [M, nq + nkv]
+
+
+def qknorm_rope_bwd(dout, raw, qw, kw, cos_tab, sin_tab, S, nq, nkv, hd, eps):
+    """Gradient of the raw projection: torch.autograd through the float64 forward.  dout [M, nq + nkv, hd]; returns the same shape."""
+    x = raw[:, :(nq + nkv) * hd].to(F64).clone().requires_grad_(True)
+    out = qknorm_rope_fwd(x, qw, kw, cos_tab, sin_tab, S, nq, nkv, hd, eps)
+    (g,) = torch.autograd.grad(out, x, dout.to(F64))
+    return g.reshape(out.shape)
+
+
+def qknorm_rope_bwd_from_roped(dout, roped, rstd, qw, kw, cos_tab, sin_tab, S, nq, nkv, hd):
+    """The same gradient written out, from what the fused forward keeps: the ROPED output o and 1 / rms.
+        xn = R^T o,  x^ = xn / w,  g = (R^T dout) * w,  dx = rstd * (g - x^ * mean(g * x^)).
+    dout, roped [M, nq + nkv, hd]; rstd [M, nq + nkv]."""
+    M = dout.shape[0]
+    w = _head_weights(qw, kw, nq, nkv, F64)
+    c, s = _cs_rows(cos_tab, sin_tab, M, S, F64)
+    xh = _unrotate(roped.to(F64), c, s) / w
+    g = _unrotate(dout.to(F64), c, s) * w
+    t = (g * xh).mean(-1, keepdim=True)
+    return rstd.to(F64)[..., None] * (g - xh * t)
+
+
+# ---- user-sequence assembly (models/user_sequence_encoder.py:16-33, 128-142) -----------------------------------------------
+def sinusoidal_pe(length, H, dtype=F64):
+    """PE over the FLAT index: even d -> sin(pos * w_d), odd d -> cos(pos * w_{d-1}), w_d = exp(-d * ln(1e4) / H)."""
+    pos = torch.arange(length, dtype=dtype)[:, None]
+    d = torch.arange(0, H, 2, dtype=dtype)
+    w = torch.exp(d * (-math.log(10000.0) / H))
+    pe = torch.zeros(length, H, dtype=dtype)
+    pe[:, 0::2] = torch.sin(pos * w)
+    pe[:, 1::2] = torch.cos(pos * w)
+    return pe
+
+
+def user_sequence_assemble(tokens, ctx, lengths, keep=None, p=0.0):
+    """tokens [B, L, Qi, H], ctx [B, L, H], lengths [B]; keep [B, L*Qi, H] (0 / 1) or None.
+    out[b, l*Qi + j] = (tokens + ctx + PE[l*Qi + j]) * keep / (1 - p) for l < len[b], else 0; mask = l < len[b]."""
+    B, L, Qi, H = tokens.shape
+    x = (tokens.to(F64) + ctx.to(F64)[:, :, None, :]).reshape(B, L * Qi, H) + sinusoidal_pe(L * Qi, H)[None]
+    valid = (torch.arange(L)[None, :] < lengths.to(torch.int64)[:, None]).repeat_interleave(Qi, dim=1)       # [B, L*Qi]
+    if keep is not None:
+        x = x * keep.to(F64).reshape(B, L * Qi, H) / (1.0 - p)
+    return x * valid[..., None].to(F64), valid.to(F64)
+
+
+# ---- ranking head (train_item_individual_token_joint.py:331-352, 392-419) --------------------------------------------------
+def _normalize(x, eps=1e-12):
+    return x / x.norm(dim=-1, keepdim=True).clamp_min(eps)
+
+
+def cosine_scores(user, pos, neg, dtype=F64):
+    """scores [B, 1 + N]: column 0 = cos(user, pos), 1 + n = cos(user, neg_n); F.normalize eps 1e-12."""
+    u = _normalize(user.to(dtype))
+    cand = torch.cat([pos.to(dtype)[:, None, :], neg.to(dtype)], dim=1)
+    return torch.einsum("bd,bnd->bn", u, _normalize(cand))
+
+
+def catalog_scores(user, catalog, dtype=F64):
+    return _normalize(user.to(dtype)) @ _normalize(catalog.to(dtype)).t()
+
+
+def infonce(user, pos, neg, neg_mask, tau, grad_scale=1.0, dtype=F64):
+    """loss = mean_b(-s_b0 / tau + logsumexp over {0} U valid negatives of s / tau); d_user = grad_scale * dloss / duser (autograd)."""
+    u = user.to(dtype).clone().requires_grad_(True)
+    z = cosine_scores(u, pos, neg, dtype) / tau
+    if neg_mask is not None:
+        valid = torch.cat([torch.ones(z.shape[0], 1, dtype=torch.bool), neg_mask.bool()], dim=1)
+        z = z.masked_fill(~valid, float("-inf"))
+    loss = (torch.logsumexp(z, dim=1) - z[:, 0]).mean()
+    (du,) = torch.autograd.grad(loss, u)
+    return loss.detach(), du * grad_scale
+
+
+def mrr_rank(scores, neg_mask=None):
+    """1 + #{valid n : s[1 + n] > s[0]} (the positive wins ties)."""
+    gt = scores[:, 1:] > scores[:, :1]
+    if neg_mask is not None:
+        gt = gt & neg_mask.bool()
+    return 1 + gt.sum(dim=1)
+
+
+def rank_of_index(scores, gt_index):
+    ref = scores.gather(1, gt_index.to(torch.int64)[:, None])
+    return 1 + (scores > ref).sum(dim=1)
+
+
+def topk(scores, K):
+    """Descending top-K, lowest index first among equal scores: K rounds of 'first position of the maximum'."""
+    s = scores.clone().to(F64)
+    B, C = s.shape
+    taken = torch.zeros(B, C, dtype=torch.bool)
+    idx = torch.empty(B, K, dtype=torch.int64)
+    rows = torch.arange(B)
+    for k in range(K):
+        # -inf scores must stay selectable: mask by `taken`, not by value
+        cur = torch.where(taken, torch.full_like(s, float("-inf")), s)
+        best = cur.amax(dim=1, keepdim=True)
+        cand = (cur == best) & ~taken
+        i = torch.where(cand, torch.arange(C)[None, :].expand(B, C), torch.full((B, C), C)).amin(dim=1)
+        idx[:, k] = i
+        taken[rows, i] = True
+    return idx, scores.gather(1, idx)
+
+
+# ---- Q-Former heads / losses (training/item_qformer_training.py:49-56, evaluation/evaluate_item_qformer.py:75-92) ----------
+def recon_stats(rec, x, mask, dtype=F64):
+    """sums3 = (sum mask * (rec - x)^2, sum mask, sum over valid rows of cos(x_row, rec_row)); rec, x [rows, E], mask [rows]."""
+    rec, x, m = rec.to(dtype), x.to(dtype), mask.to(dtype)
+    se = (((rec - x) ** 2).sum(-1) * m).sum()
+    cos = (rec * x).sum(-1) / (x.norm(dim=-1).clamp_min(1e-12) * rec.norm(dim=-1).clamp_min(1e-12))
+    return torch.stack([se, m.sum(), (cos * (m != 0).to(dtype)).sum()])
+
+
+def recon_grad(rec, x, mask, coef, dtype=F64):
+    """d_rec = coef * 2 * mask * (rec - x) / sum(mask)."""
+    rec, x, m = rec.to(dtype), x.to(dtype), mask.to(dtype)
+    return (2.0 * coef / m.sum()) * m[:, None] * (rec - x)
+
+
+def triplet_margin(a, p, n, margin, coef, dtype=F64):
+    """TripletMarginLoss(margin, p=2, eps=1e-6 ADDED TO THE DIFFERENCE, mean); returns (loss, coef * dloss / danchor)."""
+    a = a.to(dtype).clone().requires_grad_(True)
+    dp = ((a - p.to(dtype) + 1e-6) ** 2).sum(-1).sqrt()
+    dn = ((a - n.to(dtype) + 1e-6) ** 2).sum(-1).sqrt()
+    loss = (dp - dn + margin).clamp_min(0.0).mean()
+    (da,) = torch.autograd.grad(loss, a)
+    return loss.detach(), coef * da
+
+
+def mse(a, b, coef, dtype=F64):
+    """nn.MSELoss (mean over all elements); returns (loss, coef * 2 (a - b) / n)."""
+    a, b = a.to(dtype), b.to(dtype)
+    d = a - b
+    return (d * d).mean(), (2.0 * coef / d.numel()) * d
+
+
+# ---- element-wise --------------------------------------------------------------------------------------------------------
+def gelu_grad(u):
+    """d/du [u * Phi(u)] = Phi(u) + u * phi(u), Phi through erfc so the negative tail keeps its relative accuracy."""
+    u = u.to(F64)
+    cdf = 0.5 * torch.special.erfc(-u / math.sqrt(2.0))
+    return cdf + u * torch.exp(-0.5 * u * u) / math.sqrt(2.0 * math.pi)
+
+
+def gelu(u):
+    u = u.to(F64)
+    return u * 0.5 * torch.special.erfc(-u / math.sqrt(2.0))
+
+
+def _sigmoid64(g):
+    # 1 / (1 + exp(-g)) without overflow on either side
+    e = torch.exp(-g.abs())
+    return torch.where(g >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+
+def swiglu_fwd(gate, up):
+    g, u = gate.to(F64), up.to(F64)
+    return g * _sigmoid64(g) * u
+
+
+def swiglu_bwd(dact, gate, up):
+    """(dgate, dup): dgate = dact * up * silu'(gate), silu'(g) = s (1 + g (1 - s)); dup = dact * silu(gate)."""
+    d, g, u = dact.to(F64), gate.to(F64), up.to(F64)
+    s = _sigmoid64(g)
+    one_minus_s = _sigmoid64(-g)
+    return d * u * s * (1.0 + g * one_minus_s), d * g * s
+
+
+# ---- event-context encoders, first layer (models/mwne.py:525-565, 586-607) -------------------------------------------------
+def timestamp_features(ts):
+    """9 features, EVERY STEP IN FLOAT32 in the reference's operation order (the phases are f32-chaotic at real timestamps: a float64
+    evaluation would be a different function).  Returns (features f32 [n, 9], angles f32 [n, 9]) -- angle_f is the argument of the
+    sin / cos behind feature f (0 for the secular feature), which the tolerance of ur_context_mlp1 is stated in."""
+    f32 = torch.float32
+    x = ts.to(f32).reshape(-1)
+    year, day, two_pi = torch.tensor(31557600.0, dtype=f32), torch.tensor(86400.0, dtype=f32), torch.tensor(2.0 * math.pi, dtype=f32)
+    a_day = two_pi * (torch.remainder(x, day) / day)
+    a_week = two_pi * (((x / day) + 4.0) / 7.0)
+    year_phase = torch.remainder(x, year) / year
+    a_year = two_pi * year_phase
+    a_month = two_pi * (year_phase * 12.0)
+    feats = [x / year]
+    angles = [torch.zeros_like(x)]
+    for a in (a_day, a_week, a_year, a_month):
+        feats += [torch.sin(a), torch.cos(a)]
+        angles += [a, a]
+    return torch.stack(feats, -1), torch.stack(angles, -1)
+
+
+def geo_features(coords):
+    """(lat, lon) degrees [n, 2] -> unit-sphere (x, y, z), float32 as the reference; angle slack per feature = |lat| + |lon| for x, y
+    (|d(cos a cos b)| <= |da| + |db|) and |lat| for z, returned as a pseudo-angle whose f32 ulp bounds the features' legitimate spread."""
+    f32 = torch.float32
+    c = coords.to(f32)
+    d2r = torch.tensor(math.pi / 180.0, dtype=f32)
+    lat, lon = c[:, 0] * d2r, c[:, 1] * d2r
+    feats = torch.stack([torch.cos(lat) * torch.cos(lon), torch.cos(lat) * torch.sin(lon), torch.sin(lat)], -1)
+    both = torch.maximum(lat.abs(), lon.abs()) * 2.0
+    return feats, torch.stack([both, both, lat.abs()], -1)
+
+
+def context_mlp1(feat, W1, b1):
+    """gelu(b1 + W1 feat) in float64 over the given features: [n, H2]."""
+    return gelu(feat.to(F64) @ W1.to(F64).t() + b1.to(F64))

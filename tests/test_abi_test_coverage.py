@@ -1,0 +1,120 @@
+"""CPU: every entry point declared in include/unirec_hip.h is either listed in a COVERS table -- naming the primitive-level test(s)
+that hold it against a reference -- or exempt below with a reason.  A new entry point without such a test fails here."""
+import ast
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+COVERS_MODULES = ("tests/test_gpu_primitives.py", "tests/test_gpu_head_primitives.py")
+
+EXEMPT = {
+    "ur_version": "ABI handshake; asserted at every library load (unirec_amd/_lib.py) and in tests/test_cabi.py",
+    "ur_last_error": "error text; read by every rejected call the GPU tests provoke",
+    "ur_gemm_workspace_bytes": "workspace-size query; a short workspace is rejected by ur_gemm",
+    "ur_gemm_grouped_workspace_bytes": "workspace-size query",
+    "ur_lora_bits_ld": "layout query (bytes per row of a bit plane)",
+    "ur_lora_bits_t_ld": "layout query (words per token group)",
+    "ur_lora_reduce_workspace_bytes": "workspace-size query",
+    "ur_lora_bgrad_workspace_bytes": "workspace-size query",
+    "ur_layernorm_bwd_workspace_bytes": "workspace-size query",
+    "ur_batch_reduce_workspace_bytes": "workspace-size query",
+    "ur_attn_bwd_workspace_floats": "workspace-size query",
+    "ur_attn_bwd_kv_colsum_floats": "workspace-size / capability query (tests/test_gpu_r5_parity.py exercises both answers)",
+    "ur_mean_pool_workspace_bytes": "workspace-size query; one byte less is rejected (test_argument_checks_reject_without_launching)",
+    "ur_infonce_workspace_bytes": "workspace-size query; one byte less is rejected (test_argument_checks_reject_without_launching)",
+    "ur_heads_workspace_bytes": "workspace-size query",
+    "ur_gemm_persistent_mode": "mode switch; both settings are compared bit for bit in tests/test_gpu_gemm_persistent.py",
+    "ur_attn_mode": "mode switch; every setting is compared in tests/test_gpu_switches.py",
+    "ur_comm_unique_id": "communicator plumbing, no arithmetic; tests/test_gpu_comm.py",
+    "ur_comm_init": "communicator plumbing, no arithmetic; tests/test_gpu_comm.py",
+    "ur_comm_allreduce_async": "RCCL's sum, not a kernel of this library; tests/test_gpu_comm.py",
+    "ur_comm_ticket": "communicator plumbing; tests/test_gpu_comm.py",
+    "ur_comm_wait_ticket": "communicator plumbing; tests/test_gpu_comm.py",
+    "ur_comm_wait": "communicator plumbing; tests/test_gpu_comm.py",
+    "ur_comm_destroy": "communicator plumbing; tests/test_gpu_comm.py",
+}
+
+
+def _declared_entry_points():
+    with open(os.path.join(ROOT, "include", "unirec_hip.h")) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    names = []
+    for n in re.findall(r"\b(ur_[a-z0-9_]+)\s*\(", text):
+        if n not in names:
+            names.append(n)
+    return names
+
+
+def _module(path):
+    with open(os.path.join(ROOT, path)) as f:
+        return ast.parse(f.read(), filename=path)
+
+
+def _covers_and_tests(path):
+    """(the literal COVERS dict at the top level of the module, the names of its test functions)"""
+    tree = _module(path)
+    covers = None
+    for node in tree.body:
+        if isinstance(node, ast.Assign) and any(isinstance(t, ast.Name) and t.id == "COVERS" for t in node.targets):
+            covers = ast.literal_eval(node.value)
+    tests = {n.name for n in tree.body if isinstance(n, ast.FunctionDef) and n.name.startswith("test_")}
+    return covers, tests
+
+
+def _problems(declared, tables, tests_of):
+    """tables: {module path: COVERS dict}; tests_of(path) -> set of test function names"""
+    out = []
+    listed = {}
+    for path, covers in tables.items():
+        for entry, names in covers.items():
+            listed.setdefault(entry, []).append(path)
+            if entry not in declared:
+                out.append(f"{path}: COVERS lists {entry}, which include/unirec_hip.h does not declare")
+            if not names:
+                out.append(f"{path}: COVERS[{entry!r}] names no test")
+            for name in names:
+                mod, _, fn = name.rpartition("::")
+                mod = mod or path
+                if not os.path.exists(os.path.join(ROOT, mod)) or fn not in tests_of(mod):
+                    out.append(f"{path}: COVERS[{entry!r}] names {name}, which does not exist")
+    for entry in declared:
+        if entry in EXEMPT and entry in listed:
+            out.append(f"{entry} is both exempt and listed in {listed[entry]}")
+        if entry not in EXEMPT and entry not in listed:
+            out.append(f"{entry} has no primitive-level test: add one and list it in a COVERS table, or exempt it with a reason")
+    for entry in EXEMPT:
+        if entry not in declared:
+            out.append(f"EXEMPT lists {entry}, which include/unirec_hip.h does not declare")
+    return out
+
+
+def _tables():
+    tables = {}
+    for path in COVERS_MODULES:
+        covers, _ = _covers_and_tests(path)
+        assert isinstance(covers, dict), f"{path} has no top-level COVERS dict"
+        tables[path] = covers
+    return tables
+
+
+def test_every_entry_point_has_a_primitive_level_test_or_a_reason():
+    declared = _declared_entry_points()
+    assert len(declared) >= 81 and "ur_gemm" in declared and "ur_comm_destroy" in declared
+    assert all(reason.strip() for reason in EXEMPT.values())
+    problems = _problems(declared, _tables(), lambda p: _covers_and_tests(p)[1])
+    assert not problems, "\n".join(problems)
+
+
+def test_the_check_bites():
+    """deleting an entry from a COVERS table, naming a test that does not exist, or declaring a new entry point is reported"""
+    declared = _declared_entry_points()
+    tests_of = lambda p: _covers_and_tests(p)[1]      # noqa: E731
+    tables = _tables()
+    for path in COVERS_MODULES:
+        for entry in tables[path]:
+            cut = {p: {k: v for k, v in c.items() if not (p == path and k == entry)} for p, c in tables.items()}
+            assert any(entry in msg for msg in _problems(declared, cut, tests_of)), f"deleting {entry} from {path} went unnoticed"
+    renamed = {p: dict(c) for p, c in tables.items()}
+    renamed[COVERS_MODULES[1]]["ur_topk"] = ["test_that_was_renamed_away"]
+    assert any("test_that_was_renamed_away" in msg for msg in _problems(declared, renamed, tests_of))
+    assert any("ur_brand_new_kernel" in msg for msg in _problems(declared + ["ur_brand_new_kernel"], tables, tests_of))

@@ -11,6 +11,45 @@ from unirec_amd import hip  # noqa: E402
 
 DEV = "cuda"
 
+# entry point of include/unirec_hip.h -> the primitive-level tests that hold it against a reference: a function of this module, or
+# "tests/<file>.py::<function>" where the primitive's own module does (tests/test_abi_test_coverage.py checks that every name exists;
+# the head, RoPE, pool and data primitives are listed in tests/test_gpu_head_primitives.py)
+COVERS = {
+    "ur_gemm": ["test_gemm_exact_integer", "test_gemm_big_tile_k_strided_exact", "test_gemm_epilogues", "test_gemm_second_pair_lora",
+                "test_gemm_splitk_tn", "test_gemm_swiglu_backward_epilogue", "test_gemm_swiglu_forward_epilogue"],
+    "ur_gemm_grouped": ["tests/test_gpu_gemm_grouped.py::test_one_item_qformer_layer", "tests/test_gpu_gemm_grouped.py::test_small_and_ragged_products_take_the_small_tile"],
+    "ur_gemm_swiglu_paired_supported": ["tests/test_gpu_gemm_persistent.py::test_gate_up_projection_with_paired_swiglu_epilogue"],
+    "ur_gemm_qkrope_supported": ["tests/test_gpu_gemm_persistent.py::test_qkv_projection_with_qknorm_rope_epilogue"],
+    "ur_qkrope_perm": ["tests/test_gpu_gemm_persistent.py::test_qkv_projection_with_qknorm_rope_epilogue"],
+    "ur_lora_bits_transpose": ["test_lora_reduce_ring_kernel"],
+    "ur_lora_dropout_bits": ["test_lora_kernels_with_dropout_bits", "test_lora_dropout_word_popcounts_and_triples_follow_the_binomial"],
+    "ur_lora_project": ["test_lora_kernels_with_dropout_bits", "test_lora_kernels_on_column_ranges"],
+    "ur_lora_reduce": ["test_lora_kernels_with_dropout_bits", "test_lora_reduce_ring_kernel", "test_lora_reduce_ring_kernel_on_column_ranges"],
+    "ur_lora_bgrad": ["test_lora_bgrad_ring_kernel"],
+    "ur_swiglu_lora_fwd": ["test_fused_swiglu_lora_projection_matches_the_two_kernels"],
+    "ur_rmsnorm_lora_fwd": ["test_fused_rmsnorm_lora_projection_matches_the_two_kernels"],
+    "ur_layernorm_fwd": ["test_layernorm_fwd_bwd", "test_layernorm_broadcast_rows_and_dropout"],
+    "ur_layernorm_bwd": ["test_layernorm_fwd_bwd", "test_layernorm_broadcast_rows_and_dropout"],
+    "ur_layernorm_bwd_reduce": ["test_layernorm_bwd_deferred_reduce"],
+    "ur_batch_reduce": ["test_batch_reduce_and_colsum"],
+    "ur_rmsnorm_fwd": ["test_rmsnorm_fwd_bwd"],
+    "ur_rmsnorm_bwd": ["test_rmsnorm_fwd_bwd"],
+    "ur_attn_fwd": ["tests/test_gpu_attention.py::test_qformer_attention", "tests/test_gpu_attention.py::test_qwen3_causal_gqa"],
+    "ur_attn_bwd": ["tests/test_gpu_attention.py::test_qformer_attention", "tests/test_gpu_attention.py::test_qwen3_causal_gqa"],
+    "ur_attn_dropout_keep": ["tests/test_gpu_r5_parity.py::test_attention_dropout_keep_export_matches_the_numpy_generator"],
+    "ur_gather_rows": ["tests/test_gpu_data_path.py::test_gather_rows_all_kinds"],
+    "ur_field_projection_fwd": ["test_field_projection_fwd_bwd_match_torch"],
+    "ur_field_projection_bwd": ["test_field_projection_fwd_bwd_match_torch"],
+    "ur_cast_f32_to_bf16": ["test_elementwise_and_adamw"],
+    "ur_cast_bf16_to_f32": ["test_elementwise_and_adamw"],
+    "ur_transpose_bf16": ["test_elementwise_and_adamw"],
+    "ur_transpose_bf16_batched": ["test_batched_transpose_matches_per_matrix_transposes"],
+    "ur_add_bf16": ["test_elementwise_and_adamw"],
+    "ur_adamw_step": ["test_elementwise_and_adamw"],
+    "ur_adamw_step_dev": ["tests/test_gpu_grad_clip.py::test_clipped_training_matches_torch"],
+    "ur_grad_norm_clip": ["tests/test_gpu_grad_clip.py::test_norm_matches_float64_and_is_deterministic"],
+}
+
 
 def _ints(shape, lo=-3, hi=4, seed=0):
     g = torch.Generator(device="cpu").manual_seed(seed)
@@ -223,6 +262,33 @@ def test_layernorm_fwd_bwd(M, H):
     assert torch.allclose(dg, gr.grad, rtol=1e-2, atol=2e-2 * scale)
     assert torch.allclose(db, br.grad, rtol=1e-2, atol=2e-2 * scale)
     assert torch.allclose(dbias, dz.float().sum(0), rtol=1e-3, atol=1e-3 * scale)
+
+
+@pytest.mark.parametrize("M,H", [(5, 128), (300, 768), (1000, 1024)])
+def test_layernorm_bwd_deferred_reduce(M, H):
+    """dgamma == NULL stops at the per-block partial sums; ur_layernorm_bwd_reduce finishes them: the same three parameter gradients
+    (against float64 torch, tolerances of test_layernorm_fwd_bwd) and the same dz bits as the one-call path"""
+    y, res = _bf(_randn((M, H), 11)), _bf(_randn((M, H), 12))
+    gamma = (1 + 0.1 * _randn((H,), 13)).to(DEV)
+    beta = (0.1 * _randn((H,), 14)).to(DEV)
+    out, z, mean, rstd = hip.layernorm_fwd(y, gamma, beta, 1e-12, residual=res)
+    dout = _bf(_randn((M, H), 15))
+    zf = z.double().requires_grad_(True)
+    gr, br = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+    torch.nn.functional.layer_norm(zf, (H,), gr, br, 1e-12).backward(dout.double())
+    dg, db, dbias = (torch.full((H,), float("nan"), device=DEV) for _ in range(3))
+    dz, dy, finish = hip.layernorm_bwd(dout, z, mean, rstd, gamma, dg, db, dbias, defer_reduce=True)
+    torch.cuda.synchronize()
+    assert torch.isnan(dg).all() and torch.isnan(db).all() and torch.isnan(dbias).all()      # nothing written before the reduction runs
+    finish()
+    dg1, db1, dbias1 = (torch.empty(H, device=DEV) for _ in range(3))
+    dz1, _ = hip.layernorm_bwd(dout, z, mean, rstd, gamma, dg1, db1, dbias1)
+    assert torch.equal(dz.view(torch.int16), dz1.view(torch.int16))
+    scale = math.sqrt(M)
+    assert torch.allclose(dg.double(), gr.grad, rtol=1e-2, atol=2e-2 * scale)
+    assert torch.allclose(db.double(), br.grad, rtol=1e-2, atol=2e-2 * scale)
+    assert torch.allclose(dbias, dz.float().sum(0), rtol=1e-3, atol=1e-3 * scale)
+    assert torch.allclose(dg, dg1, rtol=1e-5, atol=1e-5 * scale) and torch.allclose(db, db1, rtol=1e-5, atol=1e-5 * scale)
 
 
 def test_layernorm_broadcast_rows_and_dropout():

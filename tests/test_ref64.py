@@ -1,0 +1,337 @@
+"""CPU: the float64 references of tests/ref64.py against independent implementations (torch.nn.functional, transformers' Qwen3
+modules, the oracle/ restatements), and the element-wise criterion itself.  The GPU kernels are held against these references in
+tests/test_gpu_head_primitives.py, so they have to be right first."""
+import math
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import ref64
+from oracle import data_ref, qformer_ref, qwen3_ref
+
+F64 = torch.float64
+BF16 = torch.bfloat16
+
+
+def _gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _randn(shape, seed, dtype=F64):
+    return torch.randn(shape, generator=_gen(seed), dtype=dtype)
+
+
+# ---- the criterion -----------------------------------------------------------------------------------------------------------
+def test_bf16_ulp_is_the_spacing_of_bfloat16():
+    bits = torch.arange(0x0080, 0x7F80, dtype=torch.int32).to(torch.int16)           # every positive normal bf16
+    x = bits.view(BF16).to(F64)
+    spacing = x[1:] - x[:-1]
+    assert torch.equal(ref64.bf16_ulp(x[:-1]), spacing)
+    assert torch.equal(ref64.bf16_ulp(-x[:-1]), spacing)
+    # anything inside a binade shares its spacing; zero and subnormals sit on the floor
+    assert ref64.bf16_ulp(torch.tensor(1.9999)) == 2.0 ** -7 and ref64.bf16_ulp(torch.tensor(0.9999)) == 2.0 ** -8
+    assert ref64.bf16_ulp(torch.tensor(0.0)) == 2.0 ** -133 and ref64.bf16_ulp(torch.tensor(1e-40)) == 2.0 ** -133
+    assert ref64.f32_ulp(torch.tensor(1.0)) == 2.0 ** -23 and ref64.f32_ulp(torch.tensor(75.0)) == 2.0 ** -17
+
+
+def _rope_case(M, nq, nkv, hd, S, seed):
+    raw = (3.0 * _randn((M, (nq + 2 * nkv) * hd), seed, torch.float32)).to(BF16)
+    qw = 1.0 + 0.3 * _randn((hd,), seed + 1, torch.float32)
+    kw = 1.0 + 0.3 * _randn((hd,), seed + 2, torch.float32)
+    cos, sin = ref64.rope_table(S, hd, 1e6)
+    return raw, qw, kw, cos.float(), sin.float()
+
+
+@pytest.mark.parametrize("hd", [64, 128])
+def test_criterion_passes_a_float32_evaluation_and_catches_two_ulps(hd):
+    """A float32 torch evaluation rounded once to bf16 is within 1 ulp + 2^-18 * rowmax of float64 everywhere (the floor covers
+    xn * c + rot * s cancelling below its terms); the same data with ONE element moved by 2 ulp fails, at that index."""
+    M, nq, nkv, S = 512, 6, 2, 200
+    raw, qw, kw, cos, sin = _rope_case(M, nq, nkv, hd, S, 10)
+    r64 = ref64.qknorm_rope_fwd(raw, qw, kw, cos, sin, S, nq, nkv, hd, 1e-6)
+    got = ref64.qknorm_rope_fwd(raw, qw, kw, cos, sin, S, nq, nkv, hd, 1e-6, dtype=torch.float32).to(BF16)
+    floor = 2.0 ** -18 * ref64.rowmax(r64)
+    ref64.assert_within_ulps(got, r64, 1, floor, "f32 rope")
+    ref64.assert_within_ulps(got, r64, 0.5, floor, "f32 rope at half an ulp")      # a single correct rounding
+    bad = got.clone().to(F64)
+    i = (37, 3, hd - 5)
+    bad[i] = r64[i] + 2.0 * ref64.bf16_ulp(r64[i]) + 2.0 * floor[i[0], i[1], 0]
+    with pytest.raises(AssertionError) as e:
+        ref64.assert_within_ulps(bad, r64, 1, floor, "poked rope")
+    assert f"index {i}" in str(e.value) and "1 of " in str(e.value)
+    nan = got.clone().to(F64)
+    nan[5, 0, 1] = float("nan")
+    with pytest.raises(AssertionError, match="non-finite"):
+        ref64.assert_within_ulps(nan, r64, 1, floor)
+
+
+def test_criterion_needs_no_floor_for_swiglu():
+    g = (3.0 * _randn((257, 96), 3, torch.float32)).to(BF16)
+    u = (2.0 * _randn((257, 96), 4, torch.float32)).to(BF16)
+    r64 = ref64.swiglu_fwd(g, u)
+    got = (F.silu(g.float()) * u.float()).to(BF16)
+    worst = ref64.assert_within_ulps(got, r64, 1, 0.0, "f32 swiglu")
+    assert worst <= 0.51
+    bad = got.to(F64).clone()
+    bad[100, 7] = r64[100, 7] - 2.0 * ref64.bf16_ulp(r64[100, 7])
+    with pytest.raises(AssertionError, match=r"index \(100, 7\)"):
+        ref64.assert_within_ulps(bad, r64, 1, 0.0)
+
+
+def test_f32_criterion_scales_with_the_float32_evaluation():
+    x = _randn((5, 300), 7)
+    r64 = x.cumsum(-1)
+    r32 = x.float().cumsum(-1)
+    ref64.assert_f32_close(r32, r64, r32, what="itself")
+    bad = r32.clone()
+    bad[3, 17] += 1e-3
+    with pytest.raises(AssertionError, match=r"index \(3, 17\)"):
+        ref64.assert_f32_close(bad, r64, r32)
+    # a zero row allows nothing
+    z = torch.zeros(2, 4, dtype=F64)
+    ref64.assert_f32_close(z.float(), z, z.float())
+    with pytest.raises(AssertionError):
+        ref64.assert_f32_close(z.float() + 1e-30, z, z.float())
+    # scalars: |loss| + 1
+    ref64.assert_f32_close(torch.tensor(2.0 + 1e-6), torch.tensor(2.0, dtype=F64), torch.tensor(2.0), scale=3.0)
+    with pytest.raises(AssertionError):
+        ref64.assert_f32_close(torch.tensor(2.0 + 1e-4), torch.tensor(2.0, dtype=F64), torch.tensor(2.0), scale=3.0)
+
+
+# ---- q/k RMSNorm + RoPE --------------------------------------------------------------------------------------------------------
+def _model_qknorm_rope(raw, qw, kw, cos, sin, S, nq, nkv, hd, eps, hf):
+    """The model's own modules: transformers' Qwen3RMSNorm over head_dim + apply_rotary_pos_emb (hf=True; that norm squares in float32
+    whatever it is given, so it agrees to float32 accuracy only), or their float64 restatement in oracle/qwen3_ref.py."""
+    M = raw.shape[0]
+    x = raw[:, :(nq + nkv) * hd].to(F64).reshape(M, nq + nkv, hd)
+    pos = torch.arange(M) % S
+    c = torch.cat([cos.to(F64), cos.to(F64)], -1)[pos]
+    s = torch.cat([sin.to(F64), sin.to(F64)], -1)[pos]
+    if not hf:
+        q = qwen3_ref.rms_norm(x[:, :nq], qw.to(F64), eps)
+        k = qwen3_ref.rms_norm(x[:, nq:], kw.to(F64), eps)
+        rot = lambda t: t * c[:, None] + qwen3_ref.rotate_half(t) * s[:, None]      # noqa: E731
+        return torch.cat([rot(q), rot(k)], 1)
+    from transformers.models.qwen3.modeling_qwen3 import Qwen3RMSNorm, apply_rotary_pos_emb
+    qn, kn = Qwen3RMSNorm(hd, eps=eps).to(F64), Qwen3RMSNorm(hd, eps=eps).to(F64)
+    with torch.no_grad():
+        qn.weight.copy_(qw.to(F64))
+        kn.weight.copy_(kw.to(F64))
+    q, k = apply_rotary_pos_emb(qn(x[:, :nq]), kn(x[:, nq:]), c, s, unsqueeze_dim=1)      # [M (batch), heads, hd] against cos [M, hd]
+    return torch.cat([q.to(F64), k.to(F64)], 1)
+
+
+def _have_transformers():
+    try:
+        from transformers.models.qwen3.modeling_qwen3 import Qwen3RMSNorm, apply_rotary_pos_emb  # noqa: F401
+        return True
+    except ImportError:
+        return False
+
+
+@pytest.mark.parametrize("hd,nq,nkv,M,S", [(128, 3, 2, 70, 33), (64, 0, 3, 17, 1), (64, 5, 1, 40, 64)])
+def test_rope_forward_and_backward_match_the_models_modules(hd, nq, nkv, M, S):
+    raw, qw, kw, cos, sin = _rope_case(M, nq, nkv, hd, S, 20)
+    qw = -qw                                                                             # a negative norm weight is legal
+    mine = ref64.qknorm_rope_fwd(raw, qw, kw, cos, sin, S, nq, nkv, hd, 1e-6)
+    dout = _randn(tuple(mine.shape), 21)
+    g = ref64.qknorm_rope_bwd(dout, raw, qw, kw, cos, sin, S, nq, nkv, hd, 1e-6)
+    for hf, atol in ((False, 1e-13), (True, 2e-6)):
+        if hf and not _have_transformers():
+            continue
+        x = raw.to(F64).requires_grad_(True)
+        model = _model_qknorm_rope(x, qw, kw, cos, sin, S, nq, nkv, hd, 1e-6, hf)
+        assert torch.allclose(mine, model.detach(), rtol=0, atol=atol * float(mine.abs().max()))
+        (g_model,) = torch.autograd.grad(model, x, dout)
+        g_model = g_model[:, :(nq + nkv) * hd].reshape(mine.shape)
+        assert torch.allclose(g, g_model, rtol=0, atol=atol * float(g.abs().max()))
+    # the written-out gradient from (roped output, 1 / rms) is the same function when both are exact and the tables are an exact
+    # rotation (float64 tables: c^2 + s^2 = 1 to 1e-16; the f32 tables' 1e-7 is part of what the GPU test measures as e_rt)
+    c64, s64 = ref64.rope_table(S, hd, 1e6)
+    o64 = ref64.qknorm_rope_fwd(raw, qw, kw, c64, s64, S, nq, nkv, hd, 1e-6)
+    g64 = ref64.qknorm_rope_bwd(dout, raw, qw, kw, c64, s64, S, nq, nkv, hd, 1e-6)
+    rstd = ref64.qknorm_rope_rstd(raw, nq, nkv, hd, 1e-6)
+    g2 = ref64.qknorm_rope_bwd_from_roped(dout, o64, rstd, qw, kw, c64, s64, S, nq, nkv, hd)
+    assert torch.allclose(g2, g64, rtol=0, atol=1e-11)
+
+
+@pytest.mark.parametrize("hd,theta", [(64, 1e4), (128, 1e6)])
+def test_rope_table_matches_the_rotary_embedding_recipe(hd, theta):
+    S = 4096
+    cos, sin = ref64.rope_table(S, hd, theta)
+    # transformers' default rope init: inv_freq = 1 / base ** (arange(0, dim, 2) / dim); freqs = pos x inv_freq
+    inv = 1.0 / (theta ** (torch.arange(0, hd, 2, dtype=torch.int64).to(F64) / hd))
+    ang = torch.arange(S, dtype=F64)[:, None] * inv[None]
+    assert torch.allclose(cos, torch.cos(ang), rtol=0, atol=1e-9) and torch.allclose(sin, torch.sin(ang), rtol=0, atol=1e-9)
+    # and the float32 run of that recipe under the rope-table metric |err| / (pos * 2^-21 + 2^-22), for the lab note
+    inv32 = 1.0 / (theta ** (torch.arange(0, hd, 2, dtype=torch.int64).float() / hd))
+    ang32 = torch.arange(S, dtype=torch.float32)[:, None] * inv32[None]
+    bound = torch.arange(S, dtype=F64)[:, None] * 2.0 ** -21 + 2.0 ** -22
+    worst = max(float(((torch.cos(ang32).to(F64) - cos).abs() / bound).max()), float(((torch.sin(ang32).to(F64) - sin).abs() / bound).max()))
+    print(f"float32 inv_freq recipe, hd {hd} theta {theta:g}: worst |err| / (pos * 2^-21 + 2^-22) = {worst:.3f}")
+    assert worst < 4.0            # the same order as the bound: the recipe's own f32 error is what the bound was derived from
+
+
+# ---- PE / assembly -------------------------------------------------------------------------------------------------------------
+def test_positional_encoding_and_assembly():
+    L, Qi, H = 7, 4, 264
+    pe = ref64.sinusoidal_pe(L * Qi, H)
+    pos = np.arange(L * Qi, dtype=np.float64)[:, None]
+    for d in (0, 2, 130, 262):
+        w = np.exp(-d * np.log(10000.0) / H)
+        assert np.allclose(pe[:, d].numpy(), np.sin(pos[:, 0] * w), rtol=0, atol=1e-14)
+        assert np.allclose(pe[:, d + 1].numpy(), np.cos(pos[:, 0] * w), rtol=0, atol=1e-14)
+    assert torch.allclose(pe.float(), qformer_ref.sinusoidal_pe(L * Qi, H), rtol=0, atol=2e-6)
+    big = ref64.sinusoidal_pe(3200, 768)
+    assert float((big.float() - qformer_ref.sinusoidal_pe(3200, 768)).abs().max()) < 1e-3          # the f32 recipe drifts with pos
+    tok, ctx = _randn((3, L, Qi, H), 1, torch.float32), _randn((3, L, H), 2, torch.float32)
+    lens = torch.tensor([0, 3, L], dtype=torch.int32)
+    out, mask = ref64.user_sequence_assemble(tok, ctx, lens)
+    for b in range(3):
+        n = int(lens[b]) * Qi
+        want = qformer_ref.assemble_user_sequence(tok[b], ctx[b])
+        assert torch.allclose(out[b, :n].float(), want[:n], rtol=0, atol=1e-5)
+        assert (out[b, n:] == 0).all() and (mask[b, :n] == 1).all() and (mask[b, n:] == 0).all()
+    keep = (torch.rand((3, L * Qi, H), generator=_gen(5)) > 0.1)
+    outd, _ = ref64.user_sequence_assemble(tok, ctx, lens, keep=keep, p=0.1)
+    assert torch.equal(outd, out * keep.to(F64) / 0.9)
+
+
+# ---- ranking head ----------------------------------------------------------------------------------------------------------------
+def test_cosine_scores_and_infonce_match_functional():
+    B, N, D, tau = 5, 37, 24, 0.07
+    user, pos, neg = _randn((B, D), 1), _randn((B, D), 2), _randn((B, N, D), 3)
+    user[2] = 0                                                                          # a zero user row: scores 0
+    neg[1, 4] = 0
+    s = ref64.cosine_scores(user, pos, neg)
+    cand = torch.cat([pos[:, None], neg], 1)
+    want = F.cosine_similarity(user[:, None, :].expand_as(cand), cand, dim=-1, eps=1e-12)
+    want[2] = 0
+    want[1, 5] = 0
+    assert torch.allclose(s, want, rtol=0, atol=1e-14)
+    assert torch.allclose(ref64.catalog_scores(user, neg[0]), F.normalize(user, dim=-1, eps=1e-12) @ F.normalize(neg[0], dim=-1, eps=1e-12).t(),
+                          rtol=0, atol=1e-14)
+    user[2] = _randn((D,), 8)                      # (the gradient through a zero user row is 1 / eps-sized: not compared)
+    for mask in (None, torch.rand((B, N), generator=_gen(4)) > 0.4, torch.zeros(B, N, dtype=torch.bool)):
+        u = user.clone().requires_grad_(True)
+        z = torch.cat([(F.normalize(u, dim=-1, eps=1e-12) * F.normalize(pos, dim=-1, eps=1e-12)).sum(-1, keepdim=True),
+                       torch.einsum("bd,bnd->bn", F.normalize(u, dim=-1, eps=1e-12), F.normalize(neg, dim=-1, eps=1e-12))], 1) / tau
+        if mask is not None:
+            z = torch.cat([z[:, :1], z[:, 1:].masked_fill(~mask, float("-inf"))], 1)
+        want_loss = F.cross_entropy(z, torch.zeros(B, dtype=torch.long))
+        (want_du,) = torch.autograd.grad(want_loss, u)
+        loss, du = ref64.infonce(user, pos, neg, mask, tau, grad_scale=3.0)
+        assert abs(float(loss - want_loss.detach())) < 1e-13 and torch.allclose(du, 3.0 * want_du, rtol=0, atol=1e-13)
+        if mask is not None and not mask.any():
+            assert abs(float(loss)) < 1e-15
+        o_loss = qwen3_ref.infonce_loss(user.float(), pos.float(), neg.float(), None if mask is None else mask, tau)
+        assert abs(float(o_loss) - float(loss)) < 1e-4 * (1 + abs(float(loss)))
+
+
+def test_ranks_and_topk_match_stable_sorts():
+    g = _gen(9)
+    s = torch.randint(-3, 4, (6, 300), generator=g).float()                              # many ties
+    s[1] = 2.0                                                                           # all equal
+    s[2, 5] = s[2, 261] = 9.0                                                            # equal maxima 256 apart
+    s[3, :] = float("-inf")
+    s[4, 7] = float("inf")
+    s[4, 100:200] = float("-inf")
+    for K in (1, 10, 300):
+        idx, val = ref64.topk(s, K)
+        want = torch.argsort(-s, dim=1, stable=True)[:, :K]
+        assert torch.equal(idx, want) and torch.equal(val, s.gather(1, want))
+        tv, _ = torch.topk(s, K, dim=1)
+        assert torch.equal(val, tv)
+    assert torch.equal(ref64.topk(s, 4)[0][1], torch.arange(4))
+    mask = torch.rand((6, 299), generator=g) > 0.5
+    r = ref64.mrr_rank(s, mask)
+    for b in range(6):
+        assert int(r[b]) == 1 + sum(1 for n in range(299) if mask[b, n] and s[b, 1 + n] > s[b, 0])
+    assert int(ref64.mrr_rank(s)[1]) == 1
+    gt = torch.tensor([0, 7, 261, 4, 7, 299])
+    want_rank = torch.tensor([1 + int((s[b] > s[b, gt[b]]).sum()) for b in range(6)])
+    assert torch.equal(ref64.rank_of_index(s, gt), want_rank)
+    fin = torch.nan_to_num(s, posinf=50.0, neginf=-50.0)
+    _, o_rank, o_order = data_ref.catalog_eval(np.eye(6, dtype=np.float32), np.eye(6, dtype=np.float32), np.arange(6), 3)
+    assert (o_rank == 1).all() and (o_order[:, 0] == np.arange(6)).all()
+    order = np.argsort(-fin.numpy(), axis=1, kind="stable")[:, :10]
+    assert np.array_equal(ref64.topk(fin, 10)[0].numpy(), order)
+
+
+# ---- heads / losses --------------------------------------------------------------------------------------------------------------
+def test_recon_triplet_and_mse_match_functional():
+    B, Fn, E = 4, 5, 24
+    rec, x = _randn((B, Fn, E), 1), _randn((B, Fn, E), 2)
+    rec[0, 1] = 0                                                                        # cosine eps path
+    mask = torch.tensor([[1, 1, 0, 1, 0], [0, 0, 0, 1, 0], [1, 1, 1, 1, 1], [0, 1, 0, 0, 0]], dtype=torch.float32)
+    sums = ref64.recon_stats(rec.reshape(-1, E), x.reshape(-1, E), mask.reshape(-1))
+    mse, cos_sum, nvalid = qformer_ref.eval_reconstruction(rec, x, mask)
+    assert abs(float(sums[0] / sums[1] - mse)) < 1e-13 and abs(float(sums[2] - cos_sum)) < 1e-13 and int(sums[1]) == nvalid
+    r = rec.clone().requires_grad_(True)
+    a, p, n = _randn((B, E), 3), _randn((B, E), 4), _randn((B, E), 5)
+    total, recon, cont = qformer_ref.qformer_loss({"reconstructed_fields": r, "item_representation": a}, x, mask, p, n, 1.0, 0.5, 0.5)
+    (dr,) = torch.autograd.grad(recon, r)
+    assert torch.allclose(ref64.recon_grad(rec.reshape(-1, E), x.reshape(-1, E), mask.reshape(-1), 0.7).reshape(B, Fn, E), 0.7 * dr, rtol=0, atol=1e-14)
+    for margin in (0.5, 0.01, 3.0):
+        a2 = a.clone()
+        a2[1] = p[1]                                                                     # anchor == positive
+        a2.requires_grad_(True)
+        want = F.triplet_margin_loss(a2, p, n, margin=margin, p=2, eps=1e-6, reduction="mean")
+        (wg,) = torch.autograd.grad(want, a2)
+        loss, da = ref64.triplet_margin(a2.detach(), p, n, margin, 1.5)
+        assert abs(float(loss - want.detach())) < 1e-13 and torch.allclose(da, 1.5 * wg, rtol=0, atol=1e-13)
+    assert abs(float(ref64.triplet_margin(a, p, n, 0.5, 1.0)[0] - cont)) < 1e-13
+    u, v = _randn((1001,), 6), _randn((1001,), 7)
+    u.requires_grad_(True)
+    want = F.mse_loss(u, v)
+    (wg,) = torch.autograd.grad(want, u)
+    loss, du = ref64.mse(u.detach(), v, 0.3)
+    assert abs(float(loss - want.detach())) < 1e-14 and torch.allclose(du, 0.3 * wg, rtol=0, atol=1e-15)
+
+
+# ---- element-wise ---------------------------------------------------------------------------------------------------------------
+def test_gelu_and_swiglu_derivatives_match_autograd():
+    u = torch.linspace(-12.0, 12.0, 4001, dtype=F64).requires_grad_(True)
+    y = F.gelu(u)
+    (g,) = torch.autograd.grad(y.sum(), u)
+    assert torch.allclose(ref64.gelu_grad(u.detach()), g, rtol=1e-9, atol=1e-15)
+    assert torch.allclose(ref64.gelu(u.detach()), y.detach(), rtol=1e-9, atol=1e-15)
+    # far negative tail: erfc keeps relative accuracy where 1 + erf has none
+    t = torch.tensor([-9.0], dtype=F64)
+    exact = 0.5 * math.erfc(9.0 / math.sqrt(2.0)) - 9.0 * math.exp(-40.5) / math.sqrt(2.0 * math.pi)
+    assert abs(float(ref64.gelu_grad(t)) / exact - 1.0) < 1e-9
+    gate = torch.linspace(-40.0, 40.0, 1601, dtype=F64).requires_grad_(True)
+    up = _randn((1601,), 1).requires_grad_(True)
+    act = F.silu(gate) * up
+    d = _randn((1601,), 2)
+    dg, du = torch.autograd.grad(act, (gate, up), d)
+    assert torch.allclose(ref64.swiglu_fwd(gate.detach(), up.detach()), act.detach(), rtol=1e-12, atol=1e-300)
+    mg, mu = ref64.swiglu_bwd(d, gate.detach(), up.detach())
+    assert torch.allclose(mg, dg, rtol=1e-9, atol=1e-18) and torch.allclose(mu, du, rtol=1e-12, atol=1e-300)
+    # extremes stay finite
+    ext = torch.tensor([-3e38, -800.0, 800.0, 3e38], dtype=F64)
+    assert torch.isfinite(ref64.swiglu_fwd(ext, torch.ones(4))).all() and torch.isfinite(ref64.swiglu_bwd(torch.ones(4), ext, torch.ones(4))[0]).all()
+
+
+# ---- event-context features ------------------------------------------------------------------------------------------------------
+def test_context_features_follow_the_float32_recipe():
+    ts = torch.tensor([0.0, -1.0, -86400.0 * 3 - 5, 86400.0 * 19000, 31557600.0 * 50, 1.7e9, 1.7e9 + 12345.0, 123456.789], dtype=torch.float32)
+    feat, ang = ref64.timestamp_features(ts)
+    want = data_ref.timestamp_features(ts.numpy())
+    assert feat.shape == (8, 9) and np.allclose(feat.numpy(), want, rtol=0, atol=3e-7)      # libm sin / cos may round the last bit apart
+    assert (ang[:, 0] == 0).all() and (ang[:, 1:] >= 0).all()          # (the week phase is not reduced: its angle grows with the timestamp)
+    co = torch.tensor([[90.0, 0.0], [-90.0, 180.0], [0.0, -180.0], [40.1, -88.2], [0.0, 0.0]], dtype=torch.float32)
+    gf, _ = ref64.geo_features(co)
+    assert np.allclose(gf.numpy(), data_ref.geo_features(co.numpy()), rtol=0, atol=3e-7)
+    W1, b1 = _randn((10, 9), 3, torch.float32), _randn((10,), 4, torch.float32)
+    lin = torch.nn.Linear(9, 10).to(F64)
+    with torch.no_grad():
+        lin.weight.copy_(W1)
+        lin.bias.copy_(b1)
+        want_h = F.gelu(lin(feat.to(F64)))
+    assert torch.allclose(ref64.context_mlp1(feat, W1, b1), want_h, rtol=1e-12, atol=1e-15)
+    P = {"projection.0.weight": W1.numpy(), "projection.0.bias": b1.numpy(), "projection.2.weight": np.eye(10, dtype=np.float32),
+         "projection.2.bias": np.zeros(10, dtype=np.float32)}
+    assert np.allclose(data_ref.context_mlp(want, P), want_h.numpy(), rtol=0, atol=1e-5)

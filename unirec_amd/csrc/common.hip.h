@@ -267,7 +267,19 @@ __device__ __forceinline__ float gelu_erf_grad_f(float x) {
 // four fused multiply-adds, v_div_fmas, v_div_fixup: ~10 of the 21 vector instructions per element of the SwiGLU-backward
 // GEMM epilogue, which is bound by exactly that arithmetic).  Every SwiGLU path (stand-alone kernels, both GEMM kernels'
 // epilogues, the fused SwiGLU + adapter kernel) uses these two helpers, so they stay bit-identical to one another.
-__device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float silu_f(float x) { return x * sigmoid_f(x); }
+// Below x = -87.3 the reciprocal is subnormal and v_rcp_f32 returns 0 for it (below -88.7 e^-x itself leaves f32), although
+// x * sigmoid(x) stays a normal number down to x = -103 (torch's own float32 silu returns -0 there;
+// tests/test_gpu_head_primitives.py::test_swiglu_exhaustive holds every bf16 gate to 1 ulp): there sigmoid(x) = e^x to f32
+// precision, formed as 2^-64 * exp2(x log2(e) + 64) so that the exponential stays normal and the scaling is the only rounding into the
+// subnormals.  Every x above -87.3 takes the reciprocal path bit for bit as before.
+__device__ __forceinline__ float sigmoid_tail64_f(float x) { return __builtin_amdgcn_exp2f(fmaf(x, 1.4426950408889634f, 64.0f)); }      // e^x * 2^64
+__device__ __forceinline__ float sigmoid_f(float x) {
+  const float e = __expf(-x);
+  return e < 0x1p126f ? __builtin_amdgcn_rcpf(1.0f + e) : sigmoid_tail64_f(x) * 0x1p-64f;
+}
+__device__ __forceinline__ float silu_f(float x) {
+  const float e = __expf(-x);
+  return e < 0x1p126f ? x * __builtin_amdgcn_rcpf(1.0f + e) : (x * sigmoid_tail64_f(x)) * 0x1p-64f;      // (x first: one rounding into the subnormals)
+}
 
 static inline int ur_cdiv(long a, long b) { return (int)((a + b - 1) / b); }

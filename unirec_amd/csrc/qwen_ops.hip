@@ -384,7 +384,7 @@ extern "C" int ur_qknorm_rope_fwd(const void* qkv_raw, int64_t ldraw, const floa
   int rc = qk_common_check(qkv_raw, ldraw, q_norm_w, k_norm_w, cos_tab, sin_tab, M, S, nq, nkv, head_dim, "ur_qknorm_rope_fwd");
   if (rc) return rc;
   if (M == 0) return 0;
-  UR_REQUIRE(q_out && k_out && UR_ALIGNED16(q_out) && UR_ALIGNED16(k_out), "ur_qknorm_rope_fwd: bad outputs");
+  UR_REQUIRE((nq == 0 || q_out) && k_out && UR_ALIGNED16(q_out) && UR_ALIGNED16(k_out), "ur_qknorm_rope_fwd: bad outputs");   // (nq == 0: q_out is never written)
   const int tpb = 256 / (head_dim / 8);                    // tokens per workgroup
   const int grid = grid_cap(((long)M + tpb - 1) / tpb, 256 * 16);
   if (head_dim == 128)
@@ -404,7 +404,7 @@ extern "C" int ur_qknorm_rope_bwd(const void* dq_out, const void* dk_out, const 
   int rc = qk_common_check(qkv_raw, ldraw, q_norm_w, k_norm_w, cos_tab, sin_tab, M, S, nq, nkv, head_dim, "ur_qknorm_rope_bwd");
   if (rc) return rc;
   if (M == 0) return 0;
-  UR_REQUIRE(dq_out && dk_out && dqkv_raw && UR_ALIGNED16(dq_out) && UR_ALIGNED16(dk_out) && UR_ALIGNED16(dqkv_raw) && (lddraw % 8) == 0 &&
+  UR_REQUIRE((nq == 0 || dq_out) && dk_out && dqkv_raw && UR_ALIGNED16(dq_out) && UR_ALIGNED16(dk_out) && UR_ALIGNED16(dqkv_raw) && (lddraw % 8) == 0 &&
              lddraw >= (int64_t)(nq + nkv) * head_dim, "ur_qknorm_rope_bwd: bad gradient buffers");
   const int tpb = 256 / (head_dim / 8);                    // tokens per workgroup
   const int grid = grid_cap(((long)M + tpb - 1) / tpb, 256 * 16);
