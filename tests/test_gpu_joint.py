@@ -144,14 +144,14 @@ def test_joint_with_lora_matches_oracle(name):
 def test_merged_projection_launches_are_bit_identical(monkeypatch):
     """q|k|v and gate|up leave as ONE GEMM launch each, their LoRA term as a block-diagonal second K range (exact zeros off the
     diagonal): the pooled output and every LoRA gradient must equal the per-adapter launches bit for bit."""
-    import unirec_amd.qwen3 as qmod
     from unirec_amd.joint import InfoNCELoss
+    from unirec_amd.switches import switches
     case = cases.ALL[JOINT[0]]
     ids, am, hfe, ham, pos, neg, nmask = cases.joint_inputs(case)
     t = lambda a: torch.from_numpy(a).to(DEV)
     res = []
     for merged in (True, False):
-        monkeypatch.setattr(qmod, "_MERGE_PROJ", merged)
+        monkeypatch.setattr(switches, "merge_proj", merged)
         m, qf = _build_joint(case, use_lora=True, lora_seed=case["seed"] + 2)
         user = m(t(ids), t(am), t(hfe), t(ham))
         InfoNCELoss()(user, t(pos), t(neg), t(nmask)).backward()

@@ -120,6 +120,7 @@ def test_fused_qknorm_rope_epilogue_matches_the_separate_pass(monkeypatch, sprea
     masks: pooled output, input gradient and every LoRA gradient against the path with the separate ur_qknorm_rope pass."""
     import unirec_amd.qwen3 as qmod
     from unirec_amd.qwen3 import Qwen3Config, Qwen3LoRAModel
+    from unirec_amd.switches import switches
     B, S, L = 4, 2048, 2
     cfg = Qwen3Config(vocab_size=512, num_hidden_layers=L, lora_dropout=0.1)
     torch.manual_seed(7)
@@ -148,7 +149,7 @@ def test_fused_qknorm_rope_epilogue_matches_the_separate_pass(monkeypatch, sprea
     monkeypatch.setattr(qmod.hip, "gemm_qkv_rope", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
 
     def run(fused):
-        monkeypatch.setattr(qmod, "_FUSE_QK_ROPE", fused)
+        monkeypatch.setattr(switches, "fuse_qk_rope", fused)
         m._lora_step, m._bcomb = 11, None
         for p_ in m.parameters():
             p_.grad = None

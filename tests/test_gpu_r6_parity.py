@@ -103,13 +103,13 @@ def test_joint_c4_exact_architecture_matches_the_reference():
 @pytest.mark.parametrize("kind", ["item", "user"])
 def test_weight_gradients_on_the_side_stream_are_bit_identical(kind, monkeypatch):
     """Round 6: the Q-Formers' token reductions dW = dY^T X and bias column sums run on a side stream beside the dX chain
-    (unirec_amd/qformer.py:_DW_SIDE).  Same kernels, same arithmetic: every gradient equals the single-stream run bit for bit, also when the
+    (switches.qf_dw_stream).  Same kernels, same arithmetic: every gradient equals the single-stream run bit for bit, also when the
     step is repeated (the second step reuses memory the first one's side-stream work read)."""
-    import unirec_amd.qformer as qformer
     from unirec_amd.losses import mse_loss
+    from unirec_amd.switches import switches
 
     def run(side):
-        monkeypatch.setattr(qformer, "_DW_SIDE", side)
+        monkeypatch.setattr(switches, "qf_dw_stream", side)
         torch.manual_seed(7)
         if kind == "item":
             from unirec_amd.qformer_utils import QFormerForItemRepresentation

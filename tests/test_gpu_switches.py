@@ -6,7 +6,10 @@ bit-identity tests compare with EACH OTHER.  Here each alternative is compared w
 `joint_mid` (item Q-Former -> injection -> 2 decoder layers of the 0.6B shape, S 512, left padding -> InfoNCE; the fixture the
 reference itself produced pins the oracle for this case: tests/test_oracle_golden_r2.py) with LoRA dropout ON and the kernels' own
 masks fed in -- outputs, loss, LoRA dA / dB, and the gradient that reaches the Q-Former through every masked adapter input.
-The oracle runs once; each switch costs one product step."""
+The oracle runs once; each switch costs one product step.
+
+Every environment switch is a field of `unirec_amd.switches.switches`, read once when the package is imported; a test flips the field
+(`monkeypatch.setattr(switches, field, value)`), never the environment."""
 import functools
 
 import pytest
@@ -103,47 +106,50 @@ def test_default_path_meets_the_oracle():
     _product_step_meets_the_oracle("defaults")
 
 
-# module-level switches of unirec_amd.qwen3 / qformer (read from the environment at import): flipped on the module
-MODULE_SWITCHES = {
-    "UNIREC_MERGE_PROJ=0": [("qwen3", "_MERGE_PROJ", False)],
-    "UNIREC_MERGE_PROJ=0 UNIREC_SWIGLU_FWD_FUSED=1": [("qwen3", "_MERGE_PROJ", False), ("qwen3", "_FUSE_SWIGLU_FWD", True)],
-    "UNIREC_FUSE_NORM_LORA=0": [("qwen3", "_FUSE_NORM_LORA", False)],
-    "UNIREC_FUSE_QK_ROPE=0": [("qwen3", "_FUSE_QK_ROPE", False)],
-    "UNIREC_FUSE_SWIGLU_GEMM=0": [("qwen3", "_FUSE_SWIGLU_GEMM", False)],
-    "UNIREC_FUSE_SWIGLU_GEMM=0 UNIREC_FUSE_SWIGLU_LORA=0": [("qwen3", "_FUSE_SWIGLU_GEMM", False), ("qwen3", "_FUSE_SWIGLU_LORA", False)],
-    "UNIREC_QF_WT=0": [("qformer", "_USE_WT", False)],
-    "UNIREC_KV_COLSUM=0": [("qformer", "_KV_COLSUM", False)],
-    "UNIREC_QF_DW_STREAM=0": [("qformer", "_DW_SIDE", False)],
-    "UNIREC_QF_DW_GROUPED=0": [("qformer", "_DW_GROUPED", False)],
+# test id -> the fields of unirec_amd.switches.switches it flips (README "Switches": one field per environment variable, read once at import)
+SWITCHES = {
+    "UNIREC_MERGE_PROJ=0": {"merge_proj": False},
+    "UNIREC_MERGE_PROJ=0 UNIREC_SWIGLU_FWD_FUSED=1": {"merge_proj": False, "swiglu_fwd_fused": True},
+    "UNIREC_FUSE_NORM_LORA=0": {"fuse_norm_lora": False},
+    "UNIREC_FUSE_QK_ROPE=0": {"fuse_qk_rope": False},
+    "UNIREC_FUSE_SWIGLU_GEMM=0": {"fuse_swiglu_gemm": False},
+    "UNIREC_FUSE_SWIGLU_GEMM=0 UNIREC_FUSE_SWIGLU_LORA=0": {"fuse_swiglu_gemm": False, "fuse_swiglu_lora": False},
+    "UNIREC_QF_WT=0": {"qf_wt": False},
+    "UNIREC_KV_COLSUM=0": {"kv_colsum": False},
+    "UNIREC_QF_DW_STREAM=0": {"qf_dw_stream": False},
+    "UNIREC_QF_DW_GROUPED=0": {"qf_dw_grouped": False},
+    "UNIREC_BITS_T=0": {"bits_t": False},
+    "UNIREC_BITS_ONE_EVENT=1": {"bits_one_event": True},
+    "UNIREC_PAD_ATT=0": {"pad_att": False},
+    "UNIREC_ROPE_BWD_FUSED=0": {"rope_bwd_fused": False},
+    "UNIREC_ROPE_K_FUSED=0": {"rope_k_fused": False},
+    # the dQ kernel's q-norm + RoPE backward from the RAW projection
+    "UNIREC_FUSE_QK_ROPE_OFF_AND_ROPE_BWD_FUSED=1": {"fuse_qk_rope": False, "rope_bwd_fused": True},
+    "UNIREC_BITS_NEXT=0": {"bits_next": False},
 }
-# switches read on every call (Python layer and library)
-ENV_SWITCHES = ["UNIREC_BITS_T=0", "UNIREC_BITS_ONE_EVENT=1", "UNIREC_PAD_ATT=0", "UNIREC_ROPE_BWD_FUSED=0", "UNIREC_ROPE_K_FUSED=0",
-                "UNIREC_FUSE_QK_ROPE_OFF_AND_ROPE_BWD_FUSED=1"]
+# the switches that were module globals of qwen3 / qformer once, and those that were read on every call: the two tests keep their ids
+_FIRST_CALL_TIME = list(SWITCHES).index("UNIREC_BITS_T=0")
+IMPORT_TIME, CALL_TIME = list(SWITCHES)[:_FIRST_CALL_TIME], list(SWITCHES)[_FIRST_CALL_TIME:]
 # kernel-selection words of the library (ur_attn_mode; it reads no environment variable)
 ATTN_MODES = {"ur_attn_mode(C128, 0)": (1, 0), "ur_attn_mode(DKV_PERSIST, 0)": (2, 0), "ur_attn_mode(TINY, 0)": (0, 0)}
 
 
-@pytest.mark.parametrize("name", list(MODULE_SWITCHES))
+def _flipped_alone(name, monkeypatch):
+    from unirec_amd.switches import switches
+    for field, val in SWITCHES[name].items():
+        assert getattr(switches, field) != val, f"{name}: already the default?"
+        monkeypatch.setattr(switches, field, val)
+    _product_step_meets_the_oracle(name)
+
+
+@pytest.mark.parametrize("name", IMPORT_TIME)
 def test_module_switch_flipped_alone(name, monkeypatch):
-    import unirec_amd.qformer as qformer
-    import unirec_amd.qwen3 as qwen3
-    mods = {"qwen3": qwen3, "qformer": qformer}
-    for mod, attr, val in MODULE_SWITCHES[name]:
-        assert getattr(mods[mod], attr) != val, f"{name}: already the default?"
-        monkeypatch.setattr(mods[mod], attr, val)
-    _product_step_meets_the_oracle(name)
+    _flipped_alone(name, monkeypatch)
 
 
-@pytest.mark.parametrize("name", ENV_SWITCHES)
+@pytest.mark.parametrize("name", CALL_TIME)
 def test_call_time_switch_flipped_alone(name, monkeypatch):
-    if name == "UNIREC_FUSE_QK_ROPE_OFF_AND_ROPE_BWD_FUSED=1":      # the dQ kernel's q-norm + RoPE backward from the RAW projection
-        import unirec_amd.qwen3 as qwen3
-        monkeypatch.setattr(qwen3, "_FUSE_QK_ROPE", False)
-        monkeypatch.setenv("UNIREC_ROPE_BWD_FUSED", "1")
-    else:
-        k, v = name.split("=")
-        monkeypatch.setenv(k, v)
-    _product_step_meets_the_oracle(name)
+    _flipped_alone(name, monkeypatch)
 
 
 @pytest.mark.parametrize("name", list(ATTN_MODES))

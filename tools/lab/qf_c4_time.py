@@ -3,7 +3,7 @@ import os, sys, time
 sys.path.insert(0, os.getcwd())
 import torch
 from unirec_amd.qformer_utils import QFormerForItemRepresentation
-import unirec_amd.qformer as qformer
+from unirec_amd.switches import switches
 torch.manual_seed(0)
 m = QFormerForItemRepresentation(hidden_size=1024, num_hidden_layers=12, num_attention_heads=16, intermediate_size=4096, num_query_tokens=2,
                                  field_embedding_dim=1024, num_fields=14, dropout=0.2).cuda().train()
@@ -19,6 +19,6 @@ def run(n=10):
         if i >= 3: tf += e[0].elapsed_time(e[1]); tb += e[1].elapsed_time(e[2])
     return tf / n, tb / n
 for side in (True, False, True, False):
-    qformer._DW_SIDE = side
+    switches.qf_dw_stream = side
     t0 = time.perf_counter(); f, b = run(); host = (time.perf_counter() - t0) / 13
     print(f"side stream {side}: forward {f:.2f} ms  backward {b:.2f} ms  (host loop {host * 1e3:.2f} ms per step)")

@@ -15,7 +15,6 @@ invert_attention_mask; BertSelfAttention :169-275; BertSelfOutput :285-289; Bert
 :402-484; BertEncoder loop :517-566; BertModel.forward :804-972.
 """
 import math
-import os
 import re
 from types import SimpleNamespace
 
@@ -24,6 +23,7 @@ import torch.nn as nn
 
 from . import hip
 from .packing import ParamPack, norm_device
+from .switches import switches
 
 try:  # the reference re-exports transformers' BertConfig (models/qformer.py:46); checkpoints pickle it
     from transformers.models.bert.configuration_bert import BertConfig
@@ -113,15 +113,7 @@ class _EncoderParams(nn.Module):
         self.layer = nn.ModuleList([_LayerParams(config, i) for i in range(config.num_hidden_layers)])
 
 
-_KV_COLSUM = os.environ.get("UNIREC_KV_COLSUM", "1") != "0"     # test / lab: 0 = the K | V bias gradients by a column-sum pass over dK | dV again
-_USE_WT = os.environ.get("UNIREC_QF_WT", "1") != "0"     # lab: 0 = dX products read the [out, in] weights as K-strided operands again
-# round 6: the weight gradients dW = dY^T X (token reductions, split-K) and the bias column sums of the backward are issued on a SIDE stream:
-# they hang off the dX chain (nothing in the backward reads them) and neither they nor the dX products fill 256 CUs at the Q-Formers' row counts
-# (item Q-Former of the joint step: 6400 rows = 100 output tiles), so the two streams' kernels run beside each other.  Same kernels, same
-# arithmetic: results bit-identical (tests/test_gpu_r6_parity.py).  0 = everything on the caller's stream, as before.
-_DW_SIDE = os.environ.get("UNIREC_QF_DW_STREAM", "1") != "0"
-_DW_SIDE_MAX_ROWS = 65536       # (beyond: the inputs held until the join are whole gigabytes; C3 runs 32768 rows)
-_DW_GROUPED = os.environ.get("UNIREC_QF_DW_GROUPED", "1") != "0"
+_DW_SIDE_MAX_ROWS = 65536       # switches.qf_dw_stream applies up to here (beyond: the inputs held until the join are whole gigabytes; C3 runs 32768 rows)
 _side_streams = {}
 
 
@@ -439,7 +431,7 @@ class BertModel(nn.Module):
         """W^T of every weight a dX product reads (dx = dy W), refreshed by ONE launch per backward: with [in, out] copies the
         dX launches are K-contiguous on both operands and take the 8-phase loop like the forward (the token-major [out, in]
         weight as a K-strided operand runs the 2-slot loop: 110 vs 84 us at M 8192, N 3072, K 768).  UNIREC_QF_WT=0: lab."""
-        if not _USE_WT:
+        if not switches.qf_wt:
             return None
         bt = getattr(self, "_wt", None)
         if bt is None or bt[0] is not pack or bt[1] != (pre, with_enc):
@@ -522,7 +514,7 @@ class BertModel(nn.Module):
             return hip.gemm(dy, pack.fused16(list(names)) if len(names) > 1 else pack.w16(names[0]), s_kcontig=False, **kw)
 
         # (at 32768 rows -- the user Q-Former of C3 -- both streams' kernels fill the chip: 50.7-51.0 -> 50.4 ms per step, no more)
-        side = _side_stream(dout.device) if (_DW_SIDE and dout.is_cuda and M <= _DW_SIDE_MAX_ROWS) else None
+        side = _side_stream(dout.device) if (switches.qf_dw_stream and dout.is_cuda and M <= _DW_SIDE_MAX_ROWS) else None
         main = torch.cuda.current_stream(dout.device) if side is not None else None
         held = []
         if side is not None:
@@ -561,7 +553,7 @@ class BertModel(nn.Module):
         # The weight gradients of ONE layer as one grouped launch (ur_gemm_grouped): 5-7 products of 9-36 big tiles each over the same tokens.
         # Alone each needs 7-14 token slices to fill the chip (K tiles too short to pay for a tile's prologue, and a split-K reduction launch each);
         # together they are one round of 256 x 256 tiles at split 1-2.  UNIREC_QF_DW_GROUPED=0: one ur_gemm per weight, as before.
-        grouped = [] if (_DW_GROUPED and dout.is_cuda and M >= 256) else None
+        grouped = [] if (switches.qf_dw_grouped and dout.is_cuda and M >= 256) else None
 
         def flush_dW():
             if not grouped:
@@ -617,7 +609,7 @@ class BertModel(nn.Module):
                 # the K | V bias gradients of this layer = column sums of its dK | dV: the few-query dK/dV kernel emits them with the
                 # gradients (user Q-Former: 64 queries x 1600 keys) and the second pass over every layer's dK | dV below disappears
                 cs = None
-                if kv_colsum_fused is not False and _KV_COLSUM and hip.attn_bwd_kv_colsum_supported(actx2):
+                if kv_colsum_fused is not False and switches.kv_colsum and hip.attn_bwd_kv_colsum_supported(actx2):
                     cs = pack.fusedg(kvb)[jc * 2 * H:(jc + 1) * 2 * H]
                     kv_colsum_fused = True
                 else:

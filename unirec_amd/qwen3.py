@@ -19,13 +19,15 @@ the base GEMM's accumulators (second K-range of ur_gemm).  Activations are kept 
 no gradient checkpointing); only the RMSNorm outputs are recomputed in the backward.
 """
 import math
-import os
+from collections import namedtuple
+from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
 
 from . import hip
 from .packing import ParamPack, norm_device
+from .switches import switches
 
 BF16, F32 = torch.bfloat16, torch.float32
 LORA_TARGETS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
@@ -94,28 +96,34 @@ class _TokenTable(nn.Module):
         self.weight = nn.Parameter(torch.empty(v, d), requires_grad=False)
 
 
-# UNIREC_SWIGLU_FWD_FUSED=1 runs SwiGLU forward as the up projection's epilogue (ur_gemm swiglu_gate) instead of its own launch.
-# Measured neutral on the joint step (115.1 vs 115.5 seq/s on one box, alternating runs: the epilogue's extra gate read and act
-# write are not overlapped with MFMA work at one workgroup per CU, and the stand-alone kernel already streams at 5.4 TB/s), so
-# the separate launch stays the default; the backward fusion (swiglu_gu), which removes 6 of 15 activation passes, is always on.
-# (Needs the per-adapter launches: it has no effect unless UNIREC_MERGE_PROJ=0 as well.)
-_FUSE_SWIGLU_FWD = os.environ.get("UNIREC_SWIGLU_FWD_FUSED", "0") == "1"
-
-
-# UNIREC_MERGE_PROJ=0 (lab): one projection launch per LoRA adapter instead of the merged q|k|v and gate|up launches
-_MERGE_PROJ = os.environ.get("UNIREC_MERGE_PROJ", "1") != "0"
-# UNIREC_FUSE_NORM_LORA=0 (lab): RMSNorm forward and the q|k|v / gate|up adapters' down projection as two kernels again
-_FUSE_NORM_LORA = os.environ.get("UNIREC_FUSE_NORM_LORA", "1") != "0"
-# UNIREC_FUSE_QK_ROPE=0 (lab): q/k-norm + RoPE as their own pass over the raw q|k|v again (the fused form needs the persistent GEMM:
-# >= 128 output tiles, S >= 256, head_dim 128; smaller launches take the separate pass anyway)
-_FUSE_QK_ROPE = os.environ.get("UNIREC_FUSE_QK_ROPE", "1") != "0"
+# The four adapter groups of a layer: the adapters of a group read the same input, so they share one set of dropout-bit planes, one
+# down-projection launch and one A^T.  (key of the group's t / bits entries in saved["layers"][i], its projections)
+ADAPTER_GROUPS = (("qkv", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")), ("o", ("self_attn.o_proj",)),
+                  ("gu", ("mlp.gate_proj", "mlp.up_proj")), ("d", ("mlp.down_proj",)))
 _QK_FUSE_MAX_RATIO = 4.0      # largest |w_d| / |w_{d+64}| spread of a rotate-half pair of the q / k norm weights under which the fused epilogue is used
-# UNIREC_FUSE_SWIGLU_GEMM=0 (lab): SwiGLU forward as its own pass over gate|up again (the fused form rides in the merged gate|up launch on
-# the persistent GEMM: interleaved weight rows put gate and up of a feature into one lane; the down adapter's t = dropout(act) A^T is
-# then a lora_project pass over act)
-_FUSE_SWIGLU_GEMM = os.environ.get("UNIREC_FUSE_SWIGLU_GEMM", "1") != "0"
-# UNIREC_FUSE_SWIGLU_LORA=0 (lab): SwiGLU forward and the down_proj adapter's down projection as two kernels again
-_FUSE_SWIGLU_LORA = os.environ.get("UNIREC_FUSE_SWIGLU_LORA", "1") != "0"
+
+
+# parameter names of one adapter group of one layer: a = the lora_A.weight of every adapter (the tuple is also the key of the group's A^T
+# in _lora_transposes), b = the lora_B.weight of every adapter
+_GroupNames = namedtuple("_GroupNames", "a b")
+
+
+@dataclass(frozen=True)
+class _Plan:
+    """The launch choices of one forward: constant over its layers, taken once before the loop (Qwen3LoRAModel._plan) and kept in
+    saved["plan"], where the backward reads what the forward did."""
+    merged: bool            # q|k|v and gate|up leave as one launch each (always so without adapters), not one per adapter
+    fuse_norm: bool         # RMSNorm + the q|k|v / gate|up adapters' down projection as one kernel
+    fuse_rope: bool         # q/k-norm + RoPE in the q|k|v launch's epilogue: no raw q, k exist
+    swiglu: str             # "pair": epilogue of the merged gate|up launch, "up": epilogue of the up projection's own launch,
+    #                         "lora": one pass with the down adapter's down projection (swiglu_lora_fwd), "alone": its own pass
+    pad_att: bool           # attention output rows padded by 64 columns
+    bits_one_event: bool    # wait for every layer's prefetched planes before the first layer
+    mlp_recompute: str      # under recompute_mlp: the launch that rebuilds gate|up and act, "pair" / "merged" / "plain" (no adapters); None
+    #                         (the per-adapter launches): the layer keeps them
+    rope_bwd_in_dq: bool    # backward: the q heads' q/k-norm + RoPE backward rides in the dQ kernel's store ...
+    rope_k_in_dkv: bool     # ... and the k heads' in the dK/dV kernel's (from the roped outputs only)
+    bits_t: bool            # backward: token-packed dropout flags for the token reductions that have no prefetched copy
 
 
 def _split_k(red, out_rows, out_cols):
@@ -162,8 +170,11 @@ class Qwen3LoRAModel(nn.Module):
         self._bcomb = None             # block-diagonal LoRA B operands of the merged q|k|v and gate|up launches
         self._bits_stream = None       # side stream + planes of prefetch_lora_bits
         self._bits_pre = None
-        self.recompute_mlp = os.environ.get("UNIREC_RECOMPUTE_MLP", "0") == "1"   # drop gate|up and act after the forward, rebuild them in the backward
+        self.recompute_mlp = switches.recompute_mlp   # drop gate|up and act after the forward, rebuild them in the backward
         self.keep_norm_outputs = True   # keep the two RMSNorm outputs per layer for the backward (memory for time); False recomputes them
+        # [layer][adapter group] -> parameter names, built once: the hot loops format no strings
+        self._names = [[_GroupNames(a=tuple(f"layers.{i}.{p}.lora_A.weight" for p in projs), b=tuple(f"layers.{i}.{p}.lora_B.weight" for p in projs))
+                        for _, projs in ADAPTER_GROUPS] for i in range(config.num_hidden_layers)]
         self.reset_parameters()
 
     def reset_parameters(self, lora_b_std=0.0):
@@ -234,16 +245,8 @@ class Qwen3LoRAModel(nn.Module):
     # ---- parameter plumbing ---------------------------------------------------------------------
     def lora_named_parameters(self):
         named = dict(self.named_parameters())
-        order = []
-        for i in range(self.config.num_hidden_layers):
-            lp = f"layers.{i}."
-            for grp in (("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), ("self_attn.o_proj",),
-                        ("mlp.gate_proj", "mlp.up_proj"), ("mlp.down_proj",)):
-                order += [lp + g + ".lora_A.weight" for g in grp]
-            for g in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj",
-                      "mlp.up_proj", "mlp.down_proj"):
-                order.append(lp + g + ".lora_B.weight")
-        return [(n, named[n]) for n in order]
+        # per layer: every A (group by group: the adapters of a group are neighbours in the pack, fused16 / fusedg), then every B
+        return [(n, named[n]) for groups in self._names for ab in "ab" for g in groups for n in getattr(g, ab)]
 
     def _ensure_pack(self, device):
         if not self.use_lora:
@@ -260,7 +263,7 @@ class Qwen3LoRAModel(nn.Module):
         """bf16 operands of the frozen base weights, fused per layer: [q|k|v], o, [gate|up], down."""
         # keyed on EVERY frozen tensor (storage + in-place version): loading any of them after a forward has run must not
         # leave stale bf16 / transposed copies behind
-        key = (str(device), _FUSE_QK_ROPE, _FUSE_SWIGLU_GEMM) + tuple((p.data_ptr(), p._version) for n, p in self.named_parameters() if ".lora_" not in n)
+        key = (str(device), switches.fuse_qk_rope, switches.fuse_swiglu_gemm) + tuple((p.data_ptr(), p._version) for n, p in self.named_parameters() if ".lora_" not in n)
         if self._frozen is not None and self._frozen["key"] == key:
             return self._frozen
         fz = {"key": key, "layers": []}
@@ -279,9 +282,9 @@ class Qwen3LoRAModel(nn.Module):
                 "qkv": c16(wqkv),
                 # q|k|v with the rows of every q / k head in the paired order of the fused q/k-norm + RoPE epilogue (hip.qkrope_perm)
                 # (only when that path can be selected at all: the duplicates cost ~0.6 GB at Qwen3-0.6B)
-                "qkvP": c16(wqkv.to(dev)[rp]) if (rp is not None and _FUSE_QK_ROPE) else None,
+                "qkvP": c16(wqkv.to(dev)[rp]) if (rp is not None and switches.fuse_qk_rope) else None,
                 # gate|up with 128-row blocks of gate and up interleaved (hip.swiglu_pair_rows): the paired SwiGLU forward epilogue
-                "guP": c16(wgu.to(dev)[self._swiglu_rows(m.gate_proj.weight.shape[0], dev)]) if (_FUSE_SWIGLU_GEMM and m.gate_proj.weight.shape[0] % 128 == 0) else None,
+                "guP": c16(wgu.to(dev)[self._swiglu_rows(m.gate_proj.weight.shape[0], dev)]) if (switches.fuse_swiglu_gemm and m.gate_proj.weight.shape[0] % 128 == 0) else None,
                 "o": c16(a.o_proj.weight), "gu": c16(wgu), "d": c16(m.down_proj.weight),
                 # frozen => one-time transposed copies, so every dX GEMM is K-contiguous on both operands
                 "qkvT": c16(wqkv.t()), "oT": c16(a.o_proj.weight.t()), "guT": c16(wgu.t()), "dT": c16(m.down_proj.weight.t()),
@@ -354,9 +357,6 @@ class Qwen3LoRAModel(nn.Module):
         return _JointFn.apply(self, item_tokens16, input_ids.contiguous(), mask_u8, int(first_special_id), anchor)
 
     # ---- implementation ---------------------------------------------------------------------------
-    def _lora(self, pack, name):
-        return None if pack is None else pack.w16(name)
-
     def _drop_p(self):
         """peft applies lora_dropout only in training mode (nn.Dropout inside every LoraLayer)."""
         return float(self.config.lora_dropout) if (self.training and self.use_lora) else 0.0
@@ -375,10 +375,11 @@ class Qwen3LoRAModel(nn.Module):
     def first_sample(self, B):
         return int(self.sample_offset) if self.sample_offset is not None else int(self.dp_rank) * int(B)
 
-    def _bits_groups(self):
-        """(input width, adapters sharing it) of the four adapter groups of a layer: q|k|v, o, gate|up, down."""
+    def _group_dims(self):
+        """(input width, output width of every adapter) of the four ADAPTER_GROUPS of a layer: q|k|v, o, gate|up, down."""
         c = self.config
-        return ((c.hidden_size, 3), (c.num_attention_heads * c.head_dim, 1), (c.hidden_size, 2), (c.intermediate_size, 1))
+        D, I, NQ, NKV = c.hidden_size, c.intermediate_size, c.num_attention_heads * c.head_dim, c.num_key_value_heads * c.head_dim
+        return ((D, (NQ, NKV, NKV)), (NQ, (D,)), (D, (I, I)), (I, (D,)))
 
     def prefetch_lora_bits(self, M, device, row0=0):
         """Generate the NEXT forward's LoRA dropout bit planes (all layers, all adapter groups) on a side stream.  The planes
@@ -398,13 +399,13 @@ class Qwen3LoRAModel(nn.Module):
         main = torch.cuda.current_stream(device)
         if self._bits_stream is None:
             self._bits_stream = torch.cuda.Stream(device=device)
-        planes = {(i, g): torch.empty((nad, M, hip.lora_bits_ld(W)), dtype=torch.uint8, device=device)
-                  for i in range(self.config.num_hidden_layers) for g, (W, nad) in enumerate(self._bits_groups())}
+        planes = {(i, g): torch.empty((len(outs), M, hip.lora_bits_ld(W)), dtype=torch.uint8, device=device)
+                  for i in range(self.config.num_hidden_layers) for g, (W, outs) in enumerate(self._group_dims())}
         # token-packed copies for the backward's token reductions (hip.lora_reduce's ring kernel), made on the side stream as well
         packed = {}
-        if M % 128 == 0 and os.environ.get("UNIREC_BITS_T", "1") != "0":      # (lab switch: 0 = no token-packed copies, the register-staged reduction)
-            packed = {(i, g): torch.empty((nad, M // 32, hip.lora_bits_t_ld(W)), dtype=torch.int32, device=device)
-                      for i in range(self.config.num_hidden_layers) for g, (W, nad) in enumerate(self._bits_groups()) if W % 64 == 0}
+        if M % 128 == 0 and switches.bits_t:
+            packed = {(i, g): torch.empty((len(outs), M // 32, hip.lora_bits_t_ld(W)), dtype=torch.int32, device=device)
+                      for i in range(self.config.num_hidden_layers) for g, (W, outs) in enumerate(self._group_dims()) if W % 64 == 0}
         self._bits_stream.wait_stream(main)
         self._generate_bits(planes, packed, self._lora_step, M, device, int(row0), p)
 
@@ -424,18 +425,18 @@ class Qwen3LoRAModel(nn.Module):
             # layers of the decoder when the Q-Former's forward is shorter than it; the token-packed copies (backward only) come last
             events = []
             for i in range(self.config.num_hidden_layers):
-                for g, (W, nad) in enumerate(self._bits_groups()):
-                    hip.lora_dropout_bits(self.lora_dropout_seed(step, i, g), p, M, W, nad, device, out=planes[(i, g)], row0=row0)
+                for g, (W, outs) in enumerate(self._group_dims()):
+                    hip.lora_dropout_bits(self.lora_dropout_seed(step, i, g), p, M, W, len(outs), device, out=planes[(i, g)], row0=row0)
                 events.append(side.record_event())
             for (i, g), bt in packed.items():
-                hip.lora_bits_transpose(planes[(i, g)], self._bits_groups()[g][0], out=bt)
+                hip.lora_bits_transpose(planes[(i, g)], self._group_dims()[g][0], out=bt)
             ev_t = side.record_event()
         self._bits_pre = {"step": step, "M": M, "planes": planes, "packed": packed, "events": events, "event_t": ev_t, "row0": int(row0), "p": p}
 
     def _prefetch_next_step(self, cur, device):
         """Called by the decoder's backward when it has consumed this step's planes: the next step's are written into the SAME buffers
         on the side stream (which first waits for the main stream to get here), under the Q-Former's backward and the optimizer."""
-        if os.environ.get("UNIREC_BITS_NEXT", "1") == "0" or not self.training:
+        if not switches.bits_next or not self.training:
             return
         if self.sample_offset is not None:
             # micro-batching / explicit shards: the next forward's first row is not this one's, so planes written here would only be
@@ -451,23 +452,21 @@ class Qwen3LoRAModel(nn.Module):
         input once (1.09 -> 1.01 ms and 1.58 -> 1.49 ms per layer at C4).  The zero blocks are written once; each step
         refreshes the diagonal blocks from the bf16 shadow with one multi-tensor copy."""
         c = self.config
-        r, NQ, NKV, I = c.lora_r, c.num_attention_heads * c.head_dim, c.num_key_value_heads * c.head_dim, c.intermediate_size
+        r, I = c.lora_r, c.intermediate_size
+        dims = self._group_dims()
         if self._bcomb is None or self._bcomb["dev"] != torch.device(device) or self._bcomb["pack"] is not pack:
-            qkv = torch.zeros((c.num_hidden_layers, NQ + 2 * NKV, 3 * r), dtype=BF16, device=device)
-            gu = torch.zeros((c.num_hidden_layers, 2 * I, 2 * r), dtype=BF16, device=device)
+            qkv, gu = (torch.zeros((c.num_hidden_layers, sum(outs), len(outs) * r), dtype=BF16, device=device) for outs in (dims[0][1], dims[2][1]))
             dst, src = [], []
             for i in range(c.num_hidden_layers):
-                lp = f"layers.{i}."
-                row = 0
-                for j, (pn, n) in enumerate((("q", NQ), ("k", NKV), ("v", NKV))):
-                    dst.append(qkv[i, row:row + n, j * r:(j + 1) * r]); src.append(pack.w16(lp + f"self_attn.{pn}_proj.lora_B.weight")); row += n
-                for j, pn in enumerate(("gate", "up")):
-                    dst.append(gu[i, j * I:(j + 1) * I, j * r:(j + 1) * r]); src.append(pack.w16(lp + f"mlp.{pn}_proj.lora_B.weight"))
+                for comb, g in ((qkv, 0), (gu, 2)):
+                    row = 0
+                    for j, (bname, n) in enumerate(zip(self._names[i][g].b, dims[g][1])):
+                        dst.append(comb[i, row:row + n, j * r:(j + 1) * r]); src.append(pack.w16(bname)); row += n
             self._bcomb = {"dev": torch.device(device), "pack": pack, "qkv": qkv, "gu": gu, "dst": dst, "src": src}
         torch._foreach_copy_(self._bcomb["dst"], self._bcomb["src"])
-        rp = self._qk_row_perm(device) if _FUSE_QK_ROPE else None
+        rp = self._qk_row_perm(device) if switches.fuse_qk_rope else None
         self._bcomb["qkvP"] = self._bcomb["qkv"].index_select(1, rp) if rp is not None else None      # rows paired like fz["qkvP"]
-        self._bcomb["guP"] = (self._bcomb["gu"].index_select(1, self._swiglu_rows(I, device)) if (_FUSE_SWIGLU_GEMM and I % 128 == 0) else None)
+        self._bcomb["guP"] = (self._bcomb["gu"].index_select(1, self._swiglu_rows(I, device)) if (switches.fuse_swiglu_gemm and I % 128 == 0) else None)
         return self._bcomb["qkv"], self._bcomb["gu"]
 
     def _lora_transposes(self, pack):
@@ -477,16 +476,13 @@ class Qwen3LoRAModel(nn.Module):
         bt = getattr(self, "_lt", None)
         if bt is None or bt[0] is not pack:
             names, srcs = [], []
-            for i in range(self.config.num_hidden_layers):
-                lp = f"layers.{i}."
-                for grp in (("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), ("self_attn.o_proj",),
-                            ("mlp.gate_proj", "mlp.up_proj"), ("mlp.down_proj",)):
-                    an = tuple(lp + g + ".lora_A.weight" for g in grp)
-                    names.append(an)
-                    srcs.append(pack.fused16(list(an)) if len(an) > 1 else pack.w16(an[0]))
-                    for g in grp:
-                        names.append(lp + g + ".lora_B.weight")
-                        srcs.append(pack.w16(lp + g + ".lora_B.weight"))
+            for groups in self._names:
+                for g in groups:
+                    names.append(g.a)
+                    srcs.append(pack.fused16(list(g.a)) if len(g.a) > 1 else pack.w16(g.a[0]))
+                    for bname in g.b:
+                        names.append(bname)
+                        srcs.append(pack.w16(bname))
             bt = (pack, names, hip.BatchedTranspose(srcs))
             self._lt = bt
         outs = bt[2].run()
@@ -514,20 +510,53 @@ class Qwen3LoRAModel(nn.Module):
         t = hip.lora_project(xin, [pack.w16(n) for n in a_names], alpha=sc / (1.0 - p), bits=bits)
         return t, bits
 
+    def _plan(self, M, S, dev, pack, fz):
+        """Every launch choice that is the same for all layers of a forward over M = B * S tokens (see _Plan)."""
+        c, sw = self.config, switches
+        D, I, hd, r = c.hidden_size, c.intermediate_size, c.head_dim, c.lora_r
+        NQ, NKV = c.num_attention_heads * hd, c.num_key_value_heads * hd
+        lora = pack is not None
+        merged = not lora or (sw.merge_proj and r == 16)
+        # q/k-norm + RoPE inside the q|k|v launch (the raw q, k are never written or re-read) when the persistent GEMM takes it
+        fuse_rope = (sw.fuse_qk_rope and hd == 128 and fz["qk_norm_fusable"] and merged and
+                     hip.gemm_qkrope_supported(M, NQ + 2 * NKV, D, 3 * r if lora else 0, S, NQ, NKV, dev))
+        swiglu = "alone"
+        if lora and not merged and sw.swiglu_fwd_fused:
+            swiglu = "up"
+        elif lora and merged and sw.fuse_swiglu_gemm and I % 128 == 0 and hip.gemm_swiglu_paired_supported(M, I, D, 2 * r, dev):
+            swiglu = "pair"
+        elif lora and sw.fuse_swiglu_lora and r == 16 and I % 128 == 0:
+            swiglu = "lora"
+        # the attention output's rows are padded by 64 columns when their length is a power of two: the kernels that stream it
+        # in 128-byte column chunks (the o_proj adapter's projection and its token reduction) otherwise keep every request in
+        # flight on the same bytes of a 4 KiB-strided row, i.e. on a few memory channels (lora_project_ring_kernel: 141 -> 104 us)
+        pad_att = sw.pad_att and (NQ & (NQ - 1)) == 0 and NQ >= 1024
+        # switches.rope_bwd_fused unset: from the roped outputs only
+        in_dq = hd == 128 and (sw.rope_bwd_fused is not False if fuse_rope else sw.rope_bwd_fused is True)
+        mlp_recompute = None if not merged else ("pair" if swiglu == "pair" else ("merged" if lora else "plain"))
+        return _Plan(merged=merged, fuse_norm=sw.fuse_norm_lora and lora and r == 16 and D == 1024, fuse_rope=fuse_rope, swiglu=swiglu,
+                     pad_att=pad_att, bits_one_event=sw.bits_one_event, mlp_recompute=mlp_recompute, rope_bwd_in_dq=in_dq,
+                     rope_k_in_dkv=sw.rope_k_fused, bits_t=sw.bits_t and M % 128 == 0)
+
     def _forward_impl(self, item_tokens16, input_ids, mask_u8, first_special_id, keep=True):
         c = self.config
         dev = input_ids.device
         fz = self._ensure_frozen(dev)
         pack = self._ensure_pack(dev)
-        bc_qkv = bc_gu = None
-        if pack is not None:
-            pack.refresh_shadow()
-            if _MERGE_PROJ and c.lora_r == 16:
-                bc_qkv, bc_gu = self._lora_bcomb(pack, dev)
         B, S = input_ids.shape
         D, I, nq, nkv, hd, r = c.hidden_size, c.intermediate_size, c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.lora_r
         NQ, NKV = nq * hd, nkv * hd
         M = B * S
+        plan = self._plan(M, S, dev, pack, fz)
+        # LoRA operands: without adapters every projection below is the same call with R2 = S2 = None
+        none = (None,) * len(fz["layers"])
+        bc_qkv = bc_gu = bc_qkvP = bc_guP = none      # per layer: block-diagonal B of the merged launches (P: rows paired like fz's qkvP / guP)
+        w16 = pack.w16 if pack is not None else (lambda name: None)
+        if pack is not None:
+            pack.refresh_shadow()
+            if plan.merged:
+                bc_qkv, bc_gu = self._lora_bcomb(pack, dev)
+                bc_qkvP, bc_guP = self._bcomb["qkvP"], self._bcomb["guP"]
         eps, sc = c.rms_norm_eps, (c.lora_alpha / c.lora_r if self.use_lora else 0.0)
         cos, sin = self._rope_tables(S, dev)
         T = item_tokens16.shape[1]
@@ -538,128 +567,92 @@ class Qwen3LoRAModel(nn.Module):
         if pdrop > 0.0:
             self._lora_step += 1
         saved = {"B": B, "S": S, "T": T, "ids": input_ids, "first": first_special_id, "mask": mask_u8, "layers": [],
-                 "pdrop": pdrop, "step": step}
+                 "pdrop": pdrop, "step": step, "plan": plan}
         row0 = self.first_sample(B) * S                # token rows that precede this shard in the global minibatch
         pre, self._bits_pre = self._bits_pre, None
         if pre is not None and not (pdrop > 0.0 and pre["step"] == step and pre["M"] == M and pre["row0"] == row0 and pack is not None):
             self._bits_pre = pre
             self._release_prefetched(dev)           # not this forward's planes: order their last writes before the blocks are reused
             pre = None
+        pre_events = None
         if pre is not None:
             saved["bits_t"] = pre.get("packed", {})                      # (layer, group) -> token-packed copy for the backward
             saved["bits_t_event"] = pre["event_t"]
             saved["bits_pre"] = pre                                      # (its buffers take the next step's planes after the backward)
             pre_events = pre["events"]                                   # planes prefetched on the side stream, one event per layer
             pre = pre["planes"]
-        else:
-            pre, pre_events = None, None
         bp = (lambda i, g: pre[(i, g)]) if pre is not None else (lambda i, g: None)
-        fuse_norm = _FUSE_NORM_LORA and pack is not None and c.lora_r == 16 and D == 1024
+
+        def lora_down(xin, i, g):
+            """(t, bits) of adapter group g of layer i on its input xin; (None, None) without adapters"""
+            if pack is None:
+                return None, None
+            return self._lora_down(xin, self._names[i][g].a, pack, sc, self.lora_dropout_seed(step, i, g), pdrop, bp(i, g), row0=row0)
+
+        def norm_lora_down(xin, w, i, g):
+            """(h, rstd, t, bits): RMSNorm and lora_down of its output, as one kernel when the plan says so"""
+            if plan.fuse_norm:      # (h is written once, never re-read by a projection kernel)
+                return self._norm_lora_down(xin, w, eps, self._names[i][g].a, pack, sc, self.lora_dropout_seed(step, i, g), pdrop, bp(i, g), row0=row0)
+            h, rstd = hip.rmsnorm_fwd(xin, w, eps)
+            return (h, rstd) + lora_down(h, i, g)      # t [M, nad * r] = s * dropout(h) A^T
+
         for i, fl in enumerate(fz["layers"]):
-            lp = f"layers.{i}."
+            nm = self._names[i]
             L = {"x": x}
             if pre_events is not None:
-                # (lab switch UNIREC_BITS_ONE_EVENT=1: wait for every layer's planes before the first layer, the former behaviour)
-                torch.cuda.current_stream(dev).wait_event(pre_events[-1] if (i == 0 and os.environ.get("UNIREC_BITS_ONE_EVENT") == "1") else pre_events[i])
-            # q/k-norm + RoPE inside the q|k|v launch (the raw q, k are never written or re-read) when the persistent GEMM takes it
-            fuse_rope = (_FUSE_QK_ROPE and hd == 128 and fl["qkvP"] is not None and fz["qk_norm_fusable"] and (pack is None or bc_qkv is not None) and
-                         hip.gemm_qkrope_supported(M, NQ + 2 * NKV, D, 3 * r if pack is not None else 0, S, NQ, NKV, dev))
-            qkv = None if fuse_rope else torch.empty((M, NQ + 2 * NKV), dtype=BF16, device=dev)
-            if fuse_norm:      # RMSNorm + the q|k|v adapters' down projection in one pass over x (h is written once, never re-read by a projection kernel)
-                h, rstd1, t_qkv, L["bits_qkv"] = self._norm_lora_down(x, fl["ln1"], eps, [lp + f"self_attn.{p}_proj.lora_A.weight" for p in "qkv"],
-                                                                      pack, sc, self.lora_dropout_seed(step, i, 0), pdrop, bp(i, 0), row0=row0)
-            else:
-                h, rstd1 = hip.rmsnorm_fwd(x, fl["ln1"], eps)
-            if pack is not None:
-                if not fuse_norm:
-                    t_qkv, L["bits_qkv"] = self._lora_down(h, [lp + f"self_attn.{p}_proj.lora_A.weight" for p in "qkv"], pack, sc,
-                                                           self.lora_dropout_seed(step, i, 0), pdrop, bp(i, 0), row0=row0)     # [M,3r] = s * dropout(h) A^T
-                if fuse_rope:
-                    q_r, k_r, v2, rstd_qk = hip.gemm_qkv_rope(h, fl["qkvP"], fl["qn"], fl["kn"], cos, sin, S, NQ, NKV, eps, R2=t_qkv, S2=self._bcomb["qkvP"][i])
-                elif bc_qkv is not None:
-                    hip.gemm(h, fl["qkv"], out=qkv, R2=t_qkv, S2=bc_qkv[i])        # one launch, block-diagonal B
-                else:
-                    col = 0
-                    for j, (p, n) in enumerate((("q", NQ), ("k", NKV), ("v", NKV))):
-                        hip.gemm(h, fl["qkv"][col:col + n], out=qkv[:, col:col + n], R2=t_qkv[:, j * r:(j + 1) * r],
-                                 S2=pack.w16(lp + f"self_attn.{p}_proj.lora_B.weight"))
-                        col += n
-                L["t_qkv"] = t_qkv
-            elif fuse_rope:
-                q_r, k_r, v2, rstd_qk = hip.gemm_qkv_rope(h, fl["qkvP"], fl["qn"], fl["kn"], cos, sin, S, NQ, NKV, eps)
-            else:
-                hip.gemm(h, fl["qkv"], out=qkv)
-            if fuse_rope:
+                torch.cuda.current_stream(dev).wait_event(pre_events[-1] if (i == 0 and plan.bits_one_event) else pre_events[i])
+            qkv = None if plan.fuse_rope else torch.empty((M, NQ + 2 * NKV), dtype=BF16, device=dev)
+            h, rstd1, t_qkv, L["bits_qkv"] = norm_lora_down(x, fl["ln1"], i, 0)
+            if plan.fuse_rope:
+                q_r, k_r, v2, rstd_qk = hip.gemm_qkv_rope(h, fl["qkvP"], fl["qn"], fl["kn"], cos, sin, S, NQ, NKV, eps, R2=t_qkv, S2=bc_qkvP[i])
                 v4 = v2.view(B, S, nkv, hd)
                 L.update(q_r=q_r, k_r=k_r, rstd_qk=rstd_qk)
             else:
+                if plan.merged:
+                    hip.gemm(h, fl["qkv"], out=qkv, R2=t_qkv, S2=bc_qkv[i])        # one launch, block-diagonal B
+                else:
+                    col = 0
+                    for j, (bname, n) in enumerate(zip(nm[0].b, (NQ, NKV, NKV))):
+                        hip.gemm(h, fl["qkv"][col:col + n], out=qkv[:, col:col + n], R2=t_qkv[:, j * r:(j + 1) * r], S2=w16(bname))
+                        col += n
                 q_r, k_r = hip.qknorm_rope_fwd(qkv, fl["qn"], fl["kn"], cos, sin, S, nq, nkv, hd, eps)
                 v4 = qkv[:, NQ + NKV:].view(B, S, nkv, hd)
-            # the attention output's rows are padded by 64 columns when their length is a power of two: the kernels that stream it
-            # in 128-byte column chunks (the o_proj adapter's projection and its token reduction) otherwise keep every request in
-            # flight on the same bytes of a 4 KiB-strided row, i.e. on a few memory channels (lora_project_ring_kernel: 141 -> 104 us)
-            att_out = None
-            if (NQ & (NQ - 1)) == 0 and NQ >= 1024 and os.environ.get("UNIREC_PAD_ATT", "1") != "0":
-                att_out = torch.empty((M, NQ + 64), dtype=BF16, device=dev)[:, :NQ].view(B, S, nq, hd)
+            att_out = torch.empty((M, NQ + 64), dtype=BF16, device=dev)[:, :NQ].view(B, S, nq, hd) if plan.pad_att else None
             att, actx = hip.attn_fwd(q_r.view(B, S, nq, hd), k_r.view(B, S, nkv, hd), v4, causal=True, key_mask=mask_u8, out=att_out)
             att2 = att.view(M, NQ)
-            if pack is not None:
-                t_o, L["bits_o"] = self._lora_down(att2, [lp + "self_attn.o_proj.lora_A.weight"], pack, sc, self.lora_dropout_seed(step, i, 1), pdrop, bp(i, 1), row0=row0)
-                x2 = hip.gemm(att2, fl["o"], residual=x, R2=t_o, S2=pack.w16(lp + "self_attn.o_proj.lora_B.weight"))
-                L["t_o"] = t_o
-            else:
-                x2 = hip.gemm(att2, fl["o"], residual=x)
+            t_o, L["bits_o"] = lora_down(att2, i, 1)
+            x2 = hip.gemm(att2, fl["o"], residual=x, R2=t_o, S2=w16(nm[1].b[0]))
             gu = torch.empty((M, 2 * I), dtype=BF16, device=dev)
-            if fuse_norm:
-                h2, rstd2, t_gu, L["bits_gu"] = self._norm_lora_down(x2, fl["ln2"], eps, [lp + "mlp.gate_proj.lora_A.weight", lp + "mlp.up_proj.lora_A.weight"],
-                                                                     pack, sc, self.lora_dropout_seed(step, i, 2), pdrop, bp(i, 2), row0=row0)
+            h2, rstd2, t_gu, L["bits_gu"] = norm_lora_down(x2, fl["ln2"], i, 2)
+            act = torch.empty((M, I), dtype=BF16, device=dev) if plan.swiglu in ("pair", "up") else None
+            if plan.swiglu == "pair":            # ONE launch: gate|up (standard order, for the backward) and act = silu(gate) * up from its registers
+                hip.gemm(h2, fl["guP"], out=gu, R2=t_gu, S2=bc_guP[i], swiglu_paired=act)
+            elif plan.merged:
+                hip.gemm(h2, fl["gu"], out=gu, R2=t_gu, S2=bc_gu[i])            # one launch, block-diagonal B
             else:
-                h2, rstd2 = hip.rmsnorm_fwd(x2, fl["ln2"], eps)
-            if pack is not None:
-                if not fuse_norm:
-                    t_gu, L["bits_gu"] = self._lora_down(h2, [lp + "mlp.gate_proj.lora_A.weight", lp + "mlp.up_proj.lora_A.weight"], pack, sc,
-                                                         self.lora_dropout_seed(step, i, 2), pdrop, bp(i, 2), row0=row0)
-                # gate first; the up projection's epilogue then reads the gate tile and writes act = silu(gate) * up beside up
-                fused = _FUSE_SWIGLU_FWD and bc_gu is None
-                act = torch.empty((M, I), dtype=BF16, device=dev) if fused else None
-                pair = (_FUSE_SWIGLU_GEMM and bc_gu is not None and fl["guP"] is not None and self._bcomb.get("guP") is not None and
-                        hip.gemm_swiglu_paired_supported(M, I, D, 2 * r, dev))
-                if pair:            # ONE launch: gate|up (standard order, for the backward) and act = silu(gate) * up from its registers
-                    act = torch.empty((M, I), dtype=BF16, device=dev)
-                    hip.gemm(h2, fl["guP"], out=gu, R2=t_gu, S2=self._bcomb["guP"][i], swiglu_paired=act)
-                elif bc_gu is not None:
-                    hip.gemm(h2, fl["gu"], out=gu, R2=t_gu, S2=bc_gu[i])            # one launch, block-diagonal B
-                for j, p in enumerate(("gate", "up") if bc_gu is None else ()):
-                    hip.gemm(h2, fl["gu"][j * I:(j + 1) * I], out=gu[:, j * I:(j + 1) * I], R2=t_gu[:, j * r:(j + 1) * r],
-                             S2=pack.w16(lp + f"mlp.{p}_proj.lora_B.weight"), swiglu_fwd=(gu[:, :I], act) if (j == 1 and fused) else None)
-                fuse_act = _FUSE_SWIGLU_LORA and not fused and not pair and r == 16 and I % 128 == 0
-                if fuse_act:      # act and t_d = s * dropout(act) A_d^T from one pass over gate|up (ur_swiglu_lora_fwd)
-                    bits_d = bp(i, 3)
-                    if bits_d is None and pdrop > 0.0:
-                        bits_d = hip.lora_dropout_bits(self.lora_dropout_seed(step, i, 3), pdrop, M, I, 1, dev, row0=row0)
-                    act, t_d = hip.swiglu_lora_fwd(gu, I, pack.w16(lp + "mlp.down_proj.lora_A.weight"), alpha=sc / (1.0 - pdrop), bits=bits_d)
-                    L["bits_d"] = bits_d
-                elif not fused and not pair:
+                # gate first; under "up" the up projection's epilogue then reads the gate tile and writes act = silu(gate) * up beside up
+                for j, bname in enumerate(nm[2].b):
+                    hip.gemm(h2, fl["gu"][j * I:(j + 1) * I], out=gu[:, j * I:(j + 1) * I], R2=t_gu[:, j * r:(j + 1) * r], S2=w16(bname),
+                             swiglu_fwd=(gu[:, :I], act) if (j == 1 and plan.swiglu == "up") else None)
+            if plan.swiglu == "lora":      # act and t_d = s * dropout(act) A_d^T from one pass over gate|up (ur_swiglu_lora_fwd)
+                bits_d = bp(i, 3)
+                if bits_d is None and pdrop > 0.0:
+                    bits_d = hip.lora_dropout_bits(self.lora_dropout_seed(step, i, 3), pdrop, M, I, 1, dev, row0=row0)
+                act, t_d = hip.swiglu_lora_fwd(gu, I, w16(nm[3].a[0]), alpha=sc / (1.0 - pdrop), bits=bits_d)
+                L["bits_d"] = bits_d
+            else:
+                if plan.swiglu == "alone":
                     act = hip.swiglu_fwd(gu, I)
-                L["t_gu"] = t_gu
-            else:
-                hip.gemm(h2, fl["gu"], out=gu)
-                act = hip.swiglu_fwd(gu, I)
-            if pack is not None:
-                if not fuse_act:
-                    t_d, L["bits_d"] = self._lora_down(act, [lp + "mlp.down_proj.lora_A.weight"], pack, sc, self.lora_dropout_seed(step, i, 3), pdrop, bp(i, 3), row0=row0)
-                x3 = hip.gemm(act, fl["d"], residual=x2, R2=t_d, S2=pack.w16(lp + "mlp.down_proj.lora_B.weight"))
-                L["t_d"] = t_d
-            else:
-                x3 = hip.gemm(act, fl["d"], residual=x2)
-            L.update(rstd1=rstd1, qkv=qkv, actx=actx, att=att2, x2=x2, rstd2=rstd2, gu=gu, act=act)      # (qkv is None under the fused q/k-norm + RoPE epilogue)
+                t_d, L["bits_d"] = lora_down(act, i, 3)
+            x3 = hip.gemm(act, fl["d"], residual=x2, R2=t_d, S2=w16(nm[3].b[0]))
+            L.update(rstd1=rstd1, qkv=qkv, actx=actx, att=att2, x2=x2, rstd2=rstd2, gu=gu, act=act,      # (qkv is None under the fused q/k-norm + RoPE epilogue)
+                     t_qkv=t_qkv, t_o=t_o, t_gu=t_gu, t_d=t_d)
             # (recompute_mlp = True: every layer; an int k: layers 0 .. k - 1 only -- as much memory as the shape needs, no more recomputation than that)
             if self.recompute_mlp and keep and (self.recompute_mlp is True or i < int(self.recompute_mlp)):
                 # memory for time: gate|up and act (2 x [M, 3I] bf16 over the stack: 67 GB at C4) are dropped and rebuilt in the
                 # backward by the very launch that made them (bit-identical: same kernel, same operands).
-                how = "pair" if (pack is not None and pair) else ("merged" if (pack is not None and bc_gu is not None and not fused) else ("plain" if pack is None else None))
-                if how is not None:
-                    L.update(gu=None, act=None, mlp_recompute=how)
+                if plan.mlp_recompute is not None:
+                    L.update(gu=None, act=None, mlp_recompute=plan.mlp_recompute)
             if self.keep_norm_outputs:       # 2 x [M,D] bf16 per layer (15 GB at C4) instead of two RMSNorm recomputes
                 L.update(h=h, h2=h2)
             if keep:
@@ -676,6 +669,7 @@ class Qwen3LoRAModel(nn.Module):
         c = self.config
         fz = self._frozen
         pack = self._pack if self.use_lora else None
+        plan = saved["plan"]
         B, S, T = saved["B"], saved["S"], saved["T"]
         D, I, nq, nkv, hd, r = c.hidden_size, c.intermediate_size, c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.lora_r
         NQ, NKV = nq * hd, nkv * hd
@@ -693,47 +687,51 @@ class Qwen3LoRAModel(nn.Module):
         packed_bits = saved.get("bits_t", {})
         if saved.get("bits_t_event") is not None:
             torch.cuda.current_stream(dev).wait_event(saved["bits_t_event"])
+        # per adapter group: (first output column, width) of every adapter
+        out_cols = [[(sum(outs[:j]), n) for j, n in enumerate(outs)] for _, outs in self._group_dims()]
 
-        def lora_grads(dy, t, xin, a_names, b_specs, bits, group=None):
-            """dB_p = dy_p^T t_p ; tb = s * dy B ; dA_p = tb_p^T dropout_p(x).  Returns tb [M, len(b)*r] (bf16).
-            group = (layer, adapter group): the key of the prefetched token-packed flags."""
-            nb = len(b_specs)
-            touched.extend([b for b, _, _ in b_specs] + list(a_names))
+        def lora_grads(dy, t, xin, i, g, bits):
+            """Adapter group g of layer i: dB_p = dy_p^T t_p ; tb = s * dy B ; dA_p = tb_p^T dropout_p(x).  Returns tb [M, nad * r] (bf16)."""
+            a_names, bnames, cols = self._names[i][g].a, self._names[i][g].b, out_cols[g]
+            nb = len(bnames)
+            touched.extend(bnames + a_names)
+            gA = pack.fusedg(a_names) if nb > 1 else pack.g32(a_names[0])
             if r != 16:           # generic tiles (no dropout: _lora_down refused it)
                 tb = torch.empty((M, nb * r), dtype=BF16, device=dev)
-                for j, (bname, c0, n) in enumerate(b_specs):
+                for j, (bname, (c0, n)) in enumerate(zip(bnames, cols)):
                     dyp = dy[:, c0:c0 + n]
                     hip.gemm(dyp, t[:, j * r:(j + 1) * r], r_kcontig=False, s_kcontig=False, out=pack.g32(bname), split_k=_split_k(M, n, r))
                     hip.gemm(dyp, pack.w16(bname), s_kcontig=False, out=tb[:, j * r:(j + 1) * r], alpha=sc)
-                gA = pack.fusedg(a_names) if len(a_names) > 1 else pack.g32(a_names[0])
                 hip.gemm(tb, xin, r_kcontig=False, s_kcontig=False, out=gA, split_k=_split_k(M, nb * r, xin.shape[1]))
                 return tb
-            cols = [(c0, n) for _, c0, n in b_specs]
-            bnames = [b for b, _, _ in b_specs]
             gB = pack.fusedg(bnames) if nb > 1 else pack.g32(bnames[0])            # [sum n, r]: adapter ranges in order
             tb = hip.lora_bgrad(dy, t, [lt[b] for b in bnames], cols, gB, alpha=sc)     # dB and tb, dy read once
-            gA = pack.fusedg(a_names) if len(a_names) > 1 else pack.g32(a_names[0])
-            bits_t = packed_bits.get(group) if bits is not None else None
-            if bits is not None and bits_t is None and M % 128 == 0 and xin.shape[1] % 64 == 0 and os.environ.get("UNIREC_BITS_T", "1") != "0":
+            bits_t = packed_bits.get((i, g)) if bits is not None else None             # the prefetched token-packed flags
+            if bits is not None and bits_t is None and plan.bits_t and xin.shape[1] % 64 == 0:
                 bits_t = hip.lora_bits_transpose(bits, xin.shape[1])          # (no prefetch this step: made here)
-            hip.lora_reduce(xin, tb, gA, nad=len(a_names), alpha=1.0 / (1.0 - pdrop), bits=bits, bits_t=bits_t)
+            hip.lora_reduce(xin, tb, gA, nad=nb, alpha=1.0 / (1.0 - pdrop), bits=bits, bits_t=bits_t)
             return tb
 
-        def dx_gemm(dy, wT, tb, a_names, bits, swiglu=None):
-            """dx = dy W + sum_j mask_j * (tb_j A_j): the adapters' part joins the main reduction when there is no
-            dropout, and is a masked rank-r epilogue (ur_gemm drop_bits) when there is.  swiglu = (gu, dgu): dx is d(act)
-            and leaves the GEMM as dgate | dup (SwiGLU backward in the epilogue: d(act) is never stored)."""
-            if lt is not None:
-                AT = lt[tuple(a_names)]
-            else:
-                AT = hip.transpose_bf16(pack.fused16(a_names) if len(a_names) > 1 else pack.w16(a_names[0]))
-            drop = (bits, pdrop, r) if bits is not None else None
+        def proj_bwd(dy, wT, xin, i, g, L, swiglu=None):
+            """Backward of the projections of adapter group g of layer i (input xin, output gradient dy): the adapters' gradients
+            (lora_grads), then dx = dy W + sum_j mask_j * (tb_j A_j): the adapters' part joins the main reduction when there is no
+            dropout, and is a masked rank-r epilogue (ur_gemm drop_bits) when there is.  Without adapters: dx = dy W.
+            swiglu = (gu, dgu): dx is d(act) and leaves the GEMM as dgate | dup (SwiGLU backward in the epilogue: d(act) is never stored)."""
+            tb = AT = drop = None
+            if pack is not None:
+                key, a_names = ADAPTER_GROUPS[g][0], self._names[i][g].a
+                bits = L["bits_" + key]
+                tb = lora_grads(dy, L["t_" + key], xin, i, g, bits)
+                if lt is not None:
+                    AT = lt[a_names]
+                else:
+                    AT = hip.transpose_bf16(pack.fused16(a_names) if len(a_names) > 1 else pack.w16(a_names[0]))
+                drop = (bits, pdrop, r) if bits is not None else None
             return hip.gemm(dy, wT, R2=tb, S2=AT, drop=drop, swiglu_bwd=swiglu)
 
         scratch = {}
         for i in reversed(range(len(fz["layers"]))):
             fl, L = fz["layers"][i], saved["layers"][i]
-            lp = f"layers.{i}."
             x, x2, gu, qkv = L["x"], L["x2"], L["gu"], L["qkv"]
             # ---- MLP: x3 = x2 + down(silu(gate) * up)
             act = L["act"]
@@ -743,76 +741,44 @@ class Qwen3LoRAModel(nn.Module):
                     scratch["gu"] = torch.empty((M, 2 * I), dtype=BF16, device=dev)
                     scratch["act"] = torch.empty((M, I), dtype=BF16, device=dev)
                 gu, act = scratch["gu"], scratch["act"]
-                how = L["mlp_recompute"]
-                if how == "pair":
+                if L["mlp_recompute"] == "pair":
                     hip.gemm(h2, fl["guP"], out=gu, R2=L["t_gu"], S2=self._bcomb["guP"][i], swiglu_paired=act)
-                else:
-                    if how == "merged":
-                        hip.gemm(h2, fl["gu"], out=gu, R2=L["t_gu"], S2=self._bcomb["gu"][i])
-                    else:
-                        hip.gemm(h2, fl["gu"], out=gu)
+                else:            # "merged" / "plain" (no adapters)
+                    hip.gemm(h2, fl["gu"], out=gu, R2=L["t_gu"], S2=None if pack is None else self._bcomb["gu"][i])
                     hip.swiglu_fwd(gu, I, out=act)
             dgu = torch.empty_like(gu)
-            if pack is not None:
-                tb = lora_grads(dx, L["t_d"], act, [lp + "mlp.down_proj.lora_A.weight"], [(lp + "mlp.down_proj.lora_B.weight", 0, D)], L["bits_d"], group=(i, 3))
-                dx_gemm(dx, fl["dT"], tb, [lp + "mlp.down_proj.lora_A.weight"], L["bits_d"], swiglu=(gu, dgu))
-            else:
-                hip.gemm(dx, fl["dT"], swiglu_bwd=(gu, dgu))
-            if pack is not None:
-                a_names = [lp + "mlp.gate_proj.lora_A.weight", lp + "mlp.up_proj.lora_A.weight"]
-                tb = lora_grads(dgu, L["t_gu"], h2, a_names, [(lp + "mlp.gate_proj.lora_B.weight", 0, I), (lp + "mlp.up_proj.lora_B.weight", I, I)], L["bits_gu"], group=(i, 2))
-                dh2 = dx_gemm(dgu, fl["guT"], tb, a_names, L["bits_gu"])
-            else:
-                dh2 = hip.gemm(dgu, fl["guT"])
+            proj_bwd(dx, fl["dT"], act, i, 3, L, swiglu=(gu, dgu))
+            dh2 = proj_bwd(dgu, fl["guT"], h2, i, 2, L)
             dx2 = hip.rmsnorm_bwd(dh2, x2, fl["ln2"], L["rstd2"], add=dx)
             # ---- attention: x2 = x + o(attn)
-            att = L["att"]
-            if pack is not None:
-                tb = lora_grads(dx2, L["t_o"], att, [lp + "self_attn.o_proj.lora_A.weight"], [(lp + "self_attn.o_proj.lora_B.weight", 0, D)], L["bits_o"], group=(i, 1))
-                datt = dx_gemm(dx2, fl["oT"], tb, [lp + "self_attn.o_proj.lora_A.weight"], L["bits_o"])
-            else:
-                datt = hip.gemm(dx2, fl["oT"])
+            datt = proj_bwd(dx2, fl["oT"], L["att"], i, 1, L)
             dqkv = torch.empty((M, NQ + 2 * NKV), dtype=BF16, device=dev)
             dk_r = torch.empty((M, NKV), dtype=BF16, device=dev)
-            if "rstd_qk" in L and hd == 128 and os.environ.get("UNIREC_ROPE_BWD_FUSED", "1") != "0":
+            datt4, dk4, dv4 = datt.view(B, S, nq, hd), dk_r.view(B, S, nkv, hd), dqkv[:, NQ + NKV:].view(B, S, nkv, hd)
+            if not plan.rope_bwd_in_dq:      # the q/k-norm + RoPE backward as its own pass over dq | dk
+                dq_r = torch.empty((M, NQ), dtype=BF16, device=dev)
+                hip.attn_bwd(L["actx"], datt4, dq=dq_r.view(B, S, nq, hd), dk=dk4, dv=dv4)
+                if plan.fuse_rope:
+                    hip.qknorm_rope_bwd_roped(dq_r, dk_r, L["q_r"], L["k_r"], L["rstd_qk"], fl["qn"], fl["kn"], cos, sin, dqkv, S, nq, nkv, hd)
+                else:
+                    hip.qknorm_rope_bwd(dq_r, dk_r, qkv, fl["qn"], fl["kn"], cos, sin, dqkv, S, nq, nkv, hd, eps)
+            elif plan.fuse_rope:
                 # the forward ran q/k-norm + RoPE in the q|k|v launch: no raw q, k exist; the rows are recovered from the roped outputs.
                 # The q heads' backward rides in the dQ kernel's store (its lanes own whole rows of q_r, which it has just read as
                 # its q operand): dq never makes the round trip through HBM.
                 # (the k heads' likewise in the dK/dV kernel's store; dk_r is scratch for the shapes the generated kernels do not take)
-                k_in_call = os.environ.get("UNIREC_ROPE_K_FUSED", "1") != "0"      # test / lab switch: 0 = the k heads by a separate launch
-                hip.attn_bwd(L["actx"], datt.view(B, S, nq, hd), dk=dk_r.view(B, S, nkv, hd), dv=dqkv[:, NQ + NKV:].view(B, S, nkv, hd),
-                             rope_q=(L["q_r"], fl["qn"], cos, sin, eps, dqkv[:, :NQ]), rope_rstd=(L["rstd_qk"], 0),
-                             rope_k=(L["k_r"], fl["kn"], nq, dqkv[:, NQ:NQ + NKV]) if k_in_call else None)
-                if not k_in_call:
+                hip.attn_bwd(L["actx"], datt4, dk=dk4, dv=dv4, rope_q=(L["q_r"], fl["qn"], cos, sin, eps, dqkv[:, :NQ]), rope_rstd=(L["rstd_qk"], 0),
+                             rope_k=(L["k_r"], fl["kn"], nq, dqkv[:, NQ:NQ + NKV]) if plan.rope_k_in_dkv else None)
+                if not plan.rope_k_in_dkv:
                     hip.qknorm_rope_bwd_roped_k(dk_r, L["k_r"], L["rstd_qk"], nq, fl["kn"], cos, sin, dqkv[:, NQ:NQ + NKV], S, nkv, hd)
-            elif "rstd_qk" in L:
-                dq_r = torch.empty((M, NQ), dtype=BF16, device=dev)
-                hip.attn_bwd(L["actx"], datt.view(B, S, nq, hd), dq=dq_r.view(B, S, nq, hd), dk=dk_r.view(B, S, nkv, hd),
-                             dv=dqkv[:, NQ + NKV:].view(B, S, nkv, hd))
-                hip.qknorm_rope_bwd_roped(dq_r, dk_r, L["q_r"], L["k_r"], L["rstd_qk"], fl["qn"], fl["kn"], cos, sin, dqkv, S, nq, nkv, hd)
-            elif hd == 128 and os.environ.get("UNIREC_ROPE_BWD_FUSED", "0") == "1":
-                # UNIREC_ROPE_BWD_FUSED=1: the dQ kernel carries the q-norm + RoPE backward of the q heads (its lanes own whole
-                # rows) and writes straight into dqkv; the stand-alone kernel is left with the k heads (nq = 0, operands offset
-                # to the k columns).  Parity-tested; measured neutral on the joint step (115.7 vs 115.9 seq/s, alternating
-                # same-box runs: the ~1000 vector instructions per wave in the dQ kernel's store cost what the 4 saved
-                # activation passes return), so the separate launch stays the default.
-                hip.attn_bwd(L["actx"], datt.view(B, S, nq, hd), dk=dk_r.view(B, S, nkv, hd), dv=dqkv[:, NQ + NKV:].view(B, S, nkv, hd),
-                             rope_q=(qkv[:, :NQ], fl["qn"], cos, sin, eps, dqkv[:, :NQ]))
+            else:
+                # from the RAW projection (switches.rope_bwd_fused = True): the dQ kernel carries the q-norm + RoPE backward of the q
+                # heads (its lanes own whole rows) and writes straight into dqkv; the stand-alone kernel is left with the k heads
+                # (nq = 0, operands offset to the k columns)
+                hip.attn_bwd(L["actx"], datt4, dk=dk4, dv=dv4, rope_q=(qkv[:, :NQ], fl["qn"], cos, sin, eps, dqkv[:, :NQ]))
                 hip.qknorm_rope_bwd(dk_r, dk_r, qkv[:, NQ:], fl["qn"], fl["kn"], cos, sin, dqkv[:, NQ:], S, 0, nkv, hd, eps)
-            else:
-                dq_r = torch.empty((M, NQ), dtype=BF16, device=dev)
-                hip.attn_bwd(L["actx"], datt.view(B, S, nq, hd), dq=dq_r.view(B, S, nq, hd), dk=dk_r.view(B, S, nkv, hd),
-                             dv=dqkv[:, NQ + NKV:].view(B, S, nkv, hd))
-                hip.qknorm_rope_bwd(dq_r, dk_r, qkv, fl["qn"], fl["kn"], cos, sin, dqkv, S, nq, nkv, hd, eps)
             h = L["h"] if "h" in L else hip.rmsnorm_fwd(x, fl["ln1"], eps)[0]              # kept, or recomputed
-            if pack is not None:
-                a_names = [lp + f"self_attn.{p}_proj.lora_A.weight" for p in "qkv"]
-                specs = [(lp + "self_attn.q_proj.lora_B.weight", 0, NQ), (lp + "self_attn.k_proj.lora_B.weight", NQ, NKV),
-                         (lp + "self_attn.v_proj.lora_B.weight", NQ + NKV, NKV)]
-                tb = lora_grads(dqkv, L["t_qkv"], h, a_names, specs, L["bits_qkv"], group=(i, 0))
-                dh = dx_gemm(dqkv, fl["qkvT"], tb, a_names, L["bits_qkv"])
-            else:
-                dh = hip.gemm(dqkv, fl["qkvT"])
+            dh = proj_bwd(dqkv, fl["qkvT"], h, i, 0, L)
             dx = hip.rmsnorm_bwd(dh, x, fl["ln1"], L["rstd1"], add=dx2)
             L.clear()
             if self.grad_ready_hook is not None:      # dp.GradBuckets: layer i's LoRA gradients are final
