@@ -350,3 +350,343 @@ def geo_features(coords):
 def context_mlp1(feat, W1, b1):
     """gelu(b1 + W1 feat) in float64 over the given features: [n, H2]."""
     return gelu(feat.to(F64) @ W1.to(F64).t() + b1.to(F64))
+
+
+# ---- fused attention (include/unirec_hip.h: ur_attn_fwd / ur_attn_bwd) -----------------------------------------------------
+# Tensors use the ABI's layout: q, o, dout, dq [B, Sq, nq, hd]; k, v, dk, dv [B, Sk, nkv, hd]; key_mask [B, Sk] (1 = attend) or None;
+# keep [B, nq, Sq, Sk] (0 / 1: oracle/dropout_ref.attn_keep) or None.  Probabilities / bounds on logits are [B, nq, Sq, Sk].
+U_BF16 = 2.0 ** -8                  # bf16 unit roundoff as the bounds use it: the spacing of 8 significant bits (round-to-nearest costs half)
+F32_SLACK = 2.0 ** -20              # what assert_f32_close grants f32 arithmetic
+F32_MIN = float(torch.finfo(torch.float32).min)
+LOG2E = 1.4426950408889634
+
+
+def _bf(x):
+    """round to bfloat16 (nearest even), keep the dtype"""
+    return x.to(torch.bfloat16).to(x.dtype)
+
+
+def _bh(x, dtype):
+    return torch.as_tensor(x).detach().to("cpu").to(dtype).permute(0, 2, 1, 3)           # [B, heads, S, hd]
+
+
+def _kv_to_q(x, rep):
+    return x.repeat_interleave(rep, dim=1)                       # kv head of query head h = h // rep
+
+
+def _q_to_kv(x, rep):
+    B, nq, S, D = x.shape
+    return x.reshape(B, nq // rep, rep, S, D).sum(2)             # dk / dv of a kv head: the sum over its query heads
+
+
+def attention_allowed(key_mask, causal, B, Sq, Sk):
+    """(ok [B, 1, Sq, Sk] bool: the keys a row's softmax runs over, live [B, 1, Sq]: rows with at least one allowed key).
+    Non-causal (additive finfo(float32).min): a row without an allowed key is the uniform softmax over ALL Sk keys -- ok is all True there.
+    Causal (SDPA): allowed = causal AND key mask; a row without an allowed key stays empty (o = 0, zero gradients)."""
+    ok = torch.ones(B, 1, Sq, Sk, dtype=torch.bool)
+    if key_mask is not None:
+        ok = ok & torch.as_tensor(key_mask).cpu().bool()[:, None, None, :]
+    if causal:
+        ok = ok & torch.tril(torch.ones(Sq, Sk, dtype=torch.bool))[None, None]
+    live = ok.any(-1)
+    if not causal:
+        ok = ok | ~live[..., None]
+    return ok, live
+
+
+def _attn_probs(qh, kh, ok, live, causal, scale):
+    """P [B, nq, Sq, Sk] and lse [B, nq, Sq] of the masked, scaled logits (kh already expanded to the query heads).  A non-causal row
+    without an allowed key has every logit EQUAL (finfo.min absorbs the score): uniform, lse = finfo.min + ln Sk."""
+    s = (qh @ kh.transpose(-1, -2)) * scale
+    if not causal:
+        s = torch.where(live[..., None], s, torch.zeros_like(s))
+    s = s.masked_fill(~ok, float("-inf"))
+    m = s.amax(-1, keepdim=True)
+    m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+    e = torch.exp(s - m)
+    l = e.sum(-1, keepdim=True)
+    P = torch.where(l > 0, e / l.clamp_min(1e-300), torch.zeros_like(e))
+    lse = (m + torch.log(l)).squeeze(-1)
+    if not causal:
+        lse = torch.where(live.expand_as(lse), lse, torch.full_like(lse, F32_MIN) + math.log(s.shape[-1]))
+    return P, lse
+
+
+def _keep_scale(keep, p, dtype):
+    if keep is None:
+        return None
+    return torch.as_tensor(keep).cpu().to(dtype) / (1.0 - p)
+
+
+def attention_fwd(q, k, v, key_mask, causal, scale, keep=None, p=0.0, dtype=F64):
+    """(o [B, Sq, nq, hd], P [B, nq, Sq, Sk] BEFORE dropout, lse [B, nq, Sq] = ln sum exp of the allowed scaled logits;
+    -inf on a causal row without an allowed key).  o = (P * keep / (1 - p)) V."""
+    qh, kh, vh = _bh(q, dtype), _bh(k, dtype), _bh(v, dtype)
+    rep = qh.shape[1] // kh.shape[1]
+    ok, live = attention_allowed(key_mask, causal, qh.shape[0], qh.shape[2], kh.shape[2])
+    P, lse = _attn_probs(qh, _kv_to_q(kh, rep), ok, live, causal, scale)
+    ks = _keep_scale(keep, p, dtype)
+    Pt = P if ks is None else P * ks
+    return (Pt @ _kv_to_q(vh, rep)).permute(0, 2, 1, 3), P, lse
+
+
+def attention_bwd(q, k, v, key_mask, causal, scale, dout, keep=None, p=0.0, dtype=F64):
+    """(dq, dk, dv) written out: dP = dO V^T (masked / scaled like P under dropout), delta = rowsum(dO * O), dS = P * (dP - delta),
+    dQ = scale dS K, dK = scale dS^T Q, dV = (P keep / (1 - p))^T dO; dk / dv of a kv head sum over its query heads."""
+    qh, kh, vh, doh = _bh(q, dtype), _bh(k, dtype), _bh(v, dtype), _bh(dout, dtype)
+    rep = qh.shape[1] // kh.shape[1]
+    kq, vq = _kv_to_q(kh, rep), _kv_to_q(vh, rep)
+    ok, live = attention_allowed(key_mask, causal, qh.shape[0], qh.shape[2], kh.shape[2])
+    P, _ = _attn_probs(qh, kq, ok, live, causal, scale)
+    ks = _keep_scale(keep, p, dtype)
+    Pt = P if ks is None else P * ks
+    o = Pt @ vq
+    dP = doh @ vq.transpose(-1, -2)
+    if ks is not None:
+        dP = dP * ks
+    delta = (doh * o).sum(-1, keepdim=True)
+    dS = P * (dP - delta)
+    dq = scale * (dS @ kq)
+    dk = _q_to_kv(scale * (dS.transpose(-1, -2) @ qh), rep)
+    dv = _q_to_kv(Pt.transpose(-1, -2) @ doh, rep)
+    return dq.permute(0, 2, 1, 3), dk.permute(0, 2, 1, 3), dv.permute(0, 2, 1, 3)
+
+
+def attention_bounds(q, k, v, key_mask, causal, scale, dout, keep=None, p=0.0, qk_rounded=False):
+    """The magnitudes A of the a-priori running-error bound |got - ref| <= (U_BF16 + F32_SLACK) * A, one term per point where the
+    kernel path rounds to bf16 (docs/lab_notes.md, "Element-wise float64 tests: attention"), from the float64 reference's own
+    quantities:
+        A_o  = Pt |V| + |o|                                     (Pt = P keep / (1 - p) rounded for the PV product; o rounded at the store)
+        A_dv = Pt^T |dO| + |dv|
+        A_dS = P (2 |dPt - delta| + rowsum(|dO| (|o| + A_o)))    (dS rounded for its two products; delta is formed from the bf16 o)
+        A_dq = scale A_dS |K| + |dq|,   A_dk = scale A_dS^T |Q| + |dk|
+    qk_rounded (the generated causal head_dim-128 kernels round q * scale * log2 e, resp. k * scale * log2 e, to bf16 once more): every
+    logit moves by at most u * E, E = scale |q| . |k|, hence P by at most u * A_P, A_P = P (E + rowsum(P E)) to first order, and lse by
+    at most u * rowsum(P E); A_o, A_dv and A_dS receive the A_P term.  Returns a dict of A_o, A_dq, A_dk, A_dv (ABI layout) and
+    A_lse [B, nq, Sq]."""
+    qh, kh, vh, doh = _bh(q, F64), _bh(k, F64), _bh(v, F64), _bh(dout, F64)
+    rep = qh.shape[1] // kh.shape[1]
+    kq, vq = _kv_to_q(kh, rep), _kv_to_q(vh, rep)
+    ok, live = attention_allowed(key_mask, causal, qh.shape[0], qh.shape[2], kh.shape[2])
+    P, _ = _attn_probs(qh, kq, ok, live, causal, scale)
+    ks = _keep_scale(keep, p, F64)
+    Pt = P if ks is None else P * ks
+    o = Pt @ vq
+    dP = doh @ vq.transpose(-1, -2)
+    if ks is not None:
+        dP = dP * ks
+    delta = (doh * o).sum(-1, keepdim=True)
+    dS = P * (dP - delta)
+    dq = scale * (dS @ kq)
+    dk = _q_to_kv(scale * (dS.transpose(-1, -2) @ qh), rep)
+    dv = _q_to_kv(Pt.transpose(-1, -2) @ doh, rep)
+    A_o = Pt @ vq.abs() + o.abs()
+    A_dv_q = Pt.transpose(-1, -2) @ doh.abs()
+    A_lse = torch.zeros(P.shape[:-1], dtype=F64)
+    A_P = None
+    if qk_rounded:
+        E = scale * (qh.abs() @ kq.abs().transpose(-1, -2))
+        PE = (P * E).sum(-1, keepdim=True)
+        A_P = P * (E + PE)
+        A_lse = PE.squeeze(-1)
+        A_o = A_o + A_P @ vq.abs()
+        A_dv_q = A_dv_q + A_P.transpose(-1, -2) @ doh.abs()
+    A_dS = P * (2.0 * (dP - delta).abs() + (doh.abs() * (o.abs() + A_o)).sum(-1, keepdim=True))
+    if A_P is not None:
+        A_dS = A_dS + A_P * (dP - delta).abs()
+    A_dq = scale * (A_dS @ kq.abs()) + dq.abs()
+    A_dk = _q_to_kv(scale * (A_dS.transpose(-1, -2) @ qh.abs()), rep) + dk.abs()
+    A_dv = _q_to_kv(A_dv_q, rep) + dv.abs()
+    perm = lambda t: t.permute(0, 2, 1, 3)                       # noqa: E731
+    return {"o": perm(A_o), "dq": perm(A_dq), "dk": perm(A_dk), "dv": perm(A_dv), "lse": A_lse}
+
+
+ATTN_MUTANTS = ("drop_key_tile", "diagonal_shift", "kv_head_mod", "no_delta", "bwd_no_drop_scale", "masked_row_zero")
+
+
+def attention_emulated(q, k, v, key_mask, causal, scale, dout, keep=None, p=0.0, qk_round=None, mutant=None):
+    """The kernels' arithmetic restated in float32 torch with a bf16 rounding at every point the bound lists: (o, dq, dk, dv), bf16
+    values in float64.  Its error against the float64 reference is the yardstick of the Frobenius criterion -- never the kernel's own.
+        o  = bf((bf(Et) V) / l), Et = exp(s - row max) keep / (1 - p),  delta = rowsum(dO * o),  dS = P (dPt - delta),
+        dq = bf(bf(scale dS) K),  dk = bf(scale bf(dS)^T Q),  dv = bf(bf(Pt)^T dO)
+    qk_round: None (generic kernels); "fwd" (generated forward, generic backward: only lse carries the rounded q);
+    "all" (generated forward + dQ round q * scale * log2 e, generated dK/dV rounds k * scale * log2 e, all normalised by the forward's lse).
+    mutant: one of ATTN_MUTANTS -- a DELIBERATE bug, for tests/test_ref64.py to show that the criteria bite (keep-flag swaps need no hook:
+    feed other flags)."""
+    assert mutant is None or mutant in ATTN_MUTANTS, mutant
+    f32 = torch.float32
+    qh, kh, vh, doh = _bh(q, f32), _bh(k, f32), _bh(v, f32), _bh(dout, f32)
+    B, nq, Sq, D = qh.shape
+    nkv, Sk = kh.shape[1], kh.shape[2]
+    rep = nq // nkv
+    if mutant == "kv_head_mod":
+        idx = torch.arange(nq) % nkv
+        kq, vq = kh[:, idx], vh[:, idx]
+    else:
+        kq, vq = _kv_to_q(kh, rep), _kv_to_q(vh, rep)
+    ok, live = attention_allowed(key_mask, causal, B, Sq, Sk)
+    if mutant == "drop_key_tile" and Sk > 64:                   # the last 64-key tile is never swept
+        ok = ok.clone()
+        ok[..., ((Sk - 1) // 64) * 64:] = False
+    if mutant == "diagonal_shift" and causal:                   # key <= query - 1
+        ok = ok & torch.tril(torch.ones(Sq, Sk, dtype=torch.bool), diagonal=-1)[None, None]
+    if mutant == "masked_row_zero" and not causal and key_mask is not None:
+        ok = ok & torch.as_tensor(key_mask).cpu().bool()[:, None, None, :]
+    c = scale * LOG2E
+
+    def probs(qs, ks_, lse=None):
+        s = qs @ ks_.transpose(-1, -2)
+        if not causal:
+            s = torch.where(live[..., None], s, torch.zeros_like(s))
+        s = s.masked_fill(~ok, float("-inf"))
+        if lse is None:
+            m = s.amax(-1, keepdim=True)
+            m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+            l = torch.exp(s - m).sum(-1, keepdim=True)
+            lse = torch.where(l > 0, m + torch.log(l), torch.full_like(m, float("inf")))
+        return torch.exp(s - lse), lse, s
+
+    q_r, k_r = _bf(qh * c) / LOG2E, _bf(kq * c) / LOG2E          # natural-log logits from the re-rounded operand
+    if qk_round is None:
+        P, lse, s_f = probs(qh * scale, kq)
+        P_dq = P_dkv = P
+    else:
+        P, lse, s_f = probs(q_r, kq)
+        P_dq = P if qk_round == "all" else probs(qh * scale, kq, lse)[0]
+        P_dkv = probs(qh, k_r, lse)[0] if qk_round == "all" else P_dq
+    # the forward rounds the UNNORMALISED probabilities exp(s - row max) (the maximum itself stays exactly 1) and divides by l at the store
+    m_f = s_f.amax(-1, keepdim=True)
+    m_f = torch.where(torch.isfinite(m_f), m_f, torch.zeros_like(m_f))
+    e_f = torch.exp(s_f - m_f)
+    l_f = e_f.sum(-1, keepdim=True)
+    inv_f = torch.where(l_f > 0, 1.0 / l_f.clamp_min(1e-30), torch.zeros_like(l_f))
+    ks = _keep_scale(keep, p, f32)
+    one = torch.ones((), dtype=f32)
+    fs, bs = (one if ks is None else ks), (one if ks is None else ks)
+    if mutant == "bwd_no_drop_scale" and ks is not None:
+        bs = ks * (1.0 - p)
+    o = _bf((_bf(e_f * fs) @ vq) * inv_f)
+    dP = doh @ vq.transpose(-1, -2)
+    delta = (doh * o).sum(-1, keepdim=True)
+    if mutant == "no_delta":
+        delta = torch.zeros_like(delta)
+    dq = _bf(_bf(scale * P_dq * (dP * bs - delta)) @ kq)
+    dS = _bf(P_dkv * (dP * bs - delta))
+    dk_q = scale * (dS.transpose(-1, -2) @ qh)
+    dv_q = _bf(P_dkv * bs).transpose(-1, -2) @ doh
+    if mutant == "kv_head_mod":
+        dk = torch.zeros_like(kh).index_add_(1, idx, dk_q)
+        dv = torch.zeros_like(vh).index_add_(1, idx, dv_q)
+    else:
+        dk, dv = _q_to_kv(dk_q, rep), _q_to_kv(dv_q, rep)
+    return tuple(_bf(t).permute(0, 2, 1, 3).to(F64) for t in (o, dq, dk, dv))
+
+
+def attention_emulated_tiled(q, k, v, key_mask, causal, scale, dout, keep=None, p=0.0, tile=64, defer=6.0):
+    """A second, independently built correct emulation, for measuring how far two correct implementations lie apart in the Frobenius
+    criterion's norm (the margin 3): keys swept in tiles with an online softmax, the running maximum moved only when it grows by more
+    than 2^defer (probabilities above 1 in between), UNNORMALISED probabilities rounded for the PV product and o normalised at the end,
+    delta from the unrounded o, the dS scale applied after the dK product and before the dQ one, partial sums per tile."""
+    f32 = torch.float32
+    qh, kh, vh, doh = _bh(q, f32), _bh(k, f32), _bh(v, f32), _bh(dout, f32)
+    B, nq, Sq, D = qh.shape
+    nkv, Sk = kh.shape[1], kh.shape[2]
+    rep = nq // nkv
+    kq, vq = _kv_to_q(kh, rep), _kv_to_q(vh, rep)
+    ok, live = attention_allowed(key_mask, causal, B, Sq, Sk)
+    ks = _keep_scale(keep, p, f32)
+    s = (qh @ kq.transpose(-1, -2)) * scale
+    if not causal:
+        s = torch.where(live[..., None], s, torch.zeros_like(s))
+    s = s.masked_fill(~ok, float("-inf"))
+    m = torch.full((B, nq, Sq, 1), float("-inf"), dtype=f32)
+    l = torch.zeros((B, nq, Sq, 1), dtype=f32)
+    acc = torch.zeros((B, nq, Sq, D), dtype=f32)
+    for k0 in range(0, Sk, tile):
+        st = s[..., k0:k0 + tile]
+        mx = st.amax(-1, keepdim=True)
+        grow = ~(mx <= m + defer * math.log(2.0))
+        mnew = torch.where(grow, torch.maximum(m, mx), m)
+        mu = torch.where(torch.isfinite(mnew), mnew, torch.zeros_like(mnew))
+        alpha = torch.exp(torch.where(torch.isfinite(m), m, torch.full_like(m, -1e30)) - mu).clamp_max(1.0)
+        alpha = torch.where(torch.isfinite(m), alpha, torch.zeros_like(alpha))
+        l, acc, m = l * alpha, acc * alpha, mnew
+        e = torch.exp(st - mu)
+        l = l + e.sum(-1, keepdim=True)
+        if ks is not None:
+            e = e * ks[..., k0:k0 + tile]
+        acc = acc + _bf(e) @ vq[:, :, k0:k0 + tile]
+    inv = torch.where(l > 0, 1.0 / l.clamp_min(1e-30), torch.zeros_like(l))
+    o32 = acc * inv
+    o = _bf(o32)
+    mu = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+    delta = (doh * o32).sum(-1, keepdim=True)
+    dq = torch.zeros_like(qh)
+    dk_q = torch.zeros((B, nq, Sk, D), dtype=f32)
+    dv_q = torch.zeros((B, nq, Sk, D), dtype=f32)
+    for k0 in range(0, Sk, tile):
+        sl = slice(k0, k0 + tile)
+        P = torch.exp(s[..., sl] - mu) * inv
+        dP = doh @ vq[:, :, sl].transpose(-1, -2)
+        Pt = P
+        if ks is not None:
+            dP, Pt = dP * ks[..., sl], P * ks[..., sl]
+        dS = _bf(P * (dP - delta))
+        dq = dq + dS @ kq[:, :, sl]
+        dk_q[:, :, sl] = dS.transpose(-1, -2) @ qh
+        dv_q[:, :, sl] = _bf(Pt).transpose(-1, -2) @ doh
+    dq = dq * scale
+    dk, dv = _q_to_kv(dk_q * scale, rep), _q_to_kv(dv_q, rep)
+    return tuple(_bf(t).permute(0, 2, 1, 3).to(F64) for t in (o, dq, dk, dv))
+
+
+def attn_bound_ratio(got, ref64, A):
+    """max over EVERY element of |got - ref| / ((U_BF16 + F32_SLACK) * A); 0 / 0 counts as 0, x / 0 as inf."""
+    g, r, a = _cpu64(got), _cpu64(ref64), _cpu64(A)
+    err, bound = (g - r).abs(), (U_BF16 + F32_SLACK) * a
+    ratio = torch.where(err <= bound, err / bound.clamp_min(1e-300), torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.full_like(err, float("inf"))))
+    ratio = torch.where(err == 0, torch.zeros_like(ratio), ratio)
+    return ratio
+
+
+def assert_attn_bound(got, ref64, A, what=""):
+    """EVERY element: |got - ref| <= U_BF16 * A + F32_SLACK * A, everything finite.  Returns the worst error / bound."""
+    g, r = _cpu64(got), _cpu64(ref64)
+    assert g.shape == r.shape == tuple(A.shape), f"{what}: shapes {tuple(g.shape)} / {tuple(r.shape)} / {tuple(A.shape)}"
+    assert torch.isfinite(r).all() and torch.isfinite(_cpu64(A)).all(), f"{what}: the reference itself is not finite"
+    if g.numel() == 0:
+        return 0.0
+    bad = ~torch.isfinite(g)
+    if bad.any():
+        i = tuple(int(v) for v in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} non-finite outputs, first at {i}: got {g[i].item()}, reference {r[i].item()}")
+    ratio = attn_bound_ratio(g, r, A)
+    off = ratio > 1.0
+    if off.any():
+        i = tuple(int(v) for v in torch.unravel_index(ratio.argmax(), ratio.shape))
+        raise AssertionError(f"{what}: {int(off.sum())} of {ratio.numel()} elements exceed (2^-8 + 2^-20) * A; worst at index {i}: got {g[i].item()!r}, "
+                             f"reference {r[i].item()!r}, error {abs(g[i].item() - r[i].item()):.3e} = {ratio[i].item():.2f} x the bound (A {_cpu64(A)[i].item():.3e})")
+    return float(ratio.max())
+
+
+def attn_frob_ratio(got, ref64, emul, A, margin=3.0):
+    """per (batch, head) slice of an ABI-layout tensor [B, S, heads, hd]: ||got - ref||_F / (margin * ||emul - ref||_F + F32_SLACK * ||A||_F)"""
+    g, r, e, a = _cpu64(got), _cpu64(ref64), _cpu64(emul), _cpu64(A)
+    nrm = lambda t: t.pow(2).sum(dim=(1, 3)).sqrt()               # noqa: E731
+    err, bound = nrm(g - r), margin * nrm(e - r) + F32_SLACK * nrm(a)
+    return torch.where(err == 0, torch.zeros_like(err), err / bound.clamp_min(1e-300))
+
+
+def assert_attn_frob(got, ref64, emul, A, what="", margin=3.0):
+    """Every (batch, head) slice: ||got - ref||_F <= 3 * ||emul - ref||_F + 2^-20 * ||A||_F.  Returns the worst ratio."""
+    g = _cpu64(got)
+    if g.numel() == 0:
+        return 0.0
+    assert torch.isfinite(g).all(), f"{what}: non-finite outputs"
+    ratio = attn_frob_ratio(g, ref64, emul, A, margin)
+    off = ratio > 1.0
+    if off.any():
+        i = tuple(int(v) for v in torch.unravel_index(ratio.argmax(), ratio.shape))
+        raise AssertionError(f"{what}: {int(off.sum())} of {ratio.numel()} (batch, head) slices exceed {margin} x the emulation's Frobenius error; "
+                             f"worst at (batch, head) {i}: {ratio[i].item():.2f} x the bound")
+    return float(ratio.max())

@@ -5,6 +5,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from tests import attn_cases  # noqa: E402
 from unirec_amd import hip  # noqa: E402
 
 DEV = "cuda"
@@ -72,6 +73,11 @@ def _run(B, Sq, Sk, nq, nkv, hd, causal, mask_kind, seed=0, fused_qkv=False):
         err = (got.float() - want).abs().max().item()
         scale = want.abs().max().item()
         assert err <= 2e-2 * scale + 2e-2, f"{name}: max err {err} (scale {scale})"
+    if max(Sq, Sk) <= 512:
+        # ... and element by element against float64 (tests/test_gpu_attention_f64.py: the hard bound and the Frobenius criterion)
+        ops = (q.cpu(), k.cpu(), v.cpu(), dout.cpu(), None if km is None else km.cpu(), causal, hd ** -0.5)
+        A, emul = attn_cases.criteria_of(*ops, qk_round=attn_cases.qk_round_for(hd, causal, Sq, Sk, hip.attn_mode(hip.ATTN_MODE_C128, -2)))
+        attn_cases.hold(attn_cases.reference_of(*ops), A, emul, dict(o=o, dq=dq, dk=dk, dv=dv), f"{Sq}x{Sk} {nq}:{nkv} hd{hd} {mask_kind}", stats=ctx.stats)
     return o
 
 
