@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 13
+#define UR_ABI_VERSION 14
 
 int ur_version(void);
 const char* ur_last_error(void);
@@ -309,6 +309,33 @@ int ur_attn_mode(int key, int value);
 /* f32 words the `delta` workspace of ur_attn_bwd must hold (row constants + the call's own work-queue words) */
 int64_t ur_attn_bwd_workspace_floats(int32_t B, int32_t nq, int32_t Sq);
 int64_t ur_attn_bwd_kv_colsum_floats(const ur_attn_args* a);
+/* Which kernel each launch of ur_attn_fwd(a) / ur_attn_bwd(a, g) takes: the answer of the one selection function the launches
+ * themselves read (attn.hip: attn_select), under the ur_attn_mode words as they stand at the moment of the call.
+ *   UR_ATTN_KERNEL_NONE     nothing is launched (B == 0; dq / dkv when g == NULL)
+ *   UR_ATTN_KERNEL_GENERIC  attn_fwd_kernel / attn_bwd_dq_kernel / attn_bwd_dkv_kernel <head_dim, causal, NW>: every shape no rule below takes
+ *   UR_ATTN_KERNEL_TINY     attn_tiny_fwd / attn_tiny_bwd_kernel: head_dim 64, non-causal, nq == nkv, <= 4 queries, <= 16 keys (the backward
+ *                           is one kernel: dq and dkv are TINY together)
+ *   UR_ATTN_KERNEL_C128     the generated causal head_dim-128 kernels: Sq == Sk in [128, 4096], item ids and byte ranges in range; the
+ *                           forward for Sk % 64 == 0, the backward pair (dq and dkv together, lse_log2 = 1: plane 1 of `delta` holds
+ *                           -LSE * log2 e) for Sk % 128 == 0 without dropout
+ *   UR_ATTN_KERNEL_GQ2      forward only, lab builds with UR_FWD_GQ2=1: attn_fwd_kernel<128, true, 8, GQ2> (causal head_dim 128, nq == 2 nkv)
+ *   UR_ATTN_KERNEL_DKV2     dkv only: attn_bwd_dkv2_kernel, head_dim 128, > 64 keys, no dropout
+ *   UR_ATTN_KERNEL_FEWQ     dkv only: attn_bwd_dkv_fewq_kernel, head_dim 64, non-causal, nq == nkv, <= 64 queries, >= 256 keys (the kernel
+ *                           behind kv_colsum: ur_attn_bwd_kv_colsum_floats(a) > 0 exactly when dkv is FEWQ)
+ * Priority: forward TINY, GQ2, C128, GENERIC; dQ TINY, C128, GENERIC; dK/dV TINY, FEWQ, C128, DKV2, GENERIC.
+ * ur_attn_plan applies the size, stride and flag checks of the launch entry points (-1 and ur_last_error() on a refusal) but neither
+ * requires, align-checks nor reads a data pointer; it reads the sizes, strides, head_dim, causal, dropout_p, g->lddo and whether
+ * g->kv_colsum is set (refused unless dkv is FEWQ, as ur_attn_bwd does).  g == NULL asks about the forward only.  It launches nothing
+ * and calls no HIP function: it answers on a machine without a GPU. */
+enum { UR_ATTN_KERNEL_NONE = 0, UR_ATTN_KERNEL_GENERIC = 1, UR_ATTN_KERNEL_TINY = 2, UR_ATTN_KERNEL_C128 = 3, UR_ATTN_KERNEL_GQ2 = 4,
+       UR_ATTN_KERNEL_DKV2 = 5, UR_ATTN_KERNEL_FEWQ = 6 };
+typedef struct {
+  int32_t fwd, dq, dkv;      /* UR_ATTN_KERNEL_* */
+  int32_t lse_log2;
+  int32_t nw_q, nw_k;        /* 64-lane waves per workgroup of the GENERIC forward / dQ kernels (1, 2, 4 for <= 32, <= 64, more queries) and of
+                              * the GENERIC dK/dV kernel (the same steps in keys) */
+} ur_attn_plan_info;
+int ur_attn_plan(const ur_attn_args* a, const ur_attn_bwd_args* g, ur_attn_plan_info* out);
 /* Keep flags of the counter-based dropout every kernel here regenerates instead of storing (nn.Dropout at models/qformer.py:107,
  * 258, 287, 373).  Test / inspection entries: a parity test feeds these masks to the reference's own nn.Dropout modules and to the
  * CPU oracle, so that a TRAINING-mode step can be compared value for value.

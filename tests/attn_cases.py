@@ -1,8 +1,10 @@
 """The inputs of tests/test_gpu_attention_f64.py and what they are held to, as plain CPU code: the GPU module runs the kernels on
-these cases, tests/test_ref64.py checks on the CPU that the emulation meets the hard bound on every one of them.  No device code.
+these cases, tests/test_ref64.py checks on the CPU that the emulation meets the hard bound on every one of them.  No device execution;
+asks the built library which kernels a shape takes (hip.attn_plan).
 
 A case is a dict (see case()); inputs() builds its seeded bf16 tensors, reference() the float64 results, criteria() the bound magnitudes
 A and the emulation, hold() applies both criteria and the stats check to what a kernel returned."""
+import contextlib
 import functools
 import zlib
 
@@ -10,6 +12,7 @@ import torch
 
 from oracle import dropout_ref
 from tests import ref64
+from unirec_amd import _lib, hip
 
 BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
 HEADS = ((1, 1), (3, 3), (4, 2), (4, 1))              # (nq, nkv): GQA ratios 1, 1, 2, 4
@@ -28,16 +31,55 @@ def _input_key(c):
     return tuple((k, c[k]) for k in sorted(c) if k not in ("name", "modes"))
 
 
-def qk_round_for(hd, causal, Sq, Sk, c128_mode=1):
-    """Which launches of a shape run on the generated causal head_dim-128 kernels (attn.hip: launch_fwd / c128_bwd_ok), i.e. round
-    q * scale * log2 e (k * scale * log2 e in dK/dV) to bf16 once more: None, "fwd" (forward only: Sk % 64 == 0) or "all" (Sk % 128 == 0)."""
-    if not (causal and hd == 128 and c128_mode and Sq == Sk and Sk >= 128 and Sk % 64 == 0):
+MODE_KEYS = {"TINY": hip.ATTN_MODE_TINY, "C128": hip.ATTN_MODE_C128, "DKV_PERSIST": hip.ATTN_MODE_DKV_PERSIST, "FEWQ": hip.ATTN_MODE_FEWQ}
+
+
+def plan_args(B, Sq, Sk, nq, nkv, hd, causal, p=0.0, scale=None):
+    """(AttnArgs, AttnBwdArgs) of a dense call as far as hip.attn_plan reads them: sizes, strides and flags, no pointer"""
+    a, g = _lib.AttnArgs(), _lib.AttnBwdArgs()
+    a.B, a.Sq, a.Sk, a.nq, a.nkv, a.head_dim, a.causal = B, Sq, Sk, nq, nkv, hd, int(causal)
+    a.ldq = a.ldo = g.lddo = g.lddq = nq * hd
+    a.ldk = a.ldv = g.lddk = g.lddv = nkv * hd
+    a.scale, a.dropout_p = float(scale if scale is not None else hd ** -0.5), float(p)
+    return a, g
+
+
+@contextlib.contextmanager
+def plan_modes(modes):
+    """the ur_attn_mode words ((mode name, value), ...) set, every other word as it stands; all restored on exit"""
+    with contextlib.ExitStack() as st:
+        for k, v in modes:
+            st.enter_context(hip.attn_mode_set(MODE_KEYS[k], v))
+        yield
+
+
+def plan_of(a, g=None, modes=()):
+    """hip.attn_plan under the ur_attn_mode words `modes`"""
+    with plan_modes(modes):
+        return hip.attn_plan(a, g)
+
+
+def plan(c):
+    """the kernels case c takes under its own modes"""
+    return plan_of(*plan_args(c["B"], c["Sq"], c["Sk"], c["nq"], c["nkv"], c["hd"], c["causal"], c["p"], c["scale"]), modes=c["modes"])
+
+
+def _qk_round_of(pl):
+    """Which launches run on the generated causal head_dim-128 kernels, i.e. round q * scale * log2 e (k * scale * log2 e in dK/dV) to
+    bf16 once more: None, "fwd" (forward only) or "all" (the backward pair as well)."""
+    if pl["fwd"] != "c128":
+        assert pl["dq"] != "c128" and pl["dkv"] != "c128", pl
         return None
-    return "all" if Sk % 128 == 0 else "fwd"
+    return "all" if pl["dq"] == "c128" else "fwd"
+
+
+def qk_round_for(hd, causal, Sq, Sk, c128_mode=None, B=1, nq=1, nkv=1):
+    """_qk_round_of what the library selects for a dense call of this shape; c128_mode None: UR_ATTN_MODE_C128 as it stands"""
+    return _qk_round_of(plan_of(*plan_args(B, Sq, Sk, nq, nkv, hd, causal), modes=() if c128_mode is None else (("C128", c128_mode),)))
 
 
 def qk_round(c):
-    return qk_round_for(c["hd"], c["causal"], c["Sq"], c["Sk"], dict(c["modes"]).get("C128", 1))
+    return _qk_round_of(plan(c))
 
 
 def _mask(c, g):

@@ -76,7 +76,7 @@ def _run(B, Sq, Sk, nq, nkv, hd, causal, mask_kind, seed=0, fused_qkv=False):
     if max(Sq, Sk) <= 512:
         # ... and element by element against float64 (tests/test_gpu_attention_f64.py: the hard bound and the Frobenius criterion)
         ops = (q.cpu(), k.cpu(), v.cpu(), dout.cpu(), None if km is None else km.cpu(), causal, hd ** -0.5)
-        A, emul = attn_cases.criteria_of(*ops, qk_round=attn_cases.qk_round_for(hd, causal, Sq, Sk, hip.attn_mode(hip.ATTN_MODE_C128, -2)))
+        A, emul = attn_cases.criteria_of(*ops, qk_round=attn_cases.qk_round_for(hd, causal, Sq, Sk, B=B, nq=nq, nkv=nkv))
         attn_cases.hold(attn_cases.reference_of(*ops), A, emul, dict(o=o, dq=dq, dk=dk, dv=dv), f"{Sq}x{Sk} {nq}:{nkv} hd{hd} {mask_kind}", stats=ctx.stats)
     return o
 

@@ -44,7 +44,6 @@ COVERS = {
 DEV = "cuda"
 BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
 SENTINEL = 0x4B4B                    # a finite bf16 bit pattern nothing computes by accident
-MODE_KEYS = {"TINY": hip.ATTN_MODE_TINY, "C128": hip.ATTN_MODE_C128, "DKV_PERSIST": hip.ATTN_MODE_DKV_PERSIST, "FEWQ": hip.ATTN_MODE_FEWQ}
 WORST = {}
 
 
@@ -58,20 +57,7 @@ def _note_all(family, ratios):
         _note(f"{family} {what}", r)
 
 
-class _modes:
-    """with _modes(case["modes"]): every ur_attn_mode word of the case set, all restored on exit"""
-
-    def __init__(self, modes):
-        self.sets = [hip.attn_mode_set(MODE_KEYS[k], v) for k, v in modes]
-
-    def __enter__(self):
-        for s in self.sets:
-            s.__enter__()
-
-    def __exit__(self, *exc):
-        for s in reversed(self.sets):
-            s.__exit__(*exc)
-        return False
+_modes = ac.plan_modes      # with _modes(case["modes"]): every ur_attn_mode word of the case set, all restored on exit
 
 
 def _ids(cases):

@@ -504,7 +504,7 @@ def test_attention_criteria_catch_swapped_keep_flags():
 
 def test_attention_stats_check_and_qk_round_rule():
     """hold_stats accepts any (m, 1 / l) with m + ln l = lse (the maximum is deferred: the pair is not unique) and rejects a row sum that
-    lost one key; qk_round_for restates which shapes run on the generated kernels (attn.hip: launch_fwd / c128_bwd_ok)"""
+    lost one key; qk_round_for asks the library which shapes run on the generated kernels (hip.attn_plan)"""
     q, k, v, dout, km, _ = _attn_inputs(2, 9, 9, 2, 1, 64, 5, "left")
     ops = (q, k, v, dout, km, True, 0.125)
     ref, (A, _) = attn_cases.reference_of(*ops), attn_cases.criteria_of(*ops)

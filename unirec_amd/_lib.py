@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -74,6 +74,11 @@ class AttnBwdArgs(ctypes.Structure):
                 ("kv_colsum", c_void_p), ("kv_colsum_ws", c_void_p)]
 
 
+class AttnPlanInfo(ctypes.Structure):
+    """Mirror of ur_attn_plan_info (kernel ids: UR_ATTN_KERNEL_*)."""
+    _fields_ = [("fwd", c_int), ("dq", c_int), ("dkv", c_int), ("lse_log2", c_int), ("nw_q", c_int), ("nw_k", c_int)]
+
+
 class F32Range(ctypes.Structure):
     """Mirror of ur_f32_range."""
     _fields_ = [("ptr", c_void_p), ("n", c_i64)]
@@ -128,6 +133,7 @@ SIGNATURES = {
     "ur_attn_bwd": (c_int, [ctypes.POINTER(AttnArgs), ctypes.POINTER(AttnBwdArgs), c_void_p]),
     "ur_attn_bwd_workspace_floats": (c_i64, [c_int, c_int, c_int]),
     "ur_attn_bwd_kv_colsum_floats": (c_i64, [ctypes.POINTER(AttnArgs)]),
+    "ur_attn_plan": (c_int, [ctypes.POINTER(AttnArgs), ctypes.POINTER(AttnBwdArgs), ctypes.POINTER(AttnPlanInfo)]),
     "ur_dropout_keep": (c_int, [c_u64, c_float, c_u64, c_i64, c_void_p, c_void_p]),
     "ur_attn_dropout_keep": (c_int, [c_u64, c_float, c_u64, c_i64, c_int, c_void_p, c_void_p]),
     "ur_rope_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),

@@ -2203,28 +2203,10 @@ __global__ __launch_bounds__(256) void attn_tiny_bwd_kernel(AttnP p) {
 }
 
 // Kernel-selection switches of the attention entry points: process-wide words set through the C ABI (ur_attn_mode, include/unirec_hip.h) --
-// the library reads no environment variable.  Every alternative is a complete, tested path (bit-identity / oracle tests flip them).
+// the only environment variable the library reads is the lab switch UR_FWD_GQ2, and only in UR_LAB builds (attn_select).  Every
+// alternative is a complete, tested path (bit-identity / oracle tests flip them).
 std::atomic<int> g_attn_mode[UR_ATTN_MODE_COUNT] = {{3}, {1}, {1}, {1}};      // TINY: bit 0 forward, bit 1 backward; C128, DKV_PERSIST, FEWQ: 0 / 1
 inline int attn_mode(int key) { return g_attn_mode[key].load(std::memory_order_relaxed); }
-// UR_ATTN_MODE_TINY = 0 keeps tiny shapes on the MFMA kernels (1 / 2: tiny forward / backward only)
-inline bool tiny_enabled(bool bwd) { return (attn_mode(UR_ATTN_MODE_TINY) & (bwd ? 2 : 1)) != 0; }
-inline bool tiny_shape(const AttnP& p, int hd, bool causal, bool bwd) {
-  return hd == 64 && !causal && p.rep == 1 && p.Sq <= 4 && p.Sk <= TK && tiny_enabled(bwd);
-}
-int launch_tiny(const AttnP& p, bool bwd, hipStream_t st) {
-  const long npairs = (long)p.B * p.nq;
-  dim3 grid((unsigned)((npairs + 15) / 16));
-  if (!bwd) {
-    if (p.Sq <= 2) hipLaunchKernelGGL((attn_tiny_fwd_kernel<2>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((attn_tiny_fwd_kernel<4>), grid, dim3(256), 0, st, p);
-    UR_CHECK_LAUNCH("ur_attn_fwd(tiny)");
-  } else {
-    if (p.Sq <= 2) hipLaunchKernelGGL((attn_tiny_bwd_kernel<2>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((attn_tiny_bwd_kernel<4>), grid, dim3(256), 0, st, p);
-    UR_CHECK_LAUNCH("ur_attn_bwd(tiny)");
-  }
-  return 0;
-}
 
 // ================================================================================================
 // Causal head_dim-128 forward, hand-scheduled: the key-tile loop is ONE generated inline-asm block (tools/asmgen/attn_fwd.py ->
@@ -3048,18 +3030,28 @@ _Pragma("unroll") \
 template <int HD> constexpr int fwd_smem() { return 4 * Cfg<HD>::TILE + MAX_KTILES * 16; }
 template <int HD> constexpr int dkv_smem() { return 2 * (2 * Cfg<HD>::TILE + 5 * KT * (int)sizeof(float)); }
 
-template <typename K>
-int set_smem(K kern, int bytes, const char* name) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) UR_FAIL((int)e, "%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e));
+// One launch: the kernel's dynamic-LDS limit once per device (max_lds = 0: the default limit is enough), the launch, its check.
+// The guard is a static of the instantiation, i.e. one per kernel symbol.
+template <auto KERN, typename... Args>
+int launch(const char* name, dim3 grid, int threads, int max_lds, int lds, hipStream_t st, const Args&... args) {
+  if (max_lds > 0) {
+    static std::atomic<uint64_t> once{0};   // per device
+    UR_ONCE_PER_DEVICE(once) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+      if (e != hipSuccess) UR_FAIL((int)e, "%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e));
+    }
+  }
+  hipLaunchKernelGGL(KERN, grid, dim3(threads), lds, st, args...);
+  UR_CHECK_LAUNCH(name);
   return 0;
 }
 
-int fill(AttnP& p, const ur_attn_args* a) {
-  UR_REQUIRE(a && a->q && a->k && a->v && a->stats, "ur_attn: null argument");
+// with_ptrs = false (ur_attn_plan): the same checks without requiring, align-checking or reading any data pointer
+int fill(AttnP& p, const ur_attn_args* a, bool with_ptrs = true) {
+  UR_REQUIRE(a && (!with_ptrs || (a->q && a->k && a->v && a->stats)), "ur_attn: null argument");
   UR_REQUIRE(a->B >= 0 && a->Sq > 0 && a->Sk > 0 && a->nq > 0 && a->nkv > 0 && (a->nq % a->nkv) == 0, "ur_attn: bad sizes");
   UR_REQUIRE(a->head_dim == 64 || a->head_dim == 128, "ur_attn: head_dim must be 64 or 128 (got %d)", a->head_dim);
-  UR_REQUIRE((a->ldq % 8) == 0 && (a->ldk % 8) == 0 && (a->ldv % 8) == 0 && UR_ALIGNED16(a->q) && UR_ALIGNED16(a->k) && UR_ALIGNED16(a->v),
+  UR_REQUIRE((a->ldq % 8) == 0 && (a->ldk % 8) == 0 && (a->ldv % 8) == 0 && (!with_ptrs || (UR_ALIGNED16(a->q) && UR_ALIGNED16(a->k) && UR_ALIGNED16(a->v))),
              "ur_attn: q/k/v need 16-byte aligned rows");
   UR_REQUIRE(a->ldq >= (int64_t)a->nq * a->head_dim && a->ldk >= (int64_t)a->nkv * a->head_dim && a->ldv >= (int64_t)a->nkv * a->head_dim,
              "ur_attn: token stride smaller than heads*head_dim");
@@ -3078,127 +3070,72 @@ int fill(AttnP& p, const ur_attn_args* a) {
   return 0;
 }
 
-// the hand-scheduled causal head_dim-128 BACKWARD pair (dQ + dK/dV) runs together or not at all (they share the -LSE2 plane)
-inline bool c128_bwd_ok(const AttnP& p);
-// CUs of the current device (persistent grids), cached per device
-inline int device_cu_count() { return ur_device_cu_count(); }
-// UR_ATTN_MODE_C128 = 0 sends the causal head_dim-128 launches back to the compiler-scheduled kernels
-inline bool fwd_c128_enabled() { return attn_mode(UR_ATTN_MODE_C128) != 0; }
-// UR_ATTN_MODE_DKV_PERSIST = 0 launches one workgroup per key block
-inline bool dkv_persist_enabled() { return attn_mode(UR_ATTN_MODE_DKV_PERSIST) != 0; }
-inline bool fwd_gq2_enabled() { static const bool on = ur_lab_int("UR_FWD_GQ2", 0) == 1; return on; }
+// ---- kernel selection ---------------------------------------------------------------------------------------------------------
+// Which kernel each launch of a call takes is decided HERE and nowhere else: the launchers below, ur_attn_plan,
+// ur_attn_bwd_kv_colsum_floats, lse_log2 and the fused k-RoPE store of ur_attn_bwd all read the AttnPlan.  Pure host arithmetic on
+// sizes, strides (for the backward: with p.lddo set), p.rep, p.drop_thr, the four ur_attn_mode words and the lab variable
+// UR_FWD_GQ2 (UR_LAB builds; read once per process): no HIP call, no pointer target.
+inline int pick_nw(int S) { return S <= 32 ? 1 : (S <= 64 ? 2 : 4); }      // waves of 32 rows per workgroup of the generic kernels
+struct AttnPlan {
+  int fwd, dq, dkv;      // UR_ATTN_KERNEL_*
+  int nw_q, nw_k;        // NW of the forward / dQ launch (rows = queries) and of the dK/dV launch (rows = keys)
+  int lse_log2;          // the generated backward pair runs: plane 1 of `delta` holds -LSE * log2(e) (AttnP::lse_log2)
+};
+AttnPlan attn_select(const AttnP& p, int hd, bool causal) {
+  static const bool gq2_on = ur_lab_int("UR_FWD_GQ2", 0) == 1;
+  const int tiny_mode = attn_mode(UR_ATTN_MODE_TINY);      // 0 keeps tiny shapes on the MFMA kernels (1 / 2: tiny forward / backward only)
+  AttnPlan pl;
+  pl.nw_q = pick_nw(p.Sq);
+  pl.nw_k = pick_nw(p.Sk);
+  // <= 4 queries x <= 16 keys on the VALU kernels; the backward is ONE kernel for dQ, dK and dV
+  const bool tiny = hd == 64 && !causal && p.rep == 1 && p.Sq <= 4 && p.Sk <= TK;
+  const bool tiny_fwd = tiny && (tiny_mode & 1) != 0, tiny_bwd = tiny && (tiny_mode & 2) != 0;
+  // the generated causal head_dim-128 kernels (UR_ATTN_MODE_C128 = 0: back to the compiler-scheduled ones): 24-bit item ids, 31-bit
+  // buffer ranges.  The forward takes whole 64-key tiles; the backward PAIR (dQ + dK/dV run together or not at all: they share the
+  // -LSE2 plane) whole 128-key blocks, its own operands' ranges, no dropout.  S 192 and 576 are generated forward, generic backward.
+  const bool c128 = hd == 128 && causal && p.Sq == p.Sk && p.Sk >= 128 && p.Sk <= c128::MAX_SK && attn_mode(UR_ATTN_MODE_C128) != 0 &&
+                    (long)p.nq * p.B * 8 < (1L << 24) && p.ldk * 2L * p.Sk < (1L << 31) && p.ldv * 2L * p.Sk < (1L << 31);
+  const bool c128_fwd = c128 && (p.Sk % KT) == 0;
+  const bool c128_bwd = c128 && (p.Sk % 128) == 0 && p.ldq * 2L * p.Sq < (1L << 31) && p.lddo * 2L * p.Sq < (1L << 31) && p.drop_thr == 0 &&
+                        (long)p.B * p.nq * p.Sq * 4 < (1L << 31);
+  // few queries, many keys (UR_ATTN_MODE_FEWQ = 0: attn_bwd_dkv_kernel; one test process compares the two bit for bit); the only
+  // dK/dV kernel that can also emit the column sums of dK | dV
+  const bool fewq = hd == 64 && !causal && p.rep == 1 && p.Sq <= KT && p.Sk >= 256 && attn_mode(UR_ATTN_MODE_FEWQ) != 0;
+  pl.fwd = tiny_fwd ? UR_ATTN_KERNEL_TINY
+         : hd == 128 && causal && pl.nw_q == 4 && p.rep == 2 && gq2_on ? UR_ATTN_KERNEL_GQ2
+         : c128_fwd ? UR_ATTN_KERNEL_C128 : UR_ATTN_KERNEL_GENERIC;
+  pl.dq = tiny_bwd ? UR_ATTN_KERNEL_TINY : c128_bwd ? UR_ATTN_KERNEL_C128 : UR_ATTN_KERNEL_GENERIC;
+  pl.dkv = tiny_bwd ? UR_ATTN_KERNEL_TINY
+         : fewq ? UR_ATTN_KERNEL_FEWQ
+         : c128_bwd ? UR_ATTN_KERNEL_C128
+         : hd == 128 && pl.nw_k == 4 && p.drop_thr == 0 ? UR_ATTN_KERNEL_DKV2 : UR_ATTN_KERNEL_GENERIC;
+  pl.lse_log2 = c128_bwd ? 1 : 0;
+  return pl;
+}
+
+// ---- launchers: grid and LDS arithmetic only ----------------------------------------------------------------------------------
+inline dim3 tiny_grid(const AttnP& p) { return dim3((unsigned)(((long)p.B * p.nq + 15) / 16)); }      // 16 (batch, head) pairs per workgroup
+// item decode of the persistent generated forward / dQ kernels: a work item = one (batch, query head) x one pair of 256-row query blocks
+struct C128Items { int nitems, nch; C128Div dv; };
+inline C128Items c128_items(const AttnP& p) {
+  const int nx = ur_cdiv(p.Sq, 256), nch = (nx + 1) / 2;
+  auto magic = [](uint32_t d) { return (uint32_t)(((1ull << 32) + d - 1) / d); };
+  return {p.nq * p.B * nch, nch, C128Div{magic((uint32_t)(p.rep * nch)), magic((uint32_t)nch), magic((uint32_t)p.nkv)}};
+}
+
 template <int HD, bool CAUSAL, int NW>
-int launch_fwd(const AttnP& p, hipStream_t st) {
-  if constexpr (HD == 128 && CAUSAL && NW == 4) {
-    if (p.rep == 2 && fwd_gq2_enabled()) {
-      static std::atomic<uint64_t> once8{0};   // per device
-      UR_ONCE_PER_DEVICE(once8) { int rc = set_smem(&attn_fwd_kernel<128, true, 8, true>, fwd_smem<128>(), "ur_attn_fwd(gq2)"); if (rc) return rc; }
-      dim3 grid(ur_cdiv(p.Sq, 128) * (p.nq / 2) * p.B);
-      hipLaunchKernelGGL((attn_fwd_kernel<128, true, 8, true>), grid, dim3(512), fwd_smem<128>(), st, p);
-      UR_CHECK_LAUNCH("ur_attn_fwd(gq2)");
-      return 0;
-    }
-  }
-  if constexpr (HD == 128 && CAUSAL && NW == 4) {
-    if (p.Sq == p.Sk && (p.Sk % KT) == 0 && p.Sk >= 128 && p.Sk <= c128::MAX_SK && fwd_c128_enabled() && (long)p.nq * p.B * 8 < (1L << 24) &&
-        p.ldk * 2L * p.Sk < (1L << 31) && p.ldv * 2L * p.Sk < (1L << 31)) {
-      static std::atomic<uint64_t> once_c{0};   // per device
-      UR_ONCE_PER_DEVICE(once_c) { int rc = set_smem(&attn_fwd_c128_kernel, c128::LDS_BYTES, "ur_attn_fwd(c128)"); if (rc) return rc; }
-      const int nx = ur_cdiv(p.Sq, 256), nch = (nx + 1) / 2, nitems = p.nq * p.B * nch;
-      auto magic = [](uint32_t d) { return (uint32_t)(((1ull << 32) + d - 1) / d); };
-      const C128Div dv{magic((uint32_t)(p.rep * nch)), magic((uint32_t)nch), magic((uint32_t)p.nkv)};
-      hipLaunchKernelGGL(attn_fwd_c128_kernel, dim3(std::min(nitems, device_cu_count())), dim3(256), c128::LDS_BYTES, st, p, nitems, nch, dv);
-      UR_CHECK_LAUNCH("ur_attn_fwd(c128)");
-      return 0;
-    }
-  }
-  static std::atomic<uint64_t> once{0};   // per device
-  UR_ONCE_PER_DEVICE(once) { int rc = set_smem(&attn_fwd_kernel<HD, CAUSAL, NW>, fwd_smem<HD>(), "ur_attn_fwd"); if (rc) return rc; }
-  dim3 grid(ur_cdiv(p.Sq, 32 * NW) * p.nq * p.B);
+int launch_fwd_generic(const AttnP& p, hipStream_t st) {
   // one K | V stage and one pair of key words when every key fits one tile (the Q-Formers' 32-query launches: twice the waves per CU)
   const int smem_bytes = p.Sk <= KT ? 2 * Cfg<HD>::TILE + 16 : fwd_smem<HD>();
-  hipLaunchKernelGGL((attn_fwd_kernel<HD, CAUSAL, NW>), grid, dim3(NW * 64), smem_bytes, st, p);
-  UR_CHECK_LAUNCH("ur_attn_fwd");
-  return 0;
+  return launch<&attn_fwd_kernel<HD, CAUSAL, NW>>("ur_attn_fwd", dim3(ur_cdiv(p.Sq, 32 * NW) * p.nq * p.B), NW * 64, fwd_smem<HD>(), smem_bytes, st, p);
 }
 template <int HD, bool CAUSAL, int NW>
-int launch_dq(const AttnP& p, hipStream_t st) {
-  if constexpr (HD == 128 && CAUSAL && NW == 4) {
-    if (c128_bwd_ok(p)) {
-      static std::atomic<uint64_t> once_c{0};   // per device
-      UR_ONCE_PER_DEVICE(once_c) { int rc = set_smem(&attn_bwd_dq_c128_kernel, c128::DQ_LDS_BYTES, "ur_attn_bwd(dq c128)"); if (rc) return rc; }
-      const int nx = ur_cdiv(p.Sq, 256), nch = (nx + 1) / 2, nitems = p.nq * p.B * nch;
-      auto magic = [](uint32_t d) { return (uint32_t)(((1ull << 32) + d - 1) / d); };
-      const C128Div dv{magic((uint32_t)(p.rep * nch)), magic((uint32_t)nch), magic((uint32_t)p.nkv)};
-      hipLaunchKernelGGL(attn_bwd_dq_c128_kernel, dim3(std::min(nitems, device_cu_count())), dim3(256), c128::DQ_LDS_BYTES, st, p, nitems, nch, dv);
-      UR_CHECK_LAUNCH("ur_attn_bwd(dq c128)");
-      return 0;
-    }
-  }
-  static std::atomic<uint64_t> once{0};   // per device
-  UR_ONCE_PER_DEVICE(once) { int rc = set_smem(&attn_bwd_dq_kernel<HD, CAUSAL, NW>, fwd_smem<HD>(), "ur_attn_bwd(dq)"); if (rc) return rc; }
-  dim3 grid(ur_cdiv(p.Sq, 32 * NW) * p.nq * p.B);
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, CAUSAL, NW>), grid, dim3(NW * 64), fwd_smem<HD>(), st, p);
-  UR_CHECK_LAUNCH("ur_attn_bwd(dq)");
-  return 0;
+int launch_dq_generic(const AttnP& p, hipStream_t st) {
+  return launch<&attn_bwd_dq_kernel<HD, CAUSAL, NW>>("ur_attn_bwd(dq)", dim3(ur_cdiv(p.Sq, 32 * NW) * p.nq * p.B), NW * 64, fwd_smem<HD>(), fwd_smem<HD>(), st, p);
 }
-// UR_ATTN_MODE_FEWQ = 0 sends few-query shapes back to attn_bwd_dkv_kernel (one test process compares the two kernels bit for bit)
-inline bool fewq_enabled() { return attn_mode(UR_ATTN_MODE_FEWQ) != 0; }
-
 template <int HD, bool CAUSAL, int NW>
-int launch_dkv(const AttnP& p, hipStream_t st) {
-  if (HD == 64 && !CAUSAL && NW == 4 && p.rep == 1 && p.Sq <= KT && p.Sk >= 256 && fewq_enabled()) {
-    // few queries, many keys: one workgroup per (batch, head) pair -- or per chunk of its key blocks while the pairs
-    // alone do not fill the chip (>= 8 key blocks, i.e. two per wave, per workgroup)
-    constexpr int SMF = 2 * Cfg<64>::TILE + 5 * KT * (int)sizeof(float) + 16 + 4 * 2 * 64 * (int)sizeof(float) + 256;      // + flag + the waves' column sums + one liveness byte per key block
-    static_assert(MAX_KTILES * KT / 32 <= 256, "attn_bwd_dkv_fewq_kernel: one liveness byte per 32-key block in a 256-byte LDS tail (ur_attn caps Sk at MAX_KTILES * KT)");
-    const int nblk = ur_cdiv(p.Sk, 32), pairs = p.nq * p.B;
-    int nchunk = std::max(1, std::min(ur_cdiv(4096, pairs), nblk / 8));
-    if (p.colsum_part != nullptr) nchunk = 1;          // the column sums leave as ONE partial per (batch, head): one workgroup per pair
-    const int bpc = ur_cdiv(ur_cdiv(nblk, nchunk), 4) * 4;
-    nchunk = ur_cdiv(nblk, bpc);
-    hipLaunchKernelGGL((attn_bwd_dkv_fewq_kernel<64>), dim3(pairs * nchunk), dim3(256), SMF, st, p, nchunk, bpc);
-    UR_CHECK_LAUNCH("ur_attn_bwd(dkv fewq)");
-    return 0;
-  }
-  dim3 grid(ur_cdiv(p.Sk, 32 * NW) * p.nkv * p.B);
-  if constexpr (HD == 128 && CAUSAL && NW == 4) {
-    if (c128_bwd_ok(p)) {
-      static std::atomic<uint64_t> once_c{0};   // per device
-      UR_ONCE_PER_DEVICE(once_c) { int rc = set_smem(&attn_bwd_dkv_c128_kernel, c128::DKV_LDS_BYTES, "ur_attn_bwd(dkv c128)"); if (rc) return rc; }
-      // persistent walk where the sweep divides evenly (see the kernel): one workgroup per CU for the whole launch
-      const int ncu = device_cu_count(), ngroups = p.nkv * p.B;
-      const bool pers = dkv_persist_enabled() && (ncu % 8) == 0 && (ngroups % 8) == 0 && (long)grid.x > ncu;
-      if (pers) hipLaunchKernelGGL(attn_bwd_dkv_c128_kernel, dim3(ncu), dim3(256), c128::DKV_LDS_BYTES, st, p, 1);
-      else hipLaunchKernelGGL(attn_bwd_dkv_c128_kernel, grid, dim3(256), c128::DKV_LDS_BYTES, st, p, 0);
-      UR_CHECK_LAUNCH("ur_attn_bwd(dkv c128)");
-      return 0;
-    }
-  }
-  if (HD == 128 && NW == 4 && p.drop_thr == 0) {
-    constexpr int SM2 = 2 * (2 * Cfg<128>::TILE + 4 * KT * (int)sizeof(float));      // = NB buffers of attn_bwd_dkv2_kernel
-    static std::atomic<uint64_t> once2{0};   // per device
-    UR_ONCE_PER_DEVICE(once2) { int rc = set_smem(&attn_bwd_dkv2_kernel<CAUSAL>, SM2, "ur_attn_bwd(dkv2)"); if (rc) return rc; }
-    hipLaunchKernelGGL((attn_bwd_dkv2_kernel<CAUSAL>), grid, dim3(256), SM2, st, p);
-    UR_CHECK_LAUNCH("ur_attn_bwd(dkv2)");
-    return 0;
-  }
-  static std::atomic<uint64_t> once{0};   // per device
-  UR_ONCE_PER_DEVICE(once) { int rc = set_smem(&attn_bwd_dkv_kernel<HD, CAUSAL, NW>, dkv_smem<HD>(), "ur_attn_bwd(dkv)"); if (rc) return rc; }
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, CAUSAL, NW>), grid, dim3(NW * 64), dkv_smem<HD>(), st, p);
-  UR_CHECK_LAUNCH("ur_attn_bwd(dkv)");
-  return 0;
-}
-
-inline int pick_nw(int S) { return S <= 32 ? 1 : (S <= 64 ? 2 : 4); }
-// the shapes whose dK/dV run on attn_bwd_dkv_fewq_kernel (the only kernel that can also emit the column sums of dK | dV)
-inline bool fewq_shape(const AttnP& p, int hd, bool causal) {
-  return hd == 64 && !causal && pick_nw(p.Sk) == 4 && p.rep == 1 && p.Sq <= KT && p.Sk >= 256 && p.Sk <= MAX_KTILES * KT && fewq_enabled();
-}
-inline bool c128_bwd_ok(const AttnP& p) {
-  return p.Sq == p.Sk && (p.Sk % 128) == 0 && p.Sk >= 128 && p.Sk <= c128::MAX_SK && fwd_c128_enabled() && (long)p.nq * p.B * 8 < (1L << 24) &&
-         p.ldk * 2L * p.Sk < (1L << 31) && p.ldv * 2L * p.Sk < (1L << 31) && p.ldq * 2L * p.Sq < (1L << 31) && p.lddo * 2L * p.Sq < (1L << 31) &&
-         p.drop_thr == 0 && (long)p.B * p.nq * p.Sq * 4 < (1L << 31);
+int launch_dkv_generic(const AttnP& p, hipStream_t st) {
+  return launch<&attn_bwd_dkv_kernel<HD, CAUSAL, NW>>("ur_attn_bwd(dkv)", dim3(ur_cdiv(p.Sk, 32 * NW) * p.nkv * p.B), NW * 64, dkv_smem<HD>(), dkv_smem<HD>(), st, p);
 }
 
 #define UR_ATTN_DISPATCH(HD_, CAUSAL_, NW_, FN, ...)                                      \
@@ -3212,9 +3149,67 @@ inline bool c128_bwd_ok(const AttnP& p) {
     }                                                                                     \
   } while (0)
 
-int do_fwd(const AttnP& p, int hd, bool causal, hipStream_t st) { UR_ATTN_DISPATCH(hd, causal, pick_nw(p.Sq), launch_fwd, p, st); }
-int do_dq(const AttnP& p, int hd, bool causal, hipStream_t st) { UR_ATTN_DISPATCH(hd, causal, pick_nw(p.Sq), launch_dq, p, st); }
-int do_dkv(const AttnP& p, int hd, bool causal, hipStream_t st) { UR_ATTN_DISPATCH(hd, causal, pick_nw(p.Sk), launch_dkv, p, st); }
+int launch_fwd(const AttnP& p, const AttnPlan& pl, int hd, bool causal, hipStream_t st) {
+  switch (pl.fwd) {
+    case UR_ATTN_KERNEL_TINY:
+      if (p.Sq <= 2) return launch<&attn_tiny_fwd_kernel<2>>("ur_attn_fwd(tiny)", tiny_grid(p), 256, 0, 0, st, p);
+      return launch<&attn_tiny_fwd_kernel<4>>("ur_attn_fwd(tiny)", tiny_grid(p), 256, 0, 0, st, p);
+    case UR_ATTN_KERNEL_GQ2:
+      return launch<&attn_fwd_kernel<128, true, 8, true>>("ur_attn_fwd(gq2)", dim3(ur_cdiv(p.Sq, 128) * (p.nq / 2) * p.B), 512, fwd_smem<128>(), fwd_smem<128>(), st, p);
+    case UR_ATTN_KERNEL_C128: {
+      const C128Items it = c128_items(p);
+      return launch<&attn_fwd_c128_kernel>("ur_attn_fwd(c128)", dim3(std::min(it.nitems, ur_device_cu_count())), 256, c128::LDS_BYTES, c128::LDS_BYTES, st, p, it.nitems, it.nch, it.dv);
+    }
+  }
+  UR_ATTN_DISPATCH(hd, causal, pl.nw_q, launch_fwd_generic, p, st);
+}
+
+// dQ; the tiny kernel is the whole backward (dQ, dK and dV)
+int launch_dq(const AttnP& p, const AttnPlan& pl, int hd, bool causal, hipStream_t st) {
+  switch (pl.dq) {
+    case UR_ATTN_KERNEL_TINY:
+      if (p.Sq <= 2) return launch<&attn_tiny_bwd_kernel<2>>("ur_attn_bwd(tiny)", tiny_grid(p), 256, 0, 0, st, p);
+      return launch<&attn_tiny_bwd_kernel<4>>("ur_attn_bwd(tiny)", tiny_grid(p), 256, 0, 0, st, p);
+    case UR_ATTN_KERNEL_C128: {
+      const C128Items it = c128_items(p);
+      return launch<&attn_bwd_dq_c128_kernel>("ur_attn_bwd(dq c128)", dim3(std::min(it.nitems, ur_device_cu_count())), 256, c128::DQ_LDS_BYTES, c128::DQ_LDS_BYTES, st, p, it.nitems, it.nch,
+                                              it.dv);
+    }
+  }
+  UR_ATTN_DISPATCH(hd, causal, pl.nw_q, launch_dq_generic, p, st);
+}
+
+int launch_dkv(const AttnP& p, const AttnPlan& pl, int hd, bool causal, hipStream_t st) {
+  const dim3 grid(ur_cdiv(p.Sk, 32 * pl.nw_k) * p.nkv * p.B);
+  switch (pl.dkv) {
+    case UR_ATTN_KERNEL_TINY: return 0;      // the dQ launch was the whole backward
+    case UR_ATTN_KERNEL_FEWQ: {
+      // one workgroup per (batch, head) pair -- or per chunk of its key blocks while the pairs alone do not fill the chip (>= 8 key
+      // blocks, i.e. two per wave, per workgroup)
+      constexpr int SMF = 2 * Cfg<64>::TILE + 5 * KT * (int)sizeof(float) + 16 + 4 * 2 * 64 * (int)sizeof(float) + 256;      // + flag + the waves' column sums + one liveness byte per key block
+      static_assert(MAX_KTILES * KT / 32 <= 256, "attn_bwd_dkv_fewq_kernel: one liveness byte per 32-key block in a 256-byte LDS tail (ur_attn caps Sk at MAX_KTILES * KT)");
+      const int nblk = ur_cdiv(p.Sk, 32), pairs = p.nq * p.B;
+      int nchunk = std::max(1, std::min(ur_cdiv(4096, pairs), nblk / 8));
+      if (p.colsum_part != nullptr) nchunk = 1;          // the column sums leave as ONE partial per (batch, head): one workgroup per pair
+      const int bpc = ur_cdiv(ur_cdiv(nblk, nchunk), 4) * 4;
+      nchunk = ur_cdiv(nblk, bpc);
+      return launch<&attn_bwd_dkv_fewq_kernel<64>>("ur_attn_bwd(dkv fewq)", dim3(pairs * nchunk), 256, 0, SMF, st, p, nchunk, bpc);
+    }
+    case UR_ATTN_KERNEL_C128: {
+      // persistent walk where the sweep divides evenly (see the kernel): one workgroup per CU for the whole launch
+      // (UR_ATTN_MODE_DKV_PERSIST = 0: one workgroup per key block)
+      const int ncu = ur_device_cu_count(), ngroups = p.nkv * p.B;
+      const bool pers = attn_mode(UR_ATTN_MODE_DKV_PERSIST) != 0 && (ncu % 8) == 0 && (ngroups % 8) == 0 && (long)grid.x > ncu;
+      return launch<&attn_bwd_dkv_c128_kernel>("ur_attn_bwd(dkv c128)", pers ? dim3(ncu) : grid, 256, c128::DKV_LDS_BYTES, c128::DKV_LDS_BYTES, st, p, pers ? 1 : 0);
+    }
+    case UR_ATTN_KERNEL_DKV2: {
+      constexpr int SM2 = 2 * (2 * Cfg<128>::TILE + 4 * KT * (int)sizeof(float));      // = NB buffers of attn_bwd_dkv2_kernel
+      if (causal) return launch<&attn_bwd_dkv2_kernel<true>>("ur_attn_bwd(dkv2)", grid, 256, SM2, SM2, st, p);
+      return launch<&attn_bwd_dkv2_kernel<false>>("ur_attn_bwd(dkv2)", grid, 256, SM2, SM2, st, p);
+    }
+  }
+  UR_ATTN_DISPATCH(hd, causal, pl.nw_k, launch_dkv_generic, p, st);
+}
 
 }  // namespace
 
@@ -3235,15 +3230,34 @@ extern "C" int ur_attn_fwd(const ur_attn_args* a, void* stream) {
   if (rc) return rc;
   if (a->B == 0) return 0;
   UR_REQUIRE(a->o && UR_ALIGNED16(a->o) && (a->ldo % 4) == 0 && a->ldo >= (int64_t)a->nq * a->head_dim, "ur_attn_fwd: bad output");
-  if (tiny_shape(p, a->head_dim, a->causal != 0, false)) return launch_tiny(p, false, (hipStream_t)stream);
-  return do_fwd(p, a->head_dim, a->causal != 0, (hipStream_t)stream);
+  return launch_fwd(p, attn_select(p, a->head_dim, a->causal != 0), a->head_dim, a->causal != 0, (hipStream_t)stream);
+}
+
+extern "C" int ur_attn_plan(const ur_attn_args* a, const ur_attn_bwd_args* g, ur_attn_plan_info* out) {
+  UR_REQUIRE(out, "ur_attn_plan: null argument");
+  AttnP p;
+  int rc = fill(p, a, false);
+  if (rc) return rc;
+  UR_REQUIRE((a->ldo % 4) == 0 && a->ldo >= (int64_t)a->nq * a->head_dim, "ur_attn_plan: bad output stride");
+  UR_REQUIRE(g == nullptr || ((g->lddo % 8) == 0 && (a->ldo % 8) == 0), "ur_attn_plan: dout/o need 16-byte aligned rows");
+  if (g) p.lddo = g->lddo;
+  const AttnPlan pl = attn_select(p, a->head_dim, a->causal != 0);
+  const bool run = a->B > 0;      // B == 0: the entry points return before anything is selected
+  UR_REQUIRE(g == nullptr || g->kv_colsum == nullptr || !run || pl.dkv == UR_ATTN_KERNEL_FEWQ,
+             "ur_attn_plan: kv_colsum is produced by the few-query dK/dV kernel only (ur_attn_bwd_kv_colsum_floats(a) == 0 for this shape)");
+  out->fwd = run ? pl.fwd : UR_ATTN_KERNEL_NONE;
+  out->dq = run && g ? pl.dq : UR_ATTN_KERNEL_NONE;
+  out->dkv = run && g ? pl.dkv : UR_ATTN_KERNEL_NONE;
+  out->lse_log2 = run && g ? pl.lse_log2 : 0;
+  out->nw_q = pl.nw_q;
+  out->nw_k = pl.nw_k;
+  return 0;
 }
 
 extern "C" int64_t ur_attn_bwd_kv_colsum_floats(const ur_attn_args* a) {
   AttnP p;
   if (!a || fill(p, a) != 0 || a->B <= 0) return 0;
-  if (tiny_shape(p, a->head_dim, a->causal != 0, true) || !fewq_shape(p, a->head_dim, a->causal != 0)) return 0;
-  return 2 * (int64_t)a->B * a->nq * a->head_dim;
+  return attn_select(p, a->head_dim, a->causal != 0).dkv == UR_ATTN_KERNEL_FEWQ ? 2 * (int64_t)a->B * a->nq * a->head_dim : 0;
 }
 
 extern "C" int ur_attn_mode(int key, int value) {
@@ -3278,6 +3292,7 @@ extern "C" int ur_attn_bwd(const ur_attn_args* a, const ur_attn_bwd_args* g, voi
              ((uintptr_t)g->dv & 7) == 0, "ur_attn_bwd: gradient outputs need 8-byte aligned rows");
   p.dout = (const bf16_t*)g->dout; p.dq = (bf16_t*)g->dq; p.dk = (bf16_t*)g->dk; p.dv = (bf16_t*)g->dv; p.delta = g->delta;
   p.lddo = g->lddo; p.lddq = g->lddq; p.lddk = g->lddk; p.lddv = g->lddv;
+  const AttnPlan pl = attn_select(p, a->head_dim, a->causal != 0);      // (needs p.lddo)
   p.rp_raw = (const bf16_t*)g->rope_q_raw; p.rp_ldraw = g->rope_ldraw; p.rp_w = g->rope_q_weight; p.rp_cos = g->rope_cos; p.rp_sin = g->rope_sin;
   p.rp_eps = g->rope_eps; p.rp_draw = (bf16_t*)g->rope_dq_raw; p.rp_lddraw = g->rope_lddraw;
   p.rp_rstd = g->rope_q_raw ? g->rope_rstd : nullptr; p.rp_rstd_ld = g->rope_rstd_ld; p.rp_rstd_h0 = g->rope_rstd_h0;
@@ -3294,32 +3309,31 @@ extern "C" int ur_attn_bwd(const ur_attn_args* a, const ur_attn_bwd_args* g, voi
   hipStream_t st = (hipStream_t)stream;
   p.colsum_part = nullptr;
   if (g->kv_colsum != nullptr) {
-    UR_REQUIRE(g->kv_colsum_ws != nullptr && ur_attn_bwd_kv_colsum_floats(a) > 0,
+    UR_REQUIRE(g->kv_colsum_ws != nullptr && pl.dkv == UR_ATTN_KERNEL_FEWQ,
                "ur_attn_bwd: kv_colsum is produced by the few-query dK/dV kernel only (ur_attn_bwd_kv_colsum_floats(a) == 0 for this shape) and needs kv_colsum_ws");
     p.colsum_part = g->kv_colsum_ws;
   }
   // the workspace behind the two row-constant planes: two planes of dropout row keys, then the queue words (ur_attn_bwd_workspace_floats)
   p.rowkeys = reinterpret_cast<uint32_t*>(g->delta + 2 * (int64_t)a->B * a->nq * a->Sq);
   p.queue = reinterpret_cast<unsigned int*>(g->delta + 4 * (int64_t)a->B * a->nq * a->Sq);
-  p.lse_log2 = (a->head_dim == 128 && a->causal != 0 && c128_bwd_ok(p)) ? 1 : 0;
-  if (tiny_shape(p, a->head_dim, a->causal != 0, true)) return launch_tiny(p, true, st);      // dQ, dK, dV in one kernel
+  p.lse_log2 = pl.lse_log2;
   // the dQ kernel also computes the row constants (delta, -LSE/scale) and leaves them in `delta` for dK/dV
   // (only the generated dK/dV kernel carries the k heads' backward in its store; on every other path dk is written roped and the
   // stand-alone kernel turns it into the raw gradient here)
-  const bool rope_k_fused = rope_k && p.lse_log2 != 0;
+  const bool rope_k_fused = rope_k && pl.dkv == UR_ATTN_KERNEL_C128;
   if (rope_k && !rope_k_fused) {
     // (checked BEFORE anything is launched: a refused call leaves every output untouched)
     UR_REQUIRE(g->lddk == (int64_t)a->nkv * a->head_dim, "ur_attn_bwd: rope_k on this shape needs a dense dk [B*Sk, nkv*hd]");
     p.rk_src = nullptr;
   }
-  rc = do_dq(p, a->head_dim, a->causal != 0, st);
+  rc = launch_dq(p, pl, a->head_dim, a->causal != 0, st);
   if (rc) return rc;
-  rc = do_dkv(p, a->head_dim, a->causal != 0, st);
+  rc = launch_dkv(p, pl, a->head_dim, a->causal != 0, st);
   if (rc) return rc;
   if (p.colsum_part != nullptr) {
     const int n = 2 * a->nq * a->head_dim;
-    hipLaunchKernelGGL(kv_colsum_reduce_kernel, dim3(ur_cdiv(n, 64)), dim3(256), 0, st, (const float*)p.colsum_part, g->kv_colsum, (int)a->B, n);
-    UR_CHECK_LAUNCH("ur_attn_bwd(kv colsum)");
+    rc = launch<&kv_colsum_reduce_kernel>("ur_attn_bwd(kv colsum)", dim3(ur_cdiv(n, 64)), 256, 0, 0, st, (const float*)p.colsum_part, g->kv_colsum, (int)a->B, n);
+    if (rc) return rc;
   }
   if (rope_k && !rope_k_fused) {
     return ur_qknorm_rope_bwd_roped_k(g->dk, g->rope_k, g->rope_ldk, g->rope_rstd, g->rope_rstd_ld, g->rope_rstd_hk0, g->rope_k_weight, g->rope_cos,

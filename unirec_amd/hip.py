@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, AttnBwdArgs, GemmArgs, LoraArgs, check
+from ._lib import AttnArgs, AttnBwdArgs, AttnPlanInfo, GemmArgs, LoraArgs, check
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -325,11 +325,12 @@ def qknorm_rope_bwd_roped_k(dk_out, k_r, rstd, h0, kw, cos, sin, dk_raw, S, nkv,
 
 
 ATTN_MODE_TINY, ATTN_MODE_C128, ATTN_MODE_DKV_PERSIST, ATTN_MODE_FEWQ = 0, 1, 2, 3      # include/unirec_hip.h: UR_ATTN_MODE_*
+ATTN_KERNELS = ("none", "generic", "tiny", "c128", "gq2", "dkv2", "fewq")                # index = UR_ATTN_KERNEL_*
 
 
 def attn_mode(key, value):
     """Kernel selection of the attention entry points (ur_attn_mode, include/unirec_hip.h): sets the process-wide word `key` and returns
-    the previous value; value -1 = default, -2 = query only.  The library reads no environment variable."""
+    the previous value; value -1 = default, -2 = query only."""
     prev = int(_lib.load().ur_attn_mode(int(key), int(value)))
     if prev < 0:
         raise ValueError(f"ur_attn_mode: unknown key {key}")
@@ -653,6 +654,18 @@ def attn_fwd(q, k, v, *, causal, key_mask=None, scale=None, dropout_p=0.0, seed=
 def attn_bwd_kv_colsum_supported(ctx):
     """True when attn_bwd(ctx, ..., kv_colsum=) can also produce the column sums of dK | dV (the few-query dK/dV kernel's shapes)."""
     return int(_lib.load().ur_attn_bwd_kv_colsum_floats(ctypes.byref(ctx.args))) > 0
+
+
+def attn_plan(ctx_or_args, bwd=None):
+    """Which kernels attn_fwd / attn_bwd take for these arguments under the current attn_mode words (ur_attn_plan): a dict with
+    fwd, dq, dkv (names from ATTN_KERNELS), lse_log2 and nw_q, nw_k (waves per workgroup of the generic kernels).  ctx_or_args: an AttnCtx or an AttnArgs (only sizes, strides and flags are read:
+    no tensor and no device is needed); bwd: an AttnBwdArgs (lddo and whether kv_colsum is set are read), None = the forward only
+    (dq = dkv = "none").  Raises UniRecHipError where the entry points would refuse the arguments."""
+    a = ctx_or_args.args if isinstance(ctx_or_args, AttnCtx) else ctx_or_args
+    out = AttnPlanInfo()
+    check(_lib.load().ur_attn_plan(ctypes.byref(a), None if bwd is None else ctypes.byref(bwd), ctypes.byref(out)), "ur_attn_plan")
+    return dict(fwd=ATTN_KERNELS[out.fwd], dq=ATTN_KERNELS[out.dq], dkv=ATTN_KERNELS[out.dkv], lse_log2=int(out.lse_log2),
+                nw_q=int(out.nw_q), nw_k=int(out.nw_k))
 
 
 def attn_bwd(ctx, dout, dq=None, dk=None, dv=None, rope_q=None, rope_rstd=None, rope_k=None, kv_colsum=None):
