@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 14
+#define UR_ABI_VERSION 15      /* 15: ur_lora_args.rank takes 8, 16, 32 or 64 (was 16 only); ur_gemm_args.drop_rank takes 64 as well */
 
 int ur_version(void);
 const char* ur_last_error(void);
@@ -64,7 +64,8 @@ typedef struct {
    * drop_bits != NULL: the second pair holds K2/drop_rank adapters that share the input x [M, N]; instead of joining
    * the main reduction,  C(m,n) += sum_a keep_a(m,n)/(1-drop_p) * R2[m, a*r:(a+1)*r] . S2[n, a*r:(a+1)*r]
    * (dx = dy W + sum_a mask_a * (tb_a A_a)); keep_a comes from bit plane a of ur_lora_dropout_bits (row stride
-   * drop_bits_ld = ur_lora_bits_ld(N) bytes, plane stride drop_bits_stride bytes). */
+   * drop_bits_ld = ur_lora_bits_ld(N) bytes, plane stride drop_bits_stride bytes).  r = drop_rank in {8, 16, 24, 32, 64}, at most
+   * 4 adapters (K2 <= 256); the persistent kernel takes rank 16 with K2 <= 64, the generic kernel everything else. */
   const void* drop_bits; int64_t drop_bits_ld; int64_t drop_bits_stride;
   int32_t drop_rank; float drop_p;
   /* SwiGLU backward as the epilogue of the down-projection's dX GEMM (Qwen3MLP: down(act_fn(gate(x)) * up(x)),
@@ -129,34 +130,40 @@ int ur_gemm_grouped(const ur_gemm_args* a, int32_t count, void* workspace, int64
 int ur_gemm_persistent_mode(int mode);
 
 /* ------------------------------------------------------------------------------------------------
- * LoRA adapter products, rank 16 (peft LoraLayer; call site training/train_item_individual_token_joint.py:121-131,
- * r=16, lora_alpha=32, lora_dropout=0.1).  HBM-bound streams over one [M, W] activation X:
- *   ur_lora_project:  P[m, 16a + j] = alpha * sum_w keep_a(m,w) X[m, col0_a + w] U_a[j, w]
+ * LoRA adapter products of rank r = `rank` in {8, 16, 32, 64}, j = 0 .. r - 1 (peft LoraLayer; call site
+ * training/train_item_individual_token_joint.py:121-131, r=16, lora_alpha=32, lora_dropout=0.1).  HBM-bound streams over one
+ * [M, W] activation X, read once per call for all adapters and all of their rank rows:
+ *   ur_lora_project:  P[m, r a + j] = alpha * sum_w keep_a(m,w) X[m, col0_a + w] U_a[j, w]
  *       forward  t  = s * dropout_a(x) A_a^T   (shared = 1: the nad adapters read the same columns, one bit plane each)
  *       backward tb = s * dy_a B_a             (shared = 0: adapter a owns columns [col0[a], col0[a]+width[a]) of dy;
- *                                               U_a = B_a^T stored [16, width[a]])
- *   ur_lora_reduce:   G_a[j, w] = alpha * sum_m V[m, 16a + j] keep_a(m,w) X[m, col0_a + w]
- *       dA_a = tb_a^T dropout_a(x)  (shared = 1, g_transposed = 0: G = [16 nad, W] f32, dense)
- *       dB_a = dy_a^T t_a           (shared = 0, g_transposed = 1: G = [sum width, 16] f32, dense, adapter ranges in order)
+ *                                               U_a = B_a^T stored [r, width[a]])
+ *   ur_lora_reduce:   G_a[j, w] = alpha * sum_m V[m, r a + j] keep_a(m,w) X[m, col0_a + w]
+ *       dA_a = tb_a^T dropout_a(x)  (shared = 1, g_transposed = 0: G = [r nad, W] f32, dense)
+ *       dB_a = dy_a^T t_a           (shared = 0, g_transposed = 1: G = [sum width, r] f32, dense, adapter ranges in order)
  *       Token reduction split deterministically over blocks; partial slabs live in the caller's workspace.
  *   ur_lora_dropout_bits: dropped flags of nad adapters over an [M, W] input: plane a at bits + a*bits_stride, row m at
  *       + m*bits_ld (bits_ld = ur_lora_bits_ld(W) = 16 * ceil(W/128) bytes); the byte at column c/8 (c % 8 == 0) holds
  *       bit i (i<4) = element c+2i dropped, bit 4+i = element c+2i+1 dropped.  A pure function of (seed, p, row0 + m, c, a).
  * drop_bits == NULL: no dropout.  The 1/(1-p) scale is the caller's (alpha).
- * Constraints: rank == 16; column ranges and ldx multiples of 8; X, U, V, G 16-byte aligned; P 8-byte aligned. */
+ * Constraints: rank in {8, 16, 32, 64} (any other: a negative return whose message names the set); column ranges and ldx
+ * multiples of 8; X, U, V, G 16-byte aligned; P 8-byte aligned.  Rank 16 has LDS-DMA ring kernels for the launches described at
+ * drop_bits_t and ur_lora_bgrad; every other rank runs the register-staged kernels (an adapter = 1, 2 or 4 blocks of 16 rank rows
+ * over the same fragments of X and the adapter's one bit plane; rank 8 = a half-filled block).  A row of P does not depend on where
+ * the row sits in the launch.  ur_rmsnorm_lora_fwd and ur_swiglu_lora_fwd are rank 16 only. */
 typedef struct {
   const void* X; int64_t ldx; int32_t M;
   int32_t nad; int32_t rank; int32_t shared;
   int32_t col0[4]; int32_t width[4];
   const void* drop_bits; int64_t bits_ld; int64_t bits_stride;
   float alpha;
-  const void* U[4]; int64_t ldu[4];       /* project: U_a bf16 [16, width_a] */
-  void* P; int64_t ldp;                   /* project: bf16 [M, >= 16 nad] */
-  const void* V; int64_t ldv;             /* reduce: bf16 [M, >= 16 nad] */
+  const void* U[4]; int64_t ldu[4];       /* project: U_a bf16 [rank, width_a] */
+  void* P; int64_t ldp;                   /* project: bf16 [M, >= rank nad] */
+  const void* V; int64_t ldv;             /* reduce: bf16 [M, >= rank nad] */
   void* G; int32_t g_transposed;          /* reduce: f32, dense */
-  /* reduce only, optional: the TOKEN-packed copy of the dropped flags (ur_lora_bits_transpose).  With it (and M, the token split and
-   * every width multiples of 128 / 64) ur_lora_reduce streams X through an LDS-DMA ring and masks the transposed fragments in
-   * registers; without it the register-staged kernel runs.  Same flags, same result up to the order of the f32 token sum. */
+  /* reduce only, optional: the TOKEN-packed copy of the dropped flags (ur_lora_bits_transpose).  With it (and rank 16, M, the token
+   * split and every width multiples of 128 / 64) ur_lora_reduce streams X through an LDS-DMA ring and masks the transposed fragments in
+   * registers; without it, or at another rank, the register-staged kernel runs.  Same flags, same result up to the order of the f32
+   * token sum. */
   const void* drop_bits_t; int64_t bits_t_ld; int64_t bits_t_stride;
 } ur_lora_args;
 int64_t ur_lora_bits_ld(int32_t W);
@@ -183,8 +190,8 @@ int ur_rmsnorm_lora_fwd(const void* x, const float* w, void* out, float* rstd, i
 int64_t ur_lora_reduce_workspace_bytes(const ur_lora_args* a);
 int ur_lora_reduce(const ur_lora_args* a, void* workspace, int64_t workspace_bytes, void* stream);
 /* ur_lora_bgrad: the B side of the backward in ONE pass over dy (shared = 0, no dropout planes): P = tb = alpha * dy_a B_a
- * (as ur_lora_project with U_a = B_a^T) AND G = dB, [sum width, 16] f32 dense (as ur_lora_reduce with V = t,
- * g_transposed = 1, scale 1); partial slabs of ceil(M / 512) token blocks live in the caller's workspace. */
+ * (as ur_lora_project with U_a = B_a^T) AND G = dB, [sum width, rank] f32 dense (as ur_lora_reduce with V = t,
+ * g_transposed = 1, scale 1); partial slabs of ceil(M / 512) token blocks (rank 64: ceil(M / 256)) live in the caller's workspace. */
 int64_t ur_lora_bgrad_workspace_bytes(const ur_lora_args* a);
 int ur_lora_bgrad(const ur_lora_args* a, void* workspace, int64_t workspace_bytes, void* stream);
 

@@ -208,27 +208,45 @@ def rope(args):
     print(f"qknorm_rope bwd from the roped outputs: {t * 1e3:.1f} us  {1.5 * nb / t / 1e9:.2f} TB/s")
 
 
+# the adapter groups of a decoder layer: (name, input width, output widths)
+LORA_GROUPS = (("q|k|v", 1024, (2048, 1024, 1024)), ("o", 2048, (1024,)), ("gate|up", 1024, (3072, 3072)), ("down", 3072, (1024,)))
+
+
 def lora(args):
-    """The rank-16 LoRA side kernels at the C4 shapes (M = B*S tokens): GB/s of the activation they stream."""
-    M, r = args.B * args.S, 16
+    """The LoRA side kernels at the C4 shapes (M = B*S tokens; --B 64 is C4), per adapter group and per rank of --ranks: the forward
+    projection t = drop(x) A^T, the backward's one pass over dy (tb and dB) and its token reduction dA = tb^T drop(x), with the GB/s
+    of the activation each streams (its bytes do not depend on the rank) and the time relative to rank 16 of the same run."""
+    M = args.B * args.S
+    ranks = [int(r) for r in args.ranks.split(",")]
     g = torch.Generator().manual_seed(0)
-    x = torch.randn(M, 1024, generator=g).cuda().to(torch.bfloat16)
-    dy = torch.randn(M, 4096, generator=g).cuda().to(torch.bfloat16)
-    A = [(torch.randn(r, 1024, generator=g) * 0.1).cuda().to(torch.bfloat16) for _ in range(3)]
-    cols = [(0, 2048), (2048, 1024), (3072, 1024)]
-    Bt = [(torch.randn(r, n, generator=g) * 0.1).cuda().to(torch.bfloat16) for _, n in cols]
-    t = torch.randn(M, 3 * r, generator=g).cuda().to(torch.bfloat16)
-    bits = hip.lora_dropout_bits(1, 0.1, M, 1024, 3, "cuda")
-    gA, gB = torch.empty(3 * r, 1024, device="cuda"), torch.empty(4096, r, device="cuda")
-    for name, fn, nbytes in (
-            ("bits   3 planes of [M,1024]", lambda: hip.lora_dropout_bits(1, 0.1, M, 1024, 3, "cuda"), 3 * M * 1024 / 8),
-            ("project t  = drop(x) A^T (3)", lambda: hip.lora_project(x, A, bits=bits), x.numel() * 2),
-            ("project tb = dy B        (3)", lambda: hip.lora_project(dy, Bt, cols=cols), dy.numel() * 2),
-            ("reduce  dB = dy^T t      (3)", lambda: hip.lora_reduce(dy, t, gB, cols=cols, transposed=True), dy.numel() * 2),
-            ("bgrad   tb and dB, one pass(3)", lambda: hip.lora_bgrad(dy, t, Bt, cols, gB), dy.numel() * 2),
-            ("reduce  dA = tb^T drop(x)(3)", lambda: hip.lora_reduce(x, t, gA, nad=3, bits=bits), x.numel() * 2)):
-        ms = timeit(fn, args.iters)
-        print(f"lora {name}: {ms * 1e3:7.1f} us  {nbytes / ms / 1e6:7.1f} GB/s")
+    ms = timeit(lambda: hip.lora_dropout_bits(1, 0.1, M, 1024, 3, "cuda"), args.iters)
+    print(f"lora bits   3 planes of [M,1024]: {ms * 1e3:7.1f} us  {3 * M * 1024 / 8 / ms / 1e6:7.1f} GB/s   (M = {M}; the planes do not depend on the rank)")
+    times = {}
+    for gname, win, outs in LORA_GROUPS:
+        nad, wout = len(outs), sum(outs)
+        x = torch.randn(M, win, generator=g).cuda().to(torch.bfloat16)
+        dy = torch.randn(M, wout, generator=g).cuda().to(torch.bfloat16)
+        bits = hip.lora_dropout_bits(1, 0.1, M, win, nad, "cuda")
+        bits_t = hip.lora_bits_transpose(bits, win)
+        cols = [(sum(outs[:j]), n) for j, n in enumerate(outs)]
+        for r in ranks:
+            A = [(torch.randn(r, win, generator=g) * 0.1).cuda().to(torch.bfloat16) for _ in range(nad)]
+            Bt = [(torch.randn(r, n, generator=g) * 0.1).cuda().to(torch.bfloat16) for n in outs]
+            t = torch.randn(M, nad * r, generator=g).cuda().to(torch.bfloat16)
+            gA, gB = torch.empty(nad * r, win, device="cuda"), torch.empty(wout, r, device="cuda")
+            for kname, fn, nbytes in (
+                    ("project t  = drop(x) A^T", lambda: hip.lora_project(x, A, alpha=1.1, bits=bits), x.numel() * 2),
+                    ("bgrad   tb and dB, one pass", lambda: hip.lora_bgrad(dy, t, Bt, cols, gB), dy.numel() * 2),
+                    ("reduce  dA = tb^T drop(x)", lambda: hip.lora_reduce(x, t, gA, nad=nad, alpha=1.1, bits=bits, bits_t=bits_t if r == 16 else None), x.numel() * 2)):
+                ms = timeit(fn, args.iters)
+                times[(gname, kname, r)] = ms
+                rel = f"  x{ms / times[(gname, kname, 16)]:.2f} of rank 16" if (gname, kname, 16) in times else ""
+                print(f"lora {gname:8s} r={r:2d} {kname:28s}: {ms * 1e3:7.1f} us  {nbytes / ms / 1e6:7.1f} GB/s{rel}")
+        del x, dy, bits, bits_t
+    if 16 in ranks:
+        for r in ranks:
+            tot = sum(v for (gn, kn, rr), v in times.items() if rr == r)
+            print(f"lora all groups r={r:2d}: {tot * 1e3:7.1f} us per layer (forward projections + backward streams)  x{tot / sum(v for (gn, kn, rr), v in times.items() if rr == 16):.2f} of rank 16")
 
 
 if __name__ == "__main__":
@@ -237,6 +255,7 @@ if __name__ == "__main__":
     ap.add_argument("--B", type=int, default=8)
     ap.add_argument("--S", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--ranks", default="16,8,32,64", help="lora: the ranks to time, comma separated (rank 16 first gives every other rank its ratio)")
     ap.add_argument("--lib", action="store_true", help="gemm: also time torch.matmul on the same operands (reference point)")
     a = ap.parse_args()
     {"attn": attn, "gemm": gemm, "lora": lora, "rope": rope, "dw": dw, "xattn": xattn, "gemm_lora": gemm_lora, "gemm_merge": gemm_merge, "gemm_step": gemm_step, "rmslora": rmslora, "swilora": swilora}[a.what](a)

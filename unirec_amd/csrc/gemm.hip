@@ -492,9 +492,9 @@ extern "C" int ur_gemm(const ur_gemm_args* a, void* workspace, int64_t workspace
                "ur_gemm: SwiGLU backward epilogue: N must equal swiglu_I, gu / dgu rows of >= 2 I elements, 8-byte aligned");
   }
   if (a->drop_bits) {
-    UR_REQUIRE(a->K2 > 0 && a->drop_rank >= 8 && a->drop_rank <= 32 && (a->drop_rank % 8) == 0 && (a->K2 % a->drop_rank) == 0 &&
+    UR_REQUIRE(a->K2 > 0 && ((a->drop_rank >= 8 && a->drop_rank <= 32 && (a->drop_rank % 8) == 0) || a->drop_rank == 64) && (a->K2 % a->drop_rank) == 0 &&
                a->K2 / a->drop_rank <= 4 && a->r_kcontig && a->s_kcontig && splits_ok(a) && !a->c_f32,
-               "ur_gemm: the masked LoRA epilogue needs K-contiguous operands, bf16 output, no split_k, rank in {8,16,24,32} and at most 4 adapters");
+               "ur_gemm: the masked LoRA epilogue needs K-contiguous operands, bf16 output, no split_k, rank in {8,16,24,32,64} and at most 4 adapters");
     UR_REQUIRE(a->drop_p >= 0.f && a->drop_p < 1.f && (a->drop_bits_ld % 16) == 0 && a->drop_bits_ld * 8 >= a->N && (a->drop_bits_stride % 8) == 0 &&
                ((uintptr_t)a->drop_bits & 15) == 0, "ur_gemm: bad LoRA dropout bit planes (rows of ur_lora_bits_ld(N) bytes, 16-byte aligned)");
   }

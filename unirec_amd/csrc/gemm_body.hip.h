@@ -442,16 +442,18 @@
   if constexpr (ACC_A) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
   // ---- LoRA dropout, backward to the adapter input: C(m,n) += sum_a keep_a(m,n)/(1-p) * tb_a(m,:) . A_a(:,n).
   // Each adapter's rank-r product of a 16x16 sub-tile is ONE MFMA (k = r <= 32, zero-padded) into a scratch
-  // accumulator; the keep flags come from the adapters' dropped-flag bit planes (lora.hip: 8 bytes cover the
-  // 64 columns this wave owns of one row).
+  // accumulator -- rank 64: two such steps of 32, each masked and added on its own (the mask is linear) -- ; the keep
+  // flags come from the adapters' dropped-flag bit planes (lora.hip: 8 bytes cover the 64 columns this wave owns of one row).
   if (p.drop_bits && p.K2 > 0) {
-    const int nad = p.K2 / p.drop_rank, kq = 8 * (lane >> 4);
-    const bool kin = kq < p.drop_rank;
+    const int nks = (p.drop_rank + 31) >> 5;                   // k-steps of 32 per adapter
+    const int nstep = (p.K2 / p.drop_rank) * nks;
     const int g4 = lane >> 4;
     static_assert(HN == 32, "the masked LoRA epilogue reads one 4-byte flag word per row and column half of the wave tile");
     const long boff0 = min((long)((n0 + wc * HN) >> 3), p.drop_bits_ld - 4);
     const long boff1 = min((long)((n0 + BN / 2 + wc * HN) >> 3), p.drop_bits_ld - 4);
-    for (int a = 0; a < nad; ++a) {
+    for (int ak = 0; ak < nstep; ++ak) {
+      const int a = ak / nks, kq = 32 * (ak - a * nks) + 8 * (lane >> 4);
+      const bool kin = kq < p.drop_rank;
       bf16x8 s2[NI], r2[MI];
       const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll

@@ -1,19 +1,28 @@
-// LoRA adapter side kernels (rank 16), gfx950 only.
+// LoRA adapter side kernels (ranks 8, 16, 32, 64), gfx950 only.
 //
 // peft LoraLayer (call site training/train_item_individual_token_joint.py:121-131, r=16, lora_dropout=0.1):
 //     y = W x + s * B_a ( A_a dropout_a(x) )            one nn.Dropout per adapter a
-// The rank-16 products are HBM-bound streams over an [M, W] activation (M = tokens): running them through
-// the 128x128-tile GEMM wastes 8x of its MFMA work and LDS traffic, and masking the operand while it is
-// staged de-pipelines it.  Three kernels replace that:
+// The rank-r products are HBM-bound streams over an [M, W] activation (M = tokens): running them through
+// the 128x128-tile GEMM wastes 8x of its MFMA work and LDS traffic at r = 16, and masking the operand while it is
+// staged de-pipelines it.  Three kernels replace that (r = ur_lora_args.rank, j = 0 .. r - 1):
 //   ur_lora_dropout_bits : the dropped flags of every adapter input element, ONE bit each, generated once per
 //                          (layer, adapter group, step) by a counter-based generator and kept for the backward
-//   ur_lora_project      : P[m, 16a+j] = alpha * sum_w keep_a(m,w) X[m, c0_a+w] U_a[j,w]   (reduction over columns)
+//   ur_lora_project      : P[m, r a+j] = alpha * sum_w keep_a(m,w) X[m, c0_a+w] U_a[j,w]   (reduction over columns)
 //                          forward  t  = s * dropout(x) A^T   (adapters share x, one bit plane each)
 //                          backward tb = s * dy_a B_a         (adapter a owns a column range of dy)
-//   ur_lora_reduce       : G_a[j,w]  = alpha * sum_m V[m,16a+j] keep_a(m,w) X[m, c0_a+w]   (reduction over tokens)
+//   ur_lora_reduce       : G_a[j,w]  = alpha * sum_m V[m,r a+j] keep_a(m,w) X[m, c0_a+w]   (reduction over tokens)
 //                          dA = tb^T dropout(x) ;  dB_a^T = t_a^T dy_a   (deterministic token split + slab sum)
 // Both read X exactly once for all adapters that share it; the MFMA operands come straight from global memory
 // (project) or through one LDS round trip with hardware-transposed reads (reduce).
+//
+// Ranks.  The register-staged kernels (lora_project_kernel, lora_reduce_kernel, lora_bgrad_kernel) take r in {8, 16, 32, 64}: an
+// adapter is NB = r / 16 blocks of 16 rank rows (the MFMA's 16) that share the adapter's ONE bit plane and the same X fragments --
+// X is loaded from global memory once per kernel for all adapters and all of their blocks -- and rank 8 is a half-filled block
+// (HALF: rows 8..15 of U and columns 8..15 of V read as zero, 8 columns / rows stored).  The block index b and the plane index
+// b / NB are separate variables.  The LDS-DMA ring kernels (*_ring_kernel), rms_lora_kernel and swiglu_lora_kernel are rank-16
+// fast paths; the dispatch sends every other rank to the register-staged kernels, with or without token-packed flags (same flags,
+// same result up to the order of the f32 token sum).  Per token the order of the sum over columns does not depend on where the
+// row sits in the launch, at any rank.
 //
 // Bit layout (shared with ur_gemm's masked LoRA epilogue): plane a, row m, byte c/8 covers columns c..c+7
 // (c % 8 == 0): bit i (i < 4) = element c+2i dropped, bit 4+i = element c+2i+1 dropped -- the order in which
@@ -175,18 +184,26 @@ struct ProjP {
 // the X fragments (NAD > 1: gridDim.y == 1); separate column ranges run as NAD = 1 with blockIdx.y = adapter.
 // X fragments are the MFMA column operand straight from global memory (lane: token lane&15, 8 consecutive
 // columns); the U chunk is staged once per block through a 2-slot LDS ring (GEMM K-contiguous image).
-template <int NAD, bool MASKED>
-__global__ __launch_bounds__(256, 4) void lora_project_kernel(ProjP p) {
-  constexpr int RB = 2, KC = 128;
-  constexpr int SUB = NAD * 16 * 128;              // one 64-column sub-tile of the U chunk: rows x 128 B
+// Rank: an adapter is NB blocks of 16 rows of U (rank 16 NB: 32 -> 2, 64 -> 4) that share the adapter's ONE bit plane and the
+// same X fragments; HALF = rank 8, a half-filled block (U rows 8..15 read as zero, 8 columns of P stored).  Block b of the
+// launch belongs to adapter (plane) b / NB.  More than 6 blocks (a chunk of U is 8 KiB per block) keep ONE LDS slot and a
+// second barrier per chunk.  The instantiations of several adapters at another rank than 16 are held to two workgroups per CU for
+// their accumulators, and 16 blocks (four rank-64 adapters) take 16 tokens per wave: no scratch memory in any of them.
+template <int NAD, bool MASKED, int NB = 1, bool HALF = false>
+__global__ __launch_bounds__(256, (((NB == 1 && !HALF) || NAD == 1) ? 4 : 2)) void lora_project_kernel(ProjP p) {
+  constexpr int TB = NAD * NB;                     // 16-row blocks of U
+  constexpr int RB = TB <= 12 ? 2 : 1, KC = 128;
+  constexpr int RANK = HALF ? 8 : 16 * NB;
+  constexpr int SUB = TB * 16 * 128;               // one 64-column sub-tile of the U chunk: rows x 128 B
   constexpr int STAGE = 2 * SUB;
-  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
+  constexpr int NSLOT = TB <= 6 ? 2 : 1;
+  __shared__ __attribute__((aligned(16))) char smem[NSLOT * STAGE];
   const int y = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
   const int W = p.width[y], col0 = p.col0[y];
   const int tok0 = blockIdx.x * (4 * RB * 16) + wave * (RB * 16);
 
-  f32x4 acc[RB][NAD];
+  f32x4 acc[RB][TB];
   const bf16_t* xrow[RB];
   const uint8_t* brow[RB];
 #pragma unroll
@@ -195,17 +212,18 @@ __global__ __launch_bounds__(256, 4) void lora_project_kernel(ProjP p) {
     xrow[rb] = p.X + (long)m * p.ldx + col0;
     brow[rb] = MASKED ? p.bits + (long)m * p.bits_ld : nullptr;
 #pragma unroll
-    for (int a = 0; a < NAD; ++a) acc[rb][a] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < TB; ++b) acc[rb][b] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const int nchunks = (W + KC - 1) / KC;
   for (int c = 0; c < nchunks; ++c) {
     const int kc = c * KC;
-    uint4 ureg[NAD];
+    uint4 ureg[TB];
 #pragma unroll
-    for (int i = 0; i < NAD; ++i) {
+    for (int i = 0; i < TB; ++i) {
       const int pi = tid + 256 * i, row = pi >> 4, k = kc + (pi & 15) * 8;
-      const int a = y + (row >> 4);
-      ureg[i] = (k < W) ? *reinterpret_cast<const uint4*>(p.U[a] + (long)(row & 15) * p.ldu[a] + k) : make_uint4(0, 0, 0, 0);
+      const int a = y + (row >> 4) / NB;
+      const int ur = ((row >> 4) % NB) * 16 + (row & 15);
+      ureg[i] = (k < W && (!HALF || (row & 15) < 8)) ? *reinterpret_cast<const uint4*>(p.U[a] + (long)ur * p.ldu[a] + k) : make_uint4(0, 0, 0, 0);
     }
     uint4 xf[RB][4], bw[RB][NAD];
 #pragma unroll
@@ -220,9 +238,9 @@ __global__ __launch_bounds__(256, 4) void lora_project_kernel(ProjP p) {
         for (int a = 0; a < NAD; ++a) bw[rb][a] = *reinterpret_cast<const uint4*>(brow[rb] + (long)a * p.bits_stride + (kc >> 3));
       }
     }
-    char* st = smem + (c & 1) * STAGE;
+    char* st = smem + (NSLOT == 2 ? (c & 1) * STAGE : 0);
 #pragma unroll
-    for (int i = 0; i < NAD; ++i) {
+    for (int i = 0; i < TB; ++i) {
       const int pi = tid + 256 * i, row = pi >> 4, c16 = pi & 15;
       *reinterpret_cast<uint4*>(st + (c16 >> 3) * SUB + row * 128 + (((c16 & 7) ^ kc_g(row)) << 4)) = ureg[i];
     }
@@ -231,29 +249,36 @@ __global__ __launch_bounds__(256, 4) void lora_project_kernel(ProjP p) {
     for (int s = 0; s < 4; ++s) {
 #pragma unroll
       for (int a = 0; a < NAD; ++a) {
-        const int row = a * 16 + l15, ch = 4 * (s & 1) + g;
-        const bf16x8 uf = *reinterpret_cast<const bf16x8*>(st + (s >> 1) * SUB + row * 128 + ((ch ^ kc_g(row)) << 4));
+        uint4 xm[RB];      // the adapter's masked copy of the fragments: one plane for all of its NB blocks
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
-          uint4 x = xf[rb][s];
+          xm[rb] = xf[rb][s];
           if (MASKED) {
             const uint32_t wsel = s == 0 ? bw[rb][a].x : s == 1 ? bw[rb][a].y : s == 2 ? bw[rb][a].z : bw[rb][a].w;
-            x = drop_apply(x, (wsel >> (8 * g)) & 0xffu);
+            xm[rb] = drop_apply(xm[rb], (wsel >> (8 * g)) & 0xffu);
           }
-          acc[rb][a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uf, __builtin_bit_cast(bf16x8, x), acc[rb][a], 0, 0, 0);
+        }
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+          const int b = a * NB + nb, row = b * 16 + l15, ch = 4 * (s & 1) + g;
+          const bf16x8 uf = *reinterpret_cast<const bf16x8*>(st + (s >> 1) * SUB + row * 128 + ((ch ^ kc_g(row)) << 4));
+#pragma unroll
+          for (int rb = 0; rb < RB; ++rb)
+            acc[rb][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uf, __builtin_bit_cast(bf16x8, xm[rb]), acc[rb][b], 0, 0, 0);
         }
       }
     }
+    if (NSLOT == 1) __syncthreads();       // the one slot is re-written by the next chunk
   }
-  // lane holds P[token l15][16 (y + a) + 4 g .. + 3]
+  // lane holds P[token l15][RANK (y + a) + 16 nb + 4 g .. + 3]
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) {
     const int m = tok0 + 16 * rb + l15;
-    if (m < p.M) {
+    if (m < p.M && (!HALF || g < 2)) {
 #pragma unroll
-      for (int a = 0; a < NAD; ++a) {
-        const f32x4 v = acc[rb][a];
-        *reinterpret_cast<uint2*>(p.P + (long)m * p.ldp + 16 * (y + a) + 4 * g) =
+      for (int b = 0; b < TB; ++b) {
+        const f32x4 v = acc[rb][b];
+        *reinterpret_cast<uint2*>(p.P + (long)m * p.ldp + RANK * (y + b / NB) + 16 * (b % NB) + 4 * g) =
             make_uint2(pack_bf2(v[0] * p.alpha, v[1] * p.alpha), pack_bf2(v[2] * p.alpha, v[3] * p.alpha));
       }
     }
@@ -638,12 +663,16 @@ __device__ __forceinline__ void tr_pair(bf16x8 (&f)[2], uint32_t a0, uint32_t b0
 #ifndef UR_RED_ABLATE
 #define UR_RED_ABLATE 0     // lab (results WRONG when != 0): 1 = one LDS copy instead of one per adapter, 2 = no transposed reads / MFMAs,
 #endif                      // 3 = no flag-byte loads, 4 = no barriers, 5 = no global loads of X
-template <int NAD, bool MASKED>
+// Rank: V carries NB blocks of 16 columns per adapter (HALF = rank 8: 8 columns, staged into a 32-byte slot whose upper half is zero);
+// block b reads the masked copy of adapter b / NB.
+template <int NAD, bool MASKED, int NB = 1, bool HALF = false>
 __global__ __launch_bounds__(256) void lora_reduce_kernel(RedP p) {
-  constexpr int TOK = NAD <= 3 ? 128 : 64;          // tokens per step (two barriers per step)
+  constexpr int TB = NAD * NB;                       // 16-column blocks of V
+  constexpr int RANK = HALF ? 8 : 16 * NB;
+  constexpr int TOK = (NAD <= 3 && TB <= 4) ? 128 : 64;          // tokens per step (two barriers per step)
   constexpr int XP = TOK / 32;                       // X pieces (16 B) per thread and step
   constexpr int XT = TOK * 128;
-  constexpr int VROW = NAD * 32;
+  constexpr int VROW = TB * 32;
   __shared__ __attribute__((aligned(16))) char smem[NAD * XT + TOK * VROW];
   char* vt = smem + NAD * XT;
   const int e0 = blockIdx.z;
@@ -661,14 +690,14 @@ __global__ __launch_bounds__(256) void lora_reduce_kernel(RedP p) {
     prow[i] = pi >> 3; pch[i] = pi & 7;
     pcol[i] = min(cb + 8 * pch[i], W - 8);
   }
-  constexpr int VP = (TOK * 2 * NAD + 255) / 256;          // V pieces (16 B) per thread: TOK rows x 2 NAD pieces
+  constexpr int VP = (TOK * 2 * TB + 255) / 256;          // V pieces (16 B) per thread: TOK rows x 2 TB pieces
   int vrow[VP], vpart[VP];
   bool vthr[VP];
 #pragma unroll
   for (int i = 0; i < VP; ++i) {
     const int pi = tid + 256 * i;
-    vthr[i] = pi < TOK * 2 * NAD;
-    vrow[i] = pi / (2 * NAD); vpart[i] = pi % (2 * NAD);
+    vthr[i] = pi < TOK * 2 * TB;
+    vrow[i] = pi / (2 * TB); vpart[i] = pi % (2 * TB);
   }
 
   uint4 xr[XP], vr[VP];
@@ -687,13 +716,14 @@ __global__ __launch_bounds__(256) void lora_reduce_kernel(RedP p) {
 #pragma unroll
     for (int i = 0; i < VP; ++i) {
       vr[i] = make_uint4(0, 0, 0, 0);
-      if (vthr[i] && t0 + vrow[i] < tend) vr[i] = *reinterpret_cast<const uint4*>(p.V + (long)(t0 + vrow[i]) * p.ldv + 16 * e0 + 8 * vpart[i]);
+      if (vthr[i] && t0 + vrow[i] < tend && (!HALF || !(vpart[i] & 1)))
+        vr[i] = *reinterpret_cast<const uint4*>(p.V + (long)(t0 + vrow[i]) * p.ldv + (HALF ? 8 * (e0 + (vpart[i] >> 1)) : RANK * e0 + 8 * vpart[i]));
     }
   };
 
-  f32x4 acc[NAD];
+  f32x4 acc[TB];
 #pragma unroll
-  for (int a = 0; a < NAD; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int b = 0; b < TB; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int q = l15 >> 2, pp = lane & 3;
 
   if (tbeg < tend) gload(tbeg);
@@ -716,33 +746,34 @@ __global__ __launch_bounds__(256) void lora_reduce_kernel(RedP p) {
       const uint32_t xo = lds_off(smem) + ka * 128 + ((wave ^ f64sw(ka)) << 5) + pp * 8;
       const uint32_t vo = lds_off(vt) + ka * VROW + pp * 8;
 #pragma unroll
-      for (int a = 0; a < NAD; ++a) {
-        bf16x8 f[2];      // f[0] = X fragment (index: column), f[1] = V fragment (index: rank row j)
-        tr_pair(f, xo + a * XT, xo + a * XT + 4 * 128, vo + a * 32, vo + a * 32 + 4 * VROW);
+      for (int b = 0; b < TB; ++b) {
+        bf16x8 f[2];      // f[0] = X fragment (index: column) of adapter b / NB, f[1] = V fragment (index: rank row j of block b)
+        tr_pair(f, xo + (b / NB) * XT, xo + (b / NB) * XT + 4 * 128, vo + b * 32, vo + b * 32 + 4 * VROW);
         __builtin_amdgcn_sched_barrier(0);
         const bf16x8 fa = p.transposed ? f[1] : f[0], fb = p.transposed ? f[0] : f[1];
-        acc[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, acc[a], 0, 0, 0);
+        acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, acc[b], 0, 0, 0);
       }
     }
     if (UR_RED_ABLATE != 4) __syncthreads();
   }
-  // partial (or final) result of this token range, dense layout: entry e at goff[e], [16][W] or [W][16]
+  // partial (or final) result of this token range, dense layout: entry e at goff[e], [RANK][W] or [W][RANK]
   long total = 0;
   {
     const int ne = gridDim.z > 1 ? (int)gridDim.z : NAD;
-    total = p.goff[ne - 1] + 16L * p.width[gridDim.z > 1 ? ne - 1 : 0];
+    total = p.goff[ne - 1] + (long)RANK * p.width[gridDim.z > 1 ? ne - 1 : 0];
   }
   float* base = p.out + (long)blockIdx.y * total;
 #pragma unroll
-  for (int a = 0; a < NAD; ++a) {
-    float* ge = base + p.goff[e0 + a];
-    const f32x4 v = acc[a] * p.alpha;
-    if (p.transposed) {            // D[j = 4g+e][w = l15]  ->  G[w][j]
+  for (int b = 0; b < TB; ++b) {
+    float* ge = base + p.goff[e0 + b / NB];
+    const int j0 = 16 * (b % NB);
+    const f32x4 v = acc[b] * p.alpha;
+    if (p.transposed) {            // D[j = 4g+e][w = l15]  ->  G[w][j0 + j]
       const int w = cb + 16 * wave + l15;
-      if (w < W) *reinterpret_cast<float4*>(ge + (long)w * 16 + 4 * g) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {                       // D[w = 4g+e][j = l15]  ->  G[j][w]
+      if (w < W && (!HALF || g < 2)) *reinterpret_cast<float4*>(ge + (long)w * RANK + j0 + 4 * g) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {                       // D[w = 4g+e][j = l15]  ->  G[j0 + j][w]
       const int w = cb + 16 * wave + 4 * g;
-      if (w < W) *reinterpret_cast<float4*>(ge + (long)l15 * W + w) = make_float4(v[0], v[1], v[2], v[3]);
+      if (w < W && (!HALF || l15 < 8)) *reinterpret_cast<float4*>(ge + (long)(j0 + l15) * W + w) = make_float4(v[0], v[1], v[2], v[3]);
     }
   }
 }
@@ -971,75 +1002,92 @@ struct BgradP {
 #ifndef UR_BG_ABLATE
 #define UR_BG_ABLATE 0      // lab (tools/lab/bgrad_ablate.sh; results WRONG by construction): 1 = no dB phase, 2 = loads + tb MFMAs only, 3 = no cross-wave exchange / barriers
 #endif
+// Rank: NB blocks of 16 rank rows per entry over the SAME dy fragments (rank 32 -> 2, 64 -> 4 with 64 tokens per wave, so that the
+// tb accumulators stay in registers); HALF = rank 8 (B^T rows 8..15 and t columns 8..15 read as zero, 8 columns stored).  The dB
+// partials of the blocks leave one after the other through the one cross-wave buffer.
 constexpr int BG_TOK = 512, BG_WTOK = 128;
 constexpr int BG_XT = BG_WTOK * 128;                 // a wave's X tile: 128 tokens x 64 columns bf16
 constexpr int BG_SMEM = 4 * BG_XT + 4 * 16 * 64 * 4; // + cross-wave reduction of the [16 x 64] f32 partials
+constexpr int bg_wtok(int nb) { return nb <= 2 ? BG_WTOK : BG_WTOK / 2; }     // tokens per wave
+template <int NB = 1, bool HALF = false>
 __global__ __launch_bounds__(256, 2) void lora_bgrad_kernel(BgradP p) {
+  constexpr int WTOK = bg_wtok(NB), RBW = WTOK / 16, NK = WTOK / 32, XT = WTOK * 128;
+  constexpr int RANK = HALF ? 8 : 16 * NB;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int e = blockIdx.y;
   const int W = p.width[e], col0 = p.col0[e];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
   const int q = l15 >> 2, pp = lane & 3;
-  const int tok0 = blockIdx.x * BG_TOK + wave * BG_WTOK;
-  char* xt = smem + wave * BG_XT;
-  float* red = reinterpret_cast<float*>(smem + 4 * BG_XT);
+  const int tok0 = blockIdx.x * (4 * WTOK) + wave * WTOK;
+  char* xt = smem + wave * XT;
+  float* red = reinterpret_cast<float*>(smem + 4 * XT);
 
-  // t^T fragments of this wave's 128 tokens (MFMA row operand of the dB product: rank row j on l15, 8 tokens per lane):
-  // staged once through the wave's tile as [128 tokens][16] rows of 32 bytes, read back transposed
-  bf16x8 tT[4];
-  {
+  // t^T fragments of this wave's tokens (MFMA row operand of the dB product: rank row j on l15, 8 tokens per lane):
+  // staged once through the wave's tile as [tokens][16] rows of 32 bytes, read back transposed
+  bf16x8 tT[NB][NK];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+  for (int nb = 0; nb < NB; ++nb) {
+#pragma unroll
+    for (int i = 0; i < NK; ++i) {
       const int pi = lane + 64 * i, r = pi >> 1, part2 = pi & 1;
       const int m = tok0 + r;
       uint4 v = make_uint4(0, 0, 0, 0);
-      if (m < p.M) v = *reinterpret_cast<const uint4*>(p.V + (long)m * p.ldv + 16 * e + 8 * part2);
+      if (m < p.M && (!HALF || part2 == 0)) v = *reinterpret_cast<const uint4*>(p.V + (long)m * p.ldv + RANK * e + 16 * nb + 8 * part2);
       *reinterpret_cast<uint4*>(xt + r * 32 + part2 * 16) = v;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-    for (int k = 0; k < 4; k += 2) {
+    for (int k = 0; k < NK; k += 2) {
       bf16x8 f[2];
       const uint32_t a0 = lds_off(xt) + (32 * k + 8 * g + q) * 32 + pp * 8, a1 = a0 + 32 * 32;
       tr_pair(f, a0, a0 + 4 * 32, a1, a1 + 4 * 32);
-      tT[k] = f[0]; tT[k + 1] = f[1];
+      tT[nb][k] = f[0]; tT[nb][k + 1] = f[1];
     }
+    asm volatile("" ::: "memory");       // (the next block's staging writes stay behind these reads)
   }
-  f32x4 tb[8];
+  f32x4 tb[NB][RBW];
 #pragma unroll
-  for (int rb = 0; rb < 8; ++rb) tb[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const bf16_t* xrow[8];
+  for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-  for (int rb = 0; rb < 8; ++rb) xrow[rb] = p.X + (long)min(tok0 + 16 * rb + l15, p.M - 1) * p.ldx + col0;
+    for (int rb = 0; rb < RBW; ++rb) tb[nb][rb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const bf16_t* xrow[RBW];
+#pragma unroll
+  for (int rb = 0; rb < RBW; ++rb) xrow[rb] = p.X + (long)min(tok0 + 16 * rb + l15, p.M - 1) * p.ldx + col0;
   const bf16_t* urow = p.U[e] + (long)l15 * p.ldu[e];
+  const long ublk = 16 * p.ldu[e];
+  const bool uok = !HALF || l15 < 8;
   float* slab = p.slabs + (long)blockIdx.x * p.total + p.goff[e];
 
   for (int c0 = 0; c0 < W; c0 += 64) {
-    // this chunk's fragments: dy (token l15 of row block rb, 8 columns) and B^T (rank row l15, the same 8 columns)
-    uint4 xf[8][2], uf[2];
+    // this chunk's fragments: dy (token l15 of row block rb, 8 columns) and B^T (rank row l15 of every block, the same 8 columns)
+    uint4 xf[RBW][2], uf[NB][2];
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
       const int k = c0 + 32 * s2 + 8 * g;
       const bool ok = k < W;
 #if UR_BG_ABLATE >= 4
-      uf[s2] = *reinterpret_cast<const uint4*>(urow + k);
 #pragma unroll
-      for (int rb = 0; rb < 8; ++rb) xf[rb][s2] = *reinterpret_cast<const uint4*>(xrow[rb] + k);
+      for (int nb = 0; nb < NB; ++nb) uf[nb][s2] = *reinterpret_cast<const uint4*>(urow + nb * ublk + k);
+#pragma unroll
+      for (int rb = 0; rb < RBW; ++rb) xf[rb][s2] = *reinterpret_cast<const uint4*>(xrow[rb] + k);
 #else
-      uf[s2] = ok ? *reinterpret_cast<const uint4*>(urow + k) : make_uint4(0, 0, 0, 0);
 #pragma unroll
-      for (int rb = 0; rb < 8; ++rb) xf[rb][s2] = ok ? *reinterpret_cast<const uint4*>(xrow[rb] + k) : make_uint4(0, 0, 0, 0);   // (non-temporal measured slower here)
+      for (int nb = 0; nb < NB; ++nb) uf[nb][s2] = (ok && uok) ? *reinterpret_cast<const uint4*>(urow + nb * ublk + k) : make_uint4(0, 0, 0, 0);
+#pragma unroll
+      for (int rb = 0; rb < RBW; ++rb) xf[rb][s2] = ok ? *reinterpret_cast<const uint4*>(xrow[rb] + k) : make_uint4(0, 0, 0, 0);   // (non-temporal measured slower here)
 #endif
     }
     // (the previous chunk's transposed reads of this tile are complete: lgkmcnt(0) below precedes the MFMAs)
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-      for (int rb = 0; rb < 8; ++rb) {
+      for (int rb = 0; rb < RBW; ++rb) {
 #if UR_BG_ABLATE == 5
-        tb[rb][0] += __uint_as_float((xf[rb][s2].x ^ xf[rb][s2].y ^ xf[rb][s2].z ^ xf[rb][s2].w ^ uf[s2].x) & 0x3f800000u);
+        tb[0][rb][0] += __uint_as_float((xf[rb][s2].x ^ xf[rb][s2].y ^ xf[rb][s2].z ^ xf[rb][s2].w ^ uf[0][s2].x) & 0x3f800000u);
 #else
-        tb[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, uf[s2]), __builtin_bit_cast(bf16x8, xf[rb][s2]), tb[rb], 0, 0, 0);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+          tb[nb][rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, uf[nb][s2]), __builtin_bit_cast(bf16x8, xf[rb][s2]), tb[nb][rb], 0, 0, 0);
 #endif
         const int row = 16 * rb + l15, ch = 4 * s2 + g;
 #if UR_BG_ABLATE < 2
@@ -1050,11 +1098,13 @@ __global__ __launch_bounds__(256, 2) void lora_bgrad_kernel(BgradP p) {
     continue;
 #endif
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the wave's own writes have landed (private tile: no barrier)
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
     f32x4 db[4];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) db[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < NK; ++k) {
       const int ka = 32 * k + 8 * g + q;
 #pragma unroll
       for (int cb = 0; cb < 4; cb += 2) {
@@ -1066,8 +1116,8 @@ __global__ __launch_bounds__(256, 2) void lora_bgrad_kernel(BgradP p) {
         const uint32_t a0 = base + ((c0 ^ swk) << 4), b0 = base + 4 * 128 + ((c0 ^ swk ^ 4) << 4);
         const uint32_t a1 = base + ((c1 ^ swk) << 4), b1 = base + 4 * 128 + ((c1 ^ swk ^ 4) << 4);
         tr_pair(f, a0, b0, a1, b1);
-        db[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tT[k], f[0], db[cb], 0, 0, 0);            // D[j = 4g+e][w = l15]
-        db[cb + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tT[k], f[1], db[cb + 1], 0, 0, 0);
+        db[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tT[nb][k], f[0], db[cb], 0, 0, 0);            // D[j = 4g+e][w = l15]
+        db[cb + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tT[nb][k], f[1], db[cb + 1], 0, 0, 0);
       }
     }
 #if UR_BG_ABLATE == 3
@@ -1082,19 +1132,23 @@ __global__ __launch_bounds__(256, 2) void lora_bgrad_kernel(BgradP p) {
       const float4 r0 = *reinterpret_cast<const float4*>(red + tid * 4), r1 = *reinterpret_cast<const float4*>(red + 1024 + tid * 4);
       const float4 r2 = *reinterpret_cast<const float4*>(red + 2048 + tid * 4), r3 = *reinterpret_cast<const float4*>(red + 3072 + tid * 4);
       const int w = c0 + (tid >> 2);                        // element 4 tid = (w = tid / 4, j = 4 (tid % 4))
-      if (w < W)
-        *reinterpret_cast<float4*>(slab + (long)w * 16 + 4 * (tid & 3)) =
+      if (w < W && (!HALF || (tid & 3) < 2))
+        *reinterpret_cast<float4*>(slab + (long)w * RANK + 16 * nb + 4 * (tid & 3)) =
             make_float4(r0.x + r1.x + r2.x + r3.x, r0.y + r1.y + r2.y + r3.y, r0.z + r1.z + r2.z + r3.z, r0.w + r1.w + r2.w + r3.w);
     }
     __syncthreads();
+    }      // nb
   }
-  // tb: lane holds rows j = 4 g .. + 3 of token l15
+  // tb: lane holds rows j = 16 nb + 4 g .. + 3 of token l15
 #pragma unroll
-  for (int rb = 0; rb < 8; ++rb) {
+  for (int rb = 0; rb < RBW; ++rb) {
     const int m = tok0 + 16 * rb + l15;
-    if (m < p.M)
-      *reinterpret_cast<uint2*>(p.P + (long)m * p.ldp + 16 * e + 4 * g) =
-          make_uint2(pack_bf2(tb[rb][0] * p.alpha, tb[rb][1] * p.alpha), pack_bf2(tb[rb][2] * p.alpha, tb[rb][3] * p.alpha));
+    if (m < p.M && (!HALF || g < 2)) {
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb)
+        *reinterpret_cast<uint2*>(p.P + (long)m * p.ldp + RANK * e + 16 * nb + 4 * g) =
+            make_uint2(pack_bf2(tb[nb][rb][0] * p.alpha, tb[nb][rb][1] * p.alpha), pack_bf2(tb[nb][rb][2] * p.alpha, tb[nb][rb][3] * p.alpha));
+    }
   }
 }
 
@@ -1283,7 +1337,7 @@ __global__ __launch_bounds__(1024) void slab_sum_kernel(const float* __restrict_
 int validate_common(const ur_lora_args* a, const char* who) {
   UR_REQUIRE(a != nullptr, "%s: null args", who);
   UR_REQUIRE(a->M >= 0 && a->nad >= 1 && a->nad <= 4, "%s: M >= 0 and 1 <= nad <= 4 required (M=%d nad=%d)", who, a->M, a->nad);
-  UR_REQUIRE(a->rank == 16, "%s: the dedicated LoRA kernels are built for rank 16 (got %d)", who, a->rank);
+  UR_REQUIRE(a->rank == 8 || a->rank == 16 || a->rank == 32 || a->rank == 64, "%s: the LoRA kernels are built for the ranks 8, 16, 32 and 64 (got %d)", who, a->rank);
   UR_REQUIRE(a->X && UR_ALIGNED16(a->X) && (a->ldx % 8) == 0, "%s: X must be 16-byte aligned with ldx %% 8 == 0", who);
   const int ne = a->shared ? 1 : a->nad;
   for (int e = 0; e < ne; ++e) {
@@ -1323,10 +1377,10 @@ extern "C" int ur_lora_dropout_bits(uint64_t seed, float p, int32_t M, int32_t W
 
 extern "C" int ur_lora_project(const ur_lora_args* a, void* stream) {
   if (int rc = validate_common(a, "ur_lora_project")) return rc;
-  UR_REQUIRE(a->P && (((uintptr_t)a->P) & 7) == 0 && (a->ldp % 4) == 0 && a->ldp >= 16 * a->nad, "ur_lora_project: P must be 8-byte aligned, ldp %% 4 == 0, ldp >= 16 nad");
+  UR_REQUIRE(a->P && (((uintptr_t)a->P) & 7) == 0 && (a->ldp % 4) == 0 && a->ldp >= a->rank * a->nad, "ur_lora_project: P must be 8-byte aligned, ldp %% 4 == 0, ldp >= rank nad");
   for (int e = 0; e < a->nad; ++e)
     UR_REQUIRE(a->U[e] && UR_ALIGNED16(a->U[e]) && (a->ldu[e] % 8) == 0 && a->ldu[e] >= a->width[a->shared ? 0 : e],
-               "ur_lora_project: U[%d] must be a 16-byte aligned [16, width] bf16 matrix (ldu %% 8 == 0)", e);
+               "ur_lora_project: U[%d] must be a 16-byte aligned [rank, width] bf16 matrix (ldu %% 8 == 0)", e);
   if (a->M == 0) return 0;
   ProjP p;
   p.X = (const bf16_t*)a->X; p.ldx = a->ldx; p.M = a->M;
@@ -1340,7 +1394,7 @@ extern "C" int ur_lora_project(const ur_lora_args* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const unsigned gx = (unsigned)ur_cdiv(a->M, 128);
   const bool masked = a->drop_bits != nullptr;
-  bool ring = !a->shared || a->nad == 1;           // one adapter per entry, every width a multiple of 64: wave-private LDS-DMA rings
+  bool ring = (!a->shared || a->nad == 1) && a->rank == 16;      // one rank-16 adapter per entry, every width a multiple of 64: wave-private LDS-DMA rings
   for (int e = 0; ring && e < (a->shared ? 1 : a->nad); ++e) ring = (a->width[e] % 64) == 0;
   if (ring) {
     static std::atomic<uint64_t> attr_set[2];      // per device, per kernel
@@ -1352,17 +1406,18 @@ extern "C" int ur_lora_project(const ur_lora_args* a, void* stream) {
     dim3 grid((unsigned)ur_cdiv(a->M, 256), a->nad);
     if (masked) hipLaunchKernelGGL((lora_project_ring_kernel<true>), grid, dim3(256), P2_SMEM, st, p);
     else hipLaunchKernelGGL((lora_project_ring_kernel<false>), grid, dim3(256), P2_SMEM, st, p);
-  } else
-  if (!a->shared || a->nad == 1) {
-    dim3 grid(gx, a->nad);
-    if (masked) hipLaunchKernelGGL((lora_project_kernel<1, true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((lora_project_kernel<1, false>), grid, dim3(256), 0, st, p);
   } else {
-    dim3 grid(gx, 1);
-#define UR_PROJ(NAD)                                                                          \
-    if (masked) hipLaunchKernelGGL((lora_project_kernel<NAD, true>), grid, dim3(256), 0, st, p); \
-    else hipLaunchKernelGGL((lora_project_kernel<NAD, false>), grid, dim3(256), 0, st, p)
-    if (a->nad == 2) { UR_PROJ(2); } else if (a->nad == 3) { UR_PROJ(3); } else { UR_PROJ(4); }
+    // the register-staged kernel: (adapters that share X, 16-row blocks per adapter, rank 8) chosen by nad and rank
+    const int nad_k = (!a->shared || a->nad == 1) ? 1 : a->nad;
+    dim3 grid(nad_k * a->rank > 192 ? (unsigned)ur_cdiv(a->M, 64) : gx, nad_k == 1 ? a->nad : 1);      // (16 blocks of U: 64 tokens per workgroup)
+#define UR_PROJ(NAD, NB, HALF)                                                                          \
+    if (masked) hipLaunchKernelGGL((lora_project_kernel<NAD, true, NB, HALF>), grid, dim3(256), 0, st, p); \
+    else hipLaunchKernelGGL((lora_project_kernel<NAD, false, NB, HALF>), grid, dim3(256), 0, st, p)
+#define UR_PROJ_RANK(NAD)                                                                       \
+    if (a->rank == 8) { UR_PROJ(NAD, 1, true); } else if (a->rank == 16) { UR_PROJ(NAD, 1, false); } \
+    else if (a->rank == 32) { UR_PROJ(NAD, 2, false); } else { UR_PROJ(NAD, 4, false); }
+    if (nad_k == 1) { UR_PROJ_RANK(1) } else if (nad_k == 2) { UR_PROJ_RANK(2) } else if (nad_k == 3) { UR_PROJ_RANK(3) } else { UR_PROJ_RANK(4) }
+#undef UR_PROJ_RANK
 #undef UR_PROJ
   }
   UR_CHECK_LAUNCH("ur_lora_project");
@@ -1422,6 +1477,7 @@ extern "C" int ur_swiglu_lora_fwd(const void* gu, void* act, int32_t M, int32_t 
 // the ring kernel takes launches whose token count and every width are multiples of 128 / 64 and, under dropout, come with the
 // token-packed flags; (the split below is then a multiple of 128 tokens by construction)
 static inline bool lora_reduce_ring_ok(const ur_lora_args* a) {
+  if (a->rank != 16) return false;                 // the other ranks run the register-staged kernel, token-packed flags or not
   if ((a->M % 128) != 0 || a->M < 128) return false;
   const int ne = a->shared ? 1 : a->nad;
   for (int e = 0; e < ne; ++e)
@@ -1460,7 +1516,7 @@ static inline int lora_reduce_splits(const ur_lora_args* a) {
 }
 static inline int64_t lora_reduce_total(const ur_lora_args* a) {
   int64_t t = 0;
-  for (int e = 0; e < a->nad; ++e) t += 16LL * a->width[a->shared ? 0 : e];
+  for (int e = 0; e < a->nad; ++e) t += (int64_t)a->rank * a->width[a->shared ? 0 : e];
   return t;
 }
 
@@ -1479,15 +1535,17 @@ extern "C" int ur_lora_bits_transpose(const uint8_t* bits, int64_t bits_ld, int6
   return 0;
 }
 
+static inline bool lora_rank_ok(int r) { return r == 8 || r == 16 || r == 32 || r == 64; }
+
 extern "C" int64_t ur_lora_reduce_workspace_bytes(const ur_lora_args* a) {
-  if (!a || a->M <= 0 || a->nad < 1 || a->nad > 4) return 0;
+  if (!a || a->M <= 0 || a->nad < 1 || a->nad > 4 || !lora_rank_ok(a->rank)) return 0;
   const int splits = lora_reduce_splits(a);
   return splits > 1 ? (int64_t)splits * lora_reduce_total(a) * (int64_t)sizeof(float) : 0;
 }
 
 extern "C" int ur_lora_reduce(const ur_lora_args* a, void* workspace, int64_t workspace_bytes, void* stream) {
   if (int rc = validate_common(a, "ur_lora_reduce")) return rc;
-  UR_REQUIRE(a->V && UR_ALIGNED16(a->V) && (a->ldv % 8) == 0 && a->ldv >= 16 * a->nad, "ur_lora_reduce: V must be a 16-byte aligned [M, 16 nad] bf16 matrix");
+  UR_REQUIRE(a->V && UR_ALIGNED16(a->V) && (a->ldv % 8) == 0 && a->ldv >= a->rank * a->nad, "ur_lora_reduce: V must be a 16-byte aligned [M, rank nad] bf16 matrix");
   UR_REQUIRE(a->G && UR_ALIGNED16(a->G), "ur_lora_reduce: G must be 16-byte aligned");
   const int64_t total = lora_reduce_total(a);
   hipStream_t st = (hipStream_t)stream;
@@ -1508,7 +1566,7 @@ extern "C" int ur_lora_reduce(const ur_lora_args* a, void* workspace, int64_t wo
     const int s = a->shared ? 0 : (e < a->nad ? e : 0);
     p.col0[e] = a->col0[s]; p.width[e] = a->width[s];
     p.goff[e] = off;
-    if (e < a->nad) { off += 16L * a->width[s]; wmax = a->width[s] > wmax ? a->width[s] : wmax; }
+    if (e < a->nad) { off += (long)a->rank * a->width[s]; wmax = a->width[s] > wmax ? a->width[s] : wmax; }
   }
   p.V = (const bf16_t*)a->V; p.ldv = a->ldv;
   p.bits = (const uint8_t*)a->drop_bits; p.bits_ld = a->bits_ld; p.bits_stride = a->bits_stride;
@@ -1530,17 +1588,17 @@ extern "C" int ur_lora_reduce(const ur_lora_args* a, void* workspace, int64_t wo
     else { if (nad_k == 1) UR_RING(1, false); else if (nad_k == 2) UR_RING(2, false); else if (nad_k == 3) UR_RING(3, false); else UR_RING(4, false); }
 #undef UR_RING
     if (rc) return rc;
-  } else
-  if (!a->shared || a->nad == 1) {
-    dim3 grid(ur_cdiv(wmax, 64), splits, a->nad);
-    if (masked) hipLaunchKernelGGL((lora_reduce_kernel<1, true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((lora_reduce_kernel<1, false>), grid, dim3(256), 0, st, p);
   } else {
-    dim3 grid(ur_cdiv(wmax, 64), splits, 1);
-#define UR_RED(NAD)                                                                          \
-    if (masked) hipLaunchKernelGGL((lora_reduce_kernel<NAD, true>), grid, dim3(256), 0, st, p); \
-    else hipLaunchKernelGGL((lora_reduce_kernel<NAD, false>), grid, dim3(256), 0, st, p)
-    if (a->nad == 2) { UR_RED(2); } else if (a->nad == 3) { UR_RED(3); } else { UR_RED(4); }
+    const int nad_k = (!a->shared || a->nad == 1) ? 1 : a->nad;
+    dim3 grid(ur_cdiv(wmax, 64), splits, nad_k == 1 ? a->nad : 1);
+#define UR_RED(NAD, NB, HALF)                                                                          \
+    if (masked) hipLaunchKernelGGL((lora_reduce_kernel<NAD, true, NB, HALF>), grid, dim3(256), 0, st, p); \
+    else hipLaunchKernelGGL((lora_reduce_kernel<NAD, false, NB, HALF>), grid, dim3(256), 0, st, p)
+#define UR_RED_RANK(NAD)                                                                      \
+    if (a->rank == 8) { UR_RED(NAD, 1, true); } else if (a->rank == 16) { UR_RED(NAD, 1, false); } \
+    else if (a->rank == 32) { UR_RED(NAD, 2, false); } else { UR_RED(NAD, 4, false); }
+    if (nad_k == 1) { UR_RED_RANK(1) } else if (nad_k == 2) { UR_RED_RANK(2) } else if (nad_k == 3) { UR_RED_RANK(3) } else { UR_RED_RANK(4) }
+#undef UR_RED_RANK
 #undef UR_RED
   }
   UR_CHECK_LAUNCH("ur_lora_reduce");
@@ -1552,22 +1610,25 @@ extern "C" int ur_lora_reduce(const ur_lora_args* a, void* workspace, int64_t wo
   return 0;
 }
 
+// tokens per block of the register-staged bgrad kernel (rank 64: 64 tokens per wave)
+static inline int lora_bgrad_tok(int rank) { return 4 * bg_wtok(rank / 16); }
+
 extern "C" int64_t ur_lora_bgrad_workspace_bytes(const ur_lora_args* a) {
-  if (!a || a->M <= 0 || a->nad < 1 || a->nad > 4) return 0;
+  if (!a || a->M <= 0 || a->nad < 1 || a->nad > 4 || !lora_rank_ok(a->rank)) return 0;
   int64_t total = 0;
-  for (int e = 0; e < a->nad; ++e) total += 16LL * a->width[e];
-  return (int64_t)ur_cdiv(a->M, BG_TOK) * total * (int64_t)sizeof(float);
+  for (int e = 0; e < a->nad; ++e) total += (int64_t)a->rank * a->width[e];
+  return (int64_t)ur_cdiv(a->M, lora_bgrad_tok(a->rank)) * total * (int64_t)sizeof(float);
 }
 
 extern "C" int ur_lora_bgrad(const ur_lora_args* a, void* workspace, int64_t workspace_bytes, void* stream) {
   if (int rc = validate_common(a, "ur_lora_bgrad")) return rc;
   UR_REQUIRE(!a->shared && !a->drop_bits, "ur_lora_bgrad: adapters own column ranges of X (shared = 0), no dropout planes");
-  UR_REQUIRE(a->P && (((uintptr_t)a->P) & 7) == 0 && (a->ldp % 4) == 0 && a->ldp >= 16 * a->nad, "ur_lora_bgrad: P must be 8-byte aligned, ldp %% 4 == 0, ldp >= 16 nad");
-  UR_REQUIRE(a->V && UR_ALIGNED16(a->V) && (a->ldv % 8) == 0 && a->ldv >= 16 * a->nad, "ur_lora_bgrad: V must be a 16-byte aligned [M, 16 nad] bf16 matrix");
+  UR_REQUIRE(a->P && (((uintptr_t)a->P) & 7) == 0 && (a->ldp % 4) == 0 && a->ldp >= a->rank * a->nad, "ur_lora_bgrad: P must be 8-byte aligned, ldp %% 4 == 0, ldp >= rank nad");
+  UR_REQUIRE(a->V && UR_ALIGNED16(a->V) && (a->ldv % 8) == 0 && a->ldv >= a->rank * a->nad, "ur_lora_bgrad: V must be a 16-byte aligned [M, rank nad] bf16 matrix");
   UR_REQUIRE(a->G && UR_ALIGNED16(a->G), "ur_lora_bgrad: G must be 16-byte aligned");
   for (int e = 0; e < a->nad; ++e)
     UR_REQUIRE(a->U[e] && UR_ALIGNED16(a->U[e]) && (a->ldu[e] % 8) == 0 && a->ldu[e] >= a->width[e],
-               "ur_lora_bgrad: U[%d] must be a 16-byte aligned [16, width] bf16 matrix (ldu %% 8 == 0)", e);
+               "ur_lora_bgrad: U[%d] must be a 16-byte aligned [rank, width] bf16 matrix (ldu %% 8 == 0)", e);
   hipStream_t st = (hipStream_t)stream;
   BgradP p;
   long off = 0;
@@ -1575,7 +1636,7 @@ extern "C" int ur_lora_bgrad(const ur_lora_args* a, void* workspace, int64_t wor
     const int s = e < a->nad ? e : 0;
     p.col0[e] = a->col0[s]; p.width[e] = a->width[s]; p.goff[e] = off;
     p.U[e] = (const bf16_t*)a->U[s]; p.ldu[e] = a->ldu[s];
-    if (e < a->nad) off += 16L * a->width[s];
+    if (e < a->nad) off += (long)a->rank * a->width[s];
   }
   const int64_t total = off;
   if (a->M == 0) {
@@ -1591,21 +1652,26 @@ extern "C" int ur_lora_bgrad(const ur_lora_args* a, void* workspace, int64_t wor
   p.slabs = (float*)workspace; p.total = total; p.alpha = a->alpha;
   // every width a multiple of 64 (the decoder's are): dy goes through the LDS-DMA ring, in blocks of 1024 tokens where that still
   // gives every CU a block (half the slabs), else 512; ragged widths keep the register-staged kernel
-  bool ring = true;
+  bool ring = a->rank == 16;                       // (the other ranks keep the register-staged kernel)
   for (int e = 0; e < a->nad; ++e) ring = ring && (a->width[e] % 64) == 0;
   const int kind = !ring ? 0 : ((long)ur_cdiv(a->M, 1024) * a->nad >= ur_device_cu_count() ? 2 : 1);
-  const void* fn = kind == 0 ? reinterpret_cast<const void*>(&lora_bgrad_kernel)
-                 : kind == 1 ? reinterpret_cast<const void*>(&lora_bgrad_ring_kernel<2>) : reinterpret_cast<const void*>(&lora_bgrad_ring_kernel<4>);
-  const int smem = kind == 0 ? BG_SMEM : b2_smem(kind == 1 ? 2 : 4);
-  static std::atomic<uint64_t> attr_set[3];      // per device, per kernel
-  UR_ONCE_PER_DEVICE(attr_set[kind]) {
+  const int rk = a->rank == 8 ? 0 : a->rank == 16 ? 1 : a->rank == 32 ? 2 : 3;      // register-staged instantiation
+  const void* fn = kind == 1 ? reinterpret_cast<const void*>(&lora_bgrad_ring_kernel<2>) : kind == 2 ? reinterpret_cast<const void*>(&lora_bgrad_ring_kernel<4>)
+                 : rk == 0 ? reinterpret_cast<const void*>(&lora_bgrad_kernel<1, true>) : rk == 1 ? reinterpret_cast<const void*>(&lora_bgrad_kernel<1, false>)
+                 : rk == 2 ? reinterpret_cast<const void*>(&lora_bgrad_kernel<2, false>) : reinterpret_cast<const void*>(&lora_bgrad_kernel<4, false>);
+  const int smem = kind == 0 ? BG_SMEM : b2_smem(kind == 1 ? 2 : 4);      // (rank 64: half the token tile; the attribute may be larger than the launch)
+  static std::atomic<uint64_t> attr_set[6];      // per device, per kernel
+  UR_ONCE_PER_DEVICE(attr_set[kind == 0 ? 2 + rk : kind - 1]) {
     hipError_t er = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (er != hipSuccess) UR_FAIL((int)er, "ur_lora_bgrad: hipFuncSetAttribute failed: %s", hipGetErrorString(er));
   }
-  const int nblk = ur_cdiv(a->M, kind == 2 ? 1024 : BG_TOK);
+  const int nblk = ur_cdiv(a->M, kind == 2 ? 1024 : kind == 1 ? BG_TOK : lora_bgrad_tok(a->rank));
   if (kind == 2) hipLaunchKernelGGL(lora_bgrad_ring_kernel<4>, dim3(nblk, a->nad), dim3(256), smem, st, p);
   else if (kind == 1) hipLaunchKernelGGL(lora_bgrad_ring_kernel<2>, dim3(nblk, a->nad), dim3(256), smem, st, p);
-  else hipLaunchKernelGGL(lora_bgrad_kernel, dim3(nblk, a->nad), dim3(256), BG_SMEM, st, p);
+  else if (rk == 0) hipLaunchKernelGGL((lora_bgrad_kernel<1, true>), dim3(nblk, a->nad), dim3(256), BG_SMEM, st, p);
+  else if (rk == 1) hipLaunchKernelGGL((lora_bgrad_kernel<1, false>), dim3(nblk, a->nad), dim3(256), BG_SMEM, st, p);
+  else if (rk == 2) hipLaunchKernelGGL((lora_bgrad_kernel<2, false>), dim3(nblk, a->nad), dim3(256), BG_SMEM, st, p);
+  else hipLaunchKernelGGL((lora_bgrad_kernel<4, false>), dim3(nblk, a->nad), dim3(256), BG_SMEM, st, p);
   UR_CHECK_LAUNCH("ur_lora_bgrad");
   const long total4 = total / 4;
   hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((total4 + 63) / 64)), dim3(1024), 0, st, (const float*)workspace, (float*)a->G, total4, nblk);

@@ -358,7 +358,16 @@ def gemm_persistent_mode(mode):
     return int(_lib.load().ur_gemm_persistent_mode(int(mode)))
 
 
-# ---- LoRA adapter products (rank 16): include/unirec_hip.h, csrc/lora.hip ---------------------------
+# ---- LoRA adapter products (ranks 8, 16, 32, 64): include/unirec_hip.h, csrc/lora.hip ---------------
+LORA_RANKS = (8, 16, 32, 64)      # what ur_lora_project / ur_lora_reduce / ur_lora_bgrad are built for
+
+
+def _lora_rank(r, who):
+    if int(r) not in LORA_RANKS:
+        raise ValueError(f"{who}: LoRA rank {int(r)} is not supported (supported ranks: {', '.join(map(str, LORA_RANKS))})")
+    return int(r)
+
+
 def lora_bits_ld(W):
     return int(_lib.load().ur_lora_bits_ld(int(W)))
 
@@ -402,12 +411,12 @@ def lora_bits_to_keep(bits, W):
     return (1 - dropped).reshape(nad, M, ld * 8)[:, :, :W].to(torch.uint8)
 
 
-def _lora_args(X, cols, shared, bits, alpha):
+def _lora_args(X, cols, shared, bits, alpha, rank=16):
     a = LoraArgs()
     if X.dtype != BF16 or not X.is_cuda or X.dim() != 2 or X.stride(1) != 1:
         raise ValueError("lora: X must be a 2-D bf16 device tensor with unit inner stride")
     a.X, a.ldx, a.M = X.data_ptr(), X.stride(0), X.shape[0]
-    a.nad, a.rank, a.shared = len(cols), 16, int(shared)
+    a.nad, a.rank, a.shared = len(cols), int(rank), int(shared)
     for e, (c0, w) in enumerate(cols):
         a.col0[e], a.width[e] = int(c0), int(w)
     if bits is not None:
@@ -422,20 +431,21 @@ def _cols_bytes(X, cols):
 
 @_stream_family("lora_project", lambda r, X, U, cols=None, alpha=1.0, bits=None, out=None: _cols_bytes(X, cols) + _nb(r) + (_nb(bits) if bits is not None else 0))
 def lora_project(X, U, cols=None, alpha=1.0, bits=None, out=None):
-    """P[m, 16a+j] = alpha * sum_w keep_a(m,w) X[m, c0_a+w] U_a[j,w].  U: list of bf16 [16, width_a] matrices.
-    cols=None: the adapters share all of X's columns (optionally with dropout bit planes `bits`);
+    """P[m, r a+j] = alpha * sum_w keep_a(m,w) X[m, c0_a+w] U_a[j,w].  U: list of bf16 [r, width_a] matrices, r = U[0].shape[0]
+    in LORA_RANKS.  cols=None: the adapters share all of X's columns (optionally with dropout bit planes `bits`);
     cols=[(c0, width), ...]: adapter a owns that column range of X."""
     lib = _lib.load()
     shared = cols is None
     if shared:
         cols = [(0, X.shape[1])] * len(U)
-    a = _lora_args(X, cols, shared, bits, alpha)
+    r = _lora_rank(U[0].shape[0], "lora_project")
+    a = _lora_args(X, cols, shared, bits, alpha, r)
     for e, u in enumerate(U):
-        if u.dtype != BF16 or u.shape[0] != 16 or u.stride(1) != 1 or u.shape[1] != cols[e][1]:
-            raise ValueError("lora_project: U[a] must be bf16 [16, width_a]")
+        if u.dtype != BF16 or u.dim() != 2 or u.shape[0] != r or u.stride(1) != 1 or u.shape[1] != cols[e][1]:
+            raise ValueError(f"lora_project: U[a] must be bf16 [{r}, width_a]")
         a.U[e], a.ldu[e] = u.data_ptr(), u.stride(0)
     if out is None:
-        out = torch.empty((X.shape[0], 16 * len(U)), dtype=BF16, device=X.device)
+        out = torch.empty((X.shape[0], r * len(U)), dtype=BF16, device=X.device)
     a.P, a.ldp = out.data_ptr(), out.stride(0)
     check(lib.ur_lora_project(ctypes.byref(a), _stream()), "ur_lora_project")
     return out
@@ -480,22 +490,31 @@ def rmsnorm_lora_fwd(x, w, eps, U, alpha=1.0, bits=None):
     return out, rstd, t
 
 
+def _reduce_rank(out, X, cols, nad):
+    """rank of a token reduction = rows of its dense output per input column"""
+    wsum = sum(w for _, w in cols) if cols is not None else X.shape[1] * int(nad)
+    return out.numel() // max(wsum, 1)
+
+
 @_stream_family("lora_reduce", lambda r, X, V, out, cols=None, nad=None, alpha=1.0, bits=None, transposed=False, bits_t=None:
-                _cols_bytes(X, cols) + X.shape[0] * 2 * 16 * (len(cols) if cols is not None else int(nad)) + (_nb(bits) if bits is not None else 0))
+                _cols_bytes(X, cols) + X.shape[0] * 2 * _reduce_rank(out, X, cols, nad) * (len(cols) if cols is not None else int(nad)) + (_nb(bits) if bits is not None else 0))
 def lora_reduce(X, V, out, cols=None, nad=None, alpha=1.0, bits=None, transposed=False, bits_t=None):
-    """G_a[j,w] = alpha * sum_m V[m,16a+j] keep_a(m,w) X[m, c0_a+w] into the dense f32 tensor `out`
-    ([16 nad, W] for shared columns, or [sum width, 16] with transposed=True for per-adapter column ranges).
-    bits_t: lora_bits_transpose(bits, W) -- with it the launch streams X through the LDS-DMA ring kernel."""
+    """G_a[j,w] = alpha * sum_m V[m,r a+j] keep_a(m,w) X[m, c0_a+w] into the dense f32 tensor `out`
+    ([r nad, W] for shared columns, or [sum width, r] with transposed=True for per-adapter column ranges); the rank r in LORA_RANKS is
+    what the size of `out` says.  bits_t: lora_bits_transpose(bits, W) -- with it a rank-16 launch streams X through the LDS-DMA ring
+    kernel (the other ranks run the register-staged kernel either way)."""
     lib = _lib.load()
     shared = cols is None
+    r = _reduce_rank(out, X, cols, nad)
     if shared:
         cols = [(0, X.shape[1])] * int(nad)
-    a = _lora_args(X, cols, shared, bits, alpha)
-    if V.dtype != BF16 or V.stride(1) != 1 or V.shape[0] != X.shape[0] or V.shape[1] < 16 * len(cols):
-        raise ValueError("lora_reduce: V must be bf16 [M, >= 16 nad]")
-    _need(out, F32, "out")
-    if out.numel() != 16 * sum(w for _, w in cols):
+    if out.numel() != r * sum(w for _, w in cols):
         raise ValueError("lora_reduce: out has the wrong size")
+    r = _lora_rank(r, "lora_reduce")
+    a = _lora_args(X, cols, shared, bits, alpha, r)
+    if V.dtype != BF16 or V.stride(1) != 1 or V.shape[0] != X.shape[0] or V.shape[1] < r * len(cols):
+        raise ValueError(f"lora_reduce: V must be bf16 [M, >= {r} nad]")
+    _need(out, F32, "out")
     a.V, a.ldv = V.data_ptr(), V.stride(0)
     a.G, a.g_transposed = out.data_ptr(), int(transposed)
     if bits is not None and bits_t is not None:
@@ -1042,23 +1061,24 @@ def rank_of_index(scores, gt_index):
     return rank
 
 
-@_stream_family("lora_bgrad", lambda r, dy, t, Bt, cols, gB, alpha=1.0, out=None: _cols_bytes(dy, cols) + 2 * dy.shape[0] * 2 * 16 * len(cols))
+@_stream_family("lora_bgrad", lambda r, dy, t, Bt, cols, gB, alpha=1.0, out=None: _cols_bytes(dy, cols) + 2 * dy.shape[0] * 2 * Bt[0].shape[0] * len(cols))
 def lora_bgrad(dy, t, Bt, cols, gB, alpha=1.0, out=None):
-    """One pass over dy: returns tb [M, 16 nad] = alpha * dy_a B_a (Bt: list of B_a^T [16, width_a]) and fills
-    gB [sum width, 16] f32 with dB_a = dy_a^T t_a (adapter a owns columns cols[a] of dy, t holds t_a at columns 16a)."""
+    """One pass over dy: returns tb [M, r nad] = alpha * dy_a B_a (Bt: list of B_a^T [r, width_a], r in LORA_RANKS) and fills
+    gB [sum width, r] f32 with dB_a = dy_a^T t_a (adapter a owns columns cols[a] of dy, t holds t_a at columns r a)."""
     lib = _lib.load()
-    a = _lora_args(dy, cols, False, None, alpha)
+    r = _lora_rank(Bt[0].shape[0], "lora_bgrad")
+    a = _lora_args(dy, cols, False, None, alpha, r)
     for e, u in enumerate(Bt):
-        if u.dtype != BF16 or u.shape[0] != 16 or u.stride(1) != 1 or u.shape[1] != cols[e][1]:
-            raise ValueError("lora_bgrad: Bt[a] must be bf16 [16, width_a]")
+        if u.dtype != BF16 or u.dim() != 2 or u.shape[0] != r or u.stride(1) != 1 or u.shape[1] != cols[e][1]:
+            raise ValueError(f"lora_bgrad: Bt[a] must be bf16 [{r}, width_a]")
         a.U[e], a.ldu[e] = u.data_ptr(), u.stride(0)
-    if t.dtype != BF16 or t.stride(1) != 1 or t.shape[0] != dy.shape[0] or t.shape[1] < 16 * len(cols):
-        raise ValueError("lora_bgrad: t must be bf16 [M, >= 16 nad]")
+    if t.dtype != BF16 or t.stride(1) != 1 or t.shape[0] != dy.shape[0] or t.shape[1] < r * len(cols):
+        raise ValueError(f"lora_bgrad: t must be bf16 [M, >= {r} nad]")
     _need(gB, F32, "gB")
-    if gB.numel() != 16 * sum(w for _, w in cols):
+    if gB.numel() != r * sum(w for _, w in cols):
         raise ValueError("lora_bgrad: gB has the wrong size")
     if out is None:
-        out = torch.empty((dy.shape[0], 16 * len(cols)), dtype=BF16, device=dy.device)
+        out = torch.empty((dy.shape[0], r * len(cols)), dtype=BF16, device=dy.device)
     a.V, a.ldv = t.data_ptr(), t.stride(0)
     a.P, a.ldp = out.data_ptr(), out.stride(0)
     a.G, a.g_transposed = gB.data_ptr(), 1

@@ -100,6 +100,26 @@ class _TokenTable(nn.Module):
 # down-projection launch and one A^T.  (key of the group's t / bits entries in saved["layers"][i], its projections)
 ADAPTER_GROUPS = (("qkv", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")), ("o", ("self_attn.o_proj",)),
                   ("gu", ("mlp.gate_proj", "mlp.up_proj")), ("d", ("mlp.down_proj",)))
+# What the persistent GEMM takes as a LoRA second K range: ONE K tile (csrc/gemm_pers.hip, `supported`: K2 <= BK = 64).  The library
+# has no query for it; this is the one host-side statement of that constant.
+PERS_GEMM_K2_MAX = 64
+_MAX_SHARED_ADAPTERS = max(len(projs) for _, projs in ADAPTER_GROUPS)      # q|k|v: the widest merged launch
+
+
+def lora_rank_rule(r, sw=switches):
+    """The launch choices that depend on the LoRA rank: a pure function of (rank, switches), read by Qwen3LoRAModel._plan.
+      merged      q|k|v and gate|up leave as one launch each while the merged launch's second K range (adapters * r) still fits the
+                  persistent GEMM; otherwise one launch per adapter (K2 = r <= 64 each)
+      fuse_norm   RMSNorm + down projection as one kernel (ur_rmsnorm_lora_fwd: rank 16)
+      swiglu_lora SwiGLU + the down adapter's down projection as one kernel (ur_swiglu_lora_fwd: rank 16)
+      bits_t      token-packed dropout flags: only the rank-16 ring kernel of ur_lora_reduce consumes them"""
+    r = int(r)
+    return {"merged": bool(sw.merge_proj) and _MAX_SHARED_ADAPTERS * r <= PERS_GEMM_K2_MAX,
+            "fuse_norm": bool(sw.fuse_norm_lora) and r == 16,
+            "swiglu_lora": bool(sw.fuse_swiglu_lora) and r == 16,
+            "bits_t": bool(sw.bits_t) and r == 16}
+
+
 _QK_FUSE_MAX_RATIO = 4.0      # largest |w_d| / |w_{d+64}| spread of a rotate-half pair of the q / k norm weights under which the fused epilogue is used
 
 
@@ -126,11 +146,6 @@ class _Plan:
     bits_t: bool            # backward: token-packed dropout flags for the token reductions that have no prefetched copy
 
 
-def _split_k(red, out_rows, out_cols):
-    tiles = ((out_rows + 127) // 128) * ((out_cols + 127) // 128)
-    return int(max(1, min(1024 // max(tiles, 1), red // 512, 128)))
-
-
 class _JointFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, item_tokens16, input_ids, mask_u8, first_special_id, anchor):
@@ -153,6 +168,9 @@ class Qwen3LoRAModel(nn.Module):
         self.config = config
         r = config.lora_r if use_lora else 0
         self.use_lora = r > 0
+        if self.use_lora and int(r) not in hip.LORA_RANKS:
+            raise ValueError(f"Qwen3LoRAModel: lora_r = {r} is not supported; the adapter kernels are built for the ranks "
+                             f"{', '.join(map(str, hip.LORA_RANKS))} (one rank for all modules: no rank_pattern)")
         self.embed_tokens = _TokenTable(config.vocab_size, config.hidden_size)
         self.layers = nn.ModuleList([_Layer(config, r) for _ in range(config.num_hidden_layers)])
         self.norm = _Norm(config.hidden_size)
@@ -389,7 +407,7 @@ class Qwen3LoRAModel(nn.Module):
         this step's (`_prefetch_next_step`), under the Q-Former's backward.  The planes are allocated on the caller's stream (the
         caching allocator keys blocks by stream) and written on the side stream after it has caught up with the caller's stream."""
         p = self._drop_p()
-        if p <= 0.0 or self.config.lora_r != 16 or not torch.is_grad_enabled():
+        if p <= 0.0 or not torch.is_grad_enabled():
             self._release_prefetched(device)
             return
         pre = self._bits_pre
@@ -403,7 +421,7 @@ class Qwen3LoRAModel(nn.Module):
                   for i in range(self.config.num_hidden_layers) for g, (W, outs) in enumerate(self._group_dims())}
         # token-packed copies for the backward's token reductions (hip.lora_reduce's ring kernel), made on the side stream as well
         packed = {}
-        if M % 128 == 0 and switches.bits_t:
+        if M % 128 == 0 and lora_rank_rule(self.config.lora_r)["bits_t"]:
             packed = {(i, g): torch.empty((len(outs), M // 32, hip.lora_bits_t_ld(W)), dtype=torch.int32, device=device)
                       for i in range(self.config.num_hidden_layers) for g, (W, outs) in enumerate(self._group_dims()) if W % 64 == 0}
         self._bits_stream.wait_stream(main)
@@ -499,11 +517,6 @@ class Qwen3LoRAModel(nn.Module):
     def _lora_down(self, xin, a_names, pack, sc, seed, p, pre=None, row0=0):
         """(t, bits): t[M, nb*r] = s * dropout_j(x) A_j^T for the nb adapters that share the input x (one dropped-flag
         bit plane per adapter, generated once here and kept for the backward)."""
-        if self.config.lora_r != 16:
-            if p > 0.0:
-                raise hip._lib.UniRecHipError("LoRA dropout is implemented for rank 16 (the reference's r) only")
-            A = pack.fused16(a_names) if len(a_names) > 1 else pack.w16(a_names[0])
-            return hip.gemm(xin, A, alpha=sc), None
         bits = pre
         if bits is None and p > 0.0:
             bits = hip.lora_dropout_bits(seed, p, xin.shape[0], xin.shape[1], len(a_names), xin.device, row0=row0)
@@ -516,7 +529,8 @@ class Qwen3LoRAModel(nn.Module):
         D, I, hd, r = c.hidden_size, c.intermediate_size, c.head_dim, c.lora_r
         NQ, NKV = c.num_attention_heads * hd, c.num_key_value_heads * hd
         lora = pack is not None
-        merged = not lora or (sw.merge_proj and r == 16)
+        rule = lora_rank_rule(r, sw)
+        merged = not lora or rule["merged"]
         # q/k-norm + RoPE inside the q|k|v launch (the raw q, k are never written or re-read) when the persistent GEMM takes it
         fuse_rope = (sw.fuse_qk_rope and hd == 128 and fz["qk_norm_fusable"] and merged and
                      hip.gemm_qkrope_supported(M, NQ + 2 * NKV, D, 3 * r if lora else 0, S, NQ, NKV, dev))
@@ -525,7 +539,7 @@ class Qwen3LoRAModel(nn.Module):
             swiglu = "up"
         elif lora and merged and sw.fuse_swiglu_gemm and I % 128 == 0 and hip.gemm_swiglu_paired_supported(M, I, D, 2 * r, dev):
             swiglu = "pair"
-        elif lora and sw.fuse_swiglu_lora and r == 16 and I % 128 == 0:
+        elif lora and rule["swiglu_lora"] and I % 128 == 0:
             swiglu = "lora"
         # the attention output's rows are padded by 64 columns when their length is a power of two: the kernels that stream it
         # in 128-byte column chunks (the o_proj adapter's projection and its token reduction) otherwise keep every request in
@@ -534,9 +548,9 @@ class Qwen3LoRAModel(nn.Module):
         # switches.rope_bwd_fused unset: from the roped outputs only
         in_dq = hd == 128 and (sw.rope_bwd_fused is not False if fuse_rope else sw.rope_bwd_fused is True)
         mlp_recompute = None if not merged else ("pair" if swiglu == "pair" else ("merged" if lora else "plain"))
-        return _Plan(merged=merged, fuse_norm=sw.fuse_norm_lora and lora and r == 16 and D == 1024, fuse_rope=fuse_rope, swiglu=swiglu,
+        return _Plan(merged=merged, fuse_norm=rule["fuse_norm"] and lora and D == 1024, fuse_rope=fuse_rope, swiglu=swiglu,
                      pad_att=pad_att, bits_one_event=sw.bits_one_event, mlp_recompute=mlp_recompute, rope_bwd_in_dq=in_dq,
-                     rope_k_in_dkv=sw.rope_k_fused, bits_t=sw.bits_t and M % 128 == 0)
+                     rope_k_in_dkv=sw.rope_k_fused, bits_t=(rule["bits_t"] if lora else sw.bits_t) and M % 128 == 0)
 
     def _forward_impl(self, item_tokens16, input_ids, mask_u8, first_special_id, keep=True):
         c = self.config
@@ -682,7 +696,7 @@ class Qwen3LoRAModel(nn.Module):
         touched = []
 
         pdrop, step = saved["pdrop"], saved["step"]
-        lt = self._lora_transposes(pack) if (pack is not None and r == 16) else None      # name(s) -> transposed bf16 operand
+        lt = self._lora_transposes(pack) if pack is not None else None      # name(s) -> transposed bf16 operand
 
         packed_bits = saved.get("bits_t", {})
         if saved.get("bits_t_event") is not None:
@@ -696,14 +710,6 @@ class Qwen3LoRAModel(nn.Module):
             nb = len(bnames)
             touched.extend(bnames + a_names)
             gA = pack.fusedg(a_names) if nb > 1 else pack.g32(a_names[0])
-            if r != 16:           # generic tiles (no dropout: _lora_down refused it)
-                tb = torch.empty((M, nb * r), dtype=BF16, device=dev)
-                for j, (bname, (c0, n)) in enumerate(zip(bnames, cols)):
-                    dyp = dy[:, c0:c0 + n]
-                    hip.gemm(dyp, t[:, j * r:(j + 1) * r], r_kcontig=False, s_kcontig=False, out=pack.g32(bname), split_k=_split_k(M, n, r))
-                    hip.gemm(dyp, pack.w16(bname), s_kcontig=False, out=tb[:, j * r:(j + 1) * r], alpha=sc)
-                hip.gemm(tb, xin, r_kcontig=False, s_kcontig=False, out=gA, split_k=_split_k(M, nb * r, xin.shape[1]))
-                return tb
             gB = pack.fusedg(bnames) if nb > 1 else pack.g32(bnames[0])            # [sum n, r]: adapter ranges in order
             tb = hip.lora_bgrad(dy, t, [lt[b] for b in bnames], cols, gB, alpha=sc)     # dB and tb, dy read once
             bits_t = packed_bits.get((i, g)) if bits is not None else None             # the prefetched token-packed flags
@@ -722,10 +728,7 @@ class Qwen3LoRAModel(nn.Module):
                 key, a_names = ADAPTER_GROUPS[g][0], self._names[i][g].a
                 bits = L["bits_" + key]
                 tb = lora_grads(dy, L["t_" + key], xin, i, g, bits)
-                if lt is not None:
-                    AT = lt[a_names]
-                else:
-                    AT = hip.transpose_bf16(pack.fused16(a_names) if len(a_names) > 1 else pack.w16(a_names[0]))
+                AT = lt[a_names]
                 drop = (bits, pdrop, r) if bits is not None else None
             return hip.gemm(dy, wT, R2=tb, S2=AT, drop=drop, swiglu_bwd=swiglu)
 
