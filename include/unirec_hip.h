@@ -201,7 +201,7 @@ int ur_lora_bgrad(const ur_lora_args* a, void* workspace, int64_t workspace_byte
  * z = dropout_pre(y) + residual;  out = dropout_post(LN(z) * gamma + beta)
  *   y [M,H] bf16 (row m reads y[(m % y_rows)], so a [Q,H] query table broadcasts over the batch);
  *   residual [M,H] bf16 or NULL; z_save [M,H] bf16 or NULL (kept for backward);
- *   mean, rstd [M] f32.  H % 8 == 0, H <= 8192.  Dropout masks are a pure function of
+ *   mean, rstd [M] f32.  H % 8 == 0, H <= 2048.  Dropout masks are a pure function of
  *   (seed, element index) and are regenerated by the backward.  drop_row0: index of row 0 of this launch in the GLOBAL
  *   minibatch (element index = (drop_row0 + row) * H + h): a data-parallel rank passes the rows that precede its shard, so
  *   the masks -- and the training run -- do not depend on the number of ranks; 0 for a single process. */
@@ -209,13 +209,18 @@ int ur_layernorm_fwd(const void* y, int32_t y_rows, const void* residual, const 
                      void* out, void* z_save, float* mean, float* rstd, int32_t M, int32_t H, float eps,
                      float p_pre, uint64_t seed_pre, float p_post, uint64_t seed_post, int64_t drop_row0, void* stream);
 /* Backward.  dz [M,H] bf16 = gradient w.r.t. z (the residual branch); dy [M,H] bf16 = dz with the
- * pre-dropout mask applied (may alias dz when p_pre == 0; may be NULL when not needed).
+ * pre-dropout mask applied (may alias dz when p_pre == 0 -- with p_pre > 0 the alias is rejected: both tensors are stored and dz would be
+ * lost --; may be NULL when not needed).
  * dgamma, dbeta [H] f32 are OVERWRITTEN; dbias [H] f32 (column sum of dy, i.e. the gradient of the
  * preceding dense bias) is written when non-NULL.  workspace: ur_layernorm_bwd_workspace_bytes(H).
+ * M == 0 (unlike the forward and the RMSNorm entry points, which return at once): no row of dz / dy is written, and the parameter
+ * gradients that were asked for are overwritten with the empty sum, 0.
  * dgamma == NULL (round 6): the call stops at the per-block partial sums in `workspace` and the caller finishes them with
  * ur_layernorm_bwd_reduce(workspace, M, H, ...) -- on ANY stream ordered behind this call: the three parameter gradients hang off the
  * backward's dX chain (unirec_amd/qformer.py runs the reduction on its side stream beside the next layer's products).  The workspace then
- * belongs to that pending reduction until it has run. */
+ * belongs to that pending reduction until it has run.  M and H MUST be the backward's: the number of partial rows in use is a function
+ * of M (one per block of the backward's grid), the library keeps no record of it, and a reduction with another M sums partial rows the
+ * backward never wrote, or leaves some out, without any error. */
 int64_t ur_layernorm_bwd_workspace_bytes(int32_t H);
 int ur_layernorm_bwd(const void* dout, const void* z, const float* mean, const float* rstd, const float* gamma,
                      void* dz, void* dy, float* dgamma, float* dbeta, float* dbias, int32_t M, int32_t H,

@@ -1,5 +1,6 @@
-"""Float64 restatements of the head, RoPE, pool and data primitives of include/unirec_hip.h, and the element-wise criteria the
-GPU tests hold the kernels to (tests/test_gpu_head_primitives.py).  Plain torch on the CPU: no fixtures, no device code.
+"""Float64 restatements of the head, RoPE, pool, data, attention, norm, reduction and GEMM-epilogue primitives of include/unirec_hip.h,
+and the element-wise criteria the GPU tests hold the kernels to (tests/test_gpu_head_primitives.py, tests/test_gpu_attention_f64.py,
+tests/test_gpu_norm_f64.py).  Plain torch on the CPU: no fixtures, no device code.
 
 Every reference is written from the formula in the header comment of its entry point and is itself checked against an
 independent implementation in tests/test_ref64.py.  All functions take / return CPU tensors; inputs of any float dtype are
@@ -690,3 +691,264 @@ def assert_attn_frob(got, ref64, emul, A, what="", margin=3.0):
         raise AssertionError(f"{what}: {int(off.sum())} of {ratio.numel()} (batch, head) slices exceed {margin} x the emulation's Frobenius error; "
                              f"worst at (batch, head) {i}: {ratio[i].item():.2f} x the bound")
     return float(ratio.max())
+
+
+# ---- LayerNorm / RMSNorm / batch reduce / GEMM epilogue (include/unirec_hip.h: ur_layernorm_*, ur_rmsnorm_*, ur_batch_reduce, ur_gemm) ---
+def assert_bf16_rows(got, ref64, ref32, what="", scale=None, floor=2.0 ** -18):
+    """bf16 outputs of the row-normalising kernels.  EVERY element:
+        |got - ref64| <= 1 bf16 ulp(ref64) + 2^-18 * row max |ref64| + 8 * e32_row,   e32_row = row max |ref32 - ref64|,
+    ref32 the SAME two-pass formula in float32 torch on the CPU (the yardstick of assert_f32_close).  The e32 term is there for rows whose
+    mean dwarfs their spread (docs/lab_notes.md, "Element-wise float64 tests: norm, reduction and GEMM epilogue kernels"); on centred rows
+    it is far below the first two.  scale [rows, 1]: the row scale of the floor where it is not the row maximum of ref64 itself -- the
+    UNMASKED row of a dropout-masked output, whose cancellation error does not shrink when the mask removes the row's large elements.
+    floor = 0: 1 ulp + 8 * e32_row alone (z_save under pre-dropout).  Everything finite.  Returns the worst error / bound."""
+    r, r32 = _cpu64(ref64), _cpu64(ref32)
+    assert r.shape == r32.shape, f"{what}: shapes {tuple(r.shape)} / {tuple(r32.shape)}"
+    assert torch.isfinite(r32).all(), f"{what}: the float32 re-evaluation of the reference is not finite"
+    if r.numel() == 0:
+        return assert_within_ulps(got, r, 1, 0.0, what)
+    e32 = (r32 - r).abs().amax(dim=-1, keepdim=True)
+    sc = r.abs().amax(dim=-1, keepdim=True) if scale is None else _cpu64(scale).reshape(-1, 1)
+    return assert_within_ulps(got, r, 1, floor * sc + 8.0 * e32, what)
+
+
+GELU_TAIL = 1e-6                    # |gelu(x)| at or below this: the fitted Phi of common.hip.h (and float32 erf itself) is held absolutely
+
+
+def assert_gelu_close(got, x, what=""):
+    """gelu outputs (bf16) of the bf16 inputs x: 1 bf16 ulp of the float64 value wherever |gelu(x)| > 1e-6 -- the region in which
+    tests/test_gelu_cdf.py demands the exact bf16 of the emulation --, |error| <= 1e-6 below it (x < -5 and |x| < 2e-6: float32
+    0.5 x (1 + erf(x / sqrt 2)) returns -0 for every x <= -5.6, docs/lab_notes.md).  Returns the worst error / bound."""
+    g, r = _cpu64(got), gelu(_cpu64(x))
+    big = r.abs() > GELU_TAIL
+    z = torch.zeros_like(r)
+    ratio = assert_within_ulps(torch.where(big, g, z), torch.where(big, r, z), 1, 0.0, what)
+    assert torch.isfinite(g).all(), f"{what}: non-finite outputs"
+    err = torch.where(big, z, (g - r).abs())
+    if (err > GELU_TAIL).any():
+        i = tuple(int(v) for v in torch.unravel_index(err.argmax(), err.shape))
+        raise AssertionError(f"{what}: {int((err > GELU_TAIL).sum())} outputs with |gelu(x)| <= 1e-6 are off by more than 1e-6; worst at {i}: "
+                             f"got {g[i].item()!r}, reference {r[i].item()!r}")
+    return max(ratio, float(err.max()) / GELU_TAIL)
+
+
+def assert_colsum_close(got, ref64, ref32, abs_terms, what=""):
+    """f32 column sums over M rows (dgamma, dbeta, dbias, ur_batch_reduce).  EVERY column:
+        |got - ref64| <= 8 * |ref32 - ref64| + 2^-20 * sum_m |term|      (abs_terms = that sum per column; ref32 = ref64 where the terms are given
+    exactly and only the summation rounds).  Everything finite.  Returns the worst error / bound (0 / 0 counts as 0)."""
+    g, r, r32, a = _cpu64(got), _cpu64(ref64), _cpu64(ref32), _cpu64(abs_terms)
+    assert g.shape == r.shape == r32.shape == a.shape, f"{what}: shapes {tuple(g.shape)} / {tuple(r.shape)} / {tuple(r32.shape)} / {tuple(a.shape)}"
+    assert torch.isfinite(r).all() and torch.isfinite(r32).all(), f"{what}: the reference itself is not finite"
+    if g.numel() == 0:
+        return 0.0
+    bad = ~torch.isfinite(g)
+    if bad.any():
+        i = tuple(int(v) for v in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} non-finite outputs, first at {i}: got {g[i].item()}, reference {r[i].item()}")
+    err, bound = (g - r).abs(), 8.0 * (r32 - r).abs() + 2.0 ** -20 * a
+    off = err > bound
+    if off.any():
+        excess = torch.where(off, err - bound, torch.zeros_like(err))
+        i = tuple(int(v) for v in torch.unravel_index(excess.argmax(), err.shape))
+        raise AssertionError(f"{what}: {int(off.sum())} of {err.numel()} sums exceed 8 * e32 + 2^-20 * sum |term|; worst at index {i}: got {g[i].item()!r}, "
+                             f"reference {r[i].item()!r}, error {err[i].item():.3e}, allowed {bound[i].item():.3e} (sum |term| {a[i].item():.3e})")
+    return float(torch.where(err == 0, torch.zeros_like(err), err / bound.clamp_min(1e-300)).max())
+
+
+def _drop_scale(keep, p, dtype):
+    if keep is None:
+        return None
+    return torch.as_tensor(keep).to(dtype) / torch.as_tensor(1.0 - p, dtype=dtype)
+
+
+def layernorm_z(y, residual=None, keep_pre=None, p_pre=0.0, y_rows=None, M=None, dtype=F64):
+    """z = y[m % y_rows] * keep_pre / (1 - p_pre) + residual, UNROUNDED: [M, H]."""
+    y = torch.as_tensor(y).detach().cpu()
+    y = y.reshape(-1, y.shape[-1]).to(dtype)
+    y_rows = y.shape[0] if y_rows is None else int(y_rows)
+    M = y_rows if M is None else int(M)
+    z = y[torch.arange(M) % y_rows]
+    s = _drop_scale(keep_pre, p_pre, dtype)
+    if s is not None:
+        z = z * s
+    if residual is not None:
+        z = z + torch.as_tensor(residual).detach().cpu().to(dtype)
+    return z
+
+
+def layernorm_of_z(z, gamma, beta, eps, keep_post=None, p_post=0.0, dtype=F64):
+    """(out, mean, rstd, xhat) of the given z, two-pass: mean, then the mean of the squared deviations."""
+    z = z.to(dtype)
+    mean = z.mean(-1, keepdim=True)
+    d = z - mean
+    rstd = torch.rsqrt((d * d).mean(-1, keepdim=True) + eps)
+    xhat = d * rstd
+    out = xhat * gamma.to(dtype) + beta.to(dtype)
+    s = _drop_scale(keep_post, p_post, dtype)
+    if s is not None:
+        out = out * s
+    return out, mean.squeeze(-1), rstd.squeeze(-1), xhat
+
+
+def layernorm_fwd(y, residual, gamma, beta, eps, keep_pre=None, p_pre=0.0, keep_post=None, p_post=0.0, y_rows=None, M=None, dtype=F64):
+    """(z, out, mean, rstd): z = bf16(dropout_pre(y) + residual) -- the value the kernel saves --, out = dropout_post(LN(z) * gamma + beta)
+    of that ROUNDED z, as the kernel normalises it by design (forward and backward see the same z).  keep_* [M, H] 0 / 1
+    (oracle/dropout_ref.hidden_keep) or None."""
+    z = _bf(layernorm_z(y, residual, keep_pre, p_pre, y_rows, M, dtype))
+    out, mean, rstd, _ = layernorm_of_z(z, gamma, beta, eps, keep_post, p_post, dtype)
+    return z, out, mean, rstd
+
+
+def layernorm_bwd(dout, z, gamma, eps, keep_pre=None, p_pre=0.0, keep_post=None, p_post=0.0, dtype=F64):
+    """(dz, dy, dgamma, dbeta): torch.autograd through the forward from z; dy = dz * keep_pre / (1 - p_pre)."""
+    zz = torch.as_tensor(z).detach().cpu().to(dtype).clone().requires_grad_(True)
+    g = gamma.detach().cpu().to(dtype).clone().requires_grad_(True)
+    b = torch.zeros_like(g).requires_grad_(True)
+    out, _, _, _ = layernorm_of_z(zz, g, b, eps, keep_post, p_post, dtype)
+    dz, dg, db = torch.autograd.grad(out, (zz, g, b), torch.as_tensor(dout).detach().cpu().to(dtype))
+    s = _drop_scale(keep_pre, p_pre, dtype)
+    return dz, (dz if s is None else dz * s), dg, db
+
+
+def layernorm_bwd_terms(dout, z, eps, keep_post=None, p_post=0.0):
+    """(sum_m |dout' * xhat|, sum_m |dout'|) per column, dout' = dout * keep_post / (1 - p_post): what the dgamma / dbeta sums run over."""
+    zz = torch.as_tensor(z).detach().cpu().to(F64)
+    d = torch.as_tensor(dout).detach().cpu().to(F64)
+    s = _drop_scale(keep_post, p_post, F64)
+    if s is not None:
+        d = d * s
+    xhat = layernorm_of_z(zz, torch.ones(zz.shape[-1], dtype=F64), torch.zeros(zz.shape[-1], dtype=F64), eps)[3]
+    return (d * xhat).abs().sum(0), d.abs().sum(0)
+
+
+def rmsnorm_fwd(x, w, eps, dtype=F64):
+    """(out, rstd): out = w * (x * rsqrt(mean(x^2) + eps))."""
+    x = torch.as_tensor(x).to(dtype)
+    rstd = torch.rsqrt((x * x).mean(-1, keepdim=True) + eps)
+    return w.to(dtype) * (x * rstd), rstd.squeeze(-1)
+
+
+def rmsnorm_bwd(dout, x, w, eps, add=None, dtype=F64):
+    """dx = add + d out / d x (weights frozen): torch.autograd through the forward."""
+    xx = torch.as_tensor(x).detach().cpu().to(dtype).clone().requires_grad_(True)
+    out, _ = rmsnorm_fwd(xx, w.detach().cpu(), eps, dtype)
+    (dx,) = torch.autograd.grad(out, xx, torch.as_tensor(dout).detach().cpu().to(dtype))
+    return dx if add is None else dx + torch.as_tensor(add).detach().cpu().to(dtype)
+
+
+def batch_reduce(x, nb, rows, H, dtype=F64):
+    """out[r][h] = sum_{b < nb} in[b * rows + r][h]: [rows, H]."""
+    return torch.as_tensor(x).detach().cpu().to(dtype).reshape(nb, rows, H).sum(0)
+
+
+def gemm_epilogue(acc, alpha=1.0, bias=None, residual=None, aux=None, dtype=F64):
+    """v = (alpha * acc + bias[n] + residual[m][n]) * gelu'(aux[m][n]) of the EXACT product acc [M, N]; the kernel stores C = bf16(v) and
+    gelu_out = bf16(gelu(C)) (ur_gemm_args)."""
+    v = torch.as_tensor(alpha, dtype=dtype) * acc.to(dtype)
+    if bias is not None:
+        v = v + bias.to(dtype)[None, :]
+    if residual is not None:
+        v = v + residual.to(dtype)
+    if aux is not None:
+        v = v * gelu_grad(aux).to(dtype)
+    return v
+
+
+def gelu_grad_f32(u):
+    """gelu'(u) = Phi(u) + u phi(u) with every step in float32 torch, Phi = 0.5 (1 + erf(u / sqrt 2)) as the reference model's own GELU forms
+    it: absolutely accurate (about 1e-7), not relatively -- below u = -5 it is a difference of two numbers of 1e-7 and smaller"""
+    f32 = torch.float32
+    u = torch.as_tensor(u).to(f32)
+    cdf = 0.5 * (1.0 + torch.erf(u * torch.tensor(1.0 / math.sqrt(2.0), dtype=f32)))
+    return cdf + u * (torch.exp(-0.5 * u * u) * torch.tensor(1.0 / math.sqrt(2.0 * math.pi), dtype=f32))
+
+
+def _ratio(err, bound):
+    return float(torch.where(err == 0, torch.zeros_like(err), err / bound.clamp_min(1e-300)).max()) if err.numel() else 0.0
+
+
+def assert_gemm_c(C, acc, alpha, bias=None, residual=None, what=""):
+    """bf16 C of an exact product without the gelu' factor: 1 bf16 ulp + 2^-20 (|alpha acc| + |bias| + |res|) around v = alpha acc + bias + res
+    (three float32 roundings of terms of those magnitudes).  Returns the worst error / bound."""
+    v = gemm_epilogue(acc, alpha, bias, residual)
+    mag = (alpha * acc.to(F64)).abs()
+    if bias is not None:
+        mag = mag + bias.to(F64).abs()[None, :]
+    if residual is not None:
+        mag = mag + residual.to(F64).abs()
+    return assert_within_ulps(C, v, 1, 2.0 ** -20 * mag, what)
+
+
+def assert_gemm_gelu_grad(C, acc, alpha, bias, residual, aux, what=""):
+    """bf16 C = bf16(pre * gelu'(aux)), pre = alpha acc + bias + res: 1 bf16 ulp + 2^-18 |pre| + 2^-20 (|alpha acc| + |bias| + |res|) |gelu'(aux)|
+    -- the floor of test_gelu_bwd_exhaustive (2^-18 |dy|), pre being what the factor multiplies, and the floor assert_gemm_c grants pre.  gelu' = Phi + u phi is held ABSOLUTELY by float32 arithmetic (gelu_grad_f32: below
+    u = -5 it is the difference of two numbers of 1e-7; tests/test_ref64.py shows the float32 evaluation missing 2^-18 |pre gelu'| there and
+    meeting 2^-18 |pre|).  Returns the worst error / bound."""
+    v, pre = gemm_epilogue(acc, alpha, bias, residual, aux), gemm_epilogue(acc, alpha, bias, residual)
+    mag = (alpha * acc.to(F64)).abs()
+    if bias is not None:
+        mag = mag + bias.to(F64).abs()[None, :]
+    if residual is not None:
+        mag = mag + residual.to(F64).abs()
+    # + assert_gemm_c's floor of pre itself, seen through the factor: alpha acc + bias + res may cancel (three float32 roundings of its terms)
+    return assert_within_ulps(C, v, 1, 2.0 ** -18 * pre.abs() + 2.0 ** -20 * mag * gelu_grad(aux).abs(), what)
+
+
+def assert_gemm_f32(C32, acc, alpha, bias=None, what=""):
+    """f32 output: |got - (alpha acc + bias)| <= 2^-22 (|alpha acc| + |bias|), everything finite.  Returns the worst error / bound."""
+    g, v = _cpu64(C32), gemm_epilogue(acc, alpha, bias)
+    assert torch.isfinite(g).all(), f"{what}: non-finite outputs"
+    bound = 2.0 ** -22 * ((alpha * acc.to(F64)).abs() + (bias.to(F64).abs()[None, :] if bias is not None else 0.0))
+    err = (g - v).abs()
+    assert (err <= bound).all(), f"{what}: {int((err > bound).sum())} elements exceed 2^-22 (|alpha acc| + |bias|), worst {_ratio(err, bound):.2f} x"
+    return _ratio(err, bound)
+
+
+NORM_MUTANTS = ("one_pass_variance", "no_m1", "gelu_unrounded", "bias_after_gelu_grad")
+
+
+def norm_emulated(z, gamma, beta, eps, dout, mutant=None):
+    """The LayerNorm kernels' arithmetic in float32 torch, outputs rounded to bf16: (out, dz).  mutant: 'one_pass_variance' (var = E[z^2] -
+    mean^2 in the forward) or 'no_m1' (the backward loses the mean of dout * gamma) -- DELIBERATE bugs, for tests/test_ref64.py."""
+    assert mutant in (None, "one_pass_variance", "no_m1"), mutant
+    f32 = torch.float32
+    z, g, b, d = z.to(f32), gamma.to(f32), beta.to(f32), dout.to(f32)
+    mean = z.mean(-1, keepdim=True)
+    if mutant == "one_pass_variance":
+        var = (z * z).mean(-1, keepdim=True) - mean * mean
+    else:
+        var = ((z - mean) ** 2).mean(-1, keepdim=True)
+    rs = torch.rsqrt(var + eps)
+    xh = (z - mean) * rs
+    out = xh * g + b
+    go = d * g
+    m1 = go.mean(-1, keepdim=True) if mutant != "no_m1" else torch.zeros_like(mean)
+    m2 = (go * xh).mean(-1, keepdim=True)
+    dz = rs * (go - m1 - xh * m2)
+    return _bf(out).to(F64), _bf(dz).to(F64)
+
+
+def gemm_epilogue_emulated(acc, alpha, bias, residual, aux, mutant=None):
+    """The GEMM epilogue in float32 torch (gelu' too: gelu_grad_f32): (C, gelu_out) as bf16 values in float64.  mutant: 'gelu_unrounded' (gelu_out from v instead of
+    bf16(v)) or 'bias_after_gelu_grad' (v = (alpha acc + res) * gelu'(aux) + bias)."""
+    assert mutant in (None, "gelu_unrounded", "bias_after_gelu_grad"), mutant
+    f32 = torch.float32
+    v = acc.to(f32) * alpha
+    fac = gelu_grad_f32(aux) if aux is not None else None
+    if mutant == "bias_after_gelu_grad":
+        if residual is not None:
+            v = v + residual.to(f32)
+        if fac is not None:
+            v = v * fac
+        if bias is not None:
+            v = v + bias.to(f32)[None, :]
+    else:
+        if bias is not None:
+            v = v + bias.to(f32)[None, :]
+        if residual is not None:
+            v = v + residual.to(f32)
+        if fac is not None:
+            v = v * fac
+    C = _bf(v)
+    g = gelu(v if mutant == "gelu_unrounded" else C).to(f32)
+    return C.to(F64), _bf(g).to(F64)

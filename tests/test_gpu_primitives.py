@@ -27,13 +27,6 @@ COVERS = {
     "ur_lora_reduce": ["test_lora_kernels_with_dropout_bits", "test_lora_reduce_ring_kernel", "test_lora_reduce_ring_kernel_on_column_ranges"],
     "ur_lora_bgrad": ["test_lora_bgrad_ring_kernel"],
     "ur_swiglu_lora_fwd": ["test_fused_swiglu_lora_projection_matches_the_two_kernels"],
-    "ur_rmsnorm_lora_fwd": ["test_fused_rmsnorm_lora_projection_matches_the_two_kernels"],
-    "ur_layernorm_fwd": ["test_layernorm_fwd_bwd", "test_layernorm_broadcast_rows_and_dropout"],
-    "ur_layernorm_bwd": ["test_layernorm_fwd_bwd", "test_layernorm_broadcast_rows_and_dropout"],
-    "ur_layernorm_bwd_reduce": ["test_layernorm_bwd_deferred_reduce"],
-    "ur_batch_reduce": ["test_batch_reduce_and_colsum"],
-    "ur_rmsnorm_fwd": ["test_rmsnorm_fwd_bwd"],
-    "ur_rmsnorm_bwd": ["test_rmsnorm_fwd_bwd"],
     "ur_attn_fwd": ["tests/test_gpu_attention.py::test_qformer_attention", "tests/test_gpu_attention.py::test_qwen3_causal_gqa"],
     "ur_attn_bwd": ["tests/test_gpu_attention.py::test_qformer_attention", "tests/test_gpu_attention.py::test_qwen3_causal_gqa"],
     "ur_attn_dropout_keep": ["tests/test_gpu_r5_parity.py::test_attention_dropout_keep_export_matches_the_numpy_generator"],

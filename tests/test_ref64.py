@@ -522,3 +522,256 @@ def test_attention_stats_check_and_qk_round_rule():
     assert attn_cases.qk_round_for(128, True, 128, 128) == "all" and attn_cases.qk_round_for(128, True, 192, 192) == "fwd"
     assert attn_cases.qk_round_for(128, True, 127, 127) is None and attn_cases.qk_round_for(64, True, 128, 128) is None
     assert attn_cases.qk_round_for(128, False, 128, 128) is None and attn_cases.qk_round_for(128, True, 128, 128, c128_mode=0) is None
+
+
+# ---- LayerNorm / RMSNorm / batch reduce / GEMM epilogue ----------------------------------------------------------------------------
+from tests import norm_cases  # noqa: E402
+
+
+def _keep(M, H, p, seed, row0=0):
+    return torch.from_numpy(dropout_ref.hidden_keep(seed, p, M, H, row0).astype(np.float64))
+
+
+@pytest.mark.parametrize("M,H,y_rows,p_pre,p_post,with_res", [(7, 8, 7, 0.0, 0.0, False), (33, 520, 33, 0.1, 0.0, True), (12, 768, 4, 0.0, 0.5, False),
+                                                              (10, 1032, 3, 0.5, 0.1, True)])
+def test_layernorm_reference_matches_functional_layer_norm(M, H, y_rows, p_pre, p_post, with_res):
+    """ref64.layernorm_fwd / layernorm_bwd against torch.nn.functional.layer_norm + autograd in float64, dropout written as a product with
+    the keep flags of the numpy generator, the broadcast of y as an index_select"""
+    y = norm_cases.rows(y_rows, H, 30, kinds=(0, 1, 2, 3))
+    res = norm_cases.residual_rows(M, H, 31) if with_res else None
+    gamma, beta = norm_cases.norm_weight(H, 32), _randn((H,), 33).float()
+    kpre = _keep(M, H, p_pre, 41, 40) if p_pre else None
+    kpost = _keep(M, H, p_post, 42, 40) if p_post else None
+    z, out, mean, rstd = ref64.layernorm_fwd(y, res, gamma, beta, 1e-12, kpre, p_pre, kpost, p_post, y_rows, M)
+    zz = y.to(F64)[torch.arange(M) % y_rows]
+    if kpre is not None:
+        zz = zz * kpre / (1.0 - p_pre)
+    if res is not None:
+        zz = zz + res.to(F64)
+    assert torch.equal(z, zz.to(torch.bfloat16).to(F64))
+    zl = z.clone().requires_grad_(True)
+    g, b = gamma.to(F64).requires_grad_(True), beta.to(F64).requires_grad_(True)
+    model = F.layer_norm(zl, (H,), g, b, 1e-12)
+    if kpost is not None:
+        model = model * kpost / (1.0 - p_post)
+    assert torch.allclose(out, model.detach(), rtol=0, atol=1e-12 * float(out.abs().max()))
+    assert torch.allclose(mean, z.mean(-1), rtol=1e-14, atol=0) and torch.allclose(rstd, (z.var(-1, unbiased=False) + 1e-12).rsqrt(), rtol=1e-12, atol=0)
+    dout = _randn((M, H), 34)
+    dz_m, dg_m, db_m = torch.autograd.grad(model, (zl, g, b), dout)
+    dz, dy, dg, db = ref64.layernorm_bwd(dout, z, gamma, 1e-12, kpre, p_pre, kpost, p_post)
+    for mine, theirs in ((dz, dz_m), (dg, dg_m), (db, db_m)):
+        assert torch.allclose(mine, theirs, rtol=0, atol=1e-11 * float(theirs.abs().max()))
+    assert torch.allclose(dy, dz if kpre is None else dz * kpre / (1.0 - p_pre), rtol=1e-15, atol=0)
+    tg, tb = ref64.layernorm_bwd_terms(dout, z, 1e-12, kpost, p_post)
+    assert (tg >= dg.abs() * (1 - 1e-12)).all() and (tb >= db.abs() * (1 - 1e-12)).all()
+
+
+@pytest.mark.parametrize("M,D", [(5, 8), (9, 1032)])
+def test_rmsnorm_reference_matches_the_models_module(M, D):
+    x = norm_cases.rows(M, D, 35, kinds=(0, 1, 2))
+    w = norm_cases.norm_weight(D, 36)
+    out, rstd = ref64.rmsnorm_fwd(x, w, 1e-6)
+    assert torch.allclose(out, qwen3_ref.rms_norm(x.to(F64), w.to(F64), 1e-6), rtol=1e-13, atol=0)
+    dout, add = _randn((M, D), 37), _randn((M, D), 38)
+    dx = ref64.rmsnorm_bwd(dout, x, w, 1e-6, add)
+    xl = x.to(F64).requires_grad_(True)
+    (g_model,) = torch.autograd.grad(qwen3_ref.rms_norm(xl, w.to(F64), 1e-6), xl, dout)
+    assert torch.allclose(dx, g_model + add, rtol=0, atol=1e-12 * float(dx.abs().max()))
+    # written out: dx = rstd * (g - xhat * mean(g * xhat)), g = dout * w
+    xh, gg = x.to(F64) * rstd[:, None], dout * w.to(F64)
+    assert torch.allclose(dx - add, rstd[:, None] * (gg - xh * (gg * xh).mean(-1, keepdim=True)), rtol=0, atol=1e-11 * float(dx.abs().max()))
+    if _have_transformers():
+        from transformers.models.qwen3.modeling_qwen3 import Qwen3RMSNorm
+        mod = Qwen3RMSNorm(D, eps=1e-6).to(F64)
+        with torch.no_grad():
+            mod.weight.copy_(w.to(F64))
+        xl = x.to(F64).requires_grad_(True)
+        o = mod(xl)                                                 # squares in float32 whatever it is given: float32 accuracy
+        assert torch.allclose(out, o.detach().to(F64), rtol=0, atol=2e-6 * float(out.abs().max()))
+        (g_hf,) = torch.autograd.grad(o, xl, dout)
+        assert torch.allclose(dx - add, g_hf.to(F64), rtol=0, atol=2e-6 * float(dx.abs().max()))
+
+
+def test_batch_reduce_and_gemm_epilogue_references():
+    x = _randn((6 * 3, 16), 39).to(torch.bfloat16)
+    assert torch.allclose(ref64.batch_reduce(x, 6, 3, 16), torch.einsum("brh->rh", x.to(F64).reshape(6, 3, 16)), rtol=1e-14, atol=1e-14)
+    acc, bias, res, aux = _randn((5, 8), 40), _randn((8,), 41), _randn((5, 8), 42), _randn((5, 8), 43)
+    a = aux.clone().requires_grad_(True)
+    F.gelu(a).sum().backward()
+    v = ref64.gemm_epilogue(acc, 0.5, bias, res, aux)
+    assert torch.allclose(v, (0.5 * acc + bias + res) * a.grad, rtol=1e-12, atol=1e-14)
+    assert torch.equal(ref64.gemm_epilogue(acc, 1.0), acc) and torch.equal(ref64.gemm_epilogue(acc, 0.5, bias), 0.5 * acc + bias)
+    assert torch.allclose(ref64.gelu(acc), F.gelu(acc), rtol=1e-12, atol=1e-15)
+
+
+def _norm_criterion_case(H, kinds, seed):
+    M = 257
+    z = norm_cases.rows(M, H, seed, kinds=kinds).to(F64)
+    gamma, beta = norm_cases.norm_weight(H, seed + 1), _randn((H,), seed + 2).float()
+    dout = _randn((M, H), seed + 3).to(torch.bfloat16)
+    refs = []
+    for dt in (F64, torch.float32):
+        out = ref64.layernorm_of_z(z, gamma, beta, 1e-12, dtype=dt)[0]
+        dz = ref64.layernorm_bwd(dout, z, gamma, 1e-12, dtype=dt)[0]
+        refs.append((out, dz))
+    return z, gamma, beta, dout, refs
+
+
+@pytest.mark.parametrize("H", [8, 520, 2048])
+def test_norm_criterion_passes_the_float32_emulation_and_catches_the_mutants(H):
+    """assert_bf16_rows on the float32 emulation of the LayerNorm kernels (tests/ref64.norm_emulated): the straight one passes on every
+    kind of row; a one-pass variance fails on the offset rows from H = 520 on (on the mean-100 rows alone, too) and a backward without
+    the m1 term fails everywhere"""
+    z, gamma, beta, dout, ((o64, d64), (o32, d32)) = _norm_criterion_case(H, None, 50)
+    out, dz = ref64.norm_emulated(z, gamma, beta, 1e-12, dout)
+    assert ref64.assert_bf16_rows(out, o64, o32, "emulated out") <= 1.0
+    assert ref64.assert_bf16_rows(dz, d64, d32, "emulated dz") <= 1.0
+    if H >= 520:                # (H = 8: the squares of eight bf16 values near 100 or 1000 and their sum are exact in float32, one pass loses nothing)
+        out_m, _ = ref64.norm_emulated(z, gamma, beta, 1e-12, dout, mutant="one_pass_variance")
+        with pytest.raises(AssertionError, match="exceed 1 bf16 ulp"):
+            ref64.assert_bf16_rows(out_m, o64, o32, "one-pass variance")
+    _, dz_m = ref64.norm_emulated(z, gamma, beta, 1e-12, dout, mutant="no_m1")
+    with pytest.raises(AssertionError, match="exceed 1 bf16 ulp"):
+        ref64.assert_bf16_rows(dz_m, d64, d32, "no m1")
+    if H >= 520:                                                   # mean 100 / std 1 alone
+        z, gamma, beta, dout, ((o64, d64), (o32, d32)) = _norm_criterion_case(H, (3,), 60)
+        assert ref64.assert_bf16_rows(ref64.norm_emulated(z, gamma, beta, 1e-12, dout)[0], o64, o32, "emulated out, mean 100") <= 1.0
+        with pytest.raises(AssertionError, match="exceed 1 bf16 ulp"):
+            ref64.assert_bf16_rows(ref64.norm_emulated(z, gamma, beta, 1e-12, dout, mutant="one_pass_variance")[0], o64, o32, "one-pass variance, mean 100")
+    # centred rows: the e32 term is not what lets the emulation pass
+    z, gamma, beta, dout, ((o64, d64), (o32, d32)) = _norm_criterion_case(H, (0, 1, 2), 70)
+    out, dz = ref64.norm_emulated(z, gamma, beta, 1e-12, dout)
+    for got, r in ((out, o64), (dz, d64)):
+        assert ref64.assert_within_ulps(got, r, 1, 2.0 ** -18 * ref64.rowmax(r), "centred rows without the e32 term") <= 0.75
+
+
+def test_colsum_criterion_passes_float32_sums_and_catches_a_lost_row():
+    M, H = 2053, 16
+    x = _randn((M, H), 80).to(torch.bfloat16)
+    r64, a = x.to(F64).sum(0), x.to(F64).abs().sum(0)
+    assert ref64.assert_colsum_close(x.float().sum(0), r64, r64, a, "f32 sum") <= 1.0
+    with pytest.raises(AssertionError, match="exceed 8"):
+        ref64.assert_colsum_close(x[:-1].float().sum(0), r64, r64, a, "a lost row")
+    ints = torch.randint(-3, 4, (M, H), generator=_gen(81)).to(F64)
+    assert ref64.assert_colsum_close(ints.float().sum(0), ints.sum(0), ints.sum(0), ints.abs().sum(0), "integers") == 0.0
+
+
+def _gemm_epilogue_checks(C, g, acc, alpha, bias, res, aux):
+    """the criteria tests/test_gpu_norm_f64.py::test_gemm_epilogues_exact_products applies (the same ref64 helpers) on given outputs"""
+    if aux is None:
+        ref64.assert_gemm_c(C, acc, alpha, bias, res, "C")
+    else:
+        ref64.assert_gemm_gelu_grad(C, acc, alpha, bias, res, aux, "C, gelu' mode")
+    if g is not None:
+        ref64.assert_gelu_close(g, C, "gelu_out")
+
+
+@pytest.mark.parametrize("mutant", [None, "gelu_unrounded", "bias_after_gelu_grad"])
+def test_gemm_epilogue_criteria_catch_the_mutants(mutant):
+    """integer-valued products (exact accumulators): the float32 epilogue passes; GELU of the unrounded v and a bias added after the gelu'
+    factor fail"""
+    M, N, K = 200, 136, 72
+    R = torch.randint(-3, 4, (M, K), generator=_gen(90)).to(F64)
+    S = torch.randint(-3, 4, (N, K), generator=_gen(91)).to(F64)
+    acc = R @ S.t()
+    bias = _randn((N,), 92).float()
+    res = _randn((M, N), 93).to(torch.bfloat16)
+    aux = _randn((M, N), 94).to(torch.bfloat16)
+    failed = []
+    for name, kw in (("gelu_out", dict(residual=res, aux=None)), ("gelu_grad", dict(residual=None, aux=aux))):
+        C, g = ref64.gemm_epilogue_emulated(acc, 0.5, bias, kw["residual"], kw["aux"], mutant=mutant)
+        try:
+            _gemm_epilogue_checks(C, g if kw["aux"] is None else None, acc, 0.5, bias, kw["residual"], kw["aux"])
+        except AssertionError:
+            failed.append(name)
+    assert failed == {None: [], "gelu_unrounded": ["gelu_out"], "bias_after_gelu_grad": ["gelu_grad"]}[mutant]
+
+
+def test_margins_beyond_one_ulp_are_what_float32_costs():
+    """the four margins the GPU criteria grant beyond the bare ones -- masked rows (a, e), z under pre-dropout (b), GELU below 1e-6 (c), the
+    gelu' floor (d) --, each shown on the float32 evaluation alone:
+    (a) dy = dz * keep / (1 - p) of a row whose only kept element is one where dz cancels: the written-out float32 backward misses the
+        masked row's own maximum by orders of magnitude and meets the unmasked row's;
+    (b) z = y / (1 - p) + residual cancelling exactly (40.5 / 0.9 - 45): float32 leaves 2^-24 of the terms;
+    (c) float32 0.5 x (1 + erf(x / sqrt 2)) is -0 for x <= -5.6 and off by up to 1e-7 wherever |gelu(x)| <= 1e-6;
+    (d) the gelu' mode of the GEMM epilogue: float32 Phi(u) + u phi(u) is absolutely accurate only, so (alpha acc + bias) * gelu'(aux)
+        misses 1 ulp + 2^-18 |v| of the PRODUCT v wherever gelu'(aux) is small and meets 1 ulp + 2^-18 |alpha acc + bias|;
+    (e) out under post-dropout, as (a): the only kept element of the row is one where xhat gamma + beta cancels."""
+    H, n = 8, 256
+    z = torch.zeros(n, H, dtype=F64)
+    v = _randn((n,), 406)
+    z[torch.arange(n), torch.arange(n) % H] = (torch.sign(v) * (1.0 + 2.0 * v.abs())).to(torch.bfloat16).to(F64)
+    gamma = norm_cases.norm_weight(H, 407)
+    dout = _randn((n, H), 408).to(torch.bfloat16)
+    keep = (z != 0).to(F64)
+    d64 = ref64.layernorm_bwd(dout, z, gamma, 1e-12, keep, 0.5)
+    d32 = ref64.layernorm_bwd(dout, z, gamma, 1e-12, keep, 0.5, dtype=torch.float32)
+    dz_emul = ref64.norm_emulated(z, gamma, torch.zeros(H), 1e-12, dout)[1]
+    f32 = torch.float32
+    zf, gf = z.to(f32), dout.to(f32) * gamma.to(f32)
+    mu = zf.sum(-1, keepdim=True) / H
+    rs = torch.rsqrt(((zf - mu) ** 2).sum(-1, keepdim=True) / H + 1e-12)
+    xh = (zf - mu) * rs
+    dz_f32 = rs * (gf - gf.sum(-1, keepdim=True) / H - xh * ((gf * xh).sum(-1, keepdim=True) / H))
+    worst = 0.0
+    for dz in (dz_emul, dz_f32.to(F64)):
+        dy = (dz * keep * 2.0).to(torch.bfloat16)
+        worst = max(worst, float((dy.to(F64) - d64[1]).abs().max()))
+        ref64.assert_bf16_rows(dy, d64[1], d32[1], "dy, unmasked row scale", scale=ref64.rowmax(d64[0]) * 2.0)
+    print(f"dy of rows with one kept element: reference at most {float(d64[1].abs().max()):.3e}, float32 evaluations off by up to {worst:.3e}")
+    assert float(d64[1].abs().max()) < 1e-9 and float(d64[0].abs().amax(-1).min()) > 0.01 and worst > 1e-8
+    y, res = torch.tensor([[40.5] * 8]).to(torch.bfloat16), torch.tensor([[-45.0] * 8]).to(torch.bfloat16)
+    one = torch.ones(1, 8, dtype=F64)
+    z64, z32 = ref64.layernorm_z(y, res, one, 0.1), ref64.layernorm_z(y, res, one, 0.1, dtype=torch.float32)
+    assert float(z64.abs().max()) < 1e-13 and 1e-6 < float(z32.abs().max()) < 1e-5
+    x = torch.arange(0, 65536, dtype=torch.int32).to(torch.int16).view(torch.bfloat16)
+    x = x[torch.isfinite(x.float())]
+    r = ref64.gelu(x)
+    tail = (r.abs() <= ref64.GELU_TAIL) & (x.to(F64) <= -5.6) & (r.abs() >= 2.0 ** -133)
+    g32 = F.gelu(x.float())
+    assert int(tail.sum()) > 100 and (g32[tail] == 0).all()
+    assert 5e-8 < float((g32.to(F64) - r).abs()[r.abs() <= ref64.GELU_TAIL].max()) < 1e-6
+    # (the erf formula even misses 1 ulp up to |gelu(x)| ~ 4e-6: the 1e-6 boundary is where the fitted Phi of common.hip.h is exact, not erf)
+    with pytest.raises(AssertionError, match="exceed 1 bf16 ulp"):
+        ok = x.float().abs() < 1e30
+        ref64.assert_gelu_close(g32[ok].to(torch.bfloat16), x[ok], "float32 erf gelu")
+    # (d)
+    M, N, K = 64, 256, 72
+    acc = (torch.randint(-3, 4, (M, K), generator=_gen(96)).to(F64) @ torch.randint(-3, 4, (N, K), generator=_gen(97)).to(F64).t())
+    bias = _randn((N,), 98).float()
+    aux = (-4.0 - 4.0 * torch.rand(M, N, generator=_gen(99))).to(torch.bfloat16)          # gelu'(aux) from -5e-4 down to -1e-14
+    C, _ = ref64.gemm_epilogue_emulated(acc, 1.0, bias, None, aux)
+    v = ref64.gemm_epilogue(acc, 1.0, bias, None, aux)
+    with pytest.raises(AssertionError, match="exceed 1 bf16 ulp"):
+        ref64.assert_within_ulps(C, v, 1, 2.0 ** -18 * v.abs(), "float32 gelu' against 2^-18 |v|")
+    r = ref64.assert_gemm_gelu_grad(C, acc, 1.0, bias, None, aux, "float32 gelu' against 2^-18 |pre|")
+    print(f"float32 (alpha acc + bias) * gelu'(aux), aux in [-8, -4]: {r:.3f} of 1 ulp + 2^-18 |pre|")
+    # (d, continued) alpha acc + bias + res cancelling: the float32 sum of the three terms misses 2^-18 |pre| alone
+    res = (-(acc + bias.to(F64)) + 1e-4 * _randn((M, N), 100)).to(torch.bfloat16)
+    aux1 = _randn((M, N), 101).to(torch.bfloat16)
+    C, _ = ref64.gemm_epilogue_emulated(acc, 1.0, bias, res, aux1)
+    v, pre = ref64.gemm_epilogue(acc, 1.0, bias, res, aux1), ref64.gemm_epilogue(acc, 1.0, bias, res)
+    with pytest.raises(AssertionError, match="exceed 1 bf16 ulp"):
+        ref64.assert_within_ulps(C, v, 1, 2.0 ** -18 * pre.abs(), "float32 sum of cancelling terms against 2^-18 |pre|")
+    ref64.assert_gemm_gelu_grad(C, acc, 1.0, bias, res, aux1, "float32 sum of cancelling terms")
+    # (e)
+    H, n = 8, 64
+    zz = _randn((n, H), 410).to(torch.bfloat16).to(F64)
+    gam = norm_cases.norm_weight(H, 411)
+    xh = ref64.layernorm_of_z(zz, gam, torch.zeros(H), 1e-12)[3]
+    beta = (-(xh[0] * gam.to(F64))).float()                        # row 0: xhat gamma + beta = 0 up to the float32 rounding of beta
+    keep = torch.zeros(n, H, dtype=F64)
+    keep[0, 3] = 1.0
+    keep[1:] = (torch.rand(n - 1, H, generator=_gen(412)) < 0.5).to(F64)
+    o64 = ref64.layernorm_of_z(zz, gam, beta, 1e-12, keep, 0.5)[0]
+    o32 = ref64.layernorm_of_z(zz, gam, beta, 1e-12, keep, 0.5, dtype=torch.float32)[0]
+    zf = zz.float()
+    mu = zf.sum(-1, keepdim=True) / H
+    rs = torch.rsqrt(((zf - mu) ** 2).sum(-1, keepdim=True) / H + 1e-12)
+    out = ((((zf - mu) * rs) * gam + beta) * keep.float() * 2.0).to(torch.bfloat16)           # sums in index order
+    unmasked = ref64.rowmax(ref64.layernorm_of_z(zz, gam, beta, 1e-12)[0]) * 2.0
+    ref64.assert_bf16_rows(out, o64, o32, "out, unmasked row scale", scale=unmasked)
+    err0 = float((out.to(F64) - o64)[0].abs().max())
+    own = float(ref64.bf16_ulp(o64[0, 3]) + 2.0 ** -18 * o64[0].abs().max())
+    print(f"out of the row whose one kept element cancels: reference {float(o64[0, 3]):.3e}, float32 off by {err0:.3e}, 1 ulp + 2^-18 of the masked row {own:.3e}")
+    assert err0 > own

@@ -405,6 +405,7 @@ extern "C" int ur_layernorm_bwd(const void* dout, const void* z, const float* me
   UR_REQUIRE(UR_ALIGNED16(dout) && UR_ALIGNED16(z) && UR_ALIGNED16(dz) && UR_ALIGNED16(gamma) && (!dy || UR_ALIGNED16(dy)),
              "ur_layernorm_bwd: 16-byte alignment");
   UR_REQUIRE(p_pre >= 0.f && p_pre < 1.f && p_post >= 0.f && p_post < 1.f, "ur_layernorm_bwd: dropout p out of range");
+  UR_REQUIRE(!(dy && dy == dz && p_pre > 0.f), "ur_layernorm_bwd: dy may alias dz only when p_pre == 0 (dz would be lost under the masked dy)");
   const Drop pre = make_drop(p_pre, seed_pre, drop_row0, H), post = make_drop(p_post, seed_post, drop_row0, H);
   const int grid = row_grid(M, LN_BWD_BLOCKS);
   hipStream_t st = (hipStream_t)stream;
