@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 15      /* 15: ur_lora_args.rank takes 8, 16, 32 or 64 (was 16 only); ur_gemm_args.drop_rank takes 64 as well */
+#define UR_ABI_VERSION 16      /* 16: ur_catalog_scores takes a ur_catalog_select_t* before the stream (NULL = the call as it was) */
 
 int ur_version(void);
 const char* ur_last_error(void);
@@ -425,14 +425,40 @@ int ur_mean_pool_bwd(const float* dout_f32, const void* dout_bf16, void* dx, int
  *   tokens).  Kinds: UR_KIND_U8 / UR_KIND_BF16 / UR_KIND_F32; f32 rows may be written as bf16.
  * ur_catalog_scores: scores[b][n] = cos(user_b, item_n) against a shared catalogue [N,D] f32 (F.normalize eps 1e-12,
  *   :408-415 with pool = all items); writes user_inv_norm [B], and cat_inv_norm [N] unless cat_norm_ready.
+ *   select == NULL is the plain call.  With select the call STREAMS instead: the catalogue is scored chunk_rows rows at a time into
+ *   the workspace (the same kernel on a row range, so every score is the f32 s_bn the plain call writes, bit for bit) and each
+ *   chunk is folded into a running top-K list and a count per user; nothing of size B*N exists and `scores` is neither needed
+ *   (may be NULL) nor written.  N <= INT32_MAX.  The norms are written as in the plain call.
+ *     item n is EXCLUDED for user b if it occurs in exclude[b] and n != gt_index[b] (the ground truth is never excluded);
+ *     topk_index[b] = the K non-excluded items of largest s_bn, descending, lowest index first among equal scores (ur_topk's
+ *       rule), topk_score[b] their scores; with fewer than K candidates the tail is index -1, score -inf;
+ *     rank[b] = 1 + #{non-excluded n : s_bn > s_b,gt_b} (ur_rank_of_index's rule).
+ *   NaN scores and gt_index outside [0,N) are unspecified, as for ur_topk / ur_rank_of_index.
+ *   Size query: with select->workspace == NULL the call checks the sizes, writes the bytes it needs for (B, N, K, chunk_rows)
+ *   into select->workspace_bytes and returns 0 without launching anything.
  * ur_rank_of_index: rank_b = 1 + #{n : s_bn > s_b,gt_b} (:416-417; the positive wins ties as in ur_mrr_rank). */
+#define UR_CATALOG_TOPK_MAX 128
+typedef struct {
+  int32_t K;                 /* 1 .. UR_CATALOG_TOPK_MAX */
+  int32_t E;                 /* row length of exclude (0 = no exclusion) */
+  int32_t* topk_index;       /* [B,K] out */
+  float* topk_score;         /* [B,K] out */
+  const int64_t* gt_index;   /* [B] or NULL */
+  int32_t* rank;             /* [B] out; given exactly when gt_index is */
+  const int64_t* exclude;    /* [B,E] or NULL; every row sorted ascending, negative entries = empty slots (they sort first),
+                                duplicates allowed */
+  int64_t chunk_rows;        /* catalogue rows scored per chunk; 0 = the library chooses (a chunk buffer near 64 MB); a positive
+                                value must be a multiple of 1024 */
+  void* workspace;           /* 16-byte aligned; NULL = size query */
+  int64_t workspace_bytes;   /* in: bytes at workspace; out (size query): bytes needed */
+} ur_catalog_select_t;
 #define UR_KIND_U8 0
 #define UR_KIND_BF16 1
 #define UR_KIND_F32 2
 int ur_gather_rows(const void* src, int32_t src_kind, void* out, int32_t out_kind, const int64_t* idx, int64_t row_elems,
                    int64_t n_out, int64_t n_src, void* stream);
 int ur_catalog_scores(const float* user, const float* catalog, float* scores, float* user_inv_norm, float* cat_inv_norm,
-                      int32_t cat_norm_ready, int32_t B, int64_t N, int32_t D, void* stream);
+                      int32_t cat_norm_ready, int32_t B, int64_t N, int32_t D, ur_catalog_select_t* select, void* stream);
 int ur_rank_of_index(const float* scores, const int64_t* gt_index, int32_t* rank, int32_t B, int64_t N, void* stream);
 /* ur_context_mlp1: first layer of the event-context MLPs of models/user_sequence_encoder.py:118-121:
  *   kind 0 = TimestampEncoder (models/mwne.py:525-565; in = timestamps.float() [n]; 9 features),

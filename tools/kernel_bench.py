@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the individual hot kernels (attention fwd/bwd, projection GEMMs) at the C4
 shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
-    python tools/kernel_bench.py attn|gemm|lora [--B 8] [--iters 5]"""
+    python tools/kernel_bench.py attn|gemm|lora [--B 8] [--iters 5]
+    python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 [--D 1024] [--rounds 3] [--chunks]"""
 import argparse
 import os
 import sys
@@ -249,13 +250,69 @@ def lora(args):
             print(f"lora all groups r={r:2d}: {tot * 1e3:7.1f} us per layer (forward projections + backward streams)  x{tot / sum(v for (gn, kn, rr), v in times.items() if rr == 16):.2f} of rank 16")
 
 
+def catalog(args):
+    """Full-catalogue evaluation: CatalogEvaluator.evaluate() (scores [B,N] + rank_of_index + topk, three kernels) against the streaming
+    retrieve() on the same random catalogue and users, alternating --rounds times after one call of each; wall time of the whole call (both
+    end in a host read of the metrics) and the peak allocation of a call above the level before it, scratch buffers included.
+    --chunks adds retrieve() at half and at double the default rows per chunk."""
+    from unirec_amd.evaluation import CatalogEvaluator
+    B, N, K, D = args.B, args.N, args.K, args.D
+    g = torch.Generator(device="cuda").manual_seed(0)
+    cat = torch.randn(N, D, generator=g, device="cuda")
+    user = torch.randn(B, D, generator=g, device="cuda")
+    gt = torch.randint(0, N, (B,), generator=g, device="cuda")
+    ev = CatalogEvaluator(cat)
+    ev.scores(user[:1])                                       # the catalogue norms: cached by both paths, outside every figure below
+    n_up = (N + 1023) // 1024 * 1024
+    rows = max(1024, min((64 << 20) // (4 * B) // 1024 * 1024, n_up))           # the library's default (catalog_chunk_rows)
+    variants = [("evaluate", lambda: ev.evaluate(user, gt, k=K)), (f"retrieve (chunk_rows default = {rows})", lambda: ev.retrieve(user, k=K, gt_index=gt))]
+    if args.chunks:
+        for r in (max(1024, rows // 2 // 1024 * 1024), min(rows * 2, n_up)):
+            variants.append((f"retrieve chunk_rows={r}", lambda r=r: ev.retrieve(user, k=K, gt_index=gt, chunk_rows=r)))
+    print(f"catalog B={B} N={N} D={D} K={K}: catalogue {N * D * 4 / 2**20:.0f} MiB, scores [B,N] f32 {B * N * 4 / 2**20:.0f} MiB")
+    peaks, outs, times = {}, {}, {name: [] for name, _ in variants}
+    for name, fn in variants:                                 # first call of each: warm-up, peak allocation with cold scratch, results
+        hip._ws_cache.clear()
+        torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        outs[name] = fn()
+        torch.cuda.synchronize()
+        peaks[name] = torch.cuda.max_memory_allocated() - base
+    ref = outs["evaluate"]
+    for name, _ in variants[1:]:
+        o = outs[name]
+        same = torch.equal(o["topk_index"], ref["topk_index"]) and torch.equal(o["topk_score"], ref["topk_score"]) and torch.equal(o["rank"], ref["rank"])
+        print(f"{name}: lists, scores and ranks equal evaluate()'s: {same}")
+        assert same
+    del outs
+    for name, fn in variants:                                 # scratch of every variant warm again
+        fn()
+    for _ in range(args.rounds):
+        for name, fn in variants:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    for name, _ in variants:
+        t = sorted(times[name])
+        print(f"{name:44s}: median {t[len(t) // 2]:9.2f} ms  min {t[0]:9.2f}  max {t[-1]:9.2f}  (spread {t[-1] - t[0]:.2f} over {len(t)} alternating rounds)"
+              f"  peak allocation {peaks[name] / 2**20:9.2f} MiB")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora"])
+    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog"])
     ap.add_argument("--B", type=int, default=8)
     ap.add_argument("--S", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--ranks", default="16,8,32,64", help="lora: the ranks to time, comma separated (rank 16 first gives every other rank its ratio)")
+    ap.add_argument("--N", type=int, default=1_000_000, help="catalog: items")
+    ap.add_argument("--K", type=int, default=10, help="catalog: list length")
+    ap.add_argument("--D", type=int, default=1024, help="catalog: embedding width")
+    ap.add_argument("--rounds", type=int, default=3, help="catalog: alternating timed rounds")
+    ap.add_argument("--chunks", action="store_true", help="catalog: also time retrieve() at half and double the default rows per chunk")
     ap.add_argument("--lib", action="store_true", help="gemm: also time torch.matmul on the same operands (reference point)")
     a = ap.parse_args()
-    {"attn": attn, "gemm": gemm, "lora": lora, "rope": rope, "dw": dw, "xattn": xattn, "gemm_lora": gemm_lora, "gemm_merge": gemm_merge, "gemm_step": gemm_step, "rmslora": rmslora, "swilora": swilora}[a.what](a)
+    {"attn": attn, "gemm": gemm, "lora": lora, "rope": rope, "dw": dw, "xattn": xattn, "gemm_lora": gemm_lora, "gemm_merge": gemm_merge, "gemm_step": gemm_step, "rmslora": rmslora, "swilora": swilora,
+     "catalog": catalog}[a.what](a)

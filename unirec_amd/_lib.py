@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -77,6 +77,16 @@ class AttnBwdArgs(ctypes.Structure):
 class AttnPlanInfo(ctypes.Structure):
     """Mirror of ur_attn_plan_info (kernel ids: UR_ATTN_KERNEL_*)."""
     _fields_ = [("fwd", c_int), ("dq", c_int), ("dkv", c_int), ("lse_log2", c_int), ("nw_q", c_int), ("nw_k", c_int)]
+
+
+class CatalogSelect(ctypes.Structure):
+    """Mirror of ur_catalog_select_t."""
+    _fields_ = [("K", c_int), ("E", c_int),
+                ("topk_index", c_void_p), ("topk_score", c_void_p),
+                ("gt_index", c_void_p), ("rank", c_void_p),
+                ("exclude", c_void_p),
+                ("chunk_rows", c_i64),
+                ("workspace", c_void_p), ("workspace_bytes", c_i64)]
 
 
 class F32Range(ctypes.Structure):
@@ -157,7 +167,8 @@ SIGNATURES = {
     "ur_infonce_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p,
                                    c_void_p, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
     "ur_gather_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_i64, c_i64, c_i64, c_void_p]),
-    "ur_catalog_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_i64, c_int, c_void_p]),
+    "ur_catalog_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_i64, c_int,
+                                  ctypes.POINTER(CatalogSelect), c_void_p]),
     "ur_rank_of_index": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p]),
     "ur_context_mlp1": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p]),
     "ur_mrr_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

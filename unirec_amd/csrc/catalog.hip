@@ -11,6 +11,9 @@
 //                       evaluation over pool = all items); the catalogue is read once per 16 users.
 //   ur_rank_of_index  : rank_b = 1 + #{n : s_bn > s_b,gt_b}  (:416-417: position of the positive in the descending
 //                       argsort; ties resolved for the positive, as ur_mrr_rank).
+//   ur_catalog_scores with a ur_catalog_select_t: streaming retrieval.  The host loop scores the catalogue a chunk of rows at a
+//                       time (the same kernel on a row range) and catalog_select_kernel folds each chunk into a running
+//                       top-K list and a count of scores above the ground truth's, per-user exclusion lists filtered out.
 #include "common.hip.h"
 #include "unirec_hip.h"
 
@@ -125,6 +128,147 @@ __global__ void rank_of_index_kernel(const float* __restrict__ scores, const lon
   if (threadIdx.x == 0) rank[b] = 1 + part[0] + part[1] + part[2] + part[3];
 }
 
+// ---- streaming selection (ur_catalog_select_t) -------------------------------------------------------------------------
+// s_b,gt for the rank count, before any chunk is scored: one wave per user runs catalog_scores_kernel's dot product on row gt[b]
+// (the same lane -> element map, the same fmaf chain, the same wave_sum and the same two multiplies), so ref[b] has the bits that
+// kernel writes for that row.
+__global__ __launch_bounds__(256) void catalog_gt_score_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
+                                                               const float* __restrict__ cat, const float* __restrict__ inv_c,
+                                                               const long* __restrict__ gt, float* __restrict__ ref, int B, long N, int D) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int lane = threadIdx.x & 63;
+  const long g = min(max(gt[b], 0L), N - 1);
+  const float* cp = cat + g * D;
+  const float* up = user + (long)b * D;
+  float acc = 0.f;
+  for (int d = lane * 4; d < D; d += 256) {
+    const float4 c = *reinterpret_cast<const float4*>(cp + d);
+    const float4 x = *reinterpret_cast<const float4*>(up + d);
+    acc = fmaf(c.x, x.x, fmaf(c.y, x.y, fmaf(c.z, x.z, fmaf(c.w, x.w, acc))));
+  }
+  const float ic = inv_c[g];
+  const float s = wave_sum(acc);
+  if (lane == 0) ref[b] = s * inv_u[b] * ic;
+}
+
+// The total order of the lists: score descending, index ascending.  An empty slot is (-inf, SEL_EMPTY): it follows every item.
+constexpr int SEL_TILE = 1024;                 // scores per sweep step: 4 per thread
+constexpr int SEL_SORT_MAX = 2048;             // >= UR_CATALOG_TOPK_MAX + SEL_TILE, a power of two
+constexpr int SEL_EMPTY = 0x7fffffff;
+static_assert(UR_CATALOG_TOPK_MAX + SEL_TILE <= SEL_SORT_MAX, "list + one tile of survivors must fit the sort buffer");
+__device__ __forceinline__ bool sel_before(float sa, int ia, float sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
+// n in the ascending row ex[0..E)?
+__device__ __forceinline__ bool sel_excluded(const long* __restrict__ ex, int E, long n) {
+  int lo = 0, hi = E;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (ex[mid] < n) lo = mid + 1; else hi = mid;
+  }
+  return lo < E && ex[lo] == n;
+}
+
+// One workgroup per user folds one chunk of scores (chunk[b][0..len), catalogue rows c0 .. c0+len) into the user's running list
+// (topk_score / topk_index [B,K]: sorted, empty slots = (-inf, -1)) and into rank[b] = 1 + #{non-excluded n : s_bn > ref[b]}.
+// Per tile every score is compared with the list's K-th entry; what passes and is not excluded is appended behind the list in LDS
+// through an LDS counter, and a tile that appended anything is merged by a bitonic sort of list + survivors under the total order
+// (so the result does not depend on the order of the appends).  A tile without survivors costs its read and compares.
+__global__ __launch_bounds__(256) void catalog_select_kernel(const float* __restrict__ chunk, long ld, int c0, int len, int K,
+                                                             float* __restrict__ topk_score, int* __restrict__ topk_index,
+                                                             const long* __restrict__ gt, const float* __restrict__ ref, int* __restrict__ rank,
+                                                             const long* __restrict__ exclude, int E, int first) {
+  __shared__ float ks[SEL_SORT_MAX];
+  __shared__ int ki[SEL_SORT_MAX];
+  __shared__ int n_surv[3];      // survivor counter of tile t = n_surv[t % 3] (see the sweep)
+  __shared__ int part[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float ninf = -__builtin_inff();
+  if (tid < K) {
+    float s = ninf;
+    int i = SEL_EMPTY;
+    if (!first) {
+      s = topk_score[(long)b * K + tid];
+      i = topk_index[(long)b * K + tid];
+      if (i < 0) i = SEL_EMPTY;
+    }
+    ks[tid] = s; ki[tid] = i;
+  }
+  if (tid == 0) n_surv[0] = 0;
+  __syncthreads();
+  float thr_s = ks[K - 1];
+  int thr_i = ki[K - 1];
+  const bool has_gt = gt != nullptr;
+  const long g = has_gt ? gt[b] : -1L;
+  const float rf = has_gt ? ref[b] : 0.f;
+  const long* ex = E > 0 ? exclude + (long)b * E : nullptr;
+  const float* row = chunk + (long)b * ld;
+  int cnt = 0;
+  // One barrier per tile without survivors: a thread may start appending to the next tile's counter while another still reads this
+  // tile's, so the counters rotate.  Thread 0 clears the NEXT tile's counter during this tile's sweep: that counter was last read
+  // two tiles ago, before the previous tile's barrier, and is first added to after this tile's.
+  int cur = 0;
+  for (int t0 = 0; t0 < len; t0 += SEL_TILE) {
+    const int nxt = cur == 2 ? 0 : cur + 1;
+    if (tid == 0) n_surv[nxt] = 0;
+#pragma unroll
+    for (int j = 0; j < SEL_TILE / 256; ++j) {
+      const int n = t0 + j * 256 + tid;
+      if (n < len) {
+        const float s = row[n];
+        const int idx = c0 + n;
+        const bool pass = sel_before(s, idx, thr_s, thr_i);
+        const bool above = has_gt && s > rf;
+        if (pass || above) {
+          const bool out = E > 0 && (long)idx != g && sel_excluded(ex, E, (long)idx);
+          if (!out) {
+            cnt += above ? 1 : 0;
+            if (pass) {
+              const int pos = K + atomicAdd(&n_surv[cur], 1);          // < K + SEL_TILE <= SEL_SORT_MAX
+              ks[pos] = s; ki[pos] = idx;
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    const int m = K + n_surv[cur];                                // uniform
+    cur = nxt;
+    if (m > K) {
+      int P = 2;
+      while (P < m) P <<= 1;
+      for (int i = m + tid; i < P; i += 256) { ks[i] = ninf; ki[i] = SEL_EMPTY; }
+      __syncthreads();
+      for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+          for (int i = tid; i < P; i += 256) {
+            const int q = i ^ j;
+            if (q > i) {
+              const float si = ks[i], sq = ks[q];
+              const int ii = ki[i], iq = ki[q];
+              const bool up = (i & k) == 0;                        // this pair ends in list order (best first)
+              if (up ? sel_before(sq, iq, si, ii) : sel_before(si, ii, sq, iq)) { ks[i] = sq; ki[i] = iq; ks[q] = si; ki[q] = ii; }
+            }
+          }
+          __syncthreads();
+        }
+      }
+      thr_s = ks[K - 1]; thr_i = ki[K - 1];
+    }
+  }
+  if (tid < K) {
+    topk_score[(long)b * K + tid] = ks[tid];
+    topk_index[(long)b * K + tid] = ki[tid] == SEL_EMPTY ? -1 : ki[tid];
+  }
+  if (has_gt) {
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if (lane == 0) part[wave] = cnt;
+    __syncthreads();
+    if (tid == 0) rank[b] = (first ? 1 : rank[b]) + part[0] + part[1] + part[2] + part[3];
+  }
+}
+
 // Context MLP, first layer: h1[n][j] = gelu(b1[j] + sum_f W1[j][f] * feat_f(n)), bf16 out.
 //   KIND 0: TimestampEncoder features, models/mwne.py:525-565 (9 = secular + 4 sin/cos pairs, all in f32 as the
 //           reference computes them from timestamps.float()).
@@ -198,16 +342,9 @@ extern "C" int ur_gather_rows(const void* src, int32_t src_kind, void* out, int3
   return 0;
 }
 
-extern "C" int ur_catalog_scores(const float* user, const float* catalog, float* scores, float* user_inv_norm, float* cat_inv_norm,
-                                 int32_t cat_norm_ready, int32_t B, int64_t N, int32_t D, void* stream) {
-  UR_REQUIRE(B >= 0 && N >= 0 && D > 0 && (D % 4) == 0 && D <= 2048, "ur_catalog_scores: need D %% 4 == 0 and D <= 2048 (got %d)", D);
-  if (B == 0 || N == 0) return 0;
-  UR_REQUIRE(user && catalog && scores && user_inv_norm && cat_inv_norm, "ur_catalog_scores: null pointer");
-  UR_REQUIRE(UR_ALIGNED16(user) && UR_ALIGNED16(catalog), "ur_catalog_scores: operands must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, user_inv_norm, (long)B, (int)D);
-  if (!cat_norm_ready)
-    hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, cat_inv_norm, (long)N, (int)D);
+// the scoring launch of both modes: rows [0,N) of `catalog` / `cat_inv_norm` into scores [B][N] (leading dimension N)
+static int launch_catalog_scores(const float* user, const float* user_inv_norm, const float* catalog, const float* cat_inv_norm,
+                                 float* scores, int32_t B, int64_t N, int32_t D, hipStream_t st) {
   const int ub = ur_cdiv(B, CU_USERS);
   long blocks_x = 2048 / ub;                                  // ~8 workgroups per CU in all
   if (blocks_x < 1) blocks_x = 1;
@@ -223,6 +360,78 @@ extern "C" int ur_catalog_scores(const float* user, const float* catalog, float*
   hipLaunchKernelGGL(catalog_scores_kernel, dim3((unsigned)blocks_x, (unsigned)ub), dim3(256), smem, st, user, user_inv_norm, catalog,
                      cat_inv_norm, scores, (int)B, (long)N, (int)D, (long)rpb);
   UR_CHECK_LAUNCH("ur_catalog_scores");
+  return 0;
+}
+
+// rows per chunk of the streaming mode: the caller's figure, or a chunk buffer [B, rows] near 64 MB (so that it can stay in the
+// Infinity Cache between the scoring and the selection launch); never more than N rounded up to the selection tile
+static int64_t catalog_chunk_rows(int64_t chunk_rows, int32_t B, int64_t N) {
+  const int64_t n_up = (N + SEL_TILE - 1) / SEL_TILE * SEL_TILE;
+  int64_t r = chunk_rows;
+  if (r <= 0) r = ((int64_t)64 << 20) / (4 * (int64_t)(B > 0 ? B : 1)) / SEL_TILE * SEL_TILE;
+  if (r > n_up) r = n_up;
+  if (r > ((int64_t)1 << 30)) r = (int64_t)1 << 30;           // the selection kernel indexes a chunk with an int
+  if (r < SEL_TILE) r = SEL_TILE;
+  return r;
+}
+
+extern "C" int ur_catalog_scores(const float* user, const float* catalog, float* scores, float* user_inv_norm, float* cat_inv_norm,
+                                 int32_t cat_norm_ready, int32_t B, int64_t N, int32_t D, ur_catalog_select_t* select, void* stream) {
+  UR_REQUIRE(B >= 0 && N >= 0 && D > 0 && (D % 4) == 0 && D <= 2048, "ur_catalog_scores: need D %% 4 == 0 and D <= 2048 (got %d)", D);
+  hipStream_t st = (hipStream_t)stream;
+  if (!select) {
+    if (B == 0 || N == 0) return 0;
+    UR_REQUIRE(user && catalog && scores && user_inv_norm && cat_inv_norm, "ur_catalog_scores: null pointer");
+    UR_REQUIRE(UR_ALIGNED16(user) && UR_ALIGNED16(catalog), "ur_catalog_scores: operands must be 16-byte aligned");
+    hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, user_inv_norm, (long)B, (int)D);
+    if (!cat_norm_ready)
+      hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, cat_inv_norm, (long)N, (int)D);
+    return launch_catalog_scores(user, user_inv_norm, catalog, cat_inv_norm, scores, B, N, D, st);
+  }
+  // ---- streaming selection: every check before any launch ----
+  const int K = select->K, E = select->E;
+  UR_REQUIRE(K >= 1 && K <= UR_CATALOG_TOPK_MAX, "ur_catalog_scores: select.K must be 1 .. %d (got %d)", UR_CATALOG_TOPK_MAX, K);
+  UR_REQUIRE(N <= (int64_t)INT32_MAX, "ur_catalog_scores: select mode needs N <= INT32_MAX (got %lld)", (long long)N);
+  UR_REQUIRE(select->chunk_rows >= 0 && (select->chunk_rows % SEL_TILE) == 0,
+             "ur_catalog_scores: select.chunk_rows must be 0 or a positive multiple of %d (got %lld)", SEL_TILE, (long long)select->chunk_rows);
+  UR_REQUIRE(E >= 0 && (E == 0 || select->exclude), "ur_catalog_scores: select.E > 0 needs select.exclude");
+  UR_REQUIRE((select->gt_index != nullptr) == (select->rank != nullptr), "ur_catalog_scores: select.gt_index and select.rank go together");
+  const int64_t rows = catalog_chunk_rows(select->chunk_rows, B, N);
+  const int64_t chunk_bytes = ((int64_t)B * rows * 4 + 15) / 16 * 16;
+  const int64_t need = chunk_bytes + ((int64_t)B * 4 + 15) / 16 * 16;      // chunk [B][rows] f32 | ref [B] f32
+  if (!select->workspace) {
+    select->workspace_bytes = need > 16 ? need : 16;
+    return 0;
+  }
+  UR_REQUIRE(UR_ALIGNED16(select->workspace) && select->workspace_bytes >= need,
+             "ur_catalog_scores: select.workspace must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)need, (long long)select->workspace_bytes);
+  if (B == 0) return 0;
+  UR_REQUIRE(select->topk_index && select->topk_score, "ur_catalog_scores: select.topk_index / topk_score are null");
+  UR_REQUIRE(user && user_inv_norm && (N == 0 || (catalog && cat_inv_norm)), "ur_catalog_scores: null pointer");
+  UR_REQUIRE(UR_ALIGNED16(user) && UR_ALIGNED16(catalog), "ur_catalog_scores: operands must be 16-byte aligned");
+  float* chunk = (float*)select->workspace;
+  float* ref = (float*)((char*)select->workspace + chunk_bytes);
+  const long* gt = (const long*)select->gt_index;
+  hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, user_inv_norm, (long)B, (int)D);
+  if (!cat_norm_ready && N > 0)
+    hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, cat_inv_norm, (long)N, (int)D);
+  if (gt && N > 0)
+    hipLaunchKernelGGL(catalog_gt_score_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, (const float*)user_inv_norm, catalog,
+                       (const float*)cat_inv_norm, gt, ref, (int)B, (long)N, (int)D);
+  UR_CHECK_LAUNCH("ur_catalog_scores");
+  int64_t c0 = 0;
+  do {                                                         // (N == 0: one pass over an empty chunk writes the empty lists)
+    const int64_t len = N - c0 < rows ? N - c0 : rows;
+    if (len > 0) {
+      const int rc = launch_catalog_scores(user, user_inv_norm, catalog + c0 * D, cat_inv_norm + c0, chunk, B, len, D, st);
+      if (rc != 0) return rc;
+    }
+    hipLaunchKernelGGL(catalog_select_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0, (int)len, K,
+                       select->topk_score, select->topk_index, gt, (const float*)ref, select->rank, (const long*)select->exclude, E,
+                       (int)(c0 == 0));
+    UR_CHECK_LAUNCH("ur_catalog_scores");
+    c0 += rows;
+  } while (c0 < N);
   return 0;
 }
 

@@ -7,6 +7,8 @@
   * ``MRREvaluator``              :361-419 (per-user candidate lists: positive first, cosine scores, rank of the positive)
   * ``CatalogEvaluator``          the same metric with pool = ALL items: one shared catalogue [N,D] resident in HBM,
                                   ``ur_catalog_scores`` + ``ur_rank_of_index`` + ``ur_topk``; no host sync per user.
+                                  ``retrieve`` is the catalogue-scale form: the scores are streamed in chunks through
+                                  ``ur_catalog_scores``' select mode (top-K, rank and a per-user seen-item filter; no [B,N] tensor).
 Tie rule: the positive's rank is 1 + #{strictly greater}; top-K lists the lowest index first.
 """
 import numpy as np
@@ -98,6 +100,45 @@ class MRREvaluator:
         return float(np.mean(scores))
 
 
+def pack_exclude(exclude, num_users=None):
+    """Per-user exclusion lists -> the sorted int64 [B,E] tensor ``hip.catalog_select`` takes, or None when nothing is excluded.
+    ``exclude`` is a ragged list of per-user index iterables, or an int64 [B,E] tensor padded with negative entries.  Rows come out
+    ascending and padded with -1 in front (empty slots sort first); duplicates are kept.  Pure: stays on the input's device (CPU
+    for lists)."""
+    if exclude is None:
+        return None
+    if isinstance(exclude, torch.Tensor):
+        t = exclude.to(torch.int64)
+        if t.dim() != 2:
+            raise ValueError(f"pack_exclude: a tensor must be [B,E], got {tuple(t.shape)}")
+    else:
+        rows = [sorted(int(i) for i in r) for r in exclude]
+        E = max([len(r) for r in rows] + [0])
+        t = torch.full((len(rows), E), -1, dtype=torch.int64)
+        for b, r in enumerate(rows):
+            if r:
+                t[b, E - len(r):] = torch.tensor(r, dtype=torch.int64)
+    if num_users is not None and t.shape[0] != num_users:
+        raise ValueError(f"pack_exclude: {t.shape[0]} rows for {num_users} users")
+    if t.numel() == 0 or not bool((t >= 0).any()):
+        return None
+    t = torch.where(t < 0, torch.full_like(t, -1), t)
+    return torch.sort(t, dim=1).values.contiguous()
+
+
+def ranking_metrics(rank, ks):
+    """Rank-based metrics with ONE relevant item per user, in float64 on rank's device: a [1 + 2 len(ks)] tensor
+    (mrr, hit@k for k in ks, ndcg@k for k in ks); hit@k = mean(rank <= k), ndcg@k = mean(1 / log2(1 + rank) if rank <= k else 0).
+    Pure (no host read): the caller fetches all of them at once."""
+    r = rank.to(torch.float64)
+    gain = 1.0 / torch.log2(1.0 + r)
+    zero = torch.zeros_like(r)
+    out = [(1.0 / r).mean()]
+    out += [(r <= k).to(torch.float64).mean() for k in ks]
+    out += [torch.where(r <= k, gain, zero).mean() for k in ks]
+    return torch.stack(out)
+
+
 class CatalogEvaluator:
     """MRR / hit@K / top-K of user embeddings against the whole item catalogue (pool = all items)."""
 
@@ -118,3 +159,23 @@ class CatalogEvaluator:
         idx, val = hip.topk(s, k)
         return {"rank": rank, "mrr": float((1.0 / rank.to(torch.float64)).mean().item()),
                 "hit_at_k": float((rank <= k).to(torch.float64).mean().item()), "topk_index": idx, "topk_score": val}
+
+    def retrieve(self, user_embeddings, k=10, gt_index=None, exclude=None, ks=None, chunk_rows=None):
+        """Catalogue-scale retrieval: the scores are streamed in chunks and never held as [B,N].
+        exclude: items each user has already seen (ragged lists or an int64 [B,E] tensor padded with -1, see pack_exclude); they leave
+        the lists and the ranks, except a user's own gt_index.
+        -> dict(topk_index int32 [B,k], topk_score f32 [B,k]); with gt_index also rank int32 [B], mrr, and hit_at / ndcg_at:
+        dicts keyed by each K of ks (default (k,); any K, the metrics need only the rank).  Same scores, tie rule and rank rule as
+        evaluate()."""
+        u = user_embeddings.detach().to(self.catalog.device, F32).contiguous()
+        ex = pack_exclude(exclude, u.shape[0])
+        if ex is not None:
+            ex = ex.to(u.device)
+        gt = None if gt_index is None else torch.as_tensor(gt_index).to(u.device, torch.int64)
+        idx, val, rank, self._inv = hip.catalog_select(u, self.catalog, k, self._inv, gt_index=gt, exclude=ex, chunk_rows=chunk_rows)
+        out = {"topk_index": idx, "topk_score": val}
+        if rank is not None:
+            ks = (k,) if ks is None else tuple(int(x) for x in ks)
+            m = ranking_metrics(rank, ks).cpu().tolist()                                 # the one host read
+            out.update(rank=rank, mrr=m[0], hit_at=dict(zip(ks, m[1:1 + len(ks)])), ndcg_at=dict(zip(ks, m[1 + len(ks):])))
+        return out

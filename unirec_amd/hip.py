@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, AttnBwdArgs, AttnPlanInfo, GemmArgs, LoraArgs, check
+from ._lib import AttnArgs, AttnBwdArgs, AttnPlanInfo, CatalogSelect, GemmArgs, LoraArgs, check
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -1046,8 +1046,55 @@ def catalog_scores(user, catalog, cat_inv_norm=None):
     if not ready:
         cat_inv_norm = torch.empty((N,), dtype=F32, device=user.device)
     check(lib.ur_catalog_scores(user.data_ptr(), catalog.data_ptr(), scores.data_ptr(), uinv.data_ptr(), cat_inv_norm.data_ptr(),
-                                int(ready), B, N, D, _stream()), "ur_catalog_scores")
+                                int(ready), B, N, D, None, _stream()), "ur_catalog_scores")
     return scores, cat_inv_norm
+
+
+CATALOG_TOPK_MAX = 128      # UR_CATALOG_TOPK_MAX
+
+
+def catalog_select(user, catalog, K, cat_inv_norm=None, gt_index=None, exclude=None, chunk_rows=None):
+    """Streaming retrieval over a shared catalogue [N,D] f32 (ur_catalog_scores with a ur_catalog_select_t): the K best items per user
+    of user [B,D] f32 under catalog_scores' own f32 scores, descending, lowest index first among equal scores; no [B,N] tensor exists.
+    gt_index int64 [B]: also the 1-based rank of that item (1 + the number of strictly greater scores).  exclude int64 [B,E], rows
+    sorted ascending with negative entries as empty slots: those items are left out of the list and of the count, except the user's
+    own gt_index.  chunk_rows: catalogue rows scored per chunk (a multiple of 1024; None = the library's choice).
+    Returns (topk_index int32 [B,K], topk_score f32 [B,K], rank int32 [B] or None, cat_inv_norm); with fewer than K candidates the
+    tail of a row is index -1, score -inf."""
+    lib = _lib.load()
+    _need(user, F32, "user")
+    _need(catalog, F32, "catalog")
+    B, D = user.shape
+    N = catalog.shape[0]
+    dev = user.device
+    sel = CatalogSelect()
+    sel.K, sel.chunk_rows = int(K), int(chunk_rows or 0)
+    idx = torch.empty((B, max(int(K), 0)), dtype=torch.int32, device=dev)
+    val = torch.empty((B, max(int(K), 0)), dtype=F32, device=dev)
+    sel.topk_index, sel.topk_score = idx.data_ptr(), val.data_ptr()
+    rank = gt = None
+    if gt_index is not None:
+        gt = gt_index.to(device=dev, dtype=torch.int64).contiguous()
+        if gt.shape != (B,):
+            raise ValueError(f"catalog_select: gt_index must have shape [{B}], got {tuple(gt.shape)}")
+        rank = torch.empty((B,), dtype=torch.int32, device=dev)
+        sel.gt_index, sel.rank = gt.data_ptr(), rank.data_ptr()
+    if exclude is not None:
+        _need(exclude, torch.int64, "exclude")
+        if exclude.dim() != 2 or exclude.shape[0] != B:
+            raise ValueError(f"catalog_select: exclude must be [{B}, E], got {tuple(exclude.shape)}")
+        sel.E = exclude.shape[1]
+        sel.exclude = exclude.data_ptr() if sel.E else None
+    uinv = torch.empty((B,), dtype=F32, device=dev)
+    ready = cat_inv_norm is not None
+    if not ready:
+        cat_inv_norm = torch.empty((N,), dtype=F32, device=dev)
+    args = (user.data_ptr(), catalog.data_ptr(), None, uinv.data_ptr(), cat_inv_norm.data_ptr(), int(ready), B, N, D)
+    check(lib.ur_catalog_scores(*args, ctypes.byref(sel), _stream()), "ur_catalog_scores")        # size query: workspace is NULL
+    ws = workspace(sel.workspace_bytes, dev, "catalog_select")
+    sel.workspace = ws.data_ptr()
+    check(lib.ur_catalog_scores(*args, ctypes.byref(sel), _stream()), "ur_catalog_scores")
+    return idx, val, rank, cat_inv_norm
 
 
 def rank_of_index(scores, gt_index):
