@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 16      /* 16: ur_catalog_scores takes a ur_catalog_select_t* before the stream (NULL = the call as it was) */
+#define UR_ABI_VERSION 17      /* 17: ur_catalog_select_t ends in catalog_bf16 and scorer (zero = the call as it was) */
 
 int ur_version(void);
 const char* ur_last_error(void);
@@ -434,6 +434,12 @@ int ur_mean_pool_bwd(const float* dout_f32, const void* dout_bf16, void* dx, int
  *       rule), topk_score[b] their scores; with fewer than K candidates the tail is index -1, score -inf;
  *     rank[b] = 1 + #{non-excluded n : s_bn > s_b,gt_b} (ur_rank_of_index's rule).
  *   NaN scores and gt_index outside [0,N) are unspecified, as for ur_topk / ur_rank_of_index.
+ *   select->catalog_bf16 = 1: `catalog` points at bf16 [N,D] rows (passed through the same pointer; D % 4 == 0 and the 16-byte
+ *   base as for f32).  Every element is widened exactly on load, so lists, score bits, ranks and cat_inv_norm are those of the f32
+ *   copy of that catalogue.  The plain call stays f32-only.
+ *   select->scorer picks the kernel that scores a chunk: UR_CATALOG_SCORER_VECTOR is the plain call's kernel, UR_CATALOG_SCORER_MFMA
+ *   computes the same fmaf chains and the same sum tree on v_mfma_f32_16x16x4_f32 -- the same score bits, so the choice never shows
+ *   in a result; 0 leaves it to the library (by shape; docs/lab_notes.md section 22).  Both take both catalogue types.
  *   Size query: with select->workspace == NULL the call checks the sizes, writes the bytes it needs for (B, N, K, chunk_rows)
  *   into select->workspace_bytes and returns 0 without launching anything.
  * ur_rank_of_index: rank_b = 1 + #{n : s_bn > s_b,gt_b} (:416-417; the positive wins ties as in ur_mrr_rank). */
@@ -451,7 +457,11 @@ typedef struct {
                                 value must be a multiple of 1024 */
   void* workspace;           /* 16-byte aligned; NULL = size query */
   int64_t workspace_bytes;   /* in: bytes at workspace; out (size query): bytes needed */
+  int32_t catalog_bf16;      /* 0: catalog is f32 [N,D]; 1: catalog is bf16 [N,D]; anything else is rejected */
+  int32_t scorer;            /* 0: the library chooses; UR_CATALOG_SCORER_VECTOR; UR_CATALOG_SCORER_MFMA; anything else is rejected */
 } ur_catalog_select_t;
+#define UR_CATALOG_SCORER_VECTOR 1
+#define UR_CATALOG_SCORER_MFMA 2
 #define UR_KIND_U8 0
 #define UR_KIND_BF16 1
 #define UR_KIND_F32 2

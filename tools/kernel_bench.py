@@ -2,7 +2,8 @@
 """Micro-benchmarks of the individual hot kernels (attention fwd/bwd, projection GEMMs) at the C4
 shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
     python tools/kernel_bench.py attn|gemm|lora [--B 8] [--iters 5]
-    python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 [--D 1024] [--rounds 3] [--chunks]"""
+    python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 [--D 1024] [--rounds 3] [--chunks]
+    python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 --scorer vector mfma --catalog-dtype bf16"""
 import argparse
 import os
 import sys
@@ -254,22 +255,33 @@ def catalog(args):
     """Full-catalogue evaluation: CatalogEvaluator.evaluate() (scores [B,N] + rank_of_index + topk, three kernels) against the streaming
     retrieve() on the same random catalogue and users, alternating --rounds times after one call of each; wall time of the whole call (both
     end in a host read of the metrics) and the peak allocation of a call above the level before it, scratch buffers included.
-    --chunks adds retrieve() at half and at double the default rows per chunk."""
+    --chunks adds retrieve() at half and at double the default rows per chunk.
+    --scorer vector mfma times retrieve() once per named scorer instead (alternating in this process, the library's own choice last);
+    --catalog-dtype bf16 keeps the catalogue in bf16, where evaluate() does not exist and the first scorer named is the reference."""
     from unirec_amd.evaluation import CatalogEvaluator
     B, N, K, D = args.B, args.N, args.K, args.D
+    bf16 = args.catalog_dtype == "bf16"
     g = torch.Generator(device="cuda").manual_seed(0)
     cat = torch.randn(N, D, generator=g, device="cuda")
+    if bf16:
+        cat = cat.to(torch.bfloat16)
     user = torch.randn(B, D, generator=g, device="cuda")
     gt = torch.randint(0, N, (B,), generator=g, device="cuda")
-    ev = CatalogEvaluator(cat)
-    ev.scores(user[:1])                                       # the catalogue norms: cached by both paths, outside every figure below
+    ev = CatalogEvaluator(cat, dtype=cat.dtype)
+    ev.retrieve(user[:1], k=1)                                # the catalogue norms: cached by every path, outside every figure below
     n_up = (N + 1023) // 1024 * 1024
     rows = max(1024, min((64 << 20) // (4 * B) // 1024 * 1024, n_up))           # the library's default (catalog_chunk_rows)
-    variants = [("evaluate", lambda: ev.evaluate(user, gt, k=K)), (f"retrieve (chunk_rows default = {rows})", lambda: ev.retrieve(user, k=K, gt_index=gt))]
+    variants = [] if bf16 else [("evaluate", lambda: ev.evaluate(user, gt, k=K))]
+    if args.scorer:
+        variants += [(f"retrieve scorer={sc}", lambda sc=sc: ev.retrieve(user, k=K, gt_index=gt, scorer=sc)) for sc in args.scorer]
+        variants.append(("retrieve scorer=None (library)", lambda: ev.retrieve(user, k=K, gt_index=gt)))
+    else:
+        variants.append((f"retrieve (chunk_rows default = {rows})", lambda: ev.retrieve(user, k=K, gt_index=gt)))
     if args.chunks:
         for r in (max(1024, rows // 2 // 1024 * 1024), min(rows * 2, n_up)):
             variants.append((f"retrieve chunk_rows={r}", lambda r=r: ev.retrieve(user, k=K, gt_index=gt, chunk_rows=r)))
-    print(f"catalog B={B} N={N} D={D} K={K}: catalogue {N * D * 4 / 2**20:.0f} MiB, scores [B,N] f32 {B * N * 4 / 2**20:.0f} MiB")
+    print(f"catalog B={B} N={N} D={D} K={K}: catalogue {args.catalog_dtype} {cat.numel() * cat.element_size() / 2**20:.0f} MiB, "
+          f"scores [B,N] f32 {B * N * 4 / 2**20:.0f} MiB, chunk_rows default = {rows}")
     peaks, outs, times = {}, {}, {name: [] for name, _ in variants}
     for name, fn in variants:                                 # first call of each: warm-up, peak allocation with cold scratch, results
         hip._ws_cache.clear()
@@ -278,11 +290,11 @@ def catalog(args):
         outs[name] = fn()
         torch.cuda.synchronize()
         peaks[name] = torch.cuda.max_memory_allocated() - base
-    ref = outs["evaluate"]
+    ref = outs[variants[0][0]]
     for name, _ in variants[1:]:
         o = outs[name]
         same = torch.equal(o["topk_index"], ref["topk_index"]) and torch.equal(o["topk_score"], ref["topk_score"]) and torch.equal(o["rank"], ref["rank"])
-        print(f"{name}: lists, scores and ranks equal evaluate()'s: {same}")
+        print(f"{name}: lists, scores and ranks equal those of {variants[0][0]}: {same}")
         assert same
     del outs
     for name, fn in variants:                                 # scratch of every variant warm again
@@ -312,6 +324,8 @@ if __name__ == "__main__":
     ap.add_argument("--D", type=int, default=1024, help="catalog: embedding width")
     ap.add_argument("--rounds", type=int, default=3, help="catalog: alternating timed rounds")
     ap.add_argument("--chunks", action="store_true", help="catalog: also time retrieve() at half and double the default rows per chunk")
+    ap.add_argument("--scorer", nargs="+", choices=["vector", "mfma"], help="catalog: time retrieve() with each of these scorers, alternating")
+    ap.add_argument("--catalog-dtype", choices=["f32", "bf16"], default="f32", help="catalog: the dtype the catalogue is stored in")
     ap.add_argument("--lib", action="store_true", help="gemm: also time torch.matmul on the same operands (reference point)")
     a = ap.parse_args()
     {"attn": attn, "gemm": gemm, "lora": lora, "rope": rope, "dw": dw, "xattn": xattn, "gemm_lora": gemm_lora, "gemm_merge": gemm_merge, "gemm_step": gemm_step, "rmslora": rmslora, "swilora": swilora,

@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -86,7 +86,8 @@ class CatalogSelect(ctypes.Structure):
                 ("gt_index", c_void_p), ("rank", c_void_p),
                 ("exclude", c_void_p),
                 ("chunk_rows", c_i64),
-                ("workspace", c_void_p), ("workspace_bytes", c_i64)]
+                ("workspace", c_void_p), ("workspace_bytes", c_i64),
+                ("catalog_bf16", c_int), ("scorer", c_int)]
 
 
 class F32Range(ctypes.Structure):

@@ -14,6 +14,8 @@
 //   ur_catalog_scores with a ur_catalog_select_t: streaming retrieval.  The host loop scores the catalogue a chunk of rows at a
 //                       time (the same kernel on a row range) and catalog_select_kernel folds each chunk into a running
 //                       top-K list and a count of scores above the ground truth's, per-user exclusion lists filtered out.
+//                       Here the catalogue may be bf16 (widened exactly on load) and a chunk may be scored on the f32 matrix cores
+//                       (catalog_scores_mfma_kernel: the vector kernel's fmaf chains and sum tree, so the same score bits).
 #include "common.hip.h"
 #include "unirec_hip.h"
 
@@ -57,14 +59,23 @@ __global__ void gather_bytes_kernel(const uint8_t* __restrict__ src, const long*
   out[i] = (s >= 0 && s < n_src) ? src[s * row_bytes + c] : (uint8_t)0;
 }
 
-__global__ void row_inv_norm_kernel(const float* __restrict__ x, float* __restrict__ inv, long rows, int D) {
+// Catalogue element loads: the kernels below are templated on the stored type CT (float or bf16_t) and differ in nothing but these.
+// bf16 -> f32 is a 16-bit shift, exact, so a bf16 catalogue scores bit for bit as its .float() copy does.
+__device__ __forceinline__ float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float4 load4(const bf16_t* p) {
+  const uint2 v = *reinterpret_cast<const uint2*>(p);
+  return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
+}
+
+template <typename CT>
+__global__ void row_inv_norm_kernel(const CT* __restrict__ x, float* __restrict__ inv, long rows, int D) {
   const long row = (long)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
-  const float* p = x + row * D;
+  const CT* p = x + row * D;
   float s = 0.f;
   for (int d = lane * 4; d < D; d += 256) {
-    const float4 v = *reinterpret_cast<const float4*>(p + d);
+    const float4 v = load4(p + d);
     s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
   }
   s = wave_sum(s);
@@ -75,8 +86,9 @@ __global__ void row_inv_norm_kernel(const float* __restrict__ x, float* __restri
 // (their vectors staged once in LDS) and walks catalogue rows, one row per wave per step: each lane holds 4-element
 // pieces of the row and accumulates 16 dot products, reduced across the wave at the end of the row.
 constexpr int CU_USERS = 16;
+template <typename CT>
 __global__ __launch_bounds__(256) void catalog_scores_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
-                                                             const float* __restrict__ cat, const float* __restrict__ inv_c,
+                                                             const CT* __restrict__ cat, const float* __restrict__ inv_c,
                                                              float* __restrict__ scores, int B, long N, int D, long rows_per_block) {
   extern __shared__ __attribute__((aligned(16))) float us[];      // [CU_USERS][D]
   const int b0 = blockIdx.y * CU_USERS;
@@ -94,9 +106,9 @@ __global__ __launch_bounds__(256) void catalog_scores_kernel(const float* __rest
     float acc[CU_USERS];
 #pragma unroll
     for (int u = 0; u < CU_USERS; ++u) acc[u] = 0.f;
-    const float* cp = cat + n * D;
+    const CT* cp = cat + n * D;
     for (int d = lane * 4; d < D; d += 256) {
-      const float4 c = *reinterpret_cast<const float4*>(cp + d);
+      const float4 c = load4(cp + d);
 #pragma unroll
       for (int u = 0; u < CU_USERS; ++u) {
         const float4 x = *reinterpret_cast<const float4*>(us + u * D + d);
@@ -132,24 +144,154 @@ __global__ void rank_of_index_kernel(const float* __restrict__ scores, const lon
 // s_b,gt for the rank count, before any chunk is scored: one wave per user runs catalog_scores_kernel's dot product on row gt[b]
 // (the same lane -> element map, the same fmaf chain, the same wave_sum and the same two multiplies), so ref[b] has the bits that
 // kernel writes for that row.
+template <typename CT>
 __global__ __launch_bounds__(256) void catalog_gt_score_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
-                                                               const float* __restrict__ cat, const float* __restrict__ inv_c,
+                                                               const CT* __restrict__ cat, const float* __restrict__ inv_c,
                                                                const long* __restrict__ gt, float* __restrict__ ref, int B, long N, int D) {
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
   const int lane = threadIdx.x & 63;
   const long g = min(max(gt[b], 0L), N - 1);
-  const float* cp = cat + g * D;
+  const CT* cp = cat + g * D;
   const float* up = user + (long)b * D;
   float acc = 0.f;
   for (int d = lane * 4; d < D; d += 256) {
-    const float4 c = *reinterpret_cast<const float4*>(cp + d);
+    const float4 c = load4(cp + d);
     const float4 x = *reinterpret_cast<const float4*>(up + d);
     acc = fmaf(c.x, x.x, fmaf(c.y, x.y, fmaf(c.z, x.z, fmaf(c.w, x.w, acc))));
   }
   const float ic = inv_c[g];
   const float s = wave_sum(acc);
   if (lane == 0) ref[b] = s * inv_u[b] * ic;
+}
+
+// ---- f32-MFMA scorer ---------------------------------------------------------------------------------------------------------
+// The same scores as catalog_scores_kernel, bit for bit, on v_mfma_f32_16x16x4_f32 (a k-ordered f32 fmaf chain from the C input, one
+// rounding per product).  The vector kernel's score of (user u, row n) is: per lane l a chain p_l over the 4-element pieces at
+// d = 4l + 256j (j = 0, 1, ...; inside a piece w, z, y, x), then wave_sum's balanced tree over the 64 lanes (pairs 32 apart first),
+// then (v * inv_u) * inv_c.  Here "lane l" becomes chain c: for one c the pieces j = 0 .. J-1 are the K dimension (4 per MFMA, k = 0
+// .. 3 <-> w, z, y, x) of a [16 users] x [16 rows] product from C = 0, which yields p_c of all 256 pairs at once.  A piece that lies
+// past D is skipped (the condition is wave-uniform), as the lane's loop ends there; a chain without pieces stays +0.
+// A workgroup = 4 waves owns 16 UT users (vectors staged once in LDS, in operand order) and walks groups of 16 RT rows; all four
+// waves work on the same UT x RT tiles, wave w on the 16 chains c = w + 4t.  Visiting t in 4-bit bit-reversed order completes the
+// tree's pairs as they arrive (5 pending tiles at most); what is left per wave is the subtree y_w of the lanes = w mod 4, and the
+// last two levels, (y_0 + y_2) + (y_1 + y_3), go through LDS, wave w finishing tile w.  The catalogue operand is loaded straight
+// from global memory in operand layout (lane = (row, k)), two chains ahead; the four waves touch the same 64 bytes of a row together.
+constexpr int MF_TILES = 4;                    // 16x16 output tiles per wave (UT x RT) = waves per workgroup
+__host__ __device__ constexpr int mf_bitrev4(int i) { return ((i & 1) << 3) | ((i & 2) << 1) | ((i & 4) >> 1) | ((i & 8) >> 3); }
+__host__ __device__ constexpr int mf_trailing_ones(int i) { return (i & 1) ? 1 + mf_trailing_ones(i >> 1) : 0; }
+__host__ __device__ constexpr size_t mf_lds_bytes(int D, bool wide) {
+  return ((size_t)((D + 255) / 256) * (wide ? 1 : 2) * 64 * 64 + 4 * MF_TILES * 64 * 4) * sizeof(float);
+}
+
+// the wave's element of a catalogue row for one MFMA: lane (row, k) takes element 3 - k of a 4-element piece.  f32: that dword.
+// bf16: the aligned dword that holds the element and its neighbour, widened by a shift or a mask (half-word loads were 11 % slower, docs/lab_notes.md section 22).
+template <typename CT> struct mf_row;
+template <> struct mf_row<float> {
+  const float* p = nullptr;
+  mf_row() = default;
+  __device__ __forceinline__ mf_row(const float* row, int k) : p(row + (3 - k)) {}
+  __device__ __forceinline__ float at(int off) const { return p[off]; }                 // off: element offset of the piece in the row
+};
+template <> struct mf_row<bf16_t> {
+  const uint32_t* p = nullptr;
+  bool hi = false;
+  mf_row() = default;
+  __device__ __forceinline__ mf_row(const bf16_t* row, int k) : p(reinterpret_cast<const uint32_t*>(row) + ((3 - k) >> 1)), hi((3 - k) & 1) {}
+  __device__ __forceinline__ float at(int off) const {
+    const uint32_t v = p[off >> 1];
+    return __uint_as_float(hi ? (v & 0xffff0000u) : (v << 16));
+  }
+};
+
+// WIDE: D > 1024 (16 users per workgroup, 8 pieces per chain at most).  FULL: D = 256 JMAX, so every chain has every piece and the
+// conditions below fold away; the code is one straight line per row group.
+template <typename CT, bool WIDE, bool FULL>
+__global__ __launch_bounds__(256) void catalog_scores_mfma_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
+                                                                  const CT* __restrict__ cat, const float* __restrict__ inv_c,
+                                                                  float* __restrict__ scores, int B, long N, int D, long rows_per_block, int ub) {
+  constexpr int UT = WIDE ? 1 : 2, RT = MF_TILES / UT, JMAX = WIDE ? 8 : 4;
+  extern __shared__ __attribute__((aligned(16))) float us[];       // [64 chains][J][UT][k 4][user 16] | exchange [4 waves][MF_TILES][64] f32x4
+  const int J = (D + 255) >> 8;
+  f32x4* ex = reinterpret_cast<f32x4*>(us + J * UT * 64 * 64);
+  const int ug = blockIdx.x % ub;
+  const long rb = blockIdx.x / ub;
+  const int b0 = ug * 16 * UT;
+  const int nb = min(16 * UT, B - b0);
+  const int D4 = D >> 2;
+  for (int i = threadIdx.x; i < 16 * UT * D4; i += 256) {
+    const int u = i / D4, d = (i - u * D4) * 4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (u < nb) v = *reinterpret_cast<const float4*>(user + (long)(b0 + u) * D + d);
+    float* q = us + (((((d & 255) >> 2) * J + (d >> 8)) * UT + (u >> 4)) << 6) + (u & 15);
+    q[0] = v.w; q[16] = v.z; q[32] = v.y; q[48] = v.x;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, col = lane & 15, k = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long r0 = rb * rows_per_block, r1 = min(N, r0 + rows_per_block);
+  for (long n0 = r0; n0 < r1; n0 += 16 * RT) {
+    mf_row<CT> bp[RT];                           // a row past the end is read as the last one and never stored
+#pragma unroll
+    for (int r = 0; r < RT; ++r) bp[r] = mf_row<CT>(cat + min(n0 + r * 16 + col, N - 1) * D, k);
+    float bq[3][JMAX][RT];
+    f32x4 st[5][MF_TILES];                       // st[s]: a finished subtree of 2^s chains waiting for its sibling
+#pragma unroll
+    for (int i = -2; i < 16; ++i) {
+      if (i + 2 < 16) {
+        const int t = mf_bitrev4(i + 2);
+#pragma unroll
+        for (int j = 0; j < JMAX; ++j)
+#pragma unroll
+          for (int r = 0; r < RT; ++r)
+            bq[(i + 2) % 3][j][r] = bp[r].at((FULL || 4 * w + 16 * t + 256 * j < D) ? 4 * w + 16 * t + 256 * j : 0);   // (a piece past D: unused)
+      }
+      if (i >= 0) {
+        const int c = w + 4 * mf_bitrev4(i);
+        f32x4 acc[MF_TILES];
+#pragma unroll
+        for (int x = 0; x < MF_TILES; ++x) acc[x] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < JMAX; ++j) {
+          if (FULL || 4 * c + 256 * j < D) {
+            const float* ap = us + (((c * J + j) * UT) << 6) + lane;
+#pragma unroll
+            for (int t = 0; t < UT; ++t) {
+              const float a = ap[t * 64];
+#pragma unroll
+              for (int r = 0; r < RT; ++r)
+                acc[t * RT + r] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bq[i % 3][j][r], acc[t * RT + r], 0, 0, 0);
+            }
+          }
+        }
+        const int lvl = mf_trailing_ones(i);
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+          if (s < lvl) {
+#pragma unroll
+            for (int x = 0; x < MF_TILES; ++x) acc[x] = st[s][x] + acc[x];
+          }
+#pragma unroll
+        for (int x = 0; x < MF_TILES; ++x) st[lvl][x] = acc[x];
+      }
+    }
+    __syncthreads();                             // the previous group's exchange has been read
+#pragma unroll
+    for (int x = 0; x < MF_TILES; ++x) ex[(w * MF_TILES + x) * 64 + lane] = st[4][x];
+    __syncthreads();
+    const f32x4 v = (ex[(0 * MF_TILES + w) * 64 + lane] + ex[(2 * MF_TILES + w) * 64 + lane]) +
+                    (ex[(1 * MF_TILES + w) * 64 + lane] + ex[(3 * MF_TILES + w) * 64 + lane]);
+    const int ut = w / RT;
+    const long n = n0 + (w % RT) * 16 + col;     // C/D layout: column = lane & 15 (row of the catalogue), row = 4 (lane >> 4) + reg (user)
+    if (n < N) {
+      const float ic = inv_c[n];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int u = ut * 16 + k * 4 + e;
+        if (u < nb) scores[(long)(b0 + u) * N + n] = v[e] * inv_u[b0 + u] * ic;
+      }
+    }
+  }
 }
 
 // The total order of the lists: score descending, index ascending.  An empty slot is (-inf, SEL_EMPTY): it follows every item.
@@ -342,8 +484,9 @@ extern "C" int ur_gather_rows(const void* src, int32_t src_kind, void* out, int3
   return 0;
 }
 
-// the scoring launch of both modes: rows [0,N) of `catalog` / `cat_inv_norm` into scores [B][N] (leading dimension N)
-static int launch_catalog_scores(const float* user, const float* user_inv_norm, const float* catalog, const float* cat_inv_norm,
+// the vector scoring launch of both modes: rows [0,N) of `catalog` / `cat_inv_norm` into scores [B][N] (leading dimension N)
+template <typename CT>
+static int launch_catalog_scores(const float* user, const float* user_inv_norm, const CT* catalog, const float* cat_inv_norm,
                                  float* scores, int32_t B, int64_t N, int32_t D, hipStream_t st) {
   const int ub = ur_cdiv(B, CU_USERS);
   long blocks_x = 2048 / ub;                                  // ~8 workgroups per CU in all
@@ -354,13 +497,49 @@ static int launch_catalog_scores(const float* user, const float* user_inv_norm, 
   const size_t smem = (size_t)CU_USERS * D * sizeof(float);
   static std::atomic<uint64_t> attr_set{0};   // per device
   UR_ONCE_PER_DEVICE(attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&catalog_scores_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CU_USERS * 2048 * 4);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&catalog_scores_kernel<CT>), hipFuncAttributeMaxDynamicSharedMemorySize, CU_USERS * 2048 * 4);
     if (e != hipSuccess) UR_FAIL((int)e, "ur_catalog_scores: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
   }
-  hipLaunchKernelGGL(catalog_scores_kernel, dim3((unsigned)blocks_x, (unsigned)ub), dim3(256), smem, st, user, user_inv_norm, catalog,
+  hipLaunchKernelGGL(catalog_scores_kernel<CT>, dim3((unsigned)blocks_x, (unsigned)ub), dim3(256), smem, st, user, user_inv_norm, catalog,
                      cat_inv_norm, scores, (int)B, (long)N, (int)D, (long)rpb);
   UR_CHECK_LAUNCH("ur_catalog_scores");
   return 0;
+}
+
+// the f32-MFMA scoring launch of the streaming mode: the same arguments, the same scores
+template <typename CT>
+static int launch_catalog_scores_mfma(const float* user, const float* user_inv_norm, const CT* catalog, const float* cat_inv_norm,
+                                      float* scores, int32_t B, int64_t N, int32_t D, hipStream_t st) {
+  const bool wide = D > 1024;
+  const int ub = ur_cdiv(B, wide ? 16 : 32);
+  const int group = wide ? 16 * MF_TILES : 16 * MF_TILES / 2;      // rows per step of a workgroup
+  long blocks_x = 1024 / ub;                                  // one workgroup per CU at a time (LDS): ~4 rounds
+  if (blocks_x < 1) blocks_x = 1;
+  long rpb = (N + blocks_x - 1) / blocks_x;
+  rpb = (rpb + group - 1) / group * group;
+  blocks_x = (N + rpb - 1) / rpb;
+  void (*kernel)(const float*, const float*, const CT*, const float*, float*, int, long, int, long, int) =
+      wide ? (D == 2048 ? catalog_scores_mfma_kernel<CT, true, true> : catalog_scores_mfma_kernel<CT, true, false>)
+           : (D == 1024 ? catalog_scores_mfma_kernel<CT, false, true> : catalog_scores_mfma_kernel<CT, false, false>);
+  static std::atomic<uint64_t> attr_set[4];   // per device, one per kernel
+  UR_ONCE_PER_DEVICE(attr_set[2 * wide + (D == 1024 || D == 2048)]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf_lds_bytes(2048, true));
+    if (e != hipSuccess) UR_FAIL((int)e, "ur_catalog_scores: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks_x * ub)), dim3(256), mf_lds_bytes(D, wide), st, user, user_inv_norm, catalog, cat_inv_norm,
+                     scores, (int)B, (long)N, (int)D, (long)rpb, ub);
+  UR_CHECK_LAUNCH("ur_catalog_scores");
+  return 0;
+}
+
+// which scorer the streaming mode runs when the caller leaves the choice to the library (select.scorer == 0).  Both give the same
+// bits, so this is a matter of time alone: docs/lab_notes.md section 22 has the measurements behind it.
+// Measured at D = 1024 only (the embedding width of this project): the MFMA scorer wins at every sampled (B, N) on an f32 catalogue
+// and at B = 64 and 512 on a bf16 one; at B = 8 on bf16 the two are within 2 %.  Other widths have not been timed and stay on the
+// vector scorer.
+static bool catalog_default_is_mfma(int32_t B, int64_t N, int32_t D, bool bf16) {
+  (void)N;
+  return D == 1024 && (B > CU_USERS || !bf16);
 }
 
 // rows per chunk of the streaming mode: the caller's figure, or a chunk buffer [B, rows] near 64 MB (so that it can stay in the
@@ -375,6 +554,38 @@ static int64_t catalog_chunk_rows(int64_t chunk_rows, int32_t B, int64_t N) {
   return r;
 }
 
+// the launches of the streaming mode, after every check
+template <typename CT>
+static int catalog_stream(const float* user, const CT* catalog, float* user_inv_norm, float* cat_inv_norm, int32_t cat_norm_ready, int32_t B,
+                          int64_t N, int32_t D, ur_catalog_select_t* select, int64_t chunk_bytes, int64_t rows, bool mfma, hipStream_t st) {
+  const int K = select->K, E = select->E;
+  float* chunk = (float*)select->workspace;
+  float* ref = (float*)((char*)select->workspace + chunk_bytes);
+  const long* gt = (const long*)select->gt_index;
+  hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, user_inv_norm, (long)B, (int)D);
+  if (!cat_norm_ready && N > 0)
+    hipLaunchKernelGGL(row_inv_norm_kernel<CT>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, cat_inv_norm, (long)N, (int)D);
+  if (gt && N > 0)
+    hipLaunchKernelGGL(catalog_gt_score_kernel<CT>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, (const float*)user_inv_norm, catalog,
+                       (const float*)cat_inv_norm, gt, ref, (int)B, (long)N, (int)D);
+  UR_CHECK_LAUNCH("ur_catalog_scores");
+  int64_t c0 = 0;
+  do {                                                         // (N == 0: one pass over an empty chunk writes the empty lists)
+    const int64_t len = N - c0 < rows ? N - c0 : rows;
+    if (len > 0) {
+      const int rc = mfma ? launch_catalog_scores_mfma<CT>(user, user_inv_norm, catalog + c0 * D, cat_inv_norm + c0, chunk, B, len, D, st)
+                          : launch_catalog_scores<CT>(user, user_inv_norm, catalog + c0 * D, cat_inv_norm + c0, chunk, B, len, D, st);
+      if (rc != 0) return rc;
+    }
+    hipLaunchKernelGGL(catalog_select_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0, (int)len, K,
+                       select->topk_score, select->topk_index, gt, (const float*)ref, select->rank, (const long*)select->exclude, E,
+                       (int)(c0 == 0));
+    UR_CHECK_LAUNCH("ur_catalog_scores");
+    c0 += rows;
+  } while (c0 < N);
+  return 0;
+}
+
 extern "C" int ur_catalog_scores(const float* user, const float* catalog, float* scores, float* user_inv_norm, float* cat_inv_norm,
                                  int32_t cat_norm_ready, int32_t B, int64_t N, int32_t D, ur_catalog_select_t* select, void* stream) {
   UR_REQUIRE(B >= 0 && N >= 0 && D > 0 && (D % 4) == 0 && D <= 2048, "ur_catalog_scores: need D %% 4 == 0 and D <= 2048 (got %d)", D);
@@ -383,10 +594,10 @@ extern "C" int ur_catalog_scores(const float* user, const float* catalog, float*
     if (B == 0 || N == 0) return 0;
     UR_REQUIRE(user && catalog && scores && user_inv_norm && cat_inv_norm, "ur_catalog_scores: null pointer");
     UR_REQUIRE(UR_ALIGNED16(user) && UR_ALIGNED16(catalog), "ur_catalog_scores: operands must be 16-byte aligned");
-    hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, user_inv_norm, (long)B, (int)D);
+    hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, user_inv_norm, (long)B, (int)D);
     if (!cat_norm_ready)
-      hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, cat_inv_norm, (long)N, (int)D);
-    return launch_catalog_scores(user, user_inv_norm, catalog, cat_inv_norm, scores, B, N, D, st);
+      hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, cat_inv_norm, (long)N, (int)D);
+    return launch_catalog_scores<float>(user, user_inv_norm, catalog, cat_inv_norm, scores, B, N, D, st);
   }
   // ---- streaming selection: every check before any launch ----
   const int K = select->K, E = select->E;
@@ -396,6 +607,10 @@ extern "C" int ur_catalog_scores(const float* user, const float* catalog, float*
              "ur_catalog_scores: select.chunk_rows must be 0 or a positive multiple of %d (got %lld)", SEL_TILE, (long long)select->chunk_rows);
   UR_REQUIRE(E >= 0 && (E == 0 || select->exclude), "ur_catalog_scores: select.E > 0 needs select.exclude");
   UR_REQUIRE((select->gt_index != nullptr) == (select->rank != nullptr), "ur_catalog_scores: select.gt_index and select.rank go together");
+  UR_REQUIRE(select->catalog_bf16 == 0 || select->catalog_bf16 == 1, "ur_catalog_scores: select.catalog_bf16 must be 0 or 1 (got %d)", select->catalog_bf16);
+  UR_REQUIRE(select->scorer >= 0 && select->scorer <= UR_CATALOG_SCORER_MFMA,
+             "ur_catalog_scores: select.scorer must be 0 (the library chooses), 1 (vector) or 2 (f32 MFMA) (got %d)", select->scorer);
+  const bool bf16 = select->catalog_bf16 == 1;
   const int64_t rows = catalog_chunk_rows(select->chunk_rows, B, N);
   const int64_t chunk_bytes = ((int64_t)B * rows * 4 + 15) / 16 * 16;
   const int64_t need = chunk_bytes + ((int64_t)B * 4 + 15) / 16 * 16;      // chunk [B][rows] f32 | ref [B] f32
@@ -409,30 +624,10 @@ extern "C" int ur_catalog_scores(const float* user, const float* catalog, float*
   UR_REQUIRE(select->topk_index && select->topk_score, "ur_catalog_scores: select.topk_index / topk_score are null");
   UR_REQUIRE(user && user_inv_norm && (N == 0 || (catalog && cat_inv_norm)), "ur_catalog_scores: null pointer");
   UR_REQUIRE(UR_ALIGNED16(user) && UR_ALIGNED16(catalog), "ur_catalog_scores: operands must be 16-byte aligned");
-  float* chunk = (float*)select->workspace;
-  float* ref = (float*)((char*)select->workspace + chunk_bytes);
-  const long* gt = (const long*)select->gt_index;
-  hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, user_inv_norm, (long)B, (int)D);
-  if (!cat_norm_ready && N > 0)
-    hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, cat_inv_norm, (long)N, (int)D);
-  if (gt && N > 0)
-    hipLaunchKernelGGL(catalog_gt_score_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, (const float*)user_inv_norm, catalog,
-                       (const float*)cat_inv_norm, gt, ref, (int)B, (long)N, (int)D);
-  UR_CHECK_LAUNCH("ur_catalog_scores");
-  int64_t c0 = 0;
-  do {                                                         // (N == 0: one pass over an empty chunk writes the empty lists)
-    const int64_t len = N - c0 < rows ? N - c0 : rows;
-    if (len > 0) {
-      const int rc = launch_catalog_scores(user, user_inv_norm, catalog + c0 * D, cat_inv_norm + c0, chunk, B, len, D, st);
-      if (rc != 0) return rc;
-    }
-    hipLaunchKernelGGL(catalog_select_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0, (int)len, K,
-                       select->topk_score, select->topk_index, gt, (const float*)ref, select->rank, (const long*)select->exclude, E,
-                       (int)(c0 == 0));
-    UR_CHECK_LAUNCH("ur_catalog_scores");
-    c0 += rows;
-  } while (c0 < N);
-  return 0;
+  const bool mfma = select->scorer == UR_CATALOG_SCORER_MFMA || (select->scorer == 0 && catalog_default_is_mfma(B, N, D, bf16));
+  if (bf16)
+    return catalog_stream(user, (const bf16_t*)catalog, user_inv_norm, cat_inv_norm, cat_norm_ready, B, N, D, select, chunk_bytes, rows, mfma, st);
+  return catalog_stream(user, catalog, user_inv_norm, cat_inv_norm, cat_norm_ready, B, N, D, select, chunk_bytes, rows, mfma, st);
 }
 
 extern "C" int ur_rank_of_index(const float* scores, const int64_t* gt_index, int32_t* rank, int32_t B, int64_t N, void* stream) {

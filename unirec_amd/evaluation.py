@@ -9,6 +9,7 @@
                                   ``ur_catalog_scores`` + ``ur_rank_of_index`` + ``ur_topk``; no host sync per user.
                                   ``retrieve`` is the catalogue-scale form: the scores are streamed in chunks through
                                   ``ur_catalog_scores``' select mode (top-K, rank and a per-user seen-item filter; no [B,N] tensor).
+                                  The catalogue may stay bf16 (``dtype=torch.bfloat16``): ``retrieve`` reads it as it is.
 Tie rule: the positive's rank is 1 + #{strictly greater}; top-K lists the lowest index first.
 """
 import numpy as np
@@ -142,12 +143,18 @@ def ranking_metrics(rank, ks):
 class CatalogEvaluator:
     """MRR / hit@K / top-K of user embeddings against the whole item catalogue (pool = all items)."""
 
-    def __init__(self, catalog, item_ids=None, device="cuda"):
-        self.catalog = torch.as_tensor(catalog).to(device, F32).contiguous()      # [N,D], stays in HBM
+    def __init__(self, catalog, item_ids=None, device="cuda", dtype=F32):
+        """dtype=torch.bfloat16 keeps the catalogue in bf16 (f32 input is rounded to nearest even; no f32 copy is kept or made):
+        retrieve() then gives what it gives on that catalogue's .float(), bit for bit; evaluate() / scores() need an f32 catalogue."""
+        if dtype not in (F32, torch.bfloat16):
+            raise ValueError(f"CatalogEvaluator: dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+        self.catalog = torch.as_tensor(catalog).to(device, dtype).contiguous()    # [N,D], stays in HBM
         self.item_ids = None if item_ids is None else [str(i) for i in item_ids]
         self._inv = None                                                          # catalogue 1/||c||, computed once
 
     def scores(self, user_embeddings):
+        if self.catalog.dtype != F32:
+            raise ValueError("CatalogEvaluator: scores() / evaluate() hold a [B,N] tensor and take an f32 catalogue; use retrieve() on a bf16 one")
         s, self._inv = hip.catalog_scores(user_embeddings.detach().to(self.catalog.device, F32).contiguous(), self.catalog, self._inv)
         return s
 
@@ -160,19 +167,21 @@ class CatalogEvaluator:
         return {"rank": rank, "mrr": float((1.0 / rank.to(torch.float64)).mean().item()),
                 "hit_at_k": float((rank <= k).to(torch.float64).mean().item()), "topk_index": idx, "topk_score": val}
 
-    def retrieve(self, user_embeddings, k=10, gt_index=None, exclude=None, ks=None, chunk_rows=None):
+    def retrieve(self, user_embeddings, k=10, gt_index=None, exclude=None, ks=None, chunk_rows=None, scorer=None):
         """Catalogue-scale retrieval: the scores are streamed in chunks and never held as [B,N].
         exclude: items each user has already seen (ragged lists or an int64 [B,E] tensor padded with -1, see pack_exclude); they leave
         the lists and the ranks, except a user's own gt_index.
         -> dict(topk_index int32 [B,k], topk_score f32 [B,k]); with gt_index also rank int32 [B], mrr, and hit_at / ndcg_at:
         dicts keyed by each K of ks (default (k,); any K, the metrics need only the rank).  Same scores, tie rule and rank rule as
-        evaluate()."""
+        evaluate().  scorer: None (the library's choice), "vector" or "mfma": which kernel scores the chunks; the results are the same bits."""
+        hip.catalog_scorer_id(scorer)
         u = user_embeddings.detach().to(self.catalog.device, F32).contiguous()
         ex = pack_exclude(exclude, u.shape[0])
         if ex is not None:
             ex = ex.to(u.device)
         gt = None if gt_index is None else torch.as_tensor(gt_index).to(u.device, torch.int64)
-        idx, val, rank, self._inv = hip.catalog_select(u, self.catalog, k, self._inv, gt_index=gt, exclude=ex, chunk_rows=chunk_rows)
+        idx, val, rank, self._inv = hip.catalog_select(u, self.catalog, k, self._inv, gt_index=gt, exclude=ex, chunk_rows=chunk_rows,
+                                                        scorer=scorer)
         out = {"topk_index": idx, "topk_score": val}
         if rank is not None:
             ks = (k,) if ks is None else tuple(int(x) for x in ks)

@@ -1053,22 +1053,38 @@ def catalog_scores(user, catalog, cat_inv_norm=None):
 CATALOG_TOPK_MAX = 128      # UR_CATALOG_TOPK_MAX
 
 
-def catalog_select(user, catalog, K, cat_inv_norm=None, gt_index=None, exclude=None, chunk_rows=None):
-    """Streaming retrieval over a shared catalogue [N,D] f32 (ur_catalog_scores with a ur_catalog_select_t): the K best items per user
-    of user [B,D] f32 under catalog_scores' own f32 scores, descending, lowest index first among equal scores; no [B,N] tensor exists.
+CATALOG_SCORERS = {None: 0, "vector": 1, "mfma": 2}      # ur_catalog_select_t.scorer (UR_CATALOG_SCORER_*)
+
+
+def catalog_scorer_id(scorer):
+    """None | "vector" | "mfma" -> the value of ur_catalog_select_t.scorer; anything else is a ValueError."""
+    if not (scorer is None or isinstance(scorer, str)) or scorer not in CATALOG_SCORERS:
+        raise ValueError(f"catalog scorer must be None, 'vector' or 'mfma', got {scorer!r}")
+    return CATALOG_SCORERS[scorer]
+
+
+def catalog_select(user, catalog, K, cat_inv_norm=None, gt_index=None, exclude=None, chunk_rows=None, scorer=None):
+    """Streaming retrieval over a shared catalogue [N,D] f32 or bf16 (ur_catalog_scores with a ur_catalog_select_t): the K best items per
+    user of user [B,D] f32 under catalog_scores' own f32 scores, descending, lowest index first among equal scores; no [B,N] tensor
+    exists.  A bf16 catalogue is widened exactly as it is read and gives what catalog.float() gives, bit for bit.
     gt_index int64 [B]: also the 1-based rank of that item (1 + the number of strictly greater scores).  exclude int64 [B,E], rows
     sorted ascending with negative entries as empty slots: those items are left out of the list and of the count, except the user's
     own gt_index.  chunk_rows: catalogue rows scored per chunk (a multiple of 1024; None = the library's choice).
+    scorer: the kernel that scores a chunk, "vector" or "mfma" (f32 matrix cores); both give the same bits, None = the library's choice.
     Returns (topk_index int32 [B,K], topk_score f32 [B,K], rank int32 [B] or None, cat_inv_norm); with fewer than K candidates the
     tail of a row is index -1, score -inf."""
+    scorer_id = catalog_scorer_id(scorer)
     lib = _lib.load()
     _need(user, F32, "user")
-    _need(catalog, F32, "catalog")
+    if catalog.dtype not in (F32, BF16):
+        raise ValueError(f"catalog_select: catalog must be f32 or bf16, got {catalog.dtype}")
+    _need(catalog, catalog.dtype, "catalog")
     B, D = user.shape
     N = catalog.shape[0]
     dev = user.device
     sel = CatalogSelect()
     sel.K, sel.chunk_rows = int(K), int(chunk_rows or 0)
+    sel.catalog_bf16, sel.scorer = int(catalog.dtype == BF16), scorer_id
     idx = torch.empty((B, max(int(K), 0)), dtype=torch.int32, device=dev)
     val = torch.empty((B, max(int(K), 0)), dtype=F32, device=dev)
     sel.topk_index, sel.topk_score = idx.data_ptr(), val.data_ptr()
