@@ -123,9 +123,8 @@ int ur_gemm_grouped(const ur_gemm_args* a, int32_t count, void* workspace, int64
 /* Launches with K-contiguous operands, bf16 output, M, N multiples of 256, K a multiple of 64 (>= 256), >= 128 output tiles and
  * a plain / bias / residual / masked-LoRA / SwiGLU-backward epilogue run on the persistent kernel (csrc/gemm_pers.hip: one
  * workgroup per CU walks its tiles, the LDS-DMA ring never drains, epilogue from registers) -- bit-identical to the generic
- * kernel.  ur_gemm_persistent_mode(0) keeps every launch on the generic kernel, (1) enables the persistent one (2 behaves as 1 in
- * the product library; round 5's wave-specialised lab kernel left the product build in round 6: tools/lab/gemm_ws.hip), (-1) returns
- * to the default (1); returns the previous setting.  Process-wide; for A/B timing and the bit-identity tests.  The library reads
+ * kernel.  ur_gemm_persistent_mode(0) keeps every launch on the generic kernel, (1) enables the persistent one (2 behaves as 1),
+ * (-1) returns to the default (1); returns the previous setting.  Process-wide; for A/B timing and the bit-identity tests.  The library reads
  * no environment variable. */
 int ur_gemm_persistent_mode(int mode);
 
@@ -330,16 +329,15 @@ int64_t ur_attn_bwd_kv_colsum_floats(const ur_attn_args* a);
  *   UR_ATTN_KERNEL_C128     the generated causal head_dim-128 kernels: Sq == Sk in [128, 4096], item ids and byte ranges in range; the
  *                           forward for Sk % 64 == 0, the backward pair (dq and dkv together, lse_log2 = 1: plane 1 of `delta` holds
  *                           -LSE * log2 e) for Sk % 128 == 0 without dropout
- *   UR_ATTN_KERNEL_GQ2      forward only, lab builds with UR_FWD_GQ2=1: attn_fwd_kernel<128, true, 8, GQ2> (causal head_dim 128, nq == 2 nkv)
  *   UR_ATTN_KERNEL_DKV2     dkv only: attn_bwd_dkv2_kernel, head_dim 128, > 64 keys, no dropout
  *   UR_ATTN_KERNEL_FEWQ     dkv only: attn_bwd_dkv_fewq_kernel, head_dim 64, non-causal, nq == nkv, <= 64 queries, >= 256 keys (the kernel
  *                           behind kv_colsum: ur_attn_bwd_kv_colsum_floats(a) > 0 exactly when dkv is FEWQ)
- * Priority: forward TINY, GQ2, C128, GENERIC; dQ TINY, C128, GENERIC; dK/dV TINY, FEWQ, C128, DKV2, GENERIC.
+ * Priority: forward TINY, C128, GENERIC; dQ TINY, C128, GENERIC; dK/dV TINY, FEWQ, C128, DKV2, GENERIC.
  * ur_attn_plan applies the size, stride and flag checks of the launch entry points (-1 and ur_last_error() on a refusal) but neither
  * requires, align-checks nor reads a data pointer; it reads the sizes, strides, head_dim, causal, dropout_p, g->lddo and whether
  * g->kv_colsum is set (refused unless dkv is FEWQ, as ur_attn_bwd does).  g == NULL asks about the forward only.  It launches nothing
  * and calls no HIP function: it answers on a machine without a GPU. */
-enum { UR_ATTN_KERNEL_NONE = 0, UR_ATTN_KERNEL_GENERIC = 1, UR_ATTN_KERNEL_TINY = 2, UR_ATTN_KERNEL_C128 = 3, UR_ATTN_KERNEL_GQ2 = 4,
+enum { UR_ATTN_KERNEL_NONE = 0, UR_ATTN_KERNEL_GENERIC = 1, UR_ATTN_KERNEL_TINY = 2, UR_ATTN_KERNEL_C128 = 3,      /* 4: unused (retired id) */
        UR_ATTN_KERNEL_DKV2 = 5, UR_ATTN_KERNEL_FEWQ = 6 };
 typedef struct {
   int32_t fwd, dq, dkv;      /* UR_ATTN_KERNEL_* */

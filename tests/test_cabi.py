@@ -32,6 +32,15 @@ def test_loader_binds_and_reports_version():
     assert isinstance(lib.ur_last_error(), bytes)
 
 
+def test_the_library_sources_read_no_environment_variable():
+    """include/unirec_hip.h: "The library reads no environment variable" -- however unirec_amd/csrc is built"""
+    csrc = os.path.join(ROOT, "unirec_amd", "csrc")
+    files = [os.path.join(d, f) for d, _, fs in os.walk(csrc) for f in fs]
+    assert len(files) > 10
+    hits = [os.path.relpath(f, ROOT) for f in files if b"getenv" in open(f, "rb").read()]
+    assert not hits, f"getenv in the library sources: {hits}"
+
+
 def test_invalid_arguments_are_rejected_without_a_gpu():
     """Argument validation happens on the host before any launch, so it is testable here."""
     lib = _lib.load()

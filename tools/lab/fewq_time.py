@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Lab: the few-query dK/dV kernel at the C3 cross-attention shape (B 512, 16 heads, 64 queries x 1600 keys, ragged masks, dropout 0.1):
-HIP-event time of ur_attn_bwd (dQ + dK/dV + column sums).  Used with the ablated libraries of tools/lab/lib_variant.sh attn ... -DUR_FEWQ_ABLATE=n."""
+HIP-event time of ur_attn_bwd (dQ + dK/dV + column sums)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

@@ -1,7 +1,7 @@
 #!/bin/bash
 # FETCH_SIZE / WRITE_SIZE of the seven projection launches of the step (separate --pmc passes) -> gpurun_out/<tag>/gemm_pmc.json
 # (--iters 0 ends kernel_bench with a division by zero AFTER the measured dispatches: its exit code is ignored)
-# usage: bash tools/lab/gemm_pmc.sh <tag>      (UR_GEMM_CW=0 in the environment: the plain tile order)
+# usage: bash tools/lab/gemm_pmc.sh <tag>
 export TMPDIR=/tmp
 OUT=gpurun_out/$1; mkdir -p $OUT
 rm -rf /tmp/pmc_f /tmp/pmc_w

@@ -26,7 +26,7 @@
 #include "common.hip.h"
 #include "unirec_hip.h"
 #ifndef UR_ATTN_FWD_C128_HDR
-#define UR_ATTN_FWD_C128_HDR "gen/attn_fwd_c128_asm.h"      // lab builds point this at an ablated variant (tools/lab/c128_variants.sh)
+#define UR_ATTN_FWD_C128_HDR "gen/attn_fwd_c128_asm.h"      // tools/lab/c128_variants.sh points the three at other outputs of tools/asmgen
 #endif
 #include UR_ATTN_FWD_C128_HDR
 #ifndef UR_ATTN_DQ_C128_HDR
@@ -44,17 +44,6 @@ constexpr float NEG_INF = -__builtin_huge_valf();
 constexpr float F32_MIN = -3.4028234663852886e38f;   // torch.finfo(torch.float32).min
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr int KT = 64;                                // keys (or queries, in dK/dV) staged per LDS tile
-#ifndef UR_FWD_PRIO
-#define UR_FWD_PRIO 1                                 // s_setprio(1) around the forward kernel's MFMA bursts (S chains, P V), 0 around the softmax: of the two waves of a
-                                                      // SIMD the one in its matrix segment issues first (1801 -> 1764 us dense causal B 64 S 2048; the same hint in
-                                                      // the dQ kernel is 1.5 % slower and is not applied there)
-#endif
-#ifndef UR_FWD_ABLATE
-#define UR_FWD_ABLATE 0                               // lab (tools/lab/dkv2_ablate.sh <tag> "<n...>" UR_FWD_ABLATE; results WRONG when != 0): 1 no max/exp2, 2 no LDS fragment reads, 3 no staging of the next tile, 4 no P V MFMAs, 5 = 3 + no barrier
-#endif
-#ifndef UR_ATTN_DEFER_MAX
-#define UR_ATTN_DEFER_MAX 1                           // lab: 0 = rescale O at every 32-key sub-tile
-#endif
 constexpr float DEFER_NAT = 6.0f * 0.6931471805599453f;   // defer the running-max update while it grows by < 2^6 (natural-log units)
 
 template <int HD> struct Cfg {
@@ -201,23 +190,6 @@ __device__ __forceinline__ void tr_frags(bf16x8 (&f)[Cfg<HD>::NDT], const char* 
     b[dt] = base + Cfg<HD>::off(row + 8, ch);
   }
   tr_read(f, a, b);
-}
-// split form of tr_frags: issue the 8 reads of one 4-fragment batch now, wait for them later (tr_landed<N>: at most N younger LDS
-// reads still outstanding); between the two the registers hold no data yet
-__device__ __forceinline__ void tr_issue4(bf16x4 (&lo)[4], bf16x4 (&hi)[4], const uint32_t (&a)[4], const uint32_t (&b)[4]) {
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8\n\tds_read_b64_tr_b16 %1, %9\n\t"
-      "ds_read_b64_tr_b16 %2, %10\n\tds_read_b64_tr_b16 %3, %11\n\t"
-      "ds_read_b64_tr_b16 %4, %12\n\tds_read_b64_tr_b16 %5, %13\n\t"
-      "ds_read_b64_tr_b16 %6, %14\n\tds_read_b64_tr_b16 %7, %15"
-      : "=&v"(lo[0]), "=&v"(hi[0]), "=&v"(lo[1]), "=&v"(hi[1]), "=&v"(lo[2]), "=&v"(hi[2]), "=&v"(lo[3]), "=&v"(hi[3])
-      : "v"(a[0]), "v"(b[0]), "v"(a[1]), "v"(b[1]), "v"(a[2]), "v"(b[2]), "v"(a[3]), "v"(b[3]));
-}
-template <int N>
-__device__ __forceinline__ void tr_landed(bf16x4 (&lo)[4], bf16x4 (&hi)[4]) {
-  asm volatile("s_waitcnt lgkmcnt(%8)"
-               : "+v"(lo[0]), "+v"(hi[0]), "+v"(lo[1]), "+v"(hi[1]), "+v"(lo[2]), "+v"(hi[2]), "+v"(lo[3]), "+v"(hi[3])
-               : "n"(N));
 }
 
 // head_dim 128 with the lane-constant part of the swizzled offsets hoisted out of the tile loop (LaneOff, 16 registers):
@@ -372,22 +344,16 @@ __device__ __forceinline__ float mask_score(float raw, float scale, bool valid, 
 }
 
 // ================================================================================================
-// GQ2 (lab, UR_FWD_GQ2=1): NW = 8 waves = the SAME 128 queries of the two query heads of one kv head (GQA 2:1): one staged K / V
-// tile serves both heads (half the LDS-DMA pieces per wave and tile, half the L2 -> LDS bytes per flop).  Measured: 1.82-1.84 ms
-// against 1.79-1.80 ms for the one-head workgroups (dense causal B 64 S 2048): the two waves of a SIMD now wait at the SAME
-// barrier, which costs more than the staging it saves.  Not the default.
 // (NW == 1: the few-query launches of the Q-Formers -- one wave per (sample, head), thousands of them, each a short latency-bound
 // chain: two waves per SIMD instead of the one that 276 registers allowed, and LDS for ONE K | V stage when Sk fits one tile)
-template <int HD, bool CAUSAL, int NW, bool GQ2 = false>
+template <int HD, bool CAUSAL, int NW>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1 ? 2 : 1))) void attn_fwd_kernel(AttnP p) {
-  constexpr int NWQ = GQ2 ? NW / 2 : NW;              // waves along the query axis
   using C = Cfg<HD>;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][K tile | V tile]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
-  const BlockMap bm = block_map<true>((p.Sq + 32 * NWQ - 1) / (32 * NWQ), GQ2 ? p.rep / 2 : p.rep, p.nkv, p.B);
-  const int wq = GQ2 ? wave % NWQ : wave;
-  const int hq = GQ2 ? bm.head * 2 + wave / NWQ : bm.head, b = bm.b, kvh = hq / p.rep;
-  const int qblk = bm.x * (32 * NWQ) + wq * 32;
+  const BlockMap bm = block_map<true>((p.Sq + 32 * NW - 1) / (32 * NW), p.rep, p.nkv, p.B);
+  const int hq = bm.head, b = bm.b, kvh = hq / p.rep;
+  const int qblk = bm.x * (32 * NW) + wave * 32;
   const int q = qblk + (lane & 31);
   const bool qok = q < p.Sq;
 
@@ -410,7 +376,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
   const float c2 = p.scale * LOG2E;
 
   int kend = p.Sk;
-  if (CAUSAL) kend = min(p.Sk, (bm.x + 1) * (32 * NWQ));
+  if (CAUSAL) kend = min(p.Sk, (bm.x + 1) * (32 * NW));
   int ntiles = (kend + KT - 1) / KT;
   const bf16_t* kb = p.k + (long)b * p.Sk * p.ldk + (long)kvh * HD;
   const bf16_t* vb = p.v + (long)b * p.Sk * p.ldv + (long)kvh * HD;
@@ -443,7 +409,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
     const char* ktile = smem + (t & 1) * 2 * C::TILE;
     const char* vtile = ktile + C::TILE;
     char* nk = smem + ((t + 1) & 1) * 2 * C::TILE;
-    if (t + 1 < ntiles && UR_FWD_ABLATE != 3 && UR_FWD_ABLATE != 5) {
+    if (t + 1 < ntiles) {
       ks.issue(nk, kb, p.ldk, k0 + KT, p.Sk, tid);
       vs.issue(nk + C::TILE, vb, p.ldv, k0 + KT, p.Sk, tid);
     }
@@ -455,22 +421,18 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
       const bool act0 = k0 < kend && !(CAUSAL && (k0 > qblk + 31 || (uint32_t)kbits.valid == 0u));
       const bool act1 = (k0 + 32) < kend && !(CAUSAL && (k0 + 32 > qblk + 31 || (uint32_t)(kbits.valid >> 32) == 0u));
       f32x16 sA = zero16(), sB = zero16();
-#if UR_FWD_PRIO
       __builtin_amdgcn_s_setprio(1);
-#endif
       if (act0) {
 #pragma unroll
         for (int st = 0; st < C::NS; ++st)
-          sA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(UR_FWD_ABLATE == 2 ? qf[(st + 1) % C::NS] : kfrag(ktile, std::integral_constant<int, 0>{}, st), qf[st], sA, 0, 0, 0);
+          sA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag(ktile, std::integral_constant<int, 0>{}, st), qf[st], sA, 0, 0, 0);
       }
       if (act1) {
 #pragma unroll
         for (int st = 0; st < C::NS; ++st)
-          sB = __builtin_amdgcn_mfma_f32_32x32x16_bf16(UR_FWD_ABLATE == 2 ? qf[(st + 2) % C::NS] : kfrag(ktile, std::integral_constant<int, 32>{}, st), qf[st], sB, 0, 0, 0);
+          sB = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag(ktile, std::integral_constant<int, 32>{}, st), qf[st], sB, 0, 0, 0);
       }
-#if UR_FWD_PRIO
       __builtin_amdgcn_s_setprio(0);
-#endif
       auto soft_pv = [&](const int sub, f32x16& s) {
         const int kbase = k0 + 32 * sub;
         const uint32_t v32 = (uint32_t)(kbits.valid >> (32 * sub)), i32 = (uint32_t)(kbits.inr >> (32 * sub));
@@ -487,12 +449,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[r] = ((r & 3) + 8 * (r >> 2) <= dqk) ? s[r] : NEG_INF;
           }
-#if UR_FWD_ABLATE == 1
-          mx = s[0];
-#else
 #pragma unroll
           for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[r]);
-#endif
           mx *= p.scale;
         } else {
           const uint32_t vh = opaque(v32 >> (4 * h)), ih = opaque(i32 >> (4 * h));
@@ -507,7 +465,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         // branch-free rescale (alpha == 1 exactly when the max did not move): keeps the O accumulators
         // in place across the loop (a conditional rescale made hipcc copy all 64 registers per sub-tile)
-#if UR_ATTN_DEFER_MAX
         // deferred running maximum: O and l are rescaled only when some row's maximum grew by more than 2^DEFER_LOG2
         // (wave-uniform branch); until then p = exp2(c*s - m_old) may exceed 1 by at most that factor, which f32 sums
         // and the bf16 P fragments carry at unchanged relative precision.  m = -inf (first tile) always takes the branch.
@@ -522,29 +479,12 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
             for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
           m = mnew;
         }
-#else
-        {
-          const float mnew = fmaxf(m, mx);
-          const float mu = (mnew == NEG_INF) ? 0.f : mnew;
-          const float alpha = fast_exp2((m - mu) * LOG2E);
-          l *= alpha;
-#pragma unroll
-          for (int dt = 0; dt < C::NDT; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-          m = mnew;
-        }
-#endif
         const float muse = (m == NEG_INF) ? 0.f : m;
         const float mc = muse * LOG2E;
         float rs = 0.f;
         if (fast) {
 #pragma unroll
-#if UR_FWD_ABLATE == 1
-          for (int r = 0; r < 16; ++r) { rs += s[r]; }
-#else
           for (int r = 0; r < 16; ++r) { s[r] = fast_exp2(fmaf(s[r], c2, -mc)); rs += s[r]; }
-#endif
         } else {
 #pragma unroll
           for (int r = 0; r < 16; ++r) { s[r] = fast_exp2((s[r] - muse) * LOG2E); rs += s[r]; }
@@ -564,46 +504,31 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 1
         }
         rs += __shfl_xor(rs, 32, 64);
         l += rs;
-#if UR_FWD_PRIO
         __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
           const bf16x8 pf = acc_frag(s, s2);
           bf16x8 vt[C::NDT];
-          if constexpr (UR_FWD_ABLATE == 2) {
-#pragma unroll
-            for (int dt = 0; dt < C::NDT; ++dt) vt[dt] = qf[dt];
-          } else if constexpr (HD == 128) {
+          if constexpr (HD == 128) {
             if (sub == 0) { if (s2 == 0) tr_frags_h<0>(vt, vtile, lo); else tr_frags_h<16>(vt, vtile, lo); }
             else { if (s2 == 0) tr_frags_h<32>(vt, vtile, lo); else tr_frags_h<48>(vt, vtile, lo); }
           } else {
             tr_frags<HD>(vt, vtile, 32 * sub + 16 * s2, lane);
           }
 #pragma unroll
-#if UR_FWD_ABLATE == 4
-          for (int dt = 0; dt < C::NDT; ++dt) o[dt][s2] += (float)(vt[dt][0] ^ pf[dt & 7]);
-#else
           for (int dt = 0; dt < C::NDT; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vt[dt], pf, o[dt], 0, 0, 0);
-#endif
         }
       };
       if (act0) soft_pv(0, sA);
-#if UR_FWD_PRIO
       __builtin_amdgcn_s_setprio(0);
-#endif
       if (act1) soft_pv(1, sB);
-#if UR_FWD_PRIO
       __builtin_amdgcn_s_setprio(0);
-#endif
     }
-    if (t + 1 < ntiles && UR_FWD_ABLATE != 3 && UR_FWD_ABLATE != 5) {
+    if (t + 1 < ntiles) {
       ks.commit(nk, tid);
       vs.commit(nk + C::TILE, tid);
     }
-#if UR_FWD_ABLATE != 5
     __syncthreads();
-#endif
   }
   {
     const float inv = l > 0.f ? 1.0f / l : 0.f;
@@ -1183,14 +1108,6 @@ __device__ __forceinline__ float lanes_transpose_sum32(const float (&v)[32], int
   return (b0 ? d[1] : d[0]) + dppx_f32<0xB1>(b0 ? d[0] : d[1]);                                              // quad_perm [1, 0, 3, 2]
 }
 
-#ifndef UR_FEWQ_PREFETCH
-#define UR_FEWQ_PREFETCH 0      // lab: 2 = the next live key block's K / V fragments are requested in the MIDDLE of the current block, into the registers the
-                                // last S / dP product has just released -- hipcc keeps both sets live instead (256 VGPRs + 96 B of scratch): 2.28 -> 2.83 ms
-                                // for dQ + dK/dV of a C3 layer; round 3's whole-block register prefetch likewise (256 VGPRs + 5 spills, 3 % slower).  0 = at the top
-#endif
-#ifndef UR_FEWQ_ABLATE
-#define UR_FEWQ_ABLATE 0        // lab builds only (WRONG results): 1 = no dK / dV stores, 2 = no K / V loads (zero fragments)
-#endif
 #ifndef UR_FEWQ_WAVES
 #define UR_FEWQ_WAVES 2         // lab: waves per SIMD the kernel is compiled for
 #endif
@@ -1258,13 +1175,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UR_FEWQ_WAV
     const long krow = kok ? key : 0;
 #pragma unroll
     for (int st = 0; st < C::NS; ++st) {
-#if UR_FEWQ_ABLATE == 2
-      kf[st] = g_frag(kbase + krow * p.ldk, st, lane, false);
-      vf[st] = g_frag(vbase + krow * p.ldv, st, lane, false);
-#else
       kf[st] = g_frag(kbase + krow * p.ldk, st, lane, kok);
       vf[st] = g_frag(vbase + krow * p.ldv, st, lane, kok);
-#endif
     }
     uint32_t m = 1;
     if (kok && kmrow) m = kmrow[key];
@@ -1276,9 +1188,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UR_FEWQ_WAV
   float csk = 0.f, csv = 0.f;          // this lane's feature of the dK / dV column sums over the wave's key blocks
   int blk = chunk * bpc + wave;
   bool have = false;                   // kf / vf / state already hold block `blk` (requested in the middle of the previous block)
-#if UR_FEWQ_PREFETCH == 2
-  const int last_sub = p.Sq > 32 ? 1 : 0;
-#endif
   for (; blk < blk_hi; blk += 4) {
     if (sample_has_key && live[blk] == 0) {
       // a key block without one valid key while the sample has some: every probability is exactly 0 -> dK = dV = 0, nothing is read
@@ -1309,15 +1218,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UR_FEWQ_WAV
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<HD>(qtile, 32 * sub, st, lane), kf[st], s, 0, 0, 0);
         dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<HD>(dotile, 32 * sub, st, lane), vf[st], dp, 0, 0, 0);
       }
-#if UR_FEWQ_PREFETCH == 2
-      if (sub == last_sub) {
-        // the K / V fragments have had their last use: the wave's NEXT live block is requested into the same registers here and lands
-        // under this block's softmax, dV / dK products and stores (the kernel is bound by this per-block chain, not by bytes)
-        const int nb = blk + 4;
-        have = nb < blk_hi && !(sample_has_key && live[nb] == 0);
-        if (have) load_kv(nb, kf, vf, state);
-      }
-#endif
       const bool fast = all_valid && !dropping && (qbase + 32 <= p.Sq);
       if (fast) {
 #pragma unroll
@@ -1395,12 +1295,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UR_FEWQ_WAV
       csv += lanes_transpose_sum32(t, lane);
     }
     const long ktok = (long)b * p.Sk + (kok ? key : 0);
-#if UR_FEWQ_ABLATE == 1          // lab (timing only, results wrong): no dK / dV stores
-    asm volatile("" :: "v"(dk[0][0]), "v"(dv[0][0]), "v"(dk[1][15]), "v"(dv[1][15]));
-#else
     store_T<HD>(p.dk + ktok * p.lddk + (long)hq * HD, dk, p.scale, lane, kok);     // dS was kept unscaled
     store_T<HD>(p.dv + ktok * p.lddv + (long)hq * HD, dv, 1.0f, lane, kok);
-#endif
   }
   if (p.colsum_part != nullptr) {
     // the four waves' sums -> one partial per (batch, head): [b][dK | dV][head][feature] (the launcher gives such calls ONE workgroup per pair)
@@ -1446,14 +1342,9 @@ __global__ __launch_bounds__(256) void kv_colsum_reduce_kernel(const float* __re
 //     dP chains: P = exp2(c * S'), dS = P * dP' -- three vector instructions per element, no row constants
 //     held in registers;
 //   * lane-constant LDS offsets (row fragments, transposed fragments) are computed once per workgroup;
-//   * four hard-fenced phases per 64-query tile: [S,dP](a) | [S,dP](b) + softmax(a) | [dV,dK](a) + softmax(b)
-//     | [dV,dK](b): every phase pairs 16 MFMAs with independent vector work of the other half.
+//   * three counted streams per 64-query tile: [S,dP](a) | [S,dP](b) + softmax(a) | [dV,dK](a, b) + softmax(b): every
+//     MFMA gap carries independent vector work of the other half.
 // LDS per buffer: Q tile | dO tile | ns[64] | nd[64] | (m, 1/l)[64] (general path only).
-// Split transposed reads for the one-wave-per-SIMD dK/dV kernel: tr_issue4 starts the 8 reads of one batch
-// (4 fragments), tr_landed<N> waits until at most N younger LDS reads are outstanding and ties the batch's
-// registers to that wait.  Between the two the registers hold no data yet: this is only sound while the
-// allocator leaves them alone (it parked them in AGPRs at 426 registers; at <= 380 it does not -- the kernel's
-// parity tests in tests/test_gpu_attention.py are what catches a build where it does).
 
 // ---- hand-ordered LDS streams of the dK/dV fast path (one wave per SIMD: nobody else hides an LDS latency, so every read
 // is issued up to 14 LDS operations ahead of its use and every use waits with a COUNTED lgkmcnt for exactly its own data;
@@ -1511,14 +1402,8 @@ __device__ __forceinline__ void mfma_acc(f32x16& acc, const bf16x8& a, const bf1
   asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
 }
 
-#ifndef UR_DKV2_REGSTAGE
-#define UR_DKV2_REGSTAGE 0   // 1 (lab): register-staged next tile instead of LDS-DMA pieces -- 33 more live registers: 144 B of scratch, kernel 2x slower
-#endif
-#ifndef UR_DKV2_V2
-#define UR_DKV2_V2 1         // 0 (lab): the four hard-fenced phases of round 1 instead of the three counted streams
-#endif
 #ifndef UR_DKV2_STAMPS
-#define UR_DKV2_STAMPS 0     // lab builds only: lane 0 of wave 0 of the first 256 workgroups logs the cycle counter at 8 points of tiles 4..11 (ur_lab_attn_stamps)
+#define UR_DKV2_STAMPS 0     // lab builds only: lane 0 of wave 0 of the first 256 workgroups logs the cycle counter at points 0, 2, 6, 7 (1: the wall clock) of tiles 4..11 (ur_lab_attn_stamps)
 #endif
 #if UR_DKV2_STAMPS
 __device__ long long g_attn_stamps[256 * 8 * 8];
@@ -1529,9 +1414,6 @@ __device__ long long g_attn_stamps[256 * 8 * 8];
 #define UR_ASTAMP(k) do { if (UR_STAMP_ON) g_attn_stamps[((blockIdx.x - UR_STAMP_BLK0) * 8 + (it - 4)) * 8 + (k)] = (long long)__builtin_readcyclecounter(); } while (0)
 #else
 #define UR_ASTAMP(k) do { } while (0)
-#endif
-#ifndef UR_DKV2_ABLATE
-#define UR_DKV2_ABLATE 0     // lab (tools/lab/dkv2_ablate.sh; timing only, results wrong): 1 no tile reload, 2 no softmax, 3 no dV/dK phases, 4 no S/dP phases, 5 diagonal tiles on the fast path; three-stream path: 6 no MFMAs, 7 no LDS reads, 8 no fillers, 9 no LDS-DMA
 #endif
 template <bool CAUSAL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void attn_bwd_dkv2_kernel(AttnP p) {
@@ -1651,8 +1533,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // load that follows an LDS-DMA (it cannot tell the two buffers apart), which would expose the whole DMA
     // latency on every tile.  Phases 3-4 only read LDS through the inline-asm transposed reads.
     const int q0 = qstart + tq_c * KT;
-    bool tile_fast = all_valid && (q0 + KT <= p.Sq) && (!CAUSAL || q0 >= kblk + 31 || UR_DKV2_ABLATE == 5);
-#if UR_DKV2_V2
     // the fast path issues the next tile's LDS-DMA itself, as whole-row pieces: the next tile must be full too.  Tiles on
     // the causal diagonal take the same three streams with the mask applied to P (two more vector instructions per
     // element) instead of the general path (position compares, row constants from LDS: ~2x a fast tile)
@@ -1660,13 +1540,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // the tile whose DMA this iteration issues (none left: this tile again, into the idle buffer)
     if (it + AH < ntot) tile_ptrs2(hr_n, tq_n, nqb, ndob, nsb, nq0); else tile_ptrs2(hr_c, tq_c, nqb, ndob, nsb, nq0);
     const bool tile_diag = CAUSAL && q0 < kblk + 31;
-    tile_fast = all_valid && (q0 + KT <= p.Sq) && (nq0 + KT <= p.Sq);
-#endif
+    const bool tile_fast = all_valid && (q0 + KT <= p.Sq) && (nq0 + KT <= p.Sq);
     UR_ASTAMP(0);
 #if UR_DKV2_STAMPS
     if (UR_STAMP_ON) g_attn_stamps[((blockIdx.x - UR_STAMP_BLK0) * 8 + (it - 4)) * 8 + 1] = (long long)wall_clock64();   // 100 MHz constant clock
 #endif
-#if UR_DKV2_V2
     if (kblk < p.Sk && tile_fast) {
      auto fast_body = [&](auto DIAG_) {
       constexpr bool DIAG = decltype(DIAG_)::value;
@@ -1697,30 +1575,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       const char* dorow = reinterpret_cast<const char*>(ndob + (long)nq0 * p.lddo) + dos.voff;
       const long qstep = 32L * p.ldq, dostep = 32L * p.lddo;           // bytes per 16 rows
       char* nbw = nbuf + wave_u * 1024;
-#if UR_DKV2_REGSTAGE
-      // register-staged next tile: 8 global_load_dwordx4 + 1 dword per lane issued in stream 1's gaps (a few cycles of issue
-      // each, against ~60 for an LDS-DMA piece), written to LDS behind stream 3.  Same lane <-> (row, chunk) map as the DMA:
-      // the swizzle sits on the source address, the LDS side is linear.
-      uint4 stg[8]; float stc = 0.f;
-      auto dma_piece = [&](auto J) {
-        constexpr int j = decltype(J)::value;
-        if constexpr (j < 4) stg[j] = *reinterpret_cast<const uint4*>(qrow + j * qstep);
-        else if constexpr (j < 8) stg[j] = *reinterpret_cast<const uint4*>(dorow + (j - 4) * dostep);
-        else {
-          const float* cb = wave_u == 0 ? p.delta + nrows + nsb + nq0 : (wave_u == 1 ? p.delta + nsb + nq0 : p.stats + (nsb + nq0 + 32 * (wave_u & 1)) * 2);
-          stc = cb[lane];
-        }
-      };
-      auto stage_commit = [&]() {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          *reinterpret_cast<uint4*>(nbw + j * 4096 + lane * 16) = stg[j];
-          *reinterpret_cast<uint4*>(nbw + C::TILE + j * 4096 + lane * 16) = stg[4 + j];
-        }
-        *reinterpret_cast<float*>(nbuf + 2 * C::TILE + 256 * wave_u + lane * 4) = stc;
-      };
-#else
-      auto stage_commit = [&]() {};
       auto dma_piece = [&](auto J) {
         constexpr int j = decltype(J)::value;
         if constexpr (j < 4) {
@@ -1732,7 +1586,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           __builtin_amdgcn_global_load_lds((gbl_void*)(cb + lane), (lds_void*)(nbuf + 2 * C::TILE + 256 * wave_u), 4, 0, 0);
         }
       };
-#endif
       // ---- streams 1 + 2: S', dP' of the two 32-query halves = 16 k-steps of {2 row fragments, 2 MFMAs}, fragments
       //      issued RD k-steps ahead; softmax of half a rides under half b's MFMAs
       constexpr int RD = 6;
@@ -1742,12 +1595,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       for (int st = 0; st < C::NS; ++st) ra[st] = bufb + rfo[st];
       auto rissue = [&](auto K) {
         constexpr int k = decltype(K)::value;
-        if (UR_DKV2_ABLATE != 7 && UR_DKV2_ABLATE != 10) rf_issue<8192 * (k >> 3), C::TILE + 8192 * (k >> 3)>(qa[k % (RD + 1)], da[k % (RD + 1)], ra[k & 7]);
-      };
-      auto soft1 = [&](f32x16& sv, f32x16& dpv, int r) {
-        const float pr = fast_exp2(sv[r] * c2);
-        sv[r] = pr;
-        dpv[r] = pr * dpv[r];
+        rf_issue<8192 * (k >> 3), C::TILE + 8192 * (k >> 3)>(qa[k % (RD + 1)], da[k % (RD + 1)], ra[k & 7]);
       };
       static_for<0, RD>([&](auto K) { rissue(K); });
       bf16x8 p0a, d0a, p1a, d1a, p0b, d0b, p1b, d1b;
@@ -1755,28 +1603,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         constexpr int k = decltype(K)::value;
         if constexpr (k + RD < 16) rissue(std::integral_constant<int, k + RD>{});
         constexpr int younger = (k + RD < 16) ? RD : (15 - k);
-        if (UR_DKV2_ABLATE != 7 && UR_DKV2_ABLATE != 10) rf_landed<2 * younger>(qa[k % (RD + 1)], da[k % (RD + 1)]);
-        if constexpr (UR_DKV2_ABLATE == 6) {
-          if constexpr (k < 8) { dma_piece(std::integral_constant<int, k>{}); if constexpr (k == 7) dma_piece(std::integral_constant<int, 8>{}); }
-          else { soft1(sa, dpa, 2 * (k - 8)); soft1(sa, dpa, 2 * (k - 8) + 1); if constexpr (k == 12) { p0a = acc_frag(sa, 0); d0a = acc_frag(dpa, 0); } }
-        } else if constexpr (k < 8) {
+        rf_landed<2 * younger>(qa[k % (RD + 1)], da[k % (RD + 1)]);
+        if constexpr (k < 8) {
           sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa[k % (RD + 1)], kf[k & 7], sa, 0, 0, 0);
           dpa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da[k % (RD + 1)], vf[k & 7], dpa, 0, 0, 0);
           pin(sa, dpa);
-          if constexpr (UR_DKV2_ABLATE != 9) { dma_piece(std::integral_constant<int, k>{}); if constexpr (k == 7) dma_piece(std::integral_constant<int, 8>{}); }
+          dma_piece(std::integral_constant<int, k>{});
+          if constexpr (k == 7) dma_piece(std::integral_constant<int, 8>{});
         } else {
           sb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa[k % (RD + 1)], kf[k & 7], sb, 0, 0, 0);
           dpb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da[k % (RD + 1)], vf[k & 7], dpb, 0, 0, 0);
           pin(sb, dpb);
-          if constexpr (UR_DKV2_ABLATE != 8 && UR_DKV2_ABLATE != 10) {      // softmax of half a, staged: scale (k) | exp2 (k+1) | dS (k+2)
-            constexpr int e = 2 * (k - 8);
-            sa[e] = mul1(sa[e], c2v); sa[e + 1] = mul1(sa[e + 1], c2v);
-            if constexpr (k >= 9) {
-              sa[e - 2] = fast_exp2(sa[e - 2]); sa[e - 1] = fast_exp2(sa[e - 1]);
-              if constexpr (DIAG) { sa[e - 2] = cmask(sa[e - 2], e - 2, 0); sa[e - 1] = cmask(sa[e - 1], e - 1, 0); }
-            }
-            if constexpr (k >= 10) { dpa[e - 4] = mul1(sa[e - 4], dpa[e - 4]); dpa[e - 3] = mul1(sa[e - 3], dpa[e - 3]); }
+          constexpr int e = 2 * (k - 8);      // softmax of half a, staged: scale (k) | exp2 (k+1) | dS (k+2)
+          sa[e] = mul1(sa[e], c2v); sa[e + 1] = mul1(sa[e + 1], c2v);
+          if constexpr (k >= 9) {
+            sa[e - 2] = fast_exp2(sa[e - 2]); sa[e - 1] = fast_exp2(sa[e - 1]);
+            if constexpr (DIAG) { sa[e - 2] = cmask(sa[e - 2], e - 2, 0); sa[e - 1] = cmask(sa[e - 1], e - 1, 0); }
           }
+          if constexpr (k >= 10) { dpa[e - 4] = mul1(sa[e - 4], dpa[e - 4]); dpa[e - 3] = mul1(sa[e - 3], dpa[e - 3]); }
           if constexpr (k == 14) { p0a = acc_frag(sa, 0); d0a = acc_frag(dpa, 0); pin(p0a); pin(d0a); }       // elements 0..7 are complete after k = 13
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -1793,7 +1637,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         constexpr int u = decltype(U)::value;
         constexpr int bt = u >> 2, dt = u & 3;
         constexpr int off = ((bt & 1) ? 0 : C::TILE) + 256 * (16 * (bt >> 1));      // even batches: dO tile, odd: Q tile; 16 query rows per pair
-        if (UR_DKV2_ABLATE != 7 && UR_DKV2_ABLATE != 10) tr_issue1<off>(tl[u % (RT + 1)], th[u % (RT + 1)], ta[dt], tb[dt]);
+        tr_issue1<off>(tl[u % (RT + 1)], th[u % (RT + 1)], ta[dt], tb[dt]);
       };
       static_for<0, RT>([&](auto U) { tissue(U); });
       // Per unit: wait for its own fragment (6 younger units stay in flight) | MFMA | issue unit u + RT | vector fillers.
@@ -1806,39 +1650,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         constexpr int u = decltype(U)::value;
         constexpr int bt = u >> 2, dt = u & 3;
         constexpr int younger = (31 - u < RT - 1) ? (31 - u) : (RT - 1);
-        if (UR_DKV2_ABLATE != 7 && UR_DKV2_ABLATE != 10) tr_landed1<2 * younger>(tl[u % (RT + 1)], th[u % (RT + 1)]);
+        tr_landed1<2 * younger>(tl[u % (RT + 1)], th[u % (RT + 1)]);
         const bf16x8 af = cat4(tl[u % (RT + 1)], th[u % (RT + 1)]);
-        if constexpr (UR_DKV2_ABLATE == 6) { sb[u & 15] += __builtin_bit_cast(float, (int)af[0] | ((int)af[4] << 16)); }
-        else {
-          auto mm = [&](f32x16& acc, const bf16x8& bfrag) {
-            if constexpr (dt == 0) mfma_acc_nop(acc, af, bfrag); else mfma_acc(acc, af, bfrag);     // first read of a fragment
-          };
-          if constexpr (bt == 0) mm(dv[dt], p0a);
-          else if constexpr (bt == 1) mm(dk[dt], d0a);
-          else if constexpr (bt == 2) mm(dv[dt], p1a);
-          else if constexpr (bt == 3) mm(dk[dt], d1a);
-          else if constexpr (bt == 4) mm(dv[dt], p0b);
-          else if constexpr (bt == 5) mm(dk[dt], d0b);
-          else if constexpr (bt == 6) mm(dv[dt], p1b);
-          else mm(dk[dt], d1b);
-        }
+        auto mm = [&](f32x16& acc, const bf16x8& bfrag) {
+          if constexpr (dt == 0) mfma_acc_nop(acc, af, bfrag); else mfma_acc(acc, af, bfrag);     // first read of a fragment
+        };
+        if constexpr (bt == 0) mm(dv[dt], p0a);
+        else if constexpr (bt == 1) mm(dk[dt], d0a);
+        else if constexpr (bt == 2) mm(dv[dt], p1a);
+        else if constexpr (bt == 3) mm(dk[dt], d1a);
+        else if constexpr (bt == 4) mm(dv[dt], p0b);
+        else if constexpr (bt == 5) mm(dk[dt], d0b);
+        else if constexpr (bt == 6) mm(dv[dt], p1b);
+        else mm(dk[dt], d1b);
         if constexpr (u + RT < 32) tissue(std::integral_constant<int, u + RT>{});
-        if constexpr (UR_DKV2_ABLATE != 8 && UR_DKV2_ABLATE != 10) {
-          // tail of half a (its elements 12..15), then half b
-          if constexpr (u == 0) {
-            sa[14] = fast_exp2(sa[14]); sa[15] = fast_exp2(sa[15]);
-            if constexpr (DIAG) { sa[14] = cmask(sa[14], 14, 0); sa[15] = cmask(sa[15], 15, 0); }
-          }
-          if constexpr (u == 1) { dpa[12] = mul1(sa[12], dpa[12]); dpa[13] = mul1(sa[13], dpa[13]); }
-          if constexpr (u == 2) { dpa[14] = mul1(sa[14], dpa[14]); dpa[15] = mul1(sa[15], dpa[15]); }
-          constexpr int sh = 3;                                         // half b starts in unit 3
-          if constexpr (u >= sh && u < sh + 16) sb[u - sh] = mul1(sb[u - sh], c2v);
-          if constexpr (u >= sh + 1 && u < sh + 17) {
-            sb[u - sh - 1] = fast_exp2(sb[u - sh - 1]);
-            if constexpr (DIAG) sb[u - sh - 1] = cmask(sb[u - sh - 1], u - sh - 1, 1);
-          }
-          if constexpr (u >= sh + 2 && u < sh + 18) dpb[u - sh - 2] = mul1(sb[u - sh - 2], dpb[u - sh - 2]);
+        // tail of half a (its elements 12..15), then half b
+        if constexpr (u == 0) {
+          sa[14] = fast_exp2(sa[14]); sa[15] = fast_exp2(sa[15]);
+          if constexpr (DIAG) { sa[14] = cmask(sa[14], 14, 0); sa[15] = cmask(sa[15], 15, 0); }
         }
+        if constexpr (u == 1) { dpa[12] = mul1(sa[12], dpa[12]); dpa[13] = mul1(sa[13], dpa[13]); }
+        if constexpr (u == 2) { dpa[14] = mul1(sa[14], dpa[14]); dpa[15] = mul1(sa[15], dpa[15]); }
+        constexpr int sh = 3;                                         // half b starts in unit 3
+        if constexpr (u >= sh && u < sh + 16) sb[u - sh] = mul1(sb[u - sh], c2v);
+        if constexpr (u >= sh + 1 && u < sh + 17) {
+          sb[u - sh - 1] = fast_exp2(sb[u - sh - 1]);
+          if constexpr (DIAG) sb[u - sh - 1] = cmask(sb[u - sh - 1], u - sh - 1, 1);
+        }
+        if constexpr (u >= sh + 2 && u < sh + 18) dpb[u - sh - 2] = mul1(sb[u - sh - 2], dpb[u - sh - 2]);
         if constexpr (u == 3) { p1a = acc_frag(sa, 1); pin(p1a); }
         if constexpr (u == 4) { d1a = acc_frag(dpa, 1); pin(d1a); }
         if constexpr (u == 13) { p0b = acc_frag(sb, 0); pin(p0b); }                  // elements 0..7 of half b are complete after unit 12
@@ -1847,118 +1686,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if constexpr (u == 22) { d1b = acc_frag(dpb, 1); pin(d1b); }
         __builtin_amdgcn_sched_barrier(0);
       });
-      stage_commit();
       UR_ASTAMP(6);
      };
      if (tile_diag) fast_body(std::true_type{}); else fast_body(std::false_type{});
-    } else
-#else
-    if (kblk < p.Sk && tile_fast) {
-      const uint32_t qbase = lds_off(qtile), dobase = lds_off(dotile);
-      // initial accumulators: rows 8g + 4h + 0..3 of the 32-row half -> registers 4g .. 4g+3
-      auto init16 = [&](f32x16& a, const float* src) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float4 v = *reinterpret_cast<const float4*>(src + 8 * g + 4 * h);
-          a[4 * g] = v.x; a[4 * g + 1] = v.y; a[4 * g + 2] = v.z; a[4 * g + 3] = v.w;
-        }
-      };
-      // S' and dP' of one 32-query half: row fragments are read two k-steps ahead of the MFMAs that use them
-      // (one wave per SIMD: nobody else hides the LDS latency), fenced per k-step so the order stays as written
-      auto s_dp = [&](f32x16& sv, f32x16& dpv, int half) {
-        init16(sv, fst + 32 * half);
-        init16(dpv, fst + 64 + 32 * half);
-        bf16x8 qa[3], da[3];
-        auto rd = [&](int st) {
-          qa[st % 3] = *reinterpret_cast<const bf16x8*>(qtile + rfo[st] + 32 * 256 * half);
-          da[st % 3] = *reinterpret_cast<const bf16x8*>(dotile + rfo[st] + 32 * 256 * half);
-        };
-        rd(0); rd(1);
-#pragma unroll
-        for (int st = 0; st < C::NS; ++st) {
-          if (st + 2 < C::NS) rd(st + 2);
-          __builtin_amdgcn_sched_barrier(0);
-          sv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa[st % 3], kf[st], sv, 0, 0, 0);
-          dpv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da[st % 3], vf[st], dpv, 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      };
-      auto soft = [&](f32x16& sv, f32x16& dpv) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float pr = fast_exp2(sv[r] * c2);
-          sv[r] = pr;
-          dpv[r] = pr * dpv[r];
-        }
-      };
-      f32x16 sa, dpa, sb, dpb;
-      // dV^T += dO^T P, dK^T += Q^T dS of one 32-query half: four batches of transposed fragments (dO^T and Q^T of
-      // the two 16-query steps), each issued one batch ahead of the 4 MFMAs that consume the previous one
-      auto dvdk_half = [&](const f32x16& pv, const f32x16& dsv, int row0) {
-        const bf16x8 p0 = acc_frag(pv, 0), d0 = acc_frag(dsv, 0), p1 = acc_frag(pv, 1), d1 = acc_frag(dsv, 1);
-        bf16x4 l0[4], h0[4], l1[4], h1[4];
-        auto issue = [&](bf16x4 (&lo)[4], bf16x4 (&hi)[4], uint32_t base, int r0) {
-          uint32_t a[4], bb[4];
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) { a[dt] = base + tao[dt] + 256 * r0; bb[dt] = base + tbo[dt] + 256 * r0; }
-          tr_issue4(lo, hi, a, bb);
-        };
-        issue(l0, h0, dobase, row0);            // batch 0: dO^T, queries row0 .. row0+15
-        issue(l1, h1, qbase, row0);             // batch 1: Q^T
-        tr_landed<8>(l0, h0);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat4(l0[dt], h0[dt]), p0, dv[dt], 0, 0, 0);
-        issue(l0, h0, dobase, row0 + 16);       // batch 2: dO^T, queries row0+16 .. row0+31
-        tr_landed<8>(l1, h1);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat4(l1[dt], h1[dt]), d0, dk[dt], 0, 0, 0);
-        issue(l1, h1, qbase, row0 + 16);        // batch 3: Q^T
-        tr_landed<8>(l0, h0);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat4(l0[dt], h0[dt]), p1, dv[dt], 0, 0, 0);
-        tr_landed<0>(l1, h1);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat4(l1[dt], h1[dt]), d1, dk[dt], 0, 0, 0);
-      };
-#if UR_DKV2_ABLATE == 4
-      sa = dk[0]; dpa = dv[0]; sb = dk[1]; dpb = dv[1];
-#else
-      // phase 1: S', dP' of half a
-      s_dp(sa, dpa, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      UR_ASTAMP(1);
-      // phase 2: S', dP' of half b; softmax of half a
-      s_dp(sb, dpb, 1);
-#endif
-      UR_ASTAMP(2);
-#if UR_DKV2_ABLATE != 2
-      soft(sa, dpa);
-#endif
-      __builtin_amdgcn_sched_barrier(0);
-      UR_ASTAMP(3);
-#if UR_DKV2_ABLATE != 1
-      if (it + 1 < ntot) load_tile(it + 1, smem + ((it + 1) & 1) * STG);
-#endif
-      __builtin_amdgcn_sched_barrier(0);
-      UR_ASTAMP(4);
-#if UR_DKV2_ABLATE == 3
-      dk[0][0] += sa[0] + dpa[1] + sb[2] + dpb[3];
-#else
-      // phase 3: dV, dK of half a; softmax of half b
-      dvdk_half(sa, dpa, 0);
-#if UR_DKV2_ABLATE != 2
-      soft(sb, dpb);
-#endif
-      __builtin_amdgcn_sched_barrier(0);
-      UR_ASTAMP(5);
-      // phase 4: dV, dK of half b
-      dvdk_half(sb, dpb, 32);
-#endif
-      UR_ASTAMP(6);
-    } else
-#endif
-    if (kblk < p.Sk) {
-
+    } else if (kblk < p.Sk) {
 #pragma unroll
       for (int sub = 0; sub < 2; ++sub) {
         const int qbase = q0 + 32 * sub;
@@ -1996,13 +1727,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           tr_frags<HD>(tq, qtile, 32 * sub + 16 * s2, lane);
 #pragma unroll
           for (int dt = 0; dt < C::NDT; ++dt) {
-#if UR_DKV2_V2
             mfma_acc_nop(dv[dt], tdo[dt], pf);      // dK^T / dV^T stay in AccVGPRs on every path (a builtin here would copy 128 registers in and out)
             mfma_acc_nop(dk[dt], tq[dt], df);
-#else
-            dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tdo[dt], pf, dv[dt], 0, 0, 0);
-            dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tq[dt], df, dk[dt], 0, 0, 0);
-#endif
           }
         }
       }
@@ -2202,9 +1928,8 @@ __global__ __launch_bounds__(256) void attn_tiny_bwd_kernel(AttnP p) {
       *reinterpret_cast<uint2*>(p.dq + ((long)t.b * p.Sq + qi) * p.lddq + e0) = make_uint2(pack_bf2(dq[qi][0], dq[qi][1]), pack_bf2(dq[qi][2], dq[qi][3]));
 }
 
-// Kernel-selection switches of the attention entry points: process-wide words set through the C ABI (ur_attn_mode, include/unirec_hip.h) --
-// the only environment variable the library reads is the lab switch UR_FWD_GQ2, and only in UR_LAB builds (attn_select).  Every
-// alternative is a complete, tested path (bit-identity / oracle tests flip them).
+// Kernel-selection switches of the attention entry points: process-wide words set through the C ABI (ur_attn_mode, include/unirec_hip.h);
+// the library reads no environment variable.  Every alternative is a complete, tested path (bit-identity / oracle tests flip them).
 std::atomic<int> g_attn_mode[UR_ATTN_MODE_COUNT] = {{3}, {1}, {1}, {1}};      // TINY: bit 0 forward, bit 1 backward; C128, DKV_PERSIST, FEWQ: 0 / 1
 inline int attn_mode(int key) { return g_attn_mode[key].load(std::memory_order_relaxed); }
 
@@ -3073,8 +2798,7 @@ int fill(AttnP& p, const ur_attn_args* a, bool with_ptrs = true) {
 // ---- kernel selection ---------------------------------------------------------------------------------------------------------
 // Which kernel each launch of a call takes is decided HERE and nowhere else: the launchers below, ur_attn_plan,
 // ur_attn_bwd_kv_colsum_floats, lse_log2 and the fused k-RoPE store of ur_attn_bwd all read the AttnPlan.  Pure host arithmetic on
-// sizes, strides (for the backward: with p.lddo set), p.rep, p.drop_thr, the four ur_attn_mode words and the lab variable
-// UR_FWD_GQ2 (UR_LAB builds; read once per process): no HIP call, no pointer target.
+// sizes, strides (for the backward: with p.lddo set), p.rep, p.drop_thr and the four ur_attn_mode words: no HIP call, no pointer target.
 inline int pick_nw(int S) { return S <= 32 ? 1 : (S <= 64 ? 2 : 4); }      // waves of 32 rows per workgroup of the generic kernels
 struct AttnPlan {
   int fwd, dq, dkv;      // UR_ATTN_KERNEL_*
@@ -3082,7 +2806,6 @@ struct AttnPlan {
   int lse_log2;          // the generated backward pair runs: plane 1 of `delta` holds -LSE * log2(e) (AttnP::lse_log2)
 };
 AttnPlan attn_select(const AttnP& p, int hd, bool causal) {
-  static const bool gq2_on = ur_lab_int("UR_FWD_GQ2", 0) == 1;
   const int tiny_mode = attn_mode(UR_ATTN_MODE_TINY);      // 0 keeps tiny shapes on the MFMA kernels (1 / 2: tiny forward / backward only)
   AttnPlan pl;
   pl.nw_q = pick_nw(p.Sq);
@@ -3101,9 +2824,7 @@ AttnPlan attn_select(const AttnP& p, int hd, bool causal) {
   // few queries, many keys (UR_ATTN_MODE_FEWQ = 0: attn_bwd_dkv_kernel; one test process compares the two bit for bit); the only
   // dK/dV kernel that can also emit the column sums of dK | dV
   const bool fewq = hd == 64 && !causal && p.rep == 1 && p.Sq <= KT && p.Sk >= 256 && attn_mode(UR_ATTN_MODE_FEWQ) != 0;
-  pl.fwd = tiny_fwd ? UR_ATTN_KERNEL_TINY
-         : hd == 128 && causal && pl.nw_q == 4 && p.rep == 2 && gq2_on ? UR_ATTN_KERNEL_GQ2
-         : c128_fwd ? UR_ATTN_KERNEL_C128 : UR_ATTN_KERNEL_GENERIC;
+  pl.fwd = tiny_fwd ? UR_ATTN_KERNEL_TINY : c128_fwd ? UR_ATTN_KERNEL_C128 : UR_ATTN_KERNEL_GENERIC;
   pl.dq = tiny_bwd ? UR_ATTN_KERNEL_TINY : c128_bwd ? UR_ATTN_KERNEL_C128 : UR_ATTN_KERNEL_GENERIC;
   pl.dkv = tiny_bwd ? UR_ATTN_KERNEL_TINY
          : fewq ? UR_ATTN_KERNEL_FEWQ
@@ -3154,8 +2875,6 @@ int launch_fwd(const AttnP& p, const AttnPlan& pl, int hd, bool causal, hipStrea
     case UR_ATTN_KERNEL_TINY:
       if (p.Sq <= 2) return launch<&attn_tiny_fwd_kernel<2>>("ur_attn_fwd(tiny)", tiny_grid(p), 256, 0, 0, st, p);
       return launch<&attn_tiny_fwd_kernel<4>>("ur_attn_fwd(tiny)", tiny_grid(p), 256, 0, 0, st, p);
-    case UR_ATTN_KERNEL_GQ2:
-      return launch<&attn_fwd_kernel<128, true, 8, true>>("ur_attn_fwd(gq2)", dim3(ur_cdiv(p.Sq, 128) * (p.nq / 2) * p.B), 512, fwd_smem<128>(), fwd_smem<128>(), st, p);
     case UR_ATTN_KERNEL_C128: {
       const C128Items it = c128_items(p);
       return launch<&attn_fwd_c128_kernel>("ur_attn_fwd(c128)", dim3(std::min(it.nitems, ur_device_cu_count())), 256, c128::LDS_BYTES, c128::LDS_BYTES, st, p, it.nitems, it.nch, it.dv);

@@ -18,21 +18,6 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define UR_WAVE 64
 
-// Lab knobs (tools/lab): experiment switches read from the environment and the kernel branches behind them exist only in builds
-// made with -DUR_LAB=1 (tools/lab/lib_variant.sh ... -DUR_LAB=1); the product library compiles them out.
-#ifndef UR_LAB
-#define UR_LAB 0
-#endif
-static inline int ur_lab_int(const char* name, int dflt) {
-#if UR_LAB
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-#else
-  (void)name;
-  return dflt;
-#endif
-}
-
 // ---- per-device once flags -------------------------------------------------------------------------
 // hipFuncSetAttribute and the CU count are properties of (function, DEVICE): a process that drives several GPUs needs them per
 // device.  Bit d of the mask = done on device d (the guarded calls are idempotent: a race only repeats one; UR_ONCE_PER_DEVICE).

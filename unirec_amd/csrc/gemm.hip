@@ -34,9 +34,6 @@ using urgemm::uniform_ptr;
 
 namespace {
 
-#ifndef UR_GEMM_NO_PH8
-#define UR_GEMM_NO_PH8 0          // lab builds only: 1 = keep the grouped 2-slot loop for the 256x256 tile (A/B against the 8-phase loop)
-#endif
 #ifndef UR_GEMM_STAMPS
 #define UR_GEMM_STAMPS 0          // lab builds only: 1 = thread 0 of every workgroup logs s_memtime at 8 points (ur_lab_gemm_stamps)
 #endif
@@ -45,9 +42,6 @@ __device__ long long g_gemm_stamps[8192 * 8];
 #define UR_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 8192 && blockIdx.z == 0) g_gemm_stamps[blockIdx.x * 8 + (k)] = (long long)__builtin_readcyclecounter(); } while (0)
 #else
 #define UR_STAMP(k) do { } while (0)
-#endif
-#ifndef UR_GEMM_ABLATE
-#define UR_GEMM_ABLATE 0          // lab builds only (tools/lab): 1 = no LDS-DMA in the steady state, 2 = no MFMAs, 3 = no barrier
 #endif
 constexpr int BK = 64;                     // K depth of one LDS stage = two v_mfma_f32_16x16x32_bf16 k-steps ("halves")
 constexpr int NSTAGE = 2;                  // LDS ring: tile t is consumed while tile t+1 lands and tile t+2 is issued
@@ -209,16 +203,8 @@ __device__ __forceinline__ void lds_frags(bf16x8* f, const char* tile, int idx0,
 // BM x BN block tile, NWM x NWN waves; each wave owns (BM/NWM) rows x (BN/NWN) columns of C.
 // EPI: 1 = SwiGLU backward epilogue (ur_gemm_args.swiglu_gu), 2 = SwiGLU forward epilogue (ur_gemm_args.swiglu_gate), each its
 // own instantiation, so the ordinary kernels' code and register allocation do not change with them.
-// MFMA with the accumulator tile in AccVGPRs (inline asm) for the 256x256 kernel: under -amdgpu-mfma-vgpr-form hipcc keeps all
-// 128 accumulator registers of a wave in arch VGPRs, which leaves the 8-phase loop exactly at the 256-register limit (and made
-// every attempt to wrap the body in a tile loop spill).  With "+a" they live in the other half of the unified file.
-#ifndef UR_GEMM_ACC_AGPR
-#define UR_GEMM_ACC_AGPR 0      // lab: at two waves per SIMD the unified file gives a wave 256 registers in TOTAL, so 128 AccVGPRs leave 128 arch VGPRs and the loop spills (468 B scratch): off
-#endif
-template <bool ACC_A>
 __device__ __forceinline__ void mfma16(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-  if constexpr (ACC_A) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-  else acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
 }
 
 template <bool RK, bool SK, bool OUTF32, int BM, int BN, int NWM, int NWN, int EPI = 0>
@@ -281,7 +267,7 @@ int launch_cfg(GemmP p, int splits, hipStream_t st) {
   }
   p.gm = ur_cdiv(p.M, BM); p.gn = ur_cdiv(p.N, BN);
   {
-    // UR_GEMM_CW = n (lab): walk each XCD's tiles in column chunks of n tiles.  With K = 1024 a tile's S panel is 512 KiB: an
+    // Column chunks of n tiles in each XCD's walk.  With K = 1024 a tile's S panel is 512 KiB: an
     // XCD's 32 concurrent tiles over 12 column tiles keep 6 MiB of S panels in play against a 4 MiB L2 and every tile
     // re-fetches its panel from the Infinity Cache; chunks of 4 halve the fabric reads of the N = 3072 launches (FETCH_SIZE
     // 2.24 -> 1.20 GB for gate_proj, profiles/r1_gemm_pmc.json) -- and cost 1 % of the joint step in alternating same-box
@@ -290,17 +276,12 @@ int launch_cfg(GemmP p, int splits, hipStream_t st) {
     // 2.4 / 5.9 GB per launch (x8.7 / x21 of A + W, ~4 TB/s) and chunks of 4 are 2.1 / 3.6 % faster in isolation
     // (tools/kernel_bench.py gemm_step), while launches of <= 12 column tiles still lose 1-3 %.  Inside the joint step,
     // alternating same-box runs: chunks of 4 on the two wide launches only 516.6 vs 517.0 ms (nothing), chunks of 4 wherever
-    // they divide 551.8 vs 545.8 ms (+1.1 %) -- the plain order stays the default (UR_GEMM_CW = n: lab).
-    static const int env_cw = ur_lab_int("UR_GEMM_CW", -1);
+    // they divide 551.8 vs 545.8 ms (+1.1 %) -- the plain order stays the default.
     p.gcw = 0;
-    // default: chunks of 4 on launches of >= 16 column tiles (the merged q|k|v and gate|up forwards) -- time-neutral inside the
+    // chunks of 4 on launches of >= 16 column tiles (the merged q|k|v and gate|up forwards) -- time-neutral inside the
     // step, but the fabric reads of those launches drop from x8.7 / x21 of A + W to what profiles/r2_gemm_pmc.json lists
-    const int cw = env_cw >= 0 ? env_cw : (p.gn >= 16 ? 4 : 0);
+    const int cw = p.gn >= 16 ? 4 : 0;
     if (cw > 0 && BM == 256 && (p.gm % 8) == 0 && p.gn > cw && (p.gn % cw) == 0) p.gcw = cw;
-  }
-  {
-    static const int env_st = ur_lab_int("UR_GEMM_STAGGER", 0);     // lab
-    p.stagger = (BM == 256 && p.gm * p.gn >= 1024) ? env_st : 0;
   }
   dim3 grid(p.gm * p.gn, 1, splits);
   hipLaunchKernelGGL((gemm_kernel<RK, SK, OUTF32, BM, BN, NWM, NWN, EPI>), grid, dim3(NWM * NWN * 64), SMEM, st, p);
@@ -313,11 +294,10 @@ int launch_cfg(GemmP p, int splits, hipStream_t st) {
 template <bool RK, bool SK, bool OUTF32>
 int launch(const GemmP& p, int splits, hipStream_t st) {
   const long big_wgs = (long)ur_cdiv(p.M, 256) * ur_cdiv(p.N, 256) * splits;
-  static const bool force128 = ur_lab_int("UR_GEMM_FORCE128", 0) == 1;      // lab: 128x128 tiles (2 workgroups per CU) everywhere
   if constexpr (RK && SK && !OUTF32) {
     if (urgemm::gemm_pers_eligible(p, splits, RK, SK, OUTF32)) return urgemm::gemm_pers_launch(p, st);    // gemm_pers.hip
     if (p.sw_gu && p.sw_mode == 1) {       // SwiGLU backward epilogue: K-contiguous bf16 launches only (ur_gemm checks)
-      if (p.M >= 256 && p.N >= 256 && big_wgs >= 256 && !force128) return launch_cfg<true, true, false, 256, 256, 2, 4, 1>(p, splits, st);
+      if (p.M >= 256 && p.N >= 256 && big_wgs >= 256) return launch_cfg<true, true, false, 256, 256, 2, 4, 1>(p, splits, st);
       return launch_cfg<true, true, false, 128, 128, 2, 2, 1>(p, splits, st);
     }
     if (p.sw_gu && p.sw_mode == 2) {       // SwiGLU forward epilogue
@@ -328,7 +308,7 @@ int launch(const GemmP& p, int splits, hipStream_t st) {
   // (token-reduction launches, both operands K-strided: one round of 224+ big tiles already beats the small tile -- the host picks
   // such splits, qformer.py:_split_k_for)
   const long big_min = (!RK && !SK) ? 224 : 256;
-  if (p.M >= 256 && p.N >= 256 && big_wgs >= big_min && !force128) return launch_cfg<RK, SK, OUTF32, 256, 256, 2, 4>(p, splits, st);
+  if (p.M >= 256 && p.N >= 256 && big_wgs >= big_min) return launch_cfg<RK, SK, OUTF32, 256, 256, 2, 4>(p, splits, st);
   return launch_cfg<RK, SK, OUTF32, 128, 128, 2, 2>(p, splits, st);
 }
 
@@ -394,7 +374,7 @@ static void fill_params(const ur_gemm_args* a, GemmP& p) {
   p.qk_rstd = a->qkr_rstd; p.qk_qw = a->qkr_qw; p.qk_kw = a->qkr_kw; p.qk_cos = a->qkr_cos; p.qk_sin = a->qkr_sin;
   p.qk_S = a->qkr_S; p.qk_nq = a->qkr_nq_cols; p.qk_nk = a->qkr_nk_cols; p.qk_eps = a->qkr_eps;
   p.sp_act = (bf16_t*)a->swp_act; p.sp_ldact = a->swp_ldact; p.sp_I = a->swp_I;
-  p.ksplit_len = 0; p.slab_stride = 0; p.gcw = 0; p.stagger = 0;
+  p.ksplit_len = 0; p.slab_stride = 0; p.gcw = 0; p.pad_ = 0;
 }
 
 static bool swiglu_paired_ok(const ur_gemm_args* a, const GemmP& p) {

@@ -2,7 +2,6 @@
 // OUTF32, BM, BN, NWM, NWN, EPI, the launch parameters `p` (GemmP) and UR_GEMM_BID (the workgroup's index among its product's tiles).
 // (A shared __device__ function instead changed the register allocation of every existing instantiation -- 36 -> 60 bytes of scratch per lane in
 // the token-major 256x256 kernel -- so the text is shared, not the function.)
-  constexpr bool ACC_A = UR_GEMM_ACC_AGPR && BM == 256 && BN == 256;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NT = NWM * NWN * 64;
   constexpr int S_BYTES = SK ? Tile<BN>::KC_BYTES : Tile<BN>::KS_BYTES;
@@ -42,16 +41,6 @@
   }
   const int m0 = bm * BM, n0 = bn * BN;
   const int z = blockIdx.z;
-  // De-phase the CUs: every tile of a launch takes the same time, so the 256 workgroups of a round reach their epilogues
-  // together and 32 MiB of C leave for HBM at once (an epilogue of ~10 k cycles, most of it write back-pressure) while HBM
-  // idles during the main loops.  The launch's FIRST wave of workgroups starts in 8 groups `stagger` cycles apart; the
-  // offsets then persist from round to round.  (Lab builds only; measured neutral: DESIGN / docs/lab_notes.md.)
-#if UR_LAB
-  if (p.stagger > 0 && blockIdx.x < 256 && blockIdx.z == 0) {
-    const long long until = (long long)__builtin_readcyclecounter() + (long long)((blockIdx.x >> 3) & 7) * p.stagger;
-    while ((long long)__builtin_readcyclecounter() < until) __builtin_amdgcn_s_sleep(16);
-  }
-#endif
   UR_STAMP(0);
 
   int kbeg = z * p.ksplit_len;
@@ -97,7 +86,7 @@
     for (int i = 0; i < NI; ++i)
 #pragma unroll
       for (int j = 0; j < MI; ++j)
-        mfma16<ACC_A>(acc[i][j], sf[i], rf[j]);
+        mfma16(acc[i][j], sf[i], rf[j]);
   };
 
   // Software pipeline, ONE barrier per 64-deep tile, placed between its two halves.  Fragment register
@@ -134,9 +123,7 @@
   auto mid = [&]() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_waitcnt(0xc07f);        // lgkmcnt(0), as a builtin so the compiler's wait tracking sees it
-#if UR_GEMM_ABLATE != 3
     __builtin_amdgcn_s_barrier();
-#endif
   };
   // One half-step (32 deep) of the steady state = MI groups, group j = the NI MFMAs of row block j.
   // The R fragment of the NEXT half-step for block j-1 is read right after block j-1's last use, so it can
@@ -157,11 +144,7 @@
       if (LF) { loads(j); __builtin_amdgcn_sched_barrier(0); }
       bf16x8 rj = crf[j];
 #pragma unroll
-#if UR_GEMM_ABLATE == 2
-      for (int i = 0; i < NI; ++i) acc[i][j][0] += (float)(csf[i][0] ^ rj[0]);       // lab build: no MFMAs
-#else
-      for (int i = 0; i < NI; ++i) mfma16<ACC_A>(acc[i][j], csf[i], rj);
-#endif
+      for (int i = 0; i < NI; ++i) mfma16(acc[i][j], csf[i], rj);
       __builtin_amdgcn_sched_barrier(0);
       if (!LF) { loads(j); __builtin_amdgcn_sched_barrier(0); }
     }
@@ -188,7 +171,7 @@
   // The same loop serves the token reductions (dW = dY^T X: BOTH operands K-strided): a half tile is one 16 KiB image there too
   // ([64 k][128 columns]), filled by two LDS-DMA pieces per wave (4 k-rows x 256 B each) and read with transposed LDS reads into
   // the same fragment registers; phases, counted waits and hazards are unchanged.
-  constexpr bool PH8 = (RK == SK) && BM == 256 && BN == 256 && NWM == 2 && NWN == 4 && (UR_GEMM_ABLATE == 0) && !UR_GEMM_NO_PH8;
+  constexpr bool PH8 = (RK == SK) && BM == 256 && BN == 256 && NWM == 2 && NWN == 4;
   if constexpr (PH8) {
     if (interior && nfull1 >= 3) {
       constexpr bool KC = RK;
@@ -277,7 +260,7 @@
           for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj)
-              mfma16<ACC_A>(acc[2 * sh + ii][4 * rh + jj], S[ii][h], R[jj][h]);
+              mfma16(acc[2 * sh + ii][4 * rh + jj], S[ii][h], R[jj][h]);
         __builtin_amdgcn_s_setprio(0);
       };
       // the two LDS-DMA pieces of this wave for half `hf` (rows 128 hf ..) of an operand tile whose k position is in `ub`
@@ -411,9 +394,7 @@
             const char* ub = is_s ? ubs + li * spiece : ubr + li * rpiece;      // scalar
             const uint32_t vo = is_s ? svoff0 : rvoff0;
             char* dst = slot + (is_s ? 0 : S_BYTES) + (li * (NT / 64) + uwave) * 1024;
-#if UR_GEMM_ABLATE != 1
             __builtin_amdgcn_global_load_lds((gbl_void*)(ub + vo), (lds_void*)dst, 16, 0, 0);
-#endif
           }
         };
         // P1: half 1 from (sfB, rf); the next half's fragments come from tile t+1
@@ -437,9 +418,6 @@
   }
 
   UR_STAMP(4);
-  // the asm MFMAs' results are read below by instructions hipcc schedules without knowing an MFMA wrote them: let the
-  // last one retire (16x16x32: 8 passes) before anything touches the accumulators
-  if constexpr (ACC_A) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
   // ---- LoRA dropout, backward to the adapter input: C(m,n) += sum_a keep_a(m,n)/(1-p) * tb_a(m,:) . A_a(:,n).
   // Each adapter's rank-r product of a 16x16 sub-tile is ONE MFMA (k = r <= 32, zero-padded) into a scratch
   // accumulator -- rank 64: two such steps of 32, each masked and added on its own (the mask is linear) -- ; the keep

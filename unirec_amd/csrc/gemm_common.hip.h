@@ -13,7 +13,7 @@ struct GemmP {
   int ksplit_len; long slab_stride;
   int gm, gn;
   int gcw;    // column-chunk width (tiles) of the per-XCD tile order; 0 = plain row-major runs
-  int stagger;   // cycles between the start groups of the launch's first wave of workgroups (0 = all start together)
+  int pad_;   // keeps the 8-byte slot of gcw: the kernels' argument offsets are part of their compiled code
   // LoRA dropout (ur_gemm_args.drop_*): masked rank-r LoRA epilogue driven by the adapters' dropped-flag bit planes
   const uint8_t* drop_bits; long drop_bits_ld, drop_bits_stride; int drop_rank; float drop_inv_keep;
   // SwiGLU backward epilogue (ur_gemm_args.swiglu_*): the result is d(act); dgate / dup leave instead of C
@@ -44,7 +44,7 @@ __device__ __forceinline__ const char* uniform_ptr(const char* p) {
   return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
 }
 
-// ---- shared by the persistent kernels (gemm_pers.hip, gemm_ws.hip) ----
+// ---- used by the persistent kernel (gemm_pers.hip) ----
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void gbl_void;
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
@@ -60,11 +60,6 @@ template <> struct raw_words<1> { typedef uint32_t type; };
 template <class T> __device__ __forceinline__ T ld_g(const void* p) {
   typedef typename raw_words<sizeof(T) / 4>::type raw_t;                   // (HIP's uint4 / float4 classes do not copy out of an address space)
   const raw_t r = *(const __attribute__((address_space(1))) raw_t*)(p);
-  return __builtin_bit_cast(T, r);
-}
-template <class T> __device__ __forceinline__ T ld_g_nt(const void* p) {      // read-once streams (the SwiGLU backward's gate | up, a residual)
-  typedef typename raw_words<sizeof(T) / 4>::type raw_t;
-  const raw_t r = __builtin_nontemporal_load((const __attribute__((address_space(1))) raw_t*)(p));
   return __builtin_bit_cast(T, r);
 }
 template <class T> __device__ __forceinline__ void st_g(void* p, const T& v) {
@@ -106,9 +101,5 @@ __device__ __forceinline__ void swap16f(float& a, float& b) {
 // Returns 0 and launches when the shape qualifies, 1 when the caller should use the generic kernel, < 0 / > 0 on error.
 bool gemm_pers_eligible(const GemmP& p, int splits, bool rk, bool sk, bool outf32);
 int gemm_pers_launch(GemmP p, hipStream_t st);
-
-// tools/lab/gemm_ws.hip (lab builds, -DUR_LAB=1): wave-specialised 128x256 kernel (the epilogue of a tile beside the next tile's K loop); a subset of the persistent kernel's launches
-bool gemm_ws_eligible(const GemmP& p);
-int gemm_ws_launch(GemmP p, hipStream_t st);
 
 }  // namespace urgemm

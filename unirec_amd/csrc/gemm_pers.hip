@@ -25,26 +25,6 @@
 namespace {
 using namespace urgemm;
 
-#ifndef UR_PERS_ABLATE
-#define UR_PERS_ABLATE 0          // lab builds only (WRONG results): 1 = epilogue without its stores, 2 = no epilogue, 3 = vmcnt(12) in every K tile, 4 = plain (not non-temporal) stores
-#endif
-#ifndef UR_PERS_JOIN
-#define UR_PERS_JOIN 0            // lab: 1 = the two wave groups re-join for EVERY epilogue (measured neutral for the plain one: the CU's store rate under load, ~17 B/clk, is the limit either way)
-#endif
-#ifndef UR_PERS_EPI_WAIT
-#define UR_PERS_EPI_WAIT 0        // lab: 1 = the epilogue starts with s_waitcnt vmcnt(0): the next tile's two prefetched K tiles have landed before the first C store
-#endif
-#ifndef UR_PERS_NT
-#define UR_PERS_NT 0              // lab: 1 = the epilogues' read-once operands (gate | up of the SwiGLU backward, residual / GELU aux) are loaded non-temporally
-#endif
-#if UR_PERS_NT
-#define UR_LD_STREAM ld_g_nt
-#else
-#define UR_LD_STREAM ld_g
-#endif
-#ifndef UR_PERS_REMAP
-#define UR_PERS_REMAP 1           // 0 = the 128-apart column groups and 16 rows x 64 B stores everywhere (A/B builds)
-#endif
 #ifndef UR_PERS_STAMPS
 #define UR_PERS_STAMPS 0          // lab builds only: n > 0 = waves 0 and 4 of every workgroup log s_memtime around their n-th output tile (ur_lab_pers_stamps)
 #endif
@@ -69,7 +49,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmP p, TileOrder or
   // instruction can cover 8 rows x 128 contiguous bytes -- whole lines -- where the old shape wrote 16 rows x 64 bytes (store-only
   // kernels: 5.8-6.0 TB/s against 3.3-4.0, tools/lab/store_lab.hip).  The LDS image does not change: LDS row sh*128 + wc*32 + x of the
   // S tile is FILLED from weight row n0 + wc*64 + sh*32 + x (a different scalar offset per LDS-DMA piece, nothing else).
-  constexpr bool REMAP = UR_PERS_REMAP && EPI != 3 && EPI != 4;      // (EPI 3 / 4: the tile's 128-column halves are two heads / gate | up)
+  constexpr bool REMAP = EPI != 3 && EPI != 4;      // (EPI 3 / 4: the tile's 128-column halves are two heads / gate | up)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int uwave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -85,20 +65,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmP p, TileOrder or
   const int nkt = nk1 + (K2S ? 1 : 0);
   const int gstride = gridDim.x;
 
-  // Lab switch (UR_PERS_STAGGER = cycles per step, default 0 = off): workgroup w starts (w / 8) % 16 steps late.  Built to test
-  // whether the store bursts of the epilogues (all CUs reach them together) are what makes them slow: they are not -- de-phased
-  // epilogues take as long (in-kernel stamps: 3.85 k cycles per wave group either way), and the de-phasing costs the operand
-  // panels their L2 sharing: CUs that read the same A / W panel a few K tiles apart no longer hit the lines their neighbours
-  // fetched (rocprofv3 FETCH_SIZE of the N = 1024 launches x1.5 of A + W in lockstep, x2.9-4.3 staggered).  See DESIGN.md 11.
-#if UR_LAB
-  if (p.stagger != 0) {
-    // p.stagger < 0 (UR_PERS_STAGGER_XCD): whole XCDs are de-phased instead (ids equal mod 8 share an XCD and its L2): the 32
-    // workgroups of an XCD stay in lockstep on their shared panels, the eight XCDs reach their epilogues 1/8 period apart
-    const int steps = p.stagger < 0 ? (int)(blockIdx.x & 7) : (int)((blockIdx.x >> 3) & 15);
-    const long long until = (long long)__builtin_readcyclecounter() + (long long)steps * (p.stagger < 0 ? -p.stagger : p.stagger);
-    while ((long long)__builtin_readcyclecounter() < until) __builtin_amdgcn_s_sleep(8);
-  }
-#endif
   // ---- producer: where the K tile that is fetched next comes from (scalars + one lane offset per operand) ----
   int vid = blockIdx.x, m0, n0;                            // current output tile
   { int bm, bn; tile_coords(ord, vid, bm, bn); m0 = bm * BM; n0 = bn * BN; }
@@ -263,7 +229,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmP p, TileOrder or
       char* slot = smem + (q & 1) * STAGE;
       const char* nslot = smem + ((q + 1) & 1) * STAGE;
       if (first_tile) ktile(slot, nslot, std::true_type{}, std::integral_constant<int, 12>{}, std::false_type{});
-      else ktile(slot, nslot, std::true_type{}, std::integral_constant<int, (UR_PERS_ABLATE == 3 || UR_PERS_ABLATE == 1 || UR_PERS_ABLATE == 2) ? 12 : 28>{}, std::false_type{});
+      else ktile(slot, nslot, std::true_type{}, std::integral_constant<int, 28>{}, std::false_type{});
       ++q;
       first_tile = false;
     }
@@ -308,21 +274,11 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmP p, TileOrder or
     }
     // the next tile's first K tile fetches ITS K tile 2
     ubs = uniform_ptr(s_base(nn0) + 2 * BK * 2); ubr = uniform_ptr(r_base(nm0) + 2 * BK * 2);
-#if UR_PERS_ABLATE == 2
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) asm volatile("" :: "v"(acc[i][j]));
-    if (true) { tiles_left -= 1; if (tiles_left == 0) break; m0 = nm0; n0 = nn0; continue; }
-#endif
     // The masked LoRA epilogue is a chain of load -> wait -> MFMA -> add: one barrier interval apart the two groups would run
     // it one after the other (each waiting at the other's barrier); re-joined they run it together.
-    constexpr bool JOIN = UR_PERS_JOIN || DROP || EPI == 3;      // (EPI 3: its row sums cross the waves through LDS behind a workgroup barrier)
+    constexpr bool JOIN = DROP || EPI == 3;      // (EPI 3: its row sums cross the waves through LDS behind a workgroup barrier)
     if (JOIN && wr == 0) __builtin_amdgcn_s_barrier();
     UR_PSTAMP(6);
-#if UR_PERS_EPI_WAIT
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     // ================= epilogue, from the accumulators (no LDS, no barrier) =================
     __builtin_amdgcn_sched_barrier(0);      // nothing of the epilogue (its loads!) is scheduled up into the last K tile's phases
     // Lane constants of the epilogue are derived from an opaque copy of the lane id EVERY tile: hoisted out of the tile loop they
@@ -511,7 +467,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmP p, TileOrder or
           z2[e] = (uint32_t)__builtin_amdgcn_update_dpp((int)xa[e], (int)xb[e], 0x128, 0xf, 0x3, false);     // ... into lanes 0..7
         }
       };
-      if constexpr (EPI == 0 && REMAP) {
+      if constexpr (EPI == 0) {
         // whole-line stores: XA = the lane's 8 columns of group sh 0, XB = of group sh 1 (32 columns further); one DPP row rotation by 8
         // lanes hands XB to the lane 8 rows away, merged under a bank mask: store 1 = rows 0..7 x 128 bytes, store 2 = rows 8..15
         uint32_t loff1, loff2;
@@ -537,30 +493,12 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmP p, TileOrder or
           __builtin_nontemporal_store(z1, (__attribute__((address_space(1))) u32x4_t*)(base + loff1));
           __builtin_nontemporal_store(z2, (__attribute__((address_space(1))) u32x4_t*)(base + loff2));
         }
-      } else
-      if constexpr (EPI == 0) {
-        const uint32_t loff = (uint32_t)((el15 * p.ldc + cs) * 2);
-#pragma unroll
-        for (int sh = 0; sh < 2; ++sh)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const f32x4 a = acc[2 * sh][j], b = acc[2 * sh + 1][j];
-            uint32_t a0 = pack_bf2(a[0] * alpha, a[1] * alpha), a1 = pack_bf2(a[2] * alpha, a[3] * alpha);
-            uint32_t b0 = pack_bf2(b[0] * alpha, b[1] * alpha), b1 = pack_bf2(b[2] * alpha, b[3] * alpha);
-            swap16(a0, b0); swap16(a1, b1);
-            char* base = uniform_wptr(reinterpret_cast<char*>(p.C) +
-                                      ((long)(m0 + (j >> 2) * 128 + wr * 64 + (j & 3) * 16) * p.ldc + n0 + sh * 128 + wc * 32) * 2);
-            const u32x4_t v = {a0, a1, b0, b1};
-#if UR_PERS_ABLATE == 1
-            asm volatile("" :: "v"(v), "v"(base + loff));
-#elif UR_PERS_ABLATE == 4
-            st_g<u32x4_t>(base + loff, v);
-#else
-            __builtin_nontemporal_store(v, (__attribute__((address_space(1))) u32x4_t*)(base + loff));
-#endif
-          }
-      } else if constexpr ((EPI == 2 || EPI == 5 || EPI == 6 || EPI == 7) && REMAP) {
-        // bias / residual / GELU with whole-line stores.  Bias and residual are added in the MFMA layout (8-byte residual pieces, as below);
+      } else if constexpr (EPI == 2 || EPI == 5 || EPI == 6 || EPI == 7) {
+        // bias / residual / GELU with whole-line stores.  EPI 5: bias only (a RUNTIME residual switch made hipcc spill 16-25 registers);
+        // EPI 6: bias, then GELU of the bf16-ROUNDED pre-activation into a second output (gemm.hip's rich epilogue: the backward's gelu'(u)
+        // sees the same u); EPI 7: the second operand is that saved pre-activation and gelu'(u) is multiplied in instead of a residual added.
+        // Bias and residual are added in the MFMA layout (lane: row m, 4 consecutive columns of each 16x16 sub-tile: 8-byte residual pieces;
+        // adding after an f32 swap -- 16-byte pieces -- costs 8 more live registers per row block and spilled);
         // quarter q = (row half q >> 1, row blocks 2 (q & 1) .. + 1) x BOTH column groups, so that every row block has its two pieces
         // at hand for the line merge; the residual pieces of quarter q + 1 are issued before quarter q's stores.
         constexpr bool RES = EPI == 2 || EPI == 7, GRAD = EPI == 7, GOUT = EPI == 6;
@@ -588,8 +526,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmP p, TileOrder or
 #pragma unroll
               for (int sh = 0; sh < 2; ++sh) {
                 const char* rbase = uniform_ptr(reinterpret_cast<const char*>(rsrc + (long)(m0 + rh * 128 + wr * 64 + (2 * (q & 1) + t) * 16) * ldrs + n0 + wc * 64 + sh * 32));
-                ra[q & 1][t][sh] = UR_LD_STREAM<uint2>(rbase + loff_r);
-                rb[q & 1][t][sh] = UR_LD_STREAM<uint2>(rbase + loff_r + 32);
+                ra[q & 1][t][sh] = ld_g<uint2>(rbase + loff_r);
+                rb[q & 1][t][sh] = ld_g<uint2>(rbase + loff_r + 32);
               }
           }
         };
@@ -639,78 +577,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmP p, TileOrder or
             }
           }
         }
-      } else if constexpr (EPI == 2 || EPI == 5 || EPI == 6 || EPI == 7) {
-        // EPI 5: bias only (a RUNTIME residual switch made hipcc spill 16-25 registers); EPI 6: bias, then GELU of the bf16-ROUNDED
-        // pre-activation into a second output (gemm.hip's rich epilogue: the backward's gelu'(u) sees the same u); EPI 7: the second
-        // operand is that saved pre-activation and gelu'(u) is multiplied in instead of a residual added
-        constexpr bool RES = EPI == 2 || EPI == 7, GRAD = EPI == 7, GOUT = EPI == 6;
-        // bias / residual in the MFMA layout (lane: row m, 4 consecutive columns of each 16x16 sub-tile: 8-byte residual pieces),
-        // then the plain path's pack + 16-lane swap + 16-byte store.  (Adding after an f32 swap -- 16-byte residual pieces --
-        // costs 8 more live registers per row block; hipcc spilled 16-25 registers around it, some inside the K tiles.)
-        const int nq4 = eg4 * 4;
-        const bf16_t* const rsrc = GRAD ? p.aux : p.res;
-        const long ldrs = GRAD ? p.ldaux : p.ldres;
-        const uint32_t loff_c = (uint32_t)((el15 * p.ldc + cs) * 2), loff_r = (uint32_t)((el15 * ldrs + nq4) * 2);
-        const uint32_t loff_g = GOUT ? (uint32_t)((el15 * p.ldg + cs) * 2) : 0u;
-        // Software pipeline over the four quarter tiles q = 2 sh + rh (see the SwiGLU-backward branch below): the residual
-        // pieces (and, per column half, the bias) of quarter q + 1 are issued BEFORE quarter q's stores -- a load issued after
-        // stores cannot be waited for without their acknowledgements (vmcnt counts both, in order).
-        uint2 ra[2][4], rb[2][4];
-        float bsa[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, bsb[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        auto load_quarter = [&](int q) {
-          const int sh = q >> 1, rh = q & 1;
-          if ((q & 1) == 0 && p.bias) {
-            const float4 b0 = ld_g<float4>(p.bias + n0 + sh * 128 + wc * 32 + nq4), b1 = ld_g<float4>(p.bias + n0 + sh * 128 + wc * 32 + 16 + nq4);
-            bsa[sh][0] = b0.x; bsa[sh][1] = b0.y; bsa[sh][2] = b0.z; bsa[sh][3] = b0.w; bsb[sh][0] = b1.x; bsb[sh][1] = b1.y; bsb[sh][2] = b1.z; bsb[sh][3] = b1.w;
-          }
-          if constexpr (RES) {
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-              const char* rbase = uniform_ptr(reinterpret_cast<const char*>(rsrc + (long)(m0 + rh * 128 + wr * 64 + jj * 16) * ldrs + n0 + sh * 128 + wc * 32));
-              ra[q & 1][jj] = ld_g<uint2>(rbase + loff_r);
-              rb[q & 1][jj] = ld_g<uint2>(rbase + loff_r + 32);
-            }
-          }
-        };
-        load_quarter(0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (q + 1 < 4) load_quarter(q + 1);
-          const int sh = q >> 1, rh = q & 1;
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const int j = 4 * rh + jj;
-            const f32x4 a = acc[2 * sh][j], b = acc[2 * sh + 1][j];
-            float va[4], vb[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { va[e] = a[e] * alpha + bsa[sh][e]; vb[e] = b[e] * alpha + bsb[sh][e]; }
-            if constexpr (RES && !GRAD) {
-              const uint2 xa = ra[q & 1][jj], xb = rb[q & 1][jj];
-              va[0] += bf_lo(xa.x); va[1] += bf_hi(xa.x); va[2] += bf_lo(xa.y); va[3] += bf_hi(xa.y);
-              vb[0] += bf_lo(xb.x); vb[1] += bf_hi(xb.x); vb[2] += bf_lo(xb.y); vb[3] += bf_hi(xb.y);
-            }
-            if constexpr (GRAD) {
-              const uint2 xa = ra[q & 1][jj], xb = rb[q & 1][jj];
-              va[0] *= gelu_erf_grad_f(bf_lo(xa.x)); va[1] *= gelu_erf_grad_f(bf_hi(xa.x)); va[2] *= gelu_erf_grad_f(bf_lo(xa.y)); va[3] *= gelu_erf_grad_f(bf_hi(xa.y));
-              vb[0] *= gelu_erf_grad_f(bf_lo(xb.x)); vb[1] *= gelu_erf_grad_f(bf_hi(xb.x)); vb[2] *= gelu_erf_grad_f(bf_lo(xb.y)); vb[3] *= gelu_erf_grad_f(bf_hi(xb.y));
-            }
-            uint32_t a0 = pack_bf2(va[0], va[1]), a1 = pack_bf2(va[2], va[3]), b0 = pack_bf2(vb[0], vb[1]), b1 = pack_bf2(vb[2], vb[3]);
-            swap16(a0, b0); swap16(a1, b1);
-            char* cb = uniform_wptr(reinterpret_cast<char*>(p.C) + ((long)(m0 + rh * 128 + wr * 64 + jj * 16) * p.ldc + n0 + sh * 128 + wc * 32) * 2);
-            const u32x4_t o = {a0, a1, b0, b1};
-            st_g<u32x4_t>(cb + loff_c, o);
-            if constexpr (GOUT) {
-              char* gb = uniform_wptr(reinterpret_cast<char*>(p.gelu_out) + ((long)(m0 + rh * 128 + wr * 64 + jj * 16) * p.ldg + n0 + sh * 128 + wc * 32) * 2);
-              const u32x4_t og = {pack_bf2(gelu_erf_f(bf_lo(a0)), gelu_erf_f(bf_hi(a0))), pack_bf2(gelu_erf_f(bf_lo(a1)), gelu_erf_f(bf_hi(a1))),
-                                  pack_bf2(gelu_erf_f(bf_lo(b0)), gelu_erf_f(bf_hi(b0))), pack_bf2(gelu_erf_f(bf_lo(b1)), gelu_erf_f(bf_hi(b1)))};
-              st_g<u32x4_t>(gb + loff_g, og);
-            }
-          }
-        }
-      } else if constexpr (EPI == 1 && REMAP) {
+      } else {
+        static_assert(EPI == 1, "the remaining epilogue is the SwiGLU backward");
         // ---- SwiGLU backward with whole-line loads and stores: the f32 products change lanes first (the line merge on 8 registers per
         // column group), then gate / up arrive and dgate / dup leave in the merged layout: 8 rows x 128 contiguous bytes per
-        // instruction.  Same software pipeline as below: quarter q = (row half, two row blocks) x both column groups.
+        // instruction.  (No bias / residual: gemm_pers_eligible.)  vmcnt counts loads and stores in issue order, so a load issued AFTER a
+        // batch of stores cannot be waited for without those stores' acknowledgements: the gate / up pieces are issued two row blocks
+        // ahead of the stores they would otherwise queue behind.
         __builtin_amdgcn_sched_barrier(0);
         int em0 = __builtin_amdgcn_readfirstlane(m0), en0 = __builtin_amdgcn_readfirstlane(n0);
         asm volatile("" : "+s"(em0), "+s"(en0));
@@ -723,8 +596,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmP p, TileOrder or
         const long up_g = (long)p.sw_I * 2;
         auto load_block = [&](int j, uint4 (&g)[2], uint4 (&u)[2]) {
           const char* gb = uniform_ptr(reinterpret_cast<const char*>(p.sw_gu + (long)(em0 + (j >> 2) * 128 + wr * 64 + (j & 3) * 16) * p.sw_ldgu + en0 + wc * 64));
-          g[0] = UR_LD_STREAM<uint4>(gb + lg1); g[1] = UR_LD_STREAM<uint4>(gb + lg2);
-          u[0] = UR_LD_STREAM<uint4>(gb + up_g + lg1); u[1] = UR_LD_STREAM<uint4>(gb + up_g + lg2);
+          g[0] = ld_g<uint4>(gb + lg1); g[1] = ld_g<uint4>(gb + lg2);
+          u[0] = ld_g<uint4>(gb + up_g + lg1); u[1] = ld_g<uint4>(gb + up_g + lg2);
         };
         load_block(0, gw[0], uw[0]);
         load_block(1, gw[1], uw[1]);
@@ -770,64 +643,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmP p, TileOrder or
             st_g<u32x4_t>(db + up_g + (pos ? ld2 : ld1), vu);
           }
         }
-      } else {
-        // ---- SwiGLU backward (EPI 1; no bias / residual: gemm_pers_eligible).  vmcnt counts loads and stores in issue order, so a
-        // load issued AFTER a batch of stores cannot be waited for without those stores' acknowledgements: four quarter-tile
-        // batches of {8 loads, wait, math, 8 stores} exposed one load latency + one store round trip each (~28 us per tile
-        // beside a 23 us K loop at K = 1024).  Software pipeline instead: quarter q + 1's gate / up pieces are issued BEFORE
-        // quarter q's stores, into the second of two 32-register buffers; the wait for quarter q's pieces then leaves the 8
-        // stores of q - 1 and the 8 loads of q + 1 in flight (hipcc counts them: vmcnt(16)).
-        static_assert(EPI == 1 && !REMAP, "the remaining epilogue is the SwiGLU backward in the 128-apart layout");
-        __builtin_amdgcn_sched_barrier(0);       // (behind the masked LoRA epilogue: its uniform bases are dead before these are made)
-        int em0 = __builtin_amdgcn_readfirstlane(m0), en0 = __builtin_amdgcn_readfirstlane(n0);
-        asm volatile("" : "+s"(em0), "+s"(en0));
-        uint4 gw[2][4], uw[2][4];
-        // every address = uniform base (scalar registers) + ONE 32-bit lane offset per tensor
-        const uint32_t loff_g = (uint32_t)((el15 * p.sw_ldgu + cs) * 2), loff_d = (uint32_t)((el15 * p.sw_lddgu + cs) * 2);
-        const long up_g = (long)p.sw_I * 2;                                  // bytes from a row's gate half to its up half
-        auto load_quarter = [&](int q, uint4 (&g)[4], uint4 (&u)[4]) {
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const char* gb = uniform_ptr(reinterpret_cast<const char*>(p.sw_gu + (long)(em0 + (q & 1) * 128 + wr * 64 + jj * 16) * p.sw_ldgu + en0 + (q >> 1) * 128 + wc * 32));
-            g[jj] = ld_g<uint4>(gb + loff_g);
-            u[jj] = ld_g<uint4>(gb + up_g + loff_g);
-          }
-        };
-        load_quarter(0, gw[0], uw[0]);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (q + 1 < 4) load_quarter(q + 1, gw[(q + 1) & 1], uw[(q + 1) & 1]);
-          const int sh = q >> 1, rh = q & 1;
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const int j = 4 * rh + jj;
-            char* db = uniform_wptr(reinterpret_cast<char*>(p.sw_dgu + (long)(em0 + rh * 128 + wr * 64 + jj * 16) * p.sw_lddgu + en0 + sh * 128 + wc * 32));
-            f32x4 a = acc[2 * sh][j], b = acc[2 * sh + 1][j];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { float x = a[e], y = b[e]; swap16f(x, y); a[e] = x; b[e] = y; }
-            const float v[8] = {a[0] * alpha, a[1] * alpha, a[2] * alpha, a[3] * alpha, b[0] * alpha, b[1] * alpha, b[2] * alpha, b[3] * alpha};
-            // d(act) = v (f32, unrounded): dgate = v u silu'(g), dup = v silu(g)   (elementwise.hip: swiglu_bwd_kernel)
-            const uint4 gq4 = gw[q & 1][jj], uq4 = uw[q & 1][jj];
-            const uint32_t gq[4] = {gq4.x, gq4.y, gq4.z, gq4.w}, uq[4] = {uq4.x, uq4.y, uq4.z, uq4.w};
-            uint32_t og[4], ou[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              float dgv[2], duv[2];
-#pragma unroll
-              for (int hh = 0; hh < 2; ++hh) {
-                const float gg = hh ? bf_hi(gq[e]) : bf_lo(gq[e]), uu = hh ? bf_hi(uq[e]) : bf_lo(uq[e]);
-                const float d = v[2 * e + hh];
-                const float sg = sigmoid_f(gg);
-                duv[hh] = d * (gg * sg);
-                dgv[hh] = d * uu * (sg * (1.0f + gg * (1.0f - sg)));
-              }
-              og[e] = pack_bf2(dgv[0], dgv[1]); ou[e] = pack_bf2(duv[0], duv[1]);
-            }
-            const u32x4_t vg = {og[0], og[1], og[2], og[3]}, vu = {ou[0], ou[1], ou[2], ou[3]};
-            st_g<u32x4_t>(db + loff_d, vg);
-            st_g<u32x4_t>(db + up_g + loff_d, vu);
-          }
-        }
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -838,7 +653,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmP p, TileOrder or
     m0 = nm0; n0 = nn0;
   }
   // drain: re-join the wave groups, let the never-consumed tail of the stream land before the workgroup's LDS is released
-  if (!(UR_PERS_JOIN || DROP || EPI == 3) && wr == 0) __builtin_amdgcn_s_barrier();
+  if (!(DROP || EPI == 3) && wr == 0) __builtin_amdgcn_s_barrier();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
@@ -854,9 +669,7 @@ int launch_pers(const GemmP& p, hipStream_t st) {
   ncu -= ncu % 8;                  // ids equal mod 8 share an XCD: the stride of the tile walk must keep that
   if (ncu <= 0) ncu = 8;
   const int ntiles = p.gm * p.gn;
-  static const int env_grid = ur_lab_int("UR_PERS_GRID", 0);      // lab: fewer workgroups (a multiple of 8)
-  const int cap = (env_grid >= 8 && env_grid < ncu) ? env_grid - env_grid % 8 : ncu;
-  const int grid = ntiles < cap ? ntiles : cap;
+  const int grid = ntiles < ncu ? ntiles : ncu;
   auto magic = [](int d) { return (uint32_t)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); };
   TileOrder o;
   o.nwg = ntiles; o.gn = p.gn; o.gcw = p.gcw;
@@ -878,7 +691,7 @@ bool gemm_pers_eligible(const GemmP& p, int splits, bool rk, bool sk, bool outf3
   const int mode = set >= 0 ? set : 1;
   if (!mode || !rk || !sk || outf32 || splits > 1) return false;
   if ((p.M % BM) || (p.N % BN) || (p.K % BK) || p.K < 4 * BK) return false;
-  static const int min_tiles = ur_lab_int("UR_PERS_MIN_TILES", 128);      // lab; default 128: half a round already gains from the register epilogue (C2 item stage 21.66 -> 21.05 ms; 256 and 512 equal within noise, user stage unchanged)
+  constexpr int min_tiles = 128;      // half a round already gains from the register epilogue (C2 item stage 21.66 -> 21.05 ms; 256 and 512 equal within noise, user stage unchanged)
   if ((long)(p.M / BM) * (p.N / BN) < min_tiles) return false;
   if ((long)(p.M / BM) * (p.N / BN) >= (1L << 20) || p.N / BN >= (1 << 12) || p.M / BM >= (1 << 15)) return false;      // fdiv: n * d < 2^32
   if (p.sw_mode == 2) return false;
@@ -894,7 +707,7 @@ bool gemm_pers_eligible(const GemmP& p, int splits, bool rk, bool sk, bool outf3
     // with the SwiGLU backward epilogue) and was even at K = 4096 / lost 1.5 % at K = 6144 in round 3 (profiles/r3_gemm_pers_ab.txt: 8 long
     // tiles per CU, nothing to hide, and the joined epilogue costs two barrier intervals); with the whole-line epilogue stores of round 5
     // it wins there too (K = 4096 +8 %, K = 6144 +2-3 %, same box), so the limit only keeps untested lengths off it
-    static const int kmax = ur_lab_int("UR_PERS_DROP_KMAX", 8192);
+    constexpr int kmax = 8192;
     if (p.K > kmax) return false;
   }
   if (p.sw_mode == 1 && (p.bias || p.res)) return false;
@@ -914,30 +727,18 @@ bool gemm_pers_eligible(const GemmP& p, int splits, bool rk, bool sk, bool outf3
 }
 
 int gemm_pers_launch(GemmP p, hipStream_t st) {
-  {
-#if UR_LAB      // lab builds only (tools/lab/gemm_ws.hip linked in by tools/lab/gemm_ws_build.sh): the wave-specialised 128 x 256 kernel of round 5
-    const int set = g_pers_mode.load(std::memory_order_relaxed);
-    if (set == 2 && gemm_ws_eligible(p)) return gemm_ws_launch(p, st);
-#endif
-  }
   p.gm = p.M / BM; p.gn = p.N / BN;
   p.gcw = 0;
   {
     // column chunks on wide launches (gemm.hip): an XCD's 32 concurrent tiles cover (32 / cw) tile rows x cw tile columns and
-    // every A row panel crosses the fabric gn / cw times.  UR_PERS_CW = n (lab) overrides the width where it divides gn.
+    // every A row panel crosses the fabric gn / cw times.
     // Measured (gate|up, gn = 24, K = 1024; same process, interleaved): cw 6 1.448 ms, 12 1.482, 2 1.496, 4 1.507, row-major
     // 1.528, 8 1.535 -- the order moves the launch by +-3 % although the fabric reads differ x2.5 between them; q|k|v (gn 16):
     // 4 and 8 equal, 2 and row-major 1-2 % slower.
-    static const int env_cw = ur_lab_int("UR_PERS_CW", -1);
-    const int cw = env_cw >= 0 ? env_cw : ((p.gn % 6) == 0 && p.gn >= 24 ? 6 : 4);
-    if (cw > 0 && p.gn >= 16 && (p.gm % 8) == 0 && p.gn > cw && (p.gn % cw) == 0) p.gcw = cw;
+    const int cw = (p.gn % 6) == 0 && p.gn >= 24 ? 6 : 4;
+    if (p.gn >= 16 && (p.gm % 8) == 0 && p.gn > cw && (p.gn % cw) == 0) p.gcw = cw;
   }
   const bool drop = p.drop_bits != nullptr && p.K2 > 0;
-  {
-    static const int env_st = ur_lab_int("UR_PERS_STAGGER", 0);      // lab: cycles per start step; 0 = off (default)
-    static const int env_sx = ur_lab_int("UR_PERS_STAGGER_XCD", 0);  // lab: cycles per XCD step
-    p.stagger = env_sx > 0 ? -env_sx : (env_st > 0 ? env_st : 0);
-  }
   const int mode = drop ? 2 : (p.K2 > 0 ? 1 : 0);
   const int epi = p.sp_act ? 4 : (p.qk_q ? 3 : (p.sw_mode == 1 ? 1 : (p.gelu_out ? 6 : (p.aux ? 7 : (p.res ? 2 : (p.bias ? 5 : 0))))));
 #define UR_PERS_CASE(E, MD) if (epi == E && mode == MD) return launch_pers<E, MD>(p, st)

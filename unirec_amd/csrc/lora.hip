@@ -40,15 +40,11 @@
 #endif
 namespace {
 
-typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
 typedef short ss2_t __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
   h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
   return h;
-}
-__device__ __forceinline__ uint32_t pk_sub16(uint32_t a, uint32_t b) {
-  return __builtin_bit_cast(uint32_t, (us2_t)(__builtin_bit_cast(us2_t, a) - __builtin_bit_cast(us2_t, b)));
 }
 __device__ __forceinline__ uint32_t pk_sign16(uint32_t a) {          // each 16-bit half -> 0xffff if its sign bit is set
   return __builtin_bit_cast(uint32_t, (ss2_t)(__builtin_bit_cast(ss2_t, a) >> 15));
@@ -84,26 +80,19 @@ __device__ __forceinline__ int sw16(int r) { return (r & 7) ^ ((r & 8) >> 1); }
 // swr = the f64sw PAIR swizzle written as a chunk swizzle serves both: transposed reads need rows {0, 2, 8, 10} (and {4, 6, 12, 14}) on
 // four different chunk pairs, row reads need the chunk positions of rows {0, 2, 12, 14} and (1 ^ those of) rows {4, 6, 8, 10} all different:
 // positions (0, 2, 0, 2, 4, 6, 4, 6) for rows (0, 2, 4, .. 14); odd rows alike in the other half of the banks.
-#ifndef UR_RING_SWR
-#define UR_RING_SWR 1        // lab: 0 = sw16 in the ring kernels (round 5)
-#endif
-__device__ __forceinline__ int swr(int r) { return UR_RING_SWR ? ((((r >> 1) & 1) << 1) | (((r >> 3) & 1) << 2)) : sw16(r); }
+__device__ __forceinline__ int swr(int r) { return (((r >> 1) & 1) << 1) | (((r >> 3) & 1) << 2); }
 // (ring kernels, [tokens][16] tiles of 32-byte rows: transposed reads of rows {0-3, 8-11} + 4 by a 32-lane group need rows r and r + 8 in
 // different halves of the 256 bytes of banks: LDS row slot s holds source row vrow(s), an involution)
-__device__ __forceinline__ int vrow(int s) { return UR_RING_SWR ? (s ^ (((s >> 3) & 1) << 2)) : s; }
+__device__ __forceinline__ int vrow(int s) { return s ^ (((s >> 3) & 1) << 2); }
 
 // ---- dropped-flag bit planes ---------------------------------------------------------------------
 // thread <-> (row m, group q of 32 columns): one 32-bit word per adapter plane.  Every element draws a 15-bit value u;
 // dropped iff u < thr = p * 2^15.  The (row, group, adapter, seed) counter is murmur-finalised ONCE into the word's key h;
-// UR_BITS_XORSHIFT = 2 (default): the 32 values are BIT-SLICED over up to 15 consecutive states of a multiply-xorshift chain started at h
+// the 32 values are BIT-SLICED over up to 15 consecutive states of a multiply-xorshift chain started at h
 //   (state k carries bit k of all 32 values, least significant first) and the 32 comparisons are one boolean step per state:
 //   lt_k = t_k ? (~b_k | lt_{k-1}) : (~b_k & lt_{k-1});  bits below thr's lowest set bit cannot decide and are not drawn.
 //   7 vector instructions per state for 32 decisions (the kernel is VALU-bound: profiles/README.md r2_lora_bits.txt).
-// = 1: 16 states, two 15-bit fields of each compared by a packed subtract; = 0: a second finaliser per pair (round 1).
 // Streams of different words start at hashed, unrelated points of the generator's single 2^32 - 1 cycle.
-#ifndef UR_BITS_XORSHIFT
-#define UR_BITS_XORSHIFT 2
-#endif
 __global__ void lora_bits_kernel(uint64_t seed, uint32_t thr15, int M, int W, int nad, long bits_ld, long bits_stride,
                                  uint8_t* __restrict__ bits, long row0) {
   // blockIdx.y counts chunks of 2^20 rows so that the (row, group) split is ONE 32-bit division (a 64-bit one costs ~150 vector
@@ -114,7 +103,6 @@ __global__ void lora_bits_kernel(uint64_t seed, uint32_t thr15, int M, int W, in
   const int q = (int)(lid - ml * ng);
   const long m = ((long)blockIdx.y << 20) + ml;
   if (ml >= (1u << 20) || m >= M) return;
-  [[maybe_unused]] const uint32_t thr_pk = thr15 * 0x10001u;
   // seed-only key (scalar unit), entered between the two mixing rounds as ur_hash2 does: the streams of two seeds are
   // neither shifted nor XOR-permuted copies of each other even when the seeds differ in a few low bits only
   const uint32_t s_lo = (uint32_t)seed, s_hi = (uint32_t)(seed >> 32);
@@ -125,7 +113,6 @@ __global__ void lora_bits_kernel(uint64_t seed, uint32_t thr15, int M, int W, in
       const uint64_t ctr = (((uint64_t)(row0 + m) * (uint64_t)ng + (uint64_t)(uint32_t)q) << 2) + (uint64_t)a;     // row0: rows that precede row 0 in the global minibatch
       const uint32_t h = fmix32((((uint32_t)ctr ^ s_lo) + fmix32((uint32_t)(ctr >> 32) + s_hi + 0x9E3779B9u)) ^ k2) + k2;
       uint32_t w = h ? h : 0x9E3779B9u;            // xorshift32 state: never zero
-#if UR_BITS_XORSHIFT == 2
       if (thr15 != 0) {
         const int k0 = __builtin_ctz(thr15);       // uniform (kernel argument): a scalar loop of 15 - k0 states
         uint32_t lt = 0;
@@ -142,23 +129,6 @@ __global__ void lora_bits_kernel(uint64_t seed, uint32_t thr15, int M, int W, in
         }
         out = lt;
       }
-#else
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#if UR_BITS_XORSHIFT == 1
-          w ^= w << 13; w ^= w >> 17; w ^= w << 5;
-#else
-          w = fmix32(h + (uint32_t)(4 * b + i + 1) * 0x9E3779B9u);       // lab: the second finaliser per pair of decisions
-#endif
-          const uint32_t d = pk_sub16(w & 0x7fff7fffu, thr_pk);        // sign of each half set iff field < thr
-          v |= ((d >> 15) & 0x10001u) << i;
-        }
-        out |= ((v | (v >> 12)) & 0xffu) << (8 * b);
-      }
-#endif
     }
     *reinterpret_cast<uint32_t*>(bits + (long)a * bits_stride + m * bits_ld + 4 * q) = out;
   }
@@ -548,16 +518,9 @@ struct SwiLoraP {
   const uint8_t* bits; long bits_ld;
   bf16_t* P; long ldp; float alpha;
 };
-#ifndef UR_SWILORA_DIRECT
-#define UR_SWILORA_DIRECT 1      // 1: A fragments straight from L2 (96 KB, resident), no LDS ring and no block barrier
-#endif
 template <bool MASKED>
 __global__ __launch_bounds__(256, 4) void swiglu_lora_kernel(SwiLoraP p) {
   constexpr int RB = 2, KC = 128;
-  [[maybe_unused]] constexpr int SUB = 16 * 128, STAGE = 2 * SUB;
-#if !UR_SWILORA_DIRECT
-  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
-#endif
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
   const int tok0 = blockIdx.x * (4 * RB * 16) + wave * (RB * 16);
   f32x4 acc[RB];
@@ -571,21 +534,13 @@ __global__ __launch_bounds__(256, 4) void swiglu_lora_kernel(SwiLoraP p) {
     brow[rb] = MASKED ? p.bits + (long)m * p.bits_ld : nullptr;
     acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-#if UR_SWILORA_DIRECT
   const bf16_t* ulane = p.U + (long)l15 * p.ldu + 8 * g;                     // MFMA row operand: A[l15, kc + 32 sx + 8 g ..]
-#else
-  const bf16_t* ulane = p.U + (long)(tid >> 4) * p.ldu + (tid & 15) * 8;      // piece tid = row tid >> 4 of A, 16-byte chunk tid & 15
-#endif
   const int nchunks = p.I / KC;
   for (int c = 0; c < nchunks; ++c) {
     const int kc = c * KC;
-#if UR_SWILORA_DIRECT
     bf16x8 afr[4];
 #pragma unroll
     for (int sx = 0; sx < 4; ++sx) afr[sx] = *reinterpret_cast<const bf16x8*>(ulane + kc + 32 * sx);
-#else
-    const uint4 ureg = *reinterpret_cast<const uint4*>(ulane + kc);
-#endif
     uint4 gf[RB][4], uf4[RB][4], bw[RB];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
@@ -596,22 +551,9 @@ __global__ __launch_bounds__(256, 4) void swiglu_lora_kernel(SwiLoraP p) {
       }
       if (MASKED) bw[rb] = *reinterpret_cast<const uint4*>(brow[rb] + (kc >> 3));
     }
-#if !UR_SWILORA_DIRECT
-    char* st = smem + (c & 1) * STAGE;
-    {
-      const int row = tid >> 4, c16 = tid & 15;
-      *reinterpret_cast<uint4*>(st + (c16 >> 3) * SUB + row * 128 + (((c16 & 7) ^ kc_g(row)) << 4)) = ureg;
-    }
-    __syncthreads();       // slot c & 1 is re-written two chunks later: every wave has passed the next barrier by then
-#endif
 #pragma unroll
     for (int sx = 0; sx < 4; ++sx) {
-#if UR_SWILORA_DIRECT
       const bf16x8 af = afr[sx];
-#else
-      const int ch = 4 * (sx & 1) + g;
-      const bf16x8 af = *reinterpret_cast<const bf16x8*>(st + (sx >> 1) * SUB + l15 * 128 + ((ch ^ kc_g(l15)) << 4));
-#endif
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb) {
         const uint32_t gw[4] = {gf[rb][sx].x, gf[rb][sx].y, gf[rb][sx].z, gf[rb][sx].w};
@@ -660,9 +602,6 @@ __device__ __forceinline__ void tr_pair(bf16x8 (&f)[2], uint32_t a0, uint32_t b0
 // grid: x = 64-column block, y = token split, z = entry (separate column ranges, NAD == 1) or 0 (NAD adapters share X).
 // Per 64-token step the block stages X[64 tokens][64 columns] (one masked copy per adapter) and V[64 tokens][16 NAD]
 // row-major in LDS; ds_read_b64_tr_b16 turns both into token-packed MFMA operands.  Wave w owns columns 16w..16w+15.
-#ifndef UR_RED_ABLATE
-#define UR_RED_ABLATE 0     // lab (results WRONG when != 0): 1 = one LDS copy instead of one per adapter, 2 = no transposed reads / MFMAs,
-#endif                      // 3 = no flag-byte loads, 4 = no barriers, 5 = no global loads of X
 // Rank: V carries NB blocks of 16 columns per adapter (HALF = rank 8: 8 columns, staged into a 32-byte slot whose upper half is zero);
 // block b reads the masked copy of adapter b / NB.
 template <int NAD, bool MASKED, int NB = 1, bool HALF = false>
@@ -706,9 +645,8 @@ __global__ __launch_bounds__(256) void lora_reduce_kernel(RedP p) {
 #pragma unroll
     for (int i = 0; i < XP; ++i) {
       const int m = min(t0 + prow[i], p.M - 1);
-      if (UR_RED_ABLATE != 5) xr[i] = ld_stream(p.X + (long)m * p.ldx + col0 + pcol[i]);
-      else xr[i] = make_uint4(m, i, t0, 1);
-      if (MASKED && UR_RED_ABLATE != 3) {
+      xr[i] = ld_stream(p.X + (long)m * p.ldx + col0 + pcol[i]);
+      if (MASKED) {
 #pragma unroll
         for (int a = 0; a < NAD; ++a) br[i][a] = p.bits[(long)a * p.bits_stride + (long)m * p.bits_ld + (pcol[i] >> 3)];
       }
@@ -732,16 +670,16 @@ __global__ __launch_bounds__(256) void lora_reduce_kernel(RedP p) {
     for (int i = 0; i < XP; ++i) {
       const int off = prow[i] * 128 + ((((pch[i] >> 1) ^ f64sw(prow[i])) << 5) | ((pch[i] & 1) << 4));
 #pragma unroll
-      for (int a = 0; a < (UR_RED_ABLATE == 1 ? 1 : NAD); ++a)
-        *reinterpret_cast<uint4*>(smem + a * XT + off) = (MASKED && UR_RED_ABLATE != 3) ? drop_apply(xr[i], br[i][a]) : xr[i];
+      for (int a = 0; a < NAD; ++a)
+        *reinterpret_cast<uint4*>(smem + a * XT + off) = MASKED ? drop_apply(xr[i], br[i][a]) : xr[i];
     }
 #pragma unroll
     for (int i = 0; i < VP; ++i)
       if (vthr[i]) *reinterpret_cast<uint4*>(vt + vrow[i] * VROW + vpart[i] * 16) = vr[i];
-    if (UR_RED_ABLATE != 4) __syncthreads();
+    __syncthreads();
     if (t0 + TOK < tend) gload(t0 + TOK);
 #pragma unroll
-    for (int ks = 0; ks < (UR_RED_ABLATE == 2 ? 0 : TOK / 32); ++ks) {
+    for (int ks = 0; ks < TOK / 32; ++ks) {
       const int ka = 32 * ks + 8 * g + q;
       const uint32_t xo = lds_off(smem) + ka * 128 + ((wave ^ f64sw(ka)) << 5) + pp * 8;
       const uint32_t vo = lds_off(vt) + ka * VROW + pp * 8;
@@ -754,7 +692,7 @@ __global__ __launch_bounds__(256) void lora_reduce_kernel(RedP p) {
         acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, acc[b], 0, 0, 0);
       }
     }
-    if (UR_RED_ABLATE != 4) __syncthreads();
+    __syncthreads();
   }
   // partial (or final) result of this token range, dense layout: entry e at goff[e], [RANK][W] or [W][RANK]
   long total = 0;
@@ -999,9 +937,6 @@ struct BgradP {
 // tb accumulators, parks the same fragments row-major in its private LDS tile and reads them back transposed
 // (ds_read_b64_tr_b16) as the operands of dB^T[16 x 64] += t^T[16 x 128] dy[128 x 64]; the four waves' partials are
 // summed through LDS and leave as this block's slab.  dy is read once where ur_lora_project + ur_lora_reduce read it twice.
-#ifndef UR_BG_ABLATE
-#define UR_BG_ABLATE 0      // lab (tools/lab/bgrad_ablate.sh; results WRONG by construction): 1 = no dB phase, 2 = loads + tb MFMAs only, 3 = no cross-wave exchange / barriers
-#endif
 // Rank: NB blocks of 16 rank rows per entry over the SAME dy fragments (rank 32 -> 2, 64 -> 4 with 64 tokens per wave, so that the
 // tb accumulators stay in registers); HALF = rank 8 (B^T rows 8..15 and t columns 8..15 read as zero, 8 columns stored).  The dB
 // partials of the blocks leave one after the other through the one cross-wave buffer.
@@ -1065,38 +1000,22 @@ __global__ __launch_bounds__(256, 2) void lora_bgrad_kernel(BgradP p) {
     for (int s2 = 0; s2 < 2; ++s2) {
       const int k = c0 + 32 * s2 + 8 * g;
       const bool ok = k < W;
-#if UR_BG_ABLATE >= 4
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) uf[nb][s2] = *reinterpret_cast<const uint4*>(urow + nb * ublk + k);
-#pragma unroll
-      for (int rb = 0; rb < RBW; ++rb) xf[rb][s2] = *reinterpret_cast<const uint4*>(xrow[rb] + k);
-#else
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) uf[nb][s2] = (ok && uok) ? *reinterpret_cast<const uint4*>(urow + nb * ublk + k) : make_uint4(0, 0, 0, 0);
 #pragma unroll
       for (int rb = 0; rb < RBW; ++rb) xf[rb][s2] = ok ? *reinterpret_cast<const uint4*>(xrow[rb] + k) : make_uint4(0, 0, 0, 0);   // (non-temporal measured slower here)
-#endif
     }
     // (the previous chunk's transposed reads of this tile are complete: lgkmcnt(0) below precedes the MFMAs)
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
       for (int rb = 0; rb < RBW; ++rb) {
-#if UR_BG_ABLATE == 5
-        tb[0][rb][0] += __uint_as_float((xf[rb][s2].x ^ xf[rb][s2].y ^ xf[rb][s2].z ^ xf[rb][s2].w ^ uf[0][s2].x) & 0x3f800000u);
-#else
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
           tb[nb][rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, uf[nb][s2]), __builtin_bit_cast(bf16x8, xf[rb][s2]), tb[nb][rb], 0, 0, 0);
-#endif
         const int row = 16 * rb + l15, ch = 4 * s2 + g;
-#if UR_BG_ABLATE < 2
         *reinterpret_cast<uint4*>(xt + row * 128 + ((ch ^ sw16(row)) << 4)) = xf[rb][s2];
-#endif
       }
-#if UR_BG_ABLATE == 1 || UR_BG_ABLATE == 2 || UR_BG_ABLATE >= 4
-    continue;
-#endif
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the wave's own writes have landed (private tile: no barrier)
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
@@ -1120,9 +1039,6 @@ __global__ __launch_bounds__(256, 2) void lora_bgrad_kernel(BgradP p) {
         db[cb + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tT[nb][k], f[1], db[cb + 1], 0, 0, 0);
       }
     }
-#if UR_BG_ABLATE == 3
-    if (c0 + 64 < W) { if (db[0][0] + db[1][0] + db[2][0] + db[3][0] == 123.456f) slab[0] = 1.f; continue; }
-#endif
     // cross-wave sum: red[wave][w (64)][j (16)]
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb)

@@ -325,7 +325,7 @@ def qknorm_rope_bwd_roped_k(dk_out, k_r, rstd, h0, kw, cos, sin, dk_raw, S, nkv,
 
 
 ATTN_MODE_TINY, ATTN_MODE_C128, ATTN_MODE_DKV_PERSIST, ATTN_MODE_FEWQ = 0, 1, 2, 3      # include/unirec_hip.h: UR_ATTN_MODE_*
-ATTN_KERNELS = ("none", "generic", "tiny", "c128", "gq2", "dkv2", "fewq")                # index = UR_ATTN_KERNEL_*
+ATTN_KERNELS = ("none", "generic", "tiny", "c128", None, "dkv2", "fewq")                 # index = UR_ATTN_KERNEL_* (4: retired id)
 
 
 def attn_mode(key, value):
