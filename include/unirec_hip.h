@@ -420,7 +420,8 @@ int ur_mean_pool_bwd(const float* dout_f32, const void* dout_bf16, void* dx, int
  * ur_gather_rows: out[i] = src[idx[i]] for rows of row_elems elements; idx < 0 or >= n_src gives a zero row -- the
  *   packed form of training/train_item_individual_token_joint.py:557-577 (_get_history_qformer_inputs: per history slot
  *   the cached [F,1024] field vectors and [F] mask, zeros for padding / unknown items) and :246-255 (cached item query
- *   tokens).  Kinds: UR_KIND_U8 / UR_KIND_BF16 / UR_KIND_F32; f32 rows may be written as bf16.
+ *   tokens).  Kinds: UR_KIND_U8 / UR_KIND_BF16 / UR_KIND_F32; f32 rows may be written as bf16, and bf16 rows as f32 (the
+ *   widening is a 16-bit shift, exact for every bit pattern; row_elems % 8 == 0, src and out 16-byte aligned).
  * ur_catalog_scores: scores[b][n] = cos(user_b, item_n) against a shared catalogue [N,D] f32 (F.normalize eps 1e-12,
  *   :408-415 with pool = all items); writes user_inv_norm [B], and cat_inv_norm [N] unless cat_norm_ready.
  *   select == NULL is the plain call.  With select the call STREAMS instead: the catalogue is scored chunk_rows rows at a time into

@@ -3,7 +3,8 @@
 shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
     python tools/kernel_bench.py attn|gemm|lora [--B 8] [--iters 5]
     python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 [--D 1024] [--rounds 3] [--chunks]
-    python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 --scorer vector mfma --catalog-dtype bf16"""
+    python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 --scorer vector mfma --catalog-dtype bf16
+    python tools/kernel_bench.py negatives --B 64 --P 1000 --N 1000000 --K 128 [--catalog-dtype f32|bf16] [--rounds 3]"""
 import argparse
 import os
 import sys
@@ -312,9 +313,56 @@ def catalog(args):
               f"  peak allocation {peaks[name] / 2**20:9.2f} MiB")
 
 
+def negatives(args):
+    """Candidates by index (unirec_amd.negatives.CatalogCandidates) on a random catalogue, every group alternating --rounds times in this
+    process after one call of each:
+      (a) the widening gather of [B,P] rows from the bf16 copy of the catalogue (hip.gather_rows to f32, one kernel) against the two-pass
+          form it replaces (gather_rows to bf16, then .float()); ms and GB/s of the bytes each form moves per element (6 against 10);
+      (b) mine(): the K hardest items of B users over the N-row catalogue (--catalog-dtype);
+      (c) candidates() as a whole: P/2 explicit + P/2 random + K mined columns, seen items, both gathers."""
+    from unirec_amd.negatives import CatalogCandidates
+    B, P, N, K, D = args.B, args.P, args.N, args.K, args.D
+    g = torch.Generator(device="cuda").manual_seed(0)
+    cat = torch.randn(N, D, generator=g, device="cuda")
+    cat16 = cat.to(torch.bfloat16)
+    if args.catalog_dtype == "bf16":
+        cat = cat16
+    user = torch.randn(B, D, generator=g, device="cuda")
+    pos = torch.randint(0, N, (B,), generator=g, device="cuda")
+    idx = torch.randint(0, N, (B, P), generator=g, device="cuda")
+    seen = torch.randint(0, N, (B, 50), generator=g, device="cuda")
+    miner = CatalogCandidates(cat, num_hard=K)
+    whole = CatalogCandidates(miner.evaluator, num_random=P - P // 2, num_hard=K, seed=1)
+    one = lambda: hip.gather_rows(cat16, idx, out_dtype=torch.float32)
+    two = lambda: hip.gather_rows(cat16, idx).float()
+    assert torch.equal(one().view(torch.int32), two().view(torch.int32))
+    el = B * P * D
+    groups = [[("gather bf16 -> f32, one kernel", one, 6 * el), ("gather bf16 -> bf16, then .float()", two, 10 * el)],
+              [(f"mine() K={K}", lambda: miner.mine(user, pos, seen), 0)],
+              [(f"candidates() {P // 2} explicit + {P - P // 2} random + {K} mined", lambda: whole.candidates(user, pos, idx[:, :P // 2], exclude=seen, step=3), 0)]]
+    print(f"negatives B={B} P={P} N={N} D={D} K={K}: catalogue {args.catalog_dtype} {cat.numel() * cat.element_size() / 2**20:.0f} MiB, "
+          f"gathered [B,P,D] f32 {el * 4 / 2**20:.0f} MiB")
+    for group in groups:
+        times = {name: [] for name, _, _ in group}
+        for name, fn, _ in group:                                 # warm-up: scratch buffers, the catalogue norms
+            fn(); fn()
+        for _ in range(args.rounds):
+            for name, fn, _ in group:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.iters):
+                    fn()
+                torch.cuda.synchronize()
+                times[name].append((time.perf_counter() - t0) * 1e3 / args.iters)
+        for name, _, nbytes in group:
+            t = sorted(times[name])
+            rate = f"  {nbytes / t[len(t) // 2] / 1e6:8.1f} GB/s" if nbytes else ""
+            print(f"{name:60s}: median {t[len(t) // 2]:9.3f} ms  min {t[0]:9.3f}  max {t[-1]:9.3f}  ({len(t)} alternating rounds of {args.iters} calls){rate}")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog"])
+    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog", "negatives"])
     ap.add_argument("--B", type=int, default=8)
     ap.add_argument("--S", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=5)
@@ -326,7 +374,8 @@ if __name__ == "__main__":
     ap.add_argument("--chunks", action="store_true", help="catalog: also time retrieve() at half and double the default rows per chunk")
     ap.add_argument("--scorer", nargs="+", choices=["vector", "mfma"], help="catalog: time retrieve() with each of these scorers, alternating")
     ap.add_argument("--catalog-dtype", choices=["f32", "bf16"], default="f32", help="catalog: the dtype the catalogue is stored in")
+    ap.add_argument("--P", type=int, default=1000, help="negatives: candidate columns per user")
     ap.add_argument("--lib", action="store_true", help="gemm: also time torch.matmul on the same operands (reference point)")
     a = ap.parse_args()
     {"attn": attn, "gemm": gemm, "lora": lora, "rope": rope, "dw": dw, "xattn": xattn, "gemm_lora": gemm_lora, "gemm_merge": gemm_merge, "gemm_step": gemm_step, "rmslora": rmslora, "swilora": swilora,
-     "catalog": catalog}[a.what](a)
+     "catalog": catalog, "negatives": negatives}[a.what](a)

@@ -5,7 +5,8 @@
 //                       training/train_item_individual_token_joint.py:557-577 (_get_history_qformer_inputs: history
 //                       slot -> [F,1024] field vectors + [F] mask, zero padding for missing items / empty slots),
 //                       :246-255 (history item query tokens), models/qformer_utils.py:150-155 (__getitem__).
-//                       f32 rows may leave as bf16 (the dtype the Q-Former kernels consume) in the same pass.
+//                       f32 rows may leave as bf16 (the dtype the Q-Former kernels consume) in the same pass, and bf16 rows
+//                       as f32 (a bf16 catalogue's rows for the f32 InfoNCE kernels; a 16-bit shift, exact for every pattern).
 //   ur_catalog_scores : scores[b][n] = cos(user_b, item_n) over a SHARED catalogue [N,D] f32 with
 //                       F.normalize(p=2, eps=1e-12) semantics (training/train_item_individual_token_joint.py:408-415,
 //                       evaluation over pool = all items); the catalogue is read once per 16 users.
@@ -22,7 +23,7 @@
 namespace {
 
 // one wave per output row; 16-byte pieces
-template <int SRC_BYTES, bool TO_BF16>
+template <int SRC_BYTES, bool TO_BF16, bool TO_F32 = false>
 __global__ void gather_rows_kernel(const char* __restrict__ src, const long* __restrict__ idx, char* __restrict__ out,
                                    long row_elems, long n_out, long n_src) {
   const long row = (long)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
@@ -33,7 +34,15 @@ __global__ void gather_rows_kernel(const char* __restrict__ src, const long* __r
   constexpr int EPP = 16 / SRC_BYTES;                   // source elements per 16-byte piece
   const long pieces = row_elems / EPP;                  // host guarantees divisibility
   const char* sp = src + (valid ? s : 0) * row_elems * SRC_BYTES;
-  if (TO_BF16) {                                        // f32 -> bf16: 2 source pieces -> one 16-byte output piece
+  if (TO_F32) {                                         // bf16 -> f32: one source piece -> its 2 adjacent 16-byte output pieces,
+    char* op = out + row * row_elems * 4;               // so a wave's stores cover whole contiguous 128-byte lines
+    for (long p = lane; p < pieces; p += 64) {
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (valid) v = *reinterpret_cast<const uint4*>(sp + p * 16);
+      *reinterpret_cast<uint4*>(op + p * 32) = make_uint4(v.x << 16, v.x & 0xffff0000u, v.y << 16, v.y & 0xffff0000u);
+      *reinterpret_cast<uint4*>(op + p * 32 + 16) = make_uint4(v.z << 16, v.z & 0xffff0000u, v.w << 16, v.w & 0xffff0000u);
+    }
+  } else if (TO_BF16) {                                 // f32 -> bf16: 2 source pieces -> one 16-byte output piece
     char* op = out + row * row_elems * 2;
     for (long p = lane; p < pieces / 2; p += 64) {
       float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
@@ -457,8 +466,9 @@ extern "C" int ur_gather_rows(const void* src, int32_t src_kind, void* out, int3
                               int64_t n_out, int64_t n_src, void* stream) {
   UR_REQUIRE(n_out >= 0 && n_src >= 0 && row_elems > 0, "ur_gather_rows: bad sizes");
   UR_REQUIRE((src_kind == UR_KIND_U8 || src_kind == UR_KIND_BF16 || src_kind == UR_KIND_F32) &&
-             (out_kind == src_kind || (src_kind == UR_KIND_F32 && out_kind == UR_KIND_BF16)),
-             "ur_gather_rows: kinds must match, or f32 -> bf16");
+             (out_kind == src_kind || (src_kind == UR_KIND_F32 && out_kind == UR_KIND_BF16) ||
+              (src_kind == UR_KIND_BF16 && out_kind == UR_KIND_F32)),
+             "ur_gather_rows: kinds must match, or f32 -> bf16, or bf16 -> f32");
   if (n_out == 0) return 0;
   UR_REQUIRE(src && out && idx, "ur_gather_rows: null pointer");
   hipStream_t st = (hipStream_t)stream;
@@ -469,7 +479,10 @@ extern "C" int ur_gather_rows(const void* src, int32_t src_kind, void* out, int3
   } else {
     UR_REQUIRE(UR_ALIGNED16(src) && UR_ALIGNED16(out), "ur_gather_rows: rows must be 16-byte aligned");
     const dim3 grid((unsigned)((n_out + 3) / 4)), block(256);
-    if (src_kind == UR_KIND_BF16) {
+    if (src_kind == UR_KIND_BF16 && out_kind == UR_KIND_F32) {
+      UR_REQUIRE((row_elems % 8) == 0, "ur_gather_rows: bf16 -> f32 rows must be multiples of 8 elements");
+      hipLaunchKernelGGL((gather_rows_kernel<2, false, true>), grid, block, 0, st, (const char*)src, (const long*)idx, (char*)out, (long)row_elems, (long)n_out, (long)n_src);
+    } else if (src_kind == UR_KIND_BF16) {
       UR_REQUIRE((row_elems % 8) == 0, "ur_gather_rows: bf16 rows must be multiples of 8 elements");
       hipLaunchKernelGGL((gather_rows_kernel<2, false>), grid, block, 0, st, (const char*)src, (const long*)idx, (char*)out, (long)row_elems, (long)n_out, (long)n_src);
     } else if (out_kind == UR_KIND_F32) {

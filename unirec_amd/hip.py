@@ -1017,7 +1017,8 @@ _KIND = {torch.uint8: 0, BF16: 1, F32: 2}
 
 def gather_rows(src, idx, out_dtype=None):
     """out[i] = src[idx[i]] over the leading axis (idx int64, any shape; negative / out-of-range -> zero row).
-    f32 sources may be gathered straight to bf16.  Returns idx.shape + src.shape[1:]."""
+    f32 sources may be gathered straight to bf16, and bf16 sources straight to f32 (out_dtype=torch.float32: the exact widening, every
+    bit pattern kept; rows of a multiple of 8 elements).  Returns idx.shape + src.shape[1:]."""
     lib = _lib.load()
     if not src.is_cuda or not src.is_contiguous() or src.dtype not in _KIND:
         raise ValueError("gather_rows: src must be a contiguous uint8 / bf16 / f32 device tensor")

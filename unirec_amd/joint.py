@@ -186,15 +186,31 @@ def mrr_ranks(user_embeddings, positive_item_embeddings, negative_item_embedding
 class MultiModalTrainer:
     """compute_loss of the reference's HF-Trainer subclass (:477-498) without the Trainer."""
 
-    def __init__(self, temperature: float = 0.07):
+    def __init__(self, temperature: float = 0.07, negatives=None):
+        """negatives: a ``negatives.CatalogCandidates``; needed by batches that carry ``positive_item_index`` instead of embeddings."""
         self.infonce_loss = InfoNCELoss(temperature)
+        self.negatives = negatives
 
-    def compute_loss(self, model, inputs, return_outputs=False, **kwargs):
+    def compute_loss(self, model, inputs, return_outputs=False, step=0, **kwargs):
+        """A batch with ``positive_item_index`` [B] takes its candidates from the resident catalogue of ``negatives``: optional
+        ``negative_item_index`` [B,P] (padded with -1), ``negative_masks``, ``seen_item_index`` (ragged or [B,E] padded with -1), plus the
+        random and mined negatives that object is configured for -- mined with the user embeddings of this very forward, random ones
+        keyed on (step, global sample index).  Any other batch carries the embeddings themselves, as the reference's collator does."""
+        by_index = "positive_item_index" in inputs
+        if by_index and self.negatives is None:
+            raise ValueError("compute_loss: the batch holds positive_item_index, which needs the trainer's `negatives` argument "
+                             "(a negatives.CatalogCandidates over the resident catalogue)")
         user_embeddings = model(input_ids=inputs["input_ids"], attention_mask=inputs["attention_mask"],
                                 history_field_embeddings=inputs["history_field_embeddings"],
                                 history_attention_mask=inputs["history_attention_mask"])
-        loss = self.infonce_loss(user_embeddings, inputs["positive_item_embeddings"], inputs["negative_item_embeddings"],
-                                 inputs.get("negative_masks", None))
+        if by_index:
+            pos, neg, mask, _ = self.negatives.candidates(
+                user_embeddings, inputs["positive_item_index"], inputs.get("negative_item_index", None), inputs.get("negative_masks", None),
+                exclude=inputs.get("seen_item_index", None), step=step, first_sample=model.base_model.first_sample(user_embeddings.shape[0]))
+            loss = self.infonce_loss(user_embeddings, pos, neg, mask)
+        else:
+            loss = self.infonce_loss(user_embeddings, inputs["positive_item_embeddings"], inputs["negative_item_embeddings"],
+                                     inputs.get("negative_masks", None))
         return (loss, user_embeddings) if return_outputs else loss
 
 
@@ -277,14 +293,16 @@ class JointTrainer:
     one deterministic norm launch and the AdamW launches reading its coefficient on the device -> scheduler step.
     Under torch.distributed the gradient buckets are wired as bench.py wires them and 1/world is folded into the gradient scale:
     the norm is the norm of the averaged gradient (DDP + clip_grad_norm_), the same on every rank.  ``state.log_history`` gets
-    {step, loss, grad_norm, learning_rate} every ``logging_steps`` -- the only host read (rank-local loss)."""
+    {step, loss, grad_norm, learning_rate} every ``logging_steps`` -- the only host read (rank-local loss).
+    ``negatives`` (a ``negatives.CatalogCandidates``) lets a batch name its candidates by index into a resident catalogue
+    (``MultiModalTrainer.compute_loss``); the random negatives of such a batch are keyed on ``state.global_step``."""
 
-    def __init__(self, model, args, num_training_steps=None, temperature: float = 0.07):
+    def __init__(self, model, args, num_training_steps=None, temperature: float = 0.07, negatives=None):
         from . import dp
         from .optim import FusedAdamW, get_scheduler
         self.model, self.args = model, args
         self.config = cfg = TrainingConfig(args, num_training_steps)
-        self.loss_fn = MultiModalTrainer(temperature)
+        self.loss_fn = MultiModalTrainer(temperature, negatives)
         dev = model.base_model.embed_tokens.weight.device
         qf, qw, uq = model.qformer_model, model.base_model, model.user_qformer
         self.qpack = None if qf is None else qf._ensure_pack(dev)
@@ -317,6 +335,7 @@ class JointTrainer:
                 self.tail_buckets.append(dp.GradBuckets(self.upack.grad, [0, self.upack.numel]))
 
     def compute_loss(self, model, inputs, return_outputs=False, **kwargs):
+        kwargs.setdefault("step", self.state.global_step)       # keys the random negatives of an index batch
         return self.loss_fn.compute_loss(model, inputs, return_outputs=return_outputs, **kwargs)
 
     def training_step(self, inputs):
