@@ -124,3 +124,123 @@ def qformer_masks(base_seed, step, p, B, Q, T, H, nh, num_layers, cross_freq, b0
             m[f"{i}.cross.out"] = hidden_keep(s(SITE_CROSS_OUT), p, B * Q, H, b0 * Q).reshape(B, Q, H)
         m[f"{i}.ffn.out"] = hidden_keep(s(SITE_FFN_OUT), p, B * Q, H, b0 * Q).reshape(B, Q, H)
     return m
+
+
+# ---- LoRA dropped-flag bit planes (unirec_amd/csrc/lora.hip: header comment, lora_bits_kernel, ur_lora_dropout_bits) ----------------
+# One 32-bit word per (adapter plane a, row m, group q of 32 columns); the row of a plane is lora_bits_ld(W) bytes = ng words, the words
+# whose 32 columns all lie at or past W are zero.  Every element draws a 15-bit value u and is DROPPED iff u < thr15.
+_PAIR_ELEM = np.array([0, 2, 4, 6, 1, 3, 5, 7])         # bit i of a flag byte -> element of its 8 columns (i < 4: c + 2i, 4 + i: c + 2i + 1)
+_LORA_GOLD = np.uint64(0x9E3779B9)
+
+
+def lora_bits_ld(W):
+    """bytes per row of a bit plane: 16 per 128 columns (ur_lora_bits_ld)"""
+    return (int(W) + 127) // 128 * 16
+
+
+def lora_thr15(p):
+    """p * 2^15 rounded to nearest (the float p widened to double, + 0.5, truncated), clamped to 32767 -- ur_lora_dropout_bits"""
+    t = float(np.float32(p)) * 32768.0 + 0.5
+    return 32767 if t > 32767.0 else int(t)
+
+
+def _fmix32(h):
+    h = _u32(h)
+    h ^= h >> np.uint64(16)
+    h = _u32(h * np.uint64(0x85EBCA6B))
+    h ^= h >> np.uint64(13)
+    h = _u32(h * np.uint64(0xC2B2AE35))
+    h ^= h >> np.uint64(16)
+    return h
+
+
+def _lora_round(w):
+    """one multiply-xorshift round of the chain"""
+    w = w ^ (w >> np.uint64(16))
+    w = _u32(w * np.uint64(0x7FEB352D))
+    return w ^ (w >> np.uint64(15))
+
+
+def lora_word_keys(seed, M, W, nad, row0=0):
+    """uint64 [nad, M, ng]: the never-zero start state of every word's chain -- the 64-bit counter ((row0 + m) * ng + q) << 2 | a,
+    murmur-finalised with the seed and the seed-only key k2 entered before and after the last round."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    s_lo, s_hi = np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32)
+    rot = _u32((s_hi << np.uint64(13)) | (s_hi >> np.uint64(19)))
+    k2 = _fmix32(_u32(s_lo * np.uint64(0x7FEB352D)) ^ rot ^ np.uint64(0x5851F42D))
+    ng = lora_bits_ld(W) // 4
+    with np.errstate(over="ignore"):
+        rows = np.asarray([int(row0) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64) + np.arange(int(M), dtype=np.uint64)
+        ctr = ((rows[None, :, None] * np.uint64(ng) + np.arange(ng, dtype=np.uint64)[None, None, :]) << np.uint64(2)) \
+            + np.arange(int(nad), dtype=np.uint64)[:, None, None]
+    lo, hi = ctr & _M32, ctr >> np.uint64(32)
+    h = _u32(_fmix32(_u32((lo ^ s_lo) + _fmix32(hi + s_hi + _LORA_GOLD)) ^ k2) + k2)
+    return np.where(h == 0, _LORA_GOLD, h)
+
+
+def lora_words(seed, p, M, W, nad, row0=0):
+    """uint32 [nad, M, lora_bits_ld(W) / 4]: the dropped-flag words ur_lora_dropout_bits writes (little-endian: byte c / 8 of a row covers
+    columns c .. c + 7).  Bit-sliced: state k of the chain carries bit k of the word's 32 values, from thr15's lowest set bit k0 up to
+    bit 14, and lt_k = t_k ? (~b_k | lt_{k-1}) : (~b_k & lt_{k-1}) is the comparison u < thr15 restricted to the bits k0 .. k."""
+    thr = lora_thr15(p)
+    w = lora_word_keys(seed, M, W, nad, row0)
+    lt = np.zeros_like(w)
+    if thr != 0:
+        k0 = (thr & -thr).bit_length() - 1
+        tb = (thr >> k0) | (0x8000 >> k0)                # the sentinel above bit 14: thr's zero bits above its top bit count
+        while tb != 1:
+            w = _lora_round(w)
+            nw = ~w & _M32
+            lt = ((nw | lt) if tb & 1 else (nw & lt))
+            tb >>= 1
+    ng = w.shape[-1]
+    live = (np.arange(ng) * 32 < int(W))[None, None, :]
+    return np.where(live, lt, np.uint64(0)).astype(np.uint32)
+
+
+def lora_dropped_plain(seed, p, M, W, nad, row0=0):
+    """uint8 [nad, M, W]: the same flags element by element -- bit b of the word is the flag of column 32 q + 8 (b / 8) + PAIR[b % 8]; its
+    15-bit value u takes bit k (k0 <= k <= 14) from bit b of chain state k - k0 + 1 and zeros below k0 (thr15 has zeros there, so those
+    bits cannot decide); dropped iff u < thr15."""
+    thr = lora_thr15(p)
+    w = lora_word_keys(seed, M, W, nad, row0)
+    ng = w.shape[-1]
+    out = np.zeros((int(nad), int(M), ng * 32), dtype=np.uint8)
+    if thr != 0:
+        k0 = (thr & -thr).bit_length() - 1
+        u = np.zeros(w.shape + (32,), dtype=np.int64)
+        b = np.arange(32, dtype=np.uint64)
+        for k in range(k0, 15):
+            w = _lora_round(w)
+            u |= (((w[..., None] >> b) & np.uint64(1)).astype(np.int64)) << k
+        col = 8 * (np.arange(32) // 8) + _PAIR_ELEM[np.arange(32) % 8]               # column of bit b inside the word
+        flags = (u < thr).astype(np.uint8)                                          # [nad, M, ng, 32] indexed by bit
+        out.reshape(int(nad), int(M), ng, 32)[..., col] = flags
+    return out[:, :, :int(W)]
+
+
+def lora_keep(seed, p, M, W, nad, row0=0):
+    """uint8 [nad, M, W] keep flags (1 = kept), unpacked from lora_words here: element e of byte c / 8 sits at bit e / 2 + 4 (e % 2)."""
+    words = lora_words(seed, p, M, W, nad, row0).astype(np.uint64)
+    c = np.arange(int(W))
+    e = c % 8
+    shift = (8 * ((c % 32) // 8) + e // 2 + 4 * (e % 2)).astype(np.uint64)
+    dropped = (words[:, :, c // 32] >> shift[None, None, :]) & np.uint64(1)
+    return (1 - dropped).astype(np.uint8)
+
+
+def lora_words_transposed(words, W):
+    """uint32 [nad, M / 32, (W + 3) / 4 * 4]: the token-packed repack ur_lora_bits_transpose makes of the planes (M % 32 == 0): word
+    (group tg, column c) carries the flags of tokens 32 tg .. + 31 of column c, token t at bit 8 (t / 8) + (t % 8) / 2 + 4 (t % 2) (the
+    pair order again, over tokens); the columns W .. ld - 1 carry whatever the row words hold there."""
+    words = np.asarray(words).astype(np.uint64)
+    nad, M, ng = words.shape
+    assert M % 32 == 0
+    ldt = (int(W) + 3) // 4 * 4
+    c = np.arange(ldt)
+    e = c % 8
+    shift = (8 * ((c % 32) // 8) + e // 2 + 4 * (e % 2)).astype(np.uint64)
+    dropped = ((words[:, :, c // 32] >> shift[None, None, :]) & np.uint64(1)).reshape(nad, M // 32, 32, ldt)
+    t = np.arange(32)
+    tpos = (8 * (t // 8) + (t % 8) // 2 + 4 * (t % 2)).astype(np.uint64)
+    return (dropped << tpos[None, None, :, None]).sum(axis=2).astype(np.uint32)

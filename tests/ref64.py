@@ -1,6 +1,6 @@
-"""Float64 restatements of the head, RoPE, pool, data, attention, norm, reduction and GEMM-epilogue primitives of include/unirec_hip.h,
-and the element-wise criteria the GPU tests hold the kernels to (tests/test_gpu_head_primitives.py, tests/test_gpu_attention_f64.py,
-tests/test_gpu_norm_f64.py).  Plain torch on the CPU: no fixtures, no device code.
+"""Float64 restatements of the head, RoPE, pool, data, attention, norm, reduction, GEMM-epilogue and LoRA primitives of
+include/unirec_hip.h, and the element-wise criteria the GPU tests hold the kernels to (tests/test_gpu_head_primitives.py,
+tests/test_gpu_attention_f64.py, tests/test_gpu_norm_f64.py, tests/test_gpu_lora_f64.py).  Plain torch on the CPU: no fixtures, no device code.
 
 Every reference is written from the formula in the header comment of its entry point and is itself checked against an
 independent implementation in tests/test_ref64.py.  All functions take / return CPU tensors; inputs of any float dtype are
@@ -952,3 +952,242 @@ def gemm_epilogue_emulated(acc, alpha, bias, residual, aux, mutant=None):
     C = _bf(v)
     g = gelu(v if mutant == "gelu_unrounded" else C).to(f32)
     return C.to(F64), _bf(g).to(F64)
+
+
+# ---- LoRA adapter kernels (include/unirec_hip.h: ur_lora_project / ur_lora_reduce / ur_lora_bgrad, ur_gemm's masked epilogue,
+#      ur_rmsnorm_lora_fwd, ur_swiglu_lora_fwd; formulas: header comment of csrc/lora.hip) -------------------------------------------
+# X [M, W] bf16; U: list of [r, width_a]; V [M, r nad]; keep [nad, M, W] 0 / 1 or None; cols None (the adapters share all of X) or
+# [(c0, width)] (adapter a owns that range).  dtype=torch.float32 re-evaluates the same formula in float32 (the e32 yardstick);
+# absolute=True returns sum |term| (with |alpha|), the magnitude the accumulation term of the criteria scales with.
+def _lora_cols(X, nad, cols):
+    return [(0, X.shape[1])] * nad if cols is None else list(cols)
+
+
+def _lora_x(X, keep, a, c0, w, dtype):
+    xa = torch.as_tensor(X).detach().cpu()[:, c0:c0 + w].to(dtype)
+    return xa if keep is None else xa * torch.as_tensor(keep[a]).to(dtype)
+
+
+def _scaled(t, alpha, dtype, absolute):
+    return t * torch.as_tensor(abs(alpha) if absolute else alpha, dtype=dtype)
+
+
+def lora_project(X, U, keep=None, alpha=1.0, cols=None, dtype=F64, absolute=False):
+    """P[m, r a + j] = alpha * sum_w keep_a(m, w) X[m, c0_a + w] U_a[j, w]: [M, r nad]."""
+    outs = []
+    for a, (c0, w) in enumerate(_lora_cols(X, len(U), cols)):
+        xa, ua = _lora_x(X, keep, a, c0, w, dtype), U[a].detach().cpu().to(dtype)
+        outs.append(xa.abs() @ ua.abs().t() if absolute else xa @ ua.t())
+    return _scaled(torch.cat(outs, 1), alpha, dtype, absolute)
+
+
+def lora_reduce(X, V, rank, nad, keep=None, alpha=1.0, cols=None, transposed=False, dtype=F64, absolute=False):
+    """G_a[j, w] = alpha * sum_m V[m, r a + j] keep_a(m, w) X[m, c0_a + w], the dense output FLATTENED: entry a after entry a - 1, each
+    [r, width_a] or, transposed, [width_a, r]."""
+    v = torch.as_tensor(V).detach().cpu().to(dtype)
+    outs = []
+    for a, (c0, w) in enumerate(_lora_cols(X, nad, cols)):
+        xa, va = _lora_x(X, keep, a, c0, w, dtype), v[:, rank * a:rank * (a + 1)]
+        g = va.abs().t() @ xa.abs() if absolute else va.t() @ xa
+        outs.append((g.t() if transposed else g).reshape(-1))
+    return _scaled(torch.cat(outs), alpha, dtype, absolute)
+
+
+def lora_bgrad(dy, t, Bt, cols, alpha=1.0, dtype=F64, absolute=False):
+    """(tb [M, r nad] = alpha * dy_a B_a, dB flattened: entry a = dy_a^T t_a [width_a, r]) -- alpha scales tb only."""
+    r = Bt[0].shape[0]
+    tb = lora_project(dy, Bt, None, alpha, cols, dtype, absolute)
+    dB = lora_reduce(dy, t, r, len(cols), None, 1.0, cols, True, dtype, absolute)
+    return tb, dB
+
+
+def lora_masked_epilogue(R, S, tb, A, keep, p, rank, dtype=F64, absolute=False):
+    """C = R S^T + sum_a keep_a / (1 - p) * (tb_a A_a): [M, N]; A [r nad, N], adapter a = rows r a .. of A and columns r a .. of tb."""
+    c = lambda t: torch.as_tensor(t).detach().cpu().to(dtype)      # noqa: E731
+    ab = (lambda t: t.abs()) if absolute else (lambda t: t)
+    R, S, tb, A = ab(c(R)), ab(c(S)), ab(c(tb)), ab(c(A))
+    out = R @ S.t()
+    inv = torch.as_tensor(1.0, dtype=dtype) / torch.as_tensor(1.0 - p, dtype=dtype)
+    for a in range(A.shape[0] // rank):
+        out = out + c(keep[a]) * inv * (tb[:, rank * a:rank * (a + 1)] @ A[rank * a:rank * (a + 1)])
+    return out
+
+
+def rms_lora_t(h_saved, U, keep=None, alpha=1.0, dtype=F64, absolute=False):
+    """The LoRA half of ur_rmsnorm_lora_fwd.  rms_lora_kernel packs h = w * (x * rstd) to bf16 (pack_bf2) ONCE, stores those bits as H and
+    feeds the SAME packed registers (after drop_apply) to the MFMA as its column operand: t is the projection of the h BITS THE KERNEL WROTE,
+    t[m, 16 a + j] = alpha * sum_c keep_a(m, c) h[m, c] A_a[j, c].  h_saved: the kernel's H output (held to the RMSNorm criterion first)."""
+    return lora_project(h_saved, U, keep, alpha, None, dtype, absolute)
+
+
+def swiglu_lora_t(act_saved, U, keep=None, alpha=1.0, dtype=F64, absolute=False):
+    """The LoRA half of ur_swiglu_lora_fwd.  swiglu_lora_kernel packs act = silu(gate) * up to bf16 once, stores those bits as ACT and
+    feeds the same registers (after drop_apply) to the MFMA: t[m, j] = alpha * sum_c keep(m, c) act[m, c] A[j, c] over the act BITS WRITTEN."""
+    return lora_project(act_saved, [U], keep, alpha, None, dtype, absolute)
+
+
+def assert_lora_bf16(got, ref64, ref32, abs_terms, what=""):
+    """bf16 outputs t / tb / C.  EVERY element: |got - ref64| <= 1 bf16 ulp(ref64) + 2^-20 * abs_terms + 8 * |ref32 - ref64|, abs_terms =
+    |alpha| sum |term| of that element (the accumulation term of assert_gemm_c / assert_colsum_close).  Returns the worst error / bound."""
+    r, r32, a = _cpu64(ref64), _cpu64(ref32), _cpu64(abs_terms)
+    assert r.shape == r32.shape == a.shape, f"{what}: shapes {tuple(r.shape)} / {tuple(r32.shape)} / {tuple(a.shape)}"
+    assert torch.isfinite(r32).all(), f"{what}: the float32 re-evaluation of the reference is not finite"
+    return assert_within_ulps(got, r, 1, 2.0 ** -20 * a + 8.0 * (r32 - r).abs(), what)
+
+
+def assert_lora_exact(got, ref64, what=""):
+    """The exact family: every element of `got` (bf16 or f32) carries the bits of the exact value rounded ONCE to its type.  The exact value
+    zero has no sign (float64 torch returns -0.0 for a lone product -3 * 0; an accumulator that starts at +0 returns +0.0): both zeros are
+    written +0 before the bits are compared.  Returns 0."""
+    g = torch.as_tensor(got).detach().cpu()
+    want = _cpu64(ref64).to(torch.float32).to(g.dtype)             # integers below 2^24 scaled by a power of two: exact in float32
+    assert want.to(F64).ne(_cpu64(ref64)).sum() == 0 or g.dtype == torch.bfloat16, f"{what}: the exact value does not fit float32"
+    g, want = torch.where(g == 0, torch.zeros_like(g), g), torch.where(want == 0, torch.zeros_like(want), want)
+    assert g.shape == want.shape, f"{what}: shape {tuple(g.shape)} vs reference {tuple(want.shape)}"
+    view = torch.int16 if g.dtype == torch.bfloat16 else torch.int32
+    off = g.contiguous().view(view) != want.contiguous().view(view)
+    if off.any():
+        i = tuple(int(v) for v in off.nonzero()[0])
+        raise AssertionError(f"{what}: {int(off.sum())} of {off.numel()} elements differ from the correctly rounded exact value; first at index {i}: "
+                             f"got {g[i].item()!r}, exact {_cpu64(ref64)[i].item()!r} -> {want[i].item()!r}")
+    return 0.0
+
+
+LORA_MUTANTS = ("tail_chunk_skipped", "plane_of_block", "pair_order", "no_drop_scale", "row0_ignored", "half_rank_neighbour",
+                "last_token_block_dropped", "col0_ignored")
+_PAIR_ELEM = (0, 2, 4, 6, 1, 3, 5, 7)
+
+
+def _acc32(parts, order):
+    """f32 sum of a list of f32 tensors: 'chunks' = one after the other, 'tree' = pairwise"""
+    parts = list(parts)
+    if not parts:
+        return None
+    if order == "chunks":
+        s = parts[0]
+        for t in parts[1:]:
+            s = s + t
+        return s
+    while len(parts) > 1:
+        parts = [parts[i] + parts[i + 1] if i + 1 < len(parts) else parts[i] for i in range(0, len(parts), 2)]
+    return parts[0]
+
+
+def lora_mutant_applies(kind, c, mutant):
+    """whether `mutant` changes what lora_emulated computes for launch `kind` of case c (a mutant that is invisible at a shape needs another)"""
+    masked, cols = c.get("keep") is not None, c.get("cols")
+    r, nad, M = c["rank"], c["nad"], c["M"]
+    if mutant == "tail_chunk_skipped":
+        return kind in ("project", "bgrad") and any(w % 128 for _, w in _lora_cols(c["X"], nad, cols))
+    if mutant == "plane_of_block":
+        return kind in ("project", "reduce", "epilogue") and masked and r >= 32 and nad >= 2
+    if mutant == "pair_order":
+        return masked
+    if mutant == "no_drop_scale":
+        return kind == "epilogue"
+    if mutant == "row0_ignored":
+        return masked and c["row0"] != 0
+    if mutant == "half_rank_neighbour":
+        return kind == "project" and masked and r == 8 and nad >= 2
+    if mutant == "last_token_block_dropped":
+        return kind != "epilogue" and M % 128 != 0
+    if mutant == "col0_ignored":
+        return kind in ("project", "reduce", "bgrad") and cols is not None and any(c0 for c0, _ in cols)
+    raise AssertionError(mutant)
+
+
+def lora_emulated(kind, c, order="chunks", mutant=None):
+    """The kernels' arithmetic restated in float32 torch: exact bf16 x bf16 products, float32 partial sums over pieces of the reduction axis
+    added in `order` ('chunks': pieces of 128 columns / tokens one after the other, the register-staged kernels' own order; 'tree': pieces of
+    32 summed pairwise), ONE rounding to bf16 for t / tb / C.  kind: 'project' -> P; 'reduce' -> flattened G (c['transposed']); 'bgrad' ->
+    (tb, dB); 'epilogue' -> C (c of lora_cases.epilogue_case).  Returns float64 tensors.
+    mutant: one of LORA_MUTANTS -- a DELIBERATE bug, for tests/test_ref64.py to show that the criteria bite:
+      tail_chunk_skipped        the columns past the last full 128 are ignored (project, tb of bgrad)
+      plane_of_block            16-row block b of a rank-32 / 64 launch uses plane b (mod nad) instead of plane b / NB
+      pair_order                flag bit i of a byte is applied to element c + i instead of c + 2 i (i < 4) / c + 2 (i - 4) + 1
+      no_drop_scale             the masked epilogue adds keep * (tb A) without 1 / (1 - p)
+      row0_ignored              the planes are drawn for rows 0 .. M - 1 instead of row0 ..
+      half_rank_neighbour       rank 8: the upper half of adapter a's block is not zero but live, and its 16-wide result lands on adapter
+                                a + 1's columns -- adapter a + 1's t is computed under plane a
+      last_token_block_dropped  the rows of the last, partly filled 128-token block are not computed (row outputs stay 0, sums lose them)
+      col0_ignored              an adapter's column range starts at column 0"""
+    assert mutant is None or mutant in LORA_MUTANTS, mutant
+    assert order in ("chunks", "tree")
+    f32 = torch.float32
+    step = 128 if order == "chunks" else 32
+    rank, nad, M = c["rank"], c["nad"], c["M"]
+    keep = c.get("keep")
+    if keep is not None:
+        if mutant == "row0_ignored":
+            import numpy as np
+            from oracle import dropout_ref
+            keep = torch.from_numpy(dropout_ref.lora_keep(c["seed"], c["p"], M, keep.shape[-1], nad, 0).astype(np.float64))
+        if mutant == "pair_order":
+            W_ = keep.shape[-1]
+            idx = torch.arange(W_)
+            keep = keep[..., (idx // 8) * 8 + torch.tensor(_PAIR_ELEM)[idx % 8]]
+        keep = keep.to(f32)
+    mlive = M if mutant != "last_token_block_dropped" else (M // 128) * 128
+
+    def plane(a, nb):
+        if keep is None:
+            return None
+        if mutant == "plane_of_block":
+            return keep[(a * (rank // 16) + nb) % nad]
+        if mutant == "half_rank_neighbour" and a > 0:
+            return keep[a - 1]
+        return keep[a]
+
+    def blocks(a):             # (first rank row, rows, plane) of adapter a's 16-row blocks (one 8-row block at rank 8)
+        return [(16 * nb, min(16, rank), plane(a, nb)) for nb in range(max(1, rank // 16))]
+
+    def xcols(X, a, cols_):
+        c0, w = _lora_cols(X, nad, cols_)[a]
+        if mutant == "col0_ignored":
+            c0 = 0
+        return X.detach().cpu()[:, c0:c0 + w].to(f32), w
+
+    def project(X, U, alpha, cols_):
+        out = torch.zeros(M, rank * nad, dtype=f32)
+        for a in range(nad):
+            xa, w = xcols(X, a, cols_)
+            wl = (w // 128) * 128 if mutant == "tail_chunk_skipped" else w
+            for j0, nj, kp in blocks(a):
+                xm = xa if kp is None else xa * kp
+                u = U[a].detach().cpu().to(f32)[j0:j0 + nj]
+                s = _acc32([xm[:, k:min(k + step, wl)] @ u[:, k:min(k + step, wl)].t() for k in range(0, wl, step)], order)
+                if s is not None:
+                    out[:mlive, rank * a + j0:rank * a + j0 + nj] = (s * torch.tensor(alpha, dtype=f32))[:mlive]
+        return _bf(out).to(F64)
+
+    def reduce(X, V, alpha, cols_, transposed):
+        v = V.detach().cpu().to(f32)
+        outs = []
+        for a in range(nad):
+            xa, w = xcols(X, a, cols_)
+            g = torch.zeros(rank, w, dtype=f32)
+            for j0, nj, kp in blocks(a):
+                xm = xa if kp is None else xa * kp
+                va = v[:, rank * a + j0:rank * a + j0 + nj]
+                s = _acc32([va[t0:min(t0 + step, mlive)].t() @ xm[t0:min(t0 + step, mlive)] for t0 in range(0, mlive, step)], order)
+                if s is not None:
+                    g[j0:j0 + nj] = s * torch.tensor(alpha, dtype=f32)
+            outs.append((g.t() if transposed else g).reshape(-1))
+        return torch.cat(outs).to(F64)
+
+    if kind == "project":
+        return project(c["X"], c["U"], c["alpha"], c["cols"])
+    if kind == "reduce":
+        return reduce(c["X"], c["V"], c["alpha"], c["cols"], bool(c.get("transposed", c["cols"] is not None)))
+    if kind == "bgrad":
+        return project(c["X"], c["U"], c["alpha"], c["cols"]), reduce(c["X"], c["V"], 1.0, c["cols"], True)
+    assert kind == "epilogue", kind
+    R, S, tb, A = (c[k].detach().cpu().to(f32) for k in ("R", "S", "tb", "A"))
+    K = R.shape[1]
+    acc = _acc32([R[:, k:k + step] @ S[:, k:k + step].t() for k in range(0, K, step)], order)
+    inv = torch.tensor(1.0, dtype=f32) if mutant == "no_drop_scale" else torch.tensor(1.0, dtype=f32) / torch.tensor(1.0 - c["p"], dtype=f32)
+    for a in range(nad):
+        for j0, nj, kp in blocks(a):
+            sl = slice(rank * a + j0, rank * a + j0 + nj)
+            acc = acc + kp * ((tb[:, sl] @ A[sl]) * inv)
+    return _bf(acc).to(F64)

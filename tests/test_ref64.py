@@ -775,3 +775,142 @@ def test_margins_beyond_one_ulp_are_what_float32_costs():
     own = float(ref64.bf16_ulp(o64[0, 3]) + 2.0 ** -18 * o64[0].abs().max())
     print(f"out of the row whose one kept element cancels: reference {float(o64[0, 3]):.3e}, float32 off by {err0:.3e}, 1 ulp + 2^-18 of the masked row {own:.3e}")
     assert err0 > own
+
+
+# ---- LoRA kernels: the criteria accept two float32 summation orders and reject every mutant ---------------------------------------------
+from tests import lora_cases  # noqa: E402
+
+
+def _lora_refs(kind, c):
+    """[(name, is_bf16, ref(**kw))] of launch `kind` of case c"""
+    if kind == "project":
+        return [("P", True, lambda **k: ref64.lora_project(c["X"], c["U"], c["keep"], c["alpha"], c["cols"], **k))]
+    if kind == "reduce":
+        tr = bool(c.get("transposed", False))
+        return [("G", False, lambda **k: ref64.lora_reduce(c["X"], c["V"], c["rank"], c["nad"], c["keep"], c["alpha"], c["cols"], tr, **k))]
+    if kind == "bgrad":
+        return [("tb", True, lambda **k: ref64.lora_bgrad(c["X"], c["V"], c["U"], c["cols"], c["alpha"], **k)[0]),
+                ("dB", False, lambda **k: ref64.lora_bgrad(c["X"], c["V"], c["U"], c["cols"], c["alpha"], **k)[1])]
+    return [("C", True, lambda **k: ref64.lora_masked_epilogue(c["R"], c["S"], c["tb"], c["A"], c["keep"], c["p"], c["rank"], **k))]
+
+
+def _lora_hold(kind, c, outs, refs=None):
+    """applies the GPU test's criterion to the emulated outputs; raises AssertionError like the GPU test would"""
+    outs = outs if isinstance(outs, tuple) else (outs,)
+    worst = 0.0
+    for (name, is_bf16, ref), got in zip(refs or _lora_refs(kind, c), outs):
+        got = got.to(BF16) if is_bf16 else got.to(torch.float32)
+        if c["family"] == "exact":
+            ref64.assert_lora_exact(got, ref(), name)
+        elif is_bf16:
+            worst = max(worst, ref64.assert_lora_bf16(got, ref(), ref(dtype=torch.float32), ref(absolute=True), name))
+        else:
+            worst = max(worst, ref64.assert_colsum_close(got, ref(), ref(dtype=torch.float32), ref(absolute=True), name))
+    return worst
+
+
+def _lora_sample(cases, every):
+    """every `every`-th launch of a path's list, both families of it (the lists are the GPU tests' own)"""
+    cases = list(cases)
+    return [c for i, c in enumerate(cases) if (i // 2) % every == 0]
+
+
+def _lora_launches():
+    L = lora_cases
+    out = []
+    for rank in L.RANKS:
+        for nad in (1, 2, 3, 4):
+            out += [("project", c) for c in _lora_sample(L.project_staged(rank, nad), 7)]
+            out += [("reduce", c) for c in _lora_sample(L.reduce_staged(rank, nad), 7)]
+        out += [("reduce", c) for c in L.reduce_ranges(rank)]
+        out += [("project", c) for c in L.project_ranges(rank)]
+        out += [("bgrad", c) for c in L.bgrad_staged(rank)]
+        for nad in (1, 2, 3):
+            out += [("epilogue", c) for c in L.epilogue_cases(rank, nad)]
+    out += [("project", c) for c in _lora_sample(L.project_ring(), 3)]
+    for nad in (1, 2, 3, 4):
+        out += [("reduce", c) for c in _lora_sample(L.reduce_ring(nad), 3)]
+    out += [("reduce", c) for c in L.reduce_ring_ranges()]
+    out += [("bgrad", c) for c in L.bgrad_ring_512()]
+    out += [("bgrad", c) for c in L.bgrad_ring_1024(8)]                  # (8 CUs: the same launch shape at a row count the CPU affords)
+    return out
+
+
+LORA_LAUNCHES = _lora_launches()
+
+
+def test_lora_references_against_einsum():
+    """the float64 references against an independent einsum evaluation over explicit per-adapter tensors"""
+    c = lora_cases.case("random", 37, 136, 32, 3, p=0.3, seed=9, row0=5)
+    x, keep = c["X"].double(), c["keep"]
+    U = torch.stack([u.double() for u in c["U"]])
+    want = c["alpha"] * torch.einsum("amw,ajw->maj", x[None] * keep, U).reshape(37, 96)
+    assert torch.allclose(ref64.lora_project(c["X"], c["U"], keep, c["alpha"]), want, rtol=1e-13, atol=1e-13)
+    V = c["V"].double().reshape(37, 3, 32)
+    want = c["alpha"] * torch.einsum("maj,amw->ajw", V, x[None] * keep)
+    assert torch.allclose(ref64.lora_reduce(c["X"], c["V"], 32, 3, keep, c["alpha"]), want.reshape(-1), rtol=1e-13, atol=1e-13)
+    assert torch.allclose(ref64.lora_reduce(c["X"], c["V"], 32, 3, keep, c["alpha"], transposed=True), want.transpose(1, 2).reshape(-1), rtol=1e-13, atol=1e-13)
+    cols = [(8, 72), (80, 56)]
+    c = lora_cases.case("random", 21, 136, 8, 2, cols=cols, seed=3)
+    tb, dB = ref64.lora_bgrad(c["X"], c["V"], c["U"], cols, 0.5)
+    x = c["X"].double()
+    for a, (c0, w) in enumerate(cols):
+        assert torch.allclose(tb[:, 8 * a:8 * a + 8], 0.5 * torch.einsum("mw,jw->mj", x[:, c0:c0 + w], c["U"][a].double()), rtol=1e-13, atol=1e-13)
+    want = torch.cat([torch.einsum("mw,mj->wj", x[:, c0:c0 + w], c["V"].double()[:, 8 * a:8 * a + 8]).reshape(-1) for a, (c0, w) in enumerate(cols)])
+    assert torch.allclose(dB, want, rtol=1e-13, atol=1e-13)
+    e = lora_cases.epilogue_case("random", 9, 136, 64, 16, 2, 0.1, seed=4)
+    want = e["R"].double() @ e["S"].double().t()
+    for a in range(2):
+        want = want + e["keep"][a] / 0.9 * torch.einsum("mj,jn->mn", e["tb"].double()[:, 16 * a:16 * a + 16], e["A"].double()[16 * a:16 * a + 16])
+    assert torch.allclose(ref64.lora_masked_epilogue(e["R"], e["S"], e["tb"], e["A"], e["keep"], 0.1, 16), want, rtol=1e-13, atol=1e-13)
+
+
+def test_lora_criteria_accept_both_summation_orders():
+    worst = {}
+    for kind, c in LORA_LAUNCHES:
+        for order in ("chunks", "tree"):
+            worst[kind] = max(worst.get(kind, 0.0), _lora_hold(kind, c, ref64.lora_emulated(kind, c, order)))
+    print("worst error / bound of the float32 emulations:", worst)
+    assert set(worst) == {"project", "reduce", "bgrad", "epilogue"}
+
+
+@pytest.mark.parametrize("mutant", ref64.LORA_MUTANTS)
+def test_lora_criteria_reject_every_mutant(mutant):
+    """wherever a mutant applies -- every launch kind it can touch, in BOTH families -- the criterion of the GPU test fails"""
+    hit = set()
+    for kind, c in LORA_LAUNCHES:
+        if not ref64.lora_mutant_applies(kind, c, mutant):
+            continue
+        with pytest.raises(AssertionError):
+            _lora_hold(kind, c, ref64.lora_emulated(kind, c, "chunks", mutant))
+            print(f"NOT rejected: {mutant} at {kind} {c['family']} r{c['rank']} nad{c['nad']} M{c['M']} p{c['p']} cols{c.get('cols')}")
+        hit.add((kind, c["family"]))
+    kinds = {"tail_chunk_skipped": ("project", "bgrad"), "plane_of_block": ("project", "reduce", "epilogue"),
+             "pair_order": ("project", "reduce", "epilogue"), "no_drop_scale": ("epilogue",), "row0_ignored": ("project", "reduce", "epilogue"),
+             "half_rank_neighbour": ("project",), "last_token_block_dropped": ("project", "reduce", "bgrad"),
+             "col0_ignored": ("project", "reduce", "bgrad")}[mutant]
+    assert hit == {(k, f) for k in kinds for f in lora_cases.FAMILIES}, hit
+
+
+def test_lora_fused_halves_project_the_saved_bits():
+    """rms_lora_t / swiglu_lora_t are the projection of the SAVED bf16 operand: an emulation that projects the unrounded float32 h instead
+    differs from them, while the emulation over the saved bits meets the criterion in both orders"""
+    M, D, nad = 65, 1024, 3
+    c = lora_cases.fused_case(M, D, nad, 0.3, seed=77, row0=3)
+    x, w = norm_cases.rows(M, D, 5), norm_cases.norm_weight(D, 6)
+    h32 = ref64.rmsnorm_fwd(x, w, 1e-6, dtype=torch.float32)[0]
+    c["X"], c["V"] = h32.to(BF16), None
+    refs = [("t", True, lambda **k: ref64.rms_lora_t(c["X"], c["U"], c["keep"], c["alpha"], **k))]
+    for order in ("chunks", "tree"):
+        assert _lora_hold("project", c, ref64.lora_emulated("project", c, order), refs) <= 1.0
+    for mutant in ("pair_order", "row0_ignored", "last_token_block_dropped"):
+        with pytest.raises(AssertionError):
+            _lora_hold("project", c, ref64.lora_emulated("project", c, "chunks", mutant), refs)
+    g = lora_cases.values("random", (M, 256), lora_cases.gen(8), scale=2.0)
+    act = ref64.swiglu_fwd(g[:, :128], g[:, 128:]).to(BF16)
+    s = lora_cases.fused_case(M, 128, 1, 0.1, seed=78)
+    s["X"] = act
+    refs = [("t", True, lambda **k: ref64.swiglu_lora_t(s["X"], s["U"][0], s["keep"], s["alpha"], **k))]
+    assert _lora_hold("project", s, ref64.lora_emulated("project", s, "tree"), refs) <= 1.0
+    with pytest.raises(AssertionError):
+        _lora_hold("project", s, ref64.lora_emulated("project", s, "chunks", "pair_order"), refs)

@@ -451,9 +451,10 @@ def lora_project(X, U, cols=None, alpha=1.0, bits=None, out=None):
     return out
 
 
-@_stream_family("swiglu_lora", lambda r, gu, I, U, alpha=1.0, bits=None: _nb(gu) + _nb(*r) + (_nb(bits) if bits is not None else 0))
-def swiglu_lora_fwd(gu, I, U, alpha=1.0, bits=None):
-    """SwiGLU forward + the down_proj adapter's down projection in one pass over gu [M, 2I]: -> (act bf16 [M, I], t bf16 [M, 16])."""
+@_stream_family("swiglu_lora", lambda r, gu, I, U, alpha=1.0, bits=None, t_out=None: _nb(gu) + _nb(*r) + (_nb(bits) if bits is not None else 0))
+def swiglu_lora_fwd(gu, I, U, alpha=1.0, bits=None, t_out=None):
+    """SwiGLU forward + the down_proj adapter's down projection in one pass over gu [M, 2I]: -> (act bf16 [M, I], t bf16 [M, 16]).
+    t_out: write t there (a bf16 [M, 16] view; its row stride may be wider)."""
     lib = _lib.load()
     _need(gu, BF16, "gu")
     M = gu.shape[0]
@@ -462,16 +463,17 @@ def swiglu_lora_fwd(gu, I, U, alpha=1.0, bits=None):
     if U.dtype != BF16 or U.shape[0] != 16 or U.stride(1) != 1 or U.shape[1] != I:
         raise ValueError("swiglu_lora_fwd: U must be bf16 [16, I]")
     a.U[0], a.ldu[0] = U.data_ptr(), U.stride(0)
-    t = torch.empty((M, 16), dtype=BF16, device=gu.device)
+    t = torch.empty((M, 16), dtype=BF16, device=gu.device) if t_out is None else t_out
     a.P, a.ldp = t.data_ptr(), t.stride(0)
     check(lib.ur_swiglu_lora_fwd(gu.data_ptr(), act.data_ptr(), M, I, ctypes.byref(a), _stream()), "ur_swiglu_lora_fwd")
     return act, t
 
 
-@_stream_family("rms_lora", lambda r, x, w, eps, U, alpha=1.0, bits=None: _nb(x) + _nb(*r) + (_nb(bits) if bits is not None else 0))
-def rmsnorm_lora_fwd(x, w, eps, U, alpha=1.0, bits=None):
+@_stream_family("rms_lora", lambda r, x, w, eps, U, alpha=1.0, bits=None, t_out=None: _nb(x) + _nb(*r) + (_nb(bits) if bits is not None else 0))
+def rmsnorm_lora_fwd(x, w, eps, U, alpha=1.0, bits=None, t_out=None):
     """RMSNorm forward + the down projection of the 2 or 3 adapters that read the normalised activation, one pass over x:
-    -> (h bf16 like x, rstd f32 [M], t bf16 [M, 16 len(U)]).  D must be 1024."""
+    -> (h bf16 like x, rstd f32 [M], t bf16 [M, 16 len(U)]).  D must be 1024.  t_out: write t there (a bf16 [M, 16 len(U)] view; its
+    row stride may be wider)."""
     lib = _lib.load()
     _need(x, BF16, "x")
     D = x.shape[-1]
@@ -483,7 +485,7 @@ def rmsnorm_lora_fwd(x, w, eps, U, alpha=1.0, bits=None):
         if u.dtype != BF16 or u.shape[0] != 16 or u.stride(1) != 1 or u.shape[1] != D:
             raise ValueError("rmsnorm_lora_fwd: U[a] must be bf16 [16, D]")
         a.U[e], a.ldu[e] = u.data_ptr(), u.stride(0)
-    t = torch.empty((M, 16 * len(U)), dtype=BF16, device=x.device)
+    t = torch.empty((M, 16 * len(U)), dtype=BF16, device=x.device) if t_out is None else t_out
     a.P, a.ldp = t.data_ptr(), t.stride(0)
     check(lib.ur_rmsnorm_lora_fwd(x.data_ptr(), w.data_ptr(), out.data_ptr(), rstd.data_ptr(), M, D, eps, ctypes.byref(a), _stream()),
           "ur_rmsnorm_lora_fwd")
