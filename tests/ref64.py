@@ -1,6 +1,7 @@
 """Float64 restatements of the head, RoPE, pool, data, attention, norm, reduction, GEMM-epilogue and LoRA primitives of
 include/unirec_hip.h, and the element-wise criteria the GPU tests hold the kernels to (tests/test_gpu_head_primitives.py,
-tests/test_gpu_attention_f64.py, tests/test_gpu_norm_f64.py, tests/test_gpu_lora_f64.py).  Plain torch on the CPU: no fixtures, no device code.
+tests/test_gpu_attention_f64.py, tests/test_gpu_norm_f64.py, tests/test_gpu_lora_f64.py, tests/test_gpu_gemm_f64.py).  Plain torch: no fixtures, no device code
+(the fused-GEMM-epilogue section at the end runs on its inputs' device, everything else on the CPU).
 
 Every reference is written from the formula in the header comment of its entry point and is itself checked against an
 independent implementation in tests/test_ref64.py.  All functions take / return CPU tensors; inputs of any float dtype are
@@ -1003,7 +1004,7 @@ def lora_bgrad(dy, t, Bt, cols, alpha=1.0, dtype=F64, absolute=False):
 
 def lora_masked_epilogue(R, S, tb, A, keep, p, rank, dtype=F64, absolute=False):
     """C = R S^T + sum_a keep_a / (1 - p) * (tb_a A_a): [M, N]; A [r nad, N], adapter a = rows r a .. of A and columns r a .. of tb."""
-    c = lambda t: torch.as_tensor(t).detach().cpu().to(dtype)      # noqa: E731
+    c = lambda t: torch.as_tensor(t).detach().to(dtype)      # noqa: E731    (on the inputs' device: tests/test_gpu_gemm_f64.py keeps them on the GPU)
     ab = (lambda t: t.abs()) if absolute else (lambda t: t)
     R, S, tb, A = ab(c(R)), ab(c(S)), ab(c(tb)), ab(c(A))
     out = R @ S.t()
@@ -1191,3 +1192,190 @@ def lora_emulated(kind, c, order="chunks", mutant=None):
             sl = slice(rank * a + j0, rank * a + j0 + nj)
             acc = acc + kp * ((tb[:, sl] @ A[sl]) * inv)
     return _bf(acc).to(F64)
+
+
+# ---- the decoder's fused GEMM epilogues (csrc/gemm_pers.hip EPI 3 / 4 / 1, gemm_body.hip.h EPI 1 / 2; ur_gemm_args.qkr_*, swp_*, swiglu_*) ---
+# Device-agnostic: these run on whatever device their inputs live on (the GPU tests keep 8 .. 35 M element outputs there); every
+# product acc is given in the NATURAL feature order (the paired weight-row order of the launches is the tests' business).
+def ulp_ratio(got, ref64, ulps=1, floor=0.0):
+    """(worst |got - ref| / (ulps * bf16_ulp(ref) + floor), number of elements above 1, number of non-finite outputs) without leaving the
+    inputs' device -- assert_within_ulps' criterion for outputs too large to walk on the CPU.  0 / 0 counts as 0."""
+    g, r = got.to(F64), ref64.to(F64)
+    assert g.shape == r.shape, f"shape {tuple(g.shape)} vs reference {tuple(r.shape)}"
+    assert torch.isfinite(r).all(), "the reference itself is not finite"
+    err = (g - r).abs()
+    bound = ulps * bf16_ulp(r) + torch.as_tensor(floor, dtype=F64, device=r.device)
+    bad = ~torch.isfinite(g)
+    ratio = torch.where(bad | (err == 0), torch.zeros_like(err), err / bound)
+    return float(ratio.max()) if ratio.numel() else 0.0, int((ratio > 1.0).sum()), int(bad.sum())
+
+
+def assert_ulp_ratio(got, ref64, ulps=1, floor=0.0, what=""):
+    """assert_within_ulps on the inputs' device: EVERY element finite and within ulps * bf16_ulp(ref) + floor.  Returns the worst ratio."""
+    worst, off, bad = ulp_ratio(got, ref64, ulps, floor)
+    assert bad == 0, f"{what}: {bad} non-finite outputs"
+    if off:
+        g, r = got.to(F64), ref64.to(F64)
+        exc = ((g - r).abs() / (ulps * bf16_ulp(r) + torch.as_tensor(floor, dtype=F64, device=r.device)))
+        i = tuple(int(v) for v in torch.unravel_index(exc.argmax(), exc.shape))
+        raise AssertionError(f"{what}: {off} of {g.numel()} elements exceed {ulps} bf16 ulp + floor; worst at index {i}: got {g[i].item()!r}, "
+                             f"reference {r[i].item()!r}, error {abs(g[i].item() - r[i].item()):.3e} = {worst:.2f} x the bound")
+    return worst
+
+
+def rope_table_f32(S, head_dim, theta):
+    """The table as ur_rope_table forms it (qwen_ops.hip): inv_freq and the ANGLE pos * inv_freq in float32, cos / sin of that float32 angle
+    correctly rounded.  The angle's rounding (half an ulp of up to 4095 rad: 1.2e-4) is what makes table row p + 16 differ from table
+    row p advanced by table row 16."""
+    f32 = torch.float32
+    half = head_dim // 2
+    inv = 1.0 / torch.pow(torch.tensor(theta, dtype=f32), (2 * torch.arange(half)).to(f32) / float(2 * half))
+    ang = (torch.arange(S).to(f32)[:, None] * inv[None, :]).to(F64)
+    return torch.cos(ang).to(f32), torch.sin(ang).to(f32)
+
+
+def qkrope_epilogue(acc, qw, kw, cos_tab, sin_tab, S, nq_cols, nk_cols, eps, dtype=F64):
+    """q/k-norm + RoPE as the epilogue of the merged q|k|v launch (ur_gemm_args.qkr_*; Qwen3Attention): acc [M, N] = the product, columns
+    q heads | k heads | v in natural feature order, 128-wide heads, token m at position m % S.  Per head rstd = 1 / sqrt(mean(acc^2) + eps),
+    x = acc * rstd * w, rotate-half RoPE with the table rows AS GIVEN (qknorm_rope_fwd's formula); v = the plain projection.
+    Returns (q_r [M, nq_cols], k_r [M, nk_cols], v [M, N - nq_cols - nk_cols], rstd [M, (nq_cols + nk_cols) / 128])."""
+    hd = 128
+    nq, nk = nq_cols // hd, nk_cols // hd
+    M = acc.shape[0]
+    a = acc.to(dtype)
+    x = a[:, :nq_cols + nk_cols].reshape(M, nq + nk, hd)
+    rstd = torch.rsqrt((x * x).mean(-1) + eps)
+    out = qknorm_rope_fwd(a, qw, kw, cos_tab, sin_tab, S, nq, nk, hd, eps, dtype).reshape(M, nq_cols + nk_cols)
+    return out[:, :nq_cols], out[:, nq_cols:], a[:, nq_cols + nk_cols:], rstd
+
+
+def swiglu_bwd_epilogue(dact64, gate, up):
+    """SwiGLU backward as the epilogue of the down-projection's dX launch (swiglu_bwd=): swiglu_bwd on the UNROUNDED d(act) -- the
+    epilogue keeps the product in f32 and never rounds it to bf16, which the stand-alone kernel's input is.  (dgate, dup)."""
+    return swiglu_bwd(dact64.to(F64), gate, up)
+
+
+def _bf16_of_exact(acc):
+    """bf16 of a product that float32 holds exactly (|acc| < 2^24 integers): ONE rounding"""
+    a32 = acc.to(torch.float32)
+    assert bool((a32.to(F64) == acc.to(F64)).all()), "the product is not exact in float32: bf16 through float32 would round twice"
+    return a32.to(torch.bfloat16)
+
+
+def swiglu_fwd_epilogue(acc_gate_up):
+    """SwiGLU forward as the epilogue of the merged gate|up launch (swiglu_paired=) and of the up projection (swiglu_fwd=): acc [M, 2 I] =
+    the exact product, gate | up.  Returns (gu = bf16(acc) -- what the launch stores for the backward --, act = silu(gate BITS) * (up
+    BITS) in float64)."""
+    gu = _bf16_of_exact(acc_gate_up)
+    I = gu.shape[1] // 2
+    return gu, swiglu_fwd(gu[:, :I], gu[:, I:])
+
+
+GEMM_EPI_MUTANTS = ("pos_not_wrapped", "step80_as_16", "rstd_neighbour_head", "k_weight_on_q", "eps_dropped", "partner_sign",
+                    "dgate_from_rounded_dact", "dup_uses_sigmoid_only", "gate_up_halves_swapped", "masked_term_unscaled")
+
+
+def qkrope_emulated(acc, qw, kw, cos_tab, sin_tab, S, nq_cols, nk_cols, eps, mutant=None, recurrence=True, rounded=True):
+    """EPI 3 of csrc/gemm_pers.hip in float32 torch, outputs rounded to bf16 (rstd stays f32): the same four outputs as qkrope_epilogue, in
+    float64.  Per 256-row tile and row-in-16 l15 the kernel loads ONE table row per wave group wr (position pos0 + 64 wr + l15, pos0 =
+    m0 % S) and advances cos / sin by the angle-addition theorem with table rows 16 and 80: + 16 three times, + 80 (from row block 3 of
+    the first row half to block 0 of the second), + 16 three times.  rstd = f32 rsqrt(sum / 128 + eps), x = (acc * rstd) * w,
+    o = xa c - xb s | xb c + xa s.  recurrence=False reads every row's own table row instead (what the stand-alone kernel does);
+    rounded=False returns q_r / k_r BEFORE the rounding to bf16 (the e32 yardstick of qkrope_bound: what float32 costs, not what bf16 does).
+    mutant (DELIBERATE bugs, tests/test_ref64.py): pos_not_wrapped (pos0 = m0: the tables must then have M rows), step80_as_16,
+    rstd_neighbour_head (the two heads of a 256-column tile swap their row constants), k_weight_on_q, eps_dropped, partner_sign."""
+    assert mutant in (None, "pos_not_wrapped", "step80_as_16", "rstd_neighbour_head", "k_weight_on_q", "eps_dropped", "partner_sign"), mutant
+    f32 = torch.float32
+    hd = 128
+    nh = (nq_cols + nk_cols) // hd
+    nq = nq_cols // hd
+    M = acc.shape[0]
+    assert M % 256 == 0 and S % 256 == 0 and nq_cols % 256 == 0 and nk_cols % 256 == 0
+    dev = acc.device
+    a = acc.to(f32)
+    x = a[:, :nq_cols + nk_cols].reshape(M, nh, hd)
+    ct, st = cos_tab.to(f32), sin_tab.to(f32)
+    # ---- cos / sin of every row, as the kernel gets them
+    m = torch.arange(M, device=dev)
+    m0 = (m // 256) * 256
+    pos0 = m0 if mutant == "pos_not_wrapped" else m0 % S
+    r = m % 256
+    if recurrence:
+        wr, l15, j = (r >> 6) & 1, r & 15, (r >> 7) * 4 + ((r >> 4) & 3)
+        base = pos0 + wr * 64 + l15
+        c, s = ct[base], st[base]                                   # [M, 64]: the row the lane loaded
+        for step in range(7):
+            t = 16 if (step != 3 or mutant == "step80_as_16") else 80
+            dc, ds = ct[t][None, :], st[t][None, :]
+            cn, sn = c * dc - s * ds, s * dc + c * ds
+            live = (j > step)[:, None]
+            c, s = torch.where(live, cn, c), torch.where(live, sn, s)
+    else:
+        c, s = ct[pos0 + r], st[pos0 + r]
+    # ---- row constants
+    ss = (x * x).sum(-1)
+    rs = torch.rsqrt(ss * torch.tensor(1.0 / 128.0, dtype=f32) + (0.0 if mutant == "eps_dropped" else torch.tensor(eps, dtype=f32)))
+    rs_used = rs.reshape(M, nh // 2, 2).flip(-1).reshape(M, nh) if mutant == "rstd_neighbour_head" else rs
+    w = torch.cat([(kw if mutant == "k_weight_on_q" else qw).to(f32)[None].expand(nq, -1), kw.to(f32)[None].expand(nh - nq, -1)], 0)
+    xn = (x * rs_used[..., None]) * w[None]
+    xa, xb = xn[..., :64], xn[..., 64:]
+    c, s = c[:, None, :], s[:, None, :]
+    o0 = xa * c - xb * s
+    o1 = (xb * c - xa * s) if mutant == "partner_sign" else (xb * c + xa * s)
+    out = torch.cat([o0, o1], -1)
+    out = (_bf(out) if rounded else out).to(F64).reshape(M, nq_cols + nk_cols)
+    return out[:, :nq_cols], out[:, nq_cols:], _bf(a[:, nq_cols + nk_cols:]).to(F64), rs_used.to(F64)
+
+
+def _sigmoid32(g):
+    return 1.0 / (1.0 + torch.exp(-g))
+
+
+def swiglu_bwd_epilogue_emulated(acc, gate, up, masked=None, mutant=None):
+    """EPI 1 (both GEMM kernels) in float32 torch: d = acc (+ keep / (1 - p) * (tb A), masked = (tb, A [r, N], keep [M, N], p)) stays f32;
+    dgate = d u (s (1 + g (1 - s))), dup = d (g s), each rounded once to bf16.  Returns (dgate, dup) in float64.
+    mutant: dgate_from_rounded_dact (d is rounded to bf16 first: the two-kernel path, a LEGITIMATE result), dup_uses_sigmoid_only
+    (dup = d s), gate_up_halves_swapped (the gate is read from the up half and the up from the gate half), masked_term_unscaled (the
+    1 / (1 - p) factor is lost)."""
+    assert mutant in (None, "dgate_from_rounded_dact", "dup_uses_sigmoid_only", "gate_up_halves_swapped", "masked_term_unscaled"), mutant
+    f32 = torch.float32
+    d = acc.to(f32)
+    if masked is not None:
+        tb, A, keep, p = masked
+        inv = torch.tensor(1.0, dtype=f32) if mutant == "masked_term_unscaled" else torch.tensor(1.0, dtype=f32) / torch.tensor(1.0 - p, dtype=f32)
+        d = d + keep.to(f32) * ((tb.to(f32) @ A.to(f32)) * inv)
+    if mutant == "dgate_from_rounded_dact":
+        d = _bf(d).to(f32)
+    g, u = gate.to(f32), up.to(f32)
+    if mutant == "gate_up_halves_swapped":
+        g, u = u, g
+    sg = _sigmoid32(g)
+    dup = d * sg if mutant == "dup_uses_sigmoid_only" else d * (g * sg)
+    dgate = d * u * (sg * (1.0 + g * (1.0 - sg)))
+    return _bf(dgate).to(F64), _bf(dup).to(F64)
+
+
+def swiglu_fwd_epilogue_emulated(acc_gate_up, mutant=None):
+    """EPI 4 / the generic swiglu_fwd= epilogue in float32 torch: gu = bf16(acc), act = bf16(silu(gate bits) * up bits).  (gu bf16, act
+    float64).  mutant: gate_up_halves_swapped (act = silu(up) * gate)."""
+    assert mutant in (None, "gate_up_halves_swapped"), mutant
+    f32 = torch.float32
+    gu = acc_gate_up.to(f32).to(torch.bfloat16)
+    I = gu.shape[1] // 2
+    g, u = gu[:, :I].to(f32), gu[:, I:].to(f32)
+    if mutant == "gate_up_halves_swapped":
+        g, u = u, g
+    return gu, _bf((g * _sigmoid32(g)) * u).to(F64)
+
+
+def qkrope_bound(ref64, emul=None):
+    """The floor of the EPI 3 criterion beside 1 bf16 ulp: 2^-18 * row max |ref| per HEAD row (the stand-alone kernel's bound), + 8 *
+    e32_row where an emulation is given, e32_row = the head row's max |emulation - ref64| -- what the float32 recipe, its angle recurrence
+    over the FLOAT32 table included, costs on this input (tests/test_ref64.py: test_margins_beyond_one_ulp_are_what_float32_costs).
+    ref64 [M, heads * 128] -> floor of the same shape."""
+    M = ref64.shape[0]
+    r = ref64.to(F64).reshape(M, -1, 128)
+    fl = 2.0 ** -18 * r.abs().amax(-1, keepdim=True)
+    if emul is not None:
+        fl = fl + 8.0 * (emul.to(F64).reshape(M, -1, 128) - r).abs().amax(-1, keepdim=True)
+    return fl.expand_as(r).reshape(M, -1)

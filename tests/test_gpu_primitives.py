@@ -18,9 +18,6 @@ COVERS = {
     "ur_gemm": ["test_gemm_exact_integer", "test_gemm_big_tile_k_strided_exact", "test_gemm_epilogues", "test_gemm_second_pair_lora",
                 "test_gemm_splitk_tn", "test_gemm_swiglu_backward_epilogue", "test_gemm_swiglu_forward_epilogue"],
     "ur_gemm_grouped": ["tests/test_gpu_gemm_grouped.py::test_one_item_qformer_layer", "tests/test_gpu_gemm_grouped.py::test_small_and_ragged_products_take_the_small_tile"],
-    "ur_gemm_swiglu_paired_supported": ["tests/test_gpu_gemm_persistent.py::test_gate_up_projection_with_paired_swiglu_epilogue"],
-    "ur_gemm_qkrope_supported": ["tests/test_gpu_gemm_persistent.py::test_qkv_projection_with_qknorm_rope_epilogue"],
-    "ur_qkrope_perm": ["tests/test_gpu_gemm_persistent.py::test_qkv_projection_with_qknorm_rope_epilogue"],
     "ur_lora_bits_transpose": ["test_lora_reduce_ring_kernel"],
     "ur_lora_dropout_bits": ["test_lora_kernels_with_dropout_bits", "test_lora_dropout_word_popcounts_and_triples_follow_the_binomial"],
     "ur_lora_project": ["test_lora_kernels_with_dropout_bits", "test_lora_kernels_on_column_ranges"],

@@ -70,18 +70,20 @@ template <class T> __device__ __forceinline__ void st_g(void* p, const T& v) {
 // XCD-aware tile order of gemm.hip, as a function of the (virtual) block id: ids equal mod 8 share an XCD
 // n / d for n * d < 2^32 by one scalar multiply-high: magic = ceil(2^32 / d) (host, TileOrder)
 struct TileOrder { int nwg, gn, gcw, rows_x, per; uint32_t m_gn, m_per, m_gcw; };
-__device__ __forceinline__ int fdiv(int n, uint32_t magic) { return (int)__umulhi((uint32_t)n, magic); }
+// n / d by the host's magic = ceil(2^32 / d).  d == 1 has no 32-bit magic (2^32 wraps to 0, and n * 0 >> 32 sent every tile of a
+// one-tile-column launch to tile row 0 and tile column `id`, far outside C): the divisor rides along and 1 is taken as it is
+__device__ __forceinline__ int fdiv(int n, uint32_t magic, int d) { return d == 1 ? n : (int)__umulhi((uint32_t)n, magic); }
 __device__ __forceinline__ void tile_coords(const TileOrder& o, int vid, int& bm, int& bn) {
   const int q = o.nwg >> 3, r = o.nwg & 7, x = vid & 7;
   const int id = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (vid >> 3);
   if (o.gcw > 0) {
     const int j = id - x * q;                        // gm % 8 == 0: every XCD owns rows_x whole tile rows (r == 0)
-    const int ch = fdiv(j, o.m_per), rem = j - ch * o.per;
-    const int rr = fdiv(rem, o.m_gcw);
+    const int ch = fdiv(j, o.m_per, o.per), rem = j - ch * o.per;
+    const int rr = fdiv(rem, o.m_gcw, o.gcw);
     bm = x * o.rows_x + rr;
     bn = ch * o.gcw + (rem - rr * o.gcw);
   } else {
-    bm = fdiv(id, o.m_gn); bn = id - bm * o.gn;
+    bm = fdiv(id, o.m_gn, o.gn); bn = id - bm * o.gn;
   }
 }
 

@@ -261,8 +261,9 @@ def gemm_swiglu_paired_supported(M, I, K, K2, device):
     return bool(lib.ur_gemm_swiglu_paired_supported(ctypes.byref(a)))
 
 
-def gemm_qkrope_supported(M, N, K, K2, Sseq, nq_cols, nk_cols, device):
-    """True when the q|k|v projection of these sizes can carry q/k-norm + RoPE in its epilogue (ur_gemm_qkrope_supported)."""
+def gemm_qkrope_supported(M, N, K, K2, Sseq, nq_cols, nk_cols, device, alpha=1.0, bias=None):
+    """True when the q|k|v projection of these sizes can carry q/k-norm + RoPE in its epilogue (ur_gemm_qkrope_supported); alpha / bias
+    (f32 [N]) fill the fields of ur_gemm_args the epilogue does not take, for which the answer is no."""
     lib = _lib.load()
     d = torch.empty(16, dtype=BF16, device=device)          # any valid 16-byte aligned pointer: only sizes / flags are inspected
     f = torch.empty(4, dtype=F32, device=device)
@@ -271,7 +272,8 @@ def gemm_qkrope_supported(M, N, K, K2, Sseq, nq_cols, nk_cols, device):
     a.qkr_rstd = a.qkr_qw = a.qkr_kw = a.qkr_cos = a.qkr_sin = f.data_ptr()
     a.ldr = a.lds = K
     a.r_kcontig = a.s_kcontig = 1
-    a.K, a.M, a.N, a.alpha, a.split_k, a.ldc = K, M, N, 1.0, 1, N
+    a.K, a.M, a.N, a.alpha, a.split_k, a.ldc = K, M, N, float(alpha), 1, N
+    a.bias = _p(bias)
     if K2:
         a.R2 = a.S2 = d.data_ptr(); a.ldr2 = a.lds2 = K2; a.K2 = K2
     a.qkr_ldq, a.qkr_ldk, a.qkr_ldv = nq_cols, nk_cols, N - nq_cols - nk_cols
@@ -279,15 +281,25 @@ def gemm_qkrope_supported(M, N, K, K2, Sseq, nq_cols, nk_cols, device):
     return bool(lib.ur_gemm_qkrope_supported(ctypes.byref(a)))
 
 
-def gemm_qkv_rope(R, S, qw, kw, cos, sin, Sseq, nq_cols, nk_cols, eps, R2=None, S2=None):
+def gemm_qkv_rope(R, S, qw, kw, cos, sin, Sseq, nq_cols, nk_cols, eps, R2=None, S2=None, out=None):
     """The merged q|k|v projection with q/k-norm + RoPE in its epilogue (ur_gemm_args.qkr_*): R [M,K] activations, S [N,K]
     weights whose q / k head rows are in the paired order (qkrope_perm), optional LoRA pair (S2 rows paired likewise).
-    Returns (q_r [M,nq_cols], k_r [M,nk_cols], v [M,N-nq-nk], rstd [M,(nq+nk)/128]); the raw q, k are never stored."""
+    Returns (q_r [M,nq_cols], k_r [M,nk_cols], v [M,N-nq-nk], rstd [M,(nq+nk)/128]); the raw q, k are never stored.
+    out = (q, k, v, rstd): write there instead -- q / k / v bf16 of those shapes with unit inner stride and ANY row stride >= the width
+    (column views of wider buffers: qkr_ldq / ldk / ldv), rstd contiguous f32."""
     lib = _lib.load()
     M, N = R.shape[0], S.shape[0]
     dev = R.device
-    outs = (torch.empty((M, nq_cols), dtype=BF16, device=dev), torch.empty((M, nk_cols), dtype=BF16, device=dev),
-            torch.empty((M, N - nq_cols - nk_cols), dtype=BF16, device=dev), torch.empty((M, (nq_cols + nk_cols) // 128), dtype=F32, device=dev))
+    shapes = ((M, nq_cols), (M, nk_cols), (M, N - nq_cols - nk_cols), (M, (nq_cols + nk_cols) // 128))
+    if out is None:
+        outs = tuple(torch.empty(sh, dtype=F32 if i == 3 else BF16, device=dev) for i, sh in enumerate(shapes))
+    else:
+        outs = tuple(out)
+        if len(outs) != 4:
+            raise ValueError("gemm_qkv_rope: out must be (q, k, v, rstd)")
+        for i, (t, sh, nm) in enumerate(zip(outs, shapes, ("q", "k", "v", "rstd"))):
+            if t.dtype != (F32 if i == 3 else BF16) or not t.is_cuda or tuple(t.shape) != sh or t.stride(1) != 1 or (i == 3 and not t.is_contiguous()):
+                raise ValueError(f"gemm_qkv_rope: out {nm} must be a {'contiguous f32' if i == 3 else 'bf16'} {sh} device tensor with unit inner stride")
     a = _qkrope_args(R, S, R2, S2, qw, kw, cos, sin, Sseq, nq_cols, nk_cols, eps, outs)
     if PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
