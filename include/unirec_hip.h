@@ -43,7 +43,8 @@ const char* ur_last_error(void);
  * The optional second range (R2,S2,K2) uses the same layout flags (LoRA low-rank term).
  * Epilogue (bf16 output): v = alpha*acc + bias[n] + residual[m][n]; v *= gelu'(aux[m][n]);
  *   C = bf16(v); gelu_out = bf16(gelu(bf16(v))).  f32 output: v = alpha*acc + bias[n].
- * split_k > 1: f32 output only, ldc == N, deterministic slab reduction in `workspace`.
+ * split_k > 1: f32 output only, ldc == N (a padded output is rejected: the slabs are dense [M, N] images of C and the
+ *   combine copies them whole), deterministic slab reduction in `workspace`.
  * Constraints: K,K2 % 8 == 0 unless both operands are K-strided; N, ldc % 4 == 0; leading dims
  * % 8 == 0; 16-byte aligned bases. */
 typedef struct {
@@ -117,7 +118,8 @@ int ur_gemm(const ur_gemm_args* a, void* workspace, int64_t workspace_bytes, voi
  * nn.Linear under /root/reference/models/qformer.py:56-92 attention projections, :238-275 feed-forward; the reference issues one
  * addmm per weight).  Alone none of those [out, in] = [768..3072, 768..3072] products over 8192 tokens fills the chip without
  * slicing the token axis into pieces too short for a tile; together they are one round of 256 x 256 tiles.  Results per product
- * equal ur_gemm's for the same tile size and split (same order of summation).  Workspace: ur_gemm_grouped_workspace_bytes. */
+ * equal ur_gemm's for the same tile size and split (same order of summation).  split_k > 1: every product needs ldc == N, as
+ * ur_gemm does (split_k <= 1 takes any ldc >= N, ldc % 4 == 0).  Workspace: ur_gemm_grouped_workspace_bytes. */
 int64_t ur_gemm_grouped_workspace_bytes(const ur_gemm_args* a, int32_t count);
 int ur_gemm_grouped(const ur_gemm_args* a, int32_t count, void* workspace, int64_t workspace_bytes, void* stream);
 /* Launches with K-contiguous operands, bf16 output, M, N multiples of 256, K a multiple of 64 (>= 256), >= 128 output tiles and

@@ -1,6 +1,7 @@
-"""Float64 restatements of the head, RoPE, pool, data, attention, norm, reduction, GEMM-epilogue and LoRA primitives of
-include/unirec_hip.h, and the element-wise criteria the GPU tests hold the kernels to (tests/test_gpu_head_primitives.py,
-tests/test_gpu_attention_f64.py, tests/test_gpu_norm_f64.py, tests/test_gpu_lora_f64.py, tests/test_gpu_gemm_f64.py).  Plain torch: no fixtures, no device code
+"""Float64 restatements of the head, RoPE, pool, data, attention, norm, reduction, GEMM-epilogue, LoRA, optimizer, cast, field-projection
+and split-K primitives of include/unirec_hip.h, and the element-wise criteria the GPU tests hold the kernels to (tests/test_gpu_head_primitives.py,
+tests/test_gpu_attention_f64.py, tests/test_gpu_norm_f64.py, tests/test_gpu_lora_f64.py, tests/test_gpu_gemm_f64.py,
+tests/test_gpu_elementwise_f64.py, tests/test_gpu_dw_f64.py).  Plain torch: no fixtures, no device code
 (the fused-GEMM-epilogue section at the end runs on its inputs' device, everything else on the CPU).
 
 Every reference is written from the formula in the header comment of its entry point and is itself checked against an
@@ -1379,3 +1380,153 @@ def qkrope_bound(ref64, emul=None):
     if emul is not None:
         fl = fl + 8.0 * (emul.to(F64).reshape(M, -1, 128) - r).abs().amax(-1, keepdim=True)
     return fl.expand_as(r).reshape(M, -1)
+
+
+# ---- AdamW, casts, bf16 add, field projection, split-K token reductions (include/unirec_hip.h: ur_adamw_step*, ur_cast_*, ur_add_bf16,
+# ur_field_projection_*, ur_gemm / ur_gemm_grouped with split_k) ---------------------------------------------------------------------
+ADAMW_MUTANTS = ("bias_correction_step_minus_1", "l2_decay_in_gradient", "eps_inside_sqrt", "grad_scale_not_on_v", "tail_unstepped")
+FPROJ_MUTANTS = ("bias_per_q", "position_skipped", "w_transposed")
+SPLITK_MUTANTS = ("slice_dropped", "slice_twice")
+GEMM_BK = 64                        # K depth of one tile of csrc/gemm.hip: ur_gemm cuts K into split_k runs of ceil(tiles / split_k) tiles
+
+
+def _f32_scalar(x, dtype):
+    """a `float` argument of the ABI: the float32 value the kernel receives, in the evaluation's dtype"""
+    return torch.tensor(float(x), dtype=torch.float32).to(dtype)
+
+
+def adamw_step(p, g, m, v, lr, b1, b2, eps, wd, step, grad_scale, coef=1.0, dtype=F64, mutant=None):
+    """torch.optim.AdamW's step (decoupled decay) as the header states it, on flat vectors; returns (p, m, v):
+        gr = g * (grad_scale * coef);  p *= 1 - lr * wd;  m = b1 m + (1 - b1) gr;  v = b2 v + (1 - b2) gr^2;
+        p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps).
+    The hyperparameters enter as the float32 values the ABI passes.  mutant: one of ADAMW_MUTANTS, a DELIBERATE bug."""
+    assert mutant is None or mutant in ADAMW_MUTANTS, mutant
+    c = lambda t: torch.as_tensor(t).detach().cpu().to(dtype).reshape(-1)      # noqa: E731
+    p0, g0, m0, v0 = c(p), c(g), c(m), c(v)
+    lr_, b1_, b2_, eps_, wd_ = (_f32_scalar(x, dtype) for x in (lr, b1, b2, eps, wd))
+    gs = _f32_scalar(grad_scale, dtype) * _f32_scalar(coef, dtype)
+    one = torch.ones((), dtype=dtype)
+    t = float(step - 1 if mutant == "bias_correction_step_minus_1" else step)
+    bc1, bc2 = one - b1_ ** t, one - b2_ ** t
+    gr = g0 * gs
+    if mutant == "l2_decay_in_gradient":
+        gr = gr + wd_ * p0
+        pn = p0
+    else:
+        pn = p0 * (one - lr_ * wd_)
+    mn = b1_ * m0 + (one - b1_) * gr
+    gv = g0 if mutant == "grad_scale_not_on_v" else gr
+    vn = b2_ * v0 + (one - b2_) * gv * gv
+    if mutant == "eps_inside_sqrt":
+        denom = torch.sqrt(vn / bc2 + eps_)
+    else:
+        denom = torch.sqrt(vn) / torch.sqrt(bc2) + eps_
+    pn = pn - (lr_ / bc1) * (mn / denom)
+    if mutant == "tail_unstepped":
+        k = (p0.numel() // 4) * 4
+        pn[k:], mn[k:], vn[k:] = p0[k:], m0[k:], v0[k:]
+    return pn, mn, vn
+
+
+def rows_of(t, width=64):
+    """a flat vector as rows of `width` elements (zero-padded): the rows of assert_f32_close, so that one large element sets the bound of its
+    own 64 neighbours only"""
+    t = torch.as_tensor(t).detach().cpu().reshape(-1)
+    pad = (-t.numel()) % width
+    if pad:
+        t = torch.cat([t, torch.zeros(pad, dtype=t.dtype)])
+    return t.reshape(-1, width)
+
+
+def cast_f32_to_bf16(x):
+    """torch's own CPU conversion (round to nearest even; NaN stays NaN, overflow gives the signed infinity)"""
+    return torch.as_tensor(x).detach().cpu().to(torch.float32).to(torch.bfloat16)
+
+
+def assert_bf16_bits(got, want, what=""):
+    """bf16 `got` carries the bits of `want`, except that every NaN equals every NaN (the payload is not specified).  Returns 0."""
+    g, w = torch.as_tensor(got).detach().cpu(), torch.as_tensor(want).detach().cpu()
+    assert g.dtype == w.dtype == torch.bfloat16 and g.shape == w.shape, f"{what}: {g.dtype} {tuple(g.shape)} vs {w.dtype} {tuple(w.shape)}"
+    gn, wn = torch.isnan(g), torch.isnan(w)
+    off = (gn != wn) | (~gn & (g.contiguous().view(torch.int16) != w.contiguous().view(torch.int16)))
+    if off.any():
+        i = tuple(int(v) for v in off.nonzero()[0])
+        raise AssertionError(f"{what}: {int(off.sum())} of {off.numel()} elements differ; first at index {i}: got {g[i].item()!r} "
+                             f"(0x{int(g.contiguous().view(torch.int16)[i]) & 0xffff:04x}), expected {w[i].item()!r} (0x{int(w.contiguous().view(torch.int16)[i]) & 0xffff:04x})")
+    return 0.0
+
+
+def add_bf16(a, b):
+    """(bf16(float32(a) + float32(b)) -- the kernel's documented rounding: the float32 sum of two bf16 values, rounded once more --, the
+    float64 sum)"""
+    a, b = torch.as_tensor(a).detach().cpu(), torch.as_tensor(b).detach().cpu()
+    return (a.to(torch.float32) + b.to(torch.float32)).to(torch.bfloat16), a.to(F64) + b.to(F64)
+
+
+def field_projection_fwd(rec, Wf, bf, dtype=F64, mutant=None):
+    """out[b, f, e] = sum_q Wf[f, q] rec[b, q, e] + bf[f]: [B, F, E]."""
+    assert mutant is None or mutant in FPROJ_MUTANTS, mutant
+    r, w, b = (torch.as_tensor(t).detach().cpu().to(dtype) for t in (rec, Wf, bf))
+    if mutant == "w_transposed":                                 # the F * Q words read as [Q, F]
+        w = w.reshape(-1).reshape(w.shape[1], w.shape[0]).t()
+    out = torch.einsum("fq,bqe->bfe", w, r)
+    return out + b[None, :, None] * (w.shape[1] if mutant == "bias_per_q" else 1)
+
+
+def field_projection_bwd(dout, rec, Wf, dtype=F64, mutant=None):
+    """(drec [B, Q, E] = sum_f Wf[f, q] dout[b, f, e];  dWf [F, Q] = sum_{b, e} dout[b, f, e] rec[b, q, e];  dbf [F] = sum_{b, e} dout[b, f, e];
+    sum |dout * rec| [F, Q];  sum |dout| [F]) -- the last two are the abs_terms of assert_colsum_close."""
+    assert mutant is None or mutant in FPROJ_MUTANTS, mutant
+    d, r, w = (torch.as_tensor(t).detach().cpu().to(dtype) for t in (dout, rec, Wf))
+    wd = w.reshape(-1).reshape(w.shape[1], w.shape[0]).t() if mutant == "w_transposed" else w
+    drec = torch.einsum("fq,bfe->bqe", wd, d)
+    dk = d
+    if mutant == "position_skipped":                             # the last (b, e) position never reaches the weight gradient
+        dk = d.clone()
+        dk[-1, :, -1] = 0
+    dWf = torch.einsum("bfe,bqe->fq", dk, r)
+    return drec, dWf, d.sum(dim=(0, 2)), torch.einsum("bfe,bqe->fq", d.abs(), r.abs()), d.abs().sum(dim=(0, 2))
+
+
+FPROJ_OPERAND_ROUNDING = 2.0 ** -9  # fproj_bwd32_kernel rounds dout to bf16 (half a unit of 8 significant bits) in front of the MFMA
+
+
+def fproj_fast_dwf_terms(abs_terms):
+    """abs_terms of assert_colsum_close for the Q = 32 fast path's dWf: the bound 8 e32 + 2^-20 sum |term| + 2^-9 sum |term|, the last
+    for the bf16 rounding of the dout operand, written as one sum |term| scaled by 1 + 2^11 (as assert_lora_bf16 passes its own)."""
+    return _cpu64(abs_terms) * (1.0 + FPROJ_OPERAND_ROUNDING * 2.0 ** 20)
+
+
+def splitk_slices(K, split_k, bk=GEMM_BK):
+    """[(k0, k1)] of the split_k runs ur_gemm / ur_gemm_grouped cut the token axis into: ceil(ceil(K / bk) / split_k) tiles each; trailing
+    runs may be short or EMPTY (k0 >= k1)."""
+    per = -(-(-(-K // bk)) // max(1, split_k)) * bk
+    return [(min(K, z * per), min(K, (z + 1) * per)) for z in range(max(1, split_k))]
+
+
+def gemm_tn(R, S, split_k=1, dtype=F64, mutant=None):
+    """Token-major product out[m, n] = sum_k R[k, m] S[k, n] (dW = dY^T X), summed run by run as the split-K slabs are; R [K, M], S [K, N]."""
+    assert mutant is None or mutant in SPLITK_MUTANTS, mutant
+    r, s = torch.as_tensor(R).detach().cpu().to(dtype), torch.as_tensor(S).detach().cpu().to(dtype)
+    runs = [(k0, k1) for k0, k1 in splitk_slices(r.shape[0], split_k) if k1 > k0]
+    if mutant == "slice_dropped":
+        runs = runs[:-1]
+    if mutant == "slice_twice":
+        runs = runs + runs[:1]
+    out = torch.zeros(r.shape[1], s.shape[1], dtype=dtype)
+    for k0, k1 in runs:
+        out = out + r[k0:k1].t() @ s[k0:k1]
+    return out
+
+
+def assert_adamw_close(got, p, g, m, v, lr, b1, b2, eps, wd, step, grad_scale, coef=1.0, coef32=None, what=""):
+    """got = (p, m, v) after one step, each held by assert_f32_close in rows of 64 against adamw_step in float64, with the same formula in
+    float32 as the yardstick (coef32: the float32 evaluation's own clip coefficient where the coefficient is itself computed).  Returns the
+    worst error / bound of the three."""
+    r64 = adamw_step(p, g, m, v, lr, b1, b2, eps, wd, step, grad_scale, coef)
+    r32 = adamw_step(p, g, m, v, lr, b1, b2, eps, wd, step, grad_scale, coef if coef32 is None else coef32, dtype=torch.float32)
+    worst = 0.0
+    for name, x, a, b in zip(("param", "exp_avg", "exp_avg_sq"), got, r64, r32):
+        assert torch.as_tensor(x).numel() == a.numel(), f"{what}: {name}: {torch.as_tensor(x).numel()} elements vs {a.numel()}"
+        worst = max(worst, assert_f32_close(rows_of(x), rows_of(a), rows_of(b), what=f"{what}: {name}"))
+    return worst

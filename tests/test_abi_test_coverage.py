@@ -7,7 +7,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COVERS_MODULES = ("tests/test_gpu_primitives.py", "tests/test_gpu_head_primitives.py", "tests/test_gpu_attention_f64.py", "tests/test_gpu_norm_f64.py",
-                  "tests/test_gpu_lora_f64.py", "tests/test_gpu_gemm_f64.py")
+                  "tests/test_gpu_lora_f64.py", "tests/test_gpu_gemm_f64.py", "tests/test_gpu_elementwise_f64.py", "tests/test_gpu_dw_f64.py")
 
 EXEMPT = {
     "ur_version": "ABI handshake; asserted at every library load (unirec_amd/_lib.py) and in tests/test_cabi.py",

@@ -17,7 +17,8 @@ DEV = "cuda"
 COVERS = {
     "ur_gemm": ["test_gemm_exact_integer", "test_gemm_big_tile_k_strided_exact", "test_gemm_epilogues", "test_gemm_second_pair_lora",
                 "test_gemm_splitk_tn", "test_gemm_swiglu_backward_epilogue", "test_gemm_swiglu_forward_epilogue"],
-    "ur_gemm_grouped": ["tests/test_gpu_gemm_grouped.py::test_one_item_qformer_layer", "tests/test_gpu_gemm_grouped.py::test_small_and_ragged_products_take_the_small_tile"],
+    "ur_gemm_grouped": ["tests/test_gpu_gemm_grouped.py::test_one_item_qformer_layer", "tests/test_gpu_gemm_grouped.py::test_small_and_ragged_products_take_the_small_tile",
+                        "tests/test_gpu_dw_f64.py::test_grouped_small_tile_exact_and_equal_to_ur_gemm", "tests/test_gpu_dw_f64.py::test_grouped_big_tile_exact", "tests/test_gpu_dw_f64.py::test_grouped_unit_normal_operands"],
     "ur_lora_bits_transpose": ["test_lora_reduce_ring_kernel"],
     "ur_lora_dropout_bits": ["test_lora_kernels_with_dropout_bits", "test_lora_dropout_word_popcounts_and_triples_follow_the_binomial"],
     "ur_lora_project": ["test_lora_kernels_with_dropout_bits", "test_lora_kernels_on_column_ranges"],
@@ -28,15 +29,17 @@ COVERS = {
     "ur_attn_bwd": ["tests/test_gpu_attention.py::test_qformer_attention", "tests/test_gpu_attention.py::test_qwen3_causal_gqa"],
     "ur_attn_dropout_keep": ["tests/test_gpu_r5_parity.py::test_attention_dropout_keep_export_matches_the_numpy_generator"],
     "ur_gather_rows": ["tests/test_gpu_data_path.py::test_gather_rows_all_kinds"],
-    "ur_field_projection_fwd": ["test_field_projection_fwd_bwd_match_torch"],
-    "ur_field_projection_bwd": ["test_field_projection_fwd_bwd_match_torch"],
-    "ur_cast_f32_to_bf16": ["test_elementwise_and_adamw"],
-    "ur_cast_bf16_to_f32": ["test_elementwise_and_adamw"],
-    "ur_transpose_bf16": ["test_elementwise_and_adamw"],
-    "ur_transpose_bf16_batched": ["test_batched_transpose_matches_per_matrix_transposes"],
-    "ur_add_bf16": ["test_elementwise_and_adamw"],
-    "ur_adamw_step": ["test_elementwise_and_adamw"],
-    "ur_adamw_step_dev": ["tests/test_gpu_grad_clip.py::test_clipped_training_matches_torch"],
+    # (element by element against float64 / bit for bit since the elementwise and dW round: tests/test_gpu_elementwise_f64.py, tests/test_gpu_dw_f64.py)
+    "ur_field_projection_fwd": ["test_field_projection_fwd_bwd_match_torch", "tests/test_gpu_dw_f64.py::test_field_projection_generic", "tests/test_gpu_dw_f64.py::test_field_projection_fast"],
+    "ur_field_projection_bwd": ["test_field_projection_fwd_bwd_match_torch", "tests/test_gpu_dw_f64.py::test_field_projection_generic", "tests/test_gpu_dw_f64.py::test_field_projection_fast"],
+    "ur_cast_f32_to_bf16": ["test_elementwise_and_adamw", "tests/test_gpu_elementwise_f64.py::test_cast_f32_to_bf16_every_upper_half"],
+    "ur_cast_bf16_to_f32": ["test_elementwise_and_adamw", "tests/test_gpu_elementwise_f64.py::test_cast_bf16_to_f32_every_pattern"],
+    "ur_transpose_bf16": ["tests/test_gpu_elementwise_f64.py::test_transposes_move_every_bit"],
+    "ur_transpose_bf16_batched": ["test_batched_transpose_matches_per_matrix_transposes", "tests/test_gpu_elementwise_f64.py::test_transposes_move_every_bit"],
+    "ur_add_bf16": ["test_elementwise_and_adamw", "tests/test_gpu_elementwise_f64.py::test_add_bf16_past_the_grid_cap"],
+    "ur_adamw_step": ["test_elementwise_and_adamw", "tests/test_gpu_elementwise_f64.py::test_adamw_step_every_element"],
+    "ur_adamw_step_dev": ["tests/test_gpu_grad_clip.py::test_clipped_training_matches_torch", "tests/test_gpu_elementwise_f64.py::test_adamw_step_dev_coefficients",
+                          "tests/test_gpu_elementwise_f64.py::test_norm_clip_then_step_on_one_stream"],
     "ur_grad_norm_clip": ["tests/test_gpu_grad_clip.py::test_norm_matches_float64_and_is_deterministic"],
 }
 

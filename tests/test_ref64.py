@@ -1104,3 +1104,185 @@ def test_swiglu_forward_criterion(mutant):
 
 def test_gemm_epilogue_mutant_list_is_the_one_exercised():
     assert set(ref64.GEMM_EPI_MUTANTS) == set(QKROPE_MUTANTS) | {"dgate_from_rounded_dact", "dup_uses_sigmoid_only", "gate_up_halves_swapped", "masked_term_unscaled"}
+
+
+# ---- AdamW, casts, bf16 add, field projection, split-K (tests/test_gpu_elementwise_f64.py, tests/test_gpu_dw_f64.py) -------------------
+from tests import ew_cases  # noqa: E402
+
+F32 = torch.float32
+
+
+def _f32(x):
+    return float(np.float32(x))
+
+
+@pytest.mark.parametrize("wd", [0.0, 0.1])
+def test_adamw_reference_matches_torch_optim_adamw(wd):
+    """three consecutive steps of torch.optim.AdamW on float64 parameters, gradients pre-multiplied by grad_scale * coef"""
+    n, lr, gs, coef = 1021, 0.05, ew_cases.ADAMW_GRAD_SCALE, 0.37
+    h = ew_cases.ADAMW_HYPER
+    p0, _, _, _ = ew_cases.adamw_inputs(n, 1, 5)
+    param = torch.nn.Parameter(p0.to(F64).clone())
+    opt = torch.optim.AdamW([param], lr=_f32(lr), betas=(_f32(h["b1"]), _f32(h["b2"])), eps=_f32(h["eps"]), weight_decay=_f32(wd))
+    p, m, v = p0, torch.zeros(n), torch.zeros(n)
+    for step in (1, 2, 3):
+        g = ew_cases.adamw_inputs(n, 1, 5 + step)[1]
+        param.grad = g.to(F64) * (_f32(gs) * _f32(coef))
+        opt.step()
+        p, m, v = ref64.adamw_step(p, g, m, v, lr, h["b1"], h["b2"], h["eps"], wd, step, gs, coef)
+        st = opt.state[param]
+        for got, want in ((p, param.detach()), (m, st["exp_avg"]), (v, st["exp_avg_sq"])):
+            assert torch.allclose(got, want, rtol=1e-12, atol=1e-300), (step, (got - want).abs().max())
+
+
+@pytest.mark.parametrize("step", ew_cases.ADAMW_STEPS)
+def test_adamw_criterion_passes_the_float32_evaluation(step):
+    h = ew_cases.ADAMW_HYPER
+    for n in ew_cases.ADAMW_SIZES[:4]:
+        p, g, m, v = ew_cases.adamw_inputs(n, step, n)
+        got = ref64.adamw_step(p, g, m, v, 0.05, h["b1"], h["b2"], h["eps"], 0.1, step, ew_cases.ADAMW_GRAD_SCALE, dtype=F32)
+        assert ref64.assert_adamw_close(got, p, g, m, v, 0.05, h["b1"], h["b2"], h["eps"], 0.1, step, ew_cases.ADAMW_GRAD_SCALE, what=f"n {n}") <= 1.0
+        assert all(torch.isfinite(t).all() for t in got)
+        assert (g == 0).any() or n < 8
+
+
+@pytest.mark.parametrize("mutant", ref64.ADAMW_MUTANTS)
+def test_adamw_criterion_rejects_every_mutant(mutant):
+    """float64 evaluations of a wrong formula at the GPU test's inputs (step 2 and 10, weight decay 0.1, n = 1021 and 7)"""
+    h = ew_cases.ADAMW_HYPER
+    for n, step in ((1021, 2), (7, 10)):
+        p, g, m, v = ew_cases.adamw_inputs(n, step, n)
+        args = (p, g, m, v, 0.05, h["b1"], h["b2"], h["eps"], 0.1, step, ew_cases.ADAMW_GRAD_SCALE)
+        assert ref64.assert_adamw_close(ref64.adamw_step(*args), *args) == 0.0
+        with pytest.raises(AssertionError):
+            ref64.assert_adamw_close(ref64.adamw_step(*args, mutant=mutant), *args, what=mutant)
+    assert set(ref64.ADAMW_MUTANTS) == {"bias_correction_step_minus_1", "l2_decay_in_gradient", "eps_inside_sqrt", "grad_scale_not_on_v", "tail_unstepped"}
+
+
+def test_adamw_clip_coefficient_zero_only_decays_the_moments():
+    h = ew_cases.ADAMW_HYPER
+    p, g, m, v = ew_cases.adamw_inputs(1021, 10, 9)
+    pn, mn, vn = ref64.adamw_step(p, g, m, v, 0.05, h["b1"], h["b2"], h["eps"], 0.0, 10, 1.0, coef=0.0)
+    assert torch.equal(mn, _f32(h["b1"]) * m.to(F64)) and torch.equal(vn, _f32(h["b2"]) * v.to(F64))
+
+
+def test_cast_reference_is_round_to_nearest_even_on_every_pattern():
+    """torch's CPU conversion against the integer recipe (bits + 0x7fff + the kept half's last bit) >> 16 on every tested word; NaN stays NaN"""
+    x = ew_cases.cast_patterns()
+    assert x.numel() == 6 * 65536
+    want = ref64.cast_f32_to_bf16(x)
+    u = x.numpy().view(np.uint32).astype(np.uint64)
+    rne = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+    nan = np.isnan(x.numpy())
+    got = want.view(torch.int16).numpy().view(np.uint16)
+    assert (got[~nan] == rne[~nan]).all()
+    assert torch.isnan(want[torch.from_numpy(nan)]).all() and nan.sum() == 6 * 256 - 2          # (0x7f80 / 0xff80 over low half 0 are the infinities)
+    assert torch.isinf(want).sum() > 2                          # overflow: 0x7f7f over 0x8000 .. rounds up to infinity
+    ref64.assert_bf16_bits(want, want, "itself")
+    trunc = torch.from_numpy((u >> 16).astype(np.uint16).view(np.int16)).view(BF16)
+    with pytest.raises(AssertionError, match="differ"):
+        ref64.assert_bf16_bits(trunc, want, "truncation")
+    flushed = torch.where(want.float().abs() < 2.0 ** -126, torch.zeros_like(want), want)
+    with pytest.raises(AssertionError, match="differ"):
+        ref64.assert_bf16_bits(flushed, want, "subnormals flushed")
+    quiet = torch.where(torch.isnan(want), torch.full_like(want, float("inf")), want)
+    with pytest.raises(AssertionError, match="differ"):
+        ref64.assert_bf16_bits(quiet, want, "NaN turned into infinity")
+    # widening: every bf16 pattern is the float32 with a zero low half
+    b = ew_cases.bf16_patterns()
+    wide = b.to(F32).view(torch.int32)
+    assert torch.equal(wide, b.view(torch.int16).to(torch.int32) << 16)
+
+
+def test_add_bf16_reference_rounds_the_float32_sum_once():
+    a, b = ew_cases.add_operands(21 * 400, 3)
+    want, s64 = ref64.add_bf16(a, b)
+    gap = torch.floor(torch.log2(a.float().abs())) - torch.floor(torch.log2(b.float().abs()))
+    assert sorted(set(gap.tolist())) == [float(d) for d in range(21)]
+    assert ref64.assert_within_ulps(want, s64, 1, 0.0, "bf16(f32 sum)") <= 0.5 + 2.0 ** -15       # half a bf16 ulp and the float32 sum's own rounding
+    trunc = ((a.float() + b.float()).view(torch.int32) >> 16).to(torch.int16).view(BF16)
+    with pytest.raises(AssertionError, match="differ"):
+        ref64.assert_bf16_bits(trunc, want, "truncated sum")
+    with pytest.raises(AssertionError):
+        ref64.assert_bf16_bits(a, want, "b never added")
+
+
+@pytest.mark.parametrize("B,Q,F_,E", [(3, 64, 32, 100), (5, 32, 14, 256), (4, 4, 8, 64)])
+def test_field_projection_references_match_autograd(B, Q, F_, E):
+    rec, Wf, bf, dout = ew_cases.fproj_inputs(B, Q, F_, E, 11)
+    r = rec.to(F64).requires_grad_(True)
+    w = Wf.to(F64).requires_grad_(True)
+    b = bf.to(F64).requires_grad_(True)
+    out = torch.einsum("fq,bqe->bfe", w, r) + b[None, :, None]
+    assert torch.allclose(ref64.field_projection_fwd(rec, Wf, bf), out.detach(), rtol=1e-13, atol=1e-13)
+    dr, dw, db = torch.autograd.grad(out, (r, w, b), dout.to(F64))
+    drec, dWf, dbf, aW, ab = ref64.field_projection_bwd(dout, rec, Wf)
+    for got, want in ((drec, dr), (dWf, dw), (dbf, db)):
+        assert torch.allclose(got, want, rtol=1e-12, atol=1e-12)
+    assert (aW >= dWf.abs()).all() and (ab >= dbf.abs()).all() and aW.shape == (F_, Q) and ab.shape == (F_,)
+
+
+def _fproj_checks(out, drec, dWf, dbf, case, fast):
+    """the criteria of tests/test_gpu_dw_f64.py on given outputs: returns the names of those that reject"""
+    rec, Wf, bf, dout = case
+    o64, o32 = ref64.field_projection_fwd(rec, Wf, bf), ref64.field_projection_fwd(rec, Wf, bf, dtype=F32)
+    r64, r32 = ref64.field_projection_bwd(dout, rec, Wf), ref64.field_projection_bwd(dout, rec, Wf, dtype=F32)
+    aW = ref64.fproj_fast_dwf_terms(r64[3]) if fast else r64[3]
+    failed = []
+    for name, fn in (("out", lambda: ref64.assert_f32_close(out, o64, o32, what="out")),
+                     ("drec", lambda: ref64.assert_bf16_rows(drec, r64[0], r32[0], "drec")),
+                     ("dWf", lambda: ref64.assert_colsum_close(dWf, r64[1], r32[1], aW, "dWf")),
+                     ("dbf", lambda: ref64.assert_colsum_close(dbf, r64[2], r32[2], r64[4], "dbf"))):
+        try:
+            fn()
+        except AssertionError:
+            failed.append(name)
+    return failed
+
+
+@pytest.mark.parametrize("mutant", [None] + list(ref64.FPROJ_MUTANTS))
+def test_field_projection_criteria_reject_every_mutant(mutant):
+    case = ew_cases.fproj_inputs(5, 32, 14, 256, 12)
+    rec, Wf, bf, dout = case
+    out = ref64.field_projection_fwd(rec, Wf, bf, dtype=F32, mutant=mutant)
+    drec, dWf, dbf, _, _ = ref64.field_projection_bwd(dout, rec, Wf, dtype=F32, mutant=mutant)
+    failed = _fproj_checks(out, drec.to(BF16), dWf, dbf, case, fast=False)
+    assert failed == {None: [], "bias_per_q": ["out"], "position_skipped": ["dWf"], "w_transposed": ["out", "drec"]}[mutant]
+
+
+def test_field_projection_fast_path_term_is_the_operand_rounding_and_still_bites():
+    """dout rounded to bf16 in front of the contraction (fproj_bwd32_kernel) passes the criterion with the 2^-9 term and is what the term is for:
+    it fails the plain one; a batch row that never reaches dWf fails both"""
+    case = ew_cases.fproj_inputs(5, 32, 14, 256, 13)
+    rec, Wf, bf, dout = case
+    out = ref64.field_projection_fwd(rec, Wf, bf, dtype=F32)
+    drec, _, dbf, _, _ = ref64.field_projection_bwd(dout, rec, Wf, dtype=F32)
+    rounded = ref64.field_projection_bwd(dout.to(BF16), rec, Wf, dtype=F32)[1]
+    assert _fproj_checks(out, drec.to(BF16), rounded, dbf, case, fast=True) == []
+    assert _fproj_checks(out, drec.to(BF16), rounded, dbf, case, fast=False) == ["dWf"]
+    lost = ref64.field_projection_bwd(dout[:-1], rec[:-1], Wf, dtype=F32)[1]
+    assert _fproj_checks(out, drec.to(BF16), lost, dbf, case, fast=True) == ["dWf"]
+
+
+def test_splitk_reference_slices_and_mutants():
+    assert ref64.splitk_slices(256, 3) == [(0, 128), (128, 256), (256, 256)]                       # the last run is empty
+    assert [b - a for a, b in ref64.splitk_slices(320, 3)] == [128, 128, 64]
+    assert [b - a for a, b in ref64.splitk_slices(1000, 16)] == [64] * 15 + [40]
+    assert ref64.splitk_slices(1000, 1) == [(0, 1000)]
+    for K, split in ((256, 3), (320, 3), (1000, 16)):
+        R = torch.randint(-3, 4, (K, 16), generator=_gen(K)).to(BF16)
+        S = torch.randint(-3, 4, (K, 24), generator=_gen(K + 1)).to(BF16)
+        exact = R.to(F64).t() @ S.to(F64)
+        assert torch.equal(ref64.gemm_tn(R, S, split), exact) and torch.equal(ref64.gemm_tn(R, S, split, dtype=F32).to(F64), exact)
+        ref64.assert_lora_exact(ref64.gemm_tn(R, S, split, dtype=F32), exact, "float32 slabs")
+        for mutant in ref64.SPLITK_MUTANTS:
+            with pytest.raises(AssertionError, match="differ"):
+                ref64.assert_lora_exact(ref64.gemm_tn(R, S, split, dtype=F32, mutant=mutant), exact, mutant)
+    # unit-normal operands: the column-sum criterion the K = 4096 GPU case uses passes float32 slabs and rejects both mutants
+    K, split = 4096, 3
+    R, S = _randn((K, 16), 70).to(BF16), _randn((K, 24), 71).to(BF16)
+    r64, r32, a = ref64.gemm_tn(R, S), ref64.gemm_tn(R, S, split, dtype=F32), R.to(F64).abs().t() @ S.to(F64).abs()
+    assert ref64.assert_colsum_close(r32, r64, ref64.gemm_tn(R, S, dtype=F32), a, "float32 slabs") <= 1.0
+    for mutant in ref64.SPLITK_MUTANTS:
+        with pytest.raises(AssertionError, match="exceed 8"):
+            ref64.assert_colsum_close(ref64.gemm_tn(R, S, split, dtype=F32, mutant=mutant), r64, ref64.gemm_tn(R, S, dtype=F32), a, mutant)

@@ -444,6 +444,8 @@ extern "C" int ur_gemm(const ur_gemm_args* a, void* workspace, int64_t workspace
   if (splits > 1) {
     UR_REQUIRE(a->c_f32 && !a->bias && !a->residual && !a->gelu_out && !a->gelu_grad_aux && a->K2 == 0,
                "ur_gemm: split_k needs f32 output and no epilogue / second pair");
+    // the slabs are dense [M, N] images of C and the combine copies whole slabs: a padded C would receive its gap columns too
+    UR_REQUIRE(a->ldc == a->N, "ur_gemm: split_k needs a dense output, ldc == N (ldc=%ld, N=%d)", (long)a->ldc, a->N);
     UR_REQUIRE(workspace && workspace_bytes >= ur_gemm_workspace_bytes(a) && UR_ALIGNED16(workspace),
                "ur_gemm: split_k workspace too small (%lld < %lld)", (long long)workspace_bytes,
                (long long)ur_gemm_workspace_bytes(a));
@@ -530,6 +532,7 @@ static int grouped_check(const ur_gemm_args* a, int32_t count) {
     UR_REQUIRE(g->K == a->K && g->split_k == a->split_k && g->alpha == a->alpha, "ur_gemm_grouped: product %d: K, split_k and alpha must equal product 0's", i);
     UR_REQUIRE((g->M % 8) == 0 && (g->N % 8) == 0 && (g->ldr % 8) == 0 && (g->lds % 8) == 0 && (g->ldc % 4) == 0 && g->ldr >= g->M && g->lds >= g->N && g->ldc >= g->N,
                "ur_gemm_grouped: product %d: M, N, ldr, lds multiples of 8, ldc of 4, leading dimensions >= row lengths", i);
+    UR_REQUIRE(g->split_k <= 1 || g->ldc == g->N, "ur_gemm_grouped: product %d: split_k needs a dense output, ldc == N (ldc=%ld, N=%d)", i, (long)g->ldc, g->N);
     UR_REQUIRE(UR_ALIGNED16(g->R) && UR_ALIGNED16(g->S) && UR_ALIGNED16(g->C), "ur_gemm_grouped: product %d: operands must be 16-byte aligned", i);
   }
   return 0;

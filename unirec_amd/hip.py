@@ -220,9 +220,11 @@ def gemm_grouped(products, split_k=1):
                 raise ValueError(f"gemm_grouped: {nm} must be a 2-D bf16 device tensor with unit inner stride")
         if R.shape[0] != S.shape[0]:
             raise ValueError(f"gemm_grouped: token counts differ ({R.shape[0]} vs {S.shape[0]})")
-        _need(out, F32, "out")
-        if out.dim() != 2 or tuple(out.shape) != (R.shape[1], S.shape[1]) or out.stride(1) != 1:
-            raise ValueError(f"gemm_grouped: out must be f32 [{R.shape[1]}, {S.shape[1]}], got {tuple(out.shape)}")
+        if not out.is_cuda:
+            raise _lib.UniRecHipError("gemm_grouped: out: expected a device tensor (the UniRec HIP path has no CPU fallback)")
+        # (a row stride above the row length is the library's to judge: ur_gemm_grouped takes it without split_k and refuses it with)
+        if out.dtype != F32 or out.dim() != 2 or tuple(out.shape) != (R.shape[1], S.shape[1]) or out.stride(1) != 1:
+            raise ValueError(f"gemm_grouped: out must be f32 [{R.shape[1]}, {S.shape[1]}] with unit inner stride, got {out.dtype} {tuple(out.shape)}")
         a.R, a.ldr, a.r_kcontig = R.data_ptr(), R.stride(0), 0
         a.S, a.lds, a.s_kcontig = S.data_ptr(), S.stride(0), 0
         a.K, a.M, a.N, a.alpha = R.shape[0], R.shape[1], S.shape[1], 1.0
