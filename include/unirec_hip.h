@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 17      /* 17: ur_catalog_select_t ends in catalog_bf16 and scorer (zero = the call as it was) */
+#define UR_ABI_VERSION 18      /* 18: ur_gemm_plan */
 
 int ur_version(void);
 const char* ur_last_error(void);
@@ -105,9 +105,11 @@ typedef struct {
    * Persistent kernel only: ur_gemm_swiglu_paired_supported tells; ur_gemm fails loudly otherwise. */
   void* swp_act; int64_t swp_ldact; int32_t swp_I;
 } ur_gemm_args;
+/* 1 when ur_gemm would run the paired SwiGLU forward epilogue for these arguments: ur_gemm_plan accepts them with swp_act set and
+ * answers UR_GEMM_KERNEL_PERSISTENT. */
 int ur_gemm_swiglu_paired_supported(const ur_gemm_args* a);
-/* 1 when ur_gemm would run the q/k-norm + RoPE epilogue for these arguments, 0 when the caller must use the separate
- * ur_qknorm_rope_fwd pass. */
+/* 1 when ur_gemm would run the q/k-norm + RoPE epilogue for these arguments (ur_gemm_plan accepts them with qkr_q set and answers
+ * UR_GEMM_KERNEL_PERSISTENT), 0 when the caller must use the separate ur_qknorm_rope_fwd pass. */
 int ur_gemm_qkrope_supported(const ur_gemm_args* a);
 /* feature index stored at tile column c (0..127) of a head under the paired order */
 int ur_qkrope_perm(int c);
@@ -129,6 +131,40 @@ int ur_gemm_grouped(const ur_gemm_args* a, int32_t count, void* workspace, int64
  * (-1) returns to the default (1); returns the previous setting.  Process-wide; for A/B timing and the bit-identity tests.  The library reads
  * no environment variable. */
 int ur_gemm_persistent_mode(int mode);
+/* Which kernel ur_gemm(a, ...) (count == 0) or ur_gemm_grouped(a, count, ...) (count >= 1) launches, and how: the answer of the one
+ * selection function the launches themselves read (gemm.hip: gemm_select / gemm_select_grouped), under the ur_gemm_persistent_mode
+ * word as it stands at the moment of the call.
+ *   UR_GEMM_KERNEL_NONE        nothing is launched (M == 0 or N == 0)
+ *   UR_GEMM_KERNEL_GENERIC     gemm_kernel<layouts, output type, tile, EPI>: every ur_gemm launch the persistent kernel does not take.
+ *                              tile 256 when M, N >= 256 and ceil(M / 256) * ceil(N / 256) * split_k >= 256 workgroups (224 when both
+ *                              operands are K-strided), else 128; epi 1 / 2 = the SwiGLU backward / forward epilogue (swiglu_gu /
+ *                              swiglu_gate; K-contiguous bf16 launches), else 0; gcw = 4 on the 256 tile from 16 tile columns on, when
+ *                              the tile rows are a multiple of 8 and the tile columns of 4
+ *   UR_GEMM_KERNEL_PERSISTENT  gemm_pers_kernel<epi, mode>, tile 256: mode on, K-contiguous operands, bf16 output, no split_k, M, N
+ *                              multiples of 256, K of 64 and >= 256, 128 .. 2^20 - 1 tiles (< 2^15 tile rows, < 2^12 tile columns), no
+ *                              swiglu_gate; gelu_out / gelu_grad_aux only alone (no residual, second K range, or swiglu_gu / qkr_* /
+ *                              swp_* epilogue); K2 <= 64, or with drop_bits: drop_rank 16, K2 a multiple of 16, K <= 8192; no bias /
+ *                              residual with swiglu_gu; ldc and the leading dimensions of the epilogue's operands multiples of 8 with
+ *                              16-byte aligned bases; 16 rows of R / S and 32 rows of C and of every epilogue operand within 2^31 bytes.
+ *                              epi: 0 plain, 1 swiglu_gu, 2 residual (+ bias), 3 qkr_*, 4 swp_*, 5 bias, 6 gelu_out, 7 gelu_grad_aux;
+ *                              mode: 0 no second K range, 1 second K range, 2 masked (drop_bits); gcw = 6 when the tile columns are a
+ *                              multiple of 6 and >= 24, else 4, applied from 16 tile columns on when they are a multiple of gcw and
+ *                              the tile rows of 8
+ *   UR_GEMM_KERNEL_GROUPED     gemm_grouped_kernel<tile>: every ur_gemm_grouped launch; tile 256 when every product has M, N >= 256 and
+ *                              the products' 256 x 256 tiles summed, times split_k, are >= 128, else 128
+ * Priority for ur_gemm: PERSISTENT, GENERIC.  qkr_q / swp_act run on the persistent kernel only: refused unless it takes the launch.
+ * splits = max(split_k, 1).  ur_gemm_plan applies the size, stride, flag and alignment checks of the entry point (-1 and
+ * ur_last_error() on a refusal) and asks for no workspace; pointers are read for null-ness and alignment only, never followed.  It
+ * launches nothing and calls no HIP function: it answers on a machine without a GPU. */
+enum { UR_GEMM_KERNEL_NONE = 0, UR_GEMM_KERNEL_GENERIC = 1, UR_GEMM_KERNEL_PERSISTENT = 2, UR_GEMM_KERNEL_GROUPED = 3 };
+typedef struct {
+  int32_t kernel;            /* UR_GEMM_KERNEL_* */
+  int32_t tile;              /* 128 or 256 */
+  int32_t epi, mode;         /* template arguments of the kernel that runs (mode: persistent kernel only) */
+  int32_t gcw;               /* column-chunk width (tiles) of the per-XCD tile order; 0 = plain row-major runs */
+  int32_t splits;
+} ur_gemm_plan_info;
+int ur_gemm_plan(const ur_gemm_args* a, int32_t count, ur_gemm_plan_info* out);
 
 /* ------------------------------------------------------------------------------------------------
  * LoRA adapter products of rank r = `rank` in {8, 16, 32, 64}, j = 0 .. r - 1 (peft LoraLayer; call site

@@ -122,6 +122,7 @@ SMALL_TILE_SHAPES = [(64, 136), (136, 64), (264, 520), (8, 8)]
 @pytest.mark.parametrize("split", [1, 3])
 def test_grouped_small_tile_exact_and_equal_to_ur_gemm(split):
     """outputs below one big tile, edge tiles in both directions, a ragged last K tile, padded row strides of the inputs"""
+    assert hip.gemm_plan([hip.gemm_plan_args(M, N, 1000, r_kcontig=False, s_kcontig=False, out_f32=True, split_k=split) for M, N in SMALL_TILE_SHAPES])["tile"] == 128
     for R, S, r, s, out in _grouped(SMALL_TILE_SHAPES, 1000, split, 100, pad=8):
         M, N = out.shape
         _note("gemm_grouped_kernel<128>", ref64.assert_lora_exact(out, ref64.gemm_tn(r, s), f"split {split}, {M} x {N}"))
@@ -131,10 +132,11 @@ def test_grouped_small_tile_exact_and_equal_to_ur_gemm(split):
 
 @pytest.mark.parametrize("K", [320, 256])
 def test_grouped_big_tile_exact(K):
-    """eight products of 264 x 520: 6 big tiles each, 144 with the split (>= 128: the 256 x 256 tile), edge tiles in both directions;
+    """eight products of 264 x 520: 6 big tiles each, 144 with the split (the 256 x 256 tile; 96 at split 2 would be the small one), edge tiles in both directions;
     K = 320 ends in a short run, K = 256 in an empty one"""
     shapes = [(264, 520)] * 8
-    assert all(M >= 256 and N >= 256 for M, N in shapes) and sum(-(-M // 256) * -(-N // 256) for M, N in shapes) * 3 >= 128
+    group = lambda split: [hip.gemm_plan_args(M, N, K, r_kcontig=False, s_kcontig=False, out_f32=True, split_k=split) for M, N in shapes]      # noqa: E731
+    assert hip.gemm_plan(group(3))["tile"] == 256 and hip.gemm_plan(group(2))["tile"] == 128
     for R, S, r, s, out in _grouped(shapes, K, 3, 200 + K):
         _note("gemm_grouped_kernel<256>", ref64.assert_lora_exact(out, ref64.gemm_tn(r, s), f"K {K}"))
 

@@ -21,8 +21,8 @@ Criteria (docs/lab_notes.md, "Element-wise float64 tests: the decoder's GEMM epi
 No element is exempt.  Every output is pre-filled with the 0x4B4B sentinel (a NaN pattern where every finite bf16 is a legitimate output) and must be written and finite where it belongs and untouched in
 the pad columns of a wider row stride; a second call must be bit-identical.  Keep flags come from oracle/dropout_ref.lora_keep only, after
 the planes handed to the kernel were compared with the twin's words.  Every case asserts the kernel it means to test is the one that runs:
-hip.gemm_qkrope_supported / gemm_swiglu_paired_supported, and for EPI 1 the library's own eligibility answer for the launch's sizes under
-gemm_persistent_mode(1) (true) and (0) (false).  Every test prints its worst error / bound ("[ratio] kernel: x")."""
+hip.gemm_qkrope_supported / gemm_swiglu_paired_supported, and for EPI 1 and the second K range the library's own selection for the launch's
+arguments (hip.gemm_plan) under gemm_persistent_mode(1) and (0).  Every test prints its worst error / bound ("[ratio] kernel: x")."""
 import numpy as np
 import pytest
 import torch
@@ -146,10 +146,16 @@ class _mode:
         return False
 
 
-def _persistent_takes(M, N, K, K2):
-    """the library's own eligibility answer (gemm_pers_eligible through ur_gemm_swiglu_paired_supported: a K-contiguous bf16 [M, N] launch of
-    these sizes with no bias / residual) under the CURRENT ur_gemm_persistent_mode"""
-    return hip.gemm_swiglu_paired_supported(M, N // 2, K, K2, DEV)
+def _persistent_takes(M, N, K, K2=0, **launch):
+    """the library's own selection (hip.gemm_plan: ur_gemm_plan) for the K-contiguous bf16 [M, N] launch under test -- launch: its epilogue
+    operands, row strides and alpha, as hip.gemm_plan_args takes them -- under the CURRENT ur_gemm_persistent_mode"""
+    return hip.gemm_plan(M, N, K, K2, **launch)["kernel"] == "persistent"
+
+
+def _swiglu_bwd_launch(I, ld=None, **more):
+    """the SwiGLU backward epilogue's arguments as hip.gemm passes them: gu / dgu rows of ld (default 2 I) elements, C = dgu"""
+    ld = 2 * I if ld is None else ld
+    return dict(swiglu_gu=True, swiglu_dgu=True, swiglu_ldgu=ld, swiglu_lddgu=ld, ldc=ld, **more)
 
 
 _TABLES = {}
@@ -468,12 +474,15 @@ def _swiglu_bwd_case(tag, M, I, K, form, persistent, views):
         else:
             dact = dact + tb @ A
     K2 = 0 if form == "plain" else r
-    with _mode(1):
-        takes = _persistent_takes(M, I, K, K2)
-    with _mode(0):
-        assert not _persistent_takes(M, I, K, K2)
-    assert takes == persistent, f"{tag}: the launch is {'not ' if persistent else ''}taken by the persistent kernel"
     pad = 8 if I % 8 == 0 else 4
+    launch = _swiglu_bwd_launch(I, 2 * I + pad if views else None, drop_rank=r if form == "masked" else 0)
+    if K2 and views:
+        launch["ldr2"] = r + 8
+    with _mode(1):
+        takes = _persistent_takes(M, I, K, K2, **launch)
+    with _mode(0):
+        assert not _persistent_takes(M, I, K, K2, **launch)
+    assert takes == persistent, f"{tag}: the launch is {'not ' if persistent else ''}taken by the persistent kernel"
     gin = gu
     if views:
         base = torch.zeros((M, 2 * I + pad), dtype=BF16, device=DEV)
@@ -503,7 +512,10 @@ def _swiglu_bwd_case(tag, M, I, K, form, persistent, views):
 
 def _big_tile_shape():
     """tests/test_gpu_norm_f64.py: the smallest K-contiguous launch of gemm.hip's 256 x 256 configuration that stays off the persistent kernel"""
-    return 264, (256 // 2 - 1) * 256 + 8, 72
+    M, I, K = 264, (256 // 2 - 1) * 256 + 8, 72
+    pl = hip.gemm_plan(M, I, K, **_swiglu_bwd_launch(I))
+    assert (pl["kernel"], pl["tile"], pl["epi"]) == ("generic", 256, 1) and hip.gemm_plan(M, I - 256, K, **_swiglu_bwd_launch(I - 256))["tile"] == 128
+    return M, I, K
 
 
 @pytest.mark.parametrize("form", SWB_FORMS)
@@ -538,7 +550,7 @@ def test_swiglu_backward_epilogue_over_every_finite_bf16():
     gu = torch.cat([x[None, :].expand(M, I), ups[:, None].expand(M, I)], 1).contiguous().to(DEV)
     dact = d.to(F64)[:, None].expand(M, I).to(DEV)
     with _mode(1):
-        assert _persistent_takes(M, I, K, 0)
+        assert _persistent_takes(M, I, K, **_swiglu_bwd_launch(I))
         dgu, dgub = _sentinel_bf16(M, 2 * I, pattern=SENTINEL_NAN)
         hip.gemm(R.to(DEV), Wn.to(DEV), swiglu_bwd=(gu, dgu))
         again, _ = _sentinel_bf16(M, 2 * I, pattern=SENTINEL_NAN)
@@ -562,7 +574,7 @@ def test_swiglu_backward_epilogue_random_operands():
     gu = _gu(M, I, 1322).to(DEV)
     gate, up = gu[:, :I], gu[:, I:]
     with _mode(1):
-        assert _persistent_takes(M, I, K, 0)
+        assert _persistent_takes(M, I, K, **_swiglu_bwd_launch(I))
         dgu, dgub = _sentinel_bf16(M, 2 * I)
         hip.gemm(dyb.to(DEV), Wb.to(DEV), swiglu_bwd=(gu, dgu))
     _written(dgu, dgub, tag)
@@ -589,7 +601,7 @@ def test_second_k_range_widths_off_the_16_grid(K2):
     assert args[2].stride(0) == K2 and args[3].stride(0) == K2
     for mode, name in ((0, "generic"), (1, "persistent")):
         with _mode(mode):
-            assert _persistent_takes(M, N, K, K2) == bool(mode)
+            assert _persistent_takes(M, N, K, K2, alpha=1.0 / 16) == bool(mode)
             out, base = _sentinel_bf16(M, N)
             hip.gemm(args[0], args[1], R2=args[2], S2=args[3], alpha=1.0 / 16, out=out)
         _written(out, base, f"K2 {K2} {name}")

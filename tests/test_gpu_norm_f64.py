@@ -438,11 +438,14 @@ LAYOUTS = [(True, True), (True, False), (False, False), (False, True)]
 
 
 def _big_tile_shape(rk, sk):
-    """the smallest (M, N) every layout accepts for which gemm.hip's launch() takes the 256 x 256 configuration: M, N >= 256 and
-    ceil(M / 256) * ceil(N / 256) >= 256 workgroups (224 when both operands are K-strided), i.e. 2 x 128 (2 x 112) tiles -- with M, N
-    multiples of 8 (K-strided operands) and not of 256, which also keeps the launch off the persistent kernel"""
+    """the smallest (M, N) every layout accepts for which the library takes the generic kernel's 256 x 256 configuration (hip.gemm_plan holds
+    it: one tile column less is the 128 tile): 2 x 128 tiles, 2 x 112 when both operands are K-strided -- with M, N multiples of 8
+    (K-strided operands) and not of 256, which also keeps the launch off the persistent kernel"""
     wgs = 224 if (not rk and not sk) else 256
-    return 264, (wgs // 2 - 1) * 256 + 8, 72
+    M, N, K = 264, (wgs // 2 - 1) * 256 + 8, 72
+    pl = hip.gemm_plan(M, N, K, r_kcontig=rk, s_kcontig=sk)
+    assert (pl["kernel"], pl["tile"]) == ("generic", 256) and hip.gemm_plan(M, N - 256, K, r_kcontig=rk, s_kcontig=sk)["tile"] == 128
+    return M, N, K
 
 
 PERS_SHAPE = (2048, 4096, 256)      # 128 tiles of 256 x 256, K a multiple of 64 from 256 on, K-contiguous operands: the persistent kernel (gemm_pers.hip)
@@ -474,6 +477,10 @@ def test_gemm_epilogues_exact_products(shape, rk, sk):
     gelu'(aux); C = bf16(v); gelu_out = bf16(gelu(C)).  The shapes of the issue run on the generic kernel (gemm_body.hip.h); PERS_SHAPE is
     the smallest launch the persistent kernel takes, whose GELU epilogues (residual-free: EPI 6 / 7) are code of their own."""
     M, N, K = _big_tile_shape(rk, sk) if shape == "big" else shape
+    if shape == PERS_SHAPE:
+        takes = lambda **kw: hip.gemm_plan(M, N, K, **kw)      # noqa: E731
+        assert takes(bias=True)["kernel"] == "persistent" and not hip.gemm_plan(M - 256, N, K, bias=True)["kernel"] == "persistent"
+        assert (takes(bias=True, gelu_out=True)["epi"], takes(bias=True, gelu_grad_aux=True)["epi"]) == (6, 7)
     tag = f"gemm {M}x{N}x{K} rk{int(rk)} sk{int(sk)}"
     Rm, Sm, acc, bias, res, aux = _gemm_inputs(M, N, K)
     R = (Rm if rk else Rm.t()).contiguous().to(BF16).to(DEV)

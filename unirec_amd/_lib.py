@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -37,6 +37,11 @@ class GemmArgs(ctypes.Structure):
                 ("qkr_qw", c_void_p), ("qkr_kw", c_void_p), ("qkr_cos", c_void_p), ("qkr_sin", c_void_p),
                 ("qkr_S", c_int), ("qkr_nq_cols", c_int), ("qkr_nk_cols", c_int), ("qkr_eps", c_float),
                 ("swp_act", c_void_p), ("swp_ldact", c_i64), ("swp_I", c_int)]
+
+
+class GemmPlanInfo(ctypes.Structure):
+    """Mirror of ur_gemm_plan_info (kernel ids: UR_GEMM_KERNEL_*)."""
+    _fields_ = [("kernel", c_int), ("tile", c_int), ("epi", c_int), ("mode", c_int), ("gcw", c_int), ("splits", c_int)]
 
 
 class LoraArgs(ctypes.Structure):
@@ -115,6 +120,7 @@ SIGNATURES = {
     "ur_gemm_grouped_workspace_bytes": (c_i64, [ctypes.POINTER(GemmArgs), c_int]),
     "ur_gemm_grouped": (c_int, [ctypes.POINTER(GemmArgs), c_int, c_void_p, c_i64, c_void_p]),
     "ur_gemm_persistent_mode": (c_int, [c_int]),
+    "ur_gemm_plan": (c_int, [ctypes.POINTER(GemmArgs), c_int, ctypes.POINTER(GemmPlanInfo)]),
     "ur_attn_mode": (c_int, [c_int, c_int]),
     "ur_gemm_qkrope_supported": (c_int, [ctypes.POINTER(GemmArgs)]),
     "ur_gemm_swiglu_paired_supported": (c_int, [ctypes.POINTER(GemmArgs)]),

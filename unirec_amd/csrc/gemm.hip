@@ -27,6 +27,7 @@
 #include "gemm_common.hip.h"
 
 using urgemm::GemmP;
+using urgemm::GemmPlan;
 using urgemm::GemmGroups;
 using urgemm::GemmGroupSlot;
 using urgemm::UR_GEMM_MAX_GROUPS;
@@ -254,7 +255,7 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, float* __rest
 }
 
 template <bool RK, bool SK, bool OUTF32, int BM, int BN, int NWM, int NWN, int EPI = 0>
-int launch_cfg(GemmP p, int splits, hipStream_t st) {
+int launch_cfg(GemmP p, const GemmPlan& pl, hipStream_t st) {
   constexpr int S_BYTES = SK ? Tile<BN>::KC_BYTES : Tile<BN>::KS_BYTES;
   constexpr int R_BYTES = RK ? Tile<BM>::KC_BYTES : Tile<BM>::KS_BYTES;
   constexpr int RING = NSTAGE * (S_BYTES + R_BYTES), CTILE = BM * (BN * 2 + 16);      // bf16 tile == f32 half tile rows
@@ -266,50 +267,22 @@ int launch_cfg(GemmP p, int splits, hipStream_t st) {
     if (e != hipSuccess) UR_FAIL((int)e, "ur_gemm: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
   }
   p.gm = ur_cdiv(p.M, BM); p.gn = ur_cdiv(p.N, BN);
-  {
-    // Column chunks of n tiles in each XCD's walk.  With K = 1024 a tile's S panel is 512 KiB: an
-    // XCD's 32 concurrent tiles over 12 column tiles keep 6 MiB of S panels in play against a 4 MiB L2 and every tile
-    // re-fetches its panel from the Infinity Cache; chunks of 4 halve the fabric reads of the N = 3072 launches (FETCH_SIZE
-    // 2.24 -> 1.20 GB for gate_proj, profiles/r1_gemm_pmc.json) -- and cost 1 % of the joint step in alternating same-box
-    // runs (118.8 vs 117.5 seq/s), so the plain row-major runs stay the default.
-    // Round 2, merged launches (q|k|v: 16 column tiles, gate|up: 24; profiles/r2_gemm_pmc.json): the fabric reads reach
-    // 2.4 / 5.9 GB per launch (x8.7 / x21 of A + W, ~4 TB/s) and chunks of 4 are 2.1 / 3.6 % faster in isolation
-    // (tools/kernel_bench.py gemm_step), while launches of <= 12 column tiles still lose 1-3 %.  Inside the joint step,
-    // alternating same-box runs: chunks of 4 on the two wide launches only 516.6 vs 517.0 ms (nothing), chunks of 4 wherever
-    // they divide 551.8 vs 545.8 ms (+1.1 %) -- the plain order stays the default.
-    p.gcw = 0;
-    // chunks of 4 on launches of >= 16 column tiles (the merged q|k|v and gate|up forwards) -- time-neutral inside the
-    // step, but the fabric reads of those launches drop from x8.7 / x21 of A + W to what profiles/r2_gemm_pmc.json lists
-    const int cw = p.gn >= 16 ? 4 : 0;
-    if (cw > 0 && BM == 256 && (p.gm % 8) == 0 && p.gn > cw && (p.gn % cw) == 0) p.gcw = cw;
-  }
-  dim3 grid(p.gm * p.gn, 1, splits);
+  p.gcw = pl.gcw;
+  dim3 grid(p.gm * p.gn, 1, pl.splits);
   hipLaunchKernelGGL((gemm_kernel<RK, SK, OUTF32, BM, BN, NWM, NWN, EPI>), grid, dim3(NWM * NWN * 64), SMEM, st, p);
   UR_CHECK_LAUNCH("ur_gemm");
   return 0;
 }
 
-// Tile choice: 256x256 (8 waves, 130 FLOP per byte of L2 traffic) once the grid still fills the
-// chip (>= 256 workgroups); otherwise the 128x128 tile (4 waves, 2 workgroups per CU).
+// the generic kernel of a plan (EPI 1 / 2 exist for K-contiguous bf16 launches only)
 template <bool RK, bool SK, bool OUTF32>
-int launch(const GemmP& p, int splits, hipStream_t st) {
-  const long big_wgs = (long)ur_cdiv(p.M, 256) * ur_cdiv(p.N, 256) * splits;
+int launch(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
+  const bool big = pl.tile == 256;
   if constexpr (RK && SK && !OUTF32) {
-    if (urgemm::gemm_pers_eligible(p, splits, RK, SK, OUTF32)) return urgemm::gemm_pers_launch(p, st);    // gemm_pers.hip
-    if (p.sw_gu && p.sw_mode == 1) {       // SwiGLU backward epilogue: K-contiguous bf16 launches only (ur_gemm checks)
-      if (p.M >= 256 && p.N >= 256 && big_wgs >= 256) return launch_cfg<true, true, false, 256, 256, 2, 4, 1>(p, splits, st);
-      return launch_cfg<true, true, false, 128, 128, 2, 2, 1>(p, splits, st);
-    }
-    if (p.sw_gu && p.sw_mode == 2) {       // SwiGLU forward epilogue
-      if (p.M >= 256 && p.N >= 256 && big_wgs >= 256) return launch_cfg<true, true, false, 256, 256, 2, 4, 2>(p, splits, st);
-      return launch_cfg<true, true, false, 128, 128, 2, 2, 2>(p, splits, st);
-    }
+    if (pl.epi == 1) return big ? launch_cfg<true, true, false, 256, 256, 2, 4, 1>(p, pl, st) : launch_cfg<true, true, false, 128, 128, 2, 2, 1>(p, pl, st);
+    if (pl.epi == 2) return big ? launch_cfg<true, true, false, 256, 256, 2, 4, 2>(p, pl, st) : launch_cfg<true, true, false, 128, 128, 2, 2, 2>(p, pl, st);
   }
-  // (token-reduction launches, both operands K-strided: one round of 224+ big tiles already beats the small tile -- the host picks
-  // such splits, qformer.py:_split_k_for)
-  const long big_min = (!RK && !SK) ? 224 : 256;
-  if (p.M >= 256 && p.N >= 256 && big_wgs >= big_min) return launch_cfg<RK, SK, OUTF32, 256, 256, 2, 4>(p, splits, st);
-  return launch_cfg<RK, SK, OUTF32, 128, 128, 2, 2>(p, splits, st);
+  return big ? launch_cfg<RK, SK, OUTF32, 256, 256, 2, 4>(p, pl, st) : launch_cfg<RK, SK, OUTF32, 128, 128, 2, 2>(p, pl, st);
 }
 
 // split-K combine of a grouped launch: blockIdx.y = group
@@ -346,8 +319,6 @@ int launch_grouped_cfg(const GemmP& p, const GemmGroups& gs, int nwg, int splits
 
 }  // namespace
 
-static inline bool splits_ok(const ur_gemm_args* a) { return a->split_k <= 1; }
-
 #if UR_GEMM_STAMPS
 extern "C" int ur_lab_gemm_stamps(long long* host, int n) {
   return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gemm_stamps), sizeof(long long) * n);
@@ -360,7 +331,7 @@ static void fill_params(const ur_gemm_args* a, GemmP& p) {
   p.C = a->C; p.ldc = a->ldc; p.M = a->M; p.N = a->N; p.alpha = a->alpha;
   p.bias = a->bias; p.res = (const bf16_t*)a->residual; p.ldres = a->ldres;
   p.gelu_out = (bf16_t*)a->gelu_out; p.ldg = a->ldg; p.aux = (const bf16_t*)a->gelu_grad_aux; p.ldaux = a->ldaux;
-  p.gm = 0; p.gn = 0;   // set by launch_cfg for the chosen tile
+  p.gm = 0; p.gn = 0;   // set by the launcher for the plan's tile
   p.drop_bits = (const uint8_t*)a->drop_bits; p.drop_bits_ld = a->drop_bits_ld; p.drop_bits_stride = a->drop_bits_stride;
   p.drop_rank = a->drop_rank;
   p.drop_inv_keep = a->drop_bits ? 1.0f / (1.0f - a->drop_p) : 1.0f;
@@ -377,49 +348,137 @@ static void fill_params(const ur_gemm_args* a, GemmP& p) {
   p.ksplit_len = 0; p.slab_stride = 0; p.gcw = 0; p.pad_ = 0;
 }
 
-static bool swiglu_paired_ok(const ur_gemm_args* a, const GemmP& p) {
-  if (!a->swp_act || a->swp_I <= 0 || a->N != 2 * a->swp_I || (a->swp_I % 128)) return false;
-  if (!a->r_kcontig || !a->s_kcontig || a->c_f32 || a->split_k > 1) return false;
-  if (a->bias || a->residual || a->gelu_out || a->gelu_grad_aux || a->drop_bits || a->swiglu_gu || a->swiglu_gate || a->qkr_q || a->alpha != 1.0f) return false;
-  if ((a->swp_ldact & 7) || a->swp_ldact < a->swp_I || !UR_ALIGNED16(a->swp_act) || a->ldc < a->N) return false;
-  return urgemm::gemm_pers_eligible(p, 1, true, true, false);
+// ---- kernel selection ---------------------------------------------------------------------------------------------------------
+// Kernel, tile, epilogue instantiation and tile order of a launch are decided HERE and nowhere else: the launchers, ur_gemm_plan and the
+// *_supported queries read the GemmPlan.  Pure host arithmetic on sizes, strides, flags, the null-ness and low bits of pointers and the
+// ur_gemm_persistent_mode word: no HIP call, no pointer target.
+static std::atomic<int> g_pers_mode{-1};     // -1 = not set: the default (1); 0 = generic kernel only (A/B runs, bit-identity tests)
+extern "C" int ur_gemm_persistent_mode(int mode) { return g_pers_mode.exchange(mode < 0 ? -1 : (mode > 2 ? 1 : mode)); }
+
+// what gemm_pers.hip's kernel takes (its header comment): interior 256 x 256 tiles of K-contiguous bf16-output launches
+static bool pers_takes(const GemmP& p, int splits, bool rk, bool sk, bool outf32) {
+  constexpr int BM = 256, BN = 256;
+  const int set = g_pers_mode.load(std::memory_order_relaxed);
+  const int mode = set >= 0 ? set : 1;
+  if (!mode || !rk || !sk || outf32 || splits > 1) return false;
+  if ((p.M % BM) || (p.N % BN) || (p.K % BK) || p.K < 4 * BK) return false;
+  constexpr int min_tiles = 128;      // half a round already gains from the register epilogue (C2 item stage 21.66 -> 21.05 ms; 256 and 512 equal within noise, user stage unchanged)
+  if ((long)(p.M / BM) * (p.N / BN) < min_tiles) return false;
+  if ((long)(p.M / BM) * (p.N / BN) >= (1L << 20) || p.N / BN >= (1 << 12) || p.M / BM >= (1 << 15)) return false;      // fdiv: n * d < 2^32
+  if (p.sw_mode == 2) return false;
+  if (p.gelu_out || p.aux) {                 // the GELU epilogues (EPI 6 / 7): alone on the first K range, never with a residual
+    if ((p.gelu_out && p.aux) || p.res || p.K2 > 0 || p.sw_mode || p.qk_q || p.sp_act) return false;
+    if (p.gelu_out && ((p.ldg & 7) || (reinterpret_cast<uintptr_t>(p.gelu_out) & 15))) return false;
+    if (p.aux && ((p.ldaux & 7) || (reinterpret_cast<uintptr_t>(p.aux) & 15))) return false;
+  }
+  if (p.K2 > 0 && !p.drop_bits && p.K2 > BK) return false;      // the second K range is ONE K tile of the stream
+  if (p.drop_bits && p.K2 > 0) {
+    if (p.drop_rank != 16 || (p.K2 & 15)) return false;                        // the masked epilogue here is rank 16 only
+    // measured (tools/lab/gemm_pers_ab.py, C4 shapes): with the masked LoRA epilogue the persistent kernel wins at K = 1024 (+5 %, +17 %
+    // with the SwiGLU backward epilogue) and was even at K = 4096 / lost 1.5 % at K = 6144 in round 3 (profiles/r3_gemm_pers_ab.txt: 8 long
+    // tiles per CU, nothing to hide, and the joined epilogue costs two barrier intervals); with the whole-line epilogue stores of round 5
+    // it wins there too (K = 4096 +8 %, K = 6144 +2-3 %, same box), so the limit only keeps untested lengths off it
+    constexpr int kmax = 8192;
+    if (p.K > kmax) return false;
+  }
+  if (p.sw_mode == 1 && (p.bias || p.res)) return false;
+  // 16-byte pieces everywhere
+  if ((p.ldc & 7) || (reinterpret_cast<uintptr_t>(p.C) & 15)) return false;
+  if (p.res && ((p.ldres & 7) || (reinterpret_cast<uintptr_t>(p.res) & 15))) return false;
+  if (p.sw_mode == 1 && ((p.sw_ldgu & 7) || (p.sw_lddgu & 7) || (p.sw_I & 7) || (reinterpret_cast<uintptr_t>(p.sw_gu) & 15) ||
+                         (reinterpret_cast<uintptr_t>(p.sw_dgu) & 15))) return false;
+  // 32-bit lane offsets
+  if (p.lds * 16 >= (1L << 31) || p.ldr * 16 >= (1L << 31) || p.ldc * 32 >= (1L << 31)) return false;
+  // (every epilogue operand is addressed as uniform base + a 32-bit lane offset of at most 16 rows)
+  auto wide = [](long ld) { return ld * 32 >= (1L << 31); };
+  if ((p.res && wide(p.ldres)) || (p.sw_mode == 1 && (wide(p.sw_ldgu) || wide(p.sw_lddgu))) || (p.qk_q && (wide(p.qk_ldq) || wide(p.qk_ldk) || wide(p.qk_ldv))) ||
+      (p.sp_act && wide(p.sp_ldact)) || (p.gelu_out && wide(p.ldg)) || (p.aux && wide(p.ldaux)) || (p.drop_bits && (wide(p.drop_bits_ld) || wide(p.lds2) || wide(p.ldr2))))
+    return false;
+  return true;
 }
 
-extern "C" int ur_gemm_swiglu_paired_supported(const ur_gemm_args* a) {
-  if (!a || a->M <= 0 || a->N <= 0 || !a->R || !a->S) return 0;
-  GemmP p;
-  fill_params(a, p);
-  return swiglu_paired_ok(a, p) ? 1 : 0;
+// ur_gemm: the persistent kernel wherever it is eligible (the qkr_* / swp_* epilogues exist there only: NONE otherwise), else the generic one
+static GemmPlan gemm_select(const GemmP& p, int splits, bool rk, bool sk, bool outf32) {
+  GemmPlan pl = {UR_GEMM_KERNEL_GENERIC, 128, 0, 0, 0, splits};
+  if (pers_takes(p, splits, rk, sk, outf32)) {
+    pl.kernel = UR_GEMM_KERNEL_PERSISTENT; pl.tile = 256;
+    const int gm = p.M / 256, gn = p.N / 256;
+    // column chunks on wide launches (below): an XCD's 32 concurrent tiles cover (32 / cw) tile rows x cw tile columns and every A row
+    // panel crosses the fabric gn / cw times. Measured (gate|up, gn = 24, K = 1024; same process, interleaved): cw 6 1.448 ms, 12 1.482, 2
+    // 1.496, 4 1.507, row-major 1.528, 8 1.535 -- the order moves the launch by +-3 % although the fabric reads differ x2.5 between them;
+    // q|k|v (gn 16): 4 and 8 equal, 2 and row-major 1-2 % slower.
+    const int cw = (gn % 6) == 0 && gn >= 24 ? 6 : 4;
+    if (gn >= 16 && (gm % 8) == 0 && gn > cw && (gn % cw) == 0) pl.gcw = cw;
+    pl.mode = p.drop_bits != nullptr && p.K2 > 0 ? 2 : (p.K2 > 0 ? 1 : 0);
+    pl.epi = p.sp_act ? 4 : (p.qk_q ? 3 : (p.sw_mode == 1 ? 1 : (p.gelu_out ? 6 : (p.aux ? 7 : (p.res ? 2 : (p.bias ? 5 : 0))))));
+    return pl;
+  }
+  if (p.qk_q || p.sp_act) { pl.kernel = UR_GEMM_KERNEL_NONE; return pl; }
+  if (rk && sk && !outf32) pl.epi = p.sw_mode;      // SwiGLU backward (1) / forward (2) epilogue: K-contiguous bf16 launches only (gemm_check)
+  // Tile choice: 256x256 (8 waves, 130 FLOP per byte of L2 traffic) once the grid still fills the chip (>= 256 workgroups); otherwise the
+  // 128x128 tile (4 waves, 2 workgroups per CU). (token-reduction launches, both operands K-strided: one round of 224+ big tiles already
+  // beats the small tile -- the host picks such splits, qformer.py:_split_k_for)
+  const long big_wgs = (long)ur_cdiv(p.M, 256) * ur_cdiv(p.N, 256) * splits;
+  const long big_min = (!rk && !sk) ? 224 : 256;
+  if (p.M >= 256 && p.N >= 256 && big_wgs >= big_min) pl.tile = 256;
+  // Column chunks of n tiles in each XCD's walk.  With K = 1024 a tile's S panel is 512 KiB: an XCD's 32 concurrent tiles over 12 column
+  // tiles keep 6 MiB of S panels in play against a 4 MiB L2 and every tile re-fetches its panel from the Infinity Cache; chunks of 4 halve
+  // the fabric reads of the N = 3072 launches (FETCH_SIZE 2.24 -> 1.20 GB for gate_proj, profiles/r1_gemm_pmc.json) -- and cost 1 % of the
+  // joint step in alternating same-box runs (118.8 vs 117.5 seq/s), so the plain row-major runs stay the default. Round 2, merged launches
+  // (q|k|v: 16 column tiles, gate|up: 24; profiles/r2_gemm_pmc.json): the fabric reads reach 2.4 / 5.9 GB per launch (x8.7 / x21 of A + W,
+  // ~4 TB/s) and chunks of 4 are 2.1 / 3.6 % faster in isolation (tools/kernel_bench.py gemm_step), while launches of <= 12 column tiles
+  // still lose 1-3 %.  Inside the joint step, alternating same-box runs: chunks of 4 on the two wide launches only 516.6 vs 517.0 ms
+  // (nothing), chunks of 4 wherever they divide 551.8 vs 545.8 ms (+1.1 %) -- the plain order stays the default.
+  // chunks of 4 on launches of >= 16 column tiles (the merged q|k|v and gate|up forwards) -- time-neutral inside the step, but the fabric
+  // reads of those launches drop from x8.7 / x21 of A + W to what profiles/r2_gemm_pmc.json lists
+  const int gm = ur_cdiv(p.M, pl.tile), gn = ur_cdiv(p.N, pl.tile);
+  const int cw = gn >= 16 ? 4 : 0;
+  if (cw > 0 && pl.tile == 256 && (gm % 8) == 0 && gn > cw && (gn % cw) == 0) pl.gcw = cw;
+  return pl;
+}
+
+// ur_gemm_grouped: 256 x 256 when every product has at least one whole big tile in both directions and the grid still fills half the chip
+static GemmPlan gemm_select_grouped(const ur_gemm_args* a, int count) {
+  const int splits = a->split_k > 1 ? a->split_k : 1;
+  bool big = true;
+  long t256 = 0;
+  for (int i = 0; i < count; ++i) {
+    big = big && a[i].M >= 256 && a[i].N >= 256;
+    t256 += (long)ur_cdiv(a[i].M, 256) * ur_cdiv(a[i].N, 256);
+  }
+  big = big && t256 * splits >= 128;
+  return GemmPlan{UR_GEMM_KERNEL_GROUPED, big ? 256 : 128, 0, 0, 0, splits};
+}
+
+// the paired-SwiGLU epilogue (ur_gemm_args.swp_*), like the next one on the persistent kernel only
+static bool swiglu_paired_ok(const ur_gemm_args* a, const GemmPlan& pl) {
+  if (a->swp_I <= 0 || a->N != 2 * a->swp_I || (a->swp_I % 128)) return false;
+  if (a->bias || a->residual || a->gelu_out || a->gelu_grad_aux || a->drop_bits || a->swiglu_gu || a->swiglu_gate || a->qkr_q || a->alpha != 1.0f) return false;
+  if ((a->swp_ldact & 7) || a->swp_ldact < a->swp_I || !UR_ALIGNED16(a->swp_act) || a->ldc < a->N) return false;
+  return pl.kernel == UR_GEMM_KERNEL_PERSISTENT;
 }
 
 // the q/k-norm + RoPE epilogue exists on the persistent kernel only: everything ur_gemm_args.qkr_* promises, checked once
-static bool qkrope_ok(const ur_gemm_args* a, const GemmP& p) {
-  if (!a->qkr_q || !a->qkr_k || !a->qkr_v || !a->qkr_rstd || !a->qkr_qw || !a->qkr_kw || !a->qkr_cos || !a->qkr_sin) return false;
-  if (!a->r_kcontig || !a->s_kcontig || a->c_f32 || a->split_k > 1) return false;
+static bool qkrope_ok(const ur_gemm_args* a, const GemmPlan& pl) {
+  if (!a->qkr_k || !a->qkr_v || !a->qkr_rstd || !a->qkr_qw || !a->qkr_kw || !a->qkr_cos || !a->qkr_sin) return false;
   if (a->bias || a->residual || a->gelu_out || a->gelu_grad_aux || a->drop_bits || a->swiglu_gu || a->swiglu_gate || a->alpha != 1.0f) return false;
   if (a->qkr_S < 256 || (a->qkr_S % 256) || (a->qkr_nq_cols % 256) || (a->qkr_nk_cols % 256) || a->qkr_nq_cols < 0 || a->qkr_nk_cols < 0 ||
       a->qkr_nq_cols + a->qkr_nk_cols > a->N || ((a->N - a->qkr_nq_cols - a->qkr_nk_cols) % 256)) return false;
   if ((a->qkr_ldq & 7) || (a->qkr_ldk & 7) || (a->qkr_ldv & 7) || !UR_ALIGNED16(a->qkr_q) || !UR_ALIGNED16(a->qkr_k) || !UR_ALIGNED16(a->qkr_v) ||
       !UR_ALIGNED16(a->qkr_qw) || !UR_ALIGNED16(a->qkr_kw) || !UR_ALIGNED16(a->qkr_cos) || !UR_ALIGNED16(a->qkr_sin)) return false;
   if (a->qkr_ldq < a->qkr_nq_cols || a->qkr_ldk < a->qkr_nk_cols || a->qkr_ldv < a->N - a->qkr_nq_cols - a->qkr_nk_cols) return false;
-  return urgemm::gemm_pers_eligible(p, 1, true, true, false);
+  return pl.kernel == UR_GEMM_KERNEL_PERSISTENT;
 }
 
 extern "C" int ur_qkrope_perm(int c) { return ((c >> 4) & 1) * 64 + ((c >> 5) & 3) * 16 + (c & 15); }
-
-extern "C" int ur_gemm_qkrope_supported(const ur_gemm_args* a) {
-  if (!a || a->M <= 0 || a->N <= 0 || !a->R || !a->S) return 0;
-  GemmP p;
-  fill_params(a, p);
-  return qkrope_ok(a, p) ? 1 : 0;
-}
 
 extern "C" int64_t ur_gemm_workspace_bytes(const ur_gemm_args* a) {
   if (!a || a->split_k <= 1) return 0;
   return (int64_t)a->split_k * a->M * a->ldc * (int64_t)sizeof(float);
 }
 
-extern "C" int ur_gemm(const ur_gemm_args* a, void* workspace, int64_t workspace_bytes, void* stream) {
+// everything ur_gemm requires of its arguments but the split_k workspace (ur_gemm_plan asks for none); M == 0 or N == 0 passes: nothing runs
+static int gemm_check(const ur_gemm_args* a) {
   UR_REQUIRE(a != nullptr, "ur_gemm: null args");
   UR_REQUIRE(a->M >= 0 && a->N >= 0 && a->K >= 0 && a->K2 >= 0, "ur_gemm: negative dimension");
   if (a->M == 0 || a->N == 0) return 0;
@@ -446,9 +505,6 @@ extern "C" int ur_gemm(const ur_gemm_args* a, void* workspace, int64_t workspace
                "ur_gemm: split_k needs f32 output and no epilogue / second pair");
     // the slabs are dense [M, N] images of C and the combine copies whole slabs: a padded C would receive its gap columns too
     UR_REQUIRE(a->ldc == a->N, "ur_gemm: split_k needs a dense output, ldc == N (ldc=%ld, N=%d)", (long)a->ldc, a->N);
-    UR_REQUIRE(workspace && workspace_bytes >= ur_gemm_workspace_bytes(a) && UR_ALIGNED16(workspace),
-               "ur_gemm: split_k workspace too small (%lld < %lld)", (long long)workspace_bytes,
-               (long long)ur_gemm_workspace_bytes(a));
   }
   if (a->c_f32) {
     UR_REQUIRE(!a->residual && !a->gelu_out && !a->gelu_grad_aux, "ur_gemm: f32 output supports alpha/bias only");
@@ -475,42 +531,60 @@ extern "C" int ur_gemm(const ur_gemm_args* a, void* workspace, int64_t workspace
   }
   if (a->drop_bits) {
     UR_REQUIRE(a->K2 > 0 && ((a->drop_rank >= 8 && a->drop_rank <= 32 && (a->drop_rank % 8) == 0) || a->drop_rank == 64) && (a->K2 % a->drop_rank) == 0 &&
-               a->K2 / a->drop_rank <= 4 && a->r_kcontig && a->s_kcontig && splits_ok(a) && !a->c_f32,
+               a->K2 / a->drop_rank <= 4 && a->r_kcontig && a->s_kcontig && splits <= 1 && !a->c_f32,
                "ur_gemm: the masked LoRA epilogue needs K-contiguous operands, bf16 output, no split_k, rank in {8,16,24,32,64} and at most 4 adapters");
     UR_REQUIRE(a->drop_p >= 0.f && a->drop_p < 1.f && (a->drop_bits_ld % 16) == 0 && a->drop_bits_ld * 8 >= a->N && (a->drop_bits_stride % 8) == 0 &&
                ((uintptr_t)a->drop_bits & 15) == 0, "ur_gemm: bad LoRA dropout bit planes (rows of ur_lora_bits_ld(N) bytes, 16-byte aligned)");
   }
-  GemmP p;
+  return 0;
+}
+
+// check, fill, select: what ur_gemm launches for `a` (UR_GEMM_KERNEL_NONE: M == 0 or N == 0), or the refusal
+static int gemm_plan_of(const ur_gemm_args* a, GemmP& p, GemmPlan& pl) {
+  pl = GemmPlan{UR_GEMM_KERNEL_NONE, 0, 0, 0, 0, 0};
+  if (int rc = gemm_check(a)) return rc;
+  if (a->M == 0 || a->N == 0) return 0;
   fill_params(a, p);
-  p.slab_stride = 0;
+  pl = gemm_select(p, a->split_k > 1 ? a->split_k : 1, a->r_kcontig != 0, a->s_kcontig != 0, a->c_f32 != 0);
+  if (a->swp_act)
+    UR_REQUIRE(swiglu_paired_ok(a, pl), "ur_gemm: the paired SwiGLU forward epilogue is not available for these arguments (ur_gemm_swiglu_paired_supported)");
+  else if (a->qkr_q)
+    UR_REQUIRE(qkrope_ok(a, pl), "ur_gemm: the q/k-norm + RoPE epilogue is not available for these arguments (ur_gemm_qkrope_supported)");
+  return 0;
+}
+
+static int persistent_with(const ur_gemm_args* a, int epi) {
+  GemmP p; GemmPlan pl;
+  return gemm_plan_of(a, p, pl) == 0 && pl.kernel == UR_GEMM_KERNEL_PERSISTENT && pl.epi == epi;
+}
+extern "C" int ur_gemm_swiglu_paired_supported(const ur_gemm_args* a) { return persistent_with(a, 4); }
+extern "C" int ur_gemm_qkrope_supported(const ur_gemm_args* a) { return persistent_with(a, 3); }
+
+extern "C" int ur_gemm(const ur_gemm_args* a, void* workspace, int64_t workspace_bytes, void* stream) {
+  GemmP p; GemmPlan pl;
+  if (int rc = gemm_plan_of(a, p, pl)) return rc;
+  if (pl.kernel == UR_GEMM_KERNEL_NONE) return 0;
+  const int splits = pl.splits;
   if (splits > 1) {
-    int tiles = ur_cdiv(a->K, BK);
-    p.ksplit_len = ur_cdiv(tiles, splits) * BK;
+    UR_REQUIRE(workspace && workspace_bytes >= ur_gemm_workspace_bytes(a) && UR_ALIGNED16(workspace),
+               "ur_gemm: split_k workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)ur_gemm_workspace_bytes(a));
+    p.ksplit_len = ur_cdiv(ur_cdiv(a->K, BK), splits) * BK;
     p.slab_stride = (long)a->M * a->ldc;
     p.C = workspace;
   } else {
     p.ksplit_len = a->K > 0 ? ur_cdiv(a->K, BK) * BK : BK;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (a->swp_act) {
-    UR_REQUIRE(swiglu_paired_ok(a, p), "ur_gemm: the paired SwiGLU forward epilogue is not available for these arguments (ur_gemm_swiglu_paired_supported)");
-    return urgemm::gemm_pers_launch(p, st);
-  }
-  if (a->qkr_q) {
-    UR_REQUIRE(qkrope_ok(a, p), "ur_gemm: the q/k-norm + RoPE epilogue is not available for these arguments (ur_gemm_qkrope_supported)");
-    return urgemm::gemm_pers_launch(p, st);
-  }
+  if (pl.kernel == UR_GEMM_KERNEL_PERSISTENT) return urgemm::gemm_pers_launch(p, pl, st);
   int rc;
   const bool rk = a->r_kcontig != 0, sk = a->s_kcontig != 0, f32 = a->c_f32 != 0;
-  if (rk && sk) rc = f32 ? launch<true, true, true>(p, splits, st) : launch<true, true, false>(p, splits, st);
-  else if (rk && !sk) rc = f32 ? launch<true, false, true>(p, splits, st) : launch<true, false, false>(p, splits, st);
-  else if (!rk && !sk) rc = f32 ? launch<false, false, true>(p, splits, st) : launch<false, false, false>(p, splits, st);
-  else rc = f32 ? launch<false, true, true>(p, splits, st) : launch<false, true, false>(p, splits, st);
+  if (rk && sk) rc = f32 ? launch<true, true, true>(p, pl, st) : launch<true, true, false>(p, pl, st);
+  else if (rk && !sk) rc = f32 ? launch<true, false, true>(p, pl, st) : launch<true, false, false>(p, pl, st);
+  else if (!rk && !sk) rc = f32 ? launch<false, false, true>(p, pl, st) : launch<false, false, false>(p, pl, st);
+  else rc = f32 ? launch<false, true, true>(p, pl, st) : launch<false, true, false>(p, pl, st);
   if (rc) return rc;
   if (splits > 1) {
-    long total = (long)a->M * a->ldc;
-    UR_REQUIRE((total % 4) == 0, "ur_gemm: split_k output size must be a multiple of 4");
-    long total4 = total / 4;
+    const long total4 = (long)a->M * a->ldc / 4;
     int blocks = (int)((total4 + 255) / 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)workspace, (float*)a->C,
@@ -547,25 +621,14 @@ extern "C" int64_t ur_gemm_grouped_workspace_bytes(const ur_gemm_args* a, int32_
 
 extern "C" int ur_gemm_grouped(const ur_gemm_args* a, int32_t count, void* workspace, int64_t workspace_bytes, void* stream) {
   if (int rc = grouped_check(a, count)) return rc;
-  const int splits = a->split_k > 1 ? a->split_k : 1;
+  const GemmPlan pl = gemm_select_grouped(a, count);
+  const int splits = pl.splits, BT = pl.tile;
   if (splits > 1)
     UR_REQUIRE(workspace && UR_ALIGNED16(workspace) && workspace_bytes >= ur_gemm_grouped_workspace_bytes(a, count),
                "ur_gemm_grouped: split_k workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)ur_gemm_grouped_workspace_bytes(a, count));
-  // tile: 256 x 256 when every product has at least one whole big tile in both directions and the grid still fills half the chip
-  bool big = true;
-  long t256 = 0;
-  for (int i = 0; i < count; ++i) {
-    big = big && a[i].M >= 256 && a[i].N >= 256;
-    t256 += (long)ur_cdiv(a[i].M, 256) * ur_cdiv(a[i].N, 256);
-  }
-  big = big && t256 * splits >= 128;
-  const int BT = big ? 256 : 128;
   GemmP p;
   fill_params(a, p);
-  {
-    const int tiles = ur_cdiv(a->K, BK);
-    p.ksplit_len = ur_cdiv(tiles, splits) * BK;
-  }
+  p.ksplit_len = ur_cdiv(ur_cdiv(a->K, BK), splits) * BK;
   GemmGroups gs = {};
   ReduceGroups rg = {};
   gs.n = rg.n = count; gs.pad_ = rg.pad_ = 0;
@@ -591,7 +654,7 @@ extern "C" int ur_gemm_grouped(const ur_gemm_args* a, int32_t count, void* works
   }
   for (int i = count; i < UR_GEMM_MAX_GROUPS; ++i) { gs.g[i] = gs.g[count - 1]; rg.g[i] = rg.g[count - 1]; }
   hipStream_t st = (hipStream_t)stream;
-  int rc = big ? launch_grouped_cfg<256, 256, 2, 4>(p, gs, nwg, splits, st) : launch_grouped_cfg<128, 128, 2, 2>(p, gs, nwg, splits, st);
+  int rc = BT == 256 ? launch_grouped_cfg<256, 256, 2, 4>(p, gs, nwg, splits, st) : launch_grouped_cfg<128, 128, 2, 2>(p, gs, nwg, splits, st);
   if (rc) return rc;
   if (splits > 1) {
     int blocks = (int)((maxtot4 + 255) / 256);
@@ -599,5 +662,20 @@ extern "C" int ur_gemm_grouped(const ur_gemm_args* a, int32_t count, void* works
     hipLaunchKernelGGL(splitk_reduce_grouped_kernel, dim3(blocks, count), dim3(256), 0, st, rg, splits);
     UR_CHECK_LAUNCH("ur_gemm_grouped(splitk_reduce)");
   }
+  return 0;
+}
+
+// ur_gemm_plan (unirec_hip.h): the selection above for ur_gemm(a, ...) (count == 0) or ur_gemm_grouped(a, count, ...), after the entry
+// point's own argument checks
+extern "C" int ur_gemm_plan(const ur_gemm_args* a, int32_t count, ur_gemm_plan_info* out) {
+  UR_REQUIRE(out != nullptr && count >= 0, "ur_gemm_plan: null argument or negative count");
+  GemmP p; GemmPlan pl;
+  if (count == 0) {
+    if (int rc = gemm_plan_of(a, p, pl)) return rc;
+  } else {
+    if (int rc = grouped_check(a, count)) return rc;
+    pl = gemm_select_grouped(a, count);
+  }
+  out->kernel = pl.kernel; out->tile = pl.tile; out->epi = pl.epi; out->mode = pl.mode; out->gcw = pl.gcw; out->splits = pl.splits;
   return 0;
 }

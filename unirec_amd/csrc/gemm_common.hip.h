@@ -99,9 +99,19 @@ __device__ __forceinline__ void swap16f(float& a, float& b) {
   a = __uint_as_float(ua); b = __uint_as_float(ub);
 }
 
-// gemm_pers.hip: persistent 256x256 kernel for interior, K-contiguous, bf16-output launches (see its header comment).
-// Returns 0 and launches when the shape qualifies, 1 when the caller should use the generic kernel, < 0 / > 0 on error.
-bool gemm_pers_eligible(const GemmP& p, int splits, bool rk, bool sk, bool outf32);
-int gemm_pers_launch(GemmP p, hipStream_t st);
+// Which kernel a launch takes and how: the answer of gemm.hip's gemm_select / gemm_select_grouped, read by every launcher and by
+// ur_gemm_plan (host only; never a kernel argument).
+struct GemmPlan {
+  int kernel;   // UR_GEMM_KERNEL_*
+  int tile;     // 128 or 256 (rows = columns of the block tile)
+  int epi;      // template EPI of the kernel that runs: generic 0 / 1 / 2, persistent 0 .. 7
+  int mode;     // persistent kernel's MODE: 0 = no second K range, 1 = second K range in the K stream, 2 = masked LoRA epilogue
+  int gcw;      // GemmP::gcw of the launch
+  int splits;
+};
+
+// gemm_pers.hip: persistent 256x256 kernel for interior, K-contiguous, bf16-output launches (see its header comment): launches
+// gemm_pers_kernel<pl.epi, pl.mode> of a plan whose kernel is UR_GEMM_KERNEL_PERSISTENT.
+int gemm_pers_launch(GemmP p, const GemmPlan& pl, hipStream_t st);
 
 }  // namespace urgemm

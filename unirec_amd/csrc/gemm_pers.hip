@@ -581,7 +581,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pers_kernel(GemmP p, TileOrder or
         static_assert(EPI == 1, "the remaining epilogue is the SwiGLU backward");
         // ---- SwiGLU backward with whole-line loads and stores: the f32 products change lanes first (the line merge on 8 registers per
         // column group), then gate / up arrive and dgate / dup leave in the merged layout: 8 rows x 128 contiguous bytes per
-        // instruction.  (No bias / residual: gemm_pers_eligible.)  vmcnt counts loads and stores in issue order, so a load issued AFTER a
+        // instruction.  (No bias / residual: gemm.hip, pers_takes.)  vmcnt counts loads and stores in issue order, so a load issued AFTER a
         // batch of stores cannot be waited for without those stores' acknowledgements: the gate / up pieces are issued two row blocks
         // ahead of the stores they would otherwise queue behind.
         __builtin_amdgcn_sched_barrier(0);
@@ -684,64 +684,9 @@ int launch_pers(const GemmP& p, hipStream_t st) {
 
 namespace urgemm {
 
-static std::atomic<int> g_pers_mode{-1};     // -1 = not set: the default (1); 0 = generic kernel only (A/B runs, bit-identity tests)
-
-bool gemm_pers_eligible(const GemmP& p, int splits, bool rk, bool sk, bool outf32) {
-  const int set = g_pers_mode.load(std::memory_order_relaxed);
-  const int mode = set >= 0 ? set : 1;
-  if (!mode || !rk || !sk || outf32 || splits > 1) return false;
-  if ((p.M % BM) || (p.N % BN) || (p.K % BK) || p.K < 4 * BK) return false;
-  constexpr int min_tiles = 128;      // half a round already gains from the register epilogue (C2 item stage 21.66 -> 21.05 ms; 256 and 512 equal within noise, user stage unchanged)
-  if ((long)(p.M / BM) * (p.N / BN) < min_tiles) return false;
-  if ((long)(p.M / BM) * (p.N / BN) >= (1L << 20) || p.N / BN >= (1 << 12) || p.M / BM >= (1 << 15)) return false;      // fdiv: n * d < 2^32
-  if (p.sw_mode == 2) return false;
-  if (p.gelu_out || p.aux) {                 // the GELU epilogues (EPI 6 / 7): alone on the first K range, never with a residual
-    if ((p.gelu_out && p.aux) || p.res || p.K2 > 0 || p.sw_mode || p.qk_q || p.sp_act) return false;
-    if (p.gelu_out && ((p.ldg & 7) || (reinterpret_cast<uintptr_t>(p.gelu_out) & 15))) return false;
-    if (p.aux && ((p.ldaux & 7) || (reinterpret_cast<uintptr_t>(p.aux) & 15))) return false;
-  }
-  if (p.K2 > 0 && !p.drop_bits && p.K2 > BK) return false;
-  if (p.drop_bits && p.K2 > 0) {
-    if (p.drop_rank != 16 || (p.K2 & 15)) return false;                        // the masked epilogue here is rank 16 only
-    // measured (tools/lab/gemm_pers_ab.py, C4 shapes): with the masked LoRA epilogue the persistent kernel wins at K = 1024 (+5 %, +17 %
-    // with the SwiGLU backward epilogue) and was even at K = 4096 / lost 1.5 % at K = 6144 in round 3 (profiles/r3_gemm_pers_ab.txt: 8 long
-    // tiles per CU, nothing to hide, and the joined epilogue costs two barrier intervals); with the whole-line epilogue stores of round 5
-    // it wins there too (K = 4096 +8 %, K = 6144 +2-3 %, same box), so the limit only keeps untested lengths off it
-    constexpr int kmax = 8192;
-    if (p.K > kmax) return false;
-  }
-  if (p.sw_mode == 1 && (p.bias || p.res)) return false;
-  // 16-byte pieces everywhere
-  if ((p.ldc & 7) || (reinterpret_cast<uintptr_t>(p.C) & 15)) return false;
-  if (p.res && ((p.ldres & 7) || (reinterpret_cast<uintptr_t>(p.res) & 15))) return false;
-  if (p.sw_mode == 1 && ((p.sw_ldgu & 7) || (p.sw_lddgu & 7) || (p.sw_I & 7) || (reinterpret_cast<uintptr_t>(p.sw_gu) & 15) ||
-                         (reinterpret_cast<uintptr_t>(p.sw_dgu) & 15))) return false;
-  // 32-bit lane offsets
-  if (p.lds * 16 >= (1L << 31) || p.ldr * 16 >= (1L << 31) || p.ldc * 32 >= (1L << 31)) return false;
-  // (every epilogue operand is addressed as uniform base + a 32-bit lane offset of at most 16 rows)
-  auto wide = [](long ld) { return ld * 32 >= (1L << 31); };
-  if ((p.res && wide(p.ldres)) || (p.sw_mode == 1 && (wide(p.sw_ldgu) || wide(p.sw_lddgu))) || (p.qk_q && (wide(p.qk_ldq) || wide(p.qk_ldk) || wide(p.qk_ldv))) ||
-      (p.sp_act && wide(p.sp_ldact)) || (p.gelu_out && wide(p.ldg)) || (p.aux && wide(p.ldaux)) || (p.drop_bits && (wide(p.drop_bits_ld) || wide(p.lds2) || wide(p.ldr2))))
-    return false;
-  return true;
-}
-
-int gemm_pers_launch(GemmP p, hipStream_t st) {
-  p.gm = p.M / BM; p.gn = p.N / BN;
-  p.gcw = 0;
-  {
-    // column chunks on wide launches (gemm.hip): an XCD's 32 concurrent tiles cover (32 / cw) tile rows x cw tile columns and
-    // every A row panel crosses the fabric gn / cw times.
-    // Measured (gate|up, gn = 24, K = 1024; same process, interleaved): cw 6 1.448 ms, 12 1.482, 2 1.496, 4 1.507, row-major
-    // 1.528, 8 1.535 -- the order moves the launch by +-3 % although the fabric reads differ x2.5 between them; q|k|v (gn 16):
-    // 4 and 8 equal, 2 and row-major 1-2 % slower.
-    const int cw = (p.gn % 6) == 0 && p.gn >= 24 ? 6 : 4;
-    if (p.gn >= 16 && (p.gm % 8) == 0 && p.gn > cw && (p.gn % cw) == 0) p.gcw = cw;
-  }
-  const bool drop = p.drop_bits != nullptr && p.K2 > 0;
-  const int mode = drop ? 2 : (p.K2 > 0 ? 1 : 0);
-  const int epi = p.sp_act ? 4 : (p.qk_q ? 3 : (p.sw_mode == 1 ? 1 : (p.gelu_out ? 6 : (p.aux ? 7 : (p.res ? 2 : (p.bias ? 5 : 0))))));
-#define UR_PERS_CASE(E, MD) if (epi == E && mode == MD) return launch_pers<E, MD>(p, st)
+int gemm_pers_launch(GemmP p, const GemmPlan& pl, hipStream_t st) {
+  p.gm = p.M / BM; p.gn = p.N / BN; p.gcw = pl.gcw;
+#define UR_PERS_CASE(E, MD) if (pl.epi == E && pl.mode == MD) return launch_pers<E, MD>(p, st)
   UR_PERS_CASE(0, 0); UR_PERS_CASE(0, 1); UR_PERS_CASE(0, 2);
   UR_PERS_CASE(1, 0); UR_PERS_CASE(1, 1); UR_PERS_CASE(1, 2);
   UR_PERS_CASE(2, 0); UR_PERS_CASE(2, 1); UR_PERS_CASE(2, 2);
@@ -750,7 +695,7 @@ int gemm_pers_launch(GemmP p, hipStream_t st) {
   UR_PERS_CASE(5, 0); UR_PERS_CASE(5, 1); UR_PERS_CASE(5, 2);
   UR_PERS_CASE(6, 0); UR_PERS_CASE(7, 0);
 #undef UR_PERS_CASE
-  UR_FAIL(-1, "ur_gemm(persistent): no kernel for epilogue %d, mode %d", epi, mode);
+  UR_FAIL(-1, "ur_gemm(persistent): no kernel for epilogue %d, mode %d", pl.epi, pl.mode);
 }
 
 }  // namespace urgemm
@@ -760,8 +705,3 @@ extern "C" int ur_lab_pers_stamps(long long* host, int n) {
   return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_pers_stamps), sizeof(long long) * n);
 }
 #endif
-
-extern "C" int ur_gemm_persistent_mode(int mode) {
-  const int prev = urgemm::g_pers_mode.exchange(mode < 0 ? -1 : (mode > 2 ? 1 : mode));
-  return prev;
-}

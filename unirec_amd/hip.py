@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, AttnBwdArgs, AttnPlanInfo, CatalogSelect, GemmArgs, LoraArgs, check
+from ._lib import AttnArgs, AttnBwdArgs, AttnPlanInfo, CatalogSelect, GemmArgs, GemmPlanInfo, LoraArgs, check
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -87,6 +87,44 @@ def workspace(nbytes, device, tag="default"):
 
 
 # ------------------------------------------------------------------------------------------------
+GEMM_MAX_GROUPS = 8
+GEMM_KERNELS = ("none", "generic", "persistent", "grouped")      # index = UR_GEMM_KERNEL_* (include/unirec_hip.h)
+_ADDR = 4096      # an aligned non-null address: what the selection queries put where a launch has a tensor (they follow no pointer)
+
+
+def _operand(t, what, shape=None):
+    if t.dtype != BF16 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or (shape is not None and tuple(t.shape) != shape[0]):
+        raise ValueError(f"{what} must be a {'2-D bf16' if shape is None else 'bf16 ' + shape[1]} device tensor with unit inner stride")
+
+
+def _gemm_args(R, ldr, S, lds, C, ldc, M, N, K, r_kcontig=1, s_kcontig=1, c_f32=0, alpha=1.0, split_k=1, pair2=None):
+    """The operand and output fields of a GemmArgs from addresses and row strides; pair2 = (R2, ldr2, S2, lds2, K2)."""
+    a = GemmArgs()
+    a.R, a.ldr, a.r_kcontig = R, ldr, int(r_kcontig)
+    a.S, a.lds, a.s_kcontig = S, lds, int(s_kcontig)
+    a.C, a.ldc, a.c_f32 = C, ldc, int(c_f32)
+    a.M, a.N, a.K, a.alpha, a.split_k = M, N, K, float(alpha), int(split_k)
+    if pair2 is not None:
+        a.R2, a.ldr2, a.S2, a.lds2, a.K2 = pair2
+    return a
+
+
+def _pair2(R2, S2, r_kcontig=True):
+    return None if R2 is None else (R2.data_ptr(), R2.stride(0), S2.data_ptr(), S2.stride(0), R2.shape[1] if r_kcontig else R2.shape[0])
+
+
+def _launch(fn, what, args, entry):
+    """check(fn(*args, stream)); when PROFILE is a list (bench.py's roofline leg) HIP events on the launching stream bracket the call
+    and (e0, e1, *entry()) is appended."""
+    if PROFILE is None:
+        return check(fn(*args, _stream()), what)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    check(fn(*args, _stream()), what)
+    e1.record()
+    PROFILE.append((e0, e1, *entry()))
+
+
 def gemm(R, S, *, r_kcontig=True, s_kcontig=True, M=None, N=None, K=None, out=None, out_f32=False, alpha=1.0,
          bias=None, residual=None, gelu_out=None, gelu_grad_aux=None, R2=None, S2=None, split_k=1, drop=None,
          swiglu_bwd=None, swiglu_fwd=None, swiglu_paired=None):
@@ -98,9 +136,8 @@ def gemm(R, S, *, r_kcontig=True, s_kcontig=True, M=None, N=None, K=None, out=No
     gate | up in the standard order and act = silu(gate) * up leaves beside it (persistent kernel only: gemm_swiglu_paired_supported).
     See ur_gemm_args in include/unirec_hip.h."""
     lib = _lib.load()
-    for t, n in ((R, "R"), (S, "S")):
-        if t.dtype != BF16 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1:
-            raise ValueError(f"gemm: {n} must be a 2-D bf16 device tensor with unit inner stride")
+    _operand(R, "gemm: R")
+    _operand(S, "gemm: S")
     if M is None:
         M = R.shape[0] if r_kcontig else R.shape[1]
     if N is None:
@@ -112,21 +149,14 @@ def gemm(R, S, *, r_kcontig=True, s_kcontig=True, M=None, N=None, K=None, out=No
         raise ValueError(f"gemm: K mismatch R:{K} S:{Ks}")
     if swiglu_bwd is not None:
         gu_, dgu_ = swiglu_bwd
-        for t, n in ((gu_, "gu"), (dgu_, "dgu")):
-            if t.dtype != BF16 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != M or t.shape[1] != 2 * N:
-                raise ValueError(f"gemm: swiglu_bwd {n} must be a bf16 [M, 2N] device tensor with unit inner stride")
+        _operand(gu_, "gemm: swiglu_bwd gu", ((M, 2 * N), "[M, 2N]"))
+        _operand(dgu_, "gemm: swiglu_bwd dgu", ((M, 2 * N), "[M, 2N]"))
         out = dgu_            # C is not written in this mode; any valid bf16 pointer with ldc >= N
     if out is None:
         out = torch.empty((M, N), dtype=F32 if out_f32 else BF16, device=R.device)
-    a = GemmArgs()
-    a.R, a.ldr, a.r_kcontig = R.data_ptr(), R.stride(0), int(r_kcontig)
-    a.S, a.lds, a.s_kcontig = S.data_ptr(), S.stride(0), int(s_kcontig)
-    a.K = K
-    if R2 is not None:
-        a.R2, a.ldr2, a.S2, a.lds2 = R2.data_ptr(), R2.stride(0), S2.data_ptr(), S2.stride(0)
-        a.K2 = R2.shape[1] if r_kcontig else R2.shape[0]
-    a.C, a.ldc, a.c_f32 = out.data_ptr(), out.stride(0), int(out.dtype == F32)
-    a.M, a.N, a.alpha = M, N, float(alpha)
+    f32 = int(out.dtype == F32)
+    a = _gemm_args(R.data_ptr(), R.stride(0), S.data_ptr(), S.stride(0), out.data_ptr(), out.stride(0), M, N, K, r_kcontig, s_kcontig, f32,
+                   alpha, split_k, _pair2(R2, S2, r_kcontig))
     a.bias = _p(bias)
     if residual is not None:
         a.residual, a.ldres = residual.data_ptr(), residual.stride(0)
@@ -134,21 +164,17 @@ def gemm(R, S, *, r_kcontig=True, s_kcontig=True, M=None, N=None, K=None, out=No
         a.gelu_out, a.ldg = gelu_out.data_ptr(), gelu_out.stride(0)
     if gelu_grad_aux is not None:
         a.gelu_grad_aux, a.ldaux = gelu_grad_aux.data_ptr(), gelu_grad_aux.stride(0)
-    a.split_k = int(split_k)
     if swiglu_bwd is not None:
         a.swiglu_gu, a.swiglu_ldgu = gu_.data_ptr(), gu_.stride(0)
         a.swiglu_dgu, a.swiglu_lddgu, a.swiglu_I = dgu_.data_ptr(), dgu_.stride(0), N
     if swiglu_fwd is not None:
         gate_, act_ = swiglu_fwd
-        for t, n in ((gate_, "gate"), (act_, "act")):
-            if t.dtype != BF16 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != M or t.shape[1] != N:
-                raise ValueError(f"gemm: swiglu_fwd {n} must be a bf16 [M, N] device tensor with unit inner stride")
+        _operand(gate_, "gemm: swiglu_fwd gate", ((M, N), "[M, N]"))
+        _operand(act_, "gemm: swiglu_fwd act", ((M, N), "[M, N]"))
         a.swiglu_gate, a.swiglu_ldgate, a.swiglu_act, a.swiglu_ldact = gate_.data_ptr(), gate_.stride(0), act_.data_ptr(), act_.stride(0)
     if swiglu_paired is not None:
-        act_ = swiglu_paired
-        if act_.dtype != BF16 or not act_.is_cuda or act_.dim() != 2 or act_.stride(1) != 1 or act_.shape[0] != M or act_.shape[1] * 2 != N:
-            raise ValueError("gemm: swiglu_paired act must be a bf16 [M, N/2] device tensor with unit inner stride")
-        a.swp_act, a.swp_ldact, a.swp_I = act_.data_ptr(), act_.stride(0), N // 2
+        _operand(swiglu_paired, "gemm: swiglu_paired act", ((M, N // 2), "[M, N/2]"))
+        a.swp_act, a.swp_ldact, a.swp_I = swiglu_paired.data_ptr(), swiglu_paired.stride(0), N // 2
     if drop is not None:
         bits, pdrop, rank = drop
         a.drop_bits, a.drop_bits_ld, a.drop_bits_stride = bits.data_ptr(), bits.stride(1), bits.stride(0)
@@ -157,15 +183,9 @@ def gemm(R, S, *, r_kcontig=True, s_kcontig=True, M=None, N=None, K=None, out=No
     if split_k > 1:
         wsb = lib.ur_gemm_workspace_bytes(ctypes.byref(a))
         ws = workspace(wsb, R.device, "gemm").data_ptr()
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(lib.ur_gemm(ctypes.byref(a), ws, wsb, _stream()), "ur_gemm")
-        e1.record()
-        PROFILE.append((e0, e1, int(r_kcontig), int(s_kcontig), int(out.dtype == F32), M, N, K + int(a.K2), int(split_k),
-                        1 if swiglu_bwd is not None else (2 if swiglu_fwd is not None else (4 if swiglu_paired is not None else 0))))
-        return out
-    check(lib.ur_gemm(ctypes.byref(a), ws, wsb, _stream()), "ur_gemm")
+    _launch(lib.ur_gemm, "ur_gemm", (ctypes.byref(a), ws, wsb),
+            lambda: (int(r_kcontig), int(s_kcontig), f32, M, N, K + int(a.K2), int(split_k),
+                     1 if swiglu_bwd is not None else (2 if swiglu_fwd is not None else (4 if swiglu_paired is not None else 0))))
     return out
 
 
@@ -178,31 +198,11 @@ def qkrope_perm(head_dim=128):
     return torch.tensor([lib.ur_qkrope_perm(c) for c in range(128)], dtype=torch.long)
 
 
-def _qkrope_args(R, S, R2, S2, qw, kw, cos, sin, Sseq, nq_cols, nk_cols, eps, outs):
-    M, N, K = R.shape[0], S.shape[0], R.shape[1]
-    a = GemmArgs()
-    a.R, a.ldr, a.r_kcontig = R.data_ptr(), R.stride(0), 1
-    a.S, a.lds, a.s_kcontig = S.data_ptr(), S.stride(0), 1
-    a.K, a.M, a.N, a.alpha, a.split_k = K, M, N, 1.0, 1
-    if R2 is not None:
-        a.R2, a.ldr2, a.S2, a.lds2, a.K2 = R2.data_ptr(), R2.stride(0), S2.data_ptr(), S2.stride(0), R2.shape[1]
-    q, k, v, rstd = outs
-    a.C, a.ldc, a.c_f32 = q.data_ptr(), q.stride(0), 0                # not written in this mode: any valid pointer
-    a.qkr_q, a.qkr_ldq, a.qkr_k, a.qkr_ldk, a.qkr_v, a.qkr_ldv = q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0)
-    a.qkr_rstd = rstd.data_ptr()
-    a.qkr_qw, a.qkr_kw, a.qkr_cos, a.qkr_sin = qw.data_ptr(), kw.data_ptr(), cos.data_ptr(), sin.data_ptr()
-    a.qkr_S, a.qkr_nq_cols, a.qkr_nk_cols, a.qkr_eps = int(Sseq), int(nq_cols), int(nk_cols), float(eps)
-    return a
-
-
 def swiglu_pair_rows(I):
     """Row order of the merged gate|up weight (and of its LoRA B operand) for the paired SwiGLU epilogue: blocks of 128 gate rows
     alternate with the 128 up rows of the same features -- index tensor `rows` with W_paired = W[rows], W = [gate; up] [2 I, K]."""
     t = torch.arange(I // 128)[:, None, None] * 128 + torch.arange(128)[None, None, :]          # [I/128, 1, 128]
     return torch.cat([t, t + I], dim=1).reshape(-1)
-
-
-GEMM_MAX_GROUPS = 8
 
 
 def gemm_grouped(products, split_k=1):
@@ -214,10 +214,9 @@ def gemm_grouped(products, split_k=1):
     if not 1 <= n <= GEMM_MAX_GROUPS:
         raise ValueError(f"gemm_grouped: 1 .. {GEMM_MAX_GROUPS} products per launch (got {n})")
     arr = (GemmArgs * n)()
-    for a, (R, S, out) in zip(arr, products):
-        for t_, nm in ((R, "R"), (S, "S")):
-            if t_.dtype != BF16 or not t_.is_cuda or t_.dim() != 2 or t_.stride(1) != 1:
-                raise ValueError(f"gemm_grouped: {nm} must be a 2-D bf16 device tensor with unit inner stride")
+    for i, (R, S, out) in enumerate(products):
+        _operand(R, "gemm_grouped: R")
+        _operand(S, "gemm_grouped: S")
         if R.shape[0] != S.shape[0]:
             raise ValueError(f"gemm_grouped: token counts differ ({R.shape[0]} vs {S.shape[0]})")
         if not out.is_cuda:
@@ -225,62 +224,63 @@ def gemm_grouped(products, split_k=1):
         # (a row stride above the row length is the library's to judge: ur_gemm_grouped takes it without split_k and refuses it with)
         if out.dtype != F32 or out.dim() != 2 or tuple(out.shape) != (R.shape[1], S.shape[1]) or out.stride(1) != 1:
             raise ValueError(f"gemm_grouped: out must be f32 [{R.shape[1]}, {S.shape[1]}] with unit inner stride, got {out.dtype} {tuple(out.shape)}")
-        a.R, a.ldr, a.r_kcontig = R.data_ptr(), R.stride(0), 0
-        a.S, a.lds, a.s_kcontig = S.data_ptr(), S.stride(0), 0
-        a.K, a.M, a.N, a.alpha = R.shape[0], R.shape[1], S.shape[1], 1.0
-        a.C, a.ldc, a.c_f32 = out.data_ptr(), out.stride(0), 1
-        a.split_k = int(split_k)
+        arr[i] = _gemm_args(R.data_ptr(), R.stride(0), S.data_ptr(), S.stride(0), out.data_ptr(), out.stride(0), R.shape[1], S.shape[1], R.shape[0],
+                            0, 0, 1, 1.0, split_k)
     ws, wsb = 0, 0
     if split_k > 1:
         wsb = lib.ur_gemm_grouped_workspace_bytes(arr, n)
         ws = workspace(wsb, products[0][0].device, "gemm_grouped").data_ptr()
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(lib.ur_gemm_grouped(arr, n, ws, wsb, _stream()), "ur_gemm_grouped")
-        e1.record()
+
+    def entry():
         # (one entry for the launch: M = the products' output rows summed at the widest N -- FLOP-exact only for equal N; see flops below)
         fl = sum(2.0 * R.shape[0] * R.shape[1] * S.shape[1] for R, S, _ in products)
         K = products[0][0].shape[0]
         N = max(S.shape[1] for _, S, _ in products)
-        PROFILE.append((e0, e1, 0, 0, 1, int(round(fl / (2.0 * K * N))), N, K, int(split_k), 0))
-        return
-    check(lib.ur_gemm_grouped(arr, n, ws, wsb, _stream()), "ur_gemm_grouped")
+        return 0, 0, 1, int(round(fl / (2.0 * K * N))), N, K, int(split_k), 0
+    _launch(lib.ur_gemm_grouped, "ur_gemm_grouped", (arr, n, ws, wsb), entry)
 
 
-def gemm_swiglu_paired_supported(M, I, K, K2, device):
-    """True when the merged gate|up projection of these sizes can carry the SwiGLU forward in its epilogue."""
-    lib = _lib.load()
-    d = torch.empty(16, dtype=BF16, device=device)
-    a = GemmArgs()
-    a.R = a.S = a.C = a.swp_act = d.data_ptr()
-    a.ldr = a.lds = K
-    a.r_kcontig = a.s_kcontig = 1
-    a.K, a.M, a.N, a.alpha, a.split_k, a.ldc = K, M, 2 * I, 1.0, 1, 2 * I
-    if K2:
-        a.R2 = a.S2 = d.data_ptr(); a.ldr2 = a.lds2 = K2; a.K2 = K2
-    a.swp_ldact, a.swp_I = I, I
-    return bool(lib.ur_gemm_swiglu_paired_supported(ctypes.byref(a)))
+def gemm_plan_args(M, N, K, K2=0, *, r_kcontig=True, s_kcontig=True, out_f32=False, split_k=1, alpha=1.0, ldc=None, drop_rank=0, **ptrs):
+    """A GemmArgs of these sizes for the selection queries: dense rows, and _ADDR in C and in every pointer field named in ptrs
+    (bias=True, swiglu_gu=True, ...; C=address sets another one)."""
+    pair2 = (_ADDR, K2 if r_kcontig else M, _ADDR, K2 if s_kcontig else N, K2) if K2 else None
+    a = _gemm_args(_ADDR, K if r_kcontig else M, _ADDR, K if s_kcontig else N, _ADDR, N if ldc is None else ldc, M, N, K, r_kcontig, s_kcontig,
+                   out_f32, alpha, split_k, pair2)
+    a.ldres = a.ldg = a.ldaux = a.swiglu_ldgate = a.swiglu_ldact = a.swiglu_I = N
+    a.swiglu_ldgu = a.swiglu_lddgu = 2 * N
+    if drop_rank:
+        a.drop_bits, a.drop_bits_ld, a.drop_bits_stride, a.drop_rank, a.drop_p = _ADDR, (N + 127) // 128 * 16, (N + 127) // 128 * 16 * M, drop_rank, 0.5
+    for name, v in ptrs.items():
+        setattr(a, name, _ADDR if v is True else int(v))
+    return a
 
 
-def gemm_qkrope_supported(M, N, K, K2, Sseq, nq_cols, nk_cols, device, alpha=1.0, bias=None):
+def gemm_plan(a, *sizes, **flags):
+    """Which kernel ur_gemm / ur_gemm_grouped launches and how, under the current gemm_persistent_mode (ur_gemm_plan): a dict with
+    kernel (a name from GEMM_KERNELS), tile, epi, mode, gcw and splits.  a: a GemmArgs (ur_gemm), a sequence of them (ur_gemm_grouped),
+    or M followed by N, K[, K2] and the keywords of gemm_plan_args.  No tensor and no device is needed.  Raises UniRecHipError where the
+    entry point would refuse the arguments."""
+    if isinstance(a, int):
+        a = gemm_plan_args(a, *sizes, **flags)
+    count = 0 if isinstance(a, GemmArgs) else len(a)
+    out = GemmPlanInfo()
+    check(_lib.load().ur_gemm_plan((GemmArgs * count)(*a) if count else ctypes.byref(a), count, ctypes.byref(out)), "ur_gemm_plan")
+    return dict(kernel=GEMM_KERNELS[out.kernel], tile=int(out.tile), epi=int(out.epi), mode=int(out.mode), gcw=int(out.gcw), splits=int(out.splits))
+
+
+def gemm_swiglu_paired_supported(M, I, K, K2, device=None):
+    """True when the merged gate|up projection of these sizes can carry the SwiGLU forward in its epilogue (`device` is not needed)."""
+    a = gemm_plan_args(M, 2 * I, K, K2, swp_act=True, swp_ldact=I, swp_I=I)
+    return bool(_lib.load().ur_gemm_swiglu_paired_supported(ctypes.byref(a)))
+
+
+def gemm_qkrope_supported(M, N, K, K2, Sseq, nq_cols, nk_cols, device=None, alpha=1.0, bias=None):
     """True when the q|k|v projection of these sizes can carry q/k-norm + RoPE in its epilogue (ur_gemm_qkrope_supported); alpha / bias
-    (f32 [N]) fill the fields of ur_gemm_args the epilogue does not take, for which the answer is no."""
-    lib = _lib.load()
-    d = torch.empty(16, dtype=BF16, device=device)          # any valid 16-byte aligned pointer: only sizes / flags are inspected
-    f = torch.empty(4, dtype=F32, device=device)
-    a = GemmArgs()
-    a.R = a.S = a.C = a.qkr_q = a.qkr_k = a.qkr_v = d.data_ptr()
-    a.qkr_rstd = a.qkr_qw = a.qkr_kw = a.qkr_cos = a.qkr_sin = f.data_ptr()
-    a.ldr = a.lds = K
-    a.r_kcontig = a.s_kcontig = 1
-    a.K, a.M, a.N, a.alpha, a.split_k, a.ldc = K, M, N, float(alpha), 1, N
-    a.bias = _p(bias)
-    if K2:
-        a.R2 = a.S2 = d.data_ptr(); a.ldr2 = a.lds2 = K2; a.K2 = K2
-    a.qkr_ldq, a.qkr_ldk, a.qkr_ldv = nq_cols, nk_cols, N - nq_cols - nk_cols
-    a.qkr_S, a.qkr_nq_cols, a.qkr_nk_cols, a.qkr_eps = int(Sseq), int(nq_cols), int(nk_cols), 1e-6
-    return bool(lib.ur_gemm_qkrope_supported(ctypes.byref(a)))
+    (f32 [N]) fill the fields of ur_gemm_args the epilogue does not take, for which the answer is no.  `device` is not needed."""
+    a = gemm_plan_args(M, N, K, K2, alpha=alpha, bias=bias is not None, qkr_q=True, qkr_k=True, qkr_v=True, qkr_rstd=True, qkr_qw=True, qkr_kw=True,
+                   qkr_cos=True, qkr_sin=True, qkr_ldq=nq_cols, qkr_ldk=nk_cols, qkr_ldv=N - nq_cols - nk_cols, qkr_S=Sseq, qkr_nq_cols=nq_cols,
+                   qkr_nk_cols=nk_cols)
+    return bool(_lib.load().ur_gemm_qkrope_supported(ctypes.byref(a)))
 
 
 def gemm_qkv_rope(R, S, qw, kw, cos, sin, Sseq, nq_cols, nk_cols, eps, R2=None, S2=None, out=None):
@@ -290,7 +290,7 @@ def gemm_qkv_rope(R, S, qw, kw, cos, sin, Sseq, nq_cols, nk_cols, eps, R2=None, 
     out = (q, k, v, rstd): write there instead -- q / k / v bf16 of those shapes with unit inner stride and ANY row stride >= the width
     (column views of wider buffers: qkr_ldq / ldk / ldv), rstd contiguous f32."""
     lib = _lib.load()
-    M, N = R.shape[0], S.shape[0]
+    M, N, K = R.shape[0], S.shape[0], R.shape[1]
     dev = R.device
     shapes = ((M, nq_cols), (M, nk_cols), (M, N - nq_cols - nk_cols), (M, (nq_cols + nk_cols) // 128))
     if out is None:
@@ -302,15 +302,13 @@ def gemm_qkv_rope(R, S, qw, kw, cos, sin, Sseq, nq_cols, nk_cols, eps, R2=None, 
         for i, (t, sh, nm) in enumerate(zip(outs, shapes, ("q", "k", "v", "rstd"))):
             if t.dtype != (F32 if i == 3 else BF16) or not t.is_cuda or tuple(t.shape) != sh or t.stride(1) != 1 or (i == 3 and not t.is_contiguous()):
                 raise ValueError(f"gemm_qkv_rope: out {nm} must be a {'contiguous f32' if i == 3 else 'bf16'} {sh} device tensor with unit inner stride")
-    a = _qkrope_args(R, S, R2, S2, qw, kw, cos, sin, Sseq, nq_cols, nk_cols, eps, outs)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(lib.ur_gemm(ctypes.byref(a), 0, 0, _stream()), "ur_gemm(qkrope)")
-        e1.record()
-        PROFILE.append((e0, e1, 1, 1, 0, M, N, R.shape[1] + int(a.K2), 1, 3))
-        return outs
-    check(lib.ur_gemm(ctypes.byref(a), 0, 0, _stream()), "ur_gemm(qkrope)")
+    q, k, v, rstd = outs
+    # (C is not written in this mode: any valid pointer)
+    a = _gemm_args(R.data_ptr(), R.stride(0), S.data_ptr(), S.stride(0), q.data_ptr(), q.stride(0), M, N, K, pair2=_pair2(R2, S2))
+    a.qkr_q, a.qkr_ldq, a.qkr_k, a.qkr_ldk, a.qkr_v, a.qkr_ldv = q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0)
+    a.qkr_rstd, a.qkr_qw, a.qkr_kw, a.qkr_cos, a.qkr_sin = rstd.data_ptr(), qw.data_ptr(), kw.data_ptr(), cos.data_ptr(), sin.data_ptr()
+    a.qkr_S, a.qkr_nq_cols, a.qkr_nk_cols, a.qkr_eps = int(Sseq), int(nq_cols), int(nk_cols), float(eps)
+    _launch(lib.ur_gemm, "ur_gemm(qkrope)", (ctypes.byref(a), 0, 0), lambda: (1, 1, 0, M, N, K + int(a.K2), 1, 3))
     return outs
 
 

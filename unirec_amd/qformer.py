@@ -134,7 +134,8 @@ def _dead(name):
 
 
 def _split_k_for(out_rows, out_cols, red):
-    """dW GEMMs have tiny output grids; split the token reduction so the launch fills 256 CUs."""
+    """dW GEMMs have tiny output grids; split the token reduction so the launch fills 256 CUs.  (Written around ur_gemm's tile thresholds:
+    tests/test_gemm_plan.py asks hip.gemm_plan whether the cited shapes still reach the 256x256 tile at the split picked here.)"""
     tiles = ((out_rows + 127) // 128) * ((out_cols + 127) // 128)
     want = max(1, 512 // max(tiles, 1))
     sp = int(max(1, min(want, red // 256, 64)))

@@ -100,8 +100,8 @@ class _TokenTable(nn.Module):
 # down-projection launch and one A^T.  (key of the group's t / bits entries in saved["layers"][i], its projections)
 ADAPTER_GROUPS = (("qkv", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")), ("o", ("self_attn.o_proj",)),
                   ("gu", ("mlp.gate_proj", "mlp.up_proj")), ("d", ("mlp.down_proj",)))
-# What the persistent GEMM takes as a LoRA second K range: ONE K tile (csrc/gemm_pers.hip, `supported`: K2 <= BK = 64).  The library
-# has no query for it; this is the one host-side statement of that constant.
+# What the persistent GEMM takes as a LoRA second K range: ONE K tile (csrc/gemm.hip, pers_takes: K2 <= BK = 64).  The one host-side
+# statement of that constant; tests/test_gemm_plan.py holds it to the library's answer (hip.gemm_plan).
 PERS_GEMM_K2_MAX = 64
 _MAX_SHARED_ADAPTERS = max(len(projs) for _, projs in ADAPTER_GROUPS)      # q|k|v: the widest merged launch
 
