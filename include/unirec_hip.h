@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 18      /* 18: ur_gemm_plan */
+#define UR_ABI_VERSION 19      /* 18: ur_gemm_plan; 19: ur_rmsnorm_lora_fwd takes 1 to 3 adapters */
 
 int ur_version(void);
 const char* ur_last_error(void);
@@ -215,7 +215,7 @@ int ur_lora_dropout_bits(uint64_t seed, float p, int32_t M, int32_t W, int32_t n
                          int64_t bits_stride, int64_t row0, void* stream);
 int ur_lora_project(const ur_lora_args* a, void* stream);
 /* RMSNorm forward (ur_rmsnorm_fwd: out = w * (x * rstd), Qwen3RMSNorm modeling_qwen3.py:59-64) fused with the down
-   projection of the 2 or 3 adapters that read the normalised activation (q|k|v or gate|up): `a` as for ur_lora_project with
+   projection of the 1 to 3 adapters that read the normalised activation (the present ones of q|k|v or gate|up): `a` as for ur_lora_project with
    shared = 1 and X ignored (the adapters read `out`): P[m, 16a + j] = alpha * sum_c keep_a(m,c) out[m,c] U_a[j,c].  `out` is
    written once and not re-read.  D == 1024 (the Qwen3-0.6B hidden size). */
 /* SwiGLU forward (ur_swiglu_fwd: act = silu(gate) * up over gu = [gate | up], Qwen3MLP modeling_qwen3.py:81-83) fused with

@@ -5,7 +5,11 @@ For every rank of --ranks, in ONE process: a Qwen3LoRAModel with random weights,
 dropout planes, forward, backward) timed with device events; and, in isolation, the four masked dX GEMMs of a layer's backward
 (frozen W^T + the adapters' masked rank-r epilogue), times the layer count, with their share of the step: for ranks other than 16
 they run on the generic GEMM kernel, for rank 16 on the persistent one.  Prints one JSON line; --out writes it to a file too.
-    python tools/lora_rank_bench.py [--ranks 16,8,32,64] [--B 64] [--S 2048] [--layers 28] [--steps 10] [--warmup 3] [--out FILE]"""
+--targets times placements (peft's target_modules): placements separated by ';', the projections of one by ',', `all` = all seven --
+every rank of --ranks runs once per placement, rows carry "targets" and "step_vs_all" (the isolated dX GEMMs are the all-seven
+launches and are timed for `all` only).
+    python tools/lora_rank_bench.py [--ranks 16,8,32,64] [--B 64] [--S 2048] [--layers 28] [--steps 10] [--warmup 3] [--out FILE]
+                                    [--targets "all;q_proj,v_proj;q_proj,k_proj,v_proj,o_proj"]"""
 import argparse
 import gc
 import json
@@ -50,8 +54,10 @@ def dx_gemms_ms(M, cfg, r, p, iters):
     return out
 
 
-def step_ms(args, r):
-    cfg = Qwen3Config(vocab_size=4096, num_hidden_layers=args.layers, lora_r=r, lora_alpha=2.0 * r, lora_dropout=args.dropout)
+def step_ms(args, r, targets=None):
+    """targets: the projections that carry an adapter (None: all seven)"""
+    cfg = Qwen3Config(vocab_size=4096, num_hidden_layers=args.layers, lora_r=r, lora_alpha=2.0 * r, lora_dropout=args.dropout,
+                      lora_target_modules=targets)
     torch.manual_seed(0)
     m = Qwen3LoRAModel(cfg)
     m.reset_parameters(lora_b_std=0.02)
@@ -74,13 +80,18 @@ def step_ms(args, r):
     torch.cuda.synchronize()
     ms = events_ms(step, args.steps)
     plan = m._plan(B * S, S, ids.device, m._pack, m._frozen)
-    dx = dx_gemms_ms(B * S, cfg, r, args.dropout, 5)
+    dx = dx_gemms_ms(B * S, cfg, r, args.dropout, 5) if targets is None else {}
     peak = torch.cuda.max_memory_allocated() / 2 ** 30
+    params = [(n, p.detach()) for n, p in m.lora_named_parameters()]
     del m, tok, ids, am
     gc.collect()
     torch.cuda.empty_cache()
     torch.cuda.reset_peak_memory_stats()
     dx_step = args.layers * sum(dx.values())
+    if targets is not None:
+        return {"rank": r, "targets": list(targets), "step_ms": round(ms, 2), "seq_per_s": round(B / ms * 1e3, 2), "peak_GiB": round(peak, 1),
+                "trainable_params": sum(p.numel() for _, p in params),
+                "plan": {"merged": plan.merged, "fuse_norm": plan.fuse_norm, "fuse_rope": plan.fuse_rope, "swiglu": plan.swiglu, "bits_t": plan.bits_t}}
     return {"rank": r, "step_ms": round(ms, 2), "seq_per_s": round(B / ms * 1e3, 2), "peak_GiB": round(peak, 1),
             "plan": {"merged": plan.merged, "fuse_norm": plan.fuse_norm, "fuse_rope": plan.fuse_rope, "swiglu": plan.swiglu, "bits_t": plan.bits_t},
             "dx_gemm_ms_per_layer": {k: round(v, 3) for k, v in dx.items()}, "dx_gemm_ms_per_step": round(dx_step, 2),
@@ -97,12 +108,21 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--targets", default=None, help="placements separated by ';', projections by ',', 'all' = all seven")
     a = ap.parse_args()
-    rows = [step_ms(a, int(r)) for r in a.ranks.split(",")]
-    base = next((x for x in rows if x["rank"] == 16), None)
-    for x in rows:
-        x["step_vs_rank16"] = round(x["step_ms"] / base["step_ms"], 3) if base else None
-    res = {"what": "decoder training step per LoRA rank", "B": a.B, "S": a.S, "layers": a.layers, "dropout": a.dropout, "steps": a.steps,
+    if a.targets:
+        from unirec_amd.qwen3 import LORA_TARGETS
+        places = [LORA_TARGETS if t.strip() == "all" else tuple(x.strip() for x in t.split(",")) for t in a.targets.split(";")]
+        rows = [step_ms(a, int(r), list(t)) for r in a.ranks.split(",") for t in places]
+        for x in rows:
+            base = next((y for y in rows if y["rank"] == x["rank"] and tuple(y["targets"]) == LORA_TARGETS), None)
+            x["step_vs_all"] = round(x["step_ms"] / base["step_ms"], 3) if base else None
+    else:
+        rows = [step_ms(a, int(r)) for r in a.ranks.split(",")]
+        base = next((x for x in rows if x["rank"] == 16), None)
+        for x in rows:
+            x["step_vs_rank16"] = round(x["step_ms"] / base["step_ms"], 3) if base else None
+    res = {"what": "decoder training step per LoRA rank" + (" and placement" if a.targets else ""), "B": a.B, "S": a.S, "layers": a.layers, "dropout": a.dropout, "steps": a.steps,
            "warmup": a.warmup, "device": torch.cuda.get_device_name(0), "ranks": rows}
     line = json.dumps(res)
     print(line)

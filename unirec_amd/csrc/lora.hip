@@ -380,7 +380,9 @@ __global__ __launch_bounds__(256) void lora_project_ring_kernel(ProjP p) {
 
 // ---- RMSNorm forward + the adapters' down projection in ONE pass over the residual stream ---------------------------------
 // h = w * (x * rstd) (Qwen3RMSNorm, modeling_qwen3.py:59-64) is written once and never re-read by a projection kernel:
-// t[m, 16a + j] = alpha * sum_c keep_a(m, c) h[m, c] A_a[j, c] for the NAD adapters that consume h (q|k|v: 3, gate|up: 2)
+// t[m, 16a + j] = alpha * sum_c keep_a(m, c) h[m, c] A_a[j, c] for the NAD adapters that consume h (q|k|v: up to 3, gate|up: up to 2;
+// NAD = 1: a placement with one adapter in the group -- the same LDS image with one 16-row U block per 64-column half, SUB = 2 KiB,
+// one staging piece per thread; plane a of the flags is bits + a * bits_stride whatever NAD is)
 // comes out of the same registers.  A wave owns 16 tokens x D = 1024 columns: lane (token l15, column group g) holds its 32
 // 16-byte pieces of the row from one burst of loads (32 KiB in flight per wave, no barrier in front of them), the sum of
 // squares closes over the four lane groups with two shuffles, and the normalised pieces are the MFMA column operand
@@ -1344,7 +1346,7 @@ extern "C" int ur_rmsnorm_lora_fwd(const void* x, const float* w, void* out, flo
                                    const ur_lora_args* a, void* stream) {
   UR_REQUIRE(D == 1024, "ur_rmsnorm_lora_fwd: built for the hidden size 1024 (D=%d)", D);
   UR_REQUIRE(M >= 0 && x && w && out && rstd && UR_ALIGNED16(x) && UR_ALIGNED16(w) && UR_ALIGNED16(out), "ur_rmsnorm_lora_fwd: null / misaligned");
-  UR_REQUIRE(a && a->nad >= 2 && a->nad <= 3 && a->rank == 16 && a->shared == 1, "ur_rmsnorm_lora_fwd: 2 or 3 rank-16 adapters sharing the normalised input");
+  UR_REQUIRE(a && a->nad >= 1 && a->nad <= 3 && a->rank == 16 && a->shared == 1, "ur_rmsnorm_lora_fwd: 1 to 3 rank-16 adapters sharing the normalised input");
   UR_REQUIRE(a->P && (((uintptr_t)a->P) & 7) == 0 && (a->ldp % 4) == 0 && a->ldp >= 16 * a->nad, "ur_rmsnorm_lora_fwd: P must be 8-byte aligned, ldp %% 4 == 0, ldp >= 16 nad");
   UR_REQUIRE(!a->drop_bits || (UR_ALIGNED16(a->drop_bits) && (a->bits_ld % 16) == 0 && a->bits_ld >= D / 8 && (a->bits_stride % 16) == 0),
              "ur_rmsnorm_lora_fwd: bad dropout bit planes");
@@ -1359,7 +1361,10 @@ extern "C" int ur_rmsnorm_lora_fwd(const void* x, const float* w, void* out, flo
   const dim3 grid((unsigned)ur_cdiv(M, 64));
   hipStream_t st = (hipStream_t)stream;
   const bool masked = a->drop_bits != nullptr;
-  if (a->nad == 2) {
+  if (a->nad == 1) {
+    if (masked) hipLaunchKernelGGL((rms_lora_kernel<1, true>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((rms_lora_kernel<1, false>), grid, dim3(256), 0, st, p);
+  } else if (a->nad == 2) {
     if (masked) hipLaunchKernelGGL((rms_lora_kernel<2, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((rms_lora_kernel<2, false>), grid, dim3(256), 0, st, p);
   } else {

@@ -342,25 +342,31 @@ def _hoisted(n):
 
 def layer_boundaries(pack, layer_prefixes, group_size):
     """Bucket boundaries for a pack whose entries are ordered by layer: one bucket per `group_size`
-    consecutive layers (plus whatever precedes the first / follows the last layer)."""
+    consecutive layers (plus whatever precedes the first / follows the last layer).  A layer without parameters in the pack (no LoRA
+    adapter on it: layers_to_transform) contributes no boundary: a group's bucket starts at its lowest layer that has any, and a group
+    without parameters has no bucket."""
     # (the Q-Formers keep the cross-attention K | V projections of ALL layers side by side ahead of layer 0 -- one GEMM serves them,
     # qformer.py:_cross_kv_names.  Their gradients are final right after the layer loop, BEFORE the embedding LayerNorm / query-table
     # reduction that closes the backward: they get a bucket of their own, sent from its own hook (BertModel.grad_ready_hook(-2)),
     # so the exposed tail of the step is the small query-table bucket, not 50 MB of K | V gradients)
     hoisted = _hoisted
-    starts = []
+    starts = []                 # per layer: offset of its first parameter, None for a layer that has none
     for pre in layer_prefixes:
         offs = [pack.offsets[n] for n in pack.names if n.startswith(pre) and not hoisted(n)]
-        starts.append(min(offs))
+        starts.append(min(offs) if offs else None)
+    owners = [k for k, s in enumerate(starts) if s is not None]
+    if not owners:
+        raise ValueError("layer_boundaries: no layer prefix owns a parameter of the pack")
     bounds = [0]
     h_offs = [pack.offsets[n] for n in pack.names if hoisted(n)]
-    if h_offs and 0 < min(h_offs) < min(starts):
+    if h_offs and 0 < min(h_offs) < min(starts[k] for k in owners):
         bounds.append(min(h_offs))
     for k in range(0, len(starts), group_size):
-        if starts[k] > bounds[-1]:
-            bounds.append(starts[k])
+        own = [s for s in starts[k:k + group_size] if s is not None]
+        if own and min(own) > bounds[-1]:
+            bounds.append(min(own))
     # everything after the last layer group (heads) gets its own trailing bucket
-    last_layer_end = max(pack.offsets[n] + ((pack.params[n].numel() + 7) // 8) * 8 for n in pack.names if n.startswith(layer_prefixes[-1]) and not hoisted(n))
+    last_layer_end = max(pack.offsets[n] + ((pack.params[n].numel() + 7) // 8) * 8 for n in pack.names if n.startswith(layer_prefixes[owners[-1]]) and not hoisted(n))
     if last_layer_end < pack.numel:
         bounds.append(last_layer_end)
     bounds.append(pack.numel)
@@ -370,17 +376,23 @@ def layer_boundaries(pack, layer_prefixes, group_size):
 def bucket_hook(pack, buckets, layer_prefixes, group_size):
     """`grad_ready_hook` of a model whose backward walks its layers last to first (BertModel, Qwen3LoRAModel) for the buckets of
     `layer_boundaries(pack, layer_prefixes, group_size)`: signal i >= 0 = layer i's gradients are final (the bucket of a layer group
-    goes out when its LOWEST layer is done), -2 = the hoisted cross-attention K | V gradients, -1 = whatever precedes them (query
+    goes out when its LOWEST layer that owns parameters is done; the signal of a layer without any is a no-op), -2 = the hoisted cross-attention K | V gradients, -1 = whatever precedes them (query
     table, embedding LayerNorm).  Buckets are found by OFFSET, so the mapping follows the boundaries whatever they contain."""
     import bisect
     bounds = buckets.bounds
 
     def at(off):
         return bisect.bisect_right(bounds, off) - 1
-    first_of = {}
+    first_of = {}               # lowest layer of a group that owns parameters -> the group's bucket
+    lowest = None               # the lowest layer that owns parameters at all
     for i, pre in enumerate(layer_prefixes):
         offs = [pack.offsets[n] for n in pack.names if n.startswith(pre) and not _hoisted(n)]
-        if (i % group_size) == 0 and offs:
+        if not offs:
+            continue
+        if lowest is None:
+            lowest = i
+        k = i - i % group_size
+        if not any(k <= j < i for j in first_of):
             first_of[i] = at(min(offs))
     h_offs = [pack.offsets[n] for n in pack.names if _hoisted(n)]
     h_bucket = at(min(h_offs)) if h_offs else None
@@ -388,8 +400,9 @@ def bucket_hook(pack, buckets, layer_prefixes, group_size):
     if h_bucket == lead:
         h_bucket = None            # no boundary between them (nothing precedes the K | V block): one signal, the last one, sends it
     # a pack with NOTHING ahead of layer 0 (the LoRA pack: `layers.0.` sits at offset 0) has no -1 signal to wait for -- its model
-    # (Qwen3LoRAModel.backward) fires layer signals only -- so the lead bucket goes out with layer 0, the lowest layer of its group
-    lead_by_layer = first_of.get(0) == lead and h_bucket is None and not h_offs
+    # (Qwen3LoRAModel.backward) fires layer signals only -- so the lead bucket goes out with the lowest layer that owns parameters
+    # (layer 0 unless layers_to_transform leaves it without adapters)
+    lead_by_layer = lowest is not None and first_of.get(lowest) == lead and h_bucket is None and not h_offs
 
     def hook(i):
         if i == -1:
@@ -398,7 +411,7 @@ def bucket_hook(pack, buckets, layer_prefixes, group_size):
         elif i == -2:
             if h_bucket is not None:
                 buckets.ready(h_bucket)
-        elif i == 0 and lead_by_layer:
+        elif i == lowest and lead_by_layer:
             buckets.ready(lead)
         elif i in first_of and first_of[i] not in (lead, h_bucket):
             buckets.ready(first_of[i])

@@ -483,11 +483,13 @@ def swiglu_lora_fwd(gu, I, U, alpha=1.0, bits=None, t_out=None):
 
 @_stream_family("rms_lora", lambda r, x, w, eps, U, alpha=1.0, bits=None, t_out=None: _nb(x) + _nb(*r) + (_nb(bits) if bits is not None else 0))
 def rmsnorm_lora_fwd(x, w, eps, U, alpha=1.0, bits=None, t_out=None):
-    """RMSNorm forward + the down projection of the 2 or 3 adapters that read the normalised activation, one pass over x:
+    """RMSNorm forward + the down projection of the 1 to 3 adapters that read the normalised activation, one pass over x:
     -> (h bf16 like x, rstd f32 [M], t bf16 [M, 16 len(U)]).  D must be 1024.  t_out: write t there (a bf16 [M, 16 len(U)] view; its
     row stride may be wider)."""
     lib = _lib.load()
     _need(x, BF16, "x")
+    if not 1 <= len(U) <= 3:
+        raise ValueError(f"rmsnorm_lora_fwd: 1 to 3 adapters share the normalised input (got {len(U)})")
     D = x.shape[-1]
     M = x.numel() // D
     out = torch.empty_like(x)

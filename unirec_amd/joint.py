@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import hip
-from .qwen3 import Qwen3Config, Qwen3LoRAModel
+from .qwen3 import Qwen3Config, Qwen3LoRAModel, normalize_lora_layers, normalize_lora_targets
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -46,6 +46,53 @@ class HistoryTokenTable:
             json.dump(self._ids, f)
 
 
+# peft.LoraConfig fields this package does not implement: accepted only with the value under which they do nothing
+_LORA_INERT = (("rank_pattern", lambda v: not v, "empty (one rank for all modules)"),
+               ("alpha_pattern", lambda v: not v, "empty (one lora_alpha for all modules)"),
+               ("bias", lambda v: v == "none", '"none" (no bias is trained)'),
+               ("use_dora", lambda v: not v, "False"),
+               ("fan_in_fan_out", lambda v: not v, "False"),
+               ("modules_to_save", lambda v: v is None or len(v) == 0, "None or empty"),
+               ("layers_pattern", lambda v: v is None or len(v) == 0, "None or empty"),
+               ("exclude_modules", lambda v: v is None or len(v) == 0, "None or empty"))
+_ABSENT = object()
+
+
+def apply_lora_config(cfg, lora_config):
+    """Copy a ``peft.LoraConfig``-like object or dict into a Qwen3Config: r, lora_alpha, lora_dropout, target_modules,
+    layers_to_transform and use_rslora are honoured (the placement is validated here, against this config's layer count); the fields
+    of _LORA_INERT raise a ValueError that names the field unless they hold their inert value.  An absent field is never an error.
+    One deviation from peft: an absent / None ``target_modules`` keeps all seven projections (peft would pick q_proj and v_proj for
+    the Qwen family) -- the reference's own config names all seven, and that has been this package's behaviour all along."""
+    get = (lambda k: lora_config.get(k, _ABSENT)) if isinstance(lora_config, dict) else (lambda k: getattr(lora_config, k, _ABSENT))
+    for name, inert, what in _LORA_INERT:
+        v = get(name)
+        if v is not _ABSENT and not inert(v):
+            raise ValueError(f"lora_config.{name} = {v!r} is not supported: only {what} is accepted")
+    for src, dst in (("r", "lora_r"), ("lora_alpha", "lora_alpha"), ("lora_dropout", "lora_dropout")):
+        if get(src) is not _ABSENT:
+            setattr(cfg, dst, get(src))
+    targets, layers, rs = get("target_modules"), get("layers_to_transform"), get("use_rslora")
+    if targets is not _ABSENT and targets is not None:
+        cfg.lora_target_modules = list(normalize_lora_targets(targets))
+    if layers is not _ABSENT and layers is not None:
+        cfg.lora_layers_to_transform = list(normalize_lora_layers(layers, cfg.num_hidden_layers))
+    if rs is not _ABSENT:
+        cfg.use_rslora = bool(rs)
+    return cfg
+
+
+def adapter_config_dict(cfg, base_model_name_or_path=None):
+    """``adapter_config.json`` in peft's format for the adapters a Qwen3Config describes (what ``PeftModel.save_pretrained`` writes
+    next to ``adapter_model.bin``; ``peft.LoraConfig.from_pretrained`` reads it back)."""
+    layers = cfg.lora_layers_to_transform
+    return {"peft_type": "LORA", "task_type": "FEATURE_EXTRACTION", "base_model_name_or_path": base_model_name_or_path,
+            "r": int(cfg.lora_r), "lora_alpha": cfg.lora_alpha, "lora_dropout": float(cfg.lora_dropout),
+            "target_modules": list(normalize_lora_targets(cfg.lora_target_modules)),
+            "layers_to_transform": None if layers is None else list(normalize_lora_layers(layers, cfg.num_hidden_layers)),
+            "use_rslora": bool(cfg.use_rslora), "bias": "none", "inference_mode": True}
+
+
 class MultiModalQwenEmbedding(nn.Module):
     def __init__(self, base_model_name: str = "Qwen/Qwen3-Embedding-0.6B", qformer_model: nn.Module = None, use_lora: bool = True,
                  lora_config=None, qwen_config: Qwen3Config = None, num_history_items: int = 10,
@@ -60,9 +107,9 @@ class MultiModalQwenEmbedding(nn.Module):
         self.num_query_tokens_per_item = num_query_tokens_per_item
         self.qformer_model = qformer_model
         cfg = qwen_config or Qwen3Config()
-        if lora_config is not None:      # peft.LoraConfig-like object or dict: r / lora_alpha / lora_dropout
-            get = (lambda k, d: lora_config.get(k, d)) if isinstance(lora_config, dict) else (lambda k, d: getattr(lora_config, k, d))
-            cfg.lora_r, cfg.lora_alpha, cfg.lora_dropout = get("r", cfg.lora_r), get("lora_alpha", cfg.lora_alpha), get("lora_dropout", cfg.lora_dropout)
+        if lora_config is not None:      # peft.LoraConfig-like object or dict: every field is honoured or refused by name
+            apply_lora_config(cfg, lora_config)
+        self.base_model_name = base_model_name
         self.base_model = Qwen3LoRAModel(cfg, use_lora=use_lora)
         self.hidden_size = cfg.hidden_size
         if qformer_model is not None and qformer_model.config.hidden_size != self.hidden_size:
@@ -130,6 +177,8 @@ class MultiModalQwenEmbedding(nn.Module):
         self.tokenizer.save_pretrained(save_directory)
         if self.use_lora:
             torch.save(self.base_model.peft_state_dict(), os.path.join(save_directory, "adapter_model.bin"))
+            with open(os.path.join(save_directory, "adapter_config.json"), "w") as f:      # peft's own companion of adapter_model.bin
+                json.dump(adapter_config_dict(self.base_model.config, self.base_model_name), f, indent=2)
         else:
             torch.save(self.base_model.state_dict(), os.path.join(save_directory, "base_model.bin"))
         torch.save(self.qformer_model.state_dict(), os.path.join(save_directory, "qformer_model.bin"))

@@ -38,12 +38,53 @@ class Qwen3Config:
 
     def __init__(self, vocab_size=151669, hidden_size=1024, intermediate_size=3072, num_hidden_layers=28,
                  num_attention_heads=16, num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-6, rope_theta=1e6,
-                 lora_r=16, lora_alpha=32.0, lora_dropout=0.1, initializer_range=0.02):
+                 lora_r=16, lora_alpha=32.0, lora_dropout=0.1, initializer_range=0.02,
+                 lora_target_modules=None, lora_layers_to_transform=None, use_rslora=False):
         self.vocab_size, self.hidden_size, self.intermediate_size = vocab_size, hidden_size, intermediate_size
         self.num_hidden_layers, self.num_attention_heads, self.num_key_value_heads = num_hidden_layers, num_attention_heads, num_key_value_heads
         self.head_dim, self.rms_norm_eps, self.rope_theta = head_dim, rms_norm_eps, rope_theta
         self.lora_r, self.lora_alpha, self.lora_dropout = lora_r, lora_alpha, lora_dropout
         self.initializer_range = initializer_range
+        # LoRA placement (peft's target_modules / layers_to_transform; None = all seven projections / every layer) and peft's
+        # use_rslora (scale lora_alpha / sqrt(r) instead of lora_alpha / r)
+        self.lora_target_modules, self.lora_layers_to_transform, self.use_rslora = lora_target_modules, lora_layers_to_transform, bool(use_rslora)
+
+
+def normalize_lora_targets(spec):
+    """peft's ``target_modules`` -> the projections that carry an adapter, as a tuple of names out of LORA_TARGETS in that order.
+    None and "all-linear" mean all seven; a list / tuple / set holds plain (``q_proj``) or dotted (``self_attn.q_proj``) names.
+    Anything peft would reject (an empty collection, a name that matches no projection) and what this package does not take
+    (a regular expression, i.e. any other string) raises ValueError."""
+    if spec is None:
+        return LORA_TARGETS
+    if isinstance(spec, str):
+        if spec == "all-linear":
+            return LORA_TARGETS
+        raise ValueError(f"target_modules = {spec!r}: a string is a peft regular expression, which is not supported; pass a list of names out of "
+                         f"{', '.join(LORA_TARGETS)} (or 'all-linear')")
+    if not isinstance(spec, (list, tuple, set, frozenset)):
+        raise ValueError(f"target_modules must be a list, tuple or set of projection names, got {type(spec).__name__}")
+    dotted = {p.rsplit(".", 1)[-1]: p for _, projs in ADAPTER_GROUPS for p in projs}
+    chosen = set()
+    for name in spec:
+        short = str(name).rsplit(".", 1)[-1]
+        if short not in dotted or str(name) not in (short, dotted[short]):
+            raise ValueError(f"target_modules: {name!r} matches no projection of the decoder ({', '.join(LORA_TARGETS)})")
+        chosen.add(short)
+    if not chosen:
+        raise ValueError("target_modules is empty: no projection would carry an adapter")
+    return tuple(t for t in LORA_TARGETS if t in chosen)
+
+
+def normalize_lora_layers(spec, num_layers):
+    """peft's ``layers_to_transform`` -> the ascending tuple of layer indices that carry adapters.  None: every layer; an int or a list
+    of ints in [0, num_layers); anything else raises ValueError."""
+    if spec is None:
+        return tuple(range(num_layers))
+    items = [spec] if isinstance(spec, int) else (list(spec) if isinstance(spec, (list, tuple, set, frozenset)) else None)
+    if not items or any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < num_layers for i in items):
+        raise ValueError(f"layers_to_transform = {spec!r}: an int or a non-empty list of ints in [0, {num_layers}) is expected")
+    return tuple(sorted(set(items)))
 
 
 class _Proj(nn.Module):
@@ -62,30 +103,31 @@ class _Norm(nn.Module):
 
 
 class _Attn(nn.Module):
-    def __init__(self, c, r):
+    def __init__(self, c, r, on):
         super().__init__()
         D, hd = c.hidden_size, c.head_dim
-        self.q_proj = _Proj(D, c.num_attention_heads * hd, r)
-        self.k_proj = _Proj(D, c.num_key_value_heads * hd, r)
-        self.v_proj = _Proj(D, c.num_key_value_heads * hd, r)
-        self.o_proj = _Proj(c.num_attention_heads * hd, D, r)
+        self.q_proj = _Proj(D, c.num_attention_heads * hd, r if "q_proj" in on else 0)
+        self.k_proj = _Proj(D, c.num_key_value_heads * hd, r if "k_proj" in on else 0)
+        self.v_proj = _Proj(D, c.num_key_value_heads * hd, r if "v_proj" in on else 0)
+        self.o_proj = _Proj(c.num_attention_heads * hd, D, r if "o_proj" in on else 0)
         self.q_norm = _Norm(hd)
         self.k_norm = _Norm(hd)
 
 
 class _MLP(nn.Module):
-    def __init__(self, c, r):
+    def __init__(self, c, r, on):
         super().__init__()
-        self.gate_proj = _Proj(c.hidden_size, c.intermediate_size, r)
-        self.up_proj = _Proj(c.hidden_size, c.intermediate_size, r)
-        self.down_proj = _Proj(c.intermediate_size, c.hidden_size, r)
+        self.gate_proj = _Proj(c.hidden_size, c.intermediate_size, r if "gate_proj" in on else 0)
+        self.up_proj = _Proj(c.hidden_size, c.intermediate_size, r if "up_proj" in on else 0)
+        self.down_proj = _Proj(c.intermediate_size, c.hidden_size, r if "down_proj" in on else 0)
 
 
 class _Layer(nn.Module):
-    def __init__(self, c, r):
+    def __init__(self, c, r, on=LORA_TARGETS):
+        """on: the projections of this layer that carry an adapter (names out of LORA_TARGETS); the others are built with r = 0"""
         super().__init__()
-        self.self_attn = _Attn(c, r)
-        self.mlp = _MLP(c, r)
+        self.self_attn = _Attn(c, r, on)
+        self.mlp = _MLP(c, r, on)
         self.input_layernorm = _Norm(c.hidden_size)
         self.post_attention_layernorm = _Norm(c.hidden_size)
 
@@ -106,15 +148,17 @@ PERS_GEMM_K2_MAX = 64
 _MAX_SHARED_ADAPTERS = max(len(projs) for _, projs in ADAPTER_GROUPS)      # q|k|v: the widest merged launch
 
 
-def lora_rank_rule(r, sw=switches):
-    """The launch choices that depend on the LoRA rank: a pure function of (rank, switches), read by Qwen3LoRAModel._plan.
+def lora_rank_rule(r, sw=switches, adapters=None):
+    """The launch choices that depend on the LoRA rank: a pure function of (rank, switches, placement), read by Qwen3LoRAModel._plan.
+    adapters: the most adapters any q|k|v or gate|up group of the model holds (None: all three of q|k|v).
       merged      q|k|v and gate|up leave as one launch each while the merged launch's second K range (adapters * r) still fits the
-                  persistent GEMM; otherwise one launch per adapter (K2 = r <= 64 each)
+                  persistent GEMM; otherwise one launch per projection (K2 = r <= 64 each)
       fuse_norm   RMSNorm + down projection as one kernel (ur_rmsnorm_lora_fwd: rank 16)
       swiglu_lora SwiGLU + the down adapter's down projection as one kernel (ur_swiglu_lora_fwd: rank 16)
       bits_t      token-packed dropout flags: only the rank-16 ring kernel of ur_lora_reduce consumes them"""
     r = int(r)
-    return {"merged": bool(sw.merge_proj) and _MAX_SHARED_ADAPTERS * r <= PERS_GEMM_K2_MAX,
+    nad = _MAX_SHARED_ADAPTERS if adapters is None else int(adapters)
+    return {"merged": bool(sw.merge_proj) and nad * r <= PERS_GEMM_K2_MAX,
             "fuse_norm": bool(sw.fuse_norm_lora) and r == 16,
             "swiglu_lora": bool(sw.fuse_swiglu_lora) and r == 16,
             "bits_t": bool(sw.bits_t) and r == 16}
@@ -126,13 +170,24 @@ _QK_FUSE_MAX_RATIO = 4.0      # largest |w_d| / |w_{d+64}| spread of a rotate-ha
 # parameter names of one adapter group of one layer: a = the lora_A.weight of every adapter (the tuple is also the key of the group's A^T
 # in _lora_transposes), b = the lora_B.weight of every adapter
 _GroupNames = namedtuple("_GroupNames", "a b")
+# where the PRESENT adapters of one adapter group of one layer sit (built once, beside the names):
+#   planes  dropout bit planes to generate: the group's planes 0 .. highest present slot (a module's slot is its position in the
+#           ADAPTER_GROUPS entry, whatever else is present: its mask never depends on the placement); 0 = no adapter
+#   view    the slice of those planes that holds the present adapters' (every subset of three slots is an arithmetic progression: the
+#           kernels take a base + plane stride); None = all of them, the tensor itself
+#   cols    (first column, width) of every present adapter inside the group's merged output
+#   split   the group as one launch per projection: (first output column, width, index of the adapter among the present ones or None,
+#           its lora_B name or None) for EVERY projection of the group
+_GroupPlace = namedtuple("_GroupPlace", "planes view cols split")
 
 
 @dataclass(frozen=True)
 class _Plan:
     """The launch choices of one forward: constant over its layers, taken once before the loop (Qwen3LoRAModel._plan) and kept in
-    saved["plan"], where the backward reads what the forward did."""
-    merged: bool            # q|k|v and gate|up leave as one launch each (always so without adapters), not one per adapter
+    saved["plan"], where the backward reads what the forward did.  It describes the layers that carry adapters; a group without an
+    adapter (a layer outside layers_to_transform, a group nobody targets) runs as the adapter-free model runs it: one launch, no down
+    projection, and of the fused forms those the plan queried for a launch without a second K range (fuse_rope, "pair")."""
+    merged: bool            # q|k|v and gate|up leave as one launch each (always so without adapters), not one per projection
     fuse_norm: bool         # RMSNorm + the q|k|v / gate|up adapters' down projection as one kernel
     fuse_rope: bool         # q/k-norm + RoPE in the q|k|v launch's epilogue: no raw q, k exist
     swiglu: str             # "pair": epilogue of the merged gate|up launch, "up": epilogue of the up projection's own launch,
@@ -161,7 +216,7 @@ class _JointFn(torch.autograd.Function):
 
 
 class Qwen3LoRAModel(nn.Module):
-    """Frozen Qwen3 decoder with LoRA adapters on all 7 projections."""
+    """Frozen Qwen3 decoder with LoRA adapters on the projections and layers the config names (default: all 7, every layer)."""
 
     def __init__(self, config: Qwen3Config, use_lora=True):
         super().__init__()
@@ -172,7 +227,13 @@ class Qwen3LoRAModel(nn.Module):
             raise ValueError(f"Qwen3LoRAModel: lora_r = {r} is not supported; the adapter kernels are built for the ranks "
                              f"{', '.join(map(str, hip.LORA_RANKS))} (one rank for all modules: no rank_pattern)")
         self.embed_tokens = _TokenTable(config.vocab_size, config.hidden_size)
-        self.layers = nn.ModuleList([_Layer(config, r) for _ in range(config.num_hidden_layers)])
+        targets = normalize_lora_targets(config.lora_target_modules) if self.use_lora else ()
+        adapted = set(normalize_lora_layers(config.lora_layers_to_transform, config.num_hidden_layers)) if self.use_lora else set()
+        on = [targets if i in adapted else () for i in range(config.num_hidden_layers)]
+        # the placement: per layer, the dotted names of the projections that carry an adapter, in canonical order
+        self.adapter_modules = tuple(tuple(p for _, projs in ADAPTER_GROUPS for p in projs if p.rsplit(".", 1)[-1] in on[i])
+                                     for i in range(config.num_hidden_layers))
+        self.layers = nn.ModuleList([_Layer(config, r, on[i]) for i in range(config.num_hidden_layers)])
         self.norm = _Norm(config.hidden_size)
         self._pack = None
         self._frozen = None
@@ -191,8 +252,14 @@ class Qwen3LoRAModel(nn.Module):
         self.recompute_mlp = switches.recompute_mlp   # drop gate|up and act after the forward, rebuild them in the backward
         self.keep_norm_outputs = True   # keep the two RMSNorm outputs per layer for the backward (memory for time); False recomputes them
         # [layer][adapter group] -> parameter names, built once: the hot loops format no strings
-        self._names = [[_GroupNames(a=tuple(f"layers.{i}.{p}.lora_A.weight" for p in projs), b=tuple(f"layers.{i}.{p}.lora_B.weight" for p in projs))
-                        for _, projs in ADAPTER_GROUPS] for i in range(config.num_hidden_layers)]
+        # (the PRESENT adapters of the group: the tuples may be empty)
+        self._names = [[_GroupNames(a=tuple(f"layers.{i}.{p}.lora_A.weight" for p in projs if p in mods),
+                                    b=tuple(f"layers.{i}.{p}.lora_B.weight" for p in projs if p in mods))
+                        for _, projs in ADAPTER_GROUPS] for i, mods in enumerate(self.adapter_modules)]
+        self._place = [[self._group_place(i, g) for g in range(len(ADAPTER_GROUPS))] for i in range(config.num_hidden_layers)]
+        # the adapter counts that occur in a q|k|v / gate|up group over the layers (a layer outside layers_to_transform counts 0): the second K
+        # ranges the merged launches are asked about (_plan)
+        self._nad_qkv, self._nad_gu = (sorted({len(nm[g].a) for nm in self._names}) for g in (0, 2))
         self.reset_parameters()
 
     def reset_parameters(self, lora_b_std=0.0):
@@ -399,6 +466,25 @@ class Qwen3LoRAModel(nn.Module):
         D, I, NQ, NKV = c.hidden_size, c.intermediate_size, c.num_attention_heads * c.head_dim, c.num_key_value_heads * c.head_dim
         return ((D, (NQ, NKV, NKV)), (NQ, (D,)), (D, (I, I)), (I, (D,)))
 
+    def _group_place(self, i, g):
+        projs, (_, outs) = ADAPTER_GROUPS[g][1], self._group_dims()[g]
+        slots = [j for j, p in enumerate(projs) if p in self.adapter_modules[i]]
+        col0 = [sum(outs[:j]) for j in range(len(outs))]
+        split = tuple((col0[j], outs[j], slots.index(j) if j in slots else None, f"layers.{i}.{p}.lora_B.weight" if j in slots else None)
+                      for j, p in enumerate(projs))
+        if not slots:
+            return _GroupPlace(0, None, (), split)
+        planes = slots[-1] + 1
+        view = None if len(slots) == planes else slice(slots[0], planes, slots[1] - slots[0] if len(slots) > 1 else 1)
+        return _GroupPlace(planes, view, tuple((col0[j], outs[j]) for j in slots), split)
+
+    def _draw_bits(self, i, g, seed, p, M, W, device, row0):
+        """The dropout planes of the present adapters of group g of layer i, drawn now (no prefetched set): the group's planes up to the
+        highest present slot are generated, the present ones are handed on as a view."""
+        pl = self._place[i][g]
+        bits = hip.lora_dropout_bits(seed, p, M, W, pl.planes, device, row0=row0)
+        return bits if pl.view is None else bits[pl.view]
+
     def prefetch_lora_bits(self, M, device, row0=0):
         """Generate the NEXT forward's LoRA dropout bit planes (all layers, all adapter groups) on a side stream.  The planes
         are pure functions of (seed, step, layer, group) -- nothing on the main stream feeds them -- so the caller starts
@@ -417,13 +503,14 @@ class Qwen3LoRAModel(nn.Module):
         main = torch.cuda.current_stream(device)
         if self._bits_stream is None:
             self._bits_stream = torch.cuda.Stream(device=device)
-        planes = {(i, g): torch.empty((len(outs), M, hip.lora_bits_ld(W)), dtype=torch.uint8, device=device)
-                  for i in range(self.config.num_hidden_layers) for g, (W, outs) in enumerate(self._group_dims())}
+        planes = {(i, g): torch.empty((self._place[i][g].planes, M, hip.lora_bits_ld(W)), dtype=torch.uint8, device=device)
+                  for i in range(self.config.num_hidden_layers) for g, (W, outs) in enumerate(self._group_dims()) if self._place[i][g].planes}
         # token-packed copies for the backward's token reductions (hip.lora_reduce's ring kernel), made on the side stream as well
         packed = {}
         if M % 128 == 0 and lora_rank_rule(self.config.lora_r)["bits_t"]:
-            packed = {(i, g): torch.empty((len(outs), M // 32, hip.lora_bits_t_ld(W)), dtype=torch.int32, device=device)
-                      for i in range(self.config.num_hidden_layers) for g, (W, outs) in enumerate(self._group_dims()) if W % 64 == 0}
+            packed = {(i, g): torch.empty((self._place[i][g].planes, M // 32, hip.lora_bits_t_ld(W)), dtype=torch.int32, device=device)
+                      for i in range(self.config.num_hidden_layers) for g, (W, outs) in enumerate(self._group_dims())
+                      if W % 64 == 0 and self._place[i][g].planes}
         self._bits_stream.wait_stream(main)
         self._generate_bits(planes, packed, self._lora_step, M, device, int(row0), p)
 
@@ -444,7 +531,8 @@ class Qwen3LoRAModel(nn.Module):
             events = []
             for i in range(self.config.num_hidden_layers):
                 for g, (W, outs) in enumerate(self._group_dims()):
-                    hip.lora_dropout_bits(self.lora_dropout_seed(step, i, g), p, M, W, len(outs), device, out=planes[(i, g)], row0=row0)
+                    if self._place[i][g].planes:
+                        hip.lora_dropout_bits(self.lora_dropout_seed(step, i, g), p, M, W, self._place[i][g].planes, device, out=planes[(i, g)], row0=row0)
                 events.append(side.record_event())
             for (i, g), bt in packed.items():
                 hip.lora_bits_transpose(planes[(i, g)], self._group_dims()[g][0], out=bt)
@@ -463,29 +551,44 @@ class Qwen3LoRAModel(nn.Module):
         self._bits_stream.wait_stream(torch.cuda.current_stream(device))
         self._generate_bits(cur["planes"], cur["packed"], self._lora_step, cur["M"], device, cur["row0"], cur["p"])
 
-    def _lora_bcomb(self, pack, device):
+    def _lora_bcomb(self, pack, device, paired_qkv=False, paired_gu=False):
         """Second-K-range operands of the merged projection launches: y[q|k|v] = h W^T + [t_q|t_k|t_v] Bc^T with
         Bc [N, 16 nad] block-diagonal (rows of adapter a carry B_a in columns 16a..16a+15, zeros elsewhere -- exact zeros, so
         the sum is bit-identical to the per-adapter launches).  q|k|v and gate|up each leave as ONE launch that reads its
         input once (1.09 -> 1.01 ms and 1.58 -> 1.49 ms per layer at C4).  The zero blocks are written once; each step
-        refreshes the diagonal blocks from the bf16 shadow with one multi-tensor copy."""
+        refreshes the diagonal blocks from the bf16 shadow with one multi-tensor copy.  paired_qkv / paired_gu: the forward runs the
+        fused q/k-norm + RoPE / paired SwiGLU epilogue and reads the operand with its rows in that launch's order ("qkvP" / "guP");
+        the per-layer views are made of the form the plan reads only."""
+        # Placement: the operand has r columns per PRESENT adapter of the group (the adapted layers share one placement, so one
+        # [adapted layers, N, r * present] tensor per group serves them); a layer without an adapter in the group has None there.
         c = self.config
-        r, I = c.lora_r, c.intermediate_size
+        r, I, L = c.lora_r, c.intermediate_size, c.num_hidden_layers
         dims = self._group_dims()
         if self._bcomb is None or self._bcomb["dev"] != torch.device(device) or self._bcomb["pack"] is not pack:
-            qkv, gu = (torch.zeros((c.num_hidden_layers, sum(outs), len(outs) * r), dtype=BF16, device=device) for outs in (dims[0][1], dims[2][1]))
+            # slab of layer i inside the group's tensor, or None
+            slab = {g: dict((i, k) for k, i in enumerate(i for i in range(L) if self._names[i][g].b)) for g in (0, 2)}
+            qkv, gu = (torch.zeros((len(slab[g]), sum(dims[g][1]), max(nads) * r), dtype=BF16, device=device) if slab[g] else None
+                       for g, nads in ((0, self._nad_qkv), (2, self._nad_gu)))
             dst, src = [], []
-            for i in range(c.num_hidden_layers):
+            for i in range(L):
                 for comb, g in ((qkv, 0), (gu, 2)):
-                    row = 0
-                    for j, (bname, n) in enumerate(zip(self._names[i][g].b, dims[g][1])):
-                        dst.append(comb[i, row:row + n, j * r:(j + 1) * r]); src.append(pack.w16(bname)); row += n
-            self._bcomb = {"dev": torch.device(device), "pack": pack, "qkv": qkv, "gu": gu, "dst": dst, "src": src}
-        torch._foreach_copy_(self._bcomb["dst"], self._bcomb["src"])
+                    for j, (bname, (col, n)) in enumerate(zip(self._names[i][g].b, self._place[i][g].cols)):
+                        dst.append(comb[slab[g][i], col:col + n, j * r:(j + 1) * r]); src.append(pack.w16(bname))
+            self._bcomb = {"dev": torch.device(device), "pack": pack, "qkv3": qkv, "gu3": gu, "dst": dst, "src": src, "slab": slab}
+        bc = self._bcomb
+        if bc["dst"]:
+            torch._foreach_copy_(bc["dst"], bc["src"])
         rp = self._qk_row_perm(device) if switches.fuse_qk_rope else None
-        self._bcomb["qkvP"] = self._bcomb["qkv"].index_select(1, rp) if rp is not None else None      # rows paired like fz["qkvP"]
-        self._bcomb["guP"] = (self._bcomb["gu"].index_select(1, self._swiglu_rows(I, device)) if (switches.fuse_swiglu_gemm and I % 128 == 0) else None)
-        return self._bcomb["qkv"], self._bcomb["gu"]
+        qkvP = bc["qkv3"].index_select(1, rp) if (rp is not None and bc["qkv3"] is not None) else None      # rows paired like fz["qkvP"]
+        guP = (bc["gu3"].index_select(1, self._swiglu_rows(I, device)) if (switches.fuse_swiglu_gemm and I % 128 == 0 and bc["gu3"] is not None) else None)
+
+        def per_layer(t3, g):
+            slab = bc["slab"][g]
+            return [t3[slab[i]] if i in slab else None for i in range(L)] if t3 is not None else none
+        none = (None,) * L
+        bc["qkv"], bc["qkvP"] = (none, per_layer(qkvP, 0)) if paired_qkv else (per_layer(bc["qkv3"], 0), none)
+        bc["gu"], bc["guP"] = (none, per_layer(guP, 2)) if paired_gu else (per_layer(bc["gu3"], 2), none)
+        return bc["qkv"], bc["gu"]
 
     def _lora_transposes(self, pack):
         """A^T (per adapter group) and B^T (per adapter) of every layer for the backward, refreshed by ONE launch per
@@ -496,6 +599,8 @@ class Qwen3LoRAModel(nn.Module):
             names, srcs = [], []
             for groups in self._names:
                 for g in groups:
+                    if not g.a:            # no adapter in this group of this layer
+                        continue
                     names.append(g.a)
                     srcs.append(pack.fused16(list(g.a)) if len(g.a) > 1 else pack.w16(g.a[0]))
                     for bname in g.b:
@@ -506,22 +611,31 @@ class Qwen3LoRAModel(nn.Module):
         outs = bt[2].run()
         return dict(zip(bt[1], outs))
 
-    def _norm_lora_down(self, x, w, eps, a_names, pack, sc, seed, p, pre=None, row0=0):
-        """(h, rstd, t, bits) = RMSNorm forward + _lora_down of the adapters that read h, as one kernel (ur_rmsnorm_lora_fwd)."""
+    def _norm_lora_down(self, x, w, eps, i, g, pack, sc, seed, p, pre=None, row0=0):
+        """(h, rstd, t, bits) = RMSNorm forward + _lora_down of the present adapters of group g of layer i, which read h, as one kernel
+        (ur_rmsnorm_lora_fwd)."""
         bits = pre
         if bits is None and p > 0.0:
-            bits = hip.lora_dropout_bits(seed, p, x.shape[0], x.shape[1], len(a_names), x.device, row0=row0)
-        h, rstd, t = hip.rmsnorm_lora_fwd(x, w, eps, [pack.w16(n) for n in a_names], alpha=sc / (1.0 - p), bits=bits)
+            bits = self._draw_bits(i, g, seed, p, x.shape[0], x.shape[1], x.device, row0)
+        h, rstd, t = hip.rmsnorm_lora_fwd(x, w, eps, [pack.w16(n) for n in self._names[i][g].a], alpha=sc / (1.0 - p), bits=bits)
         return h, rstd, t, bits
 
-    def _lora_down(self, xin, a_names, pack, sc, seed, p, pre=None, row0=0):
-        """(t, bits): t[M, nb*r] = s * dropout_j(x) A_j^T for the nb adapters that share the input x (one dropped-flag
-        bit plane per adapter, generated once here and kept for the backward)."""
+    def _lora_down(self, xin, i, g, pack, sc, seed, p, pre=None, row0=0):
+        """(t, bits): t[M, nb*r] = s * dropout_j(x) A_j^T for the nb present adapters of group g of layer i, which share the input x (one
+        dropped-flag bit plane per adapter -- the plane at the module's slot of the group's generator stream -- made once here and kept
+        for the backward)."""
         bits = pre
         if bits is None and p > 0.0:
-            bits = hip.lora_dropout_bits(seed, p, xin.shape[0], xin.shape[1], len(a_names), xin.device, row0=row0)
-        t = hip.lora_project(xin, [pack.w16(n) for n in a_names], alpha=sc / (1.0 - p), bits=bits)
+            bits = self._draw_bits(i, g, seed, p, xin.shape[0], xin.shape[1], xin.device, row0)
+        t = hip.lora_project(xin, [pack.w16(n) for n in self._names[i][g].a], alpha=sc / (1.0 - p), bits=bits)
         return t, bits
+
+    def _lora_scale(self):
+        """s of y = W x + s B A x: lora_alpha / r, or peft's rank-stabilised lora_alpha / sqrt(r) (use_rslora)"""
+        c = self.config
+        if not self.use_lora:
+            return 0.0
+        return c.lora_alpha / math.sqrt(c.lora_r) if getattr(c, "use_rslora", False) else c.lora_alpha / c.lora_r
 
     def _plan(self, M, S, dev, pack, fz):
         """Every launch choice that is the same for all layers of a forward over M = B * S tokens (see _Plan)."""
@@ -529,15 +643,18 @@ class Qwen3LoRAModel(nn.Module):
         D, I, hd, r = c.hidden_size, c.intermediate_size, c.head_dim, c.lora_r
         NQ, NKV = c.num_attention_heads * hd, c.num_key_value_heads * hd
         lora = pack is not None
-        rule = lora_rank_rule(r, sw)
+        # the second K ranges of the merged launches: r columns per PRESENT adapter of the group, one value per kind of layer (a layer
+        # outside layers_to_transform, or a group nobody targets, has none: K2 = 0, R2 = S2 = None)
+        nad_qkv, nad_gu = (self._nad_qkv, self._nad_gu) if lora else ([0], [0])
+        rule = lora_rank_rule(r, sw, max(nad_qkv[-1], nad_gu[-1])) if lora else lora_rank_rule(r, sw)
         merged = not lora or rule["merged"]
         # q/k-norm + RoPE inside the q|k|v launch (the raw q, k are never written or re-read) when the persistent GEMM takes it
         fuse_rope = (sw.fuse_qk_rope and hd == 128 and fz["qk_norm_fusable"] and merged and
-                     hip.gemm_qkrope_supported(M, NQ + 2 * NKV, D, 3 * r if lora else 0, S, NQ, NKV, dev))
+                     all(hip.gemm_qkrope_supported(M, NQ + 2 * NKV, D, n * r, S, NQ, NKV, dev) for n in nad_qkv))
         swiglu = "alone"
         if lora and not merged and sw.swiglu_fwd_fused:
             swiglu = "up"
-        elif lora and merged and sw.fuse_swiglu_gemm and I % 128 == 0 and hip.gemm_swiglu_paired_supported(M, I, D, 2 * r, dev):
+        elif lora and merged and sw.fuse_swiglu_gemm and I % 128 == 0 and all(hip.gemm_swiglu_paired_supported(M, I, D, n * r, dev) for n in nad_gu):
             swiglu = "pair"
         elif lora and rule["swiglu_lora"] and I % 128 == 0:
             swiglu = "lora"
@@ -569,9 +686,9 @@ class Qwen3LoRAModel(nn.Module):
         if pack is not None:
             pack.refresh_shadow()
             if plan.merged:
-                bc_qkv, bc_gu = self._lora_bcomb(pack, dev)
+                bc_qkv, bc_gu = self._lora_bcomb(pack, dev, paired_qkv=plan.fuse_rope, paired_gu=plan.swiglu == "pair")
                 bc_qkvP, bc_guP = self._bcomb["qkvP"], self._bcomb["guP"]
-        eps, sc = c.rms_norm_eps, (c.lora_alpha / c.lora_r if self.use_lora else 0.0)
+        eps, sc = c.rms_norm_eps, self._lora_scale()
         cos, sin = self._rope_tables(S, dev)
         T = item_tokens16.shape[1]
         tok = item_tokens16.detach().contiguous() if T > 0 else None
@@ -595,18 +712,25 @@ class Qwen3LoRAModel(nn.Module):
             saved["bits_pre"] = pre                                      # (its buffers take the next step's planes after the backward)
             pre_events = pre["events"]                                   # planes prefetched on the side stream, one event per layer
             pre = pre["planes"]
-        bp = (lambda i, g: pre[(i, g)]) if pre is not None else (lambda i, g: None)
+        place = self._place
+
+        def bp(i, g):
+            """the prefetched planes of the present adapters of group g of layer i (a view of the group's planes), or None"""
+            if pre is None:
+                return None
+            v = place[i][g].view
+            return pre[(i, g)] if v is None else pre[(i, g)][v]
 
         def lora_down(xin, i, g):
             """(t, bits) of adapter group g of layer i on its input xin; (None, None) without adapters"""
-            if pack is None:
+            if pack is None or not place[i][g].planes:
                 return None, None
-            return self._lora_down(xin, self._names[i][g].a, pack, sc, self.lora_dropout_seed(step, i, g), pdrop, bp(i, g), row0=row0)
+            return self._lora_down(xin, i, g, pack, sc, self.lora_dropout_seed(step, i, g), pdrop, bp(i, g), row0=row0)
 
         def norm_lora_down(xin, w, i, g):
             """(h, rstd, t, bits): RMSNorm and lora_down of its output, as one kernel when the plan says so"""
-            if plan.fuse_norm:      # (h is written once, never re-read by a projection kernel)
-                return self._norm_lora_down(xin, w, eps, self._names[i][g].a, pack, sc, self.lora_dropout_seed(step, i, g), pdrop, bp(i, g), row0=row0)
+            if plan.fuse_norm and place[i][g].planes:      # (h is written once, never re-read by a projection kernel)
+                return self._norm_lora_down(xin, w, eps, i, g, pack, sc, self.lora_dropout_seed(step, i, g), pdrop, bp(i, g), row0=row0)
             h, rstd = hip.rmsnorm_fwd(xin, w, eps)
             return (h, rstd) + lora_down(h, i, g)      # t [M, nad * r] = s * dropout(h) A^T
 
@@ -622,43 +746,47 @@ class Qwen3LoRAModel(nn.Module):
                 v4 = v2.view(B, S, nkv, hd)
                 L.update(q_r=q_r, k_r=k_r, rstd_qk=rstd_qk)
             else:
-                if plan.merged:
-                    hip.gemm(h, fl["qkv"], out=qkv, R2=t_qkv, S2=bc_qkv[i])        # one launch, block-diagonal B
+                if plan.merged or t_qkv is None:
+                    hip.gemm(h, fl["qkv"], out=qkv, R2=t_qkv, S2=bc_qkv[i])        # one launch, block-diagonal B (none: no adapter here)
                 else:
-                    col = 0
-                    for j, (bname, n) in enumerate(zip(nm[0].b, (NQ, NKV, NKV))):
-                        hip.gemm(h, fl["qkv"][col:col + n], out=qkv[:, col:col + n], R2=t_qkv[:, j * r:(j + 1) * r], S2=w16(bname))
-                        col += n
+                    for col, n, j, bname in place[i][0].split:      # one launch per projection; j: its adapter among the present ones
+                        hip.gemm(h, fl["qkv"][col:col + n], out=qkv[:, col:col + n], R2=None if j is None else t_qkv[:, j * r:(j + 1) * r],
+                                 S2=None if j is None else w16(bname))
                 q_r, k_r = hip.qknorm_rope_fwd(qkv, fl["qn"], fl["kn"], cos, sin, S, nq, nkv, hd, eps)
                 v4 = qkv[:, NQ + NKV:].view(B, S, nkv, hd)
             att_out = torch.empty((M, NQ + 64), dtype=BF16, device=dev)[:, :NQ].view(B, S, nq, hd) if plan.pad_att else None
             att, actx = hip.attn_fwd(q_r.view(B, S, nq, hd), k_r.view(B, S, nkv, hd), v4, causal=True, key_mask=mask_u8, out=att_out)
             att2 = att.view(M, NQ)
             t_o, L["bits_o"] = lora_down(att2, i, 1)
-            x2 = hip.gemm(att2, fl["o"], residual=x, R2=t_o, S2=w16(nm[1].b[0]))
+            x2 = hip.gemm(att2, fl["o"], residual=x, R2=t_o, S2=w16(nm[1].b[0]) if t_o is not None else None)
             gu = torch.empty((M, 2 * I), dtype=BF16, device=dev)
             h2, rstd2, t_gu, L["bits_gu"] = norm_lora_down(x2, fl["ln2"], i, 2)
-            act = torch.empty((M, I), dtype=BF16, device=dev) if plan.swiglu in ("pair", "up") else None
-            if plan.swiglu == "pair":            # ONE launch: gate|up (standard order, for the backward) and act = silu(gate) * up from its registers
+            # (a layer without a gate / up adapter under per-projection launches runs the group as the adapter-free model does: one launch,
+            # SwiGLU on its own; likewise the fused SwiGLU + down projection needs a down adapter in THIS layer)
+            swiglu = plan.swiglu
+            if (swiglu == "up" and t_gu is None) or (swiglu == "lora" and not nm[3].a):
+                swiglu = "alone"
+            act = torch.empty((M, I), dtype=BF16, device=dev) if swiglu in ("pair", "up") else None
+            if swiglu == "pair":            # ONE launch: gate|up (standard order, for the backward) and act = silu(gate) * up from its registers
                 hip.gemm(h2, fl["guP"], out=gu, R2=t_gu, S2=bc_guP[i], swiglu_paired=act)
-            elif plan.merged:
-                hip.gemm(h2, fl["gu"], out=gu, R2=t_gu, S2=bc_gu[i])            # one launch, block-diagonal B
+            elif plan.merged or t_gu is None:
+                hip.gemm(h2, fl["gu"], out=gu, R2=t_gu, S2=bc_gu[i])            # one launch, block-diagonal B (none: no adapter here)
             else:
                 # gate first; under "up" the up projection's epilogue then reads the gate tile and writes act = silu(gate) * up beside up
-                for j, bname in enumerate(nm[2].b):
-                    hip.gemm(h2, fl["gu"][j * I:(j + 1) * I], out=gu[:, j * I:(j + 1) * I], R2=t_gu[:, j * r:(j + 1) * r], S2=w16(bname),
-                             swiglu_fwd=(gu[:, :I], act) if (j == 1 and plan.swiglu == "up") else None)
-            if plan.swiglu == "lora":      # act and t_d = s * dropout(act) A_d^T from one pass over gate|up (ur_swiglu_lora_fwd)
+                for col, n, j, bname in place[i][2].split:
+                    hip.gemm(h2, fl["gu"][col:col + n], out=gu[:, col:col + n], R2=None if j is None else t_gu[:, j * r:(j + 1) * r],
+                             S2=None if j is None else w16(bname), swiglu_fwd=(gu[:, :I], act) if (col == I and swiglu == "up") else None)
+            if swiglu == "lora":      # act and t_d = s * dropout(act) A_d^T from one pass over gate|up (ur_swiglu_lora_fwd)
                 bits_d = bp(i, 3)
                 if bits_d is None and pdrop > 0.0:
                     bits_d = hip.lora_dropout_bits(self.lora_dropout_seed(step, i, 3), pdrop, M, I, 1, dev, row0=row0)
                 act, t_d = hip.swiglu_lora_fwd(gu, I, w16(nm[3].a[0]), alpha=sc / (1.0 - pdrop), bits=bits_d)
                 L["bits_d"] = bits_d
             else:
-                if plan.swiglu == "alone":
+                if swiglu == "alone":
                     act = hip.swiglu_fwd(gu, I)
                 t_d, L["bits_d"] = lora_down(act, i, 3)
-            x3 = hip.gemm(act, fl["d"], residual=x2, R2=t_d, S2=w16(nm[3].b[0]))
+            x3 = hip.gemm(act, fl["d"], residual=x2, R2=t_d, S2=w16(nm[3].b[0]) if t_d is not None else None)
             L.update(rstd1=rstd1, qkv=qkv, actx=actx, att=att2, x2=x2, rstd2=rstd2, gu=gu, act=act,      # (qkv is None under the fused q/k-norm + RoPE epilogue)
                      t_qkv=t_qkv, t_o=t_o, t_gu=t_gu, t_d=t_d)
             # (recompute_mlp = True: every layer; an int k: layers 0 .. k - 1 only -- as much memory as the shape needs, no more recomputation than that)
@@ -666,7 +794,7 @@ class Qwen3LoRAModel(nn.Module):
                 # memory for time: gate|up and act (2 x [M, 3I] bf16 over the stack: 67 GB at C4) are dropped and rebuilt in the
                 # backward by the very launch that made them (bit-identical: same kernel, same operands).
                 if plan.mlp_recompute is not None:
-                    L.update(gu=None, act=None, mlp_recompute=plan.mlp_recompute)
+                    L.update(gu=None, act=None, mlp_recompute=plan.mlp_recompute, bc_gu=bc_guP[i] if plan.mlp_recompute == "pair" else bc_gu[i])
             if self.keep_norm_outputs:       # 2 x [M,D] bf16 per layer (15 GB at C4) instead of two RMSNorm recomputes
                 L.update(h=h, h2=h2)
             if keep:
@@ -688,7 +816,7 @@ class Qwen3LoRAModel(nn.Module):
         D, I, nq, nkv, hd, r = c.hidden_size, c.intermediate_size, c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.lora_r
         NQ, NKV = nq * hd, nkv * hd
         M = B * S
-        eps, sc = c.rms_norm_eps, (c.lora_alpha / c.lora_r if self.use_lora else 0.0)
+        eps, sc = c.rms_norm_eps, self._lora_scale()
         dev = d_pooled.device
         cos, sin = self._rope_tables(S, dev)
         dlast = hip.mean_pool_bwd(d_pooled.contiguous().to(F32), S).view(M, D)
@@ -701,18 +829,19 @@ class Qwen3LoRAModel(nn.Module):
         packed_bits = saved.get("bits_t", {})
         if saved.get("bits_t_event") is not None:
             torch.cuda.current_stream(dev).wait_event(saved["bits_t_event"])
-        # per adapter group: (first output column, width) of every adapter
-        out_cols = [[(sum(outs[:j]), n) for j, n in enumerate(outs)] for _, outs in self._group_dims()]
+        place = self._place      # per layer and adapter group: (first output column, width) of every present adapter, plane views
 
         def lora_grads(dy, t, xin, i, g, bits):
             """Adapter group g of layer i: dB_p = dy_p^T t_p ; tb = s * dy B ; dA_p = tb_p^T dropout_p(x).  Returns tb [M, nad * r] (bf16)."""
-            a_names, bnames, cols = self._names[i][g].a, self._names[i][g].b, out_cols[g]
+            a_names, bnames, cols = self._names[i][g].a, self._names[i][g].b, place[i][g].cols
             nb = len(bnames)
             touched.extend(bnames + a_names)
             gA = pack.fusedg(a_names) if nb > 1 else pack.g32(a_names[0])
             gB = pack.fusedg(bnames) if nb > 1 else pack.g32(bnames[0])            # [sum n, r]: adapter ranges in order
             tb = hip.lora_bgrad(dy, t, [lt[b] for b in bnames], cols, gB, alpha=sc)     # dB and tb, dy read once
             bits_t = packed_bits.get((i, g)) if bits is not None else None             # the prefetched token-packed flags
+            if bits_t is not None and place[i][g].view is not None:
+                bits_t = bits_t[place[i][g].view]                                      # (the present adapters' planes of the group's)
             if bits is not None and bits_t is None and plan.bits_t and xin.shape[1] % 64 == 0:
                 bits_t = hip.lora_bits_transpose(bits, xin.shape[1])          # (no prefetch this step: made here)
             hip.lora_reduce(xin, tb, gA, nad=nb, alpha=1.0 / (1.0 - pdrop), bits=bits, bits_t=bits_t)
@@ -724,7 +853,7 @@ class Qwen3LoRAModel(nn.Module):
             dropout, and is a masked rank-r epilogue (ur_gemm drop_bits) when there is.  Without adapters: dx = dy W.
             swiglu = (gu, dgu): dx is d(act) and leaves the GEMM as dgate | dup (SwiGLU backward in the epilogue: d(act) is never stored)."""
             tb = AT = drop = None
-            if pack is not None:
+            if pack is not None and place[i][g].planes:
                 key, a_names = ADAPTER_GROUPS[g][0], self._names[i][g].a
                 bits = L["bits_" + key]
                 tb = lora_grads(dy, L["t_" + key], xin, i, g, bits)
@@ -745,9 +874,9 @@ class Qwen3LoRAModel(nn.Module):
                     scratch["act"] = torch.empty((M, I), dtype=BF16, device=dev)
                 gu, act = scratch["gu"], scratch["act"]
                 if L["mlp_recompute"] == "pair":
-                    hip.gemm(h2, fl["guP"], out=gu, R2=L["t_gu"], S2=self._bcomb["guP"][i], swiglu_paired=act)
+                    hip.gemm(h2, fl["guP"], out=gu, R2=L["t_gu"], S2=L["bc_gu"], swiglu_paired=act)
                 else:            # "merged" / "plain" (no adapters)
-                    hip.gemm(h2, fl["gu"], out=gu, R2=L["t_gu"], S2=None if pack is None else self._bcomb["gu"][i])
+                    hip.gemm(h2, fl["gu"], out=gu, R2=L["t_gu"], S2=L["bc_gu"])
                     hip.swiglu_fwd(gu, I, out=act)
             dgu = torch.empty_like(gu)
             proj_bwd(dx, fl["dT"], act, i, 3, L, swiglu=(gu, dgu))
