@@ -4,7 +4,8 @@ shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
     python tools/kernel_bench.py attn|gemm|lora [--B 8] [--iters 5]
     python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 [--D 1024] [--rounds 3] [--chunks]
     python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 --scorer vector mfma --catalog-dtype bf16
-    python tools/kernel_bench.py negatives --B 64 --P 1000 --N 1000000 --K 128 [--catalog-dtype f32|bf16] [--rounds 3]"""
+    python tools/kernel_bench.py negatives --B 64 --P 1000 --N 1000000 --K 128 [--catalog-dtype f32|bf16] [--rounds 3]
+    python tools/kernel_bench.py catalog_softmax --users 64 512 --dtypes f32 bf16 --N 1000000 [--D 1024] [--rounds 5]"""
 import argparse
 import os
 import sys
@@ -360,9 +361,51 @@ def negatives(args):
             print(f"{name:60s}: median {t[len(t) // 2]:9.3f} ms  min {t[0]:9.3f}  max {t[-1]:9.3f}  ({len(t)} alternating rounds of {args.iters} calls){rate}")
 
 
+def catalog_softmax(args):
+    """The full-catalogue softmax loss (hip.catalog_softmax) forward only and forward + backward, alternating --rounds times in this process
+    with one streaming retrieval pass (hip.catalog_select, K = 128, rank included) at the same shape -- the code that loss was built beside,
+    on the same box.  Per (--users, --dtypes) pair: device-event time of each call, its ratio to the retrieval pass, and what the
+    algorithm needs over that time: catalogue bytes per sweep (1 sweep forward, 3 with the backward: score, score again, gradient
+    product; retrieval: 1) against the HBM read ceiling, and 2 B N D FLOP per sweep against the f32-MFMA peak."""
+    N, D = args.N, args.D
+    g = torch.Generator(device="cuda").manual_seed(0)
+    cat32 = torch.randn(N, D, generator=g, device="cuda")
+    for dtype in (args.dtypes or [args.catalog_dtype]):
+        cat = cat32 if dtype == "f32" else cat32.to(torch.bfloat16)
+        for B in (args.users or [args.B]):
+            user = torch.randn(B, D, generator=g, device="cuda")
+            gt = torch.randint(0, N, (B,), generator=g, device="cuda")
+            seen = torch.sort(torch.randint(0, N, (B, 50), generator=g, device="cuda"), dim=1).values.contiguous()
+            inv = hip.catalog_select(user[:1].contiguous(), cat, 1)[3]             # the catalogue norms: cached by every caller
+            variants = [("retrieve K=128", lambda: hip.catalog_select(user, cat, 128, inv, gt_index=gt, exclude=seen), 1),
+                        ("softmax forward", lambda: hip.catalog_softmax(user, cat, gt, 0.07, inv, exclude=seen, need_grad=False), 1),
+                        ("softmax forward + backward", lambda: hip.catalog_softmax(user, cat, gt, 0.07, inv, exclude=seen), 3)]
+            times = {name: [] for name, _, _ in variants}
+            for name, fn, _ in variants:                                          # warm-up: code objects, scratch buffers
+                fn(); fn()
+            torch.cuda.synchronize()
+            for _ in range(args.rounds):
+                for name, fn, _ in variants:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(args.iters):
+                        fn()
+                    e1.record(); torch.cuda.synchronize()
+                    times[name].append(e0.elapsed_time(e1) / args.iters)
+            cat_bytes, flop = cat.numel() * cat.element_size(), 2.0 * B * N * D
+            med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+            print(f"catalog_softmax B={B} N={N} D={D} catalogue {dtype} ({cat_bytes / 2**30:.2f} GiB), exclude [B,50], {args.rounds} alternating rounds of {args.iters} calls")
+            for name, _, sweeps in variants:
+                t = sorted(times[name])
+                print(f"  {name:28s}: median {med[name]:8.3f} ms  min {t[0]:8.3f}  max {t[-1]:8.3f}  x{med[name] / med['retrieve K=128']:5.2f} of a retrieval pass"
+                      f"  {sweeps} sweep(s): {sweeps * cat_bytes / med[name] / 1e9:6.2f} TB/s of catalogue  {sweeps * flop / med[name] / 1e9:7.1f} TFLOP/s f32")
+            del user
+        del cat
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog", "negatives"])
+    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog", "negatives", "catalog_softmax"])
     ap.add_argument("--B", type=int, default=8)
     ap.add_argument("--S", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=5)
@@ -374,8 +417,10 @@ if __name__ == "__main__":
     ap.add_argument("--chunks", action="store_true", help="catalog: also time retrieve() at half and double the default rows per chunk")
     ap.add_argument("--scorer", nargs="+", choices=["vector", "mfma"], help="catalog: time retrieve() with each of these scorers, alternating")
     ap.add_argument("--catalog-dtype", choices=["f32", "bf16"], default="f32", help="catalog: the dtype the catalogue is stored in")
+    ap.add_argument("--users", type=int, nargs="+", help="catalog_softmax: the user counts to time (default: --B)")
+    ap.add_argument("--dtypes", nargs="+", choices=["f32", "bf16"], help="catalog_softmax: the catalogue dtypes to time (default: --catalog-dtype)")
     ap.add_argument("--P", type=int, default=1000, help="negatives: candidate columns per user")
     ap.add_argument("--lib", action="store_true", help="gemm: also time torch.matmul on the same operands (reference point)")
     a = ap.parse_args()
     {"attn": attn, "gemm": gemm, "lora": lora, "rope": rope, "dw": dw, "xattn": xattn, "gemm_lora": gemm_lora, "gemm_merge": gemm_merge, "gemm_step": gemm_step, "rmslora": rmslora, "swilora": swilora,
-     "catalog": catalog, "negatives": negatives}[a.what](a)
+     "catalog": catalog, "negatives": negatives, "catalog_softmax": catalog_softmax}[a.what](a)

@@ -1,4 +1,4 @@
-"""ctypes binding of libunirec_hip.so (the C ABI declared in include/unirec_hip.h).
+"""ctypes binding of libunirec_hip.so (the C ABI declared in include/unirec_hip.h and include/unirec_hip_loss.h).
 
 Fails loudly: there is no CPU / eager fallback for the product path.
 """
@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -93,6 +93,18 @@ class CatalogSelect(ctypes.Structure):
                 ("chunk_rows", c_i64),
                 ("workspace", c_void_p), ("workspace_bytes", c_i64),
                 ("catalog_bf16", c_int), ("scorer", c_int)]
+
+
+class CatalogSoftmax(ctypes.Structure):
+    """Mirror of ur_catalog_softmax_t (include/unirec_hip_loss.h)."""
+    _fields_ = [("user", c_void_p), ("catalog", c_void_p), ("catalog_bf16", c_int),
+                ("cat_inv_norm", c_void_p), ("cat_norm_ready", c_int),
+                ("gt_index", c_void_p), ("exclude", c_void_p), ("E", c_int),
+                ("temperature", c_float), ("grad_scale", c_float),
+                ("loss", c_void_p), ("row_loss", c_void_p), ("lse", c_void_p), ("d_user", c_void_p),
+                ("B", c_int), ("N", c_i64), ("D", c_int),
+                ("chunk_rows", c_i64), ("scorer", c_int),
+                ("workspace", c_void_p), ("workspace_bytes", c_i64)]
 
 
 class F32Range(ctypes.Structure):
@@ -204,6 +216,12 @@ SIGNATURES = {
     "ur_grad_norm_clip": (c_int, [ctypes.POINTER(F32Range), c_int, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
 }
 
+# the loss family: every symbol include/unirec_hip_loss.h declares (tests/test_catalog_softmax_host.py holds this table to that
+# header and to the built library as tests/test_cabi.py holds SIGNATURES to unirec_hip.h)
+LOSS_SIGNATURES = {
+    "ur_catalog_softmax": (c_int, [ctypes.POINTER(CatalogSoftmax), c_void_p]),
+}
+
 _lib = None
 
 
@@ -225,7 +243,7 @@ def load():
     # two runtimes and the library's launches fail with "no ROCm-capable device is detected".
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -19,6 +19,7 @@
 //                       (catalog_scores_mfma_kernel: the vector kernel's fmaf chains and sum tree, so the same score bits).
 #include "common.hip.h"
 #include "unirec_hip.h"
+#include "unirec_hip_loss.h"
 
 namespace {
 
@@ -420,6 +421,243 @@ __global__ __launch_bounds__(256) void catalog_select_kernel(const float* __rest
   }
 }
 
+// ---- full-catalogue softmax loss (ur_catalog_softmax, include/unirec_hip_loss.h) ---------------------------------------------------
+// Both passes stream the catalogue through the chunk buffer with the scoring launches of select mode.  Every kernel here reduces in
+// a fixed order (a thread's strided sequence, wave_sum's tree, the four waves in index order) and nothing is added atomically.
+// z_bn is the ROUNDED f32 product s_bn * (1 / tau) wherever it is formed (csm_z: a multiply that is never contracted into the
+// subtraction that follows it -- fused, z - max would be the product's rounding residue instead of 0 for the maximum itself), so the
+// maximum, the ground truth's z and the exponents agree to the bit and a one-term sum gives exactly 0.
+__device__ __forceinline__ float csm_z(float s, float inv_tau) {
+#pragma clang fp contract(off)
+  return s * inv_tau;
+}
+//
+// item n is excluded for the user of exclusion row ex[0..E) and ground truth g: select mode's rule and its search.  Most of a chunk
+// lies outside [first non-negative entry, last entry]: those scores skip the search.
+__device__ __forceinline__ bool csm_excluded(const long* __restrict__ ex, int E, long g, long n) {
+  return E > 0 && n != g && n <= ex[E - 1] && sel_excluded(ex, E, n);
+}
+__device__ __forceinline__ float csm_block_sum(float v, float* red) {      // red: 4 floats of LDS; every thread gets the sum
+  v = wave_sum(v);
+  __syncthreads();                                                          // (red may still be read from the previous reduction)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ float csm_block_max(float v, float* red) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// Pass 1 and the weights of pass 2 split a user's chunk row over CSM_SEGS workgroups (a few users would otherwise occupy a few compute
+// units): segment j owns the rows [j seg, (j + 1) seg) of every chunk and its own running slot [b][j], carried across the chunks in the
+// stream's order; the slots of a user are merged in index order at the end.  seg is fixed by the chunk size, so a (shorter) last
+// chunk leaves its trailing segments without rows: those keep their slots (or, on the first chunk, initialise them).
+constexpr int CSM_SEGS = 16;
+
+// Pass 1, one workgroup per (user, segment) and chunk: slot (m, l) <- the running maximum and sum_n exp(z_bn - m) over the segment's
+// rows seen so far (chunk[b][0..len) = s_bn of catalogue rows c0 .. c0+len).  Two sweeps over the rows (just written: cache
+// resident): their maximum, then the sum against max(m, that maximum); the old sum is rescaled once per chunk.
+__global__ __launch_bounds__(256) void catalog_softmax_fold_kernel(const float* __restrict__ chunk, long ld, int c0, int len, int seg,
+                                                                   const long* __restrict__ gt, const long* __restrict__ exclude, int E,
+                                                                   float inv_tau, float* __restrict__ m_run, float* __restrict__ l_run, int first) {
+  __shared__ float red[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int slot = b * CSM_SEGS + blockIdx.y;
+  const int n0 = blockIdx.y * seg, n1 = min(len, n0 + seg);
+  const float ninf = -__builtin_inff();
+  if (n0 >= n1) {                                                           // (uniform)
+    if (first && tid == 0) { m_run[slot] = ninf; l_run[slot] = 0.f; }
+    return;
+  }
+  const long g = gt[b];
+  const long* ex = E > 0 ? exclude + (long)b * E : nullptr;
+  const float* row = chunk + (long)b * ld;
+  float mx = ninf;
+  for (int n = n0 + tid; n < n1; n += 256)
+    if (!csm_excluded(ex, E, g, (long)c0 + n)) mx = fmaxf(mx, csm_z(row[n], inv_tau));
+  mx = csm_block_max(mx, red);
+  const float m_old = first ? ninf : m_run[slot];
+  const float l_old = first ? 0.f : l_run[slot];
+  const float m_new = fmaxf(m_old, mx);
+  float sum = 0.f;
+  if (mx > ninf)                                                            // (uniform; rows that are all excluded add nothing)
+    for (int n = n0 + tid; n < n1; n += 256)
+      if (!csm_excluded(ex, E, g, (long)c0 + n)) sum += expf(csm_z(row[n], inv_tau) - m_new);
+  sum = csm_block_sum(sum, red);
+  if (tid == 0) {
+    m_run[slot] = m_new;
+    l_run[slot] = (m_old > ninf ? l_old * expf(m_old - m_new) : 0.f) + sum;
+  }
+}
+
+// (m_b, l_b) = the user's CSM_SEGS slots merged in index order; lse_b = m_b + log l_b, row_loss_b = -z_b,g + lse_b (z_b,g from
+// catalog_gt_score_kernel's ref: the bits the chunk holds for row g), loss = their mean in a fixed order.  One wave.
+__global__ __launch_bounds__(64) void catalog_softmax_finish_kernel(const float* __restrict__ m_run, const float* __restrict__ l_run,
+                                                                    const float* __restrict__ ref, float inv_tau, float* __restrict__ lse,
+                                                                    float* __restrict__ row_loss, float* __restrict__ loss, int B) {
+  float s = 0.f;
+  for (int b = threadIdx.x; b < B; b += 64) {
+    float m = -__builtin_inff();
+    for (int j = 0; j < CSM_SEGS; ++j) m = fmaxf(m, m_run[b * CSM_SEGS + j]);
+    float l = 0.f;
+    for (int j = 0; j < CSM_SEGS; ++j) {
+      const float lj = l_run[b * CSM_SEGS + j];
+      if (lj > 0.f) l += lj * expf(m_run[b * CSM_SEGS + j] - m);             // (an empty slot is (-inf, 0))
+    }
+    const float v = m + logf(l);
+    const float r = v - csm_z(ref[b], inv_tau);
+    lse[b] = v;
+    row_loss[b] = r;
+    s += r;
+  }
+  s = wave_sum(s);
+  if (threadIdx.x == 0) loss[0] = s / (float)B;
+}
+
+// Pass 2, one workgroup per (user, segment) and chunk: chunk[b][n] <- w_bn * ic_n in place (w_bn = (exp(z_bn - lse_b) - [n == g_b]) / tau,
+// 0 for an excluded n) and slot t[b][j] += sum_n w_bn s_bn.
+__global__ __launch_bounds__(256) void catalog_softmax_weight_kernel(float* __restrict__ chunk, long ld, int c0, int len, int seg,
+                                                                     const float* __restrict__ inv_c, const long* __restrict__ gt,
+                                                                     const long* __restrict__ exclude, int E, float inv_tau,
+                                                                     const float* __restrict__ lse, float* __restrict__ t_run, int first) {
+  __shared__ float red[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int slot = b * CSM_SEGS + blockIdx.y;
+  const int n0 = blockIdx.y * seg, n1 = min(len, n0 + seg);
+  if (n0 >= n1) {                                                           // (uniform)
+    if (first && tid == 0) t_run[slot] = 0.f;
+    return;
+  }
+  const long g = gt[b];
+  const long* ex = E > 0 ? exclude + (long)b * E : nullptr;
+  float* row = chunk + (long)b * ld;
+  const float ls = lse[b];
+  float t = 0.f;
+  for (int n = n0 + tid; n < n1; n += 256) {
+    const long idx = (long)c0 + n;
+    const float s = row[n];
+    float w = 0.f;
+    if (!csm_excluded(ex, E, g, idx)) {
+      float p = expf(csm_z(s, inv_tau) - ls);
+      if (idx == g) p -= 1.0f;
+      w = p * inv_tau;
+    }
+    t = fmaf(w, s, t);
+    row[n] = w * inv_c[idx];
+  }
+  t = csm_block_sum(t, red);
+  if (tid == 0) t_run[slot] = (first ? 0.f : t_run[slot]) + t;
+}
+
+// Pass 2, the gradient product of one chunk: slab[z] [B,D] (+)= W [B x rows of split z] . C [those rows x D] on v_mfma_f32_16x16x4_f32,
+// the catalogue-row axis as K (W = the chunk after catalog_softmax_weight_kernel, leading dimension ld; C = the chunk's rows, bf16
+// widened exactly on load).  A workgroup = 4 waves owns CSM_USERS users x 256 columns and the rows [z rps, (z+1) rps) of the chunk; wave w
+// owns 64 of the columns as four 16-column tiles, tile t holding the columns d0 + 4 c + t (c = the MFMA column), so that a lane
+// loads its four tiles' operands of a row as one 16-byte piece and stores its results as 16-byte pieces.  One step takes 16 rows:
+// lane (user u, q = lane >> 4) brings W[u][n0 + 4q + j] and lane (q, c) the piece of row n0 + 4q + j for j = 0 .. 3, i.e. the K index
+// of MFMA j is q <-> row n0 + 4q + j -- an order of the sum, fixed by (rps, the chunk rows) alone.  A row past the split's end
+// enters as zeros on both sides.  Users past B and columns past D are computed on clamped addresses and never stored (an output
+// element depends on its own user and column only).  The slabs are accumulated across chunks by the stream's order: the first chunk
+// stores, later chunks add; a split without rows in a later (shorter) chunk leaves its slab alone.
+constexpr int CSM_UT = 2, CSM_USERS = 16 * CSM_UT;
+template <typename CT>
+__global__ __launch_bounds__(256) void catalog_softmax_grad_kernel(const float* __restrict__ wchunk, long ld, int len, const CT* __restrict__ cat,
+                                                                   float* __restrict__ slabs, int B, int D, int rps, int first) {
+  const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
+  const int wave = threadIdx.x >> 6;
+  const int b0 = blockIdx.x * CSM_USERS;
+  const int d0 = blockIdx.y * 256 + wave * 64;
+  if (d0 >= D) return;                                                      // (wave-uniform; the kernel has no barrier)
+  const int r0 = blockIdx.z * rps, r1 = min(len, r0 + rps);
+  if (r0 >= r1 && !first) return;
+  const int d = d0 + 4 * col;
+  const CT* cp = cat + min(d, D - 4);
+  const float* wp[CSM_UT];
+#pragma unroll
+  for (int t = 0; t < CSM_UT; ++t) wp[t] = wchunk + (long)min(b0 + t * 16 + col, B - 1) * ld;
+  f32x4 acc[CSM_UT][4];
+#pragma unroll
+  for (int t = 0; t < CSM_UT; ++t)
+#pragma unroll
+    for (int x = 0; x < 4; ++x) acc[t][x] = f32x4{0.f, 0.f, 0.f, 0.f};
+  int n0 = r0;
+  for (; n0 + 16 <= r1; n0 += 16) {
+    float a[CSM_UT][4];
+    float4 c[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int n = n0 + 4 * q + j;
+      c[j] = load4(cp + (long)n * D);
+#pragma unroll
+      for (int t = 0; t < CSM_UT; ++t) a[t][j] = wp[t][n];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int t = 0; t < CSM_UT; ++t) {
+        acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][j], c[j].x, acc[t][0], 0, 0, 0);
+        acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][j], c[j].y, acc[t][1], 0, 0, 0);
+        acc[t][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][j], c[j].z, acc[t][2], 0, 0, 0);
+        acc[t][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][j], c[j].w, acc[t][3], 0, 0, 0);
+      }
+  }
+  if (n0 < r1) {                                                            // the ragged last step of the split
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int n = n0 + 4 * q + j;
+      const bool in = n < r1;
+      const int ns = in ? n : r1 - 1;
+      float4 c = load4(cp + (long)ns * D);
+      if (!in) c = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int t = 0; t < CSM_UT; ++t) {
+        const float a = in ? wp[t][ns] : 0.f;
+        acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, c.x, acc[t][0], 0, 0, 0);
+        acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, c.y, acc[t][1], 0, 0, 0);
+        acc[t][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, c.z, acc[t][2], 0, 0, 0);
+        acc[t][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, c.w, acc[t][3], 0, 0, 0);
+      }
+    }
+  }
+  if (d >= D) return;
+  float* slab = slabs + (long)blockIdx.z * B * D;
+#pragma unroll
+  for (int t = 0; t < CSM_UT; ++t)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {                                           // C/D layout: column = lane & 15, row (user) = 4 (lane >> 4) + register
+      const int u = b0 + t * 16 + 4 * q + e;
+      if (u < B) {
+        float4* o = reinterpret_cast<float4*>(slab + (long)u * D + d);
+        float4 v = make_float4(acc[t][0][e], acc[t][1][e], acc[t][2][e], acc[t][3][e]);
+        if (!first) { const float4 p = *o; v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w; }
+        *o = v;
+      }
+    }
+}
+
+// d_user[b] = gscale * iu_b * (sum_z slab[z][b] - u_b * iu_b * t_b), the slabs and the slots of t_b added in index order
+__global__ __launch_bounds__(256) void catalog_softmax_duser_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
+                                                                    const float* __restrict__ t_run, const float* __restrict__ slabs,
+                                                                    float* __restrict__ d_user, int B, int D, int nslab, float gscale) {
+  const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i >= (long)B * D) return;
+  const int b = (int)(i / D);
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int z = 0; z < nslab; ++z) {
+    const float4 p = *reinterpret_cast<const float4*>(slabs + (long)z * B * D + i);
+    s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
+  }
+  float t = 0.f;
+  for (int j = 0; j < CSM_SEGS; ++j) t += t_run[b * CSM_SEGS + j];
+  const float iu = inv_u[b], k = iu * t, gs = gscale * iu;
+  const float4 u = *reinterpret_cast<const float4*>(user + i);
+  *reinterpret_cast<float4*>(d_user + i) = make_float4(gs * (s.x - u.x * k), gs * (s.y - u.y * k), gs * (s.z - u.z * k), gs * (s.w - u.w * k));
+}
+
 // Context MLP, first layer: h1[n][j] = gelu(b1[j] + sum_f W1[j][f] * feat_f(n)), bf16 out.
 //   KIND 0: TimestampEncoder features, models/mwne.py:525-565 (9 = secular + 4 sin/cos pairs, all in f32 as the
 //           reference computes them from timestamps.float()).
@@ -641,6 +879,120 @@ extern "C" int ur_catalog_scores(const float* user, const float* catalog, float*
   if (bf16)
     return catalog_stream(user, (const bf16_t*)catalog, user_inv_norm, cat_inv_norm, cat_norm_ready, B, N, D, select, chunk_bytes, rows, mfma, st);
   return catalog_stream(user, catalog, user_inv_norm, cat_inv_norm, cat_norm_ready, B, N, D, select, chunk_bytes, rows, mfma, st);
+}
+
+// ---- ur_catalog_softmax (include/unirec_hip_loss.h) ------------------------------------------------------------------------------
+// row splits of the gradient product: ~1024 workgroups in all, no split shorter than 64 rows; rps = rows per split (a multiple of 4)
+static void catalog_softmax_splits(int32_t B, int32_t D, int64_t rows, int* nsplit, int* rps) {
+  const long tiles = (long)ur_cdiv(B > 0 ? B : 1, CSM_USERS) * ur_cdiv(D, 256);
+  long s = 1024 / tiles;
+  if (s > (rows + 63) / 64) s = (rows + 63) / 64;
+  if (s < 1) s = 1;
+  long r = ((rows + s - 1) / s + 3) / 4 * 4;
+  *rps = (int)r;
+  *nsplit = (int)((rows + r - 1) / r);
+}
+
+// the workspace: chunk [B][rows] | user_inv_norm, ref: [B] each | m, l, t: [B][CSM_SEGS] each | slabs [nsplit][B][D] (with d_user only)
+struct catalog_softmax_plan {
+  int64_t rows, chunk_bytes, vec_bytes, seg_bytes, need;
+  int nsplit, rps, seg;
+};
+static catalog_softmax_plan catalog_softmax_layout(int32_t B, int64_t N, int32_t D, int64_t chunk_rows, bool grad) {
+  catalog_softmax_plan p;
+  p.rows = catalog_chunk_rows(chunk_rows, B, N);
+  p.chunk_bytes = ((int64_t)B * p.rows * 4 + 15) / 16 * 16;
+  p.vec_bytes = ((int64_t)B * 4 + 15) / 16 * 16;
+  p.seg_bytes = (int64_t)B * CSM_SEGS * 4;
+  p.seg = (int)((p.rows + CSM_SEGS - 1) / CSM_SEGS);
+  catalog_softmax_splits(B, D, p.rows, &p.nsplit, &p.rps);
+  p.need = p.chunk_bytes + 2 * p.vec_bytes + 3 * p.seg_bytes + (grad ? (int64_t)p.nsplit * B * D * 4 : 0);
+  if (p.need < 16) p.need = 16;
+  return p;
+}
+
+// the launches, after every check
+template <typename CT>
+static int catalog_softmax_stream(const ur_catalog_softmax_t* a, const CT* catalog, const catalog_softmax_plan& p, bool mfma, hipStream_t st) {
+  const int32_t B = a->B, D = a->D, E = a->E;
+  const int64_t N = a->N, rows = p.rows;
+  char* ws = (char*)a->workspace;
+  float* chunk = (float*)ws;
+  float* inv_u = (float*)(ws + p.chunk_bytes);
+  float* ref = (float*)(ws + p.chunk_bytes + p.vec_bytes);
+  float* m_run = (float*)(ws + p.chunk_bytes + 2 * p.vec_bytes);
+  float* l_run = (float*)(ws + p.chunk_bytes + 2 * p.vec_bytes + p.seg_bytes);
+  float* t_run = (float*)(ws + p.chunk_bytes + 2 * p.vec_bytes + 2 * p.seg_bytes);
+  float* slabs = (float*)(ws + p.chunk_bytes + 2 * p.vec_bytes + 3 * p.seg_bytes);
+  const long* gt = (const long*)a->gt_index;
+  const long* ex = (const long*)a->exclude;
+  const float inv_tau = 1.0f / a->temperature;
+  hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a->user, inv_u, (long)B, (int)D);
+  if (!a->cat_norm_ready)
+    hipLaunchKernelGGL(row_inv_norm_kernel<CT>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, a->cat_inv_norm, (long)N, (int)D);
+  hipLaunchKernelGGL(catalog_gt_score_kernel<CT>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a->user, (const float*)inv_u, catalog,
+                     (const float*)a->cat_inv_norm, gt, ref, (int)B, (long)N, (int)D);
+  UR_CHECK_LAUNCH("ur_catalog_softmax");
+  for (int pass = 0; pass < (a->d_user ? 2 : 1); ++pass) {
+    for (int64_t c0 = 0; c0 < N; c0 += rows) {
+      const int64_t len = N - c0 < rows ? N - c0 : rows;
+      const int rc = mfma ? launch_catalog_scores_mfma<CT>(a->user, inv_u, catalog + c0 * D, a->cat_inv_norm + c0, chunk, B, len, D, st)
+                          : launch_catalog_scores<CT>(a->user, inv_u, catalog + c0 * D, a->cat_inv_norm + c0, chunk, B, len, D, st);
+      if (rc != 0) return rc;
+      if (pass == 0) {
+        hipLaunchKernelGGL(catalog_softmax_fold_kernel, dim3((unsigned)B, CSM_SEGS), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0, (int)len,
+                           p.seg, gt, ex, E, inv_tau, m_run, l_run, (int)(c0 == 0));
+      } else {
+        hipLaunchKernelGGL(catalog_softmax_weight_kernel, dim3((unsigned)B, CSM_SEGS), dim3(256), 0, st, chunk, (long)len, (int)c0, (int)len,
+                           p.seg, (const float*)a->cat_inv_norm, gt, ex, E, inv_tau, (const float*)a->lse, t_run, (int)(c0 == 0));
+        hipLaunchKernelGGL(catalog_softmax_grad_kernel<CT>, dim3((unsigned)ur_cdiv(B, CSM_USERS), (unsigned)ur_cdiv(D, 256), (unsigned)p.nsplit),
+                           dim3(256), 0, st, (const float*)chunk, (long)len, (int)len, catalog + c0 * D, slabs, (int)B, (int)D, p.rps,
+                           (int)(c0 == 0));
+      }
+      UR_CHECK_LAUNCH("ur_catalog_softmax");
+    }
+    if (pass == 0) {
+      hipLaunchKernelGGL(catalog_softmax_finish_kernel, dim3(1), dim3(64), 0, st, (const float*)m_run, (const float*)l_run, (const float*)ref,
+                         inv_tau, a->lse, a->row_loss, a->loss, (int)B);
+    } else {
+      hipLaunchKernelGGL(catalog_softmax_duser_kernel, dim3((unsigned)(((long)B * D / 4 + 255) / 256)), dim3(256), 0, st, a->user,
+                         (const float*)inv_u, (const float*)t_run, (const float*)slabs, a->d_user, (int)B, (int)D, p.nsplit,
+                         a->grad_scale / (float)B);
+    }
+    UR_CHECK_LAUNCH("ur_catalog_softmax");
+  }
+  return 0;
+}
+
+extern "C" int ur_catalog_softmax(ur_catalog_softmax_t* a, void* stream) {
+  UR_REQUIRE(a, "ur_catalog_softmax: null argument struct");
+  const int32_t B = a->B, D = a->D, E = a->E;
+  const int64_t N = a->N;
+  UR_REQUIRE(B >= 0 && D > 0 && (D % 4) == 0 && D <= 2048, "ur_catalog_softmax: need B >= 0, D %% 4 == 0 and D <= 2048 (got B %d, D %d)", B, D);
+  UR_REQUIRE(N >= 1 && N <= (int64_t)INT32_MAX, "ur_catalog_softmax: need 1 <= N <= INT32_MAX (got %lld)", (long long)N);
+  UR_REQUIRE(a->temperature > 0.f && a->temperature <= 3.0e38f, "ur_catalog_softmax: temperature must be positive and finite (got %g)", (double)a->temperature);
+  UR_REQUIRE(a->chunk_rows >= 0 && (a->chunk_rows % SEL_TILE) == 0,
+             "ur_catalog_softmax: chunk_rows must be 0 or a positive multiple of %d (got %lld)", SEL_TILE, (long long)a->chunk_rows);
+  UR_REQUIRE(E >= 0 && (E == 0 || a->exclude), "ur_catalog_softmax: E > 0 needs exclude");
+  UR_REQUIRE(a->catalog_bf16 == 0 || a->catalog_bf16 == 1, "ur_catalog_softmax: catalog_bf16 must be 0 or 1 (got %d)", a->catalog_bf16);
+  UR_REQUIRE(a->scorer >= 0 && a->scorer <= UR_CATALOG_SCORER_MFMA,
+             "ur_catalog_softmax: scorer must be 0 (the library chooses), 1 (vector) or 2 (f32 MFMA) (got %d)", a->scorer);
+  const catalog_softmax_plan p = catalog_softmax_layout(B, N, D, a->chunk_rows, a->d_user != nullptr);
+  if (!a->workspace) {
+    a->workspace_bytes = p.need;
+    return 0;
+  }
+  UR_REQUIRE(UR_ALIGNED16(a->workspace) && a->workspace_bytes >= p.need,
+             "ur_catalog_softmax: workspace must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)p.need, (long long)a->workspace_bytes);
+  if (B == 0) return 0;
+  UR_REQUIRE(a->user && a->catalog && a->cat_inv_norm && a->gt_index && a->loss && a->row_loss && a->lse, "ur_catalog_softmax: null pointer");
+  UR_REQUIRE(UR_ALIGNED16(a->user) && UR_ALIGNED16(a->catalog) && (!a->d_user || UR_ALIGNED16(a->d_user)),
+             "ur_catalog_softmax: user, catalog and d_user must be 16-byte aligned");
+  const bool bf16 = a->catalog_bf16 == 1;
+  const bool mfma = a->scorer == UR_CATALOG_SCORER_MFMA || (a->scorer == 0 && catalog_default_is_mfma(B, N, D, bf16));
+  hipStream_t st = (hipStream_t)stream;
+  if (bf16) return catalog_softmax_stream(a, (const bf16_t*)a->catalog, p, mfma, st);
+  return catalog_softmax_stream(a, (const float*)a->catalog, p, mfma, st);
 }
 
 extern "C" int ur_rank_of_index(const float* scores, const int64_t* gt_index, int32_t* rank, int32_t B, int64_t N, void* stream) {

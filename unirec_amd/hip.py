@@ -1130,6 +1130,60 @@ def catalog_select(user, catalog, K, cat_inv_norm=None, gt_index=None, exclude=N
     return idx, val, rank, cat_inv_norm
 
 
+def catalog_softmax(user, catalog, gt_index, temperature, cat_inv_norm=None, exclude=None, chunk_rows=None, scorer=None, grad_scale=1.0,
+                    need_grad=True):
+    """The softmax loss over the whole catalogue [N,D] f32 or bf16 (ur_catalog_softmax, include/unirec_hip_loss.h): cross-entropy of
+    catalogue row gt_index[b] against every row under catalog_select's own f32 cosine scores divided by `temperature`, streamed in
+    chunks (no [B,N] tensor), and grad_scale * d loss / d user.  exclude int64 [B,E], rows sorted ascending with negative entries as empty
+    slots: those items leave the sum, except the user's own gt_index.  chunk_rows, scorer: as for catalog_select (the result's bits do
+    not depend on the scorer).  need_grad=False runs the forward pass alone.
+    Returns (loss f32 [1], row_loss f32 [B], lse f32 [B], d_user f32 [B,D] or None, cat_inv_norm)."""
+    scorer_id = catalog_scorer_id(scorer)
+    lib = _lib.load()
+    _need(user, F32, "user")
+    if catalog.dtype not in (F32, BF16):
+        raise ValueError(f"catalog_softmax: catalog must be f32 or bf16, got {catalog.dtype}")
+    _need(catalog, catalog.dtype, "catalog")
+    if user.dim() != 2 or catalog.dim() != 2 or catalog.shape[1] != user.shape[1]:
+        raise ValueError(f"catalog_softmax: user [B,D] and catalog [N,D] must share D, got {tuple(user.shape)} and {tuple(catalog.shape)}")
+    B, D = user.shape
+    N = catalog.shape[0]
+    dev = user.device
+    a = _lib.CatalogSoftmax()
+    a.user, a.catalog, a.catalog_bf16 = user.data_ptr(), catalog.data_ptr(), int(catalog.dtype == BF16)
+    a.B, a.N, a.D = B, N, D
+    a.temperature, a.grad_scale = float(temperature), float(grad_scale)
+    a.chunk_rows, a.scorer = int(chunk_rows or 0), scorer_id
+    gt = gt_index.to(device=dev, dtype=torch.int64).contiguous()
+    if gt.shape != (B,):
+        raise ValueError(f"catalog_softmax: gt_index must have shape [{B}], got {tuple(gt.shape)}")
+    a.gt_index = gt.data_ptr()
+    if exclude is not None:
+        _need(exclude, torch.int64, "exclude")
+        if exclude.dim() != 2 or exclude.shape[0] != B:
+            raise ValueError(f"catalog_softmax: exclude must be [{B}, E], got {tuple(exclude.shape)}")
+        a.E = exclude.shape[1]
+        a.exclude = exclude.data_ptr() if a.E else None
+    loss = torch.empty((1,), dtype=F32, device=dev)
+    row_loss = torch.empty((B,), dtype=F32, device=dev)
+    lse = torch.empty((B,), dtype=F32, device=dev)
+    d_user = torch.empty((B, D), dtype=F32, device=dev) if need_grad else None
+    a.loss, a.row_loss, a.lse, a.d_user = loss.data_ptr(), row_loss.data_ptr(), lse.data_ptr(), _p(d_user) or None
+    ready = cat_inv_norm is not None
+    if not ready:
+        cat_inv_norm = torch.empty((N,), dtype=F32, device=dev)
+    else:
+        _need(cat_inv_norm, F32, "cat_inv_norm")
+        if cat_inv_norm.shape != (N,):
+            raise ValueError(f"catalog_softmax: cat_inv_norm must have shape [{N}], got {tuple(cat_inv_norm.shape)}")
+    a.cat_inv_norm, a.cat_norm_ready = cat_inv_norm.data_ptr(), int(ready)
+    check(lib.ur_catalog_softmax(ctypes.byref(a), _stream()), "ur_catalog_softmax")        # size query: workspace is NULL
+    ws = workspace(a.workspace_bytes, dev, "catalog_softmax")
+    a.workspace = ws.data_ptr()
+    check(lib.ur_catalog_softmax(ctypes.byref(a), _stream()), "ur_catalog_softmax")
+    return loss, row_loss, lse, d_user, cat_inv_norm
+
+
 def rank_of_index(scores, gt_index):
     """1-based rank of column gt_index[b] in the descending order of scores[b] (ties go to the ground truth)."""
     lib = _lib.load()

@@ -232,19 +232,101 @@ def mrr_ranks(user_embeddings, positive_item_embeddings, negative_item_embedding
     return scores, hip.mrr_rank(scores, m)
 
 
+class _CatalogSoftmaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, user, owner, gt, ex):
+        ev = owner.evaluator
+        loss, row_loss, lse, du, ev._inv = hip.catalog_softmax(user, ev.catalog, gt, owner.temperature, ev._inv, exclude=ex,
+                                                                 chunk_rows=owner.chunk_rows, scorer=owner.scorer, grad_scale=1.0,
+                                                                 need_grad=True)
+        owner.last_lse, owner.last_row_loss = lse, row_loss
+        ctx.du = du
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.du * g, None, None, None
+
+
+class CatalogSoftmaxLoss(nn.Module):
+    """Cross-entropy of each user's ground-truth item against EVERY row of a resident catalogue (cosine scores / temperature), streamed
+    in chunks by ``hip.catalog_softmax``: no sampled negatives, no [B,P,D] tensor, nothing of size B x N.  The catalogue is frozen; the
+    gradient reaches the user embeddings only."""
+
+    def __init__(self, catalog, temperature: float = 0.07, scorer=None, chunk_rows=None):
+        """catalog: a CatalogEvaluator (its catalogue and cached norms are used where they lie), or an [N,D] f32 / bf16 device tensor.
+        The catalogue's inverse norms are computed by the first call and kept.  scorer, chunk_rows: as for CatalogEvaluator.retrieve."""
+        super().__init__()
+        from .evaluation import CatalogEvaluator
+        hip.catalog_scorer_id(scorer)
+        if not isinstance(catalog, CatalogEvaluator):
+            catalog = torch.as_tensor(catalog)
+            if catalog.dim() != 2 or catalog.dtype not in (F32, BF16):
+                raise ValueError("CatalogSoftmaxLoss: catalog must be a CatalogEvaluator or an [N, D] f32 / bf16 tensor")
+            catalog = CatalogEvaluator(catalog, device=catalog.device, dtype=catalog.dtype)
+        if not float(temperature) > 0:
+            raise ValueError(f"CatalogSoftmaxLoss: temperature must be positive, got {temperature}")
+        self.evaluator, self.temperature, self.scorer, self.chunk_rows = catalog, float(temperature), scorer, chunk_rows
+        self.last_lse = self.last_row_loss = None
+
+    @property
+    def catalog(self):
+        return self.evaluator.catalog
+
+    def forward(self, user_embeddings, positive_item_index, exclude=None):
+        """exclude: the items each user has seen (ragged lists or [B,E] padded with -1); they leave the softmax's sum, except the user's
+        own positive.  Keeps ``last_lse`` and ``last_row_loss`` [B] of the call."""
+        from .evaluation import pack_exclude
+        dev = self.catalog.device
+        u = user_embeddings.contiguous().to(dev, F32)
+        gt = torch.as_tensor(positive_item_index).to(dev, torch.int64)
+        ex = pack_exclude(exclude, u.shape[0])
+        ex = None if ex is None else ex.to(dev)
+        return _CatalogSoftmaxFn.apply(u, self, gt, ex)
+
+
+LOSSES = ("infonce", "catalog_softmax")
+# batch keys that name or carry sampled candidates: a catalogue-softmax step has none
+_CANDIDATE_KEYS = ("negative_item_index", "negative_masks", "positive_item_embeddings", "negative_item_embeddings")
+
+
 class MultiModalTrainer:
     """compute_loss of the reference's HF-Trainer subclass (:477-498) without the Trainer."""
 
-    def __init__(self, temperature: float = 0.07, negatives=None):
-        """negatives: a ``negatives.CatalogCandidates``; needed by batches that carry ``positive_item_index`` instead of embeddings."""
+    def __init__(self, temperature: float = 0.07, negatives=None, loss: str = "infonce"):
+        """negatives: a ``negatives.CatalogCandidates``; needed by batches that carry ``positive_item_index`` instead of embeddings.
+        loss: "infonce" (the reference's loss over one positive and the batch's negatives) or "catalog_softmax" (``CatalogSoftmaxLoss``
+        over the whole catalogue of ``negatives``, which must then sample and mine nothing)."""
+        if loss not in LOSSES:
+            raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+        self.loss = loss
         self.infonce_loss = InfoNCELoss(temperature)
         self.negatives = negatives
+        self.catalog_softmax_loss = None
+        if loss == "catalog_softmax":
+            if negatives is None:
+                raise ValueError('loss="catalog_softmax" needs the `negatives` argument (a negatives.CatalogCandidates over the resident '
+                                 "catalogue)")
+            if negatives.num_random != 0 or negatives.num_hard != 0:
+                raise ValueError(f'loss="catalog_softmax" sums over the whole catalogue: negatives.num_random and negatives.num_hard must be 0 '
+                                 f"(got {negatives.num_random} and {negatives.num_hard})")
+            self.catalog_softmax_loss = CatalogSoftmaxLoss(negatives.evaluator, temperature, scorer=negatives.scorer,
+                                                           chunk_rows=negatives.chunk_rows)
 
     def compute_loss(self, model, inputs, return_outputs=False, step=0, **kwargs):
         """A batch with ``positive_item_index`` [B] takes its candidates from the resident catalogue of ``negatives``: optional
         ``negative_item_index`` [B,P] (padded with -1), ``negative_masks``, ``seen_item_index`` (ragged or [B,E] padded with -1), plus the
         random and mined negatives that object is configured for -- mined with the user embeddings of this very forward, random ones
-        keyed on (step, global sample index).  Any other batch carries the embeddings themselves, as the reference's collator does."""
+        keyed on (step, global sample index).  Any other batch carries the embeddings themselves, as the reference's collator does.
+        With loss="catalog_softmax" the batch holds ``positive_item_index`` and optionally ``seen_item_index`` and none of the
+        candidate keys: every catalogue row the user has not seen is a candidate."""
+        if self.loss == "catalog_softmax":
+            if "positive_item_index" not in inputs:
+                raise ValueError('compute_loss: loss="catalog_softmax" needs positive_item_index in the batch')
+            for key in _CANDIDATE_KEYS:
+                if key in inputs:
+                    raise ValueError(f'compute_loss: loss="catalog_softmax" takes every catalogue row as a candidate; the batch must not '
+                                     f"carry {key}")
         by_index = "positive_item_index" in inputs
         if by_index and self.negatives is None:
             raise ValueError("compute_loss: the batch holds positive_item_index, which needs the trainer's `negatives` argument "
@@ -252,7 +334,9 @@ class MultiModalTrainer:
         user_embeddings = model(input_ids=inputs["input_ids"], attention_mask=inputs["attention_mask"],
                                 history_field_embeddings=inputs["history_field_embeddings"],
                                 history_attention_mask=inputs["history_attention_mask"])
-        if by_index:
+        if self.loss == "catalog_softmax":
+            loss = self.catalog_softmax_loss(user_embeddings, inputs["positive_item_index"], exclude=inputs.get("seen_item_index", None))
+        elif by_index:
             pos, neg, mask, _ = self.negatives.candidates(
                 user_embeddings, inputs["positive_item_index"], inputs.get("negative_item_index", None), inputs.get("negative_masks", None),
                 exclude=inputs.get("seen_item_index", None), step=step, first_sample=model.base_model.first_sample(user_embeddings.shape[0]))
@@ -344,14 +428,16 @@ class JointTrainer:
     the norm is the norm of the averaged gradient (DDP + clip_grad_norm_), the same on every rank.  ``state.log_history`` gets
     {step, loss, grad_norm, learning_rate} every ``logging_steps`` -- the only host read (rank-local loss).
     ``negatives`` (a ``negatives.CatalogCandidates``) lets a batch name its candidates by index into a resident catalogue
-    (``MultiModalTrainer.compute_loss``); the random negatives of such a batch are keyed on ``state.global_step``."""
+    (``MultiModalTrainer.compute_loss``); the random negatives of such a batch are keyed on ``state.global_step``.
+    ``loss="catalog_softmax"`` replaces InfoNCE by the softmax over that whole catalogue (``CatalogSoftmaxLoss``); gradient scale,
+    clipping and logging are the same."""
 
-    def __init__(self, model, args, num_training_steps=None, temperature: float = 0.07, negatives=None):
+    def __init__(self, model, args, num_training_steps=None, temperature: float = 0.07, negatives=None, loss: str = "infonce"):
         from . import dp
         from .optim import FusedAdamW, get_scheduler
+        self.loss_fn = MultiModalTrainer(temperature, negatives, loss)      # (first: a refused `loss` touches neither model nor device)
         self.model, self.args = model, args
         self.config = cfg = TrainingConfig(args, num_training_steps)
-        self.loss_fn = MultiModalTrainer(temperature, negatives)
         dev = model.base_model.embed_tokens.weight.device
         qf, qw, uq = model.qformer_model, model.base_model, model.user_qformer
         self.qpack = None if qf is None else qf._ensure_pack(dev)
