@@ -5,7 +5,8 @@ shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
     python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 [--D 1024] [--rounds 3] [--chunks]
     python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 --scorer vector mfma --catalog-dtype bf16
     python tools/kernel_bench.py negatives --B 64 --P 1000 --N 1000000 --K 128 [--catalog-dtype f32|bf16] [--rounds 3]
-    python tools/kernel_bench.py catalog_softmax --users 64 512 --dtypes f32 bf16 --N 1000000 [--D 1024] [--rounds 5]"""
+    python tools/kernel_bench.py catalog_softmax --users 64 512 --dtypes f32 bf16 --N 1000000 [--D 1024] [--rounds 5]
+    python tools/kernel_bench.py merge --B 64 --S 2048 [--layers 28] [--rank 16] [--rounds 5] [--iters 2]"""
 import argparse
 import os
 import sys
@@ -403,9 +404,62 @@ def catalog_softmax(args):
         del cat
 
 
+def merge(args):
+    """Merged adapters (Qwen3LoRAModel.merge_adapter): the evaluation forward of the decoder (--layers of the 0.6B shape, rank --rank on all
+    seven projections, B x S tokens, no_grad, eval mode) with the adapters merged and unmerged, alternating --rounds times in this process
+    (device events around --iters forwards); merge_adapter() itself for the whole model (host clock around a synchronised call, the cache
+    dropped before each) with the bytes of bf16 operands it adds and the HBM traffic the kernel needs (W read once in f32, the bf16
+    output written once); and the two pooled outputs' relative difference."""
+    from unirec_amd.qwen3 import Qwen3Config, Qwen3LoRAModel
+    B, S, L, r = args.B, args.S, args.layers, args.rank
+    torch.manual_seed(0)
+    m = Qwen3LoRAModel(Qwen3Config(vocab_size=4096, num_hidden_layers=L, lora_r=r, lora_alpha=2.0 * r))
+    m.reset_parameters(lora_b_std=0.02)
+    m = m.to("cuda").eval()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    ids = torch.randint(0, 4096, (B, S), generator=g, device="cuda")
+    am = torch.ones(B, S, dtype=torch.long, device="cuda")
+    am[:, :S // 8] = 0
+
+    def forward():
+        with torch.no_grad():
+            return m.forward_pooled(ids, am)
+    outs, times = {}, {"unmerged": [], "merged": []}
+    merge_ms = []
+    for _ in range(3):                                   # merge_adapter() from nothing, three times (the first loads the code object)
+        m.unmerge_adapter()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m.merge_adapter()
+        torch.cuda.synchronize()
+        merge_ms.append((time.perf_counter() - t0) * 1e3)
+    added = m._merged["bytes"]
+    w_elems = sum(p.weight.numel() for _, _, _, _, p in m._adapted_projections())
+    for form in ("unmerged", "merged"):                  # warm-up of both forms: code objects, the pack, the frozen operands
+        m.merge_adapter() if form == "merged" else m.unmerge_adapter()
+        outs[form] = forward()
+        forward()
+    torch.cuda.synchronize()
+    for _ in range(args.rounds):
+        for form in ("unmerged", "merged"):
+            m.merge_adapter() if form == "merged" else m.unmerge_adapter()
+            torch.cuda.synchronize()
+            times[form].append(timeit(forward, args.iters))
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    diff = float((outs["merged"] - outs["unmerged"]).norm() / outs["unmerged"].norm())
+    print(f"merge B={B} S={S} layers={L} rank={r} all seven projections, eval forward under no_grad, {args.rounds} alternating rounds of {args.iters} forwards")
+    for form in ("unmerged", "merged"):
+        t = sorted(times[form])
+        print(f"  forward {form:9s}: median {med[form]:9.3f} ms  min {t[0]:9.3f}  max {t[-1]:9.3f}")
+    print(f"  merged / unmerged: {med['merged'] / med['unmerged']:.4f}   (pooled outputs differ by {diff:.3e} relative)")
+    t = sorted(merge_ms[1:])
+    print(f"  merge_adapter() whole model: {t[0]:.2f} .. {t[-1]:.2f} ms (first call {merge_ms[0]:.2f} ms), adds {added / 2**20:.1f} MiB of bf16 operands; "
+          f"the kernel's own traffic {w_elems * 6 / 2**20:.1f} MiB (f32 W in, bf16 out) = {w_elems * 6 / (t[0] * 1e-3) / 1e12:.3f} TB/s over the whole call")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog", "negatives", "catalog_softmax"])
+    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog", "negatives", "catalog_softmax", "merge"])
     ap.add_argument("--B", type=int, default=8)
     ap.add_argument("--S", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=5)
@@ -420,7 +474,9 @@ if __name__ == "__main__":
     ap.add_argument("--users", type=int, nargs="+", help="catalog_softmax: the user counts to time (default: --B)")
     ap.add_argument("--dtypes", nargs="+", choices=["f32", "bf16"], help="catalog_softmax: the catalogue dtypes to time (default: --catalog-dtype)")
     ap.add_argument("--P", type=int, default=1000, help="negatives: candidate columns per user")
+    ap.add_argument("--layers", type=int, default=28, help="merge: decoder layers")
+    ap.add_argument("--rank", type=int, default=16, help="merge: LoRA rank")
     ap.add_argument("--lib", action="store_true", help="gemm: also time torch.matmul on the same operands (reference point)")
     a = ap.parse_args()
     {"attn": attn, "gemm": gemm, "lora": lora, "rope": rope, "dw": dw, "xattn": xattn, "gemm_lora": gemm_lora, "gemm_merge": gemm_merge, "gemm_step": gemm_step, "rmslora": rmslora, "swilora": swilora,
-     "catalog": catalog, "negatives": negatives, "catalog_softmax": catalog_softmax}[a.what](a)
+     "catalog": catalog, "negatives": negatives, "catalog_softmax": catalog_softmax, "merge": merge}[a.what](a)

@@ -1,4 +1,5 @@
-"""ctypes binding of libunirec_hip.so (the C ABI declared in include/unirec_hip.h and include/unirec_hip_loss.h).
+"""ctypes binding of libunirec_hip.so (the C ABI declared in include/unirec_hip.h, include/unirec_hip_loss.h and
+include/unirec_hip_adapter.h).
 
 Fails loudly: there is no CPU / eager fallback for the product path.
 """
@@ -8,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -105,6 +106,14 @@ class CatalogSoftmax(ctypes.Structure):
                 ("B", c_int), ("N", c_i64), ("D", c_int),
                 ("chunk_rows", c_i64), ("scorer", c_int),
                 ("workspace", c_void_p), ("workspace_bytes", c_i64)]
+
+
+class LoraMerge(ctypes.Structure):
+    """Mirror of ur_lora_merge_t (include/unirec_hip_adapter.h)."""
+    _fields_ = [("W", c_void_p), ("ldw", c_i64), ("A", c_void_p), ("B", c_void_p),
+                ("rank", c_int), ("scale", c_float),
+                ("out_f32", c_void_p), ("ld_f32", c_i64), ("out_bf16", c_void_p), ("ld_bf16", c_i64),
+                ("out_rows", c_int), ("in_cols", c_int)]
 
 
 class F32Range(ctypes.Structure):
@@ -222,6 +231,12 @@ LOSS_SIGNATURES = {
     "ur_catalog_softmax": (c_int, [ctypes.POINTER(CatalogSoftmax), c_void_p]),
 }
 
+# the adapter family: every symbol include/unirec_hip_adapter.h declares (tests/test_lora_merge_host.py holds this table to that header
+# and to the built library in the same way)
+ADAPTER_SIGNATURES = {
+    "ur_lora_merge": (c_int, [ctypes.POINTER(LoraMerge), c_void_p]),
+}
+
 _lib = None
 
 
@@ -243,7 +258,7 @@ def load():
     # two runtimes and the library's launches fail with "no ROCm-capable device is detected".
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(ADAPTER_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -798,6 +798,37 @@ def cast_bf16_to_f32(src, dst=None):
     return dst
 
 
+def lora_merge(W, A, B, scale, out_f32=None, out_bf16=None):
+    """out = W + scale * B A from the f32 masters in one pass over W (ur_lora_merge, include/unirec_hip_adapter.h): W f32 [out, in]
+    (rows may be strided), A f32 [r, in], B f32 [out, r], r one of LORA_RANKS.  out_f32 / out_bf16: [out, in] tensors to write (rows may be
+    strided); out_f32 may be W itself (the merge in place).  With neither given a new f32 tensor is made.  Returns (out_f32, out_bf16)."""
+    if W.dim() != 2 or A.dim() != 2 or B.dim() != 2 or A.shape[1] != W.shape[1] or B.shape != (W.shape[0], A.shape[0]):
+        raise ValueError(f"lora_merge: W [out,in], A [r,in], B [out,r] expected, got {tuple(W.shape)}, {tuple(A.shape)}, {tuple(B.shape)}")
+    _lora_rank(A.shape[0], "lora_merge")
+    _need(A, F32, "A")
+    _need(B, F32, "B")
+    lib = _lib.load()
+    if out_f32 is None and out_bf16 is None:
+        out_f32 = torch.empty(W.shape, dtype=F32, device=W.device)
+    a = _lib.LoraMerge()
+    for t, dtype, name in ((W, F32, "W"), (out_f32, F32, "out_f32"), (out_bf16, BF16, "out_bf16")):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise _lib.UniRecHipError(f"lora_merge: {name} must be a device tensor (the UniRec HIP path has no CPU fallback)")
+        if t.dtype != dtype or t.shape != W.shape or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError(f"lora_merge: {name} must be {dtype} {tuple(W.shape)} with unit column stride")
+    a.W, a.ldw, a.A, a.B = W.data_ptr(), W.stride(0), A.data_ptr(), B.data_ptr()
+    a.rank, a.scale = A.shape[0], float(scale)
+    a.out_rows, a.in_cols = W.shape
+    if out_f32 is not None:
+        a.out_f32, a.ld_f32 = out_f32.data_ptr(), out_f32.stride(0)
+    if out_bf16 is not None:
+        a.out_bf16, a.ld_bf16 = out_bf16.data_ptr(), out_bf16.stride(0)
+    check(lib.ur_lora_merge(ctypes.byref(a), _stream()), "ur_lora_merge")
+    return out_f32, out_bf16
+
+
 class BatchedTranspose:
     """Many small bf16 transposes as ONE launch (ur_transpose_bf16_batched).  Built once over persistent source tensors
     (views of a parameter pack's bf16 shadow); run() refreshes every destination; out[i] is the transposed view."""

@@ -82,6 +82,12 @@ def apply_lora_config(cfg, lora_config):
     return cfg
 
 
+def _copy_config(cfg):
+    new = Qwen3Config()
+    new.__dict__.update(cfg.__dict__)
+    return new
+
+
 def adapter_config_dict(cfg, base_model_name_or_path=None):
     """``adapter_config.json`` in peft's format for the adapters a Qwen3Config describes (what ``PeftModel.save_pretrained`` writes
     next to ``adapter_model.bin``; ``peft.LoraConfig.from_pretrained`` reads it back)."""
@@ -91,6 +97,37 @@ def adapter_config_dict(cfg, base_model_name_or_path=None):
             "target_modules": list(normalize_lora_targets(cfg.lora_target_modules)),
             "layers_to_transform": None if layers is None else list(normalize_lora_layers(layers, cfg.num_hidden_layers)),
             "use_rslora": bool(cfg.use_rslora), "bias": "none", "inference_mode": True}
+
+
+def hf_qwen3_config_dict(cfg, dtype=torch.float32):
+    """``config.json`` of a ``transformers`` Qwen3Model for the decoder a Qwen3Config describes (no adapter fields: they are folded into
+    the weights of a merged export).  rope_theta is given in both spellings: ``rope_parameters`` (transformers 5) and the flat key."""
+    return {"architectures": ["Qwen3Model"], "model_type": "qwen3",
+            "vocab_size": int(cfg.vocab_size), "hidden_size": int(cfg.hidden_size), "intermediate_size": int(cfg.intermediate_size),
+            "num_hidden_layers": int(cfg.num_hidden_layers), "num_attention_heads": int(cfg.num_attention_heads),
+            "num_key_value_heads": int(cfg.num_key_value_heads), "head_dim": int(cfg.head_dim), "hidden_act": "silu",
+            "rms_norm_eps": float(cfg.rms_norm_eps), "rope_theta": float(cfg.rope_theta),
+            "rope_parameters": {"rope_type": "default", "rope_theta": float(cfg.rope_theta)},
+            "max_position_embeddings": int(getattr(cfg, "max_position_embeddings", 32768)),
+            "attention_bias": False, "attention_dropout": 0.0, "tie_word_embeddings": True, "use_sliding_window": False,
+            "initializer_range": float(cfg.initializer_range), "use_cache": True, "dtype": str(dtype).replace("torch.", "")}
+
+
+_HF_TO_CFG = ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "num_key_value_heads",
+              "head_dim", "rms_norm_eps", "initializer_range")
+
+
+def write_hf_checkpoint(save_directory, cfg, state_dict, dtype=torch.float32):
+    """``model.safetensors`` (HF key names, tensors as given) and ``config.json``: what
+    ``transformers.Qwen3Model.from_pretrained(save_directory, local_files_only=True)`` loads."""
+    from safetensors.torch import save_file
+    lora = [k for k in state_dict if ".lora_" in k]
+    if lora:
+        raise ValueError(f"write_hf_checkpoint: {lora[0]} is an adapter tensor; a merged export holds the HF Qwen3Model keys only")
+    save_file({k: v.detach().to("cpu", dtype).contiguous() for k, v in state_dict.items()}, os.path.join(save_directory, "model.safetensors"),
+              metadata={"format": "pt"})
+    with open(os.path.join(save_directory, "config.json"), "w") as f:
+        json.dump(hf_qwen3_config_dict(cfg, dtype), f, indent=2)
 
 
 class MultiModalQwenEmbedding(nn.Module):
@@ -140,6 +177,7 @@ class MultiModalQwenEmbedding(nn.Module):
 
     def forward(self, input_ids, attention_mask=None, history_field_embeddings=None, history_attention_mask=None,
                 user_sequence_tokens=None, user_attention_mask=None):
+        self.base_model.refuse_training_while_merged()      # (before the Q-Formers launch anything)
         dev = self.base_model.embed_tokens.weight.device
         input_ids = input_ids.to(dev)
         if attention_mask is not None:
@@ -172,10 +210,31 @@ class MultiModalQwenEmbedding(nn.Module):
         :99-119 -- same result).  Returns (missing, unexpected) like ``load_state_dict``."""
         return self.base_model.load_base_weights(state_dict, strict=strict)
 
-    def save_pretrained(self, save_directory):
+    # ---- peft's calls for a finished run (Qwen3LoRAModel has the arithmetic) ------------------------------------------------------
+    def merge_adapter(self):
+        self.base_model.merge_adapter()
+
+    def unmerge_adapter(self):
+        self.base_model.unmerge_adapter()
+
+    def disable_adapter(self):
+        return self.base_model.disable_adapter()
+
+    def merge_and_unload(self):
+        self.base_model.merge_and_unload()
+        self.use_lora = False
+        return self
+
+    def save_pretrained(self, save_directory, merged=False, dtype=torch.float32):
+        """merged=False: the adapters (``adapter_model.bin`` + ``adapter_config.json``; without LoRA ``base_model.bin``), the Q-Former, the
+        tokenizer files and ``model_config.json``.  merged=True: in place of the adapter files a decoder ordinary ``transformers`` code
+        loads -- ``model.safetensors`` (HF key names, W + s B A in `dtype`, ``embed_tokens`` with its added special-token rows) and
+        ``config.json``; the live model is not modified.  from_pretrained() reads either form back."""
         os.makedirs(save_directory, exist_ok=True)
         self.tokenizer.save_pretrained(save_directory)
-        if self.use_lora:
+        if merged:
+            write_hf_checkpoint(save_directory, self.base_model.config, self.base_model.merged_state_dict(dtype), dtype)
+        elif self.use_lora:
             torch.save(self.base_model.peft_state_dict(), os.path.join(save_directory, "adapter_model.bin"))
             with open(os.path.join(save_directory, "adapter_config.json"), "w") as f:      # peft's own companion of adapter_model.bin
                 json.dump(adapter_config_dict(self.base_model.config, self.base_model_name), f, indent=2)
@@ -185,6 +244,84 @@ class MultiModalQwenEmbedding(nn.Module):
         with open(os.path.join(save_directory, "model_config.json"), "w") as f:
             json.dump({"hidden_size": self.hidden_size, "use_lora": self.use_lora}, f, indent=2)
         print(f"Model saved to {save_directory}")
+
+    def load_adapter(self, path_or_state_dict):
+        """Adapter tensors written by save_pretrained (a directory, the path of an ``adapter_model.bin``, or its state dict with peft's
+        ``base_model.model.`` prefix) into this model's adapters.  A directory's ``adapter_config.json`` must describe this model's
+        adapters (rank, scale and placement; the fields this package refuses raise through apply_lora_config); a key that does not fit
+        the placement, a wrong shape or a missing tensor raises, naming the key."""
+        sd = path_or_state_dict
+        if not isinstance(sd, dict):
+            path = os.fspath(sd)
+            if os.path.isdir(path):
+                with open(os.path.join(path, "adapter_config.json")) as f:
+                    want, have = adapter_config_dict(apply_lora_config(_copy_config(self.base_model.config), json.load(f))), adapter_config_dict(self.base_model.config)
+                for k in ("r", "lora_alpha", "target_modules", "layers_to_transform", "use_rslora"):
+                    if want[k] != have[k]:
+                        raise ValueError(f"load_adapter: adapter_config.json has {k} = {want[k]!r}, this model was built with {have[k]!r}")
+                path = os.path.join(path, "adapter_model.bin")
+            sd = torch.load(path, map_location="cpu")
+        if not self.base_model.use_lora:
+            raise ValueError("load_adapter: this model has no adapters (use_lora=False, or merge_and_unload() removed them)")
+        own = dict(self.base_model.lora_named_parameters())
+        pre = "base_model.model."
+        with torch.no_grad():
+            for k, v in sd.items():
+                n = k[len(pre):] if k.startswith(pre) else k
+                if n not in own:
+                    raise KeyError(f"load_adapter: {k} does not fit the adapter placement of this model (no such adapter tensor)")
+                if tuple(v.shape) != tuple(own[n].shape):
+                    raise ValueError(f"load_adapter: {k} has shape {tuple(v.shape)}, the model's is {tuple(own[n].shape)}")
+            missing = [n for n in own if n not in sd and pre + n not in sd]
+            if missing:
+                raise KeyError(f"load_adapter: {pre + missing[0]} is missing ({len(missing)} adapter tensors are)")
+            for k, v in sd.items():
+                p = own[k[len(pre):] if k.startswith(pre) else k]
+                p.copy_(v.to(p.device, p.dtype))
+        if self.base_model.pack is not None:
+            self.base_model.pack.mark_dirty()
+        return self
+
+    @classmethod
+    def from_pretrained(cls, save_directory, qformer_model=None, base_state_dict=None, qwen_config=None, **kwargs):
+        """The model save_pretrained wrote to save_directory, in either form.  The adapters' rank, scale and placement come from
+        ``adapter_config.json`` (through apply_lora_config: a field this package refuses raises by name), their values from
+        ``adapter_model.bin``, the Q-Former's from ``qformer_model.bin``.  The frozen base weights are not part of an adapter directory:
+        pass the checkpoint as base_state_dict (or call load_base_weights afterwards) and the decoder's shape as qwen_config.  A merged
+        directory holds both (``model.safetensors``, ``config.json``) and gives a model without adapters.  kwargs go to the constructor."""
+        with open(os.path.join(save_directory, "model_config.json")) as f:
+            use_lora = bool(json.load(f).get("use_lora", True))
+        merged_file = os.path.join(save_directory, "model.safetensors")
+        lora_config = None
+        if os.path.exists(merged_file):
+            use_lora = False
+            with open(os.path.join(save_directory, "config.json")) as f:
+                hf = json.load(f)
+            qwen_config = qwen_config or Qwen3Config()
+            for k in _HF_TO_CFG:
+                setattr(qwen_config, k, hf[k])
+            qwen_config.rope_theta = (hf.get("rope_parameters") or {}).get("rope_theta", hf.get("rope_theta", qwen_config.rope_theta))
+            from safetensors.torch import load_file
+            base_state_dict = load_file(merged_file)
+            tokens_file = os.path.join(save_directory, "history_tokens.json")
+            if kwargs.get("tokenizer") is None and os.path.exists(tokens_file):
+                # config.json's vocabulary already counts the added special-token rows: the stand-in tokenizer starts where they start
+                with open(tokens_file) as f:
+                    first = min(json.load(f).values())
+                kwargs["tokenizer"] = HistoryTokenTable(first, kwargs.get("num_history_items", 10), kwargs.get("num_query_tokens_per_item", 2))
+        elif use_lora:
+            with open(os.path.join(save_directory, "adapter_config.json")) as f:
+                lora_config = json.load(f)
+        elif base_state_dict is None:
+            base_state_dict = torch.load(os.path.join(save_directory, "base_model.bin"), map_location="cpu")
+        model = cls(qformer_model=qformer_model, use_lora=use_lora, lora_config=lora_config, qwen_config=qwen_config, **kwargs)
+        if base_state_dict is not None:
+            model.load_base_weights(base_state_dict)
+        if use_lora:
+            model.load_adapter(os.path.join(save_directory, "adapter_model.bin"))
+        if qformer_model is not None:
+            qformer_model.load_state_dict(torch.load(os.path.join(save_directory, "qformer_model.bin"), map_location="cpu"))
+        return model
 
     def get_trainable_parameters(self):
         trainable_params = sum(p.numel() for p in self.parameters() if p.requires_grad)

@@ -51,6 +51,7 @@ class ParamPack:
             p.data = v
         self._shadow_key = None
         self.dirty = True
+        self.generation = 0        # bumped by every mark_dirty(): state of the masters that torch's version counters do not see
         self.live = set()          # names whose gradient entry a backward has written since the last clear_grads()
 
     def _view(self, flat, name, shape=None):
@@ -122,6 +123,7 @@ class ParamPack:
 
     def mark_dirty(self):
         self.dirty = True
+        self.generation += 1
 
     def refresh_shadow(self, force=False):
         """fp32 master -> bf16 shadow when any parameter changed (torch's in-place version counters

@@ -18,6 +18,7 @@ dX GEMMs on the frozen bf16 weights plus rank-r reductions for dA/dB; every LoRA
 the base GEMM's accumulators (second K-range of ur_gemm).  Activations are kept in HBM (288 GB:
 no gradient checkpointing); only the RMSNorm outputs are recomputed in the backward.
 """
+import contextlib
 import math
 from collections import namedtuple
 from dataclasses import dataclass
@@ -237,6 +238,8 @@ class Qwen3LoRAModel(nn.Module):
         self.norm = _Norm(config.hidden_size)
         self._pack = None
         self._frozen = None
+        self._merged = None            # merge_adapter(): {"key", "fz", "bytes"} -- bf16 operands built from W + s B A
+        self._adapters_off = False     # inside disable_adapter()
         self._rope = None
         self.grad_ready_hook = None
         self.lora_seed = 0x5EED        # base seed of the LoRA dropout masks (per run; identical on every data-parallel rank)
@@ -251,6 +254,12 @@ class Qwen3LoRAModel(nn.Module):
         self._bits_pre = None
         self.recompute_mlp = switches.recompute_mlp   # drop gate|up and act after the forward, rebuild them in the backward
         self.keep_norm_outputs = True   # keep the two RMSNorm outputs per layer for the backward (memory for time); False recomputes them
+        self._index_adapters()
+        self.reset_parameters()
+
+    def _index_adapters(self):
+        """The tables derived from adapter_modules (built once, and again when merge_and_unload() removes the adapters)."""
+        config = self.config
         # [layer][adapter group] -> parameter names, built once: the hot loops format no strings
         # (the PRESENT adapters of the group: the tuples may be empty)
         self._names = [[_GroupNames(a=tuple(f"layers.{i}.{p}.lora_A.weight" for p in projs if p in mods),
@@ -260,7 +269,6 @@ class Qwen3LoRAModel(nn.Module):
         # the adapter counts that occur in a q|k|v / gate|up group over the layers (a layer outside layers_to_transform counts 0): the second K
         # ranges the merged launches are asked about (_plan)
         self._nad_qkv, self._nad_gu = (sorted({len(nm[g].a) for nm in self._names}) for g in (0, 2))
-        self.reset_parameters()
 
     def reset_parameters(self, lora_b_std=0.0):
         """Base N(0, initializer_range) (weights are random: no network for the checkpoint); LoRA A
@@ -422,10 +430,140 @@ class Qwen3LoRAModel(nn.Module):
                 out["base_model.model." + n] = p.detach().cpu()
         return out
 
+    # ---- merged adapters (peft's merge_adapter / unmerge_adapter / merge_and_unload / disable_adapter) ---------------------------
+    @property
+    def merged(self):
+        return self._merged is not None
+
+    def _lora_live(self):
+        """adapters exist and the forward runs their streams: not merged, not inside disable_adapter()"""
+        return self.use_lora and self._merged is None and not self._adapters_off
+
+    def _adapted_projections(self):
+        """(layer index, adapter group, first row and row count inside the group's fused operand, the _Proj) of every projection that
+        carries an adapter"""
+        for i, lyr in enumerate(self.layers):
+            for g, (_, projs) in enumerate(ADAPTER_GROUPS):
+                for (col, n, j, _), pname in zip(self._place[i][g].split, projs):
+                    if j is not None:
+                        yield i, g, col, n, lyr.get_submodule(pname)
+
+    def refuse_training_while_merged(self):
+        """A training forward on merged operands would train nothing (the adapter streams do not run) and silently drop LoRA dropout:
+        refused, before any launch."""
+        if self._merged is not None and self.training and torch.is_grad_enabled():
+            raise RuntimeError("Qwen3LoRAModel: the adapters are merged into the frozen operands (merge_adapter()); a training forward "
+                               "needs the adapter streams: call unmerge_adapter() first")
+
+    def _ensure_merged(self, device):
+        """The frozen operands with W + s B A in place of W for every projection that carries an adapter: every layout _ensure_frozen
+        keeps (qkv, qkvP, gu, guP, o, d and the four transposes) is rebuilt from the merged bf16 values (ur_lora_merge from the f32 masters,
+        one rounding to bf16); groups and layers without an adapter share the unmerged tensors.  Cached under a key that holds the base
+        weights' state and the adapters' (storage, in-place version, the pack's generation: the fused optimizer writes the masters raw)."""
+        base = self._ensure_frozen(device)
+        s = self._lora_scale()
+        key = (base["key"], s, tuple((n, p.data_ptr(), p._version) for n, p in self.lora_named_parameters()),
+               None if self._pack is None else (id(self._pack), self._pack.generation))
+        if self._merged is not None and self._merged["key"] == key:
+            return self._merged["fz"]
+        dev = torch.device(device)
+        layers = [dict(fl) if self.adapter_modules[i] else fl for i, fl in enumerate(base["layers"])]
+        fresh = {}      # (layer, group) -> the group's merged operand: a copy of the unmerged one, the adapted rows overwritten
+
+        def f32(t):
+            return t.detach().to(dev, F32).contiguous()
+        for i, g, col, n, proj in self._adapted_projections():
+            name = ADAPTER_GROUPS[g][0]
+            if (i, g) not in fresh:
+                fresh[(i, g)] = base["layers"][i][name].clone()
+            hip.lora_merge(f32(proj.weight), f32(proj.lora_A.weight), f32(proj.lora_B.weight), s, out_bf16=fresh[(i, g)][col:col + n])
+        nbytes = 0
+        for (i, g), w16 in fresh.items():
+            name, fl = ADAPTER_GROUPS[g][0], layers[i]
+            fl[name], fl[name + "T"] = w16, w16.t().contiguous()
+            if name == "qkv" and fl["qkvP"] is not None:
+                fl["qkvP"] = w16[self._qk_row_perm(dev)]
+            if name == "gu" and fl["guP"] is not None:
+                fl["guP"] = w16[self._swiglu_rows(self.config.intermediate_size, dev)]
+            nbytes += sum(fl[k].numel() * 2 for k in (name, name + "T", name + "P") if fl.get(k) is not None)
+        fz = dict(base, layers=layers)
+        self._merged = {"key": key, "fz": fz, "bytes": nbytes}
+        return fz
+
+    def merge_adapter(self, device=None):
+        """peft's merge_adapter(): from now on every forward runs the adapter-free path on bf16 operands made of W + s B A (s =
+        _lora_scale(): rsLoRA is honoured) -- no RMSNorm + adapter kernels, no lora_project, no second K range, no dropout planes.  The f32
+        masters and the LoRA parameters are not touched.  Evaluation only: a training forward is refused until unmerge_adapter().
+        device: where the operands are built (default: where the weights are)."""
+        if not self.use_lora:
+            return
+        dev = norm_device(self.embed_tokens.weight.device if device is None else device)      # (indexed: the key a forward's inputs give)
+        if dev.type != "cuda":
+            raise hip._lib.UniRecHipError("merge_adapter: the merge runs on the MI355X only (no CPU fallback): move the model to the device first")
+        self._release_prefetched(dev)
+        self._ensure_merged(dev)
+
+    def unmerge_adapter(self):
+        """Drop the merged operands.  The next forward runs on the unmerged operands, which are (re)built from the untouched f32
+        masters: exact, where peft subtracts s B A back out of the merged weight."""
+        self._merged = None
+
+    @contextlib.contextmanager
+    def disable_adapter(self):
+        """peft's disable_adapter(): inside the context the base model runs without adapters (the adapter-free path on the unmerged
+        operands), merged or not; nothing is changed."""
+        prev, self._adapters_off = self._adapters_off, True
+        try:
+            yield self
+        finally:
+            self._adapters_off = prev
+
+    def _operands(self, device):
+        """(frozen operands, parameter pack) of a forward: merged operands or disabled adapters run without the pack, which is what a
+        model built with use_lora=False runs."""
+        if self._adapters_off:
+            return self._ensure_frozen(device), None
+        if self._merged is not None:
+            return self._ensure_merged(device), None      # (re-keyed: a weight or adapter loaded while merged rebuilds them)
+        return self._ensure_frozen(device), self._ensure_pack(device)
+
+    def merged_state_dict(self, dtype=F32):
+        """The HF ``Qwen3Model`` state dict with the adapters folded in (W + s B A by ur_lora_merge into temporaries: the model is not
+        modified), on the CPU in `dtype`.  After merge_and_unload() this is state_dict() itself."""
+        adapted = {id(proj.weight): proj for _, _, _, _, proj in self._adapted_projections()}
+        s, out = self._lora_scale(), {}
+        for n, p in self.named_parameters():
+            if ".lora_" in n:
+                continue
+            proj = adapted.get(id(p))
+            w = p.detach() if proj is None else hip.lora_merge(p.detach().contiguous(), proj.lora_A.weight.detach().contiguous(),
+                                                                proj.lora_B.weight.detach().contiguous(), s)[0]
+            out[n] = w.to("cpu", dtype).contiguous()
+        return out
+
+    def merge_and_unload(self):
+        """peft's merge_and_unload(): W <- W + s B A in place on the f32 masters of every projection that carries an adapter, then the
+        adapters are removed: use_lora is False, state_dict() holds exactly the HF Qwen3Model keys.  Returns self."""
+        if not self.use_lora:
+            return self
+        self._release_prefetched(self.embed_tokens.weight.device)
+        s = self._lora_scale()      # (hip.lora_merge refuses host tensors: there is no CPU fallback of the merge)
+        for _, _, _, _, proj in list(self._adapted_projections()):
+            w = proj.weight.data
+            hip.lora_merge(w, proj.lora_A.weight.detach().contiguous(), proj.lora_B.weight.detach().contiguous(), s, out_f32=w)
+            del proj.lora_A, proj.lora_B
+        self.use_lora = False
+        self.adapter_modules = tuple(() for _ in self.layers)
+        self._index_adapters()
+        # (the kernel wrote the masters raw: no version counter moved, so the bf16 operands are dropped by hand)
+        self._frozen = self._merged = self._pack = self._bcomb = self._lt = None
+        return self
+
     # ---- public forward ---------------------------------------------------------------------------
     def forward_pooled(self, input_ids, attention_mask=None, item_tokens16=None, first_special_id=0):
         """input_ids int64 [B,S]; attention_mask [B,S] or None; item_tokens16 [B,T,D] bf16 (Q-Former
         query tokens to inject at ids first_special_id + t) or None -> mean-pooled f32 [B,D]."""
+        self.refuse_training_while_merged()
         if not input_ids.is_cuda:
             raise hip._lib.UniRecHipError("Qwen3LoRAModel runs on the MI355X only (no CPU fallback in the product path)")
         B, S = input_ids.shape
@@ -438,13 +576,13 @@ class Qwen3LoRAModel(nn.Module):
             # inference (MRREvaluator, CatalogEvaluator, token caches): nothing is kept for a backward, so the peak is one
             # layer's activations instead of all of them (178 GB at B=64, S=2048 in training)
             return self._forward_impl(item_tokens16.detach(), input_ids.contiguous(), mask_u8, int(first_special_id), keep=False)[0]
-        anchor = torch.zeros(1, device=input_ids.device, requires_grad=True) if self.use_lora else None
+        anchor = torch.zeros(1, device=input_ids.device, requires_grad=True) if self._lora_live() else None
         return _JointFn.apply(self, item_tokens16, input_ids.contiguous(), mask_u8, int(first_special_id), anchor)
 
     # ---- implementation ---------------------------------------------------------------------------
     def _drop_p(self):
         """peft applies lora_dropout only in training mode (nn.Dropout inside every LoraLayer)."""
-        return float(self.config.lora_dropout) if (self.training and self.use_lora) else 0.0
+        return float(self.config.lora_dropout) if (self.training and self._lora_live()) else 0.0
 
     def lora_dropout_seed(self, step, layer, group):
         """Seed of the dropout masks of one adapter group (the adapters that share an input: 0 = q|k|v, 1 = o,
@@ -672,8 +810,7 @@ class Qwen3LoRAModel(nn.Module):
     def _forward_impl(self, item_tokens16, input_ids, mask_u8, first_special_id, keep=True):
         c = self.config
         dev = input_ids.device
-        fz = self._ensure_frozen(dev)
-        pack = self._ensure_pack(dev)
+        fz, pack = self._operands(dev)
         B, S = input_ids.shape
         D, I, nq, nkv, hd, r = c.hidden_size, c.intermediate_size, c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.lora_r
         NQ, NKV = nq * hd, nkv * hd
@@ -698,7 +835,7 @@ class Qwen3LoRAModel(nn.Module):
         if pdrop > 0.0:
             self._lora_step += 1
         saved = {"B": B, "S": S, "T": T, "ids": input_ids, "first": first_special_id, "mask": mask_u8, "layers": [],
-                 "pdrop": pdrop, "step": step, "plan": plan}
+                 "pdrop": pdrop, "step": step, "plan": plan, "fz": fz, "pack": pack}
         row0 = self.first_sample(B) * S                # token rows that precede this shard in the global minibatch
         pre, self._bits_pre = self._bits_pre, None
         if pre is not None and not (pdrop > 0.0 and pre["step"] == step and pre["M"] == M and pre["row0"] == row0 and pack is not None):
@@ -809,8 +946,7 @@ class Qwen3LoRAModel(nn.Module):
 
     def _backward_impl(self, saved, d_pooled):
         c = self.config
-        fz = self._frozen
-        pack = self._pack if self.use_lora else None
+        fz, pack = saved["fz"], saved["pack"]      # what the forward ran on (merged or adapter-free operands: pack is None)
         plan = saved["plan"]
         B, S, T = saved["B"], saved["S"], saved["T"]
         D, I, nq, nkv, hd, r = c.hidden_size, c.intermediate_size, c.num_attention_heads, c.num_key_value_heads, c.head_dim, c.lora_r
