@@ -27,9 +27,10 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 21      /* 18: ur_gemm_plan; 19: ur_rmsnorm_lora_fwd takes 1 to 3 adapters; 20: the loss family of
+#define UR_ABI_VERSION 22      /* 18: ur_gemm_plan; 19: ur_rmsnorm_lora_fwd takes 1 to 3 adapters; 20: the loss family of
                                   unirec_hip_loss.h (the full-catalogue softmax loss; nothing in this header changed); 21: the adapter
-                                  family of unirec_hip_adapter.h (ur_lora_merge; nothing in this header changed) */
+                                  family of unirec_hip_adapter.h (ur_lora_merge; nothing in this header changed); 22: the pooling family of
+                                  unirec_hip_pool.h (ur_pool_norm_*; nothing in this header changed) */
 
 int ur_version(void);
 const char* ur_last_error(void);

@@ -6,7 +6,8 @@ shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
     python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 --scorer vector mfma --catalog-dtype bf16
     python tools/kernel_bench.py negatives --B 64 --P 1000 --N 1000000 --K 128 [--catalog-dtype f32|bf16] [--rounds 3]
     python tools/kernel_bench.py catalog_softmax --users 64 512 --dtypes f32 bf16 --N 1000000 [--D 1024] [--rounds 5]
-    python tools/kernel_bench.py merge --B 64 --S 2048 [--layers 28] [--rank 16] [--rounds 5] [--iters 2]"""
+    python tools/kernel_bench.py merge --B 64 --S 2048 [--layers 28] [--rank 16] [--rounds 5] [--iters 2]
+    python tools/kernel_bench.py pool --B 64 --S 2048 [--D 1024] [--rounds 5] [--iters 20]"""
 import argparse
 import os
 import sys
@@ -457,9 +458,56 @@ def merge(args):
           f"the kernel's own traffic {w_elems * 6 / 2**20:.1f} MiB (f32 W in, bf16 out) = {w_elems * 6 / (t[0] * 1e-3) / 1e12:.3f} TB/s over the whole call")
 
 
+def pool(args):
+    """Pooling rules at the decoder's output (B x S rows of --D bf16, left padding with 10 % masked, as the benchmark pads): the pair the
+    default rule launches -- rmsnorm_fwd + mean_pool_fwd, mean_pool_bwd + rmsnorm_bwd -- against pool_norm_fwd / pool_norm_bwd under
+    both mask-aware rules, alternating --rounds times in this process (device events around --iters calls; medians).  Each time is
+    also given as a share of the 6.3 TB/s read ceiling for the bytes that path MUST move: the pair reads x, writes and re-reads the
+    normalised rows (forward) or writes and re-reads the broadcast gradient (backward); masked_mean reads only the valid rows; last
+    reads B rows; every backward writes all of dx."""
+    B, S, D = args.B, args.S, args.D
+    eps, peak = 1e-6, 6.3e12
+    g = torch.Generator(device="cuda").manual_seed(0)
+    x = torch.randn(B, S, D, generator=g, device="cuda").to(torch.bfloat16)
+    w = 1.0 + 0.1 * torch.randn(D, generator=g, device="cuda")
+    dp = torch.randn(B, D, generator=g, device="cuda")
+    mask = torch.ones(B, S, dtype=torch.uint8, device="cuda")
+    mask[:, :S // 10] = 0
+    valid = int(mask.sum())
+    row = D * 2
+    rstd = hip.rmsnorm_fwd(x.view(B * S, D), w, eps)[1]
+    paths = {
+        "fwd mean (rmsnorm_fwd + mean_pool_fwd)": (lambda: hip.mean_pool_fwd(hip.rmsnorm_fwd(x.view(B * S, D), w, eps)[0].view(B, S, D)), 3 * B * S * row),
+        "fwd masked_mean (pool_norm_fwd)": (lambda: hip.pool_norm_fwd(x, w, eps, mask, "masked_mean"), valid * row),
+        "fwd last (pool_norm_fwd)": (lambda: hip.pool_norm_fwd(x, w, eps, mask, "last"), B * row),
+        "bwd mean (mean_pool_bwd + rmsnorm_bwd)": (lambda: hip.rmsnorm_bwd(hip.mean_pool_bwd(dp, S).view(B * S, D), x.view(B * S, D), w, rstd), 4 * B * S * row),
+        "bwd masked_mean (pool_norm_bwd)": (lambda: hip.pool_norm_bwd(dp, x, w, eps, mask, "masked_mean"), (valid + B * S) * row),
+        "bwd last (pool_norm_bwd)": (lambda: hip.pool_norm_bwd(dp, x, w, eps, mask, "last"), (B + B * S) * row),
+    }
+    times = {k: [] for k in paths}
+    for fn, _ in paths.values():
+        fn(); fn()
+    torch.cuda.synchronize()
+    for _ in range(args.rounds):
+        for k, (fn, _) in paths.items():
+            times[k].append(timeit(fn, args.iters))
+    print(f"pool B={B} S={S} D={D} left padding, {B * S - valid} of {B * S} rows masked; {args.rounds} alternating rounds of {args.iters} calls, device events")
+    med = {}
+    for k, (_, nbytes) in paths.items():
+        t = sorted(times[k])
+        med[k] = t[len(t) // 2]
+        print(f"  {k:42s}: median {med[k] * 1e3:9.1f} us  min {t[0] * 1e3:9.1f}  max {t[-1] * 1e3:9.1f}   {nbytes / 2**20:8.1f} MiB must move = "
+              f"{nbytes / (med[k] * 1e-3) / 1e12:6.3f} TB/s = {100 * nbytes / (med[k] * 1e-3) / peak:5.1f} % of 6.3 TB/s")
+    for d in ("fwd", "bwd"):
+        base = next(v for k, v in med.items() if k.startswith(d + " mean"))
+        for k, v in med.items():
+            if k.startswith(d) and not k.startswith(d + " mean"):
+                print(f"  {k} / the pair it replaces: {v / base:.3f}")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog", "negatives", "catalog_softmax", "merge"])
+    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog", "negatives", "catalog_softmax", "merge", "pool"])
     ap.add_argument("--B", type=int, default=8)
     ap.add_argument("--S", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=5)
@@ -479,4 +527,4 @@ if __name__ == "__main__":
     ap.add_argument("--lib", action="store_true", help="gemm: also time torch.matmul on the same operands (reference point)")
     a = ap.parse_args()
     {"attn": attn, "gemm": gemm, "lora": lora, "rope": rope, "dw": dw, "xattn": xattn, "gemm_lora": gemm_lora, "gemm_merge": gemm_merge, "gemm_step": gemm_step, "rmslora": rmslora, "swilora": swilora,
-     "catalog": catalog, "negatives": negatives, "catalog_softmax": catalog_softmax, "merge": merge}[a.what](a)
+     "catalog": catalog, "negatives": negatives, "catalog_softmax": catalog_softmax, "merge": merge, "pool": pool}[a.what](a)

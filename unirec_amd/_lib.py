@@ -1,5 +1,5 @@
-"""ctypes binding of libunirec_hip.so (the C ABI declared in include/unirec_hip.h, include/unirec_hip_loss.h and
-include/unirec_hip_adapter.h).
+"""ctypes binding of libunirec_hip.so (the C ABI declared in include/unirec_hip.h, include/unirec_hip_loss.h,
+include/unirec_hip_adapter.h and include/unirec_hip_pool.h).
 
 Fails loudly: there is no CPU / eager fallback for the product path.
 """
@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -237,6 +237,17 @@ ADAPTER_SIGNATURES = {
     "ur_lora_merge": (c_int, [ctypes.POINTER(LoraMerge), c_void_p]),
 }
 
+# the pooling family: every symbol include/unirec_hip_pool.h declares (tests/test_pool_host.py holds this table to that header and to
+# the built library in the same way)
+POOL_MASKED_MEAN, POOL_LAST = 1, 2      # UR_POOL_MASKED_MEAN, UR_POOL_LAST
+POOL_NORM_SLICES = 16                   # UR_POOL_NORM_SLICES
+POOL_SIGNATURES = {
+    "ur_pool_norm_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "ur_pool_norm_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_i64, c_void_p]),
+    "ur_pool_norm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_i64,
+                                 c_void_p]),
+}
+
 _lib = None
 
 
@@ -258,7 +269,8 @@ def load():
     # two runtimes and the library's launches fail with "no ROCm-capable device is detected".
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(ADAPTER_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(ADAPTER_SIGNATURES.items()) + \
+            list(POOL_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

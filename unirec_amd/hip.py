@@ -1,4 +1,4 @@
-"""Tensor-level wrappers over the C ABI (include/unirec_hip.h).
+"""Tensor-level wrappers over the C ABI (include/unirec_hip.h and the family headers beside it).
 
 PyTorch is plumbing here: it owns device memory and the current HIP stream; every computation is a
 call into libunirec_hip.so with raw ``data_ptr()``s.  All functions require CUDA(HIP) tensors and
@@ -1005,6 +1005,53 @@ def mean_pool_bwd(dout, S):
     d32 = dout.data_ptr() if dout.dtype == F32 else 0
     d16 = dout.data_ptr() if dout.dtype == BF16 else 0
     check(lib.ur_mean_pool_bwd(d32, d16, dx.data_ptr(), B, S, D, _stream()), "ur_mean_pool_bwd")
+    return dx
+
+
+# ---- mask-aware pooling fused with the final RMSNorm (include/unirec_hip_pool.h) -------------------
+POOL_MODES = {"masked_mean": _lib.POOL_MASKED_MEAN, "last": _lib.POOL_LAST}
+POOLINGS = ("mean",) + tuple(POOL_MODES)      # "mean": rmsnorm_fwd + mean_pool_fwd over all S positions (the default rule)
+
+
+def _pool_norm_args(x, w, mask, mode):
+    if mode not in POOL_MODES:
+        raise ValueError(f"pool_norm: mode must be one of {', '.join(POOL_MODES)} (got {mode!r})")
+    _need(x, BF16, "x")
+    _need(w, F32, "w")
+    if x.dim() != 3 or tuple(w.shape) != (x.shape[2],):
+        raise ValueError(f"pool_norm: x [B,S,D] and w [D] expected, got {tuple(x.shape)} and {tuple(w.shape)}")
+    if mask is not None:
+        _need(mask, torch.uint8, "mask")
+        if tuple(mask.shape) != tuple(x.shape[:2]):
+            raise ValueError(f"pool_norm: mask must be [B,S] = {tuple(x.shape[:2])}, got {tuple(mask.shape)}")
+    lib = _lib.load()
+    B, S, D = x.shape
+    wsb = lib.ur_pool_norm_workspace_bytes(B, D, POOL_MODES[mode])
+    if wsb < 0:
+        check(-1, "ur_pool_norm_workspace_bytes")
+    return lib, B, S, D, wsb, workspace(wsb, x.device, "pool_norm")
+
+
+def pool_norm_fwd(x, w, eps, mask=None, mode="masked_mean"):
+    """x [B,S,D] bf16 (the last layer's output), w [D] f32 (final norm weight), mask [B,S] uint8 or None (all valid) -> pooled f32 [B,D]:
+    RMSNorm and the pooling rule `mode` in one pass; masked rows are not read."""
+    lib, B, S, D, wsb, ws = _pool_norm_args(x, w, mask, mode)
+    out = torch.empty((B, D), dtype=F32, device=x.device)
+    check(lib.ur_pool_norm_fwd(x.data_ptr(), w.data_ptr(), _p(mask), out.data_ptr(), B, S, D, eps, POOL_MODES[mode], ws.data_ptr(), wsb,
+                               _stream()), "ur_pool_norm_fwd")
+    return out
+
+
+def pool_norm_bwd(d_pooled, x, w, eps, mask=None, mode="masked_mean"):
+    """d_pooled f32 [B,D] -> dx bf16 [B,S,D], the gradient of pool_norm_fwd with respect to x (every row written; +0 where the pooling
+    weight is 0)."""
+    lib, B, S, D, wsb, ws = _pool_norm_args(x, w, mask, mode)
+    _need(d_pooled, F32, "d_pooled")
+    if tuple(d_pooled.shape) != (B, D):
+        raise ValueError(f"pool_norm_bwd: d_pooled must be [B,D] = {(B, D)}, got {tuple(d_pooled.shape)}")
+    dx = torch.empty_like(x)
+    check(lib.ur_pool_norm_bwd(d_pooled.data_ptr(), x.data_ptr(), w.data_ptr(), _p(mask), dx.data_ptr(), B, S, D, eps, POOL_MODES[mode],
+                               ws.data_ptr(), wsb, _stream()), "ur_pool_norm_bwd")
     return dx
 
 

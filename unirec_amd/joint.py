@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import hip
-from .qwen3 import Qwen3Config, Qwen3LoRAModel, normalize_lora_layers, normalize_lora_targets
+from .qwen3 import Qwen3Config, Qwen3LoRAModel, normalize_lora_layers, normalize_lora_targets, normalize_pooling
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -133,8 +133,12 @@ def write_hf_checkpoint(save_directory, cfg, state_dict, dtype=torch.float32):
 class MultiModalQwenEmbedding(nn.Module):
     def __init__(self, base_model_name: str = "Qwen/Qwen3-Embedding-0.6B", qformer_model: nn.Module = None, use_lora: bool = True,
                  lora_config=None, qwen_config: Qwen3Config = None, num_history_items: int = 10,
-                 num_query_tokens_per_item: int = 2, tokenizer=None, user_qformer: nn.Module = None):
+                 num_query_tokens_per_item: int = 2, tokenizer=None, user_qformer: nn.Module = None, pooling: str = None):
+        """pooling: "mean" (over all S positions, padding included: the reference's rule), "masked_mean" or "last" (mask-aware: the
+        embedding does not depend on the padded length); None keeps qwen_config.pooling.  Anything else raises a ValueError."""
         super().__init__()
+        if pooling is not None:
+            normalize_pooling(pooling)      # (refused here: before any module is built)
         # U4 (SURVEY.md §8(a); README.md:44-47 / figure (c), no reference code): the User Q-Former's query
         # tokens are injected at <|user_query_k|> specials that follow the history specials.
         self.user_qformer = user_qformer
@@ -146,6 +150,8 @@ class MultiModalQwenEmbedding(nn.Module):
         cfg = qwen_config or Qwen3Config()
         if lora_config is not None:      # peft.LoraConfig-like object or dict: every field is honoured or refused by name
             apply_lora_config(cfg, lora_config)
+        if pooling is not None:
+            cfg.pooling = pooling
         self.base_model_name = base_model_name
         self.base_model = Qwen3LoRAModel(cfg, use_lora=use_lora)
         self.hidden_size = cfg.hidden_size
@@ -227,8 +233,9 @@ class MultiModalQwenEmbedding(nn.Module):
 
     def save_pretrained(self, save_directory, merged=False, dtype=torch.float32):
         """merged=False: the adapters (``adapter_model.bin`` + ``adapter_config.json``; without LoRA ``base_model.bin``), the Q-Former, the
-        tokenizer files and ``model_config.json``.  merged=True: in place of the adapter files a decoder ordinary ``transformers`` code
-        loads -- ``model.safetensors`` (HF key names, W + s B A in `dtype`, ``embed_tokens`` with its added special-token rows) and
+        tokenizer files and ``model_config.json`` (which also records the pooling rule).  merged=True: in place of the adapter files a
+        decoder ordinary ``transformers`` code loads -- ``model.safetensors`` (HF key names, W + s B A in `dtype`, ``embed_tokens`` with
+        its added special-token rows) and
         ``config.json``; the live model is not modified.  from_pretrained() reads either form back."""
         os.makedirs(save_directory, exist_ok=True)
         self.tokenizer.save_pretrained(save_directory)
@@ -242,7 +249,7 @@ class MultiModalQwenEmbedding(nn.Module):
             torch.save(self.base_model.state_dict(), os.path.join(save_directory, "base_model.bin"))
         torch.save(self.qformer_model.state_dict(), os.path.join(save_directory, "qformer_model.bin"))
         with open(os.path.join(save_directory, "model_config.json"), "w") as f:
-            json.dump({"hidden_size": self.hidden_size, "use_lora": self.use_lora}, f, indent=2)
+            json.dump({"hidden_size": self.hidden_size, "use_lora": self.use_lora, "pooling": self.base_model.pooling}, f, indent=2)
         print(f"Model saved to {save_directory}")
 
     def load_adapter(self, path_or_state_dict):
@@ -290,7 +297,10 @@ class MultiModalQwenEmbedding(nn.Module):
         pass the checkpoint as base_state_dict (or call load_base_weights afterwards) and the decoder's shape as qwen_config.  A merged
         directory holds both (``model.safetensors``, ``config.json``) and gives a model without adapters.  kwargs go to the constructor."""
         with open(os.path.join(save_directory, "model_config.json")) as f:
-            use_lora = bool(json.load(f).get("use_lora", True))
+            model_config = json.load(f)
+        use_lora = bool(model_config.get("use_lora", True))
+        if kwargs.get("pooling") is None:      # a constructor keyword wins; a directory from before the field pools as it always did
+            kwargs["pooling"] = normalize_pooling(model_config.get("pooling", "mean"))
         merged_file = os.path.join(save_directory, "model.safetensors")
         lora_config = None
         if os.path.exists(merged_file):

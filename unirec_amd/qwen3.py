@@ -32,6 +32,17 @@ from .switches import switches
 
 BF16, F32 = torch.bfloat16, torch.float32
 LORA_TARGETS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+# How the final hidden states become one vector per sequence.  "mean": over ALL S positions, padding included (the reference's rule, the
+# default); "masked_mean": over the positions the attention mask marks valid; "last": the last valid position (last-token pooling, for
+# either padding side).  The two mask-aware rules give embeddings that do not depend on the padded length.
+POOLINGS = ("mean", "masked_mean", "last")
+
+
+def normalize_pooling(value):
+    """A pooling rule out of POOLINGS, or a ValueError that names the field."""
+    if value not in POOLINGS:
+        raise ValueError(f"pooling = {value!r} is not supported: one of {', '.join(POOLINGS)} is expected")
+    return value
 
 
 class Qwen3Config:
@@ -40,7 +51,7 @@ class Qwen3Config:
     def __init__(self, vocab_size=151669, hidden_size=1024, intermediate_size=3072, num_hidden_layers=28,
                  num_attention_heads=16, num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-6, rope_theta=1e6,
                  lora_r=16, lora_alpha=32.0, lora_dropout=0.1, initializer_range=0.02,
-                 lora_target_modules=None, lora_layers_to_transform=None, use_rslora=False):
+                 lora_target_modules=None, lora_layers_to_transform=None, use_rslora=False, pooling="mean"):
         self.vocab_size, self.hidden_size, self.intermediate_size = vocab_size, hidden_size, intermediate_size
         self.num_hidden_layers, self.num_attention_heads, self.num_key_value_heads = num_hidden_layers, num_attention_heads, num_key_value_heads
         self.head_dim, self.rms_norm_eps, self.rope_theta = head_dim, rms_norm_eps, rope_theta
@@ -49,6 +60,7 @@ class Qwen3Config:
         # LoRA placement (peft's target_modules / layers_to_transform; None = all seven projections / every layer) and peft's
         # use_rslora (scale lora_alpha / sqrt(r) instead of lora_alpha / r)
         self.lora_target_modules, self.lora_layers_to_transform, self.use_rslora = lora_target_modules, lora_layers_to_transform, bool(use_rslora)
+        self.pooling = normalize_pooling(pooling)
 
 
 def normalize_lora_targets(spec):
@@ -222,6 +234,7 @@ class Qwen3LoRAModel(nn.Module):
     def __init__(self, config: Qwen3Config, use_lora=True):
         super().__init__()
         self.config = config
+        self.pooling = normalize_pooling(getattr(config, "pooling", "mean"))      # (a config object from before the field: the default)
         r = config.lora_r if use_lora else 0
         self.use_lora = r > 0
         if self.use_lora and int(r) not in hip.LORA_RANKS:
@@ -562,7 +575,8 @@ class Qwen3LoRAModel(nn.Module):
     # ---- public forward ---------------------------------------------------------------------------
     def forward_pooled(self, input_ids, attention_mask=None, item_tokens16=None, first_special_id=0):
         """input_ids int64 [B,S]; attention_mask [B,S] or None; item_tokens16 [B,T,D] bf16 (Q-Former
-        query tokens to inject at ids first_special_id + t) or None -> mean-pooled f32 [B,D]."""
+        query tokens to inject at ids first_special_id + t) or None -> pooled f32 [B,D] (self.pooling: the mean over all S positions
+        by default; "masked_mean" / "last" look at attention_mask)."""
         self.refuse_training_while_merged()
         if not input_ids.is_cuda:
             raise hip._lib.UniRecHipError("Qwen3LoRAModel runs on the MI355X only (no CPU fallback in the product path)")
@@ -937,6 +951,12 @@ class Qwen3LoRAModel(nn.Module):
             if keep:
                 saved["layers"].append(L)
             x = x3
+        if self.pooling != "mean":      # final RMSNorm + mask-aware pooling in one pass; the backward recomputes rstd from the row
+            pooled = hip.pool_norm_fwd(x.view(B, S, D), fz["norm"], eps, mask_u8, self.pooling)
+            if not keep:
+                return pooled, None
+            saved["xf"], saved["pooling"] = x, self.pooling
+            return pooled, saved
         last, rstd_f = hip.rmsnorm_fwd(x, fz["norm"], eps)
         pooled, _ = hip.mean_pool_fwd(last.view(B, S, D))
         if not keep:
@@ -955,8 +975,12 @@ class Qwen3LoRAModel(nn.Module):
         eps, sc = c.rms_norm_eps, self._lora_scale()
         dev = d_pooled.device
         cos, sin = self._rope_tables(S, dev)
-        dlast = hip.mean_pool_bwd(d_pooled.contiguous().to(F32), S).view(M, D)
-        dx = hip.rmsnorm_bwd(dlast, saved["xf"], fz["norm"], saved["rstd_f"])
+        if saved.get("pooling") is not None:      # (the rule the forward ran under, and its mask)
+            dx = hip.pool_norm_bwd(d_pooled.contiguous().to(F32), saved["xf"].view(B, S, D), fz["norm"], eps, saved["mask"],
+                                   saved["pooling"]).view(M, D)
+        else:
+            dlast = hip.mean_pool_bwd(d_pooled.contiguous().to(F32), S).view(M, D)
+            dx = hip.rmsnorm_bwd(dlast, saved["xf"], fz["norm"], saved["rstd_f"])
         touched = []
 
         pdrop, step = saved["pdrop"], saved["step"]
