@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 22      /* 18: ur_gemm_plan; 19: ur_rmsnorm_lora_fwd takes 1 to 3 adapters; 20: the loss family of
+#define UR_ABI_VERSION 23      /* 23: ur_lora_plan (the LoRA selection query; no existing declaration changed); 18: ur_gemm_plan; 19: ur_rmsnorm_lora_fwd takes 1 to 3 adapters; 20: the loss family of
                                   unirec_hip_loss.h (the full-catalogue softmax loss; nothing in this header changed); 21: the adapter
                                   family of unirec_hip_adapter.h (ur_lora_merge; nothing in this header changed); 22: the pooling family of
                                   unirec_hip_pool.h (ur_pool_norm_*; nothing in this header changed) */
@@ -189,7 +189,8 @@ int ur_gemm_plan(const ur_gemm_args* a, int32_t count, ur_gemm_plan_info* out);
  * multiples of 8; X, U, V, G 16-byte aligned; P 8-byte aligned.  Rank 16 has LDS-DMA ring kernels for the launches described at
  * drop_bits_t and ur_lora_bgrad; every other rank runs the register-staged kernels (an adapter = 1, 2 or 4 blocks of 16 rank rows
  * over the same fragments of X and the adapter's one bit plane; rank 8 = a half-filled block).  A row of P does not depend on where
- * the row sits in the launch.  ur_rmsnorm_lora_fwd and ur_swiglu_lora_fwd are rank 16 only. */
+ * the row sits in the launch.  ur_rmsnorm_lora_fwd and ur_swiglu_lora_fwd are rank 16 only.  Which kernel, grid, token split and
+ * workspace a launch of ur_lora_project / ur_lora_reduce / ur_lora_bgrad takes: ur_lora_plan (ABI 23, below). */
 typedef struct {
   const void* X; int64_t ldx; int32_t M;
   int32_t nad; int32_t rank; int32_t shared;
@@ -234,6 +235,42 @@ int ur_lora_reduce(const ur_lora_args* a, void* workspace, int64_t workspace_byt
  * g_transposed = 1, scale 1); partial slabs of ceil(M / 512) token blocks (rank 64: ceil(M / 256)) live in the caller's workspace. */
 int64_t ur_lora_bgrad_workspace_bytes(const ur_lora_args* a);
 int ur_lora_bgrad(const ur_lora_args* a, void* workspace, int64_t workspace_bytes, void* stream);
+/* ur_lora_plan (ABI 23): which kernel ur_lora_project / ur_lora_reduce / ur_lora_bgrad (op = UR_LORA_OP_*) launches for these arguments,
+ * and how -- the answer of the ONE selection function the launches and both workspace queries read (docs/lab_notes.md section 33).  Rules
+ * in priority order, "ring widths" = every adapter width a multiple of 64:
+ *   every op   NONE      M == 0: nothing is selected (project returns, reduce / bgrad clear G), 0 workspace
+ *   project    RING      rank 16, one adapter or column ranges (shared = 0), ring widths: 256 tokens per workgroup, grid y = nad
+ *              STAGED    everything else: nad_k = nad for 2 .. 4 adapters that share X, else 1 (grid y = nad); 64 tokens per workgroup
+ *                        when nad_k * rank > 192, else 128
+ *   reduce     RING      rank 16, M a multiple of 128, ring widths, and under dropout drop_bits_t present, 16-byte aligned, bits_t_ld a
+ *                        multiple of 4 and >= width[0], bits_t_stride a multiple of 4 (failing one is no refusal: STAGED runs)
+ *              STAGED    everything else
+ *              splits    token splits of whole 128-token tiles: as many as give the column blocks (ceil(max width / 64) x adapters or 1
+ *                        when they share X) 2048 workgroups (STAGED), or two rounds of the ring's workgroups per CU (2 per CU; 4 for
+ *                        adapters that share X) -- at least 1, at most the tiles and 256; tok_per_block = 128 * ceil(tiles / splits);
+ *                        grid = (ceil(max width / 64), splits, nad or 1); splits > 1 runs the slab sum over workspace_bytes
+ *   bgrad      RING1024  rank 16, ring widths, ceil(M / 1024) * nad >= cu_count: 1024 tokens per workgroup
+ *              RING      rank 16, ring widths: 512 tokens per workgroup
+ *              STAGED    everything else: 512 tokens per workgroup, 256 at rank 64
+ *              splits    = grid x = ceil(M / tok_per_block) slabs, always summed; workspace_bytes is sized for the STAGED block count
+ * blocks / half: the register-staged instantiation (rank 8: 1 / 1, 16: 1 / 0, 32: 2 / 0, 64: 4 / 0).  cu_count > 0 is used as given,
+ * 0 = the current device's (256 without a device).  The query applies the argument checks of the op's entry point (same return codes,
+ * same messages under the entry point's name; the workspace is not an argument), reads pointers for null-ness and alignment only,
+ * launches nothing and answers on a machine without a GPU. */
+enum { UR_LORA_OP_PROJECT = 0, UR_LORA_OP_REDUCE = 1, UR_LORA_OP_BGRAD = 2 };
+enum { UR_LORA_KERNEL_NONE = 0, UR_LORA_KERNEL_STAGED = 1, UR_LORA_KERNEL_RING = 2, UR_LORA_KERNEL_RING1024 = 3 };
+typedef struct {
+  int32_t kernel;                    /* UR_LORA_KERNEL_* */
+  int32_t masked;                    /* the kernel reads dropout flags */
+  int32_t nad_k;                     /* adapters per workgroup */
+  int32_t blocks, half;              /* STAGED: 16-row blocks per adapter, rank 8 */
+  int32_t splits;                    /* reduce: token splits; bgrad: slabs */
+  int32_t tok_per_block;
+  int32_t grid_x, grid_y, grid_z;
+  int32_t lds_bytes;                 /* dynamic LDS of the launch (= the kernel's raised limit when > 0) */
+  int64_t workspace_bytes;           /* what ur_lora_reduce_workspace_bytes / ur_lora_bgrad_workspace_bytes answer at this cu_count */
+} ur_lora_plan_info;
+int ur_lora_plan(int32_t op, const ur_lora_args* a, int32_t cu_count, ur_lora_plan_info* out);
 
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (+ fused dropout / residual) -- models/qformer.py:64,106-107 (embeddings: LN then

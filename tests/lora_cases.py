@@ -8,10 +8,13 @@ Two families:
            one block per CU), exact in ANY summation order -- the kernel must return the correctly rounded exact value bit for bit.
   random   bf16 normals (U at 0.2), p in {0.1, 0.3}, alpha = 1.5 / (1 - p).
 Keep masks are oracle/dropout_ref.lora_keep(seed, p, M, W, nad, row0) -- numpy, never the library's unpacker."""
+import itertools
+
 import numpy as np
 import torch
 
 from oracle import dropout_ref
+from unirec_amd import hip
 
 BF16 = torch.bfloat16
 FAMILIES = ("exact", "random")
@@ -66,6 +69,9 @@ def epilogue_case(family, M, N, K, rank, nad, p, seed=0, row0=0):
 
 
 # ---- the launches of tests/test_gpu_lora_f64.py, path by path (csrc/lora.hip: the dispatch of ur_lora_project / _reduce / _bgrad) -----
+# A case's "path" label is "<op>/<kernel> ...".  Where a list depends on a rule of the dispatch it ASKS the library (hip.lora_plan: the
+# selection function the launches read; no device needed) instead of restating the rule; tests/test_lora_plan.py holds every case of
+# every list to the kernel its label names.
 RANKS = (8, 16, 32, 64)
 ROW0_BIG = 2 ** 33 + 11
 STAGED_COLS = [(8, 72), (80, 8), (88, 64)]              # a ragged width, the minimum width, no range starts at 0
@@ -101,7 +107,7 @@ def _ranges(path, rank, cols, Ms, transposed=True):
 
 def project_staged(rank, nad):
     """register-staged kernel: every rank, 1 .. 4 adapters that share X; a lone rank-16 adapter stays on it through W % 64 != 0"""
-    ring = lambda M, W: rank == 16 and nad == 1 and W % 64 == 0      # noqa: E731
+    ring = lambda M, W: hip.lora_plan("project", M, W, rank, nad)["kernel"] == "ring"      # noqa: E731
     return _shared("project/staged", rank, nad, (1, 31, 129, 257), (8, 120, 128, 136, 392), skip=ring)
 
 
@@ -143,16 +149,11 @@ def reduce_ring_ranges():
     return _ranges("reduce/ring ranges", 16, [(0, 64), (64, 128), (192, 64)], (128, 384))
 
 
-def bgrad_tok(rank):
-    """tokens per block of the register-staged bgrad kernel (csrc/lora.hip: lora_bgrad_tok)"""
-    return 256 if rank == 64 else 512
-
-
 BGRAD_STAGED_COLS = [(8, 72), (80, 64)]                 # one width of 72: the ragged width keeps rank 16 on the register-staged kernel
 
 
 def bgrad_staged(rank):
-    t = bgrad_tok(rank)
+    t = hip.lora_plan("bgrad", 1, rank=rank, cols=BGRAD_STAGED_COLS)["tok_per_block"]      # tokens per block of the register-staged kernel
     return _ranges("bgrad/staged", rank, BGRAD_STAGED_COLS, (t - 1, t, t + 1))
 
 
@@ -160,14 +161,29 @@ def bgrad_ring_512():
     return _ranges("bgrad/ring 512", 16, [(64, 128), (192, 64)], (1, 511, 513, 1100))
 
 
+RING_1024_COLS = [(0, 64), (64, 64), (128, 64), (192, 64)]
+
+
 def bgrad_ring_1024_rows(cu_count):
-    """the smallest M with cdiv(M, 1024) * 4 adapters >= the CU count, plus 37"""
-    blocks = (cu_count + 3) // 4
-    return (blocks - 1) * 1024 + 1 + 37
+    """the first row of the smallest number of 1024-token blocks at which a device of cu_count CUs runs the 1024-token kernel, plus 37"""
+    first = lambda blocks: (blocks - 1) * 1024 + 1      # noqa: E731
+    blocks = next(b for b in itertools.count(1) if hip.lora_plan("bgrad", first(b), cols=RING_1024_COLS, cu_count=cu_count)["kernel"] == "ring1024")
+    return first(blocks) + 37
 
 
 def bgrad_ring_1024(cu_count):
-    return _ranges("bgrad/ring 1024", 16, [(0, 64), (64, 64), (128, 64), (192, 64)], (bgrad_ring_1024_rows(cu_count),))
+    return _ranges("bgrad/ring 1024", 16, RING_1024_COLS, (bgrad_ring_1024_rows(cu_count),))
+
+
+def plan_of(op, c, cu_count=0, **kw):
+    """the library's answer for case c by its sizes (lora_plan_args: dense rows, masked launches with their planes)"""
+    return hip.lora_plan(op, c["M"], c["W"], c["rank"], c["nad"], cols=c["cols"], masked=c["keep"] is not None, pad=8, cu_count=cu_count, **kw)
+
+
+def kernel_of(path):
+    """the kernel (hip.LORA_KERNELS) a path label names: '<op>/staged ...', '<op>/ring ...', 'bgrad/ring 1024'"""
+    word = path.split("/")[1]
+    return "ring1024" if word.startswith("ring 1024") else word.split()[0]
 
 
 def epilogue_cases(rank, nad):

@@ -24,6 +24,7 @@ EXEMPT = {
     "ur_attn_bwd_kv_colsum_floats": "workspace-size / capability query (tests/test_gpu_r5_parity.py exercises both answers)",
     "ur_attn_plan": "selection query; held by tests/test_attn_plan.py",
     "ur_gemm_plan": "selection query; held by tests/test_gemm_plan.py",
+    "ur_lora_plan": "selection query; held by tests/test_lora_plan.py",
     "ur_mean_pool_workspace_bytes": "workspace-size query; one byte less is rejected (test_argument_checks_reject_without_launching)",
     "ur_infonce_workspace_bytes": "workspace-size query; one byte less is rejected (test_argument_checks_reject_without_launching)",
     "ur_heads_workspace_bytes": "workspace-size query",

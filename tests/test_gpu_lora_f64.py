@@ -1,5 +1,7 @@
 """GPU: the LoRA adapter kernels and their dropout flags, ELEMENT BY ELEMENT against float64 (tests/ref64.py, checked on the CPU in
-tests/test_ref64.py), on every dispatch path of csrc/lora.hip plus ur_gemm's masked rank-r epilogue.
+tests/test_ref64.py), on every dispatch path of csrc/lora.hip plus ur_gemm's masked rank-r epilogue.  Before each launch of
+ur_lora_project / _reduce / _bgrad the library is asked (hip.lora_plan, for the very tensors of the launch, on this device) which kernel
+it takes: the one the case's label names.
 
 Flags.  ur_lora_dropout_bits is compared BYTE FOR BYTE with the numpy twin oracle/dropout_ref.lora_words (layout and zero padding words
 included), hip.lora_bits_to_keep with dropout_ref.lora_keep, ur_lora_bits_transpose with a numpy repack.  Every keep mask the kernel
@@ -164,10 +166,17 @@ def _tag(c):
     return f"{c['path']} {c['family']} r{c['rank']} nad{c['nad']} M{c['M']} W{c['W']} p{c['p']} row0 {c['row0']}" + (f" cols{c['cols']}" if c["cols"] else "")
 
 
+def _takes(op, args, c):
+    """the library's own answer (hip.lora_plan on this device) for the LoraArgs of the launch under test is the kernel c's label names"""
+    plan = hip.lora_plan(op, args)
+    assert plan["kernel"] == lora_cases.kernel_of(c["path"]), f"{_tag(c)}: the launch takes {plan}"
+
+
 def _run_project(c):
     what = _tag(c)
     X, U, bits = _wide(c["X"]), [u.to(DEV) for u in c["U"]], _planes(c)
     out, base = _sentinel_bf16(c["M"], c["rank"] * c["nad"])
+    _takes("project", hip.lora_project_args(X, U, cols=c["cols"], alpha=c["alpha"], bits=bits, out=out)[0], c)
     hip.lora_project(X, U, cols=c["cols"], alpha=c["alpha"], bits=bits, out=out)
     _written(out, base, what)
     _hold_bf16("lora_project " + c["path"], c, out, lambda **k: ref64.lora_project(c["X"], c["U"], c["keep"], c["alpha"], c["cols"], **k), what)
@@ -190,6 +199,8 @@ def _run_reduce(c, with_bits_t=False):
     outs = []
     for _ in range(2):
         out = torch.full((n,), float("nan"), device=DEV)
+        if not outs:
+            _takes("reduce", hip.lora_reduce_args(X, V, out, **kw), c)
         hip.lora_reduce(X, V, out, **kw)
         outs.append(out)
     _hold_f32("lora_reduce " + c["path"], c, outs[0],
@@ -206,6 +217,8 @@ def _run_bgrad(c):
     for _ in range(2):
         out, base = _sentinel_bf16(c["M"], c["rank"] * c["nad"])
         gB = torch.full((n,), float("nan"), device=DEV)
+        if not res:
+            _takes("bgrad", hip.lora_bgrad_args(dy, t, Bt, c["cols"], gB, alpha=c["alpha"], out=out)[0], c)
         hip.lora_bgrad(dy, t, Bt, c["cols"], gB, alpha=c["alpha"], out=out)
         _written(out, base, what)
         res.append((out, gB))
@@ -273,7 +286,7 @@ def test_reduce_ring(nad):
 # ur_lora_bgrad
 @pytest.mark.parametrize("rank", lora_cases.RANKS)
 def test_bgrad_register_staged(rank):
-    """every rank, one width of 72, M = lora_bgrad_tok(rank) - 1, + 0, + 1"""
+    """every rank, one width of 72, M = the kernel's tokens per block (the plan's tok_per_block) - 1, + 0, + 1"""
     for c in lora_cases.bgrad_staged(rank):
         _run_bgrad(c)
 

@@ -107,7 +107,8 @@ def test_project_and_reduce_over_column_ranges(r, M):
 @pytest.mark.parametrize("r", RANKS)
 def test_reduce_shared_input(r, M, W_):
     """dA_a = tb_a^T dropout_a(x), masked and not, one and three adapters; deterministic.  M = 1024 (a multiple of 128, widths of 64):
-    the launch the rank-16 ring kernel would take -- with the token-packed flags supplied the register-staged kernel still runs."""
+    the launch the rank-16 ring kernel would take -- with the token-packed flags supplied the register-staged kernel still runs (asserted
+    on the library's own answer, hip.lora_plan, for the very tensors of the launch)."""
     from unirec_amd import hip
     g = torch.Generator().manual_seed(7 * r + M + W_)
     x = _bf(torch.randn(M, W_ + 8, generator=g))[:, :W_]
@@ -126,6 +127,8 @@ def test_reduce_shared_input(r, M, W_):
             if p > 0 and M % 128 == 0:
                 bt = hip.lora_bits_transpose(bits, W_)
                 with_t = torch.full_like(gA, float("nan"))
+                plan = hip.lora_plan("reduce", hip.lora_reduce_args(x, tb, with_t, nad=nad, alpha=1.0 / (1 - p), bits=bits, bits_t=bt))
+                assert plan["kernel"] == "staged" and plan["masked"], plan
                 hip.lora_reduce(x, tb, with_t, nad=nad, alpha=1.0 / (1 - p), bits=bits, bits_t=bt)
                 _g_bound(with_t, want, f"reduce with bits_t r={r} M={M} W={W_} nad={nad}")
                 assert torch.equal(with_t, gA)                              # the same kernel: bits_t is not consumed

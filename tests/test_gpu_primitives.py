@@ -570,6 +570,8 @@ def test_lora_bgrad_ring_kernel(M, cols):
     t = torch.randn(M, len(cols) * r, generator=g).to(DEV).to(torch.bfloat16)
     ntot = sum(n for _, n in cols)
     gB = torch.full((ntot, r), float("nan"), device=DEV)
+    plan = hip.lora_plan("bgrad", hip.lora_bgrad_args(dy, t, [hip.transpose_bf16(b) for b in B], cols, gB, alpha=0.5)[0])
+    assert plan["kernel"] in ("ring", "ring1024"), plan      # the library's own answer for these tensors on this device
     tb = hip.lora_bgrad(dy, t, [hip.transpose_bf16(b) for b in B], cols, gB, alpha=0.5).float()
     want_tb = torch.cat([0.5 * dy[:, c0:c0 + n].float() @ B[a].float() for a, (c0, n) in enumerate(cols)], 1)
     want_gB = torch.cat([dy[:, c0:c0 + n].float().t() @ t[:, a * r:(a + 1) * r].float() for a, (c0, n) in enumerate(cols)], 0)

@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -57,6 +57,13 @@ class LoraArgs(ctypes.Structure):
                 ("V", c_void_p), ("ldv", c_i64),
                 ("G", c_void_p), ("g_transposed", c_int),
                 ("drop_bits_t", c_void_p), ("bits_t_ld", c_i64), ("bits_t_stride", c_i64)]
+
+
+class LoraPlanInfo(ctypes.Structure):
+    """Mirror of ur_lora_plan_info (kernel ids: UR_LORA_KERNEL_*)."""
+    _fields_ = [("kernel", c_int), ("masked", c_int), ("nad_k", c_int), ("blocks", c_int), ("half", c_int), ("splits", c_int),
+                ("tok_per_block", c_int), ("grid_x", c_int), ("grid_y", c_int), ("grid_z", c_int), ("lds_bytes", c_int),
+                ("workspace_bytes", c_i64)]
 
 
 class AttnArgs(ctypes.Structure):
@@ -157,6 +164,7 @@ SIGNATURES = {
     "ur_lora_reduce": (c_int, [ctypes.POINTER(LoraArgs), c_void_p, c_i64, c_void_p]),
     "ur_lora_bgrad_workspace_bytes": (c_i64, [ctypes.POINTER(LoraArgs)]),
     "ur_lora_bgrad": (c_int, [ctypes.POINTER(LoraArgs), c_void_p, c_i64, c_void_p]),
+    "ur_lora_plan": (c_int, [c_int, ctypes.POINTER(LoraArgs), c_int, ctypes.POINTER(LoraPlanInfo)]),
     "ur_layernorm_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_int, c_int, c_float, c_float, c_u64, c_float, c_u64, c_i64, c_void_p]),
     "ur_layernorm_bwd_workspace_bytes": (c_i64, [c_int]),

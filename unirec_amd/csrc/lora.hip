@@ -1272,6 +1272,134 @@ int validate_common(const ur_lora_args* a, const char* who) {
   return 0;
 }
 
+// the argument checks of the three entry points (ur_lora_plan runs the same ones; the workspace is checked at the launch)
+int check_project(const ur_lora_args* a) {
+  if (int rc = validate_common(a, "ur_lora_project")) return rc;
+  UR_REQUIRE(a->P && (((uintptr_t)a->P) & 7) == 0 && (a->ldp % 4) == 0 && a->ldp >= a->rank * a->nad, "ur_lora_project: P must be 8-byte aligned, ldp %% 4 == 0, ldp >= rank nad");
+  for (int e = 0; e < a->nad; ++e)
+    UR_REQUIRE(a->U[e] && UR_ALIGNED16(a->U[e]) && (a->ldu[e] % 8) == 0 && a->ldu[e] >= a->width[a->shared ? 0 : e],
+               "ur_lora_project: U[%d] must be a 16-byte aligned [rank, width] bf16 matrix (ldu %% 8 == 0)", e);
+  return 0;
+}
+int check_reduce(const ur_lora_args* a) {
+  if (int rc = validate_common(a, "ur_lora_reduce")) return rc;
+  UR_REQUIRE(a->V && UR_ALIGNED16(a->V) && (a->ldv % 8) == 0 && a->ldv >= a->rank * a->nad, "ur_lora_reduce: V must be a 16-byte aligned [M, rank nad] bf16 matrix");
+  UR_REQUIRE(a->G && UR_ALIGNED16(a->G), "ur_lora_reduce: G must be 16-byte aligned");
+  return 0;
+}
+int check_bgrad(const ur_lora_args* a) {
+  if (int rc = validate_common(a, "ur_lora_bgrad")) return rc;
+  UR_REQUIRE(!a->shared && !a->drop_bits, "ur_lora_bgrad: adapters own column ranges of X (shared = 0), no dropout planes");
+  UR_REQUIRE(a->P && (((uintptr_t)a->P) & 7) == 0 && (a->ldp % 4) == 0 && a->ldp >= a->rank * a->nad, "ur_lora_bgrad: P must be 8-byte aligned, ldp %% 4 == 0, ldp >= rank nad");
+  UR_REQUIRE(a->V && UR_ALIGNED16(a->V) && (a->ldv % 8) == 0 && a->ldv >= a->rank * a->nad, "ur_lora_bgrad: V must be a 16-byte aligned [M, rank nad] bf16 matrix");
+  UR_REQUIRE(a->G && UR_ALIGNED16(a->G), "ur_lora_bgrad: G must be 16-byte aligned");
+  for (int e = 0; e < a->nad; ++e)
+    UR_REQUIRE(a->U[e] && UR_ALIGNED16(a->U[e]) && (a->ldu[e] % 8) == 0 && a->ldu[e] >= a->width[e],
+               "ur_lora_bgrad: U[%d] must be a 16-byte aligned [rank, width] bf16 matrix (ldu %% 8 == 0)", e);
+  return 0;
+}
+
+// ---- kernel selection ---------------------------------------------------------------------------------------------------------
+// Which kernel a launch of ur_lora_project / _reduce / _bgrad takes, its grid, LDS bytes, token split and workspace are decided HERE and
+// nowhere else: the three entry points, both workspace queries and ur_lora_plan read the LoraPlan (the rule table: include/unirec_hip.h at
+// ur_lora_plan).  Integer arithmetic on sizes, strides, flags and pointer VALUES (null-ness, alignment); no HIP call, no pointer followed;
+// the CU count is an argument.  `a` has passed the nad and rank checks (the callers' checks, or lora_workspace's).
+typedef ur_lora_plan_info LoraPlan;
+constexpr int r2_smem(int nad, bool masked) { return r2_nst(nad) * (R2_XS + nad * R2_VS + (masked ? nad * 1024 : 0)); }
+static_assert(r2_smem(1, false) == r2_nst(1) * r2_stage<1, false>() && r2_smem(4, true) == r2_nst(4) * r2_stage<4, true>(), "the ring kernel's stage");
+// floats of the dense output G (shared: every adapter has the width of entry 0)
+int64_t lora_total(const ur_lora_args* a, bool shared) {
+  int64_t t = 0;
+  for (int e = 0; e < a->nad; ++e) t += (int64_t)a->rank * a->width[shared ? 0 : e];
+  return t;
+}
+LoraPlan lora_select(int op, const ur_lora_args* a, int ncu) {
+  LoraPlan pl = {};
+  if (a->M <= 0) return pl;                                      // UR_LORA_KERNEL_NONE
+  const bool per_entry = !a->shared || a->nad == 1;               // one adapter per workgroup (else: the nad adapters that share X)
+  const int ne = op != UR_LORA_OP_BGRAD && a->shared ? 1 : a->nad;      // entries of width[] in use
+  bool w64 = true;                                               // every width feeds whole 64-column LDS-DMA pieces
+  int wmax = 0;
+  for (int e = 0; e < ne; ++e) { w64 = w64 && (a->width[e] % 64) == 0; wmax = a->width[e] > wmax ? a->width[e] : wmax; }
+  const bool ring16 = a->rank == 16 && w64;                      // the ring kernels are rank-16 fast paths
+  pl.masked = a->drop_bits != nullptr;
+  pl.nad_k = per_entry ? 1 : a->nad;
+  pl.blocks = a->rank <= 16 ? 1 : a->rank / 16;                  // the register-staged instantiation: 16-row blocks, rank 8 a half-filled one
+  pl.half = a->rank == 8;
+  pl.grid_z = pl.splits = 1;
+  if (op == UR_LORA_OP_PROJECT) {
+    const bool ring = ring16 && per_entry;
+    pl.kernel = ring ? UR_LORA_KERNEL_RING : UR_LORA_KERNEL_STAGED;
+    pl.tok_per_block = ring ? 256 : pl.nad_k * a->rank > 192 ? 64 : 128;      // (16 blocks of U: 64 tokens per workgroup)
+    pl.grid_x = ur_cdiv(a->M, pl.tok_per_block);
+    pl.grid_y = per_entry ? a->nad : 1;
+    pl.lds_bytes = ring ? P2_SMEM : 0;
+  } else if (op == UR_LORA_OP_REDUCE) {
+    // the ring takes whole 128-token tiles and, under dropout, the token-packed flags (the split below is then a multiple of 128 tokens)
+    const bool bits_t_ok = a->drop_bits_t != nullptr && (a->bits_t_ld % 4) == 0 && a->bits_t_ld >= a->width[0] && UR_ALIGNED16(a->drop_bits_t) && (a->bits_t_stride % 4) == 0;
+    const bool ring = ring16 && (a->M % 128) == 0 && (!pl.masked || bits_t_ok);
+    pl.kernel = ring ? UR_LORA_KERNEL_RING : UR_LORA_KERNEL_STAGED;
+    const long colblocks = (long)ur_cdiv(wmax, 64) * ne;
+    const int tiles = ur_cdiv(a->M, 128);
+    // register-staged: ~8 blocks per CU; ring: two rounds of the workgroups a CU holds (one for a single adapter, two otherwise), never a partial third
+    const long ring_wg = (!per_entry || r2_nst(1) == 2 ? 4L : 2L) * ncu;
+    long want = ring ? ring_wg / colblocks : (2048L + colblocks - 1) / colblocks;
+    want = want < 1 ? 1 : want > 256 ? 256 : want;
+    if (want > tiles) want = tiles;
+    pl.splits = ur_cdiv(tiles, ur_cdiv(tiles, (int)want));
+    pl.tok_per_block = ur_cdiv(tiles, pl.splits) * 128;
+    pl.grid_x = ur_cdiv(wmax, 64); pl.grid_y = pl.splits; pl.grid_z = per_entry ? a->nad : 1;
+    pl.lds_bytes = ring ? r2_smem(pl.nad_k, pl.masked) : 0;
+    pl.workspace_bytes = pl.splits > 1 ? (int64_t)pl.splits * lora_total(a, a->shared) * (int64_t)sizeof(float) : 0;      // (one split writes G itself)
+  } else {
+    // every width a multiple of 64 (the decoder's are): dy goes through the LDS-DMA ring, in blocks of 1024 tokens where that still
+    // gives every CU a block (half the slabs), else 512; ragged widths and the other ranks keep the register-staged kernel
+    const int staged_tok = 4 * bg_wtok(a->rank / 16);             // (rank 64: 64 tokens per wave)
+    pl.kernel = !ring16 ? UR_LORA_KERNEL_STAGED : (long)ur_cdiv(a->M, 1024) * a->nad >= ncu ? UR_LORA_KERNEL_RING1024 : UR_LORA_KERNEL_RING;
+    pl.masked = 0; pl.nad_k = 1;
+    pl.tok_per_block = pl.kernel == UR_LORA_KERNEL_RING1024 ? 1024 : pl.kernel == UR_LORA_KERNEL_RING ? BG_TOK : staged_tok;
+    pl.splits = pl.grid_x = ur_cdiv(a->M, pl.tok_per_block);
+    pl.grid_y = a->nad;
+    pl.lds_bytes = pl.kernel == UR_LORA_KERNEL_STAGED ? BG_SMEM : b2_smem(pl.kernel == UR_LORA_KERNEL_RING ? 2 : 4);
+    pl.workspace_bytes = (int64_t)ur_cdiv(a->M, staged_tok) * lora_total(a, false) * (int64_t)sizeof(float);      // (sized for the most slabs any kernel writes)
+  }
+  return pl;
+}
+// what the workspace queries answer: 0, not an error, where lora_select has no answer
+int64_t lora_workspace(int op, const ur_lora_args* a) {
+  if (!a || a->nad < 1 || a->nad > 4 || !(a->rank == 8 || a->rank == 16 || a->rank == 32 || a->rank == 64)) return 0;
+  return lora_select(op, a, ur_device_cu_count()).workspace_bytes;
+}
+
+// One launch of the plan: the kernel's dynamic-LDS limit once per device (the guard is a static of the instantiation, i.e. one per kernel
+// symbol; lds_bytes = 0: the default limit is enough), the launch, its check under the entry point's name.
+template <auto KERN, typename P>
+int launch(const char* name, const LoraPlan& pl, hipStream_t st, const P& p) {
+  if (pl.lds_bytes > 0) {
+    static std::atomic<uint64_t> once{0};   // per device
+    UR_ONCE_PER_DEVICE(once) {
+      hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
+      if (er != hipSuccess) UR_FAIL((int)er, "%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(er));
+    }
+  }
+  hipLaunchKernelGGL(KERN, dim3(pl.grid_x, pl.grid_y, pl.grid_z), dim3(256), pl.lds_bytes, st, p);
+  UR_CHECK_LAUNCH(name);
+  return 0;
+}
+// the instantiation a plan names: <adapters per workgroup, masked> of a ring kernel, <.., 16-row blocks, rank 8> of a register-staged one
+#define UR_STAGED(KERNEL, NAD, MK)                                                                                             \
+  (pl.half ? launch<&KERNEL<NAD, MK, 1, true>>(who, pl, st, p) : pl.blocks == 1 ? launch<&KERNEL<NAD, MK, 1, false>>(who, pl, st, p) \
+   : pl.blocks == 2 ? launch<&KERNEL<NAD, MK, 2, false>>(who, pl, st, p) : launch<&KERNEL<NAD, MK, 4, false>>(who, pl, st, p))
+#define UR_BY_NAD(F, MK) (pl.nad_k == 1 ? F(1, MK) : pl.nad_k == 2 ? F(2, MK) : pl.nad_k == 3 ? F(3, MK) : F(4, MK))
+#define UR_BY_PLAN(F) (pl.masked ? UR_BY_NAD(F, true) : UR_BY_NAD(F, false))
+
+int slab_sum(const char* name, const float* ws, float* out, int64_t total, int splits, hipStream_t st) {
+  const long total4 = total / 4;
+  hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((total4 + 63) / 64)), dim3(1024), 0, st, ws, out, total4, splits);
+  UR_CHECK_LAUNCH(name);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int64_t ur_lora_bits_ld(int32_t W) { return ((int64_t)W + 127) / 128 * 16; }
@@ -1294,11 +1422,8 @@ extern "C" int ur_lora_dropout_bits(uint64_t seed, float p, int32_t M, int32_t W
 }
 
 extern "C" int ur_lora_project(const ur_lora_args* a, void* stream) {
-  if (int rc = validate_common(a, "ur_lora_project")) return rc;
-  UR_REQUIRE(a->P && (((uintptr_t)a->P) & 7) == 0 && (a->ldp % 4) == 0 && a->ldp >= a->rank * a->nad, "ur_lora_project: P must be 8-byte aligned, ldp %% 4 == 0, ldp >= rank nad");
-  for (int e = 0; e < a->nad; ++e)
-    UR_REQUIRE(a->U[e] && UR_ALIGNED16(a->U[e]) && (a->ldu[e] % 8) == 0 && a->ldu[e] >= a->width[a->shared ? 0 : e],
-               "ur_lora_project: U[%d] must be a 16-byte aligned [rank, width] bf16 matrix (ldu %% 8 == 0)", e);
+  const char* who = "ur_lora_project";
+  if (int rc = check_project(a)) return rc;
   if (a->M == 0) return 0;
   ProjP p;
   p.X = (const bf16_t*)a->X; p.ldx = a->ldx; p.M = a->M;
@@ -1310,36 +1435,12 @@ extern "C" int ur_lora_project(const ur_lora_args* a, void* stream) {
   p.bits = (const uint8_t*)a->drop_bits; p.bits_ld = a->bits_ld; p.bits_stride = a->bits_stride;
   p.P = (bf16_t*)a->P; p.ldp = a->ldp; p.alpha = a->alpha;
   hipStream_t st = (hipStream_t)stream;
-  const unsigned gx = (unsigned)ur_cdiv(a->M, 128);
-  const bool masked = a->drop_bits != nullptr;
-  bool ring = (!a->shared || a->nad == 1) && a->rank == 16;      // one rank-16 adapter per entry, every width a multiple of 64: wave-private LDS-DMA rings
-  for (int e = 0; ring && e < (a->shared ? 1 : a->nad); ++e) ring = (a->width[e] % 64) == 0;
-  if (ring) {
-    static std::atomic<uint64_t> attr_set[2];      // per device, per kernel
-    const void* fn = masked ? reinterpret_cast<const void*>(&lora_project_ring_kernel<true>) : reinterpret_cast<const void*>(&lora_project_ring_kernel<false>);
-    UR_ONCE_PER_DEVICE(attr_set[masked ? 1 : 0]) {
-      hipError_t er = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, P2_SMEM);
-      if (er != hipSuccess) UR_FAIL((int)er, "ur_lora_project: hipFuncSetAttribute failed: %s", hipGetErrorString(er));
-    }
-    dim3 grid((unsigned)ur_cdiv(a->M, 256), a->nad);
-    if (masked) hipLaunchKernelGGL((lora_project_ring_kernel<true>), grid, dim3(256), P2_SMEM, st, p);
-    else hipLaunchKernelGGL((lora_project_ring_kernel<false>), grid, dim3(256), P2_SMEM, st, p);
-  } else {
-    // the register-staged kernel: (adapters that share X, 16-row blocks per adapter, rank 8) chosen by nad and rank
-    const int nad_k = (!a->shared || a->nad == 1) ? 1 : a->nad;
-    dim3 grid(nad_k * a->rank > 192 ? (unsigned)ur_cdiv(a->M, 64) : gx, nad_k == 1 ? a->nad : 1);      // (16 blocks of U: 64 tokens per workgroup)
-#define UR_PROJ(NAD, NB, HALF)                                                                          \
-    if (masked) hipLaunchKernelGGL((lora_project_kernel<NAD, true, NB, HALF>), grid, dim3(256), 0, st, p); \
-    else hipLaunchKernelGGL((lora_project_kernel<NAD, false, NB, HALF>), grid, dim3(256), 0, st, p)
-#define UR_PROJ_RANK(NAD)                                                                       \
-    if (a->rank == 8) { UR_PROJ(NAD, 1, true); } else if (a->rank == 16) { UR_PROJ(NAD, 1, false); } \
-    else if (a->rank == 32) { UR_PROJ(NAD, 2, false); } else { UR_PROJ(NAD, 4, false); }
-    if (nad_k == 1) { UR_PROJ_RANK(1) } else if (nad_k == 2) { UR_PROJ_RANK(2) } else if (nad_k == 3) { UR_PROJ_RANK(3) } else { UR_PROJ_RANK(4) }
-#undef UR_PROJ_RANK
+  const LoraPlan pl = lora_select(UR_LORA_OP_PROJECT, a, 0);      // (no rule of this op reads the CU count)
+  if (pl.kernel == UR_LORA_KERNEL_RING)      // wave-private LDS-DMA rings
+    return pl.masked ? launch<&lora_project_ring_kernel<true>>(who, pl, st, p) : launch<&lora_project_ring_kernel<false>>(who, pl, st, p);
+#define UR_PROJ(NAD, MK) UR_STAGED(lora_project_kernel, NAD, MK)
+  return UR_BY_PLAN(UR_PROJ);
 #undef UR_PROJ
-  }
-  UR_CHECK_LAUNCH("ur_lora_project");
-  return 0;
 }
 
 extern "C" int ur_rmsnorm_lora_fwd(const void* x, const float* w, void* out, float* rstd, int32_t M, int32_t D, float eps,
@@ -1395,52 +1496,6 @@ extern "C" int ur_swiglu_lora_fwd(const void* gu, void* act, int32_t M, int32_t 
   return 0;
 }
 
-// the ring kernel takes launches whose token count and every width are multiples of 128 / 64 and, under dropout, come with the
-// token-packed flags; (the split below is then a multiple of 128 tokens by construction)
-static inline bool lora_reduce_ring_ok(const ur_lora_args* a) {
-  if (a->rank != 16) return false;                 // the other ranks run the register-staged kernel, token-packed flags or not
-  if ((a->M % 128) != 0 || a->M < 128) return false;
-  const int ne = a->shared ? 1 : a->nad;
-  for (int e = 0; e < ne; ++e)
-    if ((a->width[e] % 64) != 0) return false;
-  if (a->drop_bits != nullptr) {
-    if (a->drop_bits_t == nullptr || (a->bits_t_ld % 4) != 0 || a->bits_t_ld < a->width[0] || !UR_ALIGNED16(a->drop_bits_t) || (a->bits_t_stride % 4) != 0) return false;
-  }
-  return true;
-}
-template <int NAD, bool MASKED>
-static int launch_reduce_ring(const RedP& p, dim3 grid, hipStream_t st) {
-  constexpr int SMEM = r2_nst(NAD) * r2_stage<NAD, MASKED>();
-  static std::atomic<uint64_t> attr_set{0};      // per device
-  UR_ONCE_PER_DEVICE(attr_set) {
-    hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void*>(&lora_reduce_ring_kernel<NAD, MASKED>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (er != hipSuccess) UR_FAIL((int)er, "ur_lora_reduce: hipFuncSetAttribute failed: %s", hipGetErrorString(er));
-  }
-  hipLaunchKernelGGL((lora_reduce_ring_kernel<NAD, MASKED>), grid, dim3(256), SMEM, st, p);
-  return 0;
-}
-static inline int lora_reduce_splits(const ur_lora_args* a) {
-  int wmax = 0;
-  const int ne = a->shared ? 1 : a->nad;
-  for (int e = 0; e < ne; ++e) wmax = a->width[e] > wmax ? a->width[e] : wmax;
-  const long colblocks = (long)ur_cdiv(wmax, 64) * ne;
-  const int tiles = ur_cdiv(a->M, 128);
-  // ~8 blocks per CU for the register-staged kernel; the ring kernel runs one workgroup per CU: 2 rounds of them
-  // ring: two rounds of the workgroups a CU holds (one for a single adapter, two otherwise), never a partial third
-  const long ring_wg = ((a->shared && a->nad > 1) || r2_nst(1) == 2 ? 4L : 2L) * ur_device_cu_count();
-  long want = lora_reduce_ring_ok(a) ? ring_wg / colblocks : (2048L + colblocks - 1) / colblocks;
-  if (want < 1) want = 1;
-  if (want > tiles) want = tiles;
-  if (want > 256) want = 256;
-  const int tiles_per = ur_cdiv(tiles, (int)want);
-  return ur_cdiv(tiles, tiles_per);
-}
-static inline int64_t lora_reduce_total(const ur_lora_args* a) {
-  int64_t t = 0;
-  for (int e = 0; e < a->nad; ++e) t += (int64_t)a->rank * a->width[a->shared ? 0 : e];
-  return t;
-}
-
 extern "C" int64_t ur_lora_bits_t_ld(int32_t W) { return ((int64_t)W + 3) / 4 * 4; }
 
 extern "C" int ur_lora_bits_transpose(const uint8_t* bits, int64_t bits_ld, int64_t bits_stride, int32_t M, int32_t W, int32_t nad,
@@ -1456,100 +1511,52 @@ extern "C" int ur_lora_bits_transpose(const uint8_t* bits, int64_t bits_ld, int6
   return 0;
 }
 
-static inline bool lora_rank_ok(int r) { return r == 8 || r == 16 || r == 32 || r == 64; }
-
-extern "C" int64_t ur_lora_reduce_workspace_bytes(const ur_lora_args* a) {
-  if (!a || a->M <= 0 || a->nad < 1 || a->nad > 4 || !lora_rank_ok(a->rank)) return 0;
-  const int splits = lora_reduce_splits(a);
-  return splits > 1 ? (int64_t)splits * lora_reduce_total(a) * (int64_t)sizeof(float) : 0;
-}
+extern "C" int64_t ur_lora_reduce_workspace_bytes(const ur_lora_args* a) { return lora_workspace(UR_LORA_OP_REDUCE, a); }
 
 extern "C" int ur_lora_reduce(const ur_lora_args* a, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = validate_common(a, "ur_lora_reduce")) return rc;
-  UR_REQUIRE(a->V && UR_ALIGNED16(a->V) && (a->ldv % 8) == 0 && a->ldv >= a->rank * a->nad, "ur_lora_reduce: V must be a 16-byte aligned [M, rank nad] bf16 matrix");
-  UR_REQUIRE(a->G && UR_ALIGNED16(a->G), "ur_lora_reduce: G must be 16-byte aligned");
-  const int64_t total = lora_reduce_total(a);
+  const char* who = "ur_lora_reduce";
+  if (int rc = check_reduce(a)) return rc;
+  const int64_t total = lora_total(a, a->shared);
   hipStream_t st = (hipStream_t)stream;
   if (a->M == 0) {
     hipError_t e = hipMemsetAsync(a->G, 0, (size_t)total * sizeof(float), st);
     if (e != hipSuccess) UR_FAIL((int)e, "ur_lora_reduce: memset failed");
     return 0;
   }
-  const int splits = lora_reduce_splits(a);
-  if (splits > 1)
-    UR_REQUIRE(workspace && UR_ALIGNED16(workspace) && workspace_bytes >= ur_lora_reduce_workspace_bytes(a),
-               "ur_lora_reduce: workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)ur_lora_reduce_workspace_bytes(a));
+  const LoraPlan pl = lora_select(UR_LORA_OP_REDUCE, a, ur_device_cu_count());
+  if (pl.splits > 1)
+    UR_REQUIRE(workspace && UR_ALIGNED16(workspace) && workspace_bytes >= pl.workspace_bytes,
+               "ur_lora_reduce: workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)pl.workspace_bytes);
   RedP p;
   p.X = (const bf16_t*)a->X; p.ldx = a->ldx; p.M = a->M;
   long off = 0;
-  int wmax = 0;
   for (int e = 0; e < 4; ++e) {
     const int s = a->shared ? 0 : (e < a->nad ? e : 0);
     p.col0[e] = a->col0[s]; p.width[e] = a->width[s];
     p.goff[e] = off;
-    if (e < a->nad) { off += (long)a->rank * a->width[s]; wmax = a->width[s] > wmax ? a->width[s] : wmax; }
+    if (e < a->nad) off += (long)a->rank * a->width[s];
   }
   p.V = (const bf16_t*)a->V; p.ldv = a->ldv;
   p.bits = (const uint8_t*)a->drop_bits; p.bits_ld = a->bits_ld; p.bits_stride = a->bits_stride;
   p.bits_t = (const uint32_t*)a->drop_bits_t; p.bt_ld = a->bits_t_ld; p.bt_stride = a->bits_t_stride;
-  p.out = splits > 1 ? (float*)workspace : (float*)a->G;
+  p.out = pl.splits > 1 ? (float*)workspace : (float*)a->G;
   p.transposed = a->g_transposed ? 1 : 0;
-  const int tiles = ur_cdiv(a->M, 128);
-  p.tok_per_block = ur_cdiv(tiles, splits) * 128;
+  p.tok_per_block = pl.tok_per_block;
   p.alpha = a->alpha;
-  const bool masked = a->drop_bits != nullptr;
-  if (lora_reduce_ring_ok(a)) {
-    // X through the LDS-DMA ring (one workgroup per CU: the splits above were sized for it)
-    const bool per_entry = !a->shared || a->nad == 1;
-    dim3 grid(ur_cdiv(wmax, 64), splits, per_entry ? a->nad : 1);
-    const int nad_k = per_entry ? 1 : a->nad;
-    int rc = 0;
-#define UR_RING(NAD, MK) rc = launch_reduce_ring<NAD, MK>(p, grid, st)
-    if (masked) { if (nad_k == 1) UR_RING(1, true); else if (nad_k == 2) UR_RING(2, true); else if (nad_k == 3) UR_RING(3, true); else UR_RING(4, true); }
-    else { if (nad_k == 1) UR_RING(1, false); else if (nad_k == 2) UR_RING(2, false); else if (nad_k == 3) UR_RING(3, false); else UR_RING(4, false); }
+#define UR_RED(NAD, MK) UR_STAGED(lora_reduce_kernel, NAD, MK)
+#define UR_RING(NAD, MK) launch<&lora_reduce_ring_kernel<NAD, MK>>(who, pl, st, p)
+  // ring: X through the LDS-DMA ring (the splits were sized for its workgroups per CU)
+  if (int rc = pl.kernel == UR_LORA_KERNEL_RING ? UR_BY_PLAN(UR_RING) : UR_BY_PLAN(UR_RED)) return rc;
 #undef UR_RING
-    if (rc) return rc;
-  } else {
-    const int nad_k = (!a->shared || a->nad == 1) ? 1 : a->nad;
-    dim3 grid(ur_cdiv(wmax, 64), splits, nad_k == 1 ? a->nad : 1);
-#define UR_RED(NAD, NB, HALF)                                                                          \
-    if (masked) hipLaunchKernelGGL((lora_reduce_kernel<NAD, true, NB, HALF>), grid, dim3(256), 0, st, p); \
-    else hipLaunchKernelGGL((lora_reduce_kernel<NAD, false, NB, HALF>), grid, dim3(256), 0, st, p)
-#define UR_RED_RANK(NAD)                                                                      \
-    if (a->rank == 8) { UR_RED(NAD, 1, true); } else if (a->rank == 16) { UR_RED(NAD, 1, false); } \
-    else if (a->rank == 32) { UR_RED(NAD, 2, false); } else { UR_RED(NAD, 4, false); }
-    if (nad_k == 1) { UR_RED_RANK(1) } else if (nad_k == 2) { UR_RED_RANK(2) } else if (nad_k == 3) { UR_RED_RANK(3) } else { UR_RED_RANK(4) }
-#undef UR_RED_RANK
 #undef UR_RED
-  }
-  UR_CHECK_LAUNCH("ur_lora_reduce");
-  if (splits > 1) {
-    const long total4 = total / 4;
-    hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((total4 + 63) / 64)), dim3(1024), 0, st, (const float*)workspace, (float*)a->G, total4, splits);
-    UR_CHECK_LAUNCH("ur_lora_reduce(slab_sum)");
-  }
-  return 0;
+  return pl.splits > 1 ? slab_sum("ur_lora_reduce(slab_sum)", (const float*)workspace, (float*)a->G, total, pl.splits, st) : 0;
 }
 
-// tokens per block of the register-staged bgrad kernel (rank 64: 64 tokens per wave)
-static inline int lora_bgrad_tok(int rank) { return 4 * bg_wtok(rank / 16); }
-
-extern "C" int64_t ur_lora_bgrad_workspace_bytes(const ur_lora_args* a) {
-  if (!a || a->M <= 0 || a->nad < 1 || a->nad > 4 || !lora_rank_ok(a->rank)) return 0;
-  int64_t total = 0;
-  for (int e = 0; e < a->nad; ++e) total += (int64_t)a->rank * a->width[e];
-  return (int64_t)ur_cdiv(a->M, lora_bgrad_tok(a->rank)) * total * (int64_t)sizeof(float);
-}
+extern "C" int64_t ur_lora_bgrad_workspace_bytes(const ur_lora_args* a) { return lora_workspace(UR_LORA_OP_BGRAD, a); }
 
 extern "C" int ur_lora_bgrad(const ur_lora_args* a, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = validate_common(a, "ur_lora_bgrad")) return rc;
-  UR_REQUIRE(!a->shared && !a->drop_bits, "ur_lora_bgrad: adapters own column ranges of X (shared = 0), no dropout planes");
-  UR_REQUIRE(a->P && (((uintptr_t)a->P) & 7) == 0 && (a->ldp % 4) == 0 && a->ldp >= a->rank * a->nad, "ur_lora_bgrad: P must be 8-byte aligned, ldp %% 4 == 0, ldp >= rank nad");
-  UR_REQUIRE(a->V && UR_ALIGNED16(a->V) && (a->ldv % 8) == 0 && a->ldv >= a->rank * a->nad, "ur_lora_bgrad: V must be a 16-byte aligned [M, rank nad] bf16 matrix");
-  UR_REQUIRE(a->G && UR_ALIGNED16(a->G), "ur_lora_bgrad: G must be 16-byte aligned");
-  for (int e = 0; e < a->nad; ++e)
-    UR_REQUIRE(a->U[e] && UR_ALIGNED16(a->U[e]) && (a->ldu[e] % 8) == 0 && a->ldu[e] >= a->width[e],
-               "ur_lora_bgrad: U[%d] must be a 16-byte aligned [rank, width] bf16 matrix (ldu %% 8 == 0)", e);
+  const char* who = "ur_lora_bgrad";
+  if (int rc = check_bgrad(a)) return rc;
   hipStream_t st = (hipStream_t)stream;
   BgradP p;
   long off = 0;
@@ -1565,37 +1572,24 @@ extern "C" int ur_lora_bgrad(const ur_lora_args* a, void* workspace, int64_t wor
     if (er != hipSuccess) UR_FAIL((int)er, "ur_lora_bgrad: memset failed");
     return 0;
   }
-  UR_REQUIRE(workspace && UR_ALIGNED16(workspace) && workspace_bytes >= ur_lora_bgrad_workspace_bytes(a),
-             "ur_lora_bgrad: workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)ur_lora_bgrad_workspace_bytes(a));
+  const LoraPlan pl = lora_select(UR_LORA_OP_BGRAD, a, ur_device_cu_count());
+  UR_REQUIRE(workspace && UR_ALIGNED16(workspace) && workspace_bytes >= pl.workspace_bytes,
+             "ur_lora_bgrad: workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)pl.workspace_bytes);
   p.X = (const bf16_t*)a->X; p.ldx = a->ldx; p.M = a->M;
   p.V = (const bf16_t*)a->V; p.ldv = a->ldv;
   p.P = (bf16_t*)a->P; p.ldp = a->ldp;
   p.slabs = (float*)workspace; p.total = total; p.alpha = a->alpha;
-  // every width a multiple of 64 (the decoder's are): dy goes through the LDS-DMA ring, in blocks of 1024 tokens where that still
-  // gives every CU a block (half the slabs), else 512; ragged widths keep the register-staged kernel
-  bool ring = a->rank == 16;                       // (the other ranks keep the register-staged kernel)
-  for (int e = 0; e < a->nad; ++e) ring = ring && (a->width[e] % 64) == 0;
-  const int kind = !ring ? 0 : ((long)ur_cdiv(a->M, 1024) * a->nad >= ur_device_cu_count() ? 2 : 1);
-  const int rk = a->rank == 8 ? 0 : a->rank == 16 ? 1 : a->rank == 32 ? 2 : 3;      // register-staged instantiation
-  const void* fn = kind == 1 ? reinterpret_cast<const void*>(&lora_bgrad_ring_kernel<2>) : kind == 2 ? reinterpret_cast<const void*>(&lora_bgrad_ring_kernel<4>)
-                 : rk == 0 ? reinterpret_cast<const void*>(&lora_bgrad_kernel<1, true>) : rk == 1 ? reinterpret_cast<const void*>(&lora_bgrad_kernel<1, false>)
-                 : rk == 2 ? reinterpret_cast<const void*>(&lora_bgrad_kernel<2, false>) : reinterpret_cast<const void*>(&lora_bgrad_kernel<4, false>);
-  const int smem = kind == 0 ? BG_SMEM : b2_smem(kind == 1 ? 2 : 4);      // (rank 64: half the token tile; the attribute may be larger than the launch)
-  static std::atomic<uint64_t> attr_set[6];      // per device, per kernel
-  UR_ONCE_PER_DEVICE(attr_set[kind == 0 ? 2 + rk : kind - 1]) {
-    hipError_t er = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (er != hipSuccess) UR_FAIL((int)er, "ur_lora_bgrad: hipFuncSetAttribute failed: %s", hipGetErrorString(er));
-  }
-  const int nblk = ur_cdiv(a->M, kind == 2 ? 1024 : kind == 1 ? BG_TOK : lora_bgrad_tok(a->rank));
-  if (kind == 2) hipLaunchKernelGGL(lora_bgrad_ring_kernel<4>, dim3(nblk, a->nad), dim3(256), smem, st, p);
-  else if (kind == 1) hipLaunchKernelGGL(lora_bgrad_ring_kernel<2>, dim3(nblk, a->nad), dim3(256), smem, st, p);
-  else if (rk == 0) hipLaunchKernelGGL((lora_bgrad_kernel<1, true>), dim3(nblk, a->nad), dim3(256), BG_SMEM, st, p);
-  else if (rk == 1) hipLaunchKernelGGL((lora_bgrad_kernel<1, false>), dim3(nblk, a->nad), dim3(256), BG_SMEM, st, p);
-  else if (rk == 2) hipLaunchKernelGGL((lora_bgrad_kernel<2, false>), dim3(nblk, a->nad), dim3(256), BG_SMEM, st, p);
-  else hipLaunchKernelGGL((lora_bgrad_kernel<4, false>), dim3(nblk, a->nad), dim3(256), BG_SMEM, st, p);
-  UR_CHECK_LAUNCH("ur_lora_bgrad");
-  const long total4 = total / 4;
-  hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((total4 + 63) / 64)), dim3(1024), 0, st, (const float*)workspace, (float*)a->G, total4, nblk);
-  UR_CHECK_LAUNCH("ur_lora_bgrad(slab_sum)");
+  if (int rc = pl.kernel == UR_LORA_KERNEL_RING1024 ? launch<&lora_bgrad_ring_kernel<4>>(who, pl, st, p)
+             : pl.kernel == UR_LORA_KERNEL_RING ? launch<&lora_bgrad_ring_kernel<2>>(who, pl, st, p)
+             : pl.half ? launch<&lora_bgrad_kernel<1, true>>(who, pl, st, p) : pl.blocks == 1 ? launch<&lora_bgrad_kernel<1, false>>(who, pl, st, p)
+             : pl.blocks == 2 ? launch<&lora_bgrad_kernel<2, false>>(who, pl, st, p) : launch<&lora_bgrad_kernel<4, false>>(who, pl, st, p)) return rc;
+  return slab_sum("ur_lora_bgrad(slab_sum)", (const float*)workspace, (float*)a->G, total, pl.splits, st);
+}
+
+extern "C" int ur_lora_plan(int32_t op, const ur_lora_args* a, int32_t cu_count, ur_lora_plan_info* out) {
+  UR_REQUIRE(out && cu_count >= 0, "ur_lora_plan: null plan or negative cu_count");
+  UR_REQUIRE(op == UR_LORA_OP_PROJECT || op == UR_LORA_OP_REDUCE || op == UR_LORA_OP_BGRAD, "ur_lora_plan: unknown op %d (UR_LORA_OP_*)", op);
+  if (int rc = op == UR_LORA_OP_PROJECT ? check_project(a) : op == UR_LORA_OP_REDUCE ? check_reduce(a) : check_bgrad(a)) return rc;
+  *out = lora_select(op, a, cu_count > 0 ? cu_count : ur_device_cu_count());
   return 0;
 }

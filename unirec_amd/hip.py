@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, AttnBwdArgs, AttnPlanInfo, CatalogSelect, GemmArgs, GemmPlanInfo, LoraArgs, check
+from ._lib import AttnArgs, AttnBwdArgs, AttnPlanInfo, CatalogSelect, GemmArgs, GemmPlanInfo, LoraArgs, LoraPlanInfo, check
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -423,22 +423,88 @@ def lora_bits_to_keep(bits, W):
     return (1 - dropped).reshape(nad, M, ld * 8)[:, :, :W].to(torch.uint8)
 
 
-def _lora_args(X, cols, shared, bits, alpha, rank=16):
+def _lora_fill(X, cols, shared, bits, alpha, rank, U=(), P=None, V=None, G=None, transposed=False, bits_t=None):
+    """The LoraArgs of a launch -- what lora_project, lora_reduce, lora_bgrad, the fused kernels and lora_plan_args all fill.  X: the 2-D
+    bf16 device tensor, or (address, ld, M) for the selection query; bits: the planes' tensor, or (address, ld, plane stride); U: a
+    sequence of (address, ld); P, V: (address, ld); G: an address; bits_t: (address, ld, plane stride)."""
     a = LoraArgs()
-    if X.dtype != BF16 or not X.is_cuda or X.dim() != 2 or X.stride(1) != 1:
+    if isinstance(X, tuple):
+        a.X, a.ldx, a.M = X
+    elif X.dtype != BF16 or not X.is_cuda or X.dim() != 2 or X.stride(1) != 1:
         raise ValueError("lora: X must be a 2-D bf16 device tensor with unit inner stride")
-    a.X, a.ldx, a.M = X.data_ptr(), X.stride(0), X.shape[0]
+    else:
+        a.X, a.ldx, a.M = X.data_ptr(), X.stride(0), X.shape[0]
     a.nad, a.rank, a.shared = len(cols), int(rank), int(shared)
     for e, (c0, w) in enumerate(cols):
         a.col0[e], a.width[e] = int(c0), int(w)
     if bits is not None:
-        a.drop_bits, a.bits_ld, a.bits_stride = bits.data_ptr(), bits.stride(1), bits.stride(0)
+        a.drop_bits, a.bits_ld, a.bits_stride = bits if isinstance(bits, tuple) else (bits.data_ptr(), bits.stride(1), bits.stride(0))
+    if bits_t is not None:
+        a.drop_bits_t, a.bits_t_ld, a.bits_t_stride = bits_t
     a.alpha = float(alpha)
+    for e, (u, ldu) in enumerate(U):
+        a.U[e], a.ldu[e] = u, ldu
+    if P is not None:
+        a.P, a.ldp = P
+    if V is not None:
+        a.V, a.ldv = V
+    if G is not None:
+        a.G, a.g_transposed = G, int(transposed)
     return a
+
+
+LORA_OPS = ("project", "reduce", "bgrad")                        # index = UR_LORA_OP_* (include/unirec_hip.h)
+LORA_KERNELS = ("none", "staged", "ring", "ring1024")            # index = UR_LORA_KERNEL_*
+
+
+def lora_plan_args(M, W=None, rank=16, nad=1, *, cols=None, masked=False, bits_t=False, transposed=False, pad=0, alpha=1.0, **fields):
+    """A LoraArgs of these sizes for the selection query: nad adapters that share an [M, W] input, or cols=[(c0, width), ...] column
+    ranges; dense rows (+ pad columns) and _ADDR wherever a launch has a tensor -- X, every U, P, V, G, and the dropout planes with
+    masked / bits_t.  fields: LoraArgs fields set last (drop_bits_t=_ADDR + 4, bits_t_ld=..., shared=1 ...)."""
+    shared = cols is None
+    if shared:
+        cols = [(0, W)] * nad
+    ldx = max(c0 + w for c0, w in cols) + pad if cols else pad
+    Wb = cols[0][1] if cols else 0
+    ld, ldt = (Wb + 127) // 128 * 16, (Wb + 3) // 4 * 4          # ur_lora_bits_ld, ur_lora_bits_t_ld of the shared input
+    a = _lora_fill((_ADDR, ldx, M), cols, shared, (_ADDR, ld, ld * M) if masked else None, alpha, rank,
+                   U=[(_ADDR, w) for _, w in cols], P=(_ADDR, rank * len(cols)), V=(_ADDR, rank * len(cols)),
+                   G=_ADDR, transposed=transposed, bits_t=(_ADDR, ldt, ldt * ((M + 31) // 32)) if masked and bits_t else None)
+    for name, v in fields.items():
+        setattr(a, name, v)
+    return a
+
+
+def lora_plan(op, a, *sizes, cu_count=0, **kw):
+    """Which kernel ur_lora_project / ur_lora_reduce / ur_lora_bgrad (op: a name from LORA_OPS) launches and how (ur_lora_plan): a dict
+    with kernel (a name from LORA_KERNELS), masked, nad_k, blocks, half, splits, tok_per_block, grid, lds_bytes and workspace_bytes.
+    a: a LoraArgs, or M followed by the arguments of lora_plan_args.  cu_count = 0: the current device's (256 without one).  No tensor
+    and no device is needed.  Raises UniRecHipError where the entry point would refuse the arguments."""
+    if not isinstance(a, LoraArgs):
+        a = lora_plan_args(a, *sizes, **kw)
+    out = LoraPlanInfo()
+    check(_lib.load().ur_lora_plan(LORA_OPS.index(op) if op in LORA_OPS else int(op), ctypes.byref(a), int(cu_count), ctypes.byref(out)), "ur_lora_plan")
+    return dict(kernel=LORA_KERNELS[out.kernel], masked=bool(out.masked), nad_k=int(out.nad_k), blocks=int(out.blocks), half=bool(out.half),
+                splits=int(out.splits), tok_per_block=int(out.tok_per_block), grid=(int(out.grid_x), int(out.grid_y), int(out.grid_z)),
+                lds_bytes=int(out.lds_bytes), workspace_bytes=int(out.workspace_bytes))
 
 
 def _cols_bytes(X, cols):
     return X.shape[0] * 2 * (X.shape[1] if cols is None else sum(w for _, w in cols))
+
+
+def lora_project_args(X, U, cols=None, alpha=1.0, bits=None, out=None):
+    """(the LoraArgs of lora_project for these tensors, out) -- what the launch passes and what lora_plan("project", ...) is asked with"""
+    shared = cols is None
+    if shared:
+        cols = [(0, X.shape[1])] * len(U)
+    r = _lora_rank(U[0].shape[0], "lora_project")
+    for e, u in enumerate(U):
+        if u.dtype != BF16 or u.dim() != 2 or u.shape[0] != r or u.stride(1) != 1 or u.shape[1] != cols[e][1]:
+            raise ValueError(f"lora_project: U[a] must be bf16 [{r}, width_a]")
+    if out is None:
+        out = torch.empty((X.shape[0], r * len(U)), dtype=BF16, device=X.device)
+    return _lora_fill(X, cols, shared, bits, alpha, r, [(u.data_ptr(), u.stride(0)) for u in U], (out.data_ptr(), out.stride(0))), out
 
 
 @_stream_family("lora_project", lambda r, X, U, cols=None, alpha=1.0, bits=None, out=None: _cols_bytes(X, cols) + _nb(r) + (_nb(bits) if bits is not None else 0))
@@ -446,20 +512,8 @@ def lora_project(X, U, cols=None, alpha=1.0, bits=None, out=None):
     """P[m, r a+j] = alpha * sum_w keep_a(m,w) X[m, c0_a+w] U_a[j,w].  U: list of bf16 [r, width_a] matrices, r = U[0].shape[0]
     in LORA_RANKS.  cols=None: the adapters share all of X's columns (optionally with dropout bit planes `bits`);
     cols=[(c0, width), ...]: adapter a owns that column range of X."""
-    lib = _lib.load()
-    shared = cols is None
-    if shared:
-        cols = [(0, X.shape[1])] * len(U)
-    r = _lora_rank(U[0].shape[0], "lora_project")
-    a = _lora_args(X, cols, shared, bits, alpha, r)
-    for e, u in enumerate(U):
-        if u.dtype != BF16 or u.dim() != 2 or u.shape[0] != r or u.stride(1) != 1 or u.shape[1] != cols[e][1]:
-            raise ValueError(f"lora_project: U[a] must be bf16 [{r}, width_a]")
-        a.U[e], a.ldu[e] = u.data_ptr(), u.stride(0)
-    if out is None:
-        out = torch.empty((X.shape[0], r * len(U)), dtype=BF16, device=X.device)
-    a.P, a.ldp = out.data_ptr(), out.stride(0)
-    check(lib.ur_lora_project(ctypes.byref(a), _stream()), "ur_lora_project")
+    a, out = lora_project_args(X, U, cols, alpha, bits, out)
+    check(_lib.load().ur_lora_project(ctypes.byref(a), _stream()), "ur_lora_project")
     return out
 
 
@@ -471,12 +525,10 @@ def swiglu_lora_fwd(gu, I, U, alpha=1.0, bits=None, t_out=None):
     _need(gu, BF16, "gu")
     M = gu.shape[0]
     act = torch.empty((M, I), dtype=BF16, device=gu.device)
-    a = _lora_args(act, [(0, I)], True, bits, alpha)
     if U.dtype != BF16 or U.shape[0] != 16 or U.stride(1) != 1 or U.shape[1] != I:
         raise ValueError("swiglu_lora_fwd: U must be bf16 [16, I]")
-    a.U[0], a.ldu[0] = U.data_ptr(), U.stride(0)
     t = torch.empty((M, 16), dtype=BF16, device=gu.device) if t_out is None else t_out
-    a.P, a.ldp = t.data_ptr(), t.stride(0)
+    a = _lora_fill(act, [(0, I)], True, bits, alpha, 16, [(U.data_ptr(), U.stride(0))], (t.data_ptr(), t.stride(0)))
     check(lib.ur_swiglu_lora_fwd(gu.data_ptr(), act.data_ptr(), M, I, ctypes.byref(a), _stream()), "ur_swiglu_lora_fwd")
     return act, t
 
@@ -494,13 +546,11 @@ def rmsnorm_lora_fwd(x, w, eps, U, alpha=1.0, bits=None, t_out=None):
     M = x.numel() // D
     out = torch.empty_like(x)
     rstd = torch.empty((M,), dtype=F32, device=x.device)
-    a = _lora_args(out.view(M, D), [(0, D)] * len(U), True, bits, alpha)
-    for e, u in enumerate(U):
+    for u in U:
         if u.dtype != BF16 or u.shape[0] != 16 or u.stride(1) != 1 or u.shape[1] != D:
             raise ValueError("rmsnorm_lora_fwd: U[a] must be bf16 [16, D]")
-        a.U[e], a.ldu[e] = u.data_ptr(), u.stride(0)
     t = torch.empty((M, 16 * len(U)), dtype=BF16, device=x.device) if t_out is None else t_out
-    a.P, a.ldp = t.data_ptr(), t.stride(0)
+    a = _lora_fill(out.view(M, D), [(0, D)] * len(U), True, bits, alpha, 16, [(u.data_ptr(), u.stride(0)) for u in U], (t.data_ptr(), t.stride(0)))
     check(lib.ur_rmsnorm_lora_fwd(x.data_ptr(), w.data_ptr(), out.data_ptr(), rstd.data_ptr(), M, D, eps, ctypes.byref(a), _stream()),
           "ur_rmsnorm_lora_fwd")
     return out, rstd, t
@@ -512,6 +562,27 @@ def _reduce_rank(out, X, cols, nad):
     return out.numel() // max(wsum, 1)
 
 
+def lora_reduce_args(X, V, out, cols=None, nad=None, alpha=1.0, bits=None, transposed=False, bits_t=None):
+    """the LoraArgs of lora_reduce for these tensors -- what the launch passes and what lora_plan("reduce", ...) is asked with"""
+    shared = cols is None
+    r = _reduce_rank(out, X, cols, nad)
+    if shared:
+        cols = [(0, X.shape[1])] * int(nad)
+    if out.numel() != r * sum(w for _, w in cols):
+        raise ValueError("lora_reduce: out has the wrong size")
+    r = _lora_rank(r, "lora_reduce")
+    if V.dtype != BF16 or V.stride(1) != 1 or V.shape[0] != X.shape[0] or V.shape[1] < r * len(cols):
+        raise ValueError(f"lora_reduce: V must be bf16 [M, >= {r} nad]")
+    _need(out, F32, "out")
+    if bits is None or bits_t is None:
+        bt = None
+    elif bits_t.dtype != torch.int32 or bits_t.dim() != 3 or bits_t.shape[0] != bits.shape[0] or bits_t.shape[1] * 32 != X.shape[0] or bits_t.stride(2) != 1:
+        raise ValueError("lora_reduce: bits_t must be the int32 [nad, M / 32, ld] tensor of lora_bits_transpose")
+    else:
+        bt = (bits_t.data_ptr(), bits_t.stride(1), bits_t.stride(0))
+    return _lora_fill(X, cols, shared, bits, alpha, r, V=(V.data_ptr(), V.stride(0)), G=out.data_ptr(), transposed=transposed, bits_t=bt)
+
+
 @_stream_family("lora_reduce", lambda r, X, V, out, cols=None, nad=None, alpha=1.0, bits=None, transposed=False, bits_t=None:
                 _cols_bytes(X, cols) + X.shape[0] * 2 * _reduce_rank(out, X, cols, nad) * (len(cols) if cols is not None else int(nad)) + (_nb(bits) if bits is not None else 0))
 def lora_reduce(X, V, out, cols=None, nad=None, alpha=1.0, bits=None, transposed=False, bits_t=None):
@@ -520,23 +591,7 @@ def lora_reduce(X, V, out, cols=None, nad=None, alpha=1.0, bits=None, transposed
     what the size of `out` says.  bits_t: lora_bits_transpose(bits, W) -- with it a rank-16 launch streams X through the LDS-DMA ring
     kernel (the other ranks run the register-staged kernel either way)."""
     lib = _lib.load()
-    shared = cols is None
-    r = _reduce_rank(out, X, cols, nad)
-    if shared:
-        cols = [(0, X.shape[1])] * int(nad)
-    if out.numel() != r * sum(w for _, w in cols):
-        raise ValueError("lora_reduce: out has the wrong size")
-    r = _lora_rank(r, "lora_reduce")
-    a = _lora_args(X, cols, shared, bits, alpha, r)
-    if V.dtype != BF16 or V.stride(1) != 1 or V.shape[0] != X.shape[0] or V.shape[1] < r * len(cols):
-        raise ValueError(f"lora_reduce: V must be bf16 [M, >= {r} nad]")
-    _need(out, F32, "out")
-    a.V, a.ldv = V.data_ptr(), V.stride(0)
-    a.G, a.g_transposed = out.data_ptr(), int(transposed)
-    if bits is not None and bits_t is not None:
-        if bits_t.dtype != torch.int32 or bits_t.dim() != 3 or bits_t.shape[0] != bits.shape[0] or bits_t.shape[1] * 32 != X.shape[0] or bits_t.stride(2) != 1:
-            raise ValueError("lora_reduce: bits_t must be the int32 [nad, M / 32, ld] tensor of lora_bits_transpose")
-        a.drop_bits_t, a.bits_t_ld, a.bits_t_stride = bits_t.data_ptr(), bits_t.stride(1), bits_t.stride(0)
+    a = lora_reduce_args(X, V, out, cols, nad, alpha, bits, transposed, bits_t)
     wsb = lib.ur_lora_reduce_workspace_bytes(ctypes.byref(a))
     ws = workspace(wsb, X.device, "lora").data_ptr() if wsb else 0
     check(lib.ur_lora_reduce(ctypes.byref(a), ws, wsb, _stream()), "ur_lora_reduce")
@@ -1273,17 +1328,12 @@ def rank_of_index(scores, gt_index):
     return rank
 
 
-@_stream_family("lora_bgrad", lambda r, dy, t, Bt, cols, gB, alpha=1.0, out=None: _cols_bytes(dy, cols) + 2 * dy.shape[0] * 2 * Bt[0].shape[0] * len(cols))
-def lora_bgrad(dy, t, Bt, cols, gB, alpha=1.0, out=None):
-    """One pass over dy: returns tb [M, r nad] = alpha * dy_a B_a (Bt: list of B_a^T [r, width_a], r in LORA_RANKS) and fills
-    gB [sum width, r] f32 with dB_a = dy_a^T t_a (adapter a owns columns cols[a] of dy, t holds t_a at columns r a)."""
-    lib = _lib.load()
+def lora_bgrad_args(dy, t, Bt, cols, gB, alpha=1.0, out=None):
+    """(the LoraArgs of lora_bgrad for these tensors, out) -- what the launch passes and what lora_plan("bgrad", ...) is asked with"""
     r = _lora_rank(Bt[0].shape[0], "lora_bgrad")
-    a = _lora_args(dy, cols, False, None, alpha, r)
     for e, u in enumerate(Bt):
         if u.dtype != BF16 or u.dim() != 2 or u.shape[0] != r or u.stride(1) != 1 or u.shape[1] != cols[e][1]:
             raise ValueError(f"lora_bgrad: Bt[a] must be bf16 [{r}, width_a]")
-        a.U[e], a.ldu[e] = u.data_ptr(), u.stride(0)
     if t.dtype != BF16 or t.stride(1) != 1 or t.shape[0] != dy.shape[0] or t.shape[1] < r * len(cols):
         raise ValueError(f"lora_bgrad: t must be bf16 [M, >= {r} nad]")
     _need(gB, F32, "gB")
@@ -1291,9 +1341,16 @@ def lora_bgrad(dy, t, Bt, cols, gB, alpha=1.0, out=None):
         raise ValueError("lora_bgrad: gB has the wrong size")
     if out is None:
         out = torch.empty((dy.shape[0], r * len(cols)), dtype=BF16, device=dy.device)
-    a.V, a.ldv = t.data_ptr(), t.stride(0)
-    a.P, a.ldp = out.data_ptr(), out.stride(0)
-    a.G, a.g_transposed = gB.data_ptr(), 1
+    return _lora_fill(dy, cols, False, None, alpha, r, [(u.data_ptr(), u.stride(0)) for u in Bt], (out.data_ptr(), out.stride(0)), (t.data_ptr(), t.stride(0)),
+                      gB.data_ptr(), True), out
+
+
+@_stream_family("lora_bgrad", lambda r, dy, t, Bt, cols, gB, alpha=1.0, out=None: _cols_bytes(dy, cols) + 2 * dy.shape[0] * 2 * Bt[0].shape[0] * len(cols))
+def lora_bgrad(dy, t, Bt, cols, gB, alpha=1.0, out=None):
+    """One pass over dy: returns tb [M, r nad] = alpha * dy_a B_a (Bt: list of B_a^T [r, width_a], r in LORA_RANKS) and fills
+    gB [sum width, r] f32 with dB_a = dy_a^T t_a (adapter a owns columns cols[a] of dy, t holds t_a at columns r a)."""
+    lib = _lib.load()
+    a, out = lora_bgrad_args(dy, t, Bt, cols, gB, alpha, out)
     wsb = lib.ur_lora_bgrad_workspace_bytes(ctypes.byref(a))
     ws = workspace(wsb, dy.device, "lora").data_ptr() if wsb else 0
     check(lib.ur_lora_bgrad(ctypes.byref(a), ws, wsb, _stream()), "ur_lora_bgrad")

@@ -177,6 +177,13 @@ def lora_rank_rule(r, sw=switches, adapters=None):
             "bits_t": bool(sw.bits_t) and r == 16}
 
 
+def lora_bits_t_sizes(M=None, W=None):
+    """Token-packed flags are made only where ur_lora_reduce's ring kernel consumes them: M tokens in whole 128-token tiles, an adapter
+    input of W columns in whole 64-column pieces (a size left out is not asked about).  tests/test_lora_plan.py holds this and
+    lora_rank_rule's bits_t to the library's own selection (hip.lora_plan)."""
+    return (M is None or M % 128 == 0) and (W is None or W % 64 == 0)
+
+
 _QK_FUSE_MAX_RATIO = 4.0      # largest |w_d| / |w_{d+64}| spread of a rotate-half pair of the q / k norm weights under which the fused epilogue is used
 
 
@@ -659,10 +666,10 @@ class Qwen3LoRAModel(nn.Module):
                   for i in range(self.config.num_hidden_layers) for g, (W, outs) in enumerate(self._group_dims()) if self._place[i][g].planes}
         # token-packed copies for the backward's token reductions (hip.lora_reduce's ring kernel), made on the side stream as well
         packed = {}
-        if M % 128 == 0 and lora_rank_rule(self.config.lora_r)["bits_t"]:
+        if lora_bits_t_sizes(M) and lora_rank_rule(self.config.lora_r)["bits_t"]:
             packed = {(i, g): torch.empty((self._place[i][g].planes, M // 32, hip.lora_bits_t_ld(W)), dtype=torch.int32, device=device)
                       for i in range(self.config.num_hidden_layers) for g, (W, outs) in enumerate(self._group_dims())
-                      if W % 64 == 0 and self._place[i][g].planes}
+                      if lora_bits_t_sizes(W=W) and self._place[i][g].planes}
         self._bits_stream.wait_stream(main)
         self._generate_bits(planes, packed, self._lora_step, M, device, int(row0), p)
 
@@ -819,7 +826,7 @@ class Qwen3LoRAModel(nn.Module):
         mlp_recompute = None if not merged else ("pair" if swiglu == "pair" else ("merged" if lora else "plain"))
         return _Plan(merged=merged, fuse_norm=rule["fuse_norm"] and lora and D == 1024, fuse_rope=fuse_rope, swiglu=swiglu,
                      pad_att=pad_att, bits_one_event=sw.bits_one_event, mlp_recompute=mlp_recompute, rope_bwd_in_dq=in_dq,
-                     rope_k_in_dkv=sw.rope_k_fused, bits_t=(rule["bits_t"] if lora else sw.bits_t) and M % 128 == 0)
+                     rope_k_in_dkv=sw.rope_k_fused, bits_t=(rule["bits_t"] if lora else sw.bits_t) and lora_bits_t_sizes(M))
 
     def _forward_impl(self, item_tokens16, input_ids, mask_u8, first_special_id, keep=True):
         c = self.config
@@ -1002,7 +1009,7 @@ class Qwen3LoRAModel(nn.Module):
             bits_t = packed_bits.get((i, g)) if bits is not None else None             # the prefetched token-packed flags
             if bits_t is not None and place[i][g].view is not None:
                 bits_t = bits_t[place[i][g].view]                                      # (the present adapters' planes of the group's)
-            if bits is not None and bits_t is None and plan.bits_t and xin.shape[1] % 64 == 0:
+            if bits is not None and bits_t is None and plan.bits_t and lora_bits_t_sizes(W=xin.shape[1]):
                 bits_t = hip.lora_bits_transpose(bits, xin.shape[1])          # (no prefetch this step: made here)
             hip.lora_reduce(xin, tb, gA, nad=nb, alpha=1.0 / (1.0 - pdrop), bits=bits, bits_t=bits_t)
             return tb
