@@ -7,7 +7,8 @@ shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
     python tools/kernel_bench.py negatives --B 64 --P 1000 --N 1000000 --K 128 [--catalog-dtype f32|bf16] [--rounds 3]
     python tools/kernel_bench.py catalog_softmax --users 64 512 --dtypes f32 bf16 --N 1000000 [--D 1024] [--rounds 5]
     python tools/kernel_bench.py merge --B 64 --S 2048 [--layers 28] [--rank 16] [--rounds 5] [--iters 2]
-    python tools/kernel_bench.py pool --B 64 --S 2048 [--D 1024] [--rounds 5] [--iters 20]"""
+    python tools/kernel_bench.py pool --B 64 --S 2048 [--D 1024] [--rounds 5] [--iters 20]
+    python tools/kernel_bench.py mrl --B 64 --N 999 --D 1024 --dims 64,128,256,512,1024 [--rounds 5] [--iters 20]"""
 import argparse
 import os
 import sys
@@ -505,9 +506,64 @@ def pool(args):
                 print(f"  {k} / the pair it replaces: {v / base:.3f}")
 
 
+def mrl(args):
+    """Matryoshka InfoNCE at the joint step's candidate shape (--B users, --N negatives each, --D wide, prefixes --dims), scores + loss +
+    backward, alternating --rounds times in this process (device events around --iters calls; medians):
+      (a) hip.mrl_infonce: one pass over the candidates for all score planes, one for the whole gradient;
+      (b) per prefix, cosine_scores + infonce_fwd_bwd on slices made contiguous INSIDE the timed region (what a nested loss costs today);
+      (c) the same with the slices prepared outside it (the kernels alone);
+      (d) cosine_scores + infonce_fwd_bwd at --D only: the single-plane loss, the floor.
+    Each time is also given against the bytes that path must read of the candidates (f32), at the 6.3 TB/s read ceiling."""
+    B, N, D = args.B, args.N, args.D
+    dims = tuple(int(d) for d in args.dims.split(","))
+    peak, tau = 6.3e12, 0.07
+    g = torch.Generator(device="cuda").manual_seed(0)
+    user, pos = torch.randn(B, D, generator=g, device="cuda"), torch.randn(B, D, generator=g, device="cuda")
+    neg = torch.randn(B, N, D, generator=g, device="cuda")
+    cand = B * (N + 1) * 4                                   # bytes of one candidate column
+
+    def pair(u, p, n):
+        s, inv = hip.cosine_scores(u, p, n)
+        return hip.infonce_fwd_bwd(u, p, n, None, s, inv, tau, 1.0)
+
+    def sliced():
+        return [pair(user[:, :d].contiguous(), pos[:, :d].contiguous(), neg[..., :d].contiguous()) for d in dims]
+
+    ready = [(user[:, :d].contiguous(), pos[:, :d].contiguous(), neg[..., :d].contiguous()) for d in dims]
+    paths = {
+        "(a) mrl_infonce, fused": (lambda: hip.mrl_infonce(user, pos, neg, None, dims, None, tau, 1.0), 2 * cand * D),
+        "(b) K sliced pairs, slices made inside": (sliced, 4 * cand * sum(dims)),      # copy in + out, then two reads
+        "(c) K sliced pairs, slices ready": (lambda: [pair(*t) for t in ready], 2 * cand * sum(dims)),
+        "(d) single plane at D (the floor)": (lambda: pair(user, pos, neg), 2 * cand * D),
+    }
+    # the results must not differ: every plane and the one-hot gradients are the sliced kernels' bits (tests/test_gpu_mrl_f64.py); here
+    # the all-ones total against the sum of the sliced losses
+    loss = hip.mrl_infonce(user, pos, neg, None, dims, None, tau, 1.0)[0]
+    want = sum(float(l) for l, _ in sliced())
+    times = {k: [] for k in paths}
+    for fn, _ in paths.values():
+        fn(); fn()
+    torch.cuda.synchronize()
+    for _ in range(args.rounds):
+        for k, (fn, _) in paths.items():
+            times[k].append(timeit(fn, args.iters))
+    print(f"mrl B={B} N={N} D={D} dims={dims} (sum d_k / D = {sum(dims) / D:.3f}), candidates {cand * D / 2**20:.1f} MiB f32; {args.rounds} alternating "
+          f"rounds of {args.iters} calls, device events; loss {float(loss):.6f} against {want:.6f} from the sliced pairs")
+    med = {}
+    for k, (_, nbytes) in paths.items():
+        t = sorted(times[k])
+        med[k] = t[len(t) // 2]
+        print(f"  {k:40s}: median {med[k] * 1e3:9.1f} us  min {t[0] * 1e3:9.1f}  max {t[-1] * 1e3:9.1f}   candidate bytes moved {nbytes / 2**20:8.1f} MiB = "
+              f"{nbytes / (med[k] * 1e-3) / 1e12:6.3f} TB/s = {100 * nbytes / (med[k] * 1e-3) / peak:5.1f} % of 6.3 TB/s")
+    a = med["(a) mrl_infonce, fused"]
+    for k, v in med.items():
+        if not k.startswith("(a)"):
+            print(f"  (a) / {k}: {a / v:.3f}")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog", "negatives", "catalog_softmax", "merge", "pool"])
+    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog", "negatives", "catalog_softmax", "merge", "pool", "mrl"])
     ap.add_argument("--B", type=int, default=8)
     ap.add_argument("--S", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=5)
@@ -524,7 +580,8 @@ if __name__ == "__main__":
     ap.add_argument("--P", type=int, default=1000, help="negatives: candidate columns per user")
     ap.add_argument("--layers", type=int, default=28, help="merge: decoder layers")
     ap.add_argument("--rank", type=int, default=16, help="merge: LoRA rank")
+    ap.add_argument("--dims", default="64,128,256,512,1024", help="mrl: the nested prefix widths, comma separated, the last one --D")
     ap.add_argument("--lib", action="store_true", help="gemm: also time torch.matmul on the same operands (reference point)")
     a = ap.parse_args()
     {"attn": attn, "gemm": gemm, "lora": lora, "rope": rope, "dw": dw, "xattn": xattn, "gemm_lora": gemm_lora, "gemm_merge": gemm_merge, "gemm_step": gemm_step, "rmslora": rmslora, "swilora": swilora,
-     "catalog": catalog, "negatives": negatives, "catalog_softmax": catalog_softmax, "merge": merge, "pool": pool}[a.what](a)
+     "catalog": catalog, "negatives": negatives, "catalog_softmax": catalog_softmax, "merge": merge, "pool": pool, "mrl": mrl}[a.what](a)

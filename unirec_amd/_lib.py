@@ -1,5 +1,5 @@
 """ctypes binding of libunirec_hip.so (the C ABI declared in include/unirec_hip.h, include/unirec_hip_loss.h,
-include/unirec_hip_adapter.h and include/unirec_hip_pool.h).
+include/unirec_hip_adapter.h, include/unirec_hip_pool.h and include/unirec_hip_mrl.h).
 
 Fails loudly: there is no CPU / eager fallback for the product path.
 """
@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -121,6 +121,26 @@ class LoraMerge(ctypes.Structure):
                 ("rank", c_int), ("scale", c_float),
                 ("out_f32", c_void_p), ("ld_f32", c_i64), ("out_bf16", c_void_p), ("ld_bf16", c_i64),
                 ("out_rows", c_int), ("in_cols", c_int)]
+
+
+MRL_MAX_DIMS = 8              # UR_MRL_MAX_DIMS
+MRL_BWD_CHUNKS = 16           # UR_MRL_BWD_CHUNKS
+
+
+class MrlScores(ctypes.Structure):
+    """Mirror of ur_mrl_scores_t (include/unirec_hip_mrl.h)."""
+    _fields_ = [("user", c_void_p), ("pos", c_void_p), ("neg", c_void_p),
+                ("B", c_int), ("N", c_int), ("D", c_int), ("K", c_int), ("dims", c_int * MRL_MAX_DIMS),
+                ("scores", c_void_p), ("cand_inv_norm", c_void_p)]
+
+
+class MrlInfoNCE(ctypes.Structure):
+    """Mirror of ur_mrl_infonce_t (include/unirec_hip_mrl.h)."""
+    _fields_ = [("user", c_void_p), ("pos", c_void_p), ("neg", c_void_p), ("neg_mask", c_void_p),
+                ("B", c_int), ("N", c_int), ("D", c_int), ("K", c_int), ("dims", c_int * MRL_MAX_DIMS),
+                ("weights", c_float * MRL_MAX_DIMS), ("temperature", c_float), ("grad_scale", c_float),
+                ("scores", c_void_p), ("cand_inv_norm", c_void_p), ("plane_loss", c_void_p), ("loss", c_void_p), ("d_user", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_i64)]
 
 
 class F32Range(ctypes.Structure):
@@ -256,6 +276,13 @@ POOL_SIGNATURES = {
                                  c_void_p]),
 }
 
+# the Matryoshka family: every symbol include/unirec_hip_mrl.h declares (tests/test_mrl_host.py holds this table and the two struct
+# mirrors above to that header and to the built library in the same way)
+MRL_SIGNATURES = {
+    "ur_mrl_scores": (c_int, [ctypes.POINTER(MrlScores), c_void_p]),
+    "ur_mrl_infonce": (c_int, [ctypes.POINTER(MrlInfoNCE), c_void_p]),
+}
+
 _lib = None
 
 
@@ -278,7 +305,7 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(ADAPTER_SIGNATURES.items()) + \
-            list(POOL_SIGNATURES.items()):
+            list(POOL_SIGNATURES.items()) + list(MRL_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -66,8 +66,12 @@ class MRREvaluator:
                 "negative_item_embeddings": [item["negative_item_embeddings"] for item in batch]}
 
     @staticmethod
-    def ranks_from_embeddings(user_embeddings, positive_item_embeddings, negative_item_embeddings):
-        """:403-419 on device: ragged negatives are padded and masked; returns int32 ranks [B]."""
+    def ranks_from_embeddings(user_embeddings, positive_item_embeddings, negative_item_embeddings, dims=None):
+        """:403-419 on device: ragged negatives are padded and masked; returns int32 ranks [B].
+        dims (ascending multiples of 4, the last one D): int32 ranks [K,B] on the first dims[k] components of every embedding, the
+        candidates read once (``hip.mrl_scores``)."""
+        if dims is not None:
+            dims = hip.mrl_dims(dims, "dims", user_embeddings.shape[-1])
         u = user_embeddings.detach().to(F32).contiguous()
         dev = u.device
         p = torch.as_tensor(positive_item_embeddings).to(dev, F32).contiguous()
@@ -78,6 +82,9 @@ class MRREvaluator:
         for b, n in enumerate(negs):
             neg[b, :n.shape[0]] = n
             mask[b, :n.shape[0]] = 1
+        if dims is not None:
+            scores, _ = hip.mrl_scores(u, p, neg, dims)
+            return torch.stack([hip.mrr_rank(scores[k], mask) for k in range(len(dims))])
         scores, _ = hip.cosine_scores(u, p, neg)
         return hip.mrr_rank(scores, mask)
 
@@ -151,6 +158,15 @@ class CatalogEvaluator:
         self.catalog = torch.as_tensor(catalog).to(device, dtype).contiguous()    # [N,D], stays in HBM
         self.item_ids = None if item_ids is None else [str(i) for i in item_ids]
         self._inv = None                                                          # catalogue 1/||c||, computed once
+
+    def truncated(self, dim):
+        """A new evaluator over the first `dim` components of every catalogue row, as a contiguous [N, dim] copy of the same dtype
+        (dim / D of the bytes retrieve() streams); its norms are computed by its first call.  For a Matryoshka-trained model:
+        ``ev.truncated(256).retrieve(user[:, :256], k)``.  dim: a positive multiple of 4, at most D."""
+        D = self.catalog.shape[1]
+        if isinstance(dim, bool) or not isinstance(dim, int) or dim <= 0 or dim % 4 or dim > D:
+            raise ValueError(f"CatalogEvaluator.truncated: dim must be a positive multiple of 4 and at most D = {D}, got {dim!r}")
+        return CatalogEvaluator(self.catalog[:, :dim], item_ids=self.item_ids, device=self.catalog.device, dtype=self.catalog.dtype)
 
     def scores(self, user_embeddings):
         if self.catalog.dtype != F32:

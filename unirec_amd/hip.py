@@ -1149,6 +1149,106 @@ def mrr_rank(scores, neg_mask=None):
     return rank
 
 
+# ---- Matryoshka head (include/unirec_hip_mrl.h): csrc/mrl.hip --------------------------------------------------------------------
+MRL_MAX_DIMS = _lib.MRL_MAX_DIMS
+
+
+def mrl_dims(dims, name="dims", D=None):
+    """The checks ur_mrl_* make on the prefix widths, on the host: 1..MRL_MAX_DIMS integers, positive multiples of 4, strictly ascending,
+    the last equal to D when D is given.  Returns them as a tuple of ints; a ValueError names `name`."""
+    try:
+        out = tuple(dims)
+    except TypeError:
+        raise ValueError(f"{name} must be a sequence of 1 to {MRL_MAX_DIMS} integers, got {dims!r}") from None
+    if not 1 <= len(out) <= MRL_MAX_DIMS or any(isinstance(d, bool) or not isinstance(d, int) for d in out):
+        raise ValueError(f"{name} must hold 1 to {MRL_MAX_DIMS} integers, got {dims!r}")
+    if any(d <= 0 or d % 4 for d in out):
+        raise ValueError(f"{name}: every entry must be a positive multiple of 4, got {out}")
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError(f"{name} must be strictly ascending, got {out}")
+    if D is not None and out[-1] != int(D):
+        raise ValueError(f"{name}: the last entry must be the embedding width {int(D)}, got {out}")
+    return out
+
+
+def mrl_weights(weights, K, name="weights"):
+    """None -> all ones (Matryoshka's default); else K finite weights >= 0 with at least one positive, as a tuple of floats."""
+    import math
+    if weights is None:
+        return (1.0,) * K
+    try:
+        out = tuple(float(w) for w in weights)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a sequence of {K} numbers, got {weights!r}") from None
+    if len(out) != K:
+        raise ValueError(f"{name} must hold one weight per prefix ({K}), got {len(out)}")
+    if any(not math.isfinite(w) or w < 0 for w in out):
+        raise ValueError(f"{name}: every weight must be finite and >= 0, got {out}")
+    if not any(w > 0 for w in out):
+        raise ValueError(f"{name}: at least one weight must be positive, got {out}")
+    return out
+
+
+def _mrl_operands(user, pos, neg, dims, what):
+    for t, n in ((user, "user"), (pos, "pos"), (neg, "neg")):
+        _need(t, F32, n)
+    if user.dim() != 2 or pos.shape != user.shape or neg.dim() != 3 or neg.shape[0] != user.shape[0] or neg.shape[2] != user.shape[1]:
+        raise ValueError(f"{what}: need user [B,D], pos [B,D], neg [B,N,D], got {tuple(user.shape)}, {tuple(pos.shape)}, {tuple(neg.shape)}")
+    B, D = user.shape
+    return B, neg.shape[1], D, mrl_dims(dims, "dims", D)
+
+
+@_stream_family("J6_candidate_scores", lambda r, user, pos, neg, dims: _nb(user, pos, neg) + _nb(*r))
+def mrl_scores(user, pos, neg, dims):
+    """user [B,D], pos [B,D], neg [B,N,D] f32 -> (scores [K,B,1+N], cand_inv_norm [K,B,1+N]): plane k holds cosine_scores' bits on the
+    first dims[k] components, and the candidates are read once for all planes (ur_mrl_scores)."""
+    B, N, D, dims = _mrl_operands(user, pos, neg, dims, "mrl_scores")
+    lib = _lib.load()
+    K = len(dims)
+    scores = torch.empty((K, B, N + 1), dtype=F32, device=user.device)
+    inv = torch.empty((K, B, N + 1), dtype=F32, device=user.device)
+    a = _lib.MrlScores()
+    a.user, a.pos, a.neg = user.data_ptr(), pos.data_ptr(), neg.data_ptr()
+    a.B, a.N, a.D, a.K = B, N, D, K
+    a.dims[:K] = dims
+    a.scores, a.cand_inv_norm = scores.data_ptr(), inv.data_ptr()
+    check(lib.ur_mrl_scores(ctypes.byref(a), _stream()), "ur_mrl_scores")
+    return scores, inv
+
+
+def mrl_infonce(user, pos, neg, neg_mask, dims, weights=None, temperature=0.07, grad_scale=1.0, need_grad=True):
+    """The InfoNCE loss on every prefix dims[k] of the embeddings and its weighted sum (ur_mrl_infonce): one pass over the candidates
+    for all the score planes, one more for the whole gradient.  weights: None = all ones.
+    Returns (loss f32 [1], plane_loss f32 [K], d_user f32 [B,D] or None, scores [K,B,1+N], cand_inv_norm [K,B,1+N])."""
+    B, N, D, dims = _mrl_operands(user, pos, neg, dims, "mrl_infonce")
+    K = len(dims)
+    weights = mrl_weights(weights, K)
+    if neg_mask is not None:
+        _need(neg_mask, torch.uint8, "neg_mask")
+        if tuple(neg_mask.shape) != (B, N):
+            raise ValueError(f"mrl_infonce: neg_mask must be [B,N] = {(B, N)}, got {tuple(neg_mask.shape)}")
+    lib = _lib.load()
+    dev = user.device
+    scores = torch.empty((K, B, N + 1), dtype=F32, device=dev)
+    inv = torch.empty((K, B, N + 1), dtype=F32, device=dev)
+    plane_loss = torch.empty((K,), dtype=F32, device=dev)
+    loss = torch.empty((1,), dtype=F32, device=dev)
+    du = torch.empty((B, D), dtype=F32, device=dev) if need_grad else None
+    a = _lib.MrlInfoNCE()
+    a.user, a.pos, a.neg, a.neg_mask = user.data_ptr(), pos.data_ptr(), neg.data_ptr(), _p(neg_mask) or None
+    a.B, a.N, a.D, a.K = B, N, D, K
+    a.dims[:K] = dims
+    a.weights[:K] = weights
+    a.temperature, a.grad_scale = float(temperature), float(grad_scale)
+    a.scores, a.cand_inv_norm, a.plane_loss, a.loss, a.d_user = scores.data_ptr(), inv.data_ptr(), plane_loss.data_ptr(), loss.data_ptr(), _p(du) or None
+    check(lib.ur_mrl_infonce(ctypes.byref(a), _stream()), "ur_mrl_infonce")        # size query: workspace is NULL
+    wsb = a.workspace_bytes
+    ws = workspace(wsb, dev, "mrl_infonce")
+    a.workspace = ws.data_ptr()
+    check(lib.ur_mrl_infonce(ctypes.byref(a), _stream()), "ur_mrl_infonce")
+    return loss, plane_loss, du, scores, inv
+
+
 def topk(scores, K):
     lib = _lib.load()
     _need(scores, F32, "scores")

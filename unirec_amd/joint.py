@@ -355,26 +355,71 @@ class _InfoNCEFn(torch.autograd.Function):
         return du, None, None, None, None
 
 
+class _MatryoshkaInfoNCEFn(torch.autograd.Function):
+    """The weighted sum of the InfoNCE losses on the nested prefixes ``owner.matryoshka_dims`` of the embeddings: one
+    ``hip.mrl_infonce`` (one pass over the candidates for all score planes, one for the whole gradient)."""
+
+    @staticmethod
+    def forward(ctx, user, pos, neg, neg_mask_u8, owner):
+        loss, plane_loss, du, _, _ = hip.mrl_infonce(user, pos, neg, neg_mask_u8, owner.matryoshka_dims, owner.matryoshka_weights,
+                                                     owner.temperature, 1.0, need_grad=True)
+        owner.last_plane_loss = plane_loss
+        ctx.du = du
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.du * g, None, None, None, None
+
+
 class InfoNCELoss(nn.Module):
-    def __init__(self, temperature: float = 0.07):
+    """The reference's InfoNCE loss.  ``matryoshka_dims`` (ascending multiples of 4, the last one the embedding width) makes it the
+    Matryoshka form: sum_k matryoshka_weights[k] * InfoNCE(u[:, :d_k], p[:, :d_k], n[..., :d_k]), every prefix renormalised, weights all
+    ones unless given (a zero weight keeps the plane's loss in ``last_plane_loss`` and out of the sum and the gradient).
+    ``last_plane_loss`` holds the K per-prefix losses of the last call as a device tensor.  None is the plain loss: the same two
+    launches and the same bits as ever."""
+
+    def __init__(self, temperature: float = 0.07, matryoshka_dims=None, matryoshka_weights=None):
         super().__init__()
         self.temperature = temperature
+        if matryoshka_dims is None:
+            if matryoshka_weights is not None:
+                raise ValueError("matryoshka_weights needs matryoshka_dims")
+            self.matryoshka_dims = self.matryoshka_weights = None
+        else:
+            self.matryoshka_dims = hip.mrl_dims(matryoshka_dims, "matryoshka_dims")
+            self.matryoshka_weights = hip.mrl_weights(matryoshka_weights, len(self.matryoshka_dims), "matryoshka_weights")
+            if not float(temperature) > 0:
+                raise ValueError(f"temperature must be positive, got {temperature}")
+        self.last_plane_loss = None
 
     def forward(self, user_embeddings, positive_item_embeddings, negative_item_embeddings, negative_masks=None):
+        if self.matryoshka_dims is not None and self.matryoshka_dims[-1] != user_embeddings.shape[-1]:
+            raise ValueError(f"matryoshka_dims: the last entry must be the embedding width {user_embeddings.shape[-1]}, "
+                             f"got {self.matryoshka_dims}")
         u = user_embeddings.contiguous().to(F32)
         dev = u.device
         p = positive_item_embeddings.to(dev, F32).contiguous()
         n = negative_item_embeddings.to(dev, F32).contiguous()
         m = None if negative_masks is None else negative_masks.to(dev).to(torch.uint8).contiguous()
+        if self.matryoshka_dims is not None:
+            return _MatryoshkaInfoNCEFn.apply(u, p, n, m, self)
         return _InfoNCEFn.apply(u, p, n, m, float(self.temperature))
 
 
-def mrr_ranks(user_embeddings, positive_item_embeddings, negative_item_embeddings, negative_masks=None):
-    """(:408-419) cosine scores of [positive; negatives] and the positive's 1-based rank per user."""
+def mrr_ranks(user_embeddings, positive_item_embeddings, negative_item_embeddings, negative_masks=None, dims=None):
+    """(:408-419) cosine scores of [positive; negatives] and the positive's 1-based rank per user.
+    dims (ascending multiples of 4, the last one D): scores [K,B,N+1] and ranks [K,B] on the first dims[k] components, from one
+    ``hip.mrl_scores`` (the candidates are read once) and ``hip.mrr_rank`` per plane."""
+    if dims is not None:
+        dims = hip.mrl_dims(dims, "dims", user_embeddings.shape[-1])
     u = user_embeddings.detach().contiguous().to(F32)
     p = positive_item_embeddings.to(u.device, F32).contiguous()
     n = negative_item_embeddings.to(u.device, F32).contiguous()
     m = None if negative_masks is None else negative_masks.to(u.device).to(torch.uint8).contiguous()
+    if dims is not None:
+        scores, _ = hip.mrl_scores(u, p, n, dims)
+        return scores, torch.stack([hip.mrr_rank(scores[k], m) for k in range(len(dims))])
     scores, _ = hip.cosine_scores(u, p, n)
     return scores, hip.mrr_rank(scores, m)
 
@@ -440,14 +485,19 @@ _CANDIDATE_KEYS = ("negative_item_index", "negative_masks", "positive_item_embed
 class MultiModalTrainer:
     """compute_loss of the reference's HF-Trainer subclass (:477-498) without the Trainer."""
 
-    def __init__(self, temperature: float = 0.07, negatives=None, loss: str = "infonce"):
+    def __init__(self, temperature: float = 0.07, negatives=None, loss: str = "infonce", matryoshka_dims=None, matryoshka_weights=None):
         """negatives: a ``negatives.CatalogCandidates``; needed by batches that carry ``positive_item_index`` instead of embeddings.
         loss: "infonce" (the reference's loss over one positive and the batch's negatives) or "catalog_softmax" (``CatalogSoftmaxLoss``
-        over the whole catalogue of ``negatives``, which must then sample and mine nothing)."""
+        over the whole catalogue of ``negatives``, which must then sample and mine nothing).
+        matryoshka_dims, matryoshka_weights: the Matryoshka form of InfoNCE (``InfoNCELoss``): the loss on every nested prefix of the
+        embeddings, for embedding batches and index batches alike.  Hard negatives are still mined with full-width scores: the mined
+        set is the one the plain loss would train on, and every prefix is trained against it."""
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+        if loss == "catalog_softmax" and (matryoshka_dims is not None or matryoshka_weights is not None):
+            raise ValueError('loss="catalog_softmax" has no Matryoshka form: matryoshka_dims / matryoshka_weights need loss="infonce"')
         self.loss = loss
-        self.infonce_loss = InfoNCELoss(temperature)
+        self.infonce_loss = InfoNCELoss(temperature, matryoshka_dims, matryoshka_weights)
         self.negatives = negatives
         self.catalog_softmax_loss = None
         if loss == "catalog_softmax":
@@ -577,12 +627,15 @@ class JointTrainer:
     ``negatives`` (a ``negatives.CatalogCandidates``) lets a batch name its candidates by index into a resident catalogue
     (``MultiModalTrainer.compute_loss``); the random negatives of such a batch are keyed on ``state.global_step``.
     ``loss="catalog_softmax"`` replaces InfoNCE by the softmax over that whole catalogue (``CatalogSoftmaxLoss``); gradient scale,
-    clipping and logging are the same."""
+    clipping and logging are the same.  ``matryoshka_dims`` / ``matryoshka_weights`` make the InfoNCE loss its Matryoshka form
+    (``InfoNCELoss``); the log records then carry ``plane_loss``, the per-prefix losses averaged over the logging window."""
 
-    def __init__(self, model, args, num_training_steps=None, temperature: float = 0.07, negatives=None, loss: str = "infonce"):
+    def __init__(self, model, args, num_training_steps=None, temperature: float = 0.07, negatives=None, loss: str = "infonce",
+                 matryoshka_dims=None, matryoshka_weights=None):
         from . import dp
         from .optim import FusedAdamW, get_scheduler
-        self.loss_fn = MultiModalTrainer(temperature, negatives, loss)      # (first: a refused `loss` touches neither model nor device)
+        # (first: a refused `loss` or `matryoshka_dims` touches neither model nor device)
+        self.loss_fn = MultiModalTrainer(temperature, negatives, loss, matryoshka_dims, matryoshka_weights)
         self.model, self.args = model, args
         self.config = cfg = TrainingConfig(args, num_training_steps)
         dev = model.base_model.embed_tokens.weight.device
@@ -596,7 +649,7 @@ class JointTrainer:
                                     max_grad_norm=cfg.max_grad_norm, no_decay=self.no_decay if cfg.weight_decay > 0 else ())
         self.lr_scheduler = get_scheduler(cfg.lr_scheduler_type, self.optimizer, cfg.warmup_steps, cfg.num_training_steps)
         self.state = JointTrainerState()
-        self._tr_loss, self._since_log = None, 0
+        self._tr_loss, self._tr_planes, self._since_log = None, None, 0
         # data parallel: the buckets and hooks of bench.py's joint step (LoRA: groups of 7 layers; Q-Former: one bucket per layer)
         self.grad_scale, self.buckets, self.tail_buckets = 1.0, [], []
         if torch.distributed.is_available() and torch.distributed.is_initialized():
@@ -637,6 +690,9 @@ class JointTrainer:
         self.state.global_step += 1
         loss = loss.detach()
         self._tr_loss = loss.clone() if self._tr_loss is None else self._tr_loss + loss
+        planes = self.loss_fn.infonce_loss.last_plane_loss if self.loss_fn.loss == "infonce" else None
+        if planes is not None:
+            self._tr_planes = planes.clone() if self._tr_planes is None else self._tr_planes + planes
         self._since_log += 1
         ls = self.config.logging_steps
         if ls > 0 and self.state.global_step % ls == 0:
@@ -648,10 +704,13 @@ class JointTrainer:
         norm = self.optimizer.last_grad_norm
         if norm is not None:
             vals.append(norm)
-        host = torch.stack(vals).tolist()
+        planes = self._tr_planes
+        host = torch.cat([torch.stack(vals)] + ([] if planes is None else [planes.float()])).tolist()      # the one host read
         rec = {"step": self.state.global_step, "loss": host[0] / self._since_log}
         if norm is not None:
             rec["grad_norm"] = host[1]
         rec["learning_rate"] = lr
+        if planes is not None:
+            rec["plane_loss"] = [v / self._since_log for v in host[len(vals):]]
         self.state.log_history.append(rec)
-        self._tr_loss, self._since_log = None, 0
+        self._tr_loss, self._tr_planes, self._since_log = None, None, 0
