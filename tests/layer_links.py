@@ -96,8 +96,10 @@ class _TapedTranspose:
 class Tape:
     """Proxy for the module ``unirec_amd.hip`` (or a stand-in with the same entry points): forwards every call and records the launches."""
 
-    def __init__(self, real):
-        self.__dict__.update(_real=real, recs=[], _ctxs=[])
+    def __init__(self, real, host=None, prep=None, step=None):
+        """host / prep / step: the entry-point sets of the link map in force (default: the decoder's, HOST / PREP / STEP)"""
+        self.__dict__.update(_real=real, recs=[], _ctxs=[], _host=HOST if host is None else host, _prep=PREP if prep is None else prep,
+                             _step=STEP if step is None else step)
 
     def _snap(self, v):
         if isinstance(v, torch.Tensor):
@@ -121,9 +123,9 @@ class Tape:
         attr = getattr(self._real, name)
         if name == "BatchedTranspose":
             return lambda sources: _TapedTranspose(self, attr(sources))
-        if name in HOST or not callable(attr) or isinstance(attr, type) or name.startswith("_"):
+        if name in self._host or not callable(attr) or isinstance(attr, type) or name.startswith("_"):
             return attr
-        if name not in STEP and name not in PREP:
+        if name not in self._step and name not in self._prep:
             raise TapeError(f"hip.{name}: a launch the link map does not know")
 
         def call(*a, **k):
