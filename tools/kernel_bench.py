@@ -4,6 +4,7 @@ shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
     python tools/kernel_bench.py attn|gemm|lora [--B 8] [--iters 5]
     python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 [--D 1024] [--rounds 3] [--chunks]
     python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 --scorer vector mfma --catalog-dtype bf16
+    python tools/kernel_bench.py catalog --shortlist 128 --catalog-dtype bf16 [--N 1000000] [--D 1024] [--rounds 3]
     python tools/kernel_bench.py negatives --B 64 --P 1000 --N 1000000 --K 128 [--catalog-dtype f32|bf16] [--rounds 3]
     python tools/kernel_bench.py catalog_softmax --users 64 512 --dtypes f32 bf16 --N 1000000 [--D 1024] [--rounds 5]
     python tools/kernel_bench.py merge --B 64 --S 2048 [--layers 28] [--rank 16] [--rounds 5] [--iters 2]
@@ -264,6 +265,8 @@ def catalog(args):
     --scorer vector mfma times retrieve() once per named scorer instead (alternating in this process, the library's own choice last);
     --catalog-dtype bf16 keeps the catalogue in bf16, where evaluate() does not exist and the first scorer named is the reference."""
     from unirec_amd.evaluation import CatalogEvaluator
+    if args.shortlist:
+        return catalog_shortlist(args)
     B, N, K, D = args.B, args.N, args.K, args.D
     bf16 = args.catalog_dtype == "bf16"
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -315,6 +318,59 @@ def catalog(args):
         t = sorted(times[name])
         print(f"{name:44s}: median {t[len(t) // 2]:9.2f} ms  min {t[0]:9.2f}  max {t[-1]:9.2f}  (spread {t[-1] - t[0]:.2f} over {len(t)} alternating rounds)"
               f"  peak allocation {peaks[name] / 2**20:9.2f} MiB")
+
+
+def catalog_shortlist(args):
+    """The two-stage retrieve(k, shortlist=--shortlist) against the exact retrieve(k) (scorer=None) on the same bf16 catalogue, alternating
+    --rounds times in this process after one call of each, at (B, K) = (512, 100) and (64, 10): wall time of the whole call (each ends in a
+    host read of the metrics), the ratio of the medians, the recall of the two-stage list against the exact one, and the two stages of the
+    two-stage call timed on their own (hip.catalog_coarse_select, hip.catalog_rerank: the split that says which stage holds the time)."""
+    from unirec_amd.evaluation import CatalogEvaluator
+    N, D, S = args.N, args.D, args.shortlist
+    if args.catalog_dtype != "bf16":
+        raise SystemExit("catalog --shortlist: the coarse scorer reads a bf16 catalogue; add --catalog-dtype bf16")
+    g = torch.Generator(device="cuda").manual_seed(0)
+    cat = torch.randn(N, D, generator=g, device="cuda").to(torch.bfloat16)
+    ev = CatalogEvaluator(cat, dtype=cat.dtype)
+    del cat
+    print(f"catalog --shortlist {S}: N={N} D={D}, catalogue bf16 {N * D * 2 / 2**20:.0f} MiB, {args.rounds} alternating rounds")
+    for B, K in ((512, 100), (64, 10)):
+        user = torch.randn(B, D, generator=g, device="cuda")
+        gt = torch.randint(0, N, (B,), generator=g, device="cuda")
+        ev.retrieve(user[:1], k=1)                            # the catalogue norms: cached by every path, outside every figure below
+        variants = [("exact retrieve (scorer=None)", lambda: ev.retrieve(user, k=K, gt_index=gt)),
+                    (f"two-stage retrieve (shortlist={S})", lambda: ev.retrieve(user, k=K, gt_index=gt, shortlist=S)),
+                    ("  coarse select alone", lambda: hip.catalog_coarse_select(user, ev.catalog, S, ev._inv, gt_index=gt)),
+                    ("  re-rank alone", None)]
+        short = hip.catalog_coarse_select(user, ev.catalog, S, ev._inv, gt_index=gt)[0]
+        variants[3] = (variants[3][0], lambda: hip.catalog_rerank(user, ev.catalog, short, K, ev._inv))
+        outs = {name: fn() for name, fn in variants[:2]}      # warm-up and results
+        for name, fn in variants[2:]:
+            fn()
+        exact, two = outs[variants[0][0]], outs[variants[1][0]]
+        hit = (two["topk_index"][:, :, None] == exact["topk_index"][:, None, :]).any(2).float().mean().item()
+        same = (two["topk_index"] == exact["topk_index"]).all(1).float().mean().item()
+        rank_off = ((two["rank"] - exact["rank"]).abs().double() / exact["rank"].double()).median().item()
+        times = {name: [] for name, _ in variants}
+        for _ in range(args.rounds):
+            for name, fn in variants:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                times[name].append((time.perf_counter() - t0) * 1e3)
+        print(f"B={B} K={K}: recall@{K} of the two-stage list against the exact one {hit:.6f}; users whose whole list is identical {same:.4f}; "
+              f"median |coarse rank - exact rank| / exact rank {rank_off:.2e}")
+        med = {}
+        for name, _ in variants:
+            t = sorted(times[name])
+            med[name] = t[len(t) // 2]
+            print(f"  {name:40s}: median {med[name]:9.2f} ms  min {t[0]:9.2f}  max {t[-1]:9.2f}  (spread {t[-1] - t[0]:.2f} over {len(t)} alternating rounds)")
+        a, b = variants[0][0], variants[1][0]
+        gap = med[a] - med[b]
+        spread = max(max(times[a]) - min(times[a]), max(times[b]) - min(times[b]))
+        print(f"  exact / two-stage = {med[a] / med[b]:.2f}x  (difference {gap:.2f} ms against a spread of {spread:.2f} ms: "
+              f"{'faster by more than the spread' if gap > spread else 'NOT faster by more than the spread'})")
 
 
 def negatives(args):
@@ -574,6 +630,7 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=3, help="catalog: alternating timed rounds")
     ap.add_argument("--chunks", action="store_true", help="catalog: also time retrieve() at half and double the default rows per chunk")
     ap.add_argument("--scorer", nargs="+", choices=["vector", "mfma"], help="catalog: time retrieve() with each of these scorers, alternating")
+    ap.add_argument("--shortlist", type=int, default=0, help="catalog: time retrieve(shortlist=...) against the exact retrieve() at (512, 100) and (64, 10)")
     ap.add_argument("--catalog-dtype", choices=["f32", "bf16"], default="f32", help="catalog: the dtype the catalogue is stored in")
     ap.add_argument("--users", type=int, nargs="+", help="catalog_softmax: the user counts to time (default: --B)")
     ap.add_argument("--dtypes", nargs="+", choices=["f32", "bf16"], help="catalog_softmax: the catalogue dtypes to time (default: --catalog-dtype)")

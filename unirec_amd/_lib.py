@@ -1,5 +1,5 @@
 """ctypes binding of libunirec_hip.so (the C ABI declared in include/unirec_hip.h, include/unirec_hip_loss.h,
-include/unirec_hip_adapter.h, include/unirec_hip_pool.h and include/unirec_hip_mrl.h).
+include/unirec_hip_adapter.h, include/unirec_hip_pool.h, include/unirec_hip_mrl.h and include/unirec_hip_coarse.h).
 
 Fails loudly: there is no CPU / eager fallback for the product path.
 """
@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -140,6 +140,31 @@ class MrlInfoNCE(ctypes.Structure):
                 ("B", c_int), ("N", c_int), ("D", c_int), ("K", c_int), ("dims", c_int * MRL_MAX_DIMS),
                 ("weights", c_float * MRL_MAX_DIMS), ("temperature", c_float), ("grad_scale", c_float),
                 ("scores", c_void_p), ("cand_inv_norm", c_void_p), ("plane_loss", c_void_p), ("loss", c_void_p), ("d_user", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_i64)]
+
+
+COARSE_USER_GROUP = 64        # UR_COARSE_USER_GROUP
+
+
+class CatalogCoarse(ctypes.Structure):
+    """Mirror of ur_catalog_coarse_t (include/unirec_hip_coarse.h)."""
+    _fields_ = [("user", c_void_p), ("catalog", c_void_p), ("catalog_bf16", c_int),
+                ("cat_inv_norm", c_void_p), ("cat_norm_ready", c_int),
+                ("B", c_int), ("N", c_i64), ("D", c_int), ("K", c_int),
+                ("topk_index", c_void_p), ("topk_score", c_void_p),
+                ("gt_index", c_void_p), ("rank", c_void_p),
+                ("exclude", c_void_p), ("E", c_int),
+                ("chunk_rows", c_i64),
+                ("workspace", c_void_p), ("workspace_bytes", c_i64)]
+
+
+class CatalogRerank(ctypes.Structure):
+    """Mirror of ur_catalog_rerank_t (include/unirec_hip_coarse.h)."""
+    _fields_ = [("user", c_void_p), ("catalog", c_void_p), ("catalog_bf16", c_int),
+                ("cat_inv_norm", c_void_p), ("cat_norm_ready", c_int),
+                ("B", c_int), ("N", c_i64), ("D", c_int),
+                ("index", c_void_p), ("K_in", c_int), ("k", c_int),
+                ("topk_index", c_void_p), ("topk_score", c_void_p),
                 ("workspace", c_void_p), ("workspace_bytes", c_i64)]
 
 
@@ -283,6 +308,13 @@ MRL_SIGNATURES = {
     "ur_mrl_infonce": (c_int, [ctypes.POINTER(MrlInfoNCE), c_void_p]),
 }
 
+# the two-stage retrieval family: every symbol include/unirec_hip_coarse.h declares (tests/test_catalog_coarse_host.py holds this table
+# and the two struct mirrors above to that header and to the built library in the same way)
+COARSE_SIGNATURES = {
+    "ur_catalog_coarse_select": (c_int, [ctypes.POINTER(CatalogCoarse), c_void_p]),
+    "ur_catalog_rerank": (c_int, [ctypes.POINTER(CatalogRerank), c_void_p]),
+}
+
 _lib = None
 
 
@@ -305,7 +337,7 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(ADAPTER_SIGNATURES.items()) + \
-            list(POOL_SIGNATURES.items()) + list(MRL_SIGNATURES.items()):
+            list(POOL_SIGNATURES.items()) + list(MRL_SIGNATURES.items()) + list(COARSE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -1,0 +1,349 @@
+// Two-stage retrieval (include/unirec_hip_coarse.h), gfx950 only.
+//
+//   ur_catalog_coarse_select : an APPROXIMATE shortlist over a bf16 catalogue.  The users are rounded to bf16 once; per chunk of rows
+//                              catalog_scores_bf16_kernel writes s~_bn = ((u~_b . c_n) * iu~_b) * ic_n on v_mfma_f32_16x16x32_bf16 into
+//                              the chunk buffer and catalog_select_kernel (catalog_select.hip.h, the kernel of ur_catalog_scores' select
+//                              mode, unchanged) folds it into the lists and the rank counts.
+//   ur_catalog_rerank        : the EXACT scores of a shortlist, catalog_scores_kernel's own chain per (user, slot), sorted per user.
+//
+// The header holds the definitions in full; the comments here are about the placement.
+#include "common.hip.h"
+#include "unirec_hip.h"
+#include "unirec_hip_coarse.h"
+#include "catalog_select.hip.h"
+
+namespace {
+
+// ---- the coarse scorer ------------------------------------------------------------------------------------------------------------
+// A workgroup = CC_WAVES waves owns 16 UT users and a range of catalogue rows.  A = users (row = user), B = catalogue rows (column =
+// row n), K = the embedding axis: lane l of v_mfma_f32_16x16x32_bf16 holds A[l & 15][8 (l >> 4) + j] and B[8 (l >> 4) + j][l & 15],
+// j = 0 .. 7, and C[4 (l >> 4) + e][l & 15], e = 0 .. 3.
+//   Users: the bf16 copy is staged once in LDS in operand order, us[step s][user tile t][lane][8]: a wave's ds_read_b128 of one operand
+//   is 1024 contiguous bytes.  The staged row is padded with zeros to a multiple of 32 elements.
+//   Catalogue: rows are K-contiguous, so the lane's operand of step s is the 16 bytes at row n, element 32 s + 8 (l >> 4): straight from
+//   global memory, no LDS (an element is used once per user group).  A lane whose 8 elements lie past D takes zeros (D % 8 == 0: a
+//   lane's piece is wholly inside or wholly outside).
+//   A wave takes CC_RT 16-row tiles per step and all UT user tiles.  The K steps s = 0, 1, .. of an output tile are dealt to NC chains,
+//   step s to chain s % NC, each chain ascending from C = 0, and the chains are added at the end, c0 + c1 (NC = 2, D <= 1024) or
+//   (c0 + c2) + (c1 + c3) (NC = 4, D > 1024) -- the order of the sum is fixed by D alone.  One chain over all of D = 2048 (64 dependent
+//   f32 additions) measured 4.4 x the error of the exact scorer's lane chains + tree and missed the tests' bound; 16 steps per chain at
+//   most keep it inside.  UT CC_RT NC = 16 independent accumulators keep the matrix pipe busy between dependent steps, and an A
+//   operand read from LDS serves CC_RT MFMAs.
+// User group: UT = 4 (64 users) for D <= 1024, UT = 2 (32 users) above: 128 KB of LDS at D = 1024 and at D = 2048, one workgroup of 8
+// waves per compute unit there.  The alternative, 32 users and two workgroups per CU, doubles the times the catalogue is read (once per
+// user group); the catalogue bytes are what this kernel waits for (2 KB per row against 64 x 1024 MACs at a matrix rate that finishes them
+// in a fraction of the load's time), so the larger group was chosen and the latency is covered by 8 waves with unrolled loads in flight.
+// Blocks of the same row range and different user groups are adjacent in the grid (the user group is the fast index), so the re-reads
+// of a row range run together and meet in the L2 / Infinity Cache.
+//   Diagonal mode (gt != NULL): "row" n is the virtual row of user n, catalogue row gt[n]; a workgroup visits the virtual rows of its own
+//   users only and stores the diagonal, ref[b] = s~_b,gt[b] -- the same instructions in the same order as the chunk pass runs for that
+//   pair, hence the same bits.
+constexpr int CC_WAVES = 8;
+constexpr int CC_RT = 2;
+constexpr int CC_ROWS = CC_WAVES * CC_RT * 16;          // catalogue rows per workgroup step
+constexpr int CC_ACCS = 16;                             // 16x16 accumulators of a wave: UT x CC_RT tiles x NC chains
+constexpr int CC_LDS_MAX = 128 * 1024;
+__host__ __device__ constexpr int cc_steps(int D) { return (D + 31) >> 5; }
+__host__ __device__ constexpr size_t cc_lds_bytes(int D, int ut) { return (size_t)cc_steps(D) * ut * 64 * 16; }
+static_assert(cc_lds_bytes(1024, 4) <= CC_LDS_MAX && cc_lds_bytes(2048, 2) <= CC_LDS_MAX, "the user group must fit the LDS budget");
+static_assert(UR_COARSE_USER_GROUP == 16 * 4, "the header documents the user group of D <= 1024");
+
+template <int UT>
+__global__ __launch_bounds__(CC_WAVES * 64) void catalog_scores_bf16_kernel(const bf16_t* __restrict__ user, const float* __restrict__ inv_u,
+                                                                           const bf16_t* __restrict__ cat, const float* __restrict__ inv_c,
+                                                                           float* __restrict__ scores, long ld, const long* __restrict__ gt,
+                                                                           float* __restrict__ ref, int B, long N, int D, long rows_per_block,
+                                                                           int ub) {
+  constexpr int NC = CC_ACCS / (UT * CC_RT);                       // chains of the K axis
+  static_assert(NC == 2 || NC == 4, "the epilogue adds two or four chains");
+  extern __shared__ __attribute__((aligned(16))) bf16_t cus[];     // [steps][UT][64 lanes][8]
+  const int S = cc_steps(D);
+  const int ug = blockIdx.x % ub;
+  const long rb = blockIdx.x / ub;
+  const int b0 = ug * 16 * UT;
+  const int nb = min(16 * UT, B - b0);
+  const int P = S * 4;                                             // 8-element pieces of a padded row
+  // 64 threads = 16 users x 4 consecutive pieces: 64-byte runs of a user's row in, 1024 contiguous bytes of LDS out
+  for (int i = threadIdx.x; i < 16 * UT * P; i += CC_WAVES * 64) {
+    const int ul = i & 15, p = (i >> 4) % P, ut = (i >> 4) / P;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (p * 8 < D) v = *reinterpret_cast<const uint4*>(user + (long)min(b0 + ut * 16 + ul, B - 1) * D + p * 8);
+    *reinterpret_cast<uint4*>(cus + ((((p >> 2) * UT + ut) * 64 + ul + 16 * (p & 3)) << 3)) = v;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, col = lane & 15, kq = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool diag = gt != nullptr;
+  const long r0 = diag ? (long)b0 : rb * rows_per_block;
+  const long r1 = diag ? (long)(b0 + nb) : min(N, r0 + rows_per_block);
+  const int S_full = D >> 5;
+  const bf16_t* ap = cus + (lane << 3);
+  for (long n0 = r0 + w * 16 * CC_RT; n0 < r1; n0 += CC_ROWS) {
+    const bf16_t* bp[CC_RT];                     // a row past the end is read as the last one and never stored
+    long crow[CC_RT];
+#pragma unroll
+    for (int r = 0; r < CC_RT; ++r) {
+      const long n = min(n0 + r * 16 + col, r1 - 1);
+      crow[r] = diag ? min(max(gt[n], 0L), N - 1) : n;
+      bp[r] = cat + crow[r] * D + 8 * kq;
+    }
+    f32x4 acc[NC][UT][CC_RT];
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+#pragma unroll
+      for (int t = 0; t < UT; ++t)
+#pragma unroll
+        for (int r = 0; r < CC_RT; ++r) acc[j][t][r] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // step s of chain j: PART = the K step that ends short (lanes past D bring zeros; the staged users are padded)
+    auto step = [&](int s, f32x4 (&c)[UT][CC_RT], bool part) {
+      const bool in = !part || 32 * s + 8 * kq < D;
+      bf16x8 b[CC_RT];
+#pragma unroll
+      for (int r = 0; r < CC_RT; ++r) {
+        b[r] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (in) b[r] = *reinterpret_cast<const bf16x8*>(bp[r] + 32 * s);
+      }
+#pragma unroll
+      for (int t = 0; t < UT; ++t) {
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(ap + ((s * UT + t) << 9));
+#pragma unroll
+        for (int r = 0; r < CC_RT; ++r) c[t][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[r], c[t][r], 0, 0, 0);
+      }
+    };
+    int s0 = 0;
+    for (; s0 + NC <= S_full; s0 += NC) {
+#pragma unroll
+      for (int j = 0; j < NC; ++j) step(s0 + j, acc[j], false);
+    }
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {               // the last, incomplete round: step s still goes to chain s % NC (wave-uniform conditions)
+      if (s0 + j < S_full) step(s0 + j, acc[j], false);
+      else if (s0 + j == S_full && S_full < S) step(s0 + j, acc[j], true);
+    }
+#pragma unroll
+    for (int t = 0; t < UT; ++t)
+#pragma unroll
+      for (int r = 0; r < CC_RT; ++r) {
+        if (NC == 2) acc[0][t][r] = acc[0][t][r] + acc[1][t][r];
+        else acc[0][t][r] = (acc[0][t][r] + acc[2 % NC][t][r]) + (acc[1][t][r] + acc[3 % NC][t][r]);
+      }
+#pragma unroll
+    for (int r = 0; r < CC_RT; ++r) {
+      const long n = n0 + r * 16 + col;          // C/D layout: column = lane & 15 (row of the catalogue), row = 4 (lane >> 4) + reg (user)
+      if (n < r1) {
+        const float ic = inv_c[crow[r]];
+#pragma unroll
+        for (int t = 0; t < UT; ++t)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int u = t * 16 + kq * 4 + e;
+            if (u < nb) {
+              const float v = acc[0][t][r][e] * inv_u[b0 + u] * ic;
+              if (!diag) scores[(long)(b0 + u) * ld + n] = v;
+              else if ((long)(b0 + u) == n) ref[n] = v;
+            }
+          }
+      }
+    }
+  }
+}
+
+// ---- the exact re-rank ------------------------------------------------------------------------------------------------------------
+// One workgroup = 4 waves per user.  Wave w scores the slots w, w + 4, ..: catalog_scores_kernel's dot product on (user b, row
+// index[b][slot]) -- the same lane -> element map, the same fmaf chain, the same wave_sum and the same two multiplies, as
+// catalog_gt_score_kernel does for one row per user -- so the score has the bits that kernel writes for the pair.  An index outside
+// [0, N) is an empty slot (-inf, SEL_EMPTY).  Then a bitonic sort of the 128 slots under the total order of the lists; the first k leave.
+constexpr int RR_SLOTS = UR_CATALOG_TOPK_MAX;
+static_assert((RR_SLOTS & (RR_SLOTS - 1)) == 0 && RR_SLOTS <= 256, "the sort takes a power of two, one pair per thread at most");
+template <typename CT>
+__global__ __launch_bounds__(256) void catalog_rerank_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
+                                                             const CT* __restrict__ cat, const float* __restrict__ inv_c,
+                                                             const int* __restrict__ index, int K_in, int k, int* __restrict__ topk_index,
+                                                             float* __restrict__ topk_score, long N, int D) {
+  __shared__ float ks[RR_SLOTS];
+  __shared__ int ki[RR_SLOTS];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const float* up = user + (long)b * D;
+  const float iu = inv_u[b];
+  for (int slot = wave; slot < RR_SLOTS; slot += 4) {
+    float s = -__builtin_inff();
+    int id = SEL_EMPTY;
+    const int g = slot < K_in ? index[(long)b * K_in + slot] : -1;       // (wave-uniform)
+    if (g >= 0 && (long)g < N) {
+      const CT* cp = cat + (long)g * D;
+      float acc = 0.f;
+      for (int d = lane * 4; d < D; d += 256) {
+        const float4 c = load4(cp + d);
+        const float4 x = *reinterpret_cast<const float4*>(up + d);
+        acc = fmaf(c.x, x.x, fmaf(c.y, x.y, fmaf(c.z, x.z, fmaf(c.w, x.w, acc))));
+      }
+      const float ic = inv_c[g];
+      s = wave_sum(acc) * iu * ic;
+      id = g;
+    }
+    if (lane == 0) { ks[slot] = s; ki[slot] = id; }
+  }
+  __syncthreads();
+  for (int kk = 2; kk <= RR_SLOTS; kk <<= 1) {
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      const int i = tid, q = i ^ j;
+      if (i < RR_SLOTS && q > i) {
+        const float si = ks[i], sq = ks[q];
+        const int ii = ki[i], iq = ki[q];
+        const bool up_ = (i & kk) == 0;                                 // this pair ends in list order (best first)
+        if (up_ ? sel_before(sq, iq, si, ii) : sel_before(si, ii, sq, iq)) { ks[i] = sq; ki[i] = iq; ks[q] = si; ki[q] = ii; }
+      }
+      __syncthreads();
+    }
+  }
+  if (tid < k) {
+    topk_score[(long)b * k + tid] = ks[tid];
+    topk_index[(long)b * k + tid] = ki[tid] == SEL_EMPTY ? -1 : ki[tid];
+  }
+}
+
+// one launch of the coarse scorer: rows [0,N) of `cat` / `inv_c` into scores [B][ld], or (gt != NULL) the diagonal into ref [B]
+int launch_catalog_scores_bf16(const bf16_t* user, const float* inv_u, const bf16_t* cat, const float* inv_c, float* scores, long ld,
+                               const long* gt, float* ref, int32_t B, int64_t N, int32_t D, hipStream_t st) {
+  const bool wide = D > 1024;
+  const int ut = wide ? 2 : 4;
+  const int ub = ur_cdiv(B, 16 * ut);
+  long blocks_x = 1, rpb = N;
+  if (!gt) {
+    blocks_x = 512 / ub;                                        // ~2 rounds of one workgroup per CU; a workgroup stages its users once
+    if (blocks_x < 1) blocks_x = 1;
+    rpb = (N + blocks_x - 1) / blocks_x;
+    rpb = (rpb + CC_ROWS - 1) / CC_ROWS * CC_ROWS;
+    blocks_x = (N + rpb - 1) / rpb;
+  }
+  void (*kernel)(const bf16_t*, const float*, const bf16_t*, const float*, float*, long, const long*, float*, int, long, int, long, int) =
+      wide ? catalog_scores_bf16_kernel<2> : catalog_scores_bf16_kernel<4>;
+  static std::atomic<uint64_t> attr_set[2];   // per device, one per kernel
+  UR_ONCE_PER_DEVICE(attr_set[wide]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CC_LDS_MAX);
+    if (e != hipSuccess) UR_FAIL((int)e, "ur_catalog_coarse_select: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks_x * ub)), dim3(CC_WAVES * 64), cc_lds_bytes(D, ut), st, user, inv_u, cat, inv_c, scores, ld,
+                     gt, ref, (int)B, (long)N, (int)D, rpb, ub);
+  UR_CHECK_LAUNCH("ur_catalog_coarse_select");
+  return 0;
+}
+
+// the workspace of ur_catalog_coarse_select: u~ [B][D] bf16 | iu~ [B] | ref [B] | chunk [B][rows] f32
+struct coarse_plan {
+  int64_t rows, user_bytes, vec_bytes, chunk_bytes, need;
+};
+coarse_plan coarse_layout(int32_t B, int64_t N, int32_t D, int64_t chunk_rows) {
+  coarse_plan p;
+  p.rows = catalog_chunk_rows(chunk_rows, B, N);
+  p.user_bytes = ((int64_t)B * D * 2 + 15) / 16 * 16;
+  p.vec_bytes = ((int64_t)B * 4 + 15) / 16 * 16;
+  p.chunk_bytes = ((int64_t)B * p.rows * 4 + 15) / 16 * 16;
+  p.need = p.user_bytes + 2 * p.vec_bytes + p.chunk_bytes;
+  if (p.need < 16) p.need = 16;
+  return p;
+}
+
+}  // namespace
+
+extern "C" int ur_catalog_coarse_select(ur_catalog_coarse_t* a, void* stream) {
+  UR_REQUIRE(a, "ur_catalog_coarse_select: null argument struct");
+  const int32_t B = a->B, D = a->D, K = a->K, E = a->E;
+  const int64_t N = a->N;
+  UR_REQUIRE(B >= 0, "ur_catalog_coarse_select: need B >= 0 (got %d)", B);
+  UR_REQUIRE(N >= 0 && N <= (int64_t)INT32_MAX, "ur_catalog_coarse_select: need 0 <= N <= INT32_MAX (got %lld)", (long long)N);
+  UR_REQUIRE(D > 0 && (D % 8) == 0 && D <= 2048, "ur_catalog_coarse_select: D must be a positive multiple of 8 and <= 2048 (got %d)", D);
+  UR_REQUIRE(K >= 1 && K <= UR_CATALOG_TOPK_MAX, "ur_catalog_coarse_select: K must be 1 .. %d (got %d)", UR_CATALOG_TOPK_MAX, K);
+  UR_REQUIRE(a->chunk_rows >= 0 && (a->chunk_rows % SEL_TILE) == 0,
+             "ur_catalog_coarse_select: chunk_rows must be 0 or a positive multiple of %d (got %lld)", SEL_TILE, (long long)a->chunk_rows);
+  UR_REQUIRE(E >= 0 && (E == 0 || a->exclude), "ur_catalog_coarse_select: E > 0 needs exclude");
+  UR_REQUIRE((a->gt_index != nullptr) == (a->rank != nullptr), "ur_catalog_coarse_select: gt_index and rank go together");
+  UR_REQUIRE(a->catalog_bf16 == 1, "ur_catalog_coarse_select: catalog_bf16 must be 1, the coarse scorer reads a bf16 catalogue only (got %d)",
+             a->catalog_bf16);
+  const coarse_plan p = coarse_layout(B, N, D, a->chunk_rows);
+  if (!a->workspace) {
+    a->workspace_bytes = p.need;
+    return 0;
+  }
+  UR_REQUIRE(UR_ALIGNED16(a->workspace) && a->workspace_bytes >= p.need,
+             "ur_catalog_coarse_select: workspace must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)p.need,
+             (long long)a->workspace_bytes);
+  if (B == 0) return 0;
+  UR_REQUIRE(a->topk_index && a->topk_score, "ur_catalog_coarse_select: topk_index / topk_score are null");
+  UR_REQUIRE(a->user && (N == 0 || (a->catalog && a->cat_inv_norm)), "ur_catalog_coarse_select: user / catalog / cat_inv_norm: null pointer");
+  UR_REQUIRE(UR_ALIGNED16(a->user) && UR_ALIGNED16(a->catalog), "ur_catalog_coarse_select: user and catalog must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)a->workspace;
+  bf16_t* ubf = (bf16_t*)ws;
+  float* inv_u = (float*)(ws + p.user_bytes);
+  float* ref = (float*)(ws + p.user_bytes + p.vec_bytes);
+  float* chunk = (float*)(ws + p.user_bytes + 2 * p.vec_bytes);
+  const bf16_t* cat = (const bf16_t*)a->catalog;
+  const long* gt = (const long*)a->gt_index;
+  int rc = ur_cast_f32_to_bf16(a->user, ubf, (int64_t)B * D, stream);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(row_inv_norm_kernel<bf16_t>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, (const bf16_t*)ubf, inv_u, (long)B, (int)D);
+  if (!a->cat_norm_ready && N > 0)
+    hipLaunchKernelGGL(row_inv_norm_kernel<bf16_t>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, cat, a->cat_inv_norm, (long)N, (int)D);
+  UR_CHECK_LAUNCH("ur_catalog_coarse_select");
+  if (gt && N > 0) {
+    rc = launch_catalog_scores_bf16(ubf, inv_u, cat, a->cat_inv_norm, nullptr, 0, gt, ref, B, N, D, st);
+    if (rc != 0) return rc;
+  }
+  int64_t c0 = 0;
+  do {                                                         // (N == 0: one pass over an empty chunk writes the empty lists)
+    const int64_t len = N - c0 < p.rows ? N - c0 : p.rows;
+    if (len > 0) {
+      rc = launch_catalog_scores_bf16(ubf, inv_u, cat + c0 * D, a->cat_inv_norm + c0, chunk, (long)len, nullptr, nullptr, B, len, D, st);
+      if (rc != 0) return rc;
+    }
+    hipLaunchKernelGGL(catalog_select_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0, (int)len, (int)K,
+                       a->topk_score, a->topk_index, gt, (const float*)ref, a->rank, (const long*)a->exclude, (int)E, (int)(c0 == 0));
+    UR_CHECK_LAUNCH("ur_catalog_coarse_select");
+    c0 += p.rows;
+  } while (c0 < N);
+  return 0;
+}
+
+extern "C" int ur_catalog_rerank(ur_catalog_rerank_t* a, void* stream) {
+  UR_REQUIRE(a, "ur_catalog_rerank: null argument struct");
+  const int32_t B = a->B, D = a->D;
+  const int64_t N = a->N;
+  UR_REQUIRE(B >= 0, "ur_catalog_rerank: need B >= 0 (got %d)", B);
+  UR_REQUIRE(N >= 1 && N <= (int64_t)INT32_MAX, "ur_catalog_rerank: need 1 <= N <= INT32_MAX (got %lld)", (long long)N);
+  UR_REQUIRE(a->catalog_bf16 == 0 || a->catalog_bf16 == 1, "ur_catalog_rerank: catalog_bf16 must be 0 or 1 (got %d)", a->catalog_bf16);
+  const bool bf16 = a->catalog_bf16 == 1;
+  UR_REQUIRE(D > 0 && (D % (bf16 ? 8 : 4)) == 0 && D <= 2048,
+             "ur_catalog_rerank: D must be a positive multiple of %d and <= 2048 (got %d)", bf16 ? 8 : 4, D);
+  UR_REQUIRE(a->K_in >= 1 && a->K_in <= UR_CATALOG_TOPK_MAX, "ur_catalog_rerank: K_in must be 1 .. %d (got %d)", UR_CATALOG_TOPK_MAX, a->K_in);
+  UR_REQUIRE(a->k >= 1 && a->k <= a->K_in, "ur_catalog_rerank: k must be 1 .. K_in = %d (got %d)", a->K_in, a->k);
+  int64_t need = ((int64_t)B * 4 + 15) / 16 * 16;
+  if (need < 16) need = 16;
+  if (!a->workspace) {
+    a->workspace_bytes = need;
+    return 0;
+  }
+  UR_REQUIRE(UR_ALIGNED16(a->workspace) && a->workspace_bytes >= need,
+             "ur_catalog_rerank: workspace must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)need, (long long)a->workspace_bytes);
+  if (B == 0) return 0;
+  UR_REQUIRE(a->index && a->topk_index && a->topk_score, "ur_catalog_rerank: index / topk_index / topk_score are null");
+  UR_REQUIRE(a->user && a->catalog && a->cat_inv_norm, "ur_catalog_rerank: user / catalog / cat_inv_norm: null pointer");
+  UR_REQUIRE(UR_ALIGNED16(a->user) && UR_ALIGNED16(a->catalog), "ur_catalog_rerank: user and catalog must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  float* inv_u = (float*)a->workspace;
+  hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a->user, inv_u, (long)B, (int)D);
+  if (bf16) {
+    if (!a->cat_norm_ready)
+      hipLaunchKernelGGL(row_inv_norm_kernel<bf16_t>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const bf16_t*)a->catalog, a->cat_inv_norm, (long)N, (int)D);
+    hipLaunchKernelGGL(catalog_rerank_kernel<bf16_t>, dim3((unsigned)B), dim3(256), 0, st, a->user, (const float*)inv_u, (const bf16_t*)a->catalog,
+                       (const float*)a->cat_inv_norm, a->index, (int)a->K_in, (int)a->k, a->topk_index, a->topk_score, (long)N, (int)D);
+  } else {
+    if (!a->cat_norm_ready)
+      hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const float*)a->catalog, a->cat_inv_norm, (long)N, (int)D);
+    hipLaunchKernelGGL(catalog_rerank_kernel<float>, dim3((unsigned)B), dim3(256), 0, st, a->user, (const float*)inv_u, (const float*)a->catalog,
+                       (const float*)a->cat_inv_norm, a->index, (int)a->K_in, (int)a->k, a->topk_index, a->topk_score, (long)N, (int)D);
+  }
+  UR_CHECK_LAUNCH("ur_catalog_rerank");
+  return 0;
+}

@@ -183,24 +183,46 @@ class CatalogEvaluator:
         return {"rank": rank, "mrr": float((1.0 / rank.to(torch.float64)).mean().item()),
                 "hit_at_k": float((rank <= k).to(torch.float64).mean().item()), "topk_index": idx, "topk_score": val}
 
-    def retrieve(self, user_embeddings, k=10, gt_index=None, exclude=None, ks=None, chunk_rows=None, scorer=None):
+    def retrieve(self, user_embeddings, k=10, gt_index=None, exclude=None, ks=None, chunk_rows=None, scorer=None, shortlist=None):
         """Catalogue-scale retrieval: the scores are streamed in chunks and never held as [B,N].
         exclude: items each user has already seen (ragged lists or an int64 [B,E] tensor padded with -1, see pack_exclude); they leave
         the lists and the ranks, except a user's own gt_index.
         -> dict(topk_index int32 [B,k], topk_score f32 [B,k]); with gt_index also rank int32 [B], mrr, and hit_at / ndcg_at:
         dicts keyed by each K of ks (default (k,); any K, the metrics need only the rank).  Same scores, tie rule and rank rule as
-        evaluate().  scorer: None (the library's choice), "vector" or "mfma": which kernel scores the chunks; the results are the same bits."""
+        evaluate().  scorer: None (the library's choice), "vector" or "mfma": which kernel scores the chunks; the results are the same bits.
+        shortlist: None (the path above), or an int in [k, 128] for the two-stage path on a bf16 catalogue: ``hip.catalog_coarse_select``
+        picks `shortlist` items per user under the coarse bf16-MFMA scores and ``hip.catalog_rerank`` scores those exactly and returns the
+        best k.  topk_score then holds the exact scorer's bits for the returned items and the order is the exact one; the list equals the
+        exact list wherever the exact k-th and (shortlist + 1)-th scores lie further apart than the coarse error (2^-7 covers it).  rank
+        and the metrics come from the COARSE scores and the dict carries rank_is_coarse=True.  `scorer` must stay None."""
         hip.catalog_scorer_id(scorer)
+        if shortlist is not None:
+            if scorer is not None:
+                raise ValueError(f"retrieve: scorer={scorer!r} chooses between the exact scorers; with shortlist the coarse pass has one kernel, "
+                                 "leave scorer=None")
+            if self.catalog.dtype != torch.bfloat16:
+                raise ValueError("retrieve: shortlist needs a bf16 catalogue (CatalogEvaluator(dtype=torch.bfloat16)), this one is "
+                                 f"{self.catalog.dtype}")
+            if isinstance(shortlist, bool) or not isinstance(shortlist, int) or isinstance(k, bool) or not isinstance(k, int) or \
+                    not 1 <= k <= shortlist <= hip.CATALOG_TOPK_MAX:
+                raise ValueError(f"retrieve: shortlist must be an int in [k, {hip.CATALOG_TOPK_MAX}] (k = {k!r}), got {shortlist!r}")
         u = user_embeddings.detach().to(self.catalog.device, F32).contiguous()
         ex = pack_exclude(exclude, u.shape[0])
         if ex is not None:
             ex = ex.to(u.device)
         gt = None if gt_index is None else torch.as_tensor(gt_index).to(u.device, torch.int64)
-        idx, val, rank, self._inv = hip.catalog_select(u, self.catalog, k, self._inv, gt_index=gt, exclude=ex, chunk_rows=chunk_rows,
-                                                        scorer=scorer)
+        if shortlist is not None:
+            short, _, rank, self._inv = hip.catalog_coarse_select(u, self.catalog, shortlist, self._inv, gt_index=gt, exclude=ex,
+                                                                  chunk_rows=chunk_rows)
+            idx, val, _ = hip.catalog_rerank(u, self.catalog, short, k, self._inv)
+        else:
+            idx, val, rank, self._inv = hip.catalog_select(u, self.catalog, k, self._inv, gt_index=gt, exclude=ex, chunk_rows=chunk_rows,
+                                                            scorer=scorer)
         out = {"topk_index": idx, "topk_score": val}
         if rank is not None:
             ks = (k,) if ks is None else tuple(int(x) for x in ks)
             m = ranking_metrics(rank, ks).cpu().tolist()                                 # the one host read
             out.update(rank=rank, mrr=m[0], hit_at=dict(zip(ks, m[1:1 + len(ks)])), ndcg_at=dict(zip(ks, m[1 + len(ks):])))
+            if shortlist is not None:
+                out["rank_is_coarse"] = True
         return out

@@ -1363,6 +1363,99 @@ def catalog_select(user, catalog, K, cat_inv_norm=None, gt_index=None, exclude=N
     return idx, val, rank, cat_inv_norm
 
 
+COARSE_USER_GROUP = _lib.COARSE_USER_GROUP      # users a workgroup of the coarse scorer stages (half of it when D > 1024)
+
+
+def _catalog_norm(cat_inv_norm, N, dev, who):
+    ready = cat_inv_norm is not None
+    if not ready:
+        return torch.empty((N,), dtype=F32, device=dev), 0
+    _need(cat_inv_norm, F32, "cat_inv_norm")
+    if cat_inv_norm.shape != (N,):
+        raise ValueError(f"{who}: cat_inv_norm must have shape [{N}], got {tuple(cat_inv_norm.shape)}")
+    return cat_inv_norm, 1
+
+
+def catalog_coarse_select(user, catalog, K, cat_inv_norm=None, gt_index=None, exclude=None, chunk_rows=None):
+    """The APPROXIMATE shortlist pass over a bf16 catalogue [N,D] (ur_catalog_coarse_select, include/unirec_hip_coarse.h): catalog_select
+    with the chunks scored on the bf16 matrix cores.  The coarse score of (b, n) is the cosine of user b ROUNDED to bf16 with row n, summed
+    in f32 by v_mfma_f32_16x16x32_bf16 -- what catalog_select(user.bfloat16().float(), catalog) computes in f32 chains, up to the order of
+    the sum.  Lists (K <= 128), total order, gt_index / rank, exclude, chunk_rows and the (-1, -inf) tail are catalog_select's; the scores
+    and the rank are coarse ones.  D must be a multiple of 8 and the catalogue bf16 (``CatalogEvaluator(dtype=torch.bfloat16)``).
+    Returns (topk_index int32 [B,K], topk_score f32 [B,K], rank int32 [B] or None, cat_inv_norm)."""
+    if catalog.dtype != BF16:
+        raise ValueError(f"catalog_coarse_select: the coarse scorer reads a bf16 catalogue (CatalogEvaluator(dtype=torch.bfloat16)), got {catalog.dtype}")
+    lib = _lib.load()
+    _need(user, F32, "user")
+    _need(catalog, BF16, "catalog")
+    if user.dim() != 2 or catalog.dim() != 2 or catalog.shape[1] != user.shape[1]:
+        raise ValueError(f"catalog_coarse_select: user [B,D] and catalog [N,D] must share D, got {tuple(user.shape)} and {tuple(catalog.shape)}")
+    B, D = user.shape
+    N = catalog.shape[0]
+    dev = user.device
+    a = _lib.CatalogCoarse()
+    a.user, a.catalog, a.catalog_bf16 = user.data_ptr(), catalog.data_ptr(), 1
+    a.B, a.N, a.D, a.K, a.chunk_rows = B, N, D, int(K), int(chunk_rows or 0)
+    idx = torch.empty((B, max(int(K), 0)), dtype=torch.int32, device=dev)
+    val = torch.empty((B, max(int(K), 0)), dtype=F32, device=dev)
+    a.topk_index, a.topk_score = idx.data_ptr(), val.data_ptr()
+    rank = gt = None
+    if gt_index is not None:
+        gt = gt_index.to(device=dev, dtype=torch.int64).contiguous()
+        if gt.shape != (B,):
+            raise ValueError(f"catalog_coarse_select: gt_index must have shape [{B}], got {tuple(gt.shape)}")
+        rank = torch.empty((B,), dtype=torch.int32, device=dev)
+        a.gt_index, a.rank = gt.data_ptr(), rank.data_ptr()
+    if exclude is not None:
+        _need(exclude, torch.int64, "exclude")
+        if exclude.dim() != 2 or exclude.shape[0] != B:
+            raise ValueError(f"catalog_coarse_select: exclude must be [{B}, E], got {tuple(exclude.shape)}")
+        a.E = exclude.shape[1]
+        a.exclude = exclude.data_ptr() if a.E else None
+    cat_inv_norm, a.cat_norm_ready = _catalog_norm(cat_inv_norm, N, dev, "catalog_coarse_select")
+    a.cat_inv_norm = cat_inv_norm.data_ptr()
+    check(lib.ur_catalog_coarse_select(ctypes.byref(a), _stream()), "ur_catalog_coarse_select")        # size query: workspace is NULL
+    ws = workspace(a.workspace_bytes, dev, "catalog_coarse")
+    a.workspace = ws.data_ptr()
+    check(lib.ur_catalog_coarse_select(ctypes.byref(a), _stream()), "ur_catalog_coarse_select")
+    return idx, val, rank, cat_inv_norm
+
+
+def catalog_rerank(user, catalog, index, k=None, cat_inv_norm=None):
+    """The EXACT scores of a shortlist (ur_catalog_rerank): index int32 [B,K'] into catalog [N,D] f32 or bf16, an entry outside [0,N)
+    (-1) an empty slot.  Every pair is scored by catalog_scores' own f32 chain -- the bits catalog_scores / catalog_select give for it --
+    and each row is sorted under their total order (score descending, index ascending); the first k (default K') are returned, empty
+    slots at the tail as (-1, -inf).  Returns (topk_index int32 [B,k], topk_score f32 [B,k], cat_inv_norm)."""
+    if catalog.dtype not in (F32, BF16):
+        raise ValueError(f"catalog_rerank: catalog must be f32 or bf16, got {catalog.dtype}")
+    lib = _lib.load()
+    _need(user, F32, "user")
+    _need(catalog, catalog.dtype, "catalog")
+    _need(index, torch.int32, "index")
+    if user.dim() != 2 or catalog.dim() != 2 or catalog.shape[1] != user.shape[1]:
+        raise ValueError(f"catalog_rerank: user [B,D] and catalog [N,D] must share D, got {tuple(user.shape)} and {tuple(catalog.shape)}")
+    B, D = user.shape
+    N = catalog.shape[0]
+    if index.dim() != 2 or index.shape[0] != B:
+        raise ValueError(f"catalog_rerank: index must be [{B}, K'], got {tuple(index.shape)}")
+    dev = user.device
+    a = _lib.CatalogRerank()
+    a.user, a.catalog, a.catalog_bf16 = user.data_ptr(), catalog.data_ptr(), int(catalog.dtype == BF16)
+    a.B, a.N, a.D = B, N, D
+    a.index, a.K_in = index.data_ptr(), index.shape[1]
+    a.k = index.shape[1] if k is None else int(k)
+    idx = torch.empty((B, max(a.k, 0)), dtype=torch.int32, device=dev)
+    val = torch.empty((B, max(a.k, 0)), dtype=F32, device=dev)
+    a.topk_index, a.topk_score = idx.data_ptr(), val.data_ptr()
+    cat_inv_norm, a.cat_norm_ready = _catalog_norm(cat_inv_norm, N, dev, "catalog_rerank")
+    a.cat_inv_norm = cat_inv_norm.data_ptr()
+    check(lib.ur_catalog_rerank(ctypes.byref(a), _stream()), "ur_catalog_rerank")        # size query: workspace is NULL
+    ws = workspace(a.workspace_bytes, dev, "catalog_rerank")
+    a.workspace = ws.data_ptr()
+    check(lib.ur_catalog_rerank(ctypes.byref(a), _stream()), "ur_catalog_rerank")
+    return idx, val, cat_inv_norm
+
+
 def catalog_softmax(user, catalog, gt_index, temperature, cat_inv_norm=None, exclude=None, chunk_rows=None, scorer=None, grad_scale=1.0,
                     need_grad=True):
     """The softmax loss over the whole catalogue [N,D] f32 or bf16 (ur_catalog_softmax, include/unirec_hip_loss.h): cross-entropy of

@@ -507,6 +507,9 @@ class MultiModalTrainer:
             if negatives.num_random != 0 or negatives.num_hard != 0:
                 raise ValueError(f'loss="catalog_softmax" sums over the whole catalogue: negatives.num_random and negatives.num_hard must be 0 '
                                  f"(got {negatives.num_random} and {negatives.num_hard})")
+            if getattr(negatives, "coarse", False):
+                raise ValueError('loss="catalog_softmax" has no coarse form (its gradient would need its own definition): '
+                                 "negatives.coarse must be False")
             self.catalog_softmax_loss = CatalogSoftmaxLoss(negatives.evaluator, temperature, scorer=negatives.scorer,
                                                            chunk_rows=negatives.chunk_rows)
 

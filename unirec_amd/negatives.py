@@ -97,11 +97,19 @@ def assemble_candidates(positive_index, explicit_index=None, explicit_mask=None,
 class CatalogCandidates:
     """Positives and negatives of a joint training step as indices into a resident catalogue (``JointTrainer(negatives=...)``)."""
 
-    def __init__(self, catalog, num_random=0, num_hard=0, hard_skip=0, seed=0, scorer=None):
+    def __init__(self, catalog, num_random=0, num_hard=0, hard_skip=0, seed=0, scorer=None, coarse=False):
         """catalog: a CatalogEvaluator, or an [N,D] f32 / bf16 tensor (wrapped in one where it lies, so the catalogue norms that mining
         needs are computed once).  num_random uniformly sampled negatives per user (``sample``), num_hard mined ones (``mine``) after the
-        hard_skip best-scoring items; hard_skip + num_hard <= hip.CATALOG_TOPK_MAX.  scorer: as for CatalogEvaluator.retrieve."""
+        hard_skip best-scoring items; hard_skip + num_hard <= hip.CATALOG_TOPK_MAX.  scorer: as for CatalogEvaluator.retrieve.
+        coarse=True (a bf16 catalogue, scorer=None): ``mine`` runs ``hip.catalog_coarse_select`` -- the bf16-MFMA scores of the users
+        rounded to bf16 -- with no re-rank: the mined rows are scored exactly by the InfoNCE kernels anyway, so the coarse scores only
+        decide which near-boundary items are mined."""
         hip.catalog_scorer_id(scorer)
+        if not isinstance(coarse, bool):
+            raise ValueError(f"CatalogCandidates: coarse must be True or False, got {coarse!r}")
+        if coarse and scorer is not None:
+            raise ValueError(f"CatalogCandidates: coarse=True has one scoring kernel; scorer must be None, got {scorer!r}")
+        self.coarse = coarse
         self.num_random, self.num_hard, self.hard_skip, self.seed, self.scorer = int(num_random), int(num_hard), int(hard_skip), int(seed), scorer
         if self.num_random < 0 or self.num_hard < 0 or self.hard_skip < 0:
             raise ValueError("CatalogCandidates: num_random, num_hard and hard_skip must be >= 0")
@@ -113,6 +121,8 @@ class CatalogCandidates:
             if catalog.dim() != 2 or catalog.dtype not in (F32, BF16):
                 raise ValueError("CatalogCandidates: catalog must be a CatalogEvaluator or an [N, D] f32 / bf16 tensor")
             catalog = CatalogEvaluator(catalog, device=catalog.device, dtype=catalog.dtype)
+        if coarse and catalog.catalog.dtype != BF16:
+            raise ValueError(f"CatalogCandidates: coarse=True needs a bf16 catalogue (CatalogEvaluator(dtype=torch.bfloat16)), got {catalog.catalog.dtype}")
         self.evaluator = catalog
         self.chunk_rows = None          # catalogue rows scored per chunk when mining (a multiple of 1024); None = the library's choice
         self.last_index = self.last_mask = None
@@ -136,7 +146,10 @@ class CatalogCandidates:
         with torch.no_grad():
             u = user.detach().to(ev.catalog.device, F32).contiguous()
             gt = torch.as_tensor(gt_index).to(u.device, torch.int64)
-            idx, _, _, ev._inv = hip.catalog_select(u, ev.catalog, K, ev._inv, gt_index=gt, exclude=ex, chunk_rows=self.chunk_rows, scorer=self.scorer)
+            if self.coarse:
+                idx, _, _, ev._inv = hip.catalog_coarse_select(u, ev.catalog, K, ev._inv, gt_index=gt, exclude=ex, chunk_rows=self.chunk_rows)
+            else:
+                idx, _, _, ev._inv = hip.catalog_select(u, ev.catalog, K, ev._inv, gt_index=gt, exclude=ex, chunk_rows=self.chunk_rows, scorer=self.scorer)
             idx = idx[:, self.hard_skip:].to(torch.int64)
             return torch.where(idx == gt[:, None], torch.full_like(idx, -1), idx)
 
