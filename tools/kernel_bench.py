@@ -4,6 +4,7 @@ shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
     python tools/kernel_bench.py attn|gemm|lora [--B 8] [--iters 5]
     python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 [--D 1024] [--rounds 3] [--chunks]
     python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 --scorer vector mfma --catalog-dtype bf16
+    python tools/kernel_bench.py catalog --K 1000 --dtypes f32 bf16 --users 512 64 [--N 1000000] [--D 1024] [--rounds 5] [--segments 1 4 16]
     python tools/kernel_bench.py catalog --shortlist 128 --catalog-dtype bf16 [--N 1000000] [--D 1024] [--rounds 3]
     python tools/kernel_bench.py negatives --B 64 --P 1000 --N 1000000 --K 128 [--catalog-dtype f32|bf16] [--rounds 3]
     python tools/kernel_bench.py catalog_softmax --users 64 512 --dtypes f32 bf16 --N 1000000 [--D 1024] [--rounds 5]
@@ -267,6 +268,8 @@ def catalog(args):
     from unirec_amd.evaluation import CatalogEvaluator
     if args.shortlist:
         return catalog_shortlist(args)
+    if args.K > hip.CATALOG_TOPK_MAX:
+        return catalog_deep(args)
     B, N, K, D = args.B, args.N, args.K, args.D
     bf16 = args.catalog_dtype == "bf16"
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -318,6 +321,70 @@ def catalog(args):
         t = sorted(times[name])
         print(f"{name:44s}: median {t[len(t) // 2]:9.2f} ms  min {t[0]:9.2f}  max {t[-1]:9.2f}  (spread {t[-1] - t[0]:.2f} over {len(t)} alternating rounds)"
               f"  peak allocation {peaks[name] / 2**20:9.2f} MiB")
+
+
+def catalog_deep(args):
+    """Long lists (--K above 128, hip.catalog_deep_select) beside the existing call at K = 128, per catalogue dtype (--dtypes, default
+    --catalog-dtype) and user count (--users, default 512 and 64), alternating --rounds times in this process after one call of each:
+      (a) retrieve(k=128), the existing selection kernel;  (b) hip.catalog_deep_select at K = 128 (held equal to (a) in every bit);
+      (c) retrieve(k=--K);  and, with --segments, (c) with that many workgroups per user forced.
+    Wall time of the whole call ((a) and (c) end in a host read of the metrics), (c) / (a) and (b) / (a), the number of workgroups per user
+    the library chooses, the workspace its size query reports and the peak allocation of (c) against a [B,N] f32 matrix."""
+    import ctypes
+    from unirec_amd import _lib
+    from unirec_amd.evaluation import CatalogEvaluator
+    N, D, K = args.N, args.D, args.K
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    g = torch.Generator(device="cuda").manual_seed(0)
+    cat32 = torch.randn(N, D, generator=g, device="cuda")
+    for dtype in (args.dtypes or [args.catalog_dtype]):
+        ev = CatalogEvaluator(cat32, dtype=torch.bfloat16 if dtype == "bf16" else torch.float32)
+        for B in (args.users or [512, 64]):
+            user = torch.randn(B, D, generator=g, device="cuda")
+            gt = torch.randint(0, N, (B,), generator=g, device="cuda")
+            ev.retrieve(user[:1], k=1)                        # the catalogue norms: cached by every path, outside every figure below
+            rows = max(1024, min((64 << 20) // (4 * B) // 1024 * 1024, (N + 1023) // 1024 * 1024))
+            G = max(1, min(4 * cus // B, 1024 // B, 8, rows // 1024))          # deep_segments of unirec_amd/csrc/catalog_deep.hip.h
+            q = _lib.CatalogDeep()
+            q.B, q.N, q.D, q.K = B, N, D, K
+            _lib.check(_lib.load().ur_catalog_deep_select(ctypes.byref(q), None), "ur_catalog_deep_select")
+            variants = [("(a) retrieve(k=128)", lambda: ev.retrieve(user, k=128, gt_index=gt)),
+                        ("(b) catalog_deep_select K=128", lambda: hip.catalog_deep_select(user, ev.catalog, 128, ev._inv, gt_index=gt)),
+                        (f"(c) retrieve(k={K})", lambda: ev.retrieve(user, k=K, gt_index=gt))]
+            variants += [(f"    catalog_deep_select K={K} segments={s}", lambda s=s: hip.catalog_deep_select(user, ev.catalog, K, ev._inv, gt_index=gt, segments=s))
+                         for s in (args.segments or [])]
+            a_out, b_out = variants[0][1](), variants[1][1]()
+            same = torch.equal(b_out[0], a_out["topk_index"]) and torch.equal(b_out[1], a_out["topk_score"]) and torch.equal(b_out[2], a_out["rank"])
+            assert same, "catalog_deep_select at K = 128 differs from retrieve(k=128)"
+            hip._ws_cache.clear()
+            torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            c_out = variants[2][1]()
+            torch.cuda.synchronize()
+            peak = torch.cuda.max_memory_allocated() - base
+            assert torch.equal(c_out["topk_index"][:, :128], a_out["topk_index"]) and torch.equal(c_out["rank"], a_out["rank"])
+            for name, fn in variants:                         # scratch of every variant warm again
+                fn()
+            times = {name: [] for name, _ in variants}
+            for _ in range(args.rounds):
+                for name, fn in variants:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    times[name].append((time.perf_counter() - t0) * 1e3)
+            print(f"catalog deep: B={B} N={N} D={D} catalogue {dtype}, chunk_rows default = {rows}, {cus} CUs, workgroups per user G = {G}; "
+                  f"(b) equals (a) in every bit: {same}; the first 128 of (c) and its ranks equal (a)")
+            print(f"  workspace (size query, K={K}): {q.workspace_bytes / 2**20:.2f} MiB; peak allocation of (c): {peak / 2**20:.2f} MiB; "
+                  f"scores [B,N] f32: {B * N * 4 / 2**20:.0f} MiB")
+            med = {}
+            for name, _ in variants:
+                t = sorted(times[name])
+                med[name] = t[len(t) // 2]
+                print(f"  {name:44s}: median {med[name]:9.2f} ms  min {t[0]:9.2f}  max {t[-1]:9.2f}  (spread {t[-1] - t[0]:.2f} over {len(t)} alternating rounds)")
+            a, b, c = (v[0] for v in variants[:3])
+            print(f"  (c) / (a) = {med[c] / med[a]:.2f}  ((c) - (a) = {med[c] - med[a]:.2f} ms);  (b) / (a) = {med[b] / med[a]:.2f}")
+        del ev
 
 
 def catalog_shortlist(args):
@@ -631,6 +698,7 @@ if __name__ == "__main__":
     ap.add_argument("--chunks", action="store_true", help="catalog: also time retrieve() at half and double the default rows per chunk")
     ap.add_argument("--scorer", nargs="+", choices=["vector", "mfma"], help="catalog: time retrieve() with each of these scorers, alternating")
     ap.add_argument("--shortlist", type=int, default=0, help="catalog: time retrieve(shortlist=...) against the exact retrieve() at (512, 100) and (64, 10)")
+    ap.add_argument("--segments", type=int, nargs="+", help="catalog with --K above 128: also time the long-list call with each of these workgroup counts per user forced")
     ap.add_argument("--catalog-dtype", choices=["f32", "bf16"], default="f32", help="catalog: the dtype the catalogue is stored in")
     ap.add_argument("--users", type=int, nargs="+", help="catalog_softmax: the user counts to time (default: --B)")
     ap.add_argument("--dtypes", nargs="+", choices=["f32", "bf16"], help="catalog_softmax: the catalogue dtypes to time (default: --catalog-dtype)")

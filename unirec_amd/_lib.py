@@ -1,5 +1,6 @@
 """ctypes binding of libunirec_hip.so (the C ABI declared in include/unirec_hip.h, include/unirec_hip_loss.h,
-include/unirec_hip_adapter.h, include/unirec_hip_pool.h, include/unirec_hip_mrl.h and include/unirec_hip_coarse.h).
+include/unirec_hip_adapter.h, include/unirec_hip_pool.h, include/unirec_hip_mrl.h, include/unirec_hip_coarse.h and
+include/unirec_hip_deep.h).
 
 Fails loudly: there is no CPU / eager fallback for the product path.
 """
@@ -9,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -168,6 +169,22 @@ class CatalogRerank(ctypes.Structure):
                 ("workspace", c_void_p), ("workspace_bytes", c_i64)]
 
 
+CATALOG_DEEP_TOPK_MAX = 1024        # UR_CATALOG_DEEP_TOPK_MAX
+CATALOG_DEEP_SEGMENTS_MAX = 16      # UR_CATALOG_DEEP_SEGMENTS_MAX
+
+
+class CatalogDeep(ctypes.Structure):
+    """Mirror of ur_catalog_deep_t (include/unirec_hip_deep.h)."""
+    _fields_ = [("user", c_void_p), ("catalog", c_void_p), ("catalog_bf16", c_int), ("scorer", c_int),
+                ("cat_inv_norm", c_void_p), ("cat_norm_ready", c_int),
+                ("B", c_int), ("N", c_i64), ("D", c_int), ("K", c_int),
+                ("topk_index", c_void_p), ("topk_score", c_void_p),
+                ("gt_index", c_void_p), ("rank", c_void_p),
+                ("exclude", c_void_p), ("E", c_int),
+                ("chunk_rows", c_i64), ("segments", c_int),
+                ("workspace", c_void_p), ("workspace_bytes", c_i64)]
+
+
 class F32Range(ctypes.Structure):
     """Mirror of ur_f32_range."""
     _fields_ = [("ptr", c_void_p), ("n", c_i64)]
@@ -315,6 +332,12 @@ COARSE_SIGNATURES = {
     "ur_catalog_rerank": (c_int, [ctypes.POINTER(CatalogRerank), c_void_p]),
 }
 
+# the long-list retrieval family: every symbol include/unirec_hip_deep.h declares (tests/test_catalog_deep_host.py holds this table and
+# the struct mirror above to that header and to the built library)
+DEEP_SIGNATURES = {
+    "ur_catalog_deep_select": (c_int, [ctypes.POINTER(CatalogDeep), c_void_p]),
+}
+
 _lib = None
 
 
@@ -337,7 +360,7 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(ADAPTER_SIGNATURES.items()) + \
-            list(POOL_SIGNATURES.items()) + list(MRL_SIGNATURES.items()) + list(COARSE_SIGNATURES.items()):
+            list(POOL_SIGNATURES.items()) + list(MRL_SIGNATURES.items()) + list(COARSE_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -17,10 +17,14 @@
 //                       top-K list and a count of scores above the ground truth's, per-user exclusion lists filtered out.
 //                       Here the catalogue may be bf16 (widened exactly on load) and a chunk may be scored on the f32 matrix cores
 //                       (catalog_scores_mfma_kernel: the vector kernel's fmaf chains and sum tree, so the same score bits).
+//   ur_catalog_deep_select (include/unirec_hip_deep.h): the same streaming retrieval with lists of up to 1024 items.  The chunks are
+//                       scored by the launches of select mode; the selection kernels are those of catalog_deep.hip.h.
 #include "common.hip.h"
 #include "unirec_hip.h"
 #include "unirec_hip_loss.h"
+#include "unirec_hip_deep.h"
 #include "catalog_select.hip.h"
+#include "catalog_deep.hip.h"
 
 namespace {
 
@@ -728,6 +732,86 @@ extern "C" int ur_catalog_scores(const float* user, const float* catalog, float*
   if (bf16)
     return catalog_stream(user, (const bf16_t*)catalog, user_inv_norm, cat_inv_norm, cat_norm_ready, B, N, D, select, chunk_bytes, rows, mfma, st);
   return catalog_stream(user, catalog, user_inv_norm, cat_inv_norm, cat_norm_ready, B, N, D, select, chunk_bytes, rows, mfma, st);
+}
+
+// ---- ur_catalog_deep_select (include/unirec_hip_deep.h) --------------------------------------------------------------------------
+// the launches, after every check: select mode's norms, reference score and scoring launches; the deep selection kernels
+template <typename CT>
+static int catalog_deep_stream(const ur_catalog_deep_t* a, const CT* catalog, const deep_plan& p, bool mfma, hipStream_t st) {
+  const int32_t B = a->B, D = a->D, K = a->K, E = a->E;
+  const int64_t N = a->N;
+  char* ws = (char*)a->workspace;
+  float* chunk = (float*)ws;
+  float* ref = (float*)(ws + p.chunk_bytes);
+  float* inv_u = (float*)(ws + p.chunk_bytes + p.vec_bytes);
+  float* list_score = (float*)(ws + p.chunk_bytes + 2 * p.vec_bytes);
+  int* list_index = (int*)(ws + p.chunk_bytes + 2 * p.vec_bytes + p.list_bytes);
+  int* count = (int*)(ws + p.chunk_bytes + 2 * p.vec_bytes + 2 * p.list_bytes);
+  const long* gt = (const long*)a->gt_index;
+  const int G = deep_segments(a->segments, B, p.rows);             // <= p.gw, what the workspace holds
+  const int64_t tiles = p.rows / SEL_TILE;
+  const long seg_len = (long)((tiles + G - 1) / G) * SEL_TILE;
+  hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a->user, inv_u, (long)B, (int)D);
+  if (!a->cat_norm_ready && N > 0)
+    hipLaunchKernelGGL(row_inv_norm_kernel<CT>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, a->cat_inv_norm, (long)N, (int)D);
+  if (gt && N > 0)
+    hipLaunchKernelGGL(catalog_gt_score_kernel<CT>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a->user, (const float*)inv_u, catalog,
+                       (const float*)a->cat_inv_norm, gt, ref, (int)B, (long)N, (int)D);
+  UR_CHECK_LAUNCH("ur_catalog_deep_select");
+  int64_t c0 = 0;
+  do {                                                         // (N == 0: one pass over an empty chunk writes the empty lists)
+    const int64_t len = N - c0 < p.rows ? N - c0 : p.rows;
+    if (len > 0) {
+      const int rc = mfma ? launch_catalog_scores_mfma<CT>(a->user, inv_u, catalog + c0 * D, a->cat_inv_norm + c0, chunk, B, len, D, st)
+                          : launch_catalog_scores<CT>(a->user, inv_u, catalog + c0 * D, a->cat_inv_norm + c0, chunk, B, len, D, st);
+      if (rc != 0) return rc;
+    }
+    hipLaunchKernelGGL(catalog_deep_sweep_kernel, dim3((unsigned)((int64_t)B * G)), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0,
+                       (int)len, (int)K, G, seg_len, list_score, list_index, count, gt, (const float*)ref, (const long*)a->exclude, (int)E,
+                       (int)(c0 == 0));
+    UR_CHECK_LAUNCH("ur_catalog_deep_select");
+    c0 += p.rows;
+  } while (c0 < N);
+  hipLaunchKernelGGL(catalog_deep_merge_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)list_score, (const int*)list_index,
+                     (const int*)count, (int)K, G, a->topk_score, a->topk_index, a->rank);
+  UR_CHECK_LAUNCH("ur_catalog_deep_select");
+  return 0;
+}
+
+extern "C" int ur_catalog_deep_select(ur_catalog_deep_t* a, void* stream) {
+  UR_REQUIRE(a, "ur_catalog_deep_select: null argument struct");
+  const int32_t B = a->B, D = a->D, K = a->K, E = a->E;
+  const int64_t N = a->N;
+  UR_REQUIRE(B >= 0, "ur_catalog_deep_select: need B >= 0 (got %d)", B);
+  UR_REQUIRE(N >= 0 && N <= (int64_t)INT32_MAX, "ur_catalog_deep_select: need 0 <= N <= INT32_MAX (got %lld)", (long long)N);
+  UR_REQUIRE(D > 0 && (D % 4) == 0 && D <= 2048, "ur_catalog_deep_select: D must be a positive multiple of 4 and <= 2048 (got %d)", D);
+  UR_REQUIRE(K >= 1 && K <= UR_CATALOG_DEEP_TOPK_MAX, "ur_catalog_deep_select: K must be 1 .. %d (got %d)", UR_CATALOG_DEEP_TOPK_MAX, K);
+  UR_REQUIRE(a->chunk_rows >= 0 && (a->chunk_rows % SEL_TILE) == 0,
+             "ur_catalog_deep_select: chunk_rows must be 0 or a positive multiple of %d (got %lld)", SEL_TILE, (long long)a->chunk_rows);
+  UR_REQUIRE(E >= 0 && (E == 0 || a->exclude), "ur_catalog_deep_select: E > 0 needs exclude");
+  UR_REQUIRE((a->gt_index != nullptr) == (a->rank != nullptr), "ur_catalog_deep_select: gt_index and rank go together");
+  UR_REQUIRE(a->catalog_bf16 == 0 || a->catalog_bf16 == 1, "ur_catalog_deep_select: catalog_bf16 must be 0 or 1 (got %d)", a->catalog_bf16);
+  UR_REQUIRE(a->scorer >= 0 && a->scorer <= UR_CATALOG_SCORER_MFMA,
+             "ur_catalog_deep_select: scorer must be 0 (the library chooses), 1 (vector) or 2 (f32 MFMA) (got %d)", a->scorer);
+  UR_REQUIRE(a->segments >= 0 && a->segments <= UR_CATALOG_DEEP_SEGMENTS_MAX, "ur_catalog_deep_select: segments must be 0 .. %d (got %d)",
+             UR_CATALOG_DEEP_SEGMENTS_MAX, a->segments);
+  const deep_plan p = deep_layout(B, N, K, a->chunk_rows, a->segments);
+  if (!a->workspace) {
+    a->workspace_bytes = p.need;
+    return 0;
+  }
+  UR_REQUIRE(UR_ALIGNED16(a->workspace) && a->workspace_bytes >= p.need,
+             "ur_catalog_deep_select: workspace must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)p.need,
+             (long long)a->workspace_bytes);
+  if (B == 0) return 0;
+  UR_REQUIRE(a->topk_index && a->topk_score, "ur_catalog_deep_select: topk_index / topk_score are null");
+  UR_REQUIRE(a->user && (N == 0 || (a->catalog && a->cat_inv_norm)), "ur_catalog_deep_select: user / catalog / cat_inv_norm: null pointer");
+  UR_REQUIRE(UR_ALIGNED16(a->user) && UR_ALIGNED16(a->catalog), "ur_catalog_deep_select: user and catalog must be 16-byte aligned");
+  const bool bf16 = a->catalog_bf16 == 1;
+  const bool mfma = a->scorer == UR_CATALOG_SCORER_MFMA || (a->scorer == 0 && catalog_default_is_mfma(B, N, D, bf16));
+  hipStream_t st = (hipStream_t)stream;
+  if (bf16) return catalog_deep_stream(a, (const bf16_t*)a->catalog, p, mfma, st);
+  return catalog_deep_stream(a, (const float*)a->catalog, p, mfma, st);
 }
 
 // ---- ur_catalog_softmax (include/unirec_hip_loss.h) ------------------------------------------------------------------------------

@@ -189,13 +189,17 @@ class CatalogEvaluator:
         the lists and the ranks, except a user's own gt_index.
         -> dict(topk_index int32 [B,k], topk_score f32 [B,k]); with gt_index also rank int32 [B], mrr, and hit_at / ndcg_at:
         dicts keyed by each K of ks (default (k,); any K, the metrics need only the rank).  Same scores, tie rule and rank rule as
-        evaluate().  scorer: None (the library's choice), "vector" or "mfma": which kernel scores the chunks; the results are the same bits.
+        evaluate().  k: an int in [1, 1024]; up to 128 the lists come from ``hip.catalog_select``, longer ones from
+        ``hip.catalog_deep_select`` (the same scores, order and rank; a selection kernel built for long lists).
+        scorer: None (the library's choice), "vector" or "mfma": which kernel scores the chunks; the results are the same bits.
         shortlist: None (the path above), or an int in [k, 128] for the two-stage path on a bf16 catalogue: ``hip.catalog_coarse_select``
         picks `shortlist` items per user under the coarse bf16-MFMA scores and ``hip.catalog_rerank`` scores those exactly and returns the
         best k.  topk_score then holds the exact scorer's bits for the returned items and the order is the exact one; the list equals the
         exact list wherever the exact k-th and (shortlist + 1)-th scores lie further apart than the coarse error (2^-7 covers it).  rank
         and the metrics come from the COARSE scores and the dict carries rank_is_coarse=True.  `scorer` must stay None."""
         hip.catalog_scorer_id(scorer)
+        if shortlist is None and (isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= hip.CATALOG_DEEP_TOPK_MAX):
+            raise ValueError(f"retrieve: k must be an int in [1, {hip.CATALOG_DEEP_TOPK_MAX}], got {k!r}")
         if shortlist is not None:
             if scorer is not None:
                 raise ValueError(f"retrieve: scorer={scorer!r} chooses between the exact scorers; with shortlist the coarse pass has one kernel, "
@@ -215,9 +219,12 @@ class CatalogEvaluator:
             short, _, rank, self._inv = hip.catalog_coarse_select(u, self.catalog, shortlist, self._inv, gt_index=gt, exclude=ex,
                                                                   chunk_rows=chunk_rows)
             idx, val, _ = hip.catalog_rerank(u, self.catalog, short, k, self._inv)
-        else:
+        elif k <= hip.CATALOG_TOPK_MAX:
             idx, val, rank, self._inv = hip.catalog_select(u, self.catalog, k, self._inv, gt_index=gt, exclude=ex, chunk_rows=chunk_rows,
                                                             scorer=scorer)
+        else:
+            idx, val, rank, self._inv = hip.catalog_deep_select(u, self.catalog, k, self._inv, gt_index=gt, exclude=ex,
+                                                                 chunk_rows=chunk_rows, scorer=scorer)
         out = {"topk_index": idx, "topk_score": val}
         if rank is not None:
             ks = (k,) if ks is None else tuple(int(x) for x in ks)

@@ -1363,6 +1363,56 @@ def catalog_select(user, catalog, K, cat_inv_norm=None, gt_index=None, exclude=N
     return idx, val, rank, cat_inv_norm
 
 
+CATALOG_DEEP_TOPK_MAX = _lib.CATALOG_DEEP_TOPK_MAX      # UR_CATALOG_DEEP_TOPK_MAX
+
+
+def catalog_deep_select(user, catalog, K, cat_inv_norm=None, gt_index=None, exclude=None, chunk_rows=None, scorer=None, segments=None):
+    """catalog_select with lists of up to CATALOG_DEEP_TOPK_MAX = 1024 items (ur_catalog_deep_select, include/unirec_hip_deep.h): the
+    same f32 scores bit for bit, the same total order (score descending, lowest index first), the same gt_index / rank, exclude,
+    chunk_rows and scorer arguments and the same (-1, -inf) tail; for K <= 128 the same outputs in every bit.  The selection kernel
+    defers its merges and several workgroups share a user's chunk row; neither shows in the result.
+    segments: for tests -- the number of workgroups per user (1 .. 16) instead of the library's choice from B and the CU count; the
+    outputs do not depend on it.
+    Returns (topk_index int32 [B,K], topk_score f32 [B,K], rank int32 [B] or None, cat_inv_norm)."""
+    scorer_id = catalog_scorer_id(scorer)
+    if catalog.dtype not in (F32, BF16):
+        raise ValueError(f"catalog_deep_select: catalog must be f32 or bf16, got {catalog.dtype}")
+    lib = _lib.load()
+    _need(user, F32, "user")
+    _need(catalog, catalog.dtype, "catalog")
+    if user.dim() != 2 or catalog.dim() != 2 or catalog.shape[1] != user.shape[1]:
+        raise ValueError(f"catalog_deep_select: user [B,D] and catalog [N,D] must share D, got {tuple(user.shape)} and {tuple(catalog.shape)}")
+    B, D = user.shape
+    N = catalog.shape[0]
+    dev = user.device
+    a = _lib.CatalogDeep()
+    a.user, a.catalog, a.catalog_bf16, a.scorer = user.data_ptr(), catalog.data_ptr(), int(catalog.dtype == BF16), scorer_id
+    a.B, a.N, a.D, a.K, a.chunk_rows, a.segments = B, N, D, int(K), int(chunk_rows or 0), int(segments or 0)
+    idx = torch.empty((B, max(int(K), 0)), dtype=torch.int32, device=dev)
+    val = torch.empty((B, max(int(K), 0)), dtype=F32, device=dev)
+    a.topk_index, a.topk_score = idx.data_ptr(), val.data_ptr()
+    rank = gt = None
+    if gt_index is not None:
+        gt = gt_index.to(device=dev, dtype=torch.int64).contiguous()
+        if gt.shape != (B,):
+            raise ValueError(f"catalog_deep_select: gt_index must have shape [{B}], got {tuple(gt.shape)}")
+        rank = torch.empty((B,), dtype=torch.int32, device=dev)
+        a.gt_index, a.rank = gt.data_ptr(), rank.data_ptr()
+    if exclude is not None:
+        _need(exclude, torch.int64, "exclude")
+        if exclude.dim() != 2 or exclude.shape[0] != B:
+            raise ValueError(f"catalog_deep_select: exclude must be [{B}, E], got {tuple(exclude.shape)}")
+        a.E = exclude.shape[1]
+        a.exclude = exclude.data_ptr() if a.E else None
+    cat_inv_norm, a.cat_norm_ready = _catalog_norm(cat_inv_norm, N, dev, "catalog_deep_select")
+    a.cat_inv_norm = cat_inv_norm.data_ptr()
+    check(lib.ur_catalog_deep_select(ctypes.byref(a), _stream()), "ur_catalog_deep_select")        # size query: workspace is NULL
+    ws = workspace(a.workspace_bytes, dev, "catalog_deep")
+    a.workspace = ws.data_ptr()
+    check(lib.ur_catalog_deep_select(ctypes.byref(a), _stream()), "ur_catalog_deep_select")
+    return idx, val, rank, cat_inv_norm
+
+
 COARSE_USER_GROUP = _lib.COARSE_USER_GROUP      # users a workgroup of the coarse scorer stages (half of it when D > 1024)
 
 
