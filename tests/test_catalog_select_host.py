@@ -134,6 +134,42 @@ def test_select_argument_checks_reject_without_launching():
     assert _call(lib, _select(), N=2 ** 31 - 1) == 0
 
 
+def test_wrapper_refuses_mismatched_operands_before_the_library(monkeypatch):
+    """shapes that the library would read out of bounds: a ValueError under the wrapper's name, on host tensors, nothing loaded"""
+    from unirec_amd import hip
+
+    def no_library():
+        raise AssertionError("the library was loaded")
+    monkeypatch.setattr(_lib, "load", no_library)
+    user, cat = torch.zeros(2, 16), torch.zeros(5, 16)
+    for args, kw in (((torch.zeros(16), cat), {}),
+                     ((user, torch.zeros(5, 4, 4)), {}),
+                     ((user, torch.zeros(5, 12)), {}),
+                     ((user, cat), dict(cat_inv_norm=torch.ones(4))),
+                     ((user, cat), dict(cat_inv_norm=torch.ones(5, dtype=torch.float64)))):
+        with pytest.raises(ValueError, match="catalog_select"):
+            hip.catalog_select(*args, 3, **kw)
+
+
+def test_workspace_layouts_under_the_host_sanitizers(tmp_path):
+    """tests/host/catalog_layout_check.cpp: every catalogue workspace over a grid of sizes -- regions aligned, disjoint and inside the
+    size the query answers, the size the closed form -- as a stand-alone host program under AddressSanitizer and UBSan"""
+    import os
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # the sanitizer runtimes are linked statically: a dynamic one insists on being the first library the process loads
+    gxx, clang = shutil.which("g++"), shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
+    cxx = [gxx, "-static-libasan", "-static-libubsan"] if gxx else [clang, "-static-libsan"]
+    exe = str(tmp_path / "catalog_layout_check")
+    subprocess.run(cxx + ["-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                          "-I", os.path.join(root, "unirec_amd", "csrc"), os.path.join(root, "tests", "host", "catalog_layout_check.cpp"), "-o", exe],
+                   check=True)
+    # (the program allocates nothing it does not free at exit; the leak pass needs ptrace, which a sandbox may not grant)
+    run = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert run.returncode == 0 and run.stdout.split() == ["ok", "648"], (run.returncode, run.stdout, run.stderr)
+
+
 def test_plain_call_still_needs_scores():
     lib = _lib.load()
     rc = _call(lib, None, scores=None)

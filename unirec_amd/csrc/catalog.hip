@@ -321,7 +321,7 @@ __device__ __forceinline__ float csm_block_max(float v, float* red) {
 // units): segment j owns the rows [j seg, (j + 1) seg) of every chunk and its own running slot [b][j], carried across the chunks in the
 // stream's order; the slots of a user are merged in index order at the end.  seg is fixed by the chunk size, so a (shorter) last
 // chunk leaves its trailing segments without rows: those keep their slots (or, on the first chunk, initialise them).
-constexpr int CSM_SEGS = 16;
+// (CSM_SEGS sizes the workspace: catalog_layout.hip.h)
 
 // Pass 1, one workgroup per (user, segment) and chunk: slot (m, l) <- the running maximum and sum_n exp(z_bn - m) over the segment's
 // rows seen so far (chunk[b][0..len) = s_bn of catalogue rows c0 .. c0+len).  Two sweeps over the rows (just written: cache
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(256) void catalog_softmax_weight_kernel(float* __re
 // enters as zeros on both sides.  Users past B and columns past D are computed on clamped addresses and never stored (an output
 // element depends on its own user and column only).  The slabs are accumulated across chunks by the stream's order: the first chunk
 // stores, later chunks add; a split without rows in a later (shorter) chunk leaves its slab alone.
-constexpr int CSM_UT = 2, CSM_USERS = 16 * CSM_UT;
+// (CSM_UT and CSM_USERS size the workspace: catalog_layout.hip.h)
 template <typename CT>
 __global__ __launch_bounds__(256) void catalog_softmax_grad_kernel(const float* __restrict__ wchunk, long ld, int len, const CT* __restrict__ cat,
                                                                    float* __restrict__ slabs, int B, int D, int rps, int first) {
@@ -600,10 +600,11 @@ extern "C" int ur_gather_rows(const void* src, int32_t src_kind, void* out, int3
   return 0;
 }
 
-// the vector scoring launch of both modes: rows [0,N) of `catalog` / `cat_inv_norm` into scores [B][N] (leading dimension N)
+// the vector scoring launch of both modes: rows [0,N) of `catalog` / `cat_inv_norm` into scores [B][N] (leading dimension N);
+// who = the entry point the launch is made for, named in a failure
 template <typename CT>
 static int launch_catalog_scores(const float* user, const float* user_inv_norm, const CT* catalog, const float* cat_inv_norm,
-                                 float* scores, int32_t B, int64_t N, int32_t D, hipStream_t st) {
+                                 float* scores, int32_t B, int64_t N, int32_t D, hipStream_t st, const char* who) {
   const int ub = ur_cdiv(B, CU_USERS);
   long blocks_x = 2048 / ub;                                  // ~8 workgroups per CU in all
   if (blocks_x < 1) blocks_x = 1;
@@ -614,18 +615,18 @@ static int launch_catalog_scores(const float* user, const float* user_inv_norm, 
   static std::atomic<uint64_t> attr_set{0};   // per device
   UR_ONCE_PER_DEVICE(attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&catalog_scores_kernel<CT>), hipFuncAttributeMaxDynamicSharedMemorySize, CU_USERS * 2048 * 4);
-    if (e != hipSuccess) UR_FAIL((int)e, "ur_catalog_scores: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) UR_FAIL((int)e, "%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
   }
   hipLaunchKernelGGL(catalog_scores_kernel<CT>, dim3((unsigned)blocks_x, (unsigned)ub), dim3(256), smem, st, user, user_inv_norm, catalog,
                      cat_inv_norm, scores, (int)B, (long)N, (int)D, (long)rpb);
-  UR_CHECK_LAUNCH("ur_catalog_scores");
+  UR_CHECK_LAUNCH(who);
   return 0;
 }
 
 // the f32-MFMA scoring launch of the streaming mode: the same arguments, the same scores
 template <typename CT>
 static int launch_catalog_scores_mfma(const float* user, const float* user_inv_norm, const CT* catalog, const float* cat_inv_norm,
-                                      float* scores, int32_t B, int64_t N, int32_t D, hipStream_t st) {
+                                      float* scores, int32_t B, int64_t N, int32_t D, hipStream_t st, const char* who) {
   const bool wide = D > 1024;
   const int ub = ur_cdiv(B, wide ? 16 : 32);
   const int group = wide ? 16 * MF_TILES : 16 * MF_TILES / 2;      // rows per step of a workgroup
@@ -640,11 +641,11 @@ static int launch_catalog_scores_mfma(const float* user, const float* user_inv_n
   static std::atomic<uint64_t> attr_set[4];   // per device, one per kernel
   UR_ONCE_PER_DEVICE(attr_set[2 * wide + (D == 1024 || D == 2048)]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf_lds_bytes(2048, true));
-    if (e != hipSuccess) UR_FAIL((int)e, "ur_catalog_scores: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) UR_FAIL((int)e, "%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
   }
   hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks_x * ub)), dim3(256), mf_lds_bytes(D, wide), st, user, user_inv_norm, catalog, cat_inv_norm,
                      scores, (int)B, (long)N, (int)D, (long)rpb, ub);
-  UR_CHECK_LAUNCH("ur_catalog_scores");
+  UR_CHECK_LAUNCH(who);
   return 0;
 }
 
@@ -653,279 +654,200 @@ static int launch_catalog_scores_mfma(const float* user, const float* user_inv_n
 // Measured at D = 1024 only (the embedding width of this project): the MFMA scorer wins at every sampled (B, N) on an f32 catalogue
 // and at B = 64 and 512 on a bf16 one; at B = 8 on bf16 the two are within 2 %.  Other widths have not been timed and stay on the
 // vector scorer.
-static bool catalog_default_is_mfma(int32_t B, int64_t N, int32_t D, bool bf16) {
-  (void)N;
-  return D == 1024 && (B > CU_USERS || !bf16);
+static bool catalog_default_is_mfma(int32_t B, int32_t D, bool bf16) { return D == 1024 && (B > CU_USERS || !bf16); }
+// the one place the `scorer` field of an argument struct becomes a kernel choice
+static bool catalog_use_mfma(const catalog_call& c) {
+  return c.scorer == UR_CATALOG_SCORER_MFMA || (c.scorer == 0 && catalog_default_is_mfma(c.B, c.D, c.catalog_bf16 == 1));
+}
+
+// The two steps the exact streams (select, deep, softmax) share, after every check; inv_u = where the call keeps the user norms.
+// Before the first chunk: the user norms, the catalogue norms unless the caller brought them, the ground-truth scores into ref.
+template <typename CT>
+static int catalog_prologue(const catalog_call& c, const CT* catalog, float* inv_u, int32_t cat_norm_ready, float* ref, hipStream_t st) {
+  const float* user = (const float*)c.user;
+  float* inv_c = (float*)c.cat_inv_norm;
+  hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((c.B + 3) / 4)), dim3(256), 0, st, user, inv_u, (long)c.B, (int)c.D);
+  if (!cat_norm_ready && c.N > 0)
+    hipLaunchKernelGGL(row_inv_norm_kernel<CT>, dim3((unsigned)((c.N + 3) / 4)), dim3(256), 0, st, catalog, inv_c, (long)c.N, (int)c.D);
+  if (c.gt && c.N > 0)
+    hipLaunchKernelGGL(catalog_gt_score_kernel<CT>, dim3((unsigned)((c.B + 3) / 4)), dim3(256), 0, st, user, (const float*)inv_u, catalog,
+                       (const float*)inv_c, (const long*)c.gt, ref, (int)c.B, (long)c.N, (int)c.D);
+  UR_CHECK_LAUNCH(c.who);
+  return 0;
+}
+
+// the scores of catalogue rows [c0, c0 + len) into chunk [B][len]; an empty chunk (N == 0) launches nothing
+template <typename CT>
+static int catalog_score_chunk(const catalog_call& c, const CT* catalog, const float* inv_u, int64_t c0, int64_t len, float* chunk, hipStream_t st) {
+  if (len <= 0) return 0;
+  const float* user = (const float*)c.user;
+  const float* inv_c = (const float*)c.cat_inv_norm + c0;
+  return catalog_use_mfma(c) ? launch_catalog_scores_mfma<CT>(user, inv_u, catalog + c0 * c.D, inv_c, chunk, c.B, len, c.D, st, c.who)
+                             : launch_catalog_scores<CT>(user, inv_u, catalog + c0 * c.D, inv_c, chunk, c.B, len, c.D, st, c.who);
 }
 
 // the launches of the streaming mode, after every check
 template <typename CT>
-static int catalog_stream(const float* user, const CT* catalog, float* user_inv_norm, float* cat_inv_norm, int32_t cat_norm_ready, int32_t B,
-                          int64_t N, int32_t D, ur_catalog_select_t* select, int64_t chunk_bytes, int64_t rows, bool mfma, hipStream_t st) {
-  const int K = select->K, E = select->E;
-  float* chunk = (float*)select->workspace;
-  float* ref = (float*)((char*)select->workspace + chunk_bytes);
-  const long* gt = (const long*)select->gt_index;
-  hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, user_inv_norm, (long)B, (int)D);
-  if (!cat_norm_ready && N > 0)
-    hipLaunchKernelGGL(row_inv_norm_kernel<CT>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, cat_inv_norm, (long)N, (int)D);
-  if (gt && N > 0)
-    hipLaunchKernelGGL(catalog_gt_score_kernel<CT>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, (const float*)user_inv_norm, catalog,
-                       (const float*)cat_inv_norm, gt, ref, (int)B, (long)N, (int)D);
-  UR_CHECK_LAUNCH("ur_catalog_scores");
-  int64_t c0 = 0;
-  do {                                                         // (N == 0: one pass over an empty chunk writes the empty lists)
-    const int64_t len = N - c0 < rows ? N - c0 : rows;
-    if (len > 0) {
-      const int rc = mfma ? launch_catalog_scores_mfma<CT>(user, user_inv_norm, catalog + c0 * D, cat_inv_norm + c0, chunk, B, len, D, st)
-                          : launch_catalog_scores<CT>(user, user_inv_norm, catalog + c0 * D, cat_inv_norm + c0, chunk, B, len, D, st);
-      if (rc != 0) return rc;
-    }
-    hipLaunchKernelGGL(catalog_select_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0, (int)len, K,
-                       select->topk_score, select->topk_index, gt, (const float*)ref, select->rank, (const long*)select->exclude, E,
-                       (int)(c0 == 0));
-    UR_CHECK_LAUNCH("ur_catalog_scores");
-    c0 += rows;
-  } while (c0 < N);
-  return 0;
+static int catalog_stream(const catalog_call& c, const CT* catalog, float* inv_u, int32_t cat_norm_ready, const ur_catalog_select_t* select,
+                          const select_plan& p, hipStream_t st) {
+  char* ws = (char*)select->workspace;
+  float* chunk = (float*)(ws + p.chunk);
+  float* ref = (float*)(ws + p.ref);
+  if (const int rc = catalog_prologue(c, catalog, inv_u, cat_norm_ready, ref, st)) return rc;
+  return catalog_for_each_chunk(c.N, p.rows, [&](int64_t c0, int64_t len, int first) {
+    if (const int rc = catalog_score_chunk(c, catalog, inv_u, c0, len, chunk, st)) return rc;
+    hipLaunchKernelGGL(catalog_select_kernel, dim3((unsigned)c.B), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0, (int)len, select->K,
+                       select->topk_score, select->topk_index, (const long*)c.gt, (const float*)ref, select->rank, (const long*)select->exclude,
+                       select->E, first);
+    UR_CHECK_LAUNCH(c.who);
+    return 0;
+  });
 }
 
 extern "C" int ur_catalog_scores(const float* user, const float* catalog, float* scores, float* user_inv_norm, float* cat_inv_norm,
                                  int32_t cat_norm_ready, int32_t B, int64_t N, int32_t D, ur_catalog_select_t* select, void* stream) {
-  UR_REQUIRE(B >= 0 && N >= 0 && D > 0 && (D % 4) == 0 && D <= 2048, "ur_catalog_scores: need D %% 4 == 0 and D <= 2048 (got %d)", D);
   hipStream_t st = (hipStream_t)stream;
   if (!select) {
+    UR_REQUIRE(B >= 0 && N >= 0 && D > 0 && (D % 4) == 0 && D <= 2048, "ur_catalog_scores: need D %% 4 == 0 and D <= 2048 (got %d)", D);
     if (B == 0 || N == 0) return 0;
     UR_REQUIRE(user && catalog && scores && user_inv_norm && cat_inv_norm, "ur_catalog_scores: null pointer");
     UR_REQUIRE(UR_ALIGNED16(user) && UR_ALIGNED16(catalog), "ur_catalog_scores: operands must be 16-byte aligned");
     hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, user_inv_norm, (long)B, (int)D);
     if (!cat_norm_ready)
       hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, cat_inv_norm, (long)N, (int)D);
-    return launch_catalog_scores<float>(user, user_inv_norm, catalog, cat_inv_norm, scores, B, N, D, st);
+    return launch_catalog_scores<float>(user, user_inv_norm, catalog, cat_inv_norm, scores, B, N, D, st, "ur_catalog_scores");
   }
   // ---- streaming selection: every check before any launch ----
-  const int K = select->K, E = select->E;
-  UR_REQUIRE(K >= 1 && K <= UR_CATALOG_TOPK_MAX, "ur_catalog_scores: select.K must be 1 .. %d (got %d)", UR_CATALOG_TOPK_MAX, K);
-  UR_REQUIRE(N <= (int64_t)INT32_MAX, "ur_catalog_scores: select mode needs N <= INT32_MAX (got %lld)", (long long)N);
-  UR_REQUIRE(select->chunk_rows >= 0 && (select->chunk_rows % SEL_TILE) == 0,
-             "ur_catalog_scores: select.chunk_rows must be 0 or a positive multiple of %d (got %lld)", SEL_TILE, (long long)select->chunk_rows);
-  UR_REQUIRE(E >= 0 && (E == 0 || select->exclude), "ur_catalog_scores: select.E > 0 needs select.exclude");
-  UR_REQUIRE((select->gt_index != nullptr) == (select->rank != nullptr), "ur_catalog_scores: select.gt_index and select.rank go together");
-  UR_REQUIRE(select->catalog_bf16 == 0 || select->catalog_bf16 == 1, "ur_catalog_scores: select.catalog_bf16 must be 0 or 1 (got %d)", select->catalog_bf16);
-  UR_REQUIRE(select->scorer >= 0 && select->scorer <= UR_CATALOG_SCORER_MFMA,
-             "ur_catalog_scores: select.scorer must be 0 (the library chooses), 1 (vector) or 2 (f32 MFMA) (got %d)", select->scorer);
-  const bool bf16 = select->catalog_bf16 == 1;
-  const int64_t rows = catalog_chunk_rows(select->chunk_rows, B, N);
-  const int64_t chunk_bytes = ((int64_t)B * rows * 4 + 15) / 16 * 16;
-  const int64_t need = chunk_bytes + ((int64_t)B * 4 + 15) / 16 * 16;      // chunk [B][rows] f32 | ref [B] f32
+  const catalog_call c{"ur_catalog_scores", B, N, D, select->E, select->chunk_rows, select->catalog_bf16, select->scorer, select->gt_index,
+                       select->rank, select->exclude, user, catalog, cat_inv_norm, select->workspace, select->workspace_bytes};
+  if (const int rc = catalog_check_sizes(c, 4, 0, false)) return rc;
+  UR_REQUIRE(select->K >= 1 && select->K <= UR_CATALOG_TOPK_MAX, "ur_catalog_scores: select.K must be 1 .. %d (got %d)", UR_CATALOG_TOPK_MAX, select->K);
+  const select_plan p = select_layout(B, N, select->chunk_rows);
   if (!select->workspace) {
-    select->workspace_bytes = need > 16 ? need : 16;
+    select->workspace_bytes = p.need;
     return 0;
   }
-  UR_REQUIRE(UR_ALIGNED16(select->workspace) && select->workspace_bytes >= need,
-             "ur_catalog_scores: select.workspace must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)need, (long long)select->workspace_bytes);
+  if (const int rc = catalog_check_buffers(c, p.need, false)) return rc;
   if (B == 0) return 0;
-  UR_REQUIRE(select->topk_index && select->topk_score, "ur_catalog_scores: select.topk_index / topk_score are null");
-  UR_REQUIRE(user && user_inv_norm && (N == 0 || (catalog && cat_inv_norm)), "ur_catalog_scores: null pointer");
-  UR_REQUIRE(UR_ALIGNED16(user) && UR_ALIGNED16(catalog), "ur_catalog_scores: operands must be 16-byte aligned");
-  const bool mfma = select->scorer == UR_CATALOG_SCORER_MFMA || (select->scorer == 0 && catalog_default_is_mfma(B, N, D, bf16));
-  if (bf16)
-    return catalog_stream(user, (const bf16_t*)catalog, user_inv_norm, cat_inv_norm, cat_norm_ready, B, N, D, select, chunk_bytes, rows, mfma, st);
-  return catalog_stream(user, catalog, user_inv_norm, cat_inv_norm, cat_norm_ready, B, N, D, select, chunk_bytes, rows, mfma, st);
+  UR_REQUIRE(select->topk_index && select->topk_score && user_inv_norm, "ur_catalog_scores: select.topk_index / topk_score / user_inv_norm are null");
+  return catalog_dispatch(c.catalog_bf16 == 1, catalog, [&](auto* cat) {
+    return catalog_stream(c, cat, user_inv_norm, cat_norm_ready, select, p, st);
+  });
 }
 
 // ---- ur_catalog_deep_select (include/unirec_hip_deep.h) --------------------------------------------------------------------------
 // the launches, after every check: select mode's norms, reference score and scoring launches; the deep selection kernels
 template <typename CT>
-static int catalog_deep_stream(const ur_catalog_deep_t* a, const CT* catalog, const deep_plan& p, bool mfma, hipStream_t st) {
-  const int32_t B = a->B, D = a->D, K = a->K, E = a->E;
-  const int64_t N = a->N;
+static int catalog_deep_stream(const catalog_call& c, const ur_catalog_deep_t* a, const CT* catalog, const deep_plan& p, hipStream_t st) {
   char* ws = (char*)a->workspace;
-  float* chunk = (float*)ws;
-  float* ref = (float*)(ws + p.chunk_bytes);
-  float* inv_u = (float*)(ws + p.chunk_bytes + p.vec_bytes);
-  float* list_score = (float*)(ws + p.chunk_bytes + 2 * p.vec_bytes);
-  int* list_index = (int*)(ws + p.chunk_bytes + 2 * p.vec_bytes + p.list_bytes);
-  int* count = (int*)(ws + p.chunk_bytes + 2 * p.vec_bytes + 2 * p.list_bytes);
+  float* chunk = (float*)(ws + p.chunk);
+  float* ref = (float*)(ws + p.ref);
+  float* list_score = (float*)(ws + p.list_score);
+  int* list_index = (int*)(ws + p.list_index);
+  int* count = (int*)(ws + p.count);
   const long* gt = (const long*)a->gt_index;
+  const int B = a->B, K = a->K;
   const int G = deep_segments(a->segments, B, p.rows);             // <= p.gw, what the workspace holds
   const int64_t tiles = p.rows / SEL_TILE;
   const long seg_len = (long)((tiles + G - 1) / G) * SEL_TILE;
-  hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a->user, inv_u, (long)B, (int)D);
-  if (!a->cat_norm_ready && N > 0)
-    hipLaunchKernelGGL(row_inv_norm_kernel<CT>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, a->cat_inv_norm, (long)N, (int)D);
-  if (gt && N > 0)
-    hipLaunchKernelGGL(catalog_gt_score_kernel<CT>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a->user, (const float*)inv_u, catalog,
-                       (const float*)a->cat_inv_norm, gt, ref, (int)B, (long)N, (int)D);
-  UR_CHECK_LAUNCH("ur_catalog_deep_select");
-  int64_t c0 = 0;
-  do {                                                         // (N == 0: one pass over an empty chunk writes the empty lists)
-    const int64_t len = N - c0 < p.rows ? N - c0 : p.rows;
-    if (len > 0) {
-      const int rc = mfma ? launch_catalog_scores_mfma<CT>(a->user, inv_u, catalog + c0 * D, a->cat_inv_norm + c0, chunk, B, len, D, st)
-                          : launch_catalog_scores<CT>(a->user, inv_u, catalog + c0 * D, a->cat_inv_norm + c0, chunk, B, len, D, st);
-      if (rc != 0) return rc;
-    }
+  float* inv_u = (float*)(ws + p.inv_u);
+  if (const int rc = catalog_prologue(c, catalog, inv_u, a->cat_norm_ready, ref, st)) return rc;
+  const int swept = catalog_for_each_chunk(c.N, p.rows, [&](int64_t c0, int64_t len, int first) {
+    if (const int rc = catalog_score_chunk(c, catalog, inv_u, c0, len, chunk, st)) return rc;
     hipLaunchKernelGGL(catalog_deep_sweep_kernel, dim3((unsigned)((int64_t)B * G)), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0,
-                       (int)len, (int)K, G, seg_len, list_score, list_index, count, gt, (const float*)ref, (const long*)a->exclude, (int)E,
-                       (int)(c0 == 0));
-    UR_CHECK_LAUNCH("ur_catalog_deep_select");
-    c0 += p.rows;
-  } while (c0 < N);
+                       (int)len, K, G, seg_len, list_score, list_index, count, gt, (const float*)ref, (const long*)a->exclude, (int)a->E, first);
+    UR_CHECK_LAUNCH(c.who);
+    return 0;
+  });
+  if (swept != 0) return swept;
   hipLaunchKernelGGL(catalog_deep_merge_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)list_score, (const int*)list_index,
-                     (const int*)count, (int)K, G, a->topk_score, a->topk_index, a->rank);
-  UR_CHECK_LAUNCH("ur_catalog_deep_select");
+                     (const int*)count, K, G, a->topk_score, a->topk_index, a->rank);
+  UR_CHECK_LAUNCH(c.who);
   return 0;
 }
 
 extern "C" int ur_catalog_deep_select(ur_catalog_deep_t* a, void* stream) {
   UR_REQUIRE(a, "ur_catalog_deep_select: null argument struct");
-  const int32_t B = a->B, D = a->D, K = a->K, E = a->E;
-  const int64_t N = a->N;
-  UR_REQUIRE(B >= 0, "ur_catalog_deep_select: need B >= 0 (got %d)", B);
-  UR_REQUIRE(N >= 0 && N <= (int64_t)INT32_MAX, "ur_catalog_deep_select: need 0 <= N <= INT32_MAX (got %lld)", (long long)N);
-  UR_REQUIRE(D > 0 && (D % 4) == 0 && D <= 2048, "ur_catalog_deep_select: D must be a positive multiple of 4 and <= 2048 (got %d)", D);
-  UR_REQUIRE(K >= 1 && K <= UR_CATALOG_DEEP_TOPK_MAX, "ur_catalog_deep_select: K must be 1 .. %d (got %d)", UR_CATALOG_DEEP_TOPK_MAX, K);
-  UR_REQUIRE(a->chunk_rows >= 0 && (a->chunk_rows % SEL_TILE) == 0,
-             "ur_catalog_deep_select: chunk_rows must be 0 or a positive multiple of %d (got %lld)", SEL_TILE, (long long)a->chunk_rows);
-  UR_REQUIRE(E >= 0 && (E == 0 || a->exclude), "ur_catalog_deep_select: E > 0 needs exclude");
-  UR_REQUIRE((a->gt_index != nullptr) == (a->rank != nullptr), "ur_catalog_deep_select: gt_index and rank go together");
-  UR_REQUIRE(a->catalog_bf16 == 0 || a->catalog_bf16 == 1, "ur_catalog_deep_select: catalog_bf16 must be 0 or 1 (got %d)", a->catalog_bf16);
-  UR_REQUIRE(a->scorer >= 0 && a->scorer <= UR_CATALOG_SCORER_MFMA,
-             "ur_catalog_deep_select: scorer must be 0 (the library chooses), 1 (vector) or 2 (f32 MFMA) (got %d)", a->scorer);
+  const catalog_call c{"ur_catalog_deep_select", a->B, a->N, a->D, a->E, a->chunk_rows, a->catalog_bf16, a->scorer, a->gt_index, a->rank,
+                       a->exclude, a->user, a->catalog, a->cat_inv_norm, a->workspace, a->workspace_bytes};
+  if (const int rc = catalog_check_sizes(c, 4, 0, false)) return rc;
+  UR_REQUIRE(a->K >= 1 && a->K <= UR_CATALOG_DEEP_TOPK_MAX, "ur_catalog_deep_select: K must be 1 .. %d (got %d)", UR_CATALOG_DEEP_TOPK_MAX, a->K);
   UR_REQUIRE(a->segments >= 0 && a->segments <= UR_CATALOG_DEEP_SEGMENTS_MAX, "ur_catalog_deep_select: segments must be 0 .. %d (got %d)",
              UR_CATALOG_DEEP_SEGMENTS_MAX, a->segments);
-  const deep_plan p = deep_layout(B, N, K, a->chunk_rows, a->segments);
+  const deep_plan p = deep_layout(a->B, a->N, a->K, a->chunk_rows, a->segments);
   if (!a->workspace) {
     a->workspace_bytes = p.need;
     return 0;
   }
-  UR_REQUIRE(UR_ALIGNED16(a->workspace) && a->workspace_bytes >= p.need,
-             "ur_catalog_deep_select: workspace must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)p.need,
-             (long long)a->workspace_bytes);
-  if (B == 0) return 0;
+  if (const int rc = catalog_check_buffers(c, p.need, false)) return rc;
+  if (a->B == 0) return 0;
   UR_REQUIRE(a->topk_index && a->topk_score, "ur_catalog_deep_select: topk_index / topk_score are null");
-  UR_REQUIRE(a->user && (N == 0 || (a->catalog && a->cat_inv_norm)), "ur_catalog_deep_select: user / catalog / cat_inv_norm: null pointer");
-  UR_REQUIRE(UR_ALIGNED16(a->user) && UR_ALIGNED16(a->catalog), "ur_catalog_deep_select: user and catalog must be 16-byte aligned");
-  const bool bf16 = a->catalog_bf16 == 1;
-  const bool mfma = a->scorer == UR_CATALOG_SCORER_MFMA || (a->scorer == 0 && catalog_default_is_mfma(B, N, D, bf16));
-  hipStream_t st = (hipStream_t)stream;
-  if (bf16) return catalog_deep_stream(a, (const bf16_t*)a->catalog, p, mfma, st);
-  return catalog_deep_stream(a, (const float*)a->catalog, p, mfma, st);
+  return catalog_dispatch(c.catalog_bf16 == 1, a->catalog, [&](auto* cat) { return catalog_deep_stream(c, a, cat, p, (hipStream_t)stream); });
 }
 
 // ---- ur_catalog_softmax (include/unirec_hip_loss.h) ------------------------------------------------------------------------------
-// row splits of the gradient product: ~1024 workgroups in all, no split shorter than 64 rows; rps = rows per split (a multiple of 4)
-static void catalog_softmax_splits(int32_t B, int32_t D, int64_t rows, int* nsplit, int* rps) {
-  const long tiles = (long)ur_cdiv(B > 0 ? B : 1, CSM_USERS) * ur_cdiv(D, 256);
-  long s = 1024 / tiles;
-  if (s > (rows + 63) / 64) s = (rows + 63) / 64;
-  if (s < 1) s = 1;
-  long r = ((rows + s - 1) / s + 3) / 4 * 4;
-  *rps = (int)r;
-  *nsplit = (int)((rows + r - 1) / r);
-}
-
-// the workspace: chunk [B][rows] | user_inv_norm, ref: [B] each | m, l, t: [B][CSM_SEGS] each | slabs [nsplit][B][D] (with d_user only)
-struct catalog_softmax_plan {
-  int64_t rows, chunk_bytes, vec_bytes, seg_bytes, need;
-  int nsplit, rps, seg;
-};
-static catalog_softmax_plan catalog_softmax_layout(int32_t B, int64_t N, int32_t D, int64_t chunk_rows, bool grad) {
-  catalog_softmax_plan p;
-  p.rows = catalog_chunk_rows(chunk_rows, B, N);
-  p.chunk_bytes = ((int64_t)B * p.rows * 4 + 15) / 16 * 16;
-  p.vec_bytes = ((int64_t)B * 4 + 15) / 16 * 16;
-  p.seg_bytes = (int64_t)B * CSM_SEGS * 4;
-  p.seg = (int)((p.rows + CSM_SEGS - 1) / CSM_SEGS);
-  catalog_softmax_splits(B, D, p.rows, &p.nsplit, &p.rps);
-  p.need = p.chunk_bytes + 2 * p.vec_bytes + 3 * p.seg_bytes + (grad ? (int64_t)p.nsplit * B * D * 4 : 0);
-  if (p.need < 16) p.need = 16;
-  return p;
-}
-
-// the launches, after every check
+// the launches, after every check: pass 1 folds every chunk into the running (m, l) and finishes the loss; pass 2 (with d_user) scores
+// the chunks again, turns them into weights, accumulates the gradient slabs and finishes d_user
 template <typename CT>
-static int catalog_softmax_stream(const ur_catalog_softmax_t* a, const CT* catalog, const catalog_softmax_plan& p, bool mfma, hipStream_t st) {
+static int catalog_softmax_stream(const catalog_call& c, const ur_catalog_softmax_t* a, const CT* catalog, const catalog_softmax_plan& p,
+                                  hipStream_t st) {
   const int32_t B = a->B, D = a->D, E = a->E;
-  const int64_t N = a->N, rows = p.rows;
   char* ws = (char*)a->workspace;
-  float* chunk = (float*)ws;
-  float* inv_u = (float*)(ws + p.chunk_bytes);
-  float* ref = (float*)(ws + p.chunk_bytes + p.vec_bytes);
-  float* m_run = (float*)(ws + p.chunk_bytes + 2 * p.vec_bytes);
-  float* l_run = (float*)(ws + p.chunk_bytes + 2 * p.vec_bytes + p.seg_bytes);
-  float* t_run = (float*)(ws + p.chunk_bytes + 2 * p.vec_bytes + 2 * p.seg_bytes);
-  float* slabs = (float*)(ws + p.chunk_bytes + 2 * p.vec_bytes + 3 * p.seg_bytes);
+  float* chunk = (float*)(ws + p.chunk);
+  float* inv_u = (float*)(ws + p.inv_u);
+  float* ref = (float*)(ws + p.ref);
+  float* m_run = (float*)(ws + p.m_run);
+  float* l_run = (float*)(ws + p.l_run);
+  float* t_run = (float*)(ws + p.t_run);
+  float* slabs = (float*)(ws + p.slabs);
   const long* gt = (const long*)a->gt_index;
   const long* ex = (const long*)a->exclude;
   const float inv_tau = 1.0f / a->temperature;
-  hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a->user, inv_u, (long)B, (int)D);
-  if (!a->cat_norm_ready)
-    hipLaunchKernelGGL(row_inv_norm_kernel<CT>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, a->cat_inv_norm, (long)N, (int)D);
-  hipLaunchKernelGGL(catalog_gt_score_kernel<CT>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a->user, (const float*)inv_u, catalog,
-                     (const float*)a->cat_inv_norm, gt, ref, (int)B, (long)N, (int)D);
-  UR_CHECK_LAUNCH("ur_catalog_softmax");
-  for (int pass = 0; pass < (a->d_user ? 2 : 1); ++pass) {
-    for (int64_t c0 = 0; c0 < N; c0 += rows) {
-      const int64_t len = N - c0 < rows ? N - c0 : rows;
-      const int rc = mfma ? launch_catalog_scores_mfma<CT>(a->user, inv_u, catalog + c0 * D, a->cat_inv_norm + c0, chunk, B, len, D, st)
-                          : launch_catalog_scores<CT>(a->user, inv_u, catalog + c0 * D, a->cat_inv_norm + c0, chunk, B, len, D, st);
-      if (rc != 0) return rc;
-      if (pass == 0) {
-        hipLaunchKernelGGL(catalog_softmax_fold_kernel, dim3((unsigned)B, CSM_SEGS), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0, (int)len,
-                           p.seg, gt, ex, E, inv_tau, m_run, l_run, (int)(c0 == 0));
-      } else {
-        hipLaunchKernelGGL(catalog_softmax_weight_kernel, dim3((unsigned)B, CSM_SEGS), dim3(256), 0, st, chunk, (long)len, (int)c0, (int)len,
-                           p.seg, (const float*)a->cat_inv_norm, gt, ex, E, inv_tau, (const float*)a->lse, t_run, (int)(c0 == 0));
-        hipLaunchKernelGGL(catalog_softmax_grad_kernel<CT>, dim3((unsigned)ur_cdiv(B, CSM_USERS), (unsigned)ur_cdiv(D, 256), (unsigned)p.nsplit),
-                           dim3(256), 0, st, (const float*)chunk, (long)len, (int)len, catalog + c0 * D, slabs, (int)B, (int)D, p.rps,
-                           (int)(c0 == 0));
-      }
-      UR_CHECK_LAUNCH("ur_catalog_softmax");
-    }
-    if (pass == 0) {
-      hipLaunchKernelGGL(catalog_softmax_finish_kernel, dim3(1), dim3(64), 0, st, (const float*)m_run, (const float*)l_run, (const float*)ref,
-                         inv_tau, a->lse, a->row_loss, a->loss, (int)B);
-    } else {
-      hipLaunchKernelGGL(catalog_softmax_duser_kernel, dim3((unsigned)(((long)B * D / 4 + 255) / 256)), dim3(256), 0, st, a->user,
-                         (const float*)inv_u, (const float*)t_run, (const float*)slabs, a->d_user, (int)B, (int)D, p.nsplit,
-                         a->grad_scale / (float)B);
-    }
-    UR_CHECK_LAUNCH("ur_catalog_softmax");
-  }
+  if (const int rc = catalog_prologue(c, catalog, inv_u, a->cat_norm_ready, ref, st)) return rc;
+  const int folded = catalog_for_each_chunk(c.N, p.rows, [&](int64_t c0, int64_t len, int first) {
+    if (const int rc = catalog_score_chunk(c, catalog, inv_u, c0, len, chunk, st)) return rc;
+    hipLaunchKernelGGL(catalog_softmax_fold_kernel, dim3((unsigned)B, CSM_SEGS), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0, (int)len,
+                       p.seg, gt, ex, E, inv_tau, m_run, l_run, first);
+    UR_CHECK_LAUNCH(c.who);
+    return 0;
+  });
+  if (folded != 0) return folded;
+  hipLaunchKernelGGL(catalog_softmax_finish_kernel, dim3(1), dim3(64), 0, st, (const float*)m_run, (const float*)l_run, (const float*)ref, inv_tau,
+                     a->lse, a->row_loss, a->loss, (int)B);
+  UR_CHECK_LAUNCH(c.who);
+  if (!a->d_user) return 0;
+  const int weighted = catalog_for_each_chunk(c.N, p.rows, [&](int64_t c0, int64_t len, int first) {
+    if (const int rc = catalog_score_chunk(c, catalog, inv_u, c0, len, chunk, st)) return rc;
+    hipLaunchKernelGGL(catalog_softmax_weight_kernel, dim3((unsigned)B, CSM_SEGS), dim3(256), 0, st, chunk, (long)len, (int)c0, (int)len, p.seg,
+                       (const float*)a->cat_inv_norm, gt, ex, E, inv_tau, (const float*)a->lse, t_run, first);
+    hipLaunchKernelGGL(catalog_softmax_grad_kernel<CT>, dim3((unsigned)ur_cdiv(B, CSM_USERS), (unsigned)ur_cdiv(D, 256), (unsigned)p.nsplit),
+                       dim3(256), 0, st, (const float*)chunk, (long)len, (int)len, catalog + c0 * D, slabs, (int)B, (int)D, p.rps, first);
+    UR_CHECK_LAUNCH(c.who);
+    return 0;
+  });
+  if (weighted != 0) return weighted;
+  hipLaunchKernelGGL(catalog_softmax_duser_kernel, dim3((unsigned)(((long)B * D / 4 + 255) / 256)), dim3(256), 0, st, a->user, (const float*)inv_u,
+                     (const float*)t_run, (const float*)slabs, a->d_user, (int)B, (int)D, p.nsplit, a->grad_scale / (float)B);
+  UR_CHECK_LAUNCH(c.who);
   return 0;
 }
 
 extern "C" int ur_catalog_softmax(ur_catalog_softmax_t* a, void* stream) {
   UR_REQUIRE(a, "ur_catalog_softmax: null argument struct");
-  const int32_t B = a->B, D = a->D, E = a->E;
-  const int64_t N = a->N;
-  UR_REQUIRE(B >= 0 && D > 0 && (D % 4) == 0 && D <= 2048, "ur_catalog_softmax: need B >= 0, D %% 4 == 0 and D <= 2048 (got B %d, D %d)", B, D);
-  UR_REQUIRE(N >= 1 && N <= (int64_t)INT32_MAX, "ur_catalog_softmax: need 1 <= N <= INT32_MAX (got %lld)", (long long)N);
+  const catalog_call c{"ur_catalog_softmax", a->B, a->N, a->D, a->E, a->chunk_rows, a->catalog_bf16, a->scorer, a->gt_index, nullptr,
+                       a->exclude, a->user, a->catalog, a->cat_inv_norm, a->workspace, a->workspace_bytes};
+  if (const int rc = catalog_check_sizes(c, 4, 1, true)) return rc;
   UR_REQUIRE(a->temperature > 0.f && a->temperature <= 3.0e38f, "ur_catalog_softmax: temperature must be positive and finite (got %g)", (double)a->temperature);
-  UR_REQUIRE(a->chunk_rows >= 0 && (a->chunk_rows % SEL_TILE) == 0,
-             "ur_catalog_softmax: chunk_rows must be 0 or a positive multiple of %d (got %lld)", SEL_TILE, (long long)a->chunk_rows);
-  UR_REQUIRE(E >= 0 && (E == 0 || a->exclude), "ur_catalog_softmax: E > 0 needs exclude");
-  UR_REQUIRE(a->catalog_bf16 == 0 || a->catalog_bf16 == 1, "ur_catalog_softmax: catalog_bf16 must be 0 or 1 (got %d)", a->catalog_bf16);
-  UR_REQUIRE(a->scorer >= 0 && a->scorer <= UR_CATALOG_SCORER_MFMA,
-             "ur_catalog_softmax: scorer must be 0 (the library chooses), 1 (vector) or 2 (f32 MFMA) (got %d)", a->scorer);
-  const catalog_softmax_plan p = catalog_softmax_layout(B, N, D, a->chunk_rows, a->d_user != nullptr);
+  const catalog_softmax_plan p = catalog_softmax_layout(a->B, a->N, a->D, a->chunk_rows, a->d_user != nullptr);
   if (!a->workspace) {
     a->workspace_bytes = p.need;
     return 0;
   }
-  UR_REQUIRE(UR_ALIGNED16(a->workspace) && a->workspace_bytes >= p.need,
-             "ur_catalog_softmax: workspace must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)p.need, (long long)a->workspace_bytes);
-  if (B == 0) return 0;
-  UR_REQUIRE(a->user && a->catalog && a->cat_inv_norm && a->gt_index && a->loss && a->row_loss && a->lse, "ur_catalog_softmax: null pointer");
-  UR_REQUIRE(UR_ALIGNED16(a->user) && UR_ALIGNED16(a->catalog) && (!a->d_user || UR_ALIGNED16(a->d_user)),
-             "ur_catalog_softmax: user, catalog and d_user must be 16-byte aligned");
-  const bool bf16 = a->catalog_bf16 == 1;
-  const bool mfma = a->scorer == UR_CATALOG_SCORER_MFMA || (a->scorer == 0 && catalog_default_is_mfma(B, N, D, bf16));
-  hipStream_t st = (hipStream_t)stream;
-  if (bf16) return catalog_softmax_stream(a, (const bf16_t*)a->catalog, p, mfma, st);
-  return catalog_softmax_stream(a, (const float*)a->catalog, p, mfma, st);
+  if (const int rc = catalog_check_buffers(c, p.need, true)) return rc;
+  if (a->B == 0) return 0;
+  UR_REQUIRE(a->loss && a->row_loss && a->lse, "ur_catalog_softmax: loss / row_loss / lse: null pointer");
+  UR_REQUIRE(!a->d_user || UR_ALIGNED16(a->d_user), "ur_catalog_softmax: d_user must be 16-byte aligned");
+  return catalog_dispatch(c.catalog_bf16 == 1, a->catalog, [&](auto* cat) { return catalog_softmax_stream(c, a, cat, p, (hipStream_t)stream); });
 }
 
 extern "C" int ur_rank_of_index(const float* scores, const int64_t* gt_index, int32_t* rank, int32_t B, int64_t N, void* stream) {

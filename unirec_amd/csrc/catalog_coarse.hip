@@ -230,35 +230,16 @@ int launch_catalog_scores_bf16(const bf16_t* user, const float* inv_u, const bf1
   return 0;
 }
 
-// the workspace of ur_catalog_coarse_select: u~ [B][D] bf16 | iu~ [B] | ref [B] | chunk [B][rows] f32
-struct coarse_plan {
-  int64_t rows, user_bytes, vec_bytes, chunk_bytes, need;
-};
-coarse_plan coarse_layout(int32_t B, int64_t N, int32_t D, int64_t chunk_rows) {
-  coarse_plan p;
-  p.rows = catalog_chunk_rows(chunk_rows, B, N);
-  p.user_bytes = ((int64_t)B * D * 2 + 15) / 16 * 16;
-  p.vec_bytes = ((int64_t)B * 4 + 15) / 16 * 16;
-  p.chunk_bytes = ((int64_t)B * p.rows * 4 + 15) / 16 * 16;
-  p.need = p.user_bytes + 2 * p.vec_bytes + p.chunk_bytes;
-  if (p.need < 16) p.need = 16;
-  return p;
-}
-
 }  // namespace
 
 extern "C" int ur_catalog_coarse_select(ur_catalog_coarse_t* a, void* stream) {
   UR_REQUIRE(a, "ur_catalog_coarse_select: null argument struct");
+  const catalog_call c{"ur_catalog_coarse_select", a->B, a->N, a->D, a->E, a->chunk_rows, a->catalog_bf16, 0, a->gt_index, a->rank, a->exclude,
+                       a->user, a->catalog, a->cat_inv_norm, a->workspace, a->workspace_bytes};
+  if (const int rc = catalog_check_sizes(c, 8, 0, false)) return rc;
   const int32_t B = a->B, D = a->D, K = a->K, E = a->E;
   const int64_t N = a->N;
-  UR_REQUIRE(B >= 0, "ur_catalog_coarse_select: need B >= 0 (got %d)", B);
-  UR_REQUIRE(N >= 0 && N <= (int64_t)INT32_MAX, "ur_catalog_coarse_select: need 0 <= N <= INT32_MAX (got %lld)", (long long)N);
-  UR_REQUIRE(D > 0 && (D % 8) == 0 && D <= 2048, "ur_catalog_coarse_select: D must be a positive multiple of 8 and <= 2048 (got %d)", D);
   UR_REQUIRE(K >= 1 && K <= UR_CATALOG_TOPK_MAX, "ur_catalog_coarse_select: K must be 1 .. %d (got %d)", UR_CATALOG_TOPK_MAX, K);
-  UR_REQUIRE(a->chunk_rows >= 0 && (a->chunk_rows % SEL_TILE) == 0,
-             "ur_catalog_coarse_select: chunk_rows must be 0 or a positive multiple of %d (got %lld)", SEL_TILE, (long long)a->chunk_rows);
-  UR_REQUIRE(E >= 0 && (E == 0 || a->exclude), "ur_catalog_coarse_select: E > 0 needs exclude");
-  UR_REQUIRE((a->gt_index != nullptr) == (a->rank != nullptr), "ur_catalog_coarse_select: gt_index and rank go together");
   UR_REQUIRE(a->catalog_bf16 == 1, "ur_catalog_coarse_select: catalog_bf16 must be 1, the coarse scorer reads a bf16 catalogue only (got %d)",
              a->catalog_bf16);
   const coarse_plan p = coarse_layout(B, N, D, a->chunk_rows);
@@ -266,19 +247,15 @@ extern "C" int ur_catalog_coarse_select(ur_catalog_coarse_t* a, void* stream) {
     a->workspace_bytes = p.need;
     return 0;
   }
-  UR_REQUIRE(UR_ALIGNED16(a->workspace) && a->workspace_bytes >= p.need,
-             "ur_catalog_coarse_select: workspace must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)p.need,
-             (long long)a->workspace_bytes);
+  if (const int rc = catalog_check_buffers(c, p.need, false)) return rc;
   if (B == 0) return 0;
   UR_REQUIRE(a->topk_index && a->topk_score, "ur_catalog_coarse_select: topk_index / topk_score are null");
-  UR_REQUIRE(a->user && (N == 0 || (a->catalog && a->cat_inv_norm)), "ur_catalog_coarse_select: user / catalog / cat_inv_norm: null pointer");
-  UR_REQUIRE(UR_ALIGNED16(a->user) && UR_ALIGNED16(a->catalog), "ur_catalog_coarse_select: user and catalog must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)a->workspace;
-  bf16_t* ubf = (bf16_t*)ws;
-  float* inv_u = (float*)(ws + p.user_bytes);
-  float* ref = (float*)(ws + p.user_bytes + p.vec_bytes);
-  float* chunk = (float*)(ws + p.user_bytes + 2 * p.vec_bytes);
+  bf16_t* ubf = (bf16_t*)(ws + p.user);
+  float* inv_u = (float*)(ws + p.inv_u);
+  float* ref = (float*)(ws + p.ref);
+  float* chunk = (float*)(ws + p.chunk);
   const bf16_t* cat = (const bf16_t*)a->catalog;
   const long* gt = (const long*)a->gt_index;
   int rc = ur_cast_f32_to_bf16(a->user, ubf, (int64_t)B * D, stream);
@@ -291,19 +268,16 @@ extern "C" int ur_catalog_coarse_select(ur_catalog_coarse_t* a, void* stream) {
     rc = launch_catalog_scores_bf16(ubf, inv_u, cat, a->cat_inv_norm, nullptr, 0, gt, ref, B, N, D, st);
     if (rc != 0) return rc;
   }
-  int64_t c0 = 0;
-  do {                                                         // (N == 0: one pass over an empty chunk writes the empty lists)
-    const int64_t len = N - c0 < p.rows ? N - c0 : p.rows;
+  return catalog_for_each_chunk(N, p.rows, [&](int64_t c0, int64_t len, int first) {
     if (len > 0) {
-      rc = launch_catalog_scores_bf16(ubf, inv_u, cat + c0 * D, a->cat_inv_norm + c0, chunk, (long)len, nullptr, nullptr, B, len, D, st);
+      const int rc = launch_catalog_scores_bf16(ubf, inv_u, cat + c0 * D, a->cat_inv_norm + c0, chunk, (long)len, nullptr, nullptr, B, len, D, st);
       if (rc != 0) return rc;
     }
     hipLaunchKernelGGL(catalog_select_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0, (int)len, (int)K,
-                       a->topk_score, a->topk_index, gt, (const float*)ref, a->rank, (const long*)a->exclude, (int)E, (int)(c0 == 0));
+                       a->topk_score, a->topk_index, gt, (const float*)ref, a->rank, (const long*)a->exclude, (int)E, first);
     UR_CHECK_LAUNCH("ur_catalog_coarse_select");
-    c0 += p.rows;
-  } while (c0 < N);
-  return 0;
+    return 0;
+  });
 }
 
 extern "C" int ur_catalog_rerank(ur_catalog_rerank_t* a, void* stream) {
@@ -318,8 +292,8 @@ extern "C" int ur_catalog_rerank(ur_catalog_rerank_t* a, void* stream) {
              "ur_catalog_rerank: D must be a positive multiple of %d and <= 2048 (got %d)", bf16 ? 8 : 4, D);
   UR_REQUIRE(a->K_in >= 1 && a->K_in <= UR_CATALOG_TOPK_MAX, "ur_catalog_rerank: K_in must be 1 .. %d (got %d)", UR_CATALOG_TOPK_MAX, a->K_in);
   UR_REQUIRE(a->k >= 1 && a->k <= a->K_in, "ur_catalog_rerank: k must be 1 .. K_in = %d (got %d)", a->K_in, a->k);
-  int64_t need = ((int64_t)B * 4 + 15) / 16 * 16;
-  if (need < 16) need = 16;
+  ws_carver carve;                                             // the workspace: inv_u [B], nothing else
+  const int64_t inv_u_at = carve.take((int64_t)B * 4), need = carve.need();
   if (!a->workspace) {
     a->workspace_bytes = need;
     return 0;
@@ -331,19 +305,15 @@ extern "C" int ur_catalog_rerank(ur_catalog_rerank_t* a, void* stream) {
   UR_REQUIRE(a->user && a->catalog && a->cat_inv_norm, "ur_catalog_rerank: user / catalog / cat_inv_norm: null pointer");
   UR_REQUIRE(UR_ALIGNED16(a->user) && UR_ALIGNED16(a->catalog), "ur_catalog_rerank: user and catalog must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  float* inv_u = (float*)a->workspace;
+  float* inv_u = (float*)((char*)a->workspace + inv_u_at);
   hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a->user, inv_u, (long)B, (int)D);
-  if (bf16) {
+  return catalog_dispatch(bf16, a->catalog, [&](auto* cat) {
+    using CT = std::remove_const_t<std::remove_pointer_t<decltype(cat)>>;
     if (!a->cat_norm_ready)
-      hipLaunchKernelGGL(row_inv_norm_kernel<bf16_t>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const bf16_t*)a->catalog, a->cat_inv_norm, (long)N, (int)D);
-    hipLaunchKernelGGL(catalog_rerank_kernel<bf16_t>, dim3((unsigned)B), dim3(256), 0, st, a->user, (const float*)inv_u, (const bf16_t*)a->catalog,
+      hipLaunchKernelGGL(row_inv_norm_kernel<CT>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, cat, a->cat_inv_norm, (long)N, (int)D);
+    hipLaunchKernelGGL(catalog_rerank_kernel<CT>, dim3((unsigned)B), dim3(256), 0, st, a->user, (const float*)inv_u, cat,
                        (const float*)a->cat_inv_norm, a->index, (int)a->K_in, (int)a->k, a->topk_index, a->topk_score, (long)N, (int)D);
-  } else {
-    if (!a->cat_norm_ready)
-      hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const float*)a->catalog, a->cat_inv_norm, (long)N, (int)D);
-    hipLaunchKernelGGL(catalog_rerank_kernel<float>, dim3((unsigned)B), dim3(256), 0, st, a->user, (const float*)inv_u, (const float*)a->catalog,
-                       (const float*)a->cat_inv_norm, a->index, (int)a->K_in, (int)a->k, a->topk_index, a->topk_score, (long)N, (int)D);
-  }
-  UR_CHECK_LAUNCH("ur_catalog_rerank");
-  return 0;
+    UR_CHECK_LAUNCH("ur_catalog_rerank");
+    return 0;
+  });
 }

@@ -161,17 +161,11 @@ __global__ __launch_bounds__(256) void catalog_deep_merge_kernel(const float* __
   }
 }
 
-// workgroups per user's chunk row.  The workspace is laid out for deep_segments_cap (sizes alone: the size query touches no device);
+// workgroups per user's chunk row.  The workspace is laid out for deep_segments_cap (catalog_layout.hip.h);
 // the launch takes no more than that, than ~4 workgroups per compute unit in all, and than the chunk has tiles.  Measured at a million
 // rows and K = 1000 (docs/lab_notes.md section 37): 2 is the best count at 512 users and 8 at 64; 16 at 64 users is 4 % slower again
 // (every list is filled, written back per chunk and merged at the end), so the library stops at DEEP_SEGMENTS_AUTO.
-constexpr int DEEP_SEGMENTS_AUTO = 8;
 static_assert(DEEP_SEGMENTS_AUTO <= UR_CATALOG_DEEP_SEGMENTS_MAX, "the library's own choice is one a caller may force");
-int deep_segments_cap(int32_t segments, int32_t B) {
-  if (segments > 0) return segments;
-  int g = 1024 / (B > 0 ? B : 1);
-  return g < 1 ? 1 : g > DEEP_SEGMENTS_AUTO ? DEEP_SEGMENTS_AUTO : g;
-}
 int deep_segments(int32_t segments, int32_t B, int64_t rows) {
   if (segments > 0) return segments;
   int64_t g = deep_segments_cap(0, B);
@@ -179,24 +173,6 @@ int deep_segments(int32_t segments, int32_t B, int64_t rows) {
   if (g > by_cu) g = by_cu;
   if (g > tiles) g = tiles;
   return g < 1 ? 1 : (int)g;
-}
-
-// the workspace of ur_catalog_deep_select: chunk [B][rows] f32 | ref [B] | inv_u [B] | list scores [B][Gw][K] | list indices | counts [B][Gw]
-struct deep_plan {
-  int64_t rows, chunk_bytes, vec_bytes, list_bytes, count_bytes, need;
-  int gw;
-};
-deep_plan deep_layout(int32_t B, int64_t N, int32_t K, int64_t chunk_rows, int32_t segments) {
-  deep_plan p;
-  p.rows = catalog_chunk_rows(chunk_rows, B, N);
-  p.gw = deep_segments_cap(segments, B);
-  p.chunk_bytes = ((int64_t)B * p.rows * 4 + 15) / 16 * 16;
-  p.vec_bytes = ((int64_t)B * 4 + 15) / 16 * 16;
-  p.list_bytes = ((int64_t)B * p.gw * K * 4 + 15) / 16 * 16;
-  p.count_bytes = ((int64_t)B * p.gw * 4 + 15) / 16 * 16;
-  p.need = p.chunk_bytes + 2 * p.vec_bytes + 2 * p.list_bytes + p.count_bytes;
-  if (p.need < 16) p.need = 16;
-  return p;
 }
 
 }  // namespace

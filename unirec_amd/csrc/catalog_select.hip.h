@@ -1,9 +1,12 @@
 // What the catalogue translation units share (catalog.hip: the exact scorers and the softmax loss; catalog_coarse.hip: the bf16-MFMA
-// shortlist pass and the exact re-rank): the catalogue element loads, the row norms, the total order of the lists and the streaming
-// selection kernel with its chunk-size rule.  Everything here has internal linkage; each unit compiles its own copy of the same text.
+// shortlist pass and the exact re-rank).  Device side: the catalogue element loads, the row norms, the total order of the lists and the
+// streaming selection kernel.  Host side: the argument checks every entry point makes (catalog_call), the f32 / bf16 dispatch and the
+// chunk loop; the workspaces are in catalog_layout.hip.h.  Everything here has internal linkage; each unit compiles its own copy of
+// the same text.
 #pragma once
 #include "common.hip.h"
 #include "unirec_hip.h"
+#include "catalog_layout.hip.h"
 
 namespace {
 
@@ -31,7 +34,6 @@ __global__ void row_inv_norm_kernel(const CT* __restrict__ x, float* __restrict_
 }
 
 // The total order of the lists: score descending, index ascending.  An empty slot is (-inf, SEL_EMPTY): it follows every item.
-constexpr int SEL_TILE = 1024;                 // scores per sweep step: 4 per thread
 constexpr int SEL_SORT_MAX = 2048;             // >= UR_CATALOG_TOPK_MAX + SEL_TILE, a power of two
 constexpr int SEL_EMPTY = 0x7fffffff;
 static_assert(UR_CATALOG_TOPK_MAX + SEL_TILE <= SEL_SORT_MAX, "list + one tile of survivors must fit the sort buffer");
@@ -147,16 +149,66 @@ __global__ __launch_bounds__(256) void catalog_select_kernel(const float* __rest
   }
 }
 
-// rows per chunk of the streaming mode: the caller's figure, or a chunk buffer [B, rows] near 64 MB (so that it can stay in the
-// Infinity Cache between the scoring and the selection launch); never more than N rounded up to the selection tile
-static int64_t catalog_chunk_rows(int64_t chunk_rows, int32_t B, int64_t N) {
-  const int64_t n_up = (N + SEL_TILE - 1) / SEL_TILE * SEL_TILE;
-  int64_t r = chunk_rows;
-  if (r <= 0) r = ((int64_t)64 << 20) / (4 * (int64_t)(B > 0 ? B : 1)) / SEL_TILE * SEL_TILE;
-  if (r > n_up) r = n_up;
-  if (r > ((int64_t)1 << 30)) r = (int64_t)1 << 30;           // the selection kernel indexes a chunk with an int
-  if (r < SEL_TILE) r = SEL_TILE;
-  return r;
+// ---- host side --------------------------------------------------------------------------------------------------------------------
+// What every catalogue entry point takes and checks the same way; each fills it from its own argument struct (a field it does not
+// have stays zero, which passes).  K, segments, temperature and the outputs are the entry point's own business.
+struct catalog_call {
+  const char* who;
+  int32_t B;
+  int64_t N;
+  int32_t D, E;
+  int64_t chunk_rows;
+  int32_t catalog_bf16, scorer;
+  const void *gt, *rank, *exclude, *user, *catalog, *cat_inv_norm, *workspace;
+  int64_t workspace_bytes;
+};
+
+// the checks of the sizes and flags, all before the size query answers.  d_mult: what D must be a multiple of; n_min: the smallest
+// catalogue (0 or 1); gt_needed: the entry point has no rank output and takes gt_index unconditionally (checked with the operands)
+int catalog_check_sizes(const catalog_call& c, int d_mult, int64_t n_min, bool gt_needed) {
+  UR_REQUIRE(c.B >= 0, "%s: need B >= 0 (got %d)", c.who, c.B);
+  UR_REQUIRE(c.N >= n_min && c.N <= (int64_t)INT32_MAX, "%s: need %lld <= N <= INT32_MAX (got %lld)", c.who, (long long)n_min, (long long)c.N);
+  UR_REQUIRE(c.D > 0 && (c.D % d_mult) == 0 && c.D <= 2048, "%s: D must be a positive multiple of %d and <= 2048 (got %d)", c.who, d_mult, c.D);
+  UR_REQUIRE(c.chunk_rows >= 0 && (c.chunk_rows % SEL_TILE) == 0, "%s: chunk_rows must be 0 or a positive multiple of %d (got %lld)", c.who,
+             SEL_TILE, (long long)c.chunk_rows);
+  UR_REQUIRE(c.E >= 0 && (c.E == 0 || c.exclude), "%s: E > 0 needs exclude", c.who);
+  UR_REQUIRE(gt_needed || (c.gt != nullptr) == (c.rank != nullptr), "%s: gt_index and rank go together", c.who);
+  UR_REQUIRE(c.catalog_bf16 == 0 || c.catalog_bf16 == 1, "%s: catalog_bf16 must be 0 or 1 (got %d)", c.who, c.catalog_bf16);
+  UR_REQUIRE(c.scorer >= 0 && c.scorer <= UR_CATALOG_SCORER_MFMA, "%s: scorer must be 0 (the library chooses), 1 (vector) or 2 (f32 MFMA) (got %d)",
+             c.who, c.scorer);
+  return 0;
+}
+
+// the checks of a call that brings its workspace (`need` bytes, from the layout): the workspace, then -- unless B == 0, when the call
+// is a no-op that needs no buffer -- the operands
+int catalog_check_buffers(const catalog_call& c, int64_t need, bool gt_needed) {
+  UR_REQUIRE(UR_ALIGNED16(c.workspace) && c.workspace_bytes >= need, "%s: workspace must be 16-byte aligned and hold %lld bytes (got %lld)", c.who,
+             (long long)need, (long long)c.workspace_bytes);
+  if (c.B == 0) return 0;
+  UR_REQUIRE(c.user && (c.N == 0 || (c.catalog && c.cat_inv_norm)) && (!gt_needed || c.gt), "%s: user / catalog / cat_inv_norm / gt_index: null pointer",
+             c.who);
+  UR_REQUIRE(UR_ALIGNED16(c.user) && UR_ALIGNED16(c.catalog), "%s: user and catalog must be 16-byte aligned", c.who);
+  return 0;
+}
+
+// f(catalogue as const float* or const bf16_t*): the one place the catalog_bf16 flag becomes a type
+template <typename F>
+int catalog_dispatch(bool bf16, const void* catalog, F&& f) {
+  return bf16 ? f((const bf16_t*)catalog) : f((const float*)catalog);
+}
+
+// body(c0, len, first) per chunk of `rows` catalogue rows, until one returns non-zero.  N == 0 still makes one pass, with len == 0:
+// the selection launch of that pass writes the empty lists.
+template <typename F>
+int catalog_for_each_chunk(int64_t N, int64_t rows, F&& body) {
+  int64_t c0 = 0;
+  do {
+    const int64_t len = N - c0 < rows ? N - c0 : rows;
+    const int rc = body(c0, len, (int)(c0 == 0));
+    if (rc != 0) return rc;
+    c0 += rows;
+  } while (c0 < N);
+  return 0;
 }
 
 }  // namespace

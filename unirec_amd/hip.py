@@ -1313,6 +1313,72 @@ def catalog_scorer_id(scorer):
     return CATALOG_SCORERS[scorer]
 
 
+# What the five catalogue wrappers below share.  `who` is the wrapper's own name, in every message.
+def _catalog_norm(cat_inv_norm, N, dev, who):
+    """(cat_inv_norm, cat_norm_ready): the caller's inverse norms [N] f32, or a buffer for the library to fill"""
+    if cat_inv_norm is None:
+        return torch.empty((N,), dtype=F32, device=dev), 0
+    if cat_inv_norm.dtype != F32 or cat_inv_norm.shape != (N,):
+        raise ValueError(f"{who}: cat_inv_norm must be f32 of shape [{N}], got {cat_inv_norm.dtype} {tuple(cat_inv_norm.shape)}")
+    _need(cat_inv_norm, F32, "cat_inv_norm")
+    return cat_inv_norm, 1
+
+
+def _catalog_operands(who, user, catalog, cat_inv_norm):
+    """The operand checks: catalog's dtype, user [B,D] f32 and catalog [N,D] sharing D, cat_inv_norm [N] f32 -- the shapes first, as
+    ValueErrors, so that a call which would be read out of bounds is refused whatever else is wrong with it -- then device and contiguity.
+    Returns (B, N, D, device, cat_inv_norm, cat_norm_ready)."""
+    if catalog.dtype not in (F32, BF16):
+        raise ValueError(f"{who}: catalog must be f32 or bf16, got {catalog.dtype}")
+    if user.dim() != 2 or catalog.dim() != 2 or catalog.shape[1] != user.shape[1]:
+        raise ValueError(f"{who}: user [B,D] and catalog [N,D] must share D, got {tuple(user.shape)} and {tuple(catalog.shape)}")
+    (B, D), N = user.shape, catalog.shape[0]
+    cat_inv_norm, ready = _catalog_norm(cat_inv_norm, N, user.device, who)
+    _need(user, F32, "user")
+    _need(catalog, catalog.dtype, "catalog")
+    return B, N, D, user.device, cat_inv_norm, ready
+
+
+def _catalog_lists(a, B, K, dev):
+    """the output lists [B,K] of a call, entered into its argument struct"""
+    idx = torch.empty((B, max(K, 0)), dtype=torch.int32, device=dev)
+    val = torch.empty((B, max(K, 0)), dtype=F32, device=dev)
+    a.topk_index, a.topk_score = idx.data_ptr(), val.data_ptr()
+    return idx, val
+
+
+def _catalog_filters(who, a, B, dev, gt_index, exclude, want_rank=True):
+    """gt_index [B] (with the rank output it asks for, unless want_rank is False) and exclude [B,E], entered into the argument struct.
+    Returns (gt, rank): gt is the tensor the struct points to and must outlive the call."""
+    gt = rank = None
+    if gt_index is not None:
+        gt = gt_index.to(device=dev, dtype=torch.int64).contiguous()
+        if gt.shape != (B,):
+            raise ValueError(f"{who}: gt_index must have shape [{B}], got {tuple(gt.shape)}")
+        a.gt_index = gt.data_ptr()
+        if want_rank:
+            rank = torch.empty((B,), dtype=torch.int32, device=dev)
+            a.rank = rank.data_ptr()
+    if exclude is not None:
+        _need(exclude, torch.int64, "exclude")
+        if exclude.dim() != 2 or exclude.shape[0] != B:
+            raise ValueError(f"{who}: exclude must be [{B}, E], got {tuple(exclude.shape)}")
+        a.E = exclude.shape[1]
+        a.exclude = exclude.data_ptr() if a.E else None
+    return gt, rank
+
+
+def _catalog_call(entry, a, dev, tag, *args):
+    """entry(*args, &a, stream) twice: the size query (a.workspace is NULL), then the call with workspace(tag)"""
+    fn = getattr(_lib.load(), entry)
+
+    def call():
+        check(fn(*args, ctypes.byref(a), _stream()), entry)
+    call()
+    a.workspace = workspace(a.workspace_bytes, dev, tag).data_ptr()
+    call()
+
+
 def catalog_select(user, catalog, K, cat_inv_norm=None, gt_index=None, exclude=None, chunk_rows=None, scorer=None):
     """Streaming retrieval over a shared catalogue [N,D] f32 or bf16 (ur_catalog_scores with a ur_catalog_select_t): the K best items per
     user of user [B,D] f32 under catalog_scores' own f32 scores, descending, lowest index first among equal scores; no [B,N] tensor
@@ -1324,42 +1390,15 @@ def catalog_select(user, catalog, K, cat_inv_norm=None, gt_index=None, exclude=N
     Returns (topk_index int32 [B,K], topk_score f32 [B,K], rank int32 [B] or None, cat_inv_norm); with fewer than K candidates the
     tail of a row is index -1, score -inf."""
     scorer_id = catalog_scorer_id(scorer)
-    lib = _lib.load()
-    _need(user, F32, "user")
-    if catalog.dtype not in (F32, BF16):
-        raise ValueError(f"catalog_select: catalog must be f32 or bf16, got {catalog.dtype}")
-    _need(catalog, catalog.dtype, "catalog")
-    B, D = user.shape
-    N = catalog.shape[0]
-    dev = user.device
+    B, N, D, dev, cat_inv_norm, ready = _catalog_operands("catalog_select", user, catalog, cat_inv_norm)
     sel = CatalogSelect()
     sel.K, sel.chunk_rows = int(K), int(chunk_rows or 0)
     sel.catalog_bf16, sel.scorer = int(catalog.dtype == BF16), scorer_id
-    idx = torch.empty((B, max(int(K), 0)), dtype=torch.int32, device=dev)
-    val = torch.empty((B, max(int(K), 0)), dtype=F32, device=dev)
-    sel.topk_index, sel.topk_score = idx.data_ptr(), val.data_ptr()
-    rank = gt = None
-    if gt_index is not None:
-        gt = gt_index.to(device=dev, dtype=torch.int64).contiguous()
-        if gt.shape != (B,):
-            raise ValueError(f"catalog_select: gt_index must have shape [{B}], got {tuple(gt.shape)}")
-        rank = torch.empty((B,), dtype=torch.int32, device=dev)
-        sel.gt_index, sel.rank = gt.data_ptr(), rank.data_ptr()
-    if exclude is not None:
-        _need(exclude, torch.int64, "exclude")
-        if exclude.dim() != 2 or exclude.shape[0] != B:
-            raise ValueError(f"catalog_select: exclude must be [{B}, E], got {tuple(exclude.shape)}")
-        sel.E = exclude.shape[1]
-        sel.exclude = exclude.data_ptr() if sel.E else None
+    idx, val = _catalog_lists(sel, B, sel.K, dev)
+    gt, rank = _catalog_filters("catalog_select", sel, B, dev, gt_index, exclude)
     uinv = torch.empty((B,), dtype=F32, device=dev)
-    ready = cat_inv_norm is not None
-    if not ready:
-        cat_inv_norm = torch.empty((N,), dtype=F32, device=dev)
-    args = (user.data_ptr(), catalog.data_ptr(), None, uinv.data_ptr(), cat_inv_norm.data_ptr(), int(ready), B, N, D)
-    check(lib.ur_catalog_scores(*args, ctypes.byref(sel), _stream()), "ur_catalog_scores")        # size query: workspace is NULL
-    ws = workspace(sel.workspace_bytes, dev, "catalog_select")
-    sel.workspace = ws.data_ptr()
-    check(lib.ur_catalog_scores(*args, ctypes.byref(sel), _stream()), "ur_catalog_scores")
+    _catalog_call("ur_catalog_scores", sel, dev, "catalog_select",
+                  user.data_ptr(), catalog.data_ptr(), None, uinv.data_ptr(), cat_inv_norm.data_ptr(), ready, B, N, D)
     return idx, val, rank, cat_inv_norm
 
 
@@ -1375,55 +1414,18 @@ def catalog_deep_select(user, catalog, K, cat_inv_norm=None, gt_index=None, excl
     outputs do not depend on it.
     Returns (topk_index int32 [B,K], topk_score f32 [B,K], rank int32 [B] or None, cat_inv_norm)."""
     scorer_id = catalog_scorer_id(scorer)
-    if catalog.dtype not in (F32, BF16):
-        raise ValueError(f"catalog_deep_select: catalog must be f32 or bf16, got {catalog.dtype}")
-    lib = _lib.load()
-    _need(user, F32, "user")
-    _need(catalog, catalog.dtype, "catalog")
-    if user.dim() != 2 or catalog.dim() != 2 or catalog.shape[1] != user.shape[1]:
-        raise ValueError(f"catalog_deep_select: user [B,D] and catalog [N,D] must share D, got {tuple(user.shape)} and {tuple(catalog.shape)}")
-    B, D = user.shape
-    N = catalog.shape[0]
-    dev = user.device
     a = _lib.CatalogDeep()
-    a.user, a.catalog, a.catalog_bf16, a.scorer = user.data_ptr(), catalog.data_ptr(), int(catalog.dtype == BF16), scorer_id
-    a.B, a.N, a.D, a.K, a.chunk_rows, a.segments = B, N, D, int(K), int(chunk_rows or 0), int(segments or 0)
-    idx = torch.empty((B, max(int(K), 0)), dtype=torch.int32, device=dev)
-    val = torch.empty((B, max(int(K), 0)), dtype=F32, device=dev)
-    a.topk_index, a.topk_score = idx.data_ptr(), val.data_ptr()
-    rank = gt = None
-    if gt_index is not None:
-        gt = gt_index.to(device=dev, dtype=torch.int64).contiguous()
-        if gt.shape != (B,):
-            raise ValueError(f"catalog_deep_select: gt_index must have shape [{B}], got {tuple(gt.shape)}")
-        rank = torch.empty((B,), dtype=torch.int32, device=dev)
-        a.gt_index, a.rank = gt.data_ptr(), rank.data_ptr()
-    if exclude is not None:
-        _need(exclude, torch.int64, "exclude")
-        if exclude.dim() != 2 or exclude.shape[0] != B:
-            raise ValueError(f"catalog_deep_select: exclude must be [{B}, E], got {tuple(exclude.shape)}")
-        a.E = exclude.shape[1]
-        a.exclude = exclude.data_ptr() if a.E else None
-    cat_inv_norm, a.cat_norm_ready = _catalog_norm(cat_inv_norm, N, dev, "catalog_deep_select")
-    a.cat_inv_norm = cat_inv_norm.data_ptr()
-    check(lib.ur_catalog_deep_select(ctypes.byref(a), _stream()), "ur_catalog_deep_select")        # size query: workspace is NULL
-    ws = workspace(a.workspace_bytes, dev, "catalog_deep")
-    a.workspace = ws.data_ptr()
-    check(lib.ur_catalog_deep_select(ctypes.byref(a), _stream()), "ur_catalog_deep_select")
+    a.B, a.N, a.D, dev, cat_inv_norm, a.cat_norm_ready = _catalog_operands("catalog_deep_select", user, catalog, cat_inv_norm)
+    a.user, a.catalog, a.cat_inv_norm = user.data_ptr(), catalog.data_ptr(), cat_inv_norm.data_ptr()
+    a.catalog_bf16, a.scorer = int(catalog.dtype == BF16), scorer_id
+    a.K, a.chunk_rows, a.segments = int(K), int(chunk_rows or 0), int(segments or 0)
+    idx, val = _catalog_lists(a, a.B, a.K, dev)
+    gt, rank = _catalog_filters("catalog_deep_select", a, a.B, dev, gt_index, exclude)
+    _catalog_call("ur_catalog_deep_select", a, dev, "catalog_deep")
     return idx, val, rank, cat_inv_norm
 
 
 COARSE_USER_GROUP = _lib.COARSE_USER_GROUP      # users a workgroup of the coarse scorer stages (half of it when D > 1024)
-
-
-def _catalog_norm(cat_inv_norm, N, dev, who):
-    ready = cat_inv_norm is not None
-    if not ready:
-        return torch.empty((N,), dtype=F32, device=dev), 0
-    _need(cat_inv_norm, F32, "cat_inv_norm")
-    if cat_inv_norm.shape != (N,):
-        raise ValueError(f"{who}: cat_inv_norm must have shape [{N}], got {tuple(cat_inv_norm.shape)}")
-    return cat_inv_norm, 1
 
 
 def catalog_coarse_select(user, catalog, K, cat_inv_norm=None, gt_index=None, exclude=None, chunk_rows=None):
@@ -1435,39 +1437,13 @@ def catalog_coarse_select(user, catalog, K, cat_inv_norm=None, gt_index=None, ex
     Returns (topk_index int32 [B,K], topk_score f32 [B,K], rank int32 [B] or None, cat_inv_norm)."""
     if catalog.dtype != BF16:
         raise ValueError(f"catalog_coarse_select: the coarse scorer reads a bf16 catalogue (CatalogEvaluator(dtype=torch.bfloat16)), got {catalog.dtype}")
-    lib = _lib.load()
-    _need(user, F32, "user")
-    _need(catalog, BF16, "catalog")
-    if user.dim() != 2 or catalog.dim() != 2 or catalog.shape[1] != user.shape[1]:
-        raise ValueError(f"catalog_coarse_select: user [B,D] and catalog [N,D] must share D, got {tuple(user.shape)} and {tuple(catalog.shape)}")
-    B, D = user.shape
-    N = catalog.shape[0]
-    dev = user.device
     a = _lib.CatalogCoarse()
-    a.user, a.catalog, a.catalog_bf16 = user.data_ptr(), catalog.data_ptr(), 1
-    a.B, a.N, a.D, a.K, a.chunk_rows = B, N, D, int(K), int(chunk_rows or 0)
-    idx = torch.empty((B, max(int(K), 0)), dtype=torch.int32, device=dev)
-    val = torch.empty((B, max(int(K), 0)), dtype=F32, device=dev)
-    a.topk_index, a.topk_score = idx.data_ptr(), val.data_ptr()
-    rank = gt = None
-    if gt_index is not None:
-        gt = gt_index.to(device=dev, dtype=torch.int64).contiguous()
-        if gt.shape != (B,):
-            raise ValueError(f"catalog_coarse_select: gt_index must have shape [{B}], got {tuple(gt.shape)}")
-        rank = torch.empty((B,), dtype=torch.int32, device=dev)
-        a.gt_index, a.rank = gt.data_ptr(), rank.data_ptr()
-    if exclude is not None:
-        _need(exclude, torch.int64, "exclude")
-        if exclude.dim() != 2 or exclude.shape[0] != B:
-            raise ValueError(f"catalog_coarse_select: exclude must be [{B}, E], got {tuple(exclude.shape)}")
-        a.E = exclude.shape[1]
-        a.exclude = exclude.data_ptr() if a.E else None
-    cat_inv_norm, a.cat_norm_ready = _catalog_norm(cat_inv_norm, N, dev, "catalog_coarse_select")
-    a.cat_inv_norm = cat_inv_norm.data_ptr()
-    check(lib.ur_catalog_coarse_select(ctypes.byref(a), _stream()), "ur_catalog_coarse_select")        # size query: workspace is NULL
-    ws = workspace(a.workspace_bytes, dev, "catalog_coarse")
-    a.workspace = ws.data_ptr()
-    check(lib.ur_catalog_coarse_select(ctypes.byref(a), _stream()), "ur_catalog_coarse_select")
+    a.B, a.N, a.D, dev, cat_inv_norm, a.cat_norm_ready = _catalog_operands("catalog_coarse_select", user, catalog, cat_inv_norm)
+    a.user, a.catalog, a.cat_inv_norm, a.catalog_bf16 = user.data_ptr(), catalog.data_ptr(), cat_inv_norm.data_ptr(), 1
+    a.K, a.chunk_rows = int(K), int(chunk_rows or 0)
+    idx, val = _catalog_lists(a, a.B, a.K, dev)
+    gt, rank = _catalog_filters("catalog_coarse_select", a, a.B, dev, gt_index, exclude)
+    _catalog_call("ur_catalog_coarse_select", a, dev, "catalog_coarse")
     return idx, val, rank, cat_inv_norm
 
 
@@ -1476,33 +1452,17 @@ def catalog_rerank(user, catalog, index, k=None, cat_inv_norm=None):
     (-1) an empty slot.  Every pair is scored by catalog_scores' own f32 chain -- the bits catalog_scores / catalog_select give for it --
     and each row is sorted under their total order (score descending, index ascending); the first k (default K') are returned, empty
     slots at the tail as (-1, -inf).  Returns (topk_index int32 [B,k], topk_score f32 [B,k], cat_inv_norm)."""
-    if catalog.dtype not in (F32, BF16):
-        raise ValueError(f"catalog_rerank: catalog must be f32 or bf16, got {catalog.dtype}")
-    lib = _lib.load()
-    _need(user, F32, "user")
-    _need(catalog, catalog.dtype, "catalog")
-    _need(index, torch.int32, "index")
-    if user.dim() != 2 or catalog.dim() != 2 or catalog.shape[1] != user.shape[1]:
-        raise ValueError(f"catalog_rerank: user [B,D] and catalog [N,D] must share D, got {tuple(user.shape)} and {tuple(catalog.shape)}")
-    B, D = user.shape
-    N = catalog.shape[0]
-    if index.dim() != 2 or index.shape[0] != B:
-        raise ValueError(f"catalog_rerank: index must be [{B}, K'], got {tuple(index.shape)}")
-    dev = user.device
     a = _lib.CatalogRerank()
-    a.user, a.catalog, a.catalog_bf16 = user.data_ptr(), catalog.data_ptr(), int(catalog.dtype == BF16)
-    a.B, a.N, a.D = B, N, D
+    a.B, a.N, a.D, dev, cat_inv_norm, a.cat_norm_ready = _catalog_operands("catalog_rerank", user, catalog, cat_inv_norm)
+    a.user, a.catalog, a.cat_inv_norm = user.data_ptr(), catalog.data_ptr(), cat_inv_norm.data_ptr()
+    a.catalog_bf16 = int(catalog.dtype == BF16)
+    _need(index, torch.int32, "index")
+    if index.dim() != 2 or index.shape[0] != a.B:
+        raise ValueError(f"catalog_rerank: index must be [{a.B}, K'], got {tuple(index.shape)}")
     a.index, a.K_in = index.data_ptr(), index.shape[1]
     a.k = index.shape[1] if k is None else int(k)
-    idx = torch.empty((B, max(a.k, 0)), dtype=torch.int32, device=dev)
-    val = torch.empty((B, max(a.k, 0)), dtype=F32, device=dev)
-    a.topk_index, a.topk_score = idx.data_ptr(), val.data_ptr()
-    cat_inv_norm, a.cat_norm_ready = _catalog_norm(cat_inv_norm, N, dev, "catalog_rerank")
-    a.cat_inv_norm = cat_inv_norm.data_ptr()
-    check(lib.ur_catalog_rerank(ctypes.byref(a), _stream()), "ur_catalog_rerank")        # size query: workspace is NULL
-    ws = workspace(a.workspace_bytes, dev, "catalog_rerank")
-    a.workspace = ws.data_ptr()
-    check(lib.ur_catalog_rerank(ctypes.byref(a), _stream()), "ur_catalog_rerank")
+    idx, val = _catalog_lists(a, a.B, a.k, dev)
+    _catalog_call("ur_catalog_rerank", a, dev, "catalog_rerank")
     return idx, val, cat_inv_norm
 
 
@@ -1515,48 +1475,18 @@ def catalog_softmax(user, catalog, gt_index, temperature, cat_inv_norm=None, exc
     not depend on the scorer).  need_grad=False runs the forward pass alone.
     Returns (loss f32 [1], row_loss f32 [B], lse f32 [B], d_user f32 [B,D] or None, cat_inv_norm)."""
     scorer_id = catalog_scorer_id(scorer)
-    lib = _lib.load()
-    _need(user, F32, "user")
-    if catalog.dtype not in (F32, BF16):
-        raise ValueError(f"catalog_softmax: catalog must be f32 or bf16, got {catalog.dtype}")
-    _need(catalog, catalog.dtype, "catalog")
-    if user.dim() != 2 or catalog.dim() != 2 or catalog.shape[1] != user.shape[1]:
-        raise ValueError(f"catalog_softmax: user [B,D] and catalog [N,D] must share D, got {tuple(user.shape)} and {tuple(catalog.shape)}")
-    B, D = user.shape
-    N = catalog.shape[0]
-    dev = user.device
     a = _lib.CatalogSoftmax()
-    a.user, a.catalog, a.catalog_bf16 = user.data_ptr(), catalog.data_ptr(), int(catalog.dtype == BF16)
-    a.B, a.N, a.D = B, N, D
-    a.temperature, a.grad_scale = float(temperature), float(grad_scale)
-    a.chunk_rows, a.scorer = int(chunk_rows or 0), scorer_id
-    gt = gt_index.to(device=dev, dtype=torch.int64).contiguous()
-    if gt.shape != (B,):
-        raise ValueError(f"catalog_softmax: gt_index must have shape [{B}], got {tuple(gt.shape)}")
-    a.gt_index = gt.data_ptr()
-    if exclude is not None:
-        _need(exclude, torch.int64, "exclude")
-        if exclude.dim() != 2 or exclude.shape[0] != B:
-            raise ValueError(f"catalog_softmax: exclude must be [{B}, E], got {tuple(exclude.shape)}")
-        a.E = exclude.shape[1]
-        a.exclude = exclude.data_ptr() if a.E else None
+    a.B, a.N, a.D, dev, cat_inv_norm, a.cat_norm_ready = _catalog_operands("catalog_softmax", user, catalog, cat_inv_norm)
+    a.user, a.catalog, a.cat_inv_norm = user.data_ptr(), catalog.data_ptr(), cat_inv_norm.data_ptr()
+    a.catalog_bf16, a.scorer = int(catalog.dtype == BF16), scorer_id
+    a.temperature, a.grad_scale, a.chunk_rows = float(temperature), float(grad_scale), int(chunk_rows or 0)
+    gt, _ = _catalog_filters("catalog_softmax", a, a.B, dev, gt_index, exclude, want_rank=False)
     loss = torch.empty((1,), dtype=F32, device=dev)
-    row_loss = torch.empty((B,), dtype=F32, device=dev)
-    lse = torch.empty((B,), dtype=F32, device=dev)
-    d_user = torch.empty((B, D), dtype=F32, device=dev) if need_grad else None
+    row_loss = torch.empty((a.B,), dtype=F32, device=dev)
+    lse = torch.empty((a.B,), dtype=F32, device=dev)
+    d_user = torch.empty((a.B, a.D), dtype=F32, device=dev) if need_grad else None
     a.loss, a.row_loss, a.lse, a.d_user = loss.data_ptr(), row_loss.data_ptr(), lse.data_ptr(), _p(d_user) or None
-    ready = cat_inv_norm is not None
-    if not ready:
-        cat_inv_norm = torch.empty((N,), dtype=F32, device=dev)
-    else:
-        _need(cat_inv_norm, F32, "cat_inv_norm")
-        if cat_inv_norm.shape != (N,):
-            raise ValueError(f"catalog_softmax: cat_inv_norm must have shape [{N}], got {tuple(cat_inv_norm.shape)}")
-    a.cat_inv_norm, a.cat_norm_ready = cat_inv_norm.data_ptr(), int(ready)
-    check(lib.ur_catalog_softmax(ctypes.byref(a), _stream()), "ur_catalog_softmax")        # size query: workspace is NULL
-    ws = workspace(a.workspace_bytes, dev, "catalog_softmax")
-    a.workspace = ws.data_ptr()
-    check(lib.ur_catalog_softmax(ctypes.byref(a), _stream()), "ur_catalog_softmax")
+    _catalog_call("ur_catalog_softmax", a, dev, "catalog_softmax")
     return loss, row_loss, lse, d_user, cat_inv_norm
 
 
