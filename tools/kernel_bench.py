@@ -6,6 +6,7 @@ shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
     python tools/kernel_bench.py catalog --B 512 --N 1000000 --K 100 --scorer vector mfma --catalog-dtype bf16
     python tools/kernel_bench.py catalog --K 1000 --dtypes f32 bf16 --users 512 64 [--N 1000000] [--D 1024] [--rounds 5] [--segments 1 4 16]
     python tools/kernel_bench.py catalog --shortlist 128 --catalog-dtype bf16 [--N 1000000] [--D 1024] [--rounds 3]
+    python tools/kernel_bench.py catalog --two-stage-shortlist 1024 --K 1000 --catalog-dtype bf16 [--users 512 64] [--rounds 5]
     python tools/kernel_bench.py negatives --B 64 --P 1000 --N 1000000 --K 128 [--catalog-dtype f32|bf16] [--rounds 3]
     python tools/kernel_bench.py catalog_softmax --users 64 512 --dtypes f32 bf16 --N 1000000 [--D 1024] [--rounds 5]
     python tools/kernel_bench.py merge --B 64 --S 2048 [--layers 28] [--rank 16] [--rounds 5] [--iters 2]
@@ -266,6 +267,8 @@ def catalog(args):
     --scorer vector mfma times retrieve() once per named scorer instead (alternating in this process, the library's own choice last);
     --catalog-dtype bf16 keeps the catalogue in bf16, where evaluate() does not exist and the first scorer named is the reference."""
     from unirec_amd.evaluation import CatalogEvaluator
+    if args.two_stage_shortlist:
+        return catalog_two_stage(args)
     if args.shortlist:
         return catalog_shortlist(args)
     if args.K > hip.CATALOG_TOPK_MAX:
@@ -438,6 +441,78 @@ def catalog_shortlist(args):
         spread = max(max(times[a]) - min(times[a]), max(times[b]) - min(times[b]))
         print(f"  exact / two-stage = {med[a] / med[b]:.2f}x  (difference {gap:.2f} ms against a spread of {spread:.2f} ms: "
               f"{'faster by more than the spread' if gap > spread else 'NOT faster by more than the spread'})")
+
+
+def catalog_two_stage(args):
+    """CatalogEvaluator.retrieve_two_stage(k=--K, shortlist=--two-stage-shortlist) against the exact retrieve(k=--K) on the same bf16
+    catalogue, per user count (--users, default 512 and 64), alternating --rounds times in this process after one call of each; with a
+    shortlist of at most 128 the older retrieve(k, shortlist=) alternates as a third contender.  Wall time of the whole call (each ends in
+    a host read of the metrics), the ratio of the medians against the alternation's spread, the recall of the two-stage list against the
+    exact one and the share of users whose whole list is identical, the two stages timed on their own (hip.catalog_coarse_deep_select,
+    hip.catalog_deep_rerank), the workspaces the size queries report and the peak allocation of the two-stage call."""
+    import ctypes
+    from unirec_amd import _lib
+    from unirec_amd.evaluation import CatalogEvaluator
+    N, D, S, K = args.N, args.D, args.two_stage_shortlist, args.K
+    if args.catalog_dtype != "bf16":
+        raise SystemExit("catalog --two-stage-shortlist: the coarse scorer reads a bf16 catalogue; add --catalog-dtype bf16")
+    g = torch.Generator(device="cuda").manual_seed(0)
+    cat = torch.randn(N, D, generator=g, device="cuda").to(torch.bfloat16)
+    ev = CatalogEvaluator(cat, dtype=cat.dtype)
+    del cat
+    print(f"catalog --two-stage-shortlist {S} --K {K}: N={N} D={D}, catalogue bf16 {N * D * 2 / 2**20:.0f} MiB, {args.rounds} alternating rounds")
+    for B in (args.users or [512, 64]):
+        user = torch.randn(B, D, generator=g, device="cuda")
+        gt = torch.randint(0, N, (B,), generator=g, device="cuda")
+        ev.retrieve(user[:1], k=1)                            # the catalogue norms: cached by every path, outside every figure below
+        exact_name, two_name = f"exact retrieve(k={K})", f"retrieve_two_stage(k={K}, shortlist={S})"
+        variants = [(exact_name, lambda: ev.retrieve(user, k=K, gt_index=gt)),
+                    (two_name, lambda: ev.retrieve_two_stage(user, k=K, shortlist=S, gt_index=gt))]
+        if S <= hip.CATALOG_TOPK_MAX:
+            variants.append((f"retrieve(k={K}, shortlist={S})", lambda: ev.retrieve(user, k=K, gt_index=gt, shortlist=S)))
+        short = hip.catalog_coarse_deep_select(user, ev.catalog, S, ev._inv, gt_index=gt)[0]
+        variants += [("  coarse-deep select alone", lambda: hip.catalog_coarse_deep_select(user, ev.catalog, S, ev._inv, gt_index=gt)),
+                     ("  deep re-rank alone", lambda: hip.catalog_deep_rerank(user, ev.catalog, short, K, ev._inv))]
+        exact = variants[0][1]()
+        hip._ws_cache.clear()
+        torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        two = variants[1][1]()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        for name, fn in variants:                             # scratch of every variant warm again
+            fn()
+        hit = (two["topk_index"][:, :, None] == exact["topk_index"][:, None, :]).any(2).float().mean().item()
+        same = (two["topk_index"] == exact["topk_index"]).all(1).float().mean().item()
+        bits = torch.equal(two["topk_score"].view(torch.int32)[two["topk_index"] == exact["topk_index"]],
+                           exact["topk_score"].view(torch.int32)[two["topk_index"] == exact["topk_index"]])
+        qs, qr = _lib.CatalogCoarseDeep(), _lib.CatalogDeepRerank()
+        qs.B, qs.N, qs.D, qs.K, qs.catalog_bf16 = B, N, D, S, 1
+        qr.B, qr.N, qr.D, qr.K_in, qr.k, qr.catalog_bf16 = B, N, D, S, K, 1
+        _lib.check(_lib.load().ur_catalog_coarse_deep_select(ctypes.byref(qs), None), "ur_catalog_coarse_deep_select")
+        _lib.check(_lib.load().ur_catalog_deep_rerank(ctypes.byref(qr), None), "ur_catalog_deep_rerank")
+        times = {name: [] for name, _ in variants}
+        for _ in range(args.rounds):
+            for name, fn in variants:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                times[name].append((time.perf_counter() - t0) * 1e3)
+        print(f"B={B} K={K} shortlist={S}: recall@{K} of the two-stage list against the exact one {hit:.6f}; users whose whole list is identical "
+              f"{same:.4f}; score bits equal where the items agree: {bits}")
+        print(f"  workspace (size queries): select {qs.workspace_bytes / 2**20:.2f} MiB, re-rank {qr.workspace_bytes / 2**20:.2f} MiB; peak allocation "
+              f"of the two-stage call {peak / 2**20:.2f} MiB; scores [B,N] f32 would be {B * N * 4 / 2**20:.0f} MiB")
+        med = {}
+        for name, _ in variants:
+            t = sorted(times[name])
+            med[name] = t[len(t) // 2]
+            print(f"  {name:44s}: median {med[name]:9.2f} ms  min {t[0]:9.2f}  max {t[-1]:9.2f}  (spread {t[-1] - t[0]:.2f} over {len(t)} alternating rounds)")
+        for a in [v[0] for v in variants[:-2] if v[0] != two_name]:
+            gap = med[a] - med[two_name]
+            spread = max(max(times[a]) - min(times[a]), max(times[two_name]) - min(times[two_name]))
+            print(f"  {a.strip()} / two-stage = {med[a] / med[two_name]:.2f}x  (difference {gap:.2f} ms against a spread of {spread:.2f} ms: "
+                  f"{'faster by more than the spread' if gap > spread else 'NOT faster by more than the spread'})")
 
 
 def negatives(args):
@@ -698,6 +773,8 @@ if __name__ == "__main__":
     ap.add_argument("--chunks", action="store_true", help="catalog: also time retrieve() at half and double the default rows per chunk")
     ap.add_argument("--scorer", nargs="+", choices=["vector", "mfma"], help="catalog: time retrieve() with each of these scorers, alternating")
     ap.add_argument("--shortlist", type=int, default=0, help="catalog: time retrieve(shortlist=...) against the exact retrieve() at (512, 100) and (64, 10)")
+    ap.add_argument("--two-stage-shortlist", type=int, default=0,
+                    help="catalog: time retrieve_two_stage(k=--K, shortlist=...) against the exact retrieve(k=--K) per --users (default 512 and 64)")
     ap.add_argument("--segments", type=int, nargs="+", help="catalog with --K above 128: also time the long-list call with each of these workgroup counts per user forced")
     ap.add_argument("--catalog-dtype", choices=["f32", "bf16"], default="f32", help="catalog: the dtype the catalogue is stored in")
     ap.add_argument("--users", type=int, nargs="+", help="catalog_softmax: the user counts to time (default: --B)")

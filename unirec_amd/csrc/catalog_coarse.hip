@@ -6,11 +6,21 @@
 //                              mode, unchanged) folds it into the lists and the rank counts.
 //   ur_catalog_rerank        : the EXACT scores of a shortlist, catalog_scores_kernel's own chain per (user, slot), sorted per user.
 //
-// The header holds the definitions in full; the comments here are about the placement.
+// Long two-stage retrieval (include/unirec_hip_coarse_deep.h), the same two halves with lists of up to 1024 items:
+//
+//   ur_catalog_coarse_deep_select : the cast, norms, diagonal launch and chunk launches of ur_catalog_coarse_select, each chunk folded by
+//                                   catalog_deep_sweep_kernel and the lists joined by catalog_deep_merge_kernel (catalog_deep.hip.h, the
+//                                   kernels of ur_catalog_deep_select, unchanged; this unit compiles its own copy as catalog.hip does).
+//   ur_catalog_deep_rerank        : the same chain per (user, slot) in a launch of its own, one wave per pair, then one workgroup per
+//                                   user sorts up to 1024 pairs.
+//
+// The headers hold the definitions in full; the comments here are about the placement.
 #include "common.hip.h"
 #include "unirec_hip.h"
 #include "unirec_hip_coarse.h"
+#include "unirec_hip_coarse_deep.h"
 #include "catalog_select.hip.h"
+#include "catalog_deep.hip.h"
 
 namespace {
 
@@ -203,6 +213,70 @@ __global__ __launch_bounds__(256) void catalog_rerank_kernel(const float* __rest
   }
 }
 
+// ---- the exact re-rank of a long shortlist (ur_catalog_deep_rerank) -----------------------------------------------------------------
+// catalog_rerank_kernel gives one workgroup per user every slot: at 1024 slots a wave would walk 256 rows one after the other, each a
+// dependent fetch through index[], and 64 users would occupy a quarter of the compute units.  Here the scoring is a launch of its own,
+// one wave per (user, slot): workgroup (x, y) = slots 4 x .. 4 x + 3 of the users y, y + gridDim.y, ..; the chain is the one above, so
+// the bits are.  A wave writes its score (-inf for an empty slot) to score[b][slot]; the pairing with index[b][slot] is positional.
+// Then one workgroup per user loads its K_in pairs into LDS (2 x 4 x 1024 = 8 KB), pads them to the next power of two with empty slots
+// and sorts them with the bitonic helper of catalog_deep.hip.h (one compare-exchange pair per thread and step); the first k leave.
+// Neither launch's result depends on its grid: a score is a function of its pair, a list of its user's pairs.
+constexpr int DR_SLOTS = UR_CATALOG_DEEP_TOPK_MAX;
+constexpr int DR_GRID_Y_MAX = 65535;
+static_assert((DR_SLOTS & (DR_SLOTS - 1)) == 0 && DR_SLOTS >= UR_CATALOG_TOPK_MAX, "the sort takes a power of two; the short lists are a subset");
+template <typename CT>
+__global__ __launch_bounds__(256) void catalog_deep_rerank_score_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
+                                                                        const CT* __restrict__ cat, const float* __restrict__ inv_c,
+                                                                        const int* __restrict__ index, int K_in, float* __restrict__ score,
+                                                                        int B, long N, int D) {
+  const int lane = threadIdx.x & 63;
+  const int slot = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (slot >= K_in) return;                                              // (wave-uniform; no barrier in this kernel)
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const float* up = user + (long)b * D;
+    const float iu = inv_u[b];
+    float s = -__builtin_inff();
+    const int g = index[(long)b * K_in + slot];                          // (wave-uniform)
+    if (g >= 0 && (long)g < N) {
+      const CT* cp = cat + (long)g * D;
+      float acc = 0.f;
+      for (int d = lane * 4; d < D; d += 256) {
+        const float4 c = load4(cp + d);
+        const float4 x = *reinterpret_cast<const float4*>(up + d);
+        acc = fmaf(c.x, x.x, fmaf(c.y, x.y, fmaf(c.z, x.z, fmaf(c.w, x.w, acc))));
+      }
+      const float ic = inv_c[g];
+      s = wave_sum(acc) * iu * ic;
+    }
+    if (lane == 0) score[(long)b * K_in + slot] = s;
+  }
+}
+
+__global__ __launch_bounds__(256) void catalog_deep_rerank_sort_kernel(const float* __restrict__ score, const int* __restrict__ index, int K_in,
+                                                                       int k, int* __restrict__ topk_index, float* __restrict__ topk_score,
+                                                                       long N) {
+  __shared__ float ks[DR_SLOTS];
+  __shared__ int ki[DR_SLOTS];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int P = 2;
+  while (P < K_in) P <<= 1;                                              // <= DR_SLOTS: K_in <= UR_CATALOG_DEEP_TOPK_MAX is checked
+  for (int i = tid; i < P; i += 256) {
+    float s = -__builtin_inff();
+    int id = SEL_EMPTY;
+    if (i < K_in) {
+      const int g = index[(long)b * K_in + i];
+      if (g >= 0 && (long)g < N) { s = score[(long)b * K_in + i]; id = g; }
+    }
+    ks[i] = s; ki[i] = id;
+  }
+  __syncthreads();
+  deep_sort(ks, ki, P, tid);
+  for (int i = tid; i < k; i += 256) {
+    topk_score[(long)b * k + i] = ks[i];
+    topk_index[(long)b * k + i] = ki[i] == SEL_EMPTY ? -1 : ki[i];
+  }
+}
+
 // one launch of the coarse scorer: rows [0,N) of `cat` / `inv_c` into scores [B][ld], or (gt != NULL) the diagonal into ref [B]
 int launch_catalog_scores_bf16(const bf16_t* user, const float* inv_u, const bf16_t* cat, const float* inv_c, float* scores, long ld,
                                const long* gt, float* ref, int32_t B, int64_t N, int32_t D, hipStream_t st) {
@@ -314,6 +388,113 @@ extern "C" int ur_catalog_rerank(ur_catalog_rerank_t* a, void* stream) {
     hipLaunchKernelGGL(catalog_rerank_kernel<CT>, dim3((unsigned)B), dim3(256), 0, st, a->user, (const float*)inv_u, cat,
                        (const float*)a->cat_inv_norm, a->index, (int)a->K_in, (int)a->k, a->topk_index, a->topk_score, (long)N, (int)D);
     UR_CHECK_LAUNCH("ur_catalog_rerank");
+    return 0;
+  });
+}
+
+// ---- include/unirec_hip_coarse_deep.h ---------------------------------------------------------------------------------------------
+extern "C" int ur_catalog_coarse_deep_select(ur_catalog_coarse_deep_t* a, void* stream) {
+  UR_REQUIRE(a, "ur_catalog_coarse_deep_select: null argument struct");
+  const catalog_call c{"ur_catalog_coarse_deep_select", a->B, a->N, a->D, a->E, a->chunk_rows, a->catalog_bf16, 0, a->gt_index, a->rank,
+                       a->exclude, a->user, a->catalog, a->cat_inv_norm, a->workspace, a->workspace_bytes};
+  if (const int rc = catalog_check_sizes(c, 8, 0, false)) return rc;
+  const int32_t B = a->B, D = a->D, K = a->K, E = a->E;
+  const int64_t N = a->N;
+  UR_REQUIRE(K >= 1 && K <= UR_CATALOG_DEEP_TOPK_MAX, "ur_catalog_coarse_deep_select: K must be 1 .. %d (got %d)", UR_CATALOG_DEEP_TOPK_MAX, K);
+  UR_REQUIRE(a->catalog_bf16 == 1,
+             "ur_catalog_coarse_deep_select: catalog_bf16 must be 1, the coarse scorer reads a bf16 catalogue only (got %d)", a->catalog_bf16);
+  UR_REQUIRE(a->segments >= 0 && a->segments <= UR_CATALOG_DEEP_SEGMENTS_MAX, "ur_catalog_coarse_deep_select: segments must be 0 .. %d (got %d)",
+             UR_CATALOG_DEEP_SEGMENTS_MAX, a->segments);
+  const coarse_deep_plan p = coarse_deep_layout(B, N, D, K, a->chunk_rows, a->segments);
+  if (!a->workspace) {
+    a->workspace_bytes = p.need;
+    return 0;
+  }
+  if (const int rc = catalog_check_buffers(c, p.need, false)) return rc;
+  if (B == 0) return 0;
+  UR_REQUIRE(a->topk_index && a->topk_score, "ur_catalog_coarse_deep_select: topk_index / topk_score are null");
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)a->workspace;
+  bf16_t* ubf = (bf16_t*)(ws + p.user);
+  float* inv_u = (float*)(ws + p.inv_u);
+  float* ref = (float*)(ws + p.ref);
+  float* chunk = (float*)(ws + p.chunk);
+  float* list_score = (float*)(ws + p.list_score);
+  int* list_index = (int*)(ws + p.list_index);
+  int* count = (int*)(ws + p.count);
+  const bf16_t* cat = (const bf16_t*)a->catalog;
+  const long* gt = (const long*)a->gt_index;
+  const int G = deep_segments(a->segments, B, p.rows);             // <= p.gw, what the workspace holds
+  const int64_t tiles = p.rows / SEL_TILE;
+  const long seg_len = (long)((tiles + G - 1) / G) * SEL_TILE;
+  // the sequence of ur_catalog_coarse_select: cast, norms, the diagonal launch, then the chunks
+  int rc = ur_cast_f32_to_bf16(a->user, ubf, (int64_t)B * D, stream);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(row_inv_norm_kernel<bf16_t>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, (const bf16_t*)ubf, inv_u, (long)B, (int)D);
+  if (!a->cat_norm_ready && N > 0)
+    hipLaunchKernelGGL(row_inv_norm_kernel<bf16_t>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, cat, a->cat_inv_norm, (long)N, (int)D);
+  UR_CHECK_LAUNCH(c.who);
+  if (gt && N > 0) {
+    rc = launch_catalog_scores_bf16(ubf, inv_u, cat, a->cat_inv_norm, nullptr, 0, gt, ref, B, N, D, st);
+    if (rc != 0) return rc;
+  }
+  rc = catalog_for_each_chunk(N, p.rows, [&](int64_t c0, int64_t len, int first) {
+    if (len > 0) {
+      const int rc = launch_catalog_scores_bf16(ubf, inv_u, cat + c0 * D, a->cat_inv_norm + c0, chunk, (long)len, nullptr, nullptr, B, len, D, st);
+      if (rc != 0) return rc;
+    }
+    hipLaunchKernelGGL(catalog_deep_sweep_kernel, dim3((unsigned)((int64_t)B * G)), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0,
+                       (int)len, (int)K, G, seg_len, list_score, list_index, count, gt, (const float*)ref, (const long*)a->exclude, (int)E, first);
+    UR_CHECK_LAUNCH(c.who);
+    return 0;
+  });
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(catalog_deep_merge_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)list_score, (const int*)list_index,
+                     (const int*)count, (int)K, G, a->topk_score, a->topk_index, a->rank);
+  UR_CHECK_LAUNCH(c.who);
+  return 0;
+}
+
+extern "C" int ur_catalog_deep_rerank(ur_catalog_deep_rerank_t* a, void* stream) {
+  UR_REQUIRE(a, "ur_catalog_deep_rerank: null argument struct");
+  const int32_t B = a->B, D = a->D;
+  const int64_t N = a->N;
+  UR_REQUIRE(B >= 0, "ur_catalog_deep_rerank: need B >= 0 (got %d)", B);
+  UR_REQUIRE(N >= 1 && N <= (int64_t)INT32_MAX, "ur_catalog_deep_rerank: need 1 <= N <= INT32_MAX (got %lld)", (long long)N);
+  UR_REQUIRE(a->catalog_bf16 == 0 || a->catalog_bf16 == 1, "ur_catalog_deep_rerank: catalog_bf16 must be 0 or 1 (got %d)", a->catalog_bf16);
+  const bool bf16 = a->catalog_bf16 == 1;
+  UR_REQUIRE(D > 0 && (D % (bf16 ? 8 : 4)) == 0 && D <= 2048,
+             "ur_catalog_deep_rerank: D must be a positive multiple of %d and <= 2048 (got %d)", bf16 ? 8 : 4, D);
+  UR_REQUIRE(a->K_in >= 1 && a->K_in <= UR_CATALOG_DEEP_TOPK_MAX, "ur_catalog_deep_rerank: K_in must be 1 .. %d (got %d)",
+             UR_CATALOG_DEEP_TOPK_MAX, a->K_in);
+  UR_REQUIRE(a->k >= 1 && a->k <= a->K_in, "ur_catalog_deep_rerank: k must be 1 .. K_in = %d (got %d)", a->K_in, a->k);
+  const deep_rerank_plan p = deep_rerank_layout(B, a->K_in);
+  if (!a->workspace) {
+    a->workspace_bytes = p.need;
+    return 0;
+  }
+  UR_REQUIRE(UR_ALIGNED16(a->workspace) && a->workspace_bytes >= p.need,
+             "ur_catalog_deep_rerank: workspace must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)p.need,
+             (long long)a->workspace_bytes);
+  if (B == 0) return 0;
+  UR_REQUIRE(a->index && a->topk_index && a->topk_score, "ur_catalog_deep_rerank: index / topk_index / topk_score are null");
+  UR_REQUIRE(a->user && a->catalog && a->cat_inv_norm, "ur_catalog_deep_rerank: user / catalog / cat_inv_norm: null pointer");
+  UR_REQUIRE(UR_ALIGNED16(a->user) && UR_ALIGNED16(a->catalog), "ur_catalog_deep_rerank: user and catalog must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  float* inv_u = (float*)((char*)a->workspace + p.inv_u);
+  float* score = (float*)((char*)a->workspace + p.score);
+  const int K_in = a->K_in;
+  hipLaunchKernelGGL(row_inv_norm_kernel<float>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a->user, inv_u, (long)B, (int)D);
+  return catalog_dispatch(bf16, a->catalog, [&](auto* cat) {
+    using CT = std::remove_const_t<std::remove_pointer_t<decltype(cat)>>;
+    if (!a->cat_norm_ready)
+      hipLaunchKernelGGL(row_inv_norm_kernel<CT>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, cat, a->cat_inv_norm, (long)N, (int)D);
+    hipLaunchKernelGGL(catalog_deep_rerank_score_kernel<CT>, dim3((unsigned)((K_in + 3) / 4), (unsigned)(B < DR_GRID_Y_MAX ? B : DR_GRID_Y_MAX)),
+                       dim3(256), 0, st, a->user, (const float*)inv_u, cat, (const float*)a->cat_inv_norm, a->index, K_in, score, (int)B, (long)N,
+                       (int)D);
+    hipLaunchKernelGGL(catalog_deep_rerank_sort_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)score, a->index, K_in, (int)a->k,
+                       a->topk_index, a->topk_score, (long)N);
+    UR_CHECK_LAUNCH("ur_catalog_deep_rerank");
     return 0;
   });
 }

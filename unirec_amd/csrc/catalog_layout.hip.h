@@ -125,4 +125,39 @@ static coarse_plan coarse_layout(int32_t B, int64_t N, int32_t D, int64_t chunk_
   return p;
 }
 
+// ur_catalog_coarse_deep_select: the coarse pass's regions, then the deep selection's lists:
+// u~ [B][D] bf16 | iu~ [B] | ref [B] | chunk [B][rows] f32 | list scores [B][gw][K] | list indices [B][gw][K] | counts [B][gw]
+struct coarse_deep_plan {
+  int64_t rows, user, inv_u, ref, chunk, list_score, list_index, count, need;
+  int gw;
+};
+[[maybe_unused]] static coarse_deep_plan coarse_deep_layout(int32_t B, int64_t N, int32_t D, int32_t K, int64_t chunk_rows, int32_t segments) {
+  coarse_deep_plan p;
+  ws_carver c;
+  p.rows = catalog_chunk_rows(chunk_rows, B, N);
+  p.gw = deep_segments_cap(segments, B);
+  p.user = c.take((int64_t)B * D * 2);
+  p.inv_u = c.take((int64_t)B * 4);
+  p.ref = c.take((int64_t)B * 4);
+  p.chunk = c.take((int64_t)B * p.rows * 4);
+  p.list_score = c.take((int64_t)B * p.gw * K * 4);
+  p.list_index = c.take((int64_t)B * p.gw * K * 4);
+  p.count = c.take((int64_t)B * p.gw * 4);
+  p.need = c.need();
+  return p;
+}
+
+// ur_catalog_deep_rerank: iu [B] | scores [B][K_in] f32 (what the scoring launch hands the sorting one)
+struct deep_rerank_plan {
+  int64_t inv_u, score, need;
+};
+[[maybe_unused]] static deep_rerank_plan deep_rerank_layout(int32_t B, int32_t K_in) {
+  deep_rerank_plan p;
+  ws_carver c;
+  p.inv_u = c.take((int64_t)B * 4);
+  p.score = c.take((int64_t)B * K_in * 4);
+  p.need = c.need();
+  return p;
+}
+
 }  // namespace

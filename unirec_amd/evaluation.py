@@ -233,3 +233,41 @@ class CatalogEvaluator:
             if shortlist is not None:
                 out["rank_is_coarse"] = True
         return out
+
+    def retrieve_two_stage(self, user_embeddings, k=10, shortlist=None, gt_index=None, exclude=None, ks=None, chunk_rows=None):
+        """The two-stage path of ``retrieve(k, shortlist=S)`` with shortlists of up to 1024 items, on a bf16 catalogue:
+        ``hip.catalog_coarse_deep_select`` picks `shortlist` items per user under the coarse bf16-MFMA scores (the scorer of
+        ``hip.catalog_coarse_select``, the selection kernels of ``hip.catalog_deep_select``) and ``hip.catalog_deep_rerank`` scores those
+        exactly and returns the best k -- one path for the whole range 1 <= k <= shortlist <= 1024.
+        -> the dict of ``retrieve(k, shortlist=S)``: topk_index int32 [B,k], topk_score f32 [B,k] with the exact scorer's bits in the
+        exact order; with gt_index also rank / mrr / hit_at / ndcg_at from the COARSE scores and rank_is_coarse=True.  exclude, ks and
+        chunk_rows as in retrieve().  For shortlist <= 128 every tensor equals ``retrieve(k, shortlist=shortlist)``'s bit for bit.  The
+        list equals the exact ``retrieve(k)`` wherever the exact k-th and (shortlist + 1)-th scores lie further apart than the coarse
+        error (2^-7 covers it).
+        shortlist=None means min(1024, max(128, 2 k)): a default that leaves the re-rank twice the room it returns, NOT a tuned value --
+        choose it from the recall the catalogue needs."""
+        if self.catalog.dtype != torch.bfloat16:
+            raise ValueError("retrieve: shortlist needs a bf16 catalogue (CatalogEvaluator(dtype=torch.bfloat16)), this one is "
+                             f"{self.catalog.dtype}")
+        top = hip.CATALOG_DEEP_TOPK_MAX
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= top:
+            raise ValueError(f"retrieve_two_stage: k must be an int in [1, {top}], got {k!r}")
+        if shortlist is None:
+            shortlist = min(top, max(hip.CATALOG_TOPK_MAX, 2 * k))
+        if isinstance(shortlist, bool) or not isinstance(shortlist, int) or not k <= shortlist <= top:
+            raise ValueError(f"retrieve_two_stage: shortlist must be an int in [k, {top}] (k = {k!r}), got {shortlist!r}")
+        u = user_embeddings.detach().to(self.catalog.device, F32).contiguous()
+        ex = pack_exclude(exclude, u.shape[0])
+        if ex is not None:
+            ex = ex.to(u.device)
+        gt = None if gt_index is None else torch.as_tensor(gt_index).to(u.device, torch.int64)
+        short, _, rank, self._inv = hip.catalog_coarse_deep_select(u, self.catalog, shortlist, self._inv, gt_index=gt, exclude=ex,
+                                                                   chunk_rows=chunk_rows)
+        idx, val, _ = hip.catalog_deep_rerank(u, self.catalog, short, k, self._inv)
+        out = {"topk_index": idx, "topk_score": val}
+        if rank is not None:
+            ks = (k,) if ks is None else tuple(int(x) for x in ks)
+            m = ranking_metrics(rank, ks).cpu().tolist()                                 # the one host read
+            out.update(rank=rank, mrr=m[0], hit_at=dict(zip(ks, m[1:1 + len(ks)])), ndcg_at=dict(zip(ks, m[1 + len(ks):])),
+                       rank_is_coarse=True)
+        return out

@@ -1334,8 +1334,8 @@ def _catalog_operands(who, user, catalog, cat_inv_norm):
         raise ValueError(f"{who}: user [B,D] and catalog [N,D] must share D, got {tuple(user.shape)} and {tuple(catalog.shape)}")
     (B, D), N = user.shape, catalog.shape[0]
     cat_inv_norm, ready = _catalog_norm(cat_inv_norm, N, user.device, who)
-    _need(user, F32, "user")
-    _need(catalog, catalog.dtype, "catalog")
+    _need(user, F32, f"{who}: user")
+    _need(catalog, catalog.dtype, f"{who}: catalog")
     return B, N, D, user.device, cat_inv_norm, ready
 
 
@@ -1463,6 +1463,47 @@ def catalog_rerank(user, catalog, index, k=None, cat_inv_norm=None):
     a.k = index.shape[1] if k is None else int(k)
     idx, val = _catalog_lists(a, a.B, a.k, dev)
     _catalog_call("ur_catalog_rerank", a, dev, "catalog_rerank")
+    return idx, val, cat_inv_norm
+
+
+def catalog_coarse_deep_select(user, catalog, K, cat_inv_norm=None, gt_index=None, exclude=None, chunk_rows=None, segments=None):
+    """catalog_coarse_select with lists of up to CATALOG_DEEP_TOPK_MAX = 1024 items (ur_catalog_coarse_deep_select,
+    include/unirec_hip_coarse_deep.h): the same APPROXIMATE coarse scores bit for bit -- the same cast, norms and bf16-MFMA launches --
+    folded by the selection kernels of catalog_deep_select.  Total order, gt_index / rank, exclude, chunk_rows and the (-1, -inf) tail
+    are catalog_coarse_select's; for K <= 128 so is every output bit, and for larger K the first 128 entries and the rank are those of
+    K = 128.  D must be a multiple of 8 and the catalogue bf16.
+    segments: for tests -- the number of workgroups per user (1 .. 16) instead of the library's choice; the outputs do not depend on it.
+    Returns (topk_index int32 [B,K], topk_score f32 [B,K], rank int32 [B] or None, cat_inv_norm)."""
+    if catalog.dtype != BF16:
+        raise ValueError("catalog_coarse_deep_select: the coarse scorer reads a bf16 catalogue (CatalogEvaluator(dtype=torch.bfloat16)), "
+                         f"got {catalog.dtype}")
+    a = _lib.CatalogCoarseDeep()
+    a.B, a.N, a.D, dev, cat_inv_norm, a.cat_norm_ready = _catalog_operands("catalog_coarse_deep_select", user, catalog, cat_inv_norm)
+    a.user, a.catalog, a.cat_inv_norm, a.catalog_bf16 = user.data_ptr(), catalog.data_ptr(), cat_inv_norm.data_ptr(), 1
+    a.K, a.chunk_rows, a.segments = int(K), int(chunk_rows or 0), int(segments or 0)
+    idx, val = _catalog_lists(a, a.B, a.K, dev)
+    gt, rank = _catalog_filters("catalog_coarse_deep_select", a, a.B, dev, gt_index, exclude)
+    _catalog_call("ur_catalog_coarse_deep_select", a, dev, "catalog_coarse_deep")
+    return idx, val, rank, cat_inv_norm
+
+
+def catalog_deep_rerank(user, catalog, index, k=None, cat_inv_norm=None):
+    """catalog_rerank for shortlists of up to CATALOG_DEEP_TOPK_MAX = 1024 items (ur_catalog_deep_rerank,
+    include/unirec_hip_coarse_deep.h): index int32 [B,K'] into catalog [N,D] f32 or bf16, an entry outside [0,N) an empty slot.  Every
+    pair is scored by catalog_scores' own f32 chain, one wave per pair in a launch of its own, and each row is sorted under the total
+    order (score descending, index ascending); the first k (default K') are returned, empty slots at the tail as (-1, -inf).  For
+    K' <= 128 the outputs equal catalog_rerank's in every bit.  Returns (topk_index int32 [B,k], topk_score f32 [B,k], cat_inv_norm)."""
+    a = _lib.CatalogDeepRerank()
+    a.B, a.N, a.D, dev, cat_inv_norm, a.cat_norm_ready = _catalog_operands("catalog_deep_rerank", user, catalog, cat_inv_norm)
+    a.user, a.catalog, a.cat_inv_norm = user.data_ptr(), catalog.data_ptr(), cat_inv_norm.data_ptr()
+    a.catalog_bf16 = int(catalog.dtype == BF16)
+    _need(index, torch.int32, "catalog_deep_rerank: index")
+    if index.dim() != 2 or index.shape[0] != a.B:
+        raise ValueError(f"catalog_deep_rerank: index must be [{a.B}, K'], got {tuple(index.shape)}")
+    a.index, a.K_in = index.data_ptr(), index.shape[1]
+    a.k = index.shape[1] if k is None else int(k)
+    idx, val = _catalog_lists(a, a.B, a.k, dev)
+    _catalog_call("ur_catalog_deep_rerank", a, dev, "catalog_deep_rerank")
     return idx, val, cat_inv_norm
 
 
