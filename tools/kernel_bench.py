@@ -7,6 +7,7 @@ shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
     python tools/kernel_bench.py catalog --K 1000 --dtypes f32 bf16 --users 512 64 [--N 1000000] [--D 1024] [--rounds 5] [--segments 1 4 16]
     python tools/kernel_bench.py catalog --shortlist 128 --catalog-dtype bf16 [--N 1000000] [--D 1024] [--rounds 3]
     python tools/kernel_bench.py catalog --two-stage-shortlist 1024 --K 1000 --catalog-dtype bf16 [--users 512 64] [--rounds 5]
+    python tools/kernel_bench.py catalog --funnel-dims 256 1024 --funnel-shortlists 1024 --K 1000 [--users 512 64] [--rounds 5]
     python tools/kernel_bench.py negatives --B 64 --P 1000 --N 1000000 --K 128 [--catalog-dtype f32|bf16] [--rounds 3]
     python tools/kernel_bench.py catalog_softmax --users 64 512 --dtypes f32 bf16 --N 1000000 [--D 1024] [--rounds 5]
     python tools/kernel_bench.py merge --B 64 --S 2048 [--layers 28] [--rank 16] [--rounds 5] [--iters 2]
@@ -267,6 +268,8 @@ def catalog(args):
     --scorer vector mfma times retrieve() once per named scorer instead (alternating in this process, the library's own choice last);
     --catalog-dtype bf16 keeps the catalogue in bf16, where evaluate() does not exist and the first scorer named is the reference."""
     from unirec_amd.evaluation import CatalogEvaluator
+    if args.funnel_dims:
+        return catalog_funnel(args)
     if args.two_stage_shortlist:
         return catalog_two_stage(args)
     if args.shortlist:
@@ -513,6 +516,121 @@ def catalog_two_stage(args):
             spread = max(max(times[a]) - min(times[a]), max(times[two_name]) - min(times[two_name]))
             print(f"  {a.strip()} / two-stage = {med[a] / med[two_name]:.2f}x  (difference {gap:.2f} ms against a spread of {spread:.2f} ms: "
                   f"{'faster by more than the spread' if gap > spread else 'NOT faster by more than the spread'})")
+
+
+def _decaying_catalogue(N, D, dims, g):
+    """standard normal rows whose components in [dims[i-1], dims[i]) are scaled by 2^(-3 i), bf16: a stand-in for a Matryoshka-trained
+    embedding, whose leading components carry most of a cosine"""
+    scale = torch.ones(D, device="cuda")
+    for i in range(1, len(dims)):
+        scale[dims[i - 1]:dims[i]] = 2.0 ** (-3 * i)
+    return (torch.randn(N, D, generator=g, device="cuda") * scale).to(torch.bfloat16), scale
+
+
+def catalog_funnel(args):
+    """CatalogEvaluator.retrieve_funnel(k=--K, dims=--funnel-dims, shortlists=--funnel-shortlists) on a bf16 catalogue, per user count
+    (--users, default 512 and 64), the contenders alternating --rounds times in this process after one call of each:
+      (a) retrieve_two_stage(k, shortlists[0]) at the full width, the yardstick;
+      (b) retrieve_funnel: every stage reads its prefix of the resident catalogue in place;
+      (c) the hand composition through truncated(dims[0]): the stage-0 select on a contiguous [N, dims[0]] copy, then (b)'s re-rank stages --
+          the same arithmetic, so (b) against (c) is what the strided read costs.
+    Then the stages on their own, the scorer's share of the catalogue bytes per second, the workspaces and the peak allocation of (b), and
+    recall@k of (b) against the exact retrieve(k) on a decaying-spectrum catalogue and on a flat random one (the timings run on the
+    decaying one; the arithmetic does not depend on the values)."""
+    import ctypes
+    from unirec_amd import _lib
+    from unirec_amd.evaluation import CatalogEvaluator, ranking_metrics
+    N, D, K = args.N, args.D, args.K
+    dims, S = tuple(args.funnel_dims), tuple(args.funnel_shortlists or ())
+    S = S or None
+    g = torch.Generator(device="cuda").manual_seed(0)
+    cat, scale = _decaying_catalogue(N, D, dims, g)
+    ev = CatalogEvaluator(cat, dtype=cat.dtype)
+    del cat
+    flat = CatalogEvaluator(torch.randn(N, D, generator=g, device="cuda").to(torch.bfloat16), dtype=torch.bfloat16)
+    copy = ev.truncated(dims[0])                              # (c)'s contiguous [N, dims[0]] copy
+    print(f"catalog --funnel-dims {' '.join(map(str, dims))} --funnel-shortlists {S} --K {K}: N={N} D={D}, catalogue bf16 "
+          f"{N * D * 2 / 2**20:.0f} MiB, the truncated copy of (c) {N * dims[0] * 2 / 2**20:.0f} MiB, {args.rounds} alternating rounds")
+    for B in (args.users or [512, 64]):
+        gt = torch.randint(0, N, (B,), generator=g, device="cuda")
+        user = ev.catalog[gt].float() + 0.5 * torch.randn(B, D, generator=g, device="cuda") * scale
+        flat_user = flat.catalog[gt].float() + 0.5 * torch.randn(B, D, generator=g, device="cuda")
+        ev.retrieve(user[:1], k=1)                            # the norms of every path, outside every figure below
+        fun = ev.retrieve_funnel(user, k=K, dims=dims, shortlists=S, gt_index=gt)
+        S_used = S or (min(1024, max(128, 2 * K)),) * (len(dims) - 1)
+        inv = ev._prefix_norms(dims)
+        u0 = user[:, :dims[0]].contiguous()
+        copy.retrieve(u0[:1], k=1)
+        keep = S_used[1:] + (K,)
+
+        def hand():
+            idx, _, rank, _ = hip.catalog_coarse_deep_select(u0, copy.catalog, S_used[0], copy._inv, gt_index=gt)
+            for d, n in zip(dims[1:], keep):
+                idx, val, _ = hip.catalog_funnel_rerank(user, ev.catalog, idx, d, n, inv[d])
+            return idx, val, ranking_metrics(rank, (K,)).cpu().tolist()      # (the metrics and the host read the evaluator's calls end in)
+
+        def reranks(idx):
+            for d, n in zip(dims[1:], keep):
+                idx, val, _ = hip.catalog_funnel_rerank(user, ev.catalog, idx, d, n, inv[d])
+            return idx, val
+        a_name, b_name, c_name = f"(a) retrieve_two_stage(k={K}, shortlist={S_used[0]})", f"(b) retrieve_funnel(k={K}, dims={dims})", \
+            f"(c) select on truncated({dims[0]}) + (b)'s re-ranks"
+        short = hip.catalog_funnel_select(user, ev.catalog, dims[0], S_used[0], inv[dims[0]], gt_index=gt)[0]
+        variants = [(a_name, lambda: ev.retrieve_two_stage(user, k=K, shortlist=S_used[0], gt_index=gt)),
+                    (b_name, lambda: ev.retrieve_funnel(user, k=K, dims=dims, shortlists=S, gt_index=gt)),
+                    (c_name, hand),
+                    (f"  coarse-deep select alone, D = {D}", lambda: hip.catalog_coarse_deep_select(user, ev.catalog, S_used[0], ev._inv, gt_index=gt)),
+                    (f"  funnel select alone, dim = {dims[0]} of {D}", lambda: hip.catalog_funnel_select(user, ev.catalog, dims[0], S_used[0],
+                                                                                                       inv[dims[0]], gt_index=gt)),
+                    (f"  coarse-deep select alone, the [N, {dims[0]}] copy", lambda: hip.catalog_coarse_deep_select(u0, copy.catalog, S_used[0],
+                                                                                                                 copy._inv, gt_index=gt)),
+                    ("  the funnel's re-rank stages alone", lambda: reranks(short))]
+        h = hand()
+        assert torch.equal(h[0], fun["topk_index"]) and torch.equal(h[1].view(torch.int32), fun["topk_score"].view(torch.int32)), \
+            "(b) and (c) are the same arithmetic"
+        hip._ws_cache.clear()
+        torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        variants[1][1]()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        for name, fn in variants:                             # scratch of every variant warm again
+            fn()
+        recall = {}
+        for label, e, u in (("decaying spectrum", ev, user), ("flat random", flat, flat_user)):
+            exact = e.retrieve(u, k=K)["topk_index"]
+            got = e.retrieve_funnel(u, k=K, dims=dims, shortlists=S)["topk_index"]
+            recall[label] = ((got[:, :, None] == exact[:, None, :]).any(2).float().mean().item(), (got == exact).all(1).float().mean().item())
+        qs, qr = _lib.CatalogFunnelSelect(), _lib.CatalogFunnelRerank()
+        qs.B, qs.N, qs.dim, qs.ld, qs.ldu, qs.K, qs.catalog_bf16 = B, N, dims[0], D, D, S_used[0], 1
+        qr.B, qr.N, qr.dim, qr.ld, qr.ldu, qr.K_in, qr.k, qr.catalog_bf16 = B, N, dims[1], D, D, S_used[0], keep[0], 1
+        _lib.check(_lib.load().ur_catalog_funnel_select(ctypes.byref(qs), None), "ur_catalog_funnel_select")
+        _lib.check(_lib.load().ur_catalog_funnel_rerank(ctypes.byref(qr), None), "ur_catalog_funnel_rerank")
+        times = {name: [] for name, _ in variants}
+        for _ in range(args.rounds):
+            for name, fn in variants:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                times[name].append((time.perf_counter() - t0) * 1e3)
+        print(f"B={B} K={K} dims={dims} shortlists={S_used}:")
+        for label, (hit, same) in recall.items():
+            print(f"  recall@{K} of the funnel against the exact retrieve(k), {label} catalogue: {hit:.6f}; users whose whole list is identical {same:.4f}")
+        print(f"  workspace (size queries): select {qs.workspace_bytes / 2**20:.2f} MiB, first re-rank {qr.workspace_bytes / 2**20:.2f} MiB; peak "
+              f"allocation of the funnel call {peak / 2**20:.2f} MiB; scores [B,N] f32 would be {B * N * 4 / 2**20:.0f} MiB, a truncated copy "
+              f"{N * dims[0] * 2 / 2**20:.0f} MiB")
+        med = {}
+        for name, _ in variants:
+            t = sorted(times[name])
+            med[name] = t[len(t) // 2]
+            print(f"  {name:54s}: median {med[name]:9.2f} ms  min {t[0]:9.2f}  max {t[-1]:9.2f}  (spread {t[-1] - t[0]:.2f} over {len(t)} alternating rounds)")
+        for x, y, what in ((a_name, b_name, "(a) / (b)"), (c_name, b_name, "(c) / (b)")):
+            gap = med[x] - med[y]
+            spread = max(max(times[x]) - min(times[x]), max(times[y]) - min(times[y]))
+            verdict = "(b) faster by more than the spread" if gap > spread else "(b) slower by more than the spread" if -gap > spread else \
+                "inside the spread"
+            print(f"  {what} = {med[x] / med[y]:.2f}x  (difference {gap:.2f} ms against a spread of {spread:.2f} ms: {verdict})")
 
 
 def negatives(args):
@@ -776,6 +894,10 @@ if __name__ == "__main__":
     ap.add_argument("--two-stage-shortlist", type=int, default=0,
                     help="catalog: time retrieve_two_stage(k=--K, shortlist=...) against the exact retrieve(k=--K) per --users (default 512 and 64)")
     ap.add_argument("--segments", type=int, nargs="+", help="catalog with --K above 128: also time the long-list call with each of these workgroup counts per user forced")
+    ap.add_argument("--funnel-dims", type=int, nargs="+",
+                    help="catalog: time retrieve_funnel(k=--K, dims=...) against retrieve_two_stage at the full width and against the hand "
+                         "composition through truncated(dims[0]), per --users (default 512 and 64); the catalogue is bf16")
+    ap.add_argument("--funnel-shortlists", type=int, nargs="+", help="catalog --funnel-dims: the shortlists (default: retrieve_funnel's own)")
     ap.add_argument("--catalog-dtype", choices=["f32", "bf16"], default="f32", help="catalog: the dtype the catalogue is stored in")
     ap.add_argument("--users", type=int, nargs="+", help="catalog_softmax: the user counts to time (default: --B)")
     ap.add_argument("--dtypes", nargs="+", choices=["f32", "bf16"], help="catalog_softmax: the catalogue dtypes to time (default: --catalog-dtype)")

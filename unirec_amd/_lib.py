@@ -1,6 +1,6 @@
 """ctypes binding of libunirec_hip.so (the C ABI declared in include/unirec_hip.h, include/unirec_hip_loss.h,
 include/unirec_hip_adapter.h, include/unirec_hip_pool.h, include/unirec_hip_mrl.h, include/unirec_hip_coarse.h,
-include/unirec_hip_deep.h and include/unirec_hip_coarse_deep.h).
+include/unirec_hip_deep.h, include/unirec_hip_coarse_deep.h and include/unirec_hip_funnel.h).
 
 Fails loudly: there is no CPU / eager fallback for the product path.
 """
@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -202,6 +202,38 @@ class CatalogDeepRerank(ctypes.Structure):
     _fields_ = list(CatalogRerank._fields_)
 
 
+FUNNEL_MAX_DIMS = MRL_MAX_DIMS      # UR_FUNNEL_MAX_DIMS
+FUNNEL_USER_GROUP = 64              # UR_FUNNEL_USER_GROUP
+
+
+class CatalogPrefixNorms(ctypes.Structure):
+    """Mirror of ur_catalog_prefix_norms_t (include/unirec_hip_funnel.h)."""
+    _fields_ = [("catalog", c_void_p), ("catalog_bf16", c_int), ("N", c_i64), ("ld", c_i64),
+                ("L", c_int), ("dims", c_int * FUNNEL_MAX_DIMS), ("inv", c_void_p)]
+
+
+class CatalogFunnelSelect(ctypes.Structure):
+    """Mirror of ur_catalog_funnel_select_t (include/unirec_hip_funnel.h): CatalogCoarseDeep with dim, ld, ldu in place of D."""
+    _fields_ = [("user", c_void_p), ("catalog", c_void_p), ("catalog_bf16", c_int),
+                ("cat_inv_norm", c_void_p), ("cat_norm_ready", c_int),
+                ("B", c_int), ("N", c_i64), ("dim", c_int), ("ld", c_i64), ("ldu", c_i64), ("K", c_int),
+                ("topk_index", c_void_p), ("topk_score", c_void_p),
+                ("gt_index", c_void_p), ("rank", c_void_p),
+                ("exclude", c_void_p), ("E", c_int),
+                ("chunk_rows", c_i64), ("segments", c_int),
+                ("workspace", c_void_p), ("workspace_bytes", c_i64)]
+
+
+class CatalogFunnelRerank(ctypes.Structure):
+    """Mirror of ur_catalog_funnel_rerank_t (include/unirec_hip_funnel.h): CatalogDeepRerank with dim, ld, ldu in place of D."""
+    _fields_ = [("user", c_void_p), ("catalog", c_void_p), ("catalog_bf16", c_int),
+                ("cat_inv_norm", c_void_p), ("cat_norm_ready", c_int),
+                ("B", c_int), ("N", c_i64), ("dim", c_int), ("ld", c_i64), ("ldu", c_i64),
+                ("index", c_void_p), ("K_in", c_int), ("k", c_int),
+                ("topk_index", c_void_p), ("topk_score", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_i64)]
+
+
 class F32Range(ctypes.Structure):
     """Mirror of ur_f32_range."""
     _fields_ = [("ptr", c_void_p), ("n", c_i64)]
@@ -362,6 +394,14 @@ COARSE_DEEP_SIGNATURES = {
     "ur_catalog_deep_rerank": (c_int, [ctypes.POINTER(CatalogDeepRerank), c_void_p]),
 }
 
+# the funnel retrieval family: every symbol include/unirec_hip_funnel.h declares (tests/test_catalog_funnel_host.py holds this table and
+# the three struct mirrors above to that header and to the built library)
+FUNNEL_SIGNATURES = {
+    "ur_catalog_prefix_norms": (c_int, [ctypes.POINTER(CatalogPrefixNorms), c_void_p]),
+    "ur_catalog_funnel_select": (c_int, [ctypes.POINTER(CatalogFunnelSelect), c_void_p]),
+    "ur_catalog_funnel_rerank": (c_int, [ctypes.POINTER(CatalogFunnelRerank), c_void_p]),
+}
+
 _lib = None
 
 
@@ -385,7 +425,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(ADAPTER_SIGNATURES.items()) + \
             list(POOL_SIGNATURES.items()) + list(MRL_SIGNATURES.items()) + list(COARSE_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + \
-            list(COARSE_DEEP_SIGNATURES.items()):
+            list(COARSE_DEEP_SIGNATURES.items()) + list(FUNNEL_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -14,11 +14,20 @@
 //   ur_catalog_deep_rerank        : the same chain per (user, slot) in a launch of its own, one wave per pair, then one workgroup per
 //                                   user sorts up to 1024 pairs.
 //
+// Funnel retrieval (include/unirec_hip_funnel.h), the long two-stage pair on prefixes of the embedding, read in place with a row stride:
+//
+//   ur_catalog_prefix_norms  : the row-norm chain with a snapshot per prefix boundary, one read of the catalogue for all planes.
+//   ur_catalog_funnel_select : a strided cast of the user prefix, catalog_scores_bf16_prefix_kernel (the coarse scorer with a catalogue
+//                              row stride) and the sweep / merge kernels of catalog_deep.hip.h, unchanged.
+//   ur_catalog_funnel_rerank : the scoring launch of ur_catalog_deep_rerank with both strides, then its sorting launch, unchanged.
+//
 // The headers hold the definitions in full; the comments here are about the placement.
 #include "common.hip.h"
 #include "unirec_hip.h"
 #include "unirec_hip_coarse.h"
 #include "unirec_hip_coarse_deep.h"
+#include "unirec_hip_funnel.h"
+#include "unirec_hip_mrl.h"
 #include "catalog_select.hip.h"
 #include "catalog_deep.hip.h"
 
@@ -495,6 +504,383 @@ extern "C" int ur_catalog_deep_rerank(ur_catalog_deep_rerank_t* a, void* stream)
     hipLaunchKernelGGL(catalog_deep_rerank_sort_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)score, a->index, K_in, (int)a->k,
                        a->topk_index, a->topk_score, (long)N);
     UR_CHECK_LAUNCH("ur_catalog_deep_rerank");
+    return 0;
+  });
+}
+
+// ---- include/unirec_hip_funnel.h --------------------------------------------------------------------------------------------------
+namespace {
+
+static_assert(UR_FUNNEL_MAX_DIMS == UR_MRL_MAX_DIMS, "a funnel takes the prefixes a Matryoshka head trains");
+static_assert(UR_FUNNEL_USER_GROUP == UR_COARSE_USER_GROUP, "the prefix scorer keeps the user groups of the contiguous one");
+
+// The row norms of L prefixes in one read.  row_inv_norm_kernel's chain: lane j adds the squares of its pieces at d = 4 j + 256 i in
+// ascending i.  The sum a lane holds after its last piece below dims[l] is that chain on the slice [:dims[l]] (dims are multiples of 4:
+// a piece lies wholly on one side of a boundary), so the lane keeps it as plane l's snapshot; a lane with no piece below the boundary
+// keeps 0, as the short loop does.  Each snapshot is folded by the same wave_sum and finished by the same expression.
+struct prefix_dims {
+  int d[UR_FUNNEL_MAX_DIMS];
+};
+template <typename CT>
+__global__ void row_prefix_inv_norm_kernel(const CT* __restrict__ x, long ld, float* __restrict__ inv, long rows, prefix_dims dims, int L) {
+  const long row = (long)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const CT* p = x + row * ld;
+  const int D = dims.d[L - 1];
+  float s = 0.f;
+  float snap[UR_FUNNEL_MAX_DIMS];
+#pragma unroll
+  for (int l = 0; l < UR_FUNNEL_MAX_DIMS; ++l) snap[l] = 0.f;
+  for (int d = lane * 4; d < D; d += 256) {
+    const float4 v = load4(p + d);
+    s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+#pragma unroll
+    for (int l = 0; l < UR_FUNNEL_MAX_DIMS; ++l)
+      if (l < L && d < dims.d[l]) snap[l] = s;
+  }
+#pragma unroll
+  for (int l = 0; l < UR_FUNNEL_MAX_DIMS; ++l) {
+    if (l < L) {                                                       // (uniform)
+      const float t = wave_sum(snap[l]);
+      if (lane == 0) inv[(long)l * rows + row] = 1.0f / fmaxf(sqrtf(t), 1e-12f);
+    }
+  }
+}
+
+// user [B, ldu] f32 -> out [B, dim] bf16, nearest even: the bits ur_cast_f32_to_bf16 gives on the contiguous copy user[:, :dim]
+__global__ void cast_prefix_kernel(const float* __restrict__ user, long ldu, bf16_t* __restrict__ out, int B, int dim) {
+  const int P = dim >> 3;
+  const long total = (long)B * P, stride = (long)gridDim.x * blockDim.x;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const long b = i / P;
+    const int p = (int)(i - b * P);
+    const float* s = user + b * ldu + p * 8;
+    const float4 lo = *reinterpret_cast<const float4*>(s), hi = *reinterpret_cast<const float4*>(s + 4);
+    *reinterpret_cast<uint4*>(out + b * dim + p * 8) =
+        make_uint4(pack_bf2(lo.x, lo.y), pack_bf2(lo.z, lo.w), pack_bf2(hi.x, hi.y), pack_bf2(hi.z, hi.w));
+  }
+}
+
+// ---- the prefix scorer ------------------------------------------------------------------------------------------------------------
+// catalog_scores_bf16_kernel on the first D components of catalogue rows that are `cld` elements apart.  The users arrive as the
+// contiguous bf16 block [B, D] the entry point cast, so the staging, the operand layout, the chains (step s to chain s % NC, NC by D
+// alone) and the epilogue are that kernel's, instruction for instruction: a pair has the bits the contiguous kernel gives it on the
+// copy.  What differs is the catalogue side of a lane's address, row * cld, and what lies behind the prefix: elements D .. cld - 1 of
+// a row are live data, so the K step that ends short is masked by D -- a lane whose 8 elements start at or past D loads nothing and
+// brings zeros, wherever the row ends.  A lane reads 16 bytes at row * cld + 32 s + 8 kq only when 32 s + 8 kq + 8 <= D <= cld.
+// A wave's load of one step touches 16 rows x 64 bytes: whole 64-byte pieces of rows cld apart (cld % 8 == 0 keeps them 16-byte
+// aligned); consecutive steps walk each row's prefix front to back.
+template <int UT, int NC>
+__global__ __launch_bounds__(CC_WAVES * 64) void catalog_scores_bf16_prefix_kernel(const bf16_t* __restrict__ user, const float* __restrict__ inv_u,
+                                                                                  const bf16_t* __restrict__ cat, long cld,
+                                                                                  const float* __restrict__ inv_c, float* __restrict__ scores,
+                                                                                  long ld, const long* __restrict__ gt, float* __restrict__ ref,
+                                                                                  int B, long N, int D, long rows_per_block, int ub) {
+  static_assert(NC == 2 || NC == 4, "the epilogue adds two or four chains");
+  extern __shared__ __attribute__((aligned(16))) bf16_t cus[];     // [steps][UT][64 lanes][8]
+  const int S = cc_steps(D);
+  const int ug = blockIdx.x % ub;
+  const long rb = blockIdx.x / ub;
+  const int b0 = ug * 16 * UT;
+  const int nb = min(16 * UT, B - b0);
+  const int P = S * 4;                                             // 8-element pieces of a padded row
+  for (int i = threadIdx.x; i < 16 * UT * P; i += CC_WAVES * 64) {
+    const int ul = i & 15, p = (i >> 4) % P, ut = (i >> 4) / P;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (p * 8 < D) v = *reinterpret_cast<const uint4*>(user + (long)min(b0 + ut * 16 + ul, B - 1) * D + p * 8);
+    *reinterpret_cast<uint4*>(cus + ((((p >> 2) * UT + ut) * 64 + ul + 16 * (p & 3)) << 3)) = v;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, col = lane & 15, kq = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool diag = gt != nullptr;
+  const long r0 = diag ? (long)b0 : rb * rows_per_block;
+  const long r1 = diag ? (long)(b0 + nb) : min(N, r0 + rows_per_block);
+  const int S_full = D >> 5;
+  const bf16_t* ap = cus + (lane << 3);
+  for (long n0 = r0 + w * 16 * CC_RT; n0 < r1; n0 += CC_ROWS) {
+    const bf16_t* bp[CC_RT];                     // a row past the end is read as the last one and never stored
+    long crow[CC_RT];
+#pragma unroll
+    for (int r = 0; r < CC_RT; ++r) {
+      const long n = min(n0 + r * 16 + col, r1 - 1);
+      crow[r] = diag ? min(max(gt[n], 0L), N - 1) : n;
+      bp[r] = cat + crow[r] * cld + 8 * kq;
+    }
+    f32x4 acc[NC][UT][CC_RT];
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+#pragma unroll
+      for (int t = 0; t < UT; ++t)
+#pragma unroll
+        for (int r = 0; r < CC_RT; ++r) acc[j][t][r] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // step s of chain j: PART = the K step that ends short of 32 elements -- masked by D, the prefix, not by the row's end
+    auto step = [&](int s, f32x4 (&c)[UT][CC_RT], bool part) {
+      const bool in = !part || 32 * s + 8 * kq < D;
+      bf16x8 b[CC_RT];
+#pragma unroll
+      for (int r = 0; r < CC_RT; ++r) {
+        b[r] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (in) b[r] = *reinterpret_cast<const bf16x8*>(bp[r] + 32 * s);
+      }
+#pragma unroll
+      for (int t = 0; t < UT; ++t) {
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(ap + ((s * UT + t) << 9));
+#pragma unroll
+        for (int r = 0; r < CC_RT; ++r) c[t][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[r], c[t][r], 0, 0, 0);
+      }
+    };
+    int s0 = 0;
+    for (; s0 + NC <= S_full; s0 += NC) {
+#pragma unroll
+      for (int j = 0; j < NC; ++j) step(s0 + j, acc[j], false);
+    }
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {               // the last, incomplete round: step s still goes to chain s % NC (wave-uniform conditions)
+      if (s0 + j < S_full) step(s0 + j, acc[j], false);
+      else if (s0 + j == S_full && S_full < S) step(s0 + j, acc[j], true);
+    }
+#pragma unroll
+    for (int t = 0; t < UT; ++t)
+#pragma unroll
+      for (int r = 0; r < CC_RT; ++r) {
+        if (NC == 2) acc[0][t][r] = acc[0][t][r] + acc[1][t][r];
+        else acc[0][t][r] = (acc[0][t][r] + acc[2 % NC][t][r]) + (acc[1][t][r] + acc[3 % NC][t][r]);
+      }
+#pragma unroll
+    for (int r = 0; r < CC_RT; ++r) {
+      const long n = n0 + r * 16 + col;
+      if (n < r1) {
+        const float ic = inv_c[crow[r]];
+#pragma unroll
+        for (int t = 0; t < UT; ++t)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int u = t * 16 + kq * 4 + e;
+            if (u < nb) {
+              const float v = acc[0][t][r][e] * inv_u[b0 + u] * ic;
+              if (!diag) scores[(long)(b0 + u) * ld + n] = v;
+              else if ((long)(b0 + u) == n) ref[n] = v;
+            }
+          }
+      }
+    }
+  }
+}
+
+// one launch of the prefix scorer, the grid of launch_catalog_scores_bf16: rows [0,N) of `cat` (stride cld) / `inv_c` into scores [B][ld],
+// or (gt != NULL) the diagonal into ref [B].  The user group is a function of dim alone.
+int launch_catalog_scores_bf16_prefix(const bf16_t* user, const float* inv_u, const bf16_t* cat, long cld, const float* inv_c, float* scores,
+                                      long ld, const long* gt, float* ref, int32_t B, int64_t N, int32_t dim, hipStream_t st) {
+  const bool wide = dim > 1024;
+  const int ut = wide ? 2 : 4;
+  static_assert(UR_FUNNEL_USER_GROUP == 16 * 4, "the header documents the user group of dim <= 1024");
+  const int ub = ur_cdiv(B, 16 * ut);
+  long blocks_x = 1, rpb = N;
+  if (!gt) {
+    blocks_x = 512 / ub;
+    if (blocks_x < 1) blocks_x = 1;
+    rpb = (N + blocks_x - 1) / blocks_x;
+    rpb = (rpb + CC_ROWS - 1) / CC_ROWS * CC_ROWS;
+    blocks_x = (N + rpb - 1) / rpb;
+  }
+  void (*kernel)(const bf16_t*, const float*, const bf16_t*, long, const float*, float*, long, const long*, float*, int, long, int, long, int) =
+      wide ? catalog_scores_bf16_prefix_kernel<2, 4> : catalog_scores_bf16_prefix_kernel<4, 2>;
+  static std::atomic<uint64_t> attr_set[2];   // per device, one per kernel
+  UR_ONCE_PER_DEVICE(attr_set[wide]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CC_LDS_MAX);
+    if (e != hipSuccess) UR_FAIL((int)e, "ur_catalog_funnel_select: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks_x * ub)), dim3(CC_WAVES * 64), cc_lds_bytes(dim, ut), st, user, inv_u, cat, cld, inv_c, scores,
+                     ld, gt, ref, (int)B, (long)N, (int)dim, rpb, ub);
+  UR_CHECK_LAUNCH("ur_catalog_funnel_select");
+  return 0;
+}
+
+// the scoring launch of ur_catalog_deep_rerank with the two row strides; the chain runs over d < D
+template <typename CT>
+__global__ __launch_bounds__(256) void catalog_funnel_rerank_score_kernel(const float* __restrict__ user, long ldu, const float* __restrict__ inv_u,
+                                                                          const CT* __restrict__ cat, long cld, const float* __restrict__ inv_c,
+                                                                          const int* __restrict__ index, int K_in, float* __restrict__ score,
+                                                                          int B, long N, int D) {
+  const int lane = threadIdx.x & 63;
+  const int slot = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (slot >= K_in) return;                                              // (wave-uniform; no barrier in this kernel)
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const float* up = user + (long)b * ldu;
+    const float iu = inv_u[b];
+    float s = -__builtin_inff();
+    const int g = index[(long)b * K_in + slot];                          // (wave-uniform)
+    if (g >= 0 && (long)g < N) {
+      const CT* cp = cat + (long)g * cld;
+      float acc = 0.f;
+      for (int d = lane * 4; d < D; d += 256) {
+        const float4 c = load4(cp + d);
+        const float4 x = *reinterpret_cast<const float4*>(up + d);
+        acc = fmaf(c.x, x.x, fmaf(c.y, x.y, fmaf(c.z, x.z, fmaf(c.w, x.w, acc))));
+      }
+      const float ic = inv_c[g];
+      s = wave_sum(acc) * iu * ic;
+    }
+    if (lane == 0) score[(long)b * K_in + slot] = s;
+  }
+}
+
+template <typename CT>
+void launch_prefix_norm(const CT* x, long ld, float* inv, long rows, int dim, hipStream_t st) {
+  prefix_dims dims{};
+  dims.d[0] = dim;
+  hipLaunchKernelGGL(row_prefix_inv_norm_kernel<CT>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, ld, inv, rows, dims, 1);
+}
+
+}  // namespace
+
+extern "C" int ur_catalog_prefix_norms(const ur_catalog_prefix_norms_t* a, void* stream) {
+  UR_REQUIRE(a, "ur_catalog_prefix_norms: null argument struct");
+  UR_REQUIRE(a->catalog_bf16 == 0 || a->catalog_bf16 == 1, "ur_catalog_prefix_norms: catalog_bf16 must be 0 or 1 (got %d)", a->catalog_bf16);
+  const bool bf16 = a->catalog_bf16 == 1;
+  const int mult = bf16 ? 8 : 4;
+  const int64_t N = a->N;
+  UR_REQUIRE(N >= 0 && N <= (int64_t)INT32_MAX, "ur_catalog_prefix_norms: need 0 <= N <= INT32_MAX (got %lld)", (long long)N);
+  UR_REQUIRE(a->L >= 1 && a->L <= UR_FUNNEL_MAX_DIMS, "ur_catalog_prefix_norms: L must be 1 .. %d (got %d)", UR_FUNNEL_MAX_DIMS, a->L);
+  UR_REQUIRE(a->ld > 0 && (a->ld % mult) == 0, "ur_catalog_prefix_norms: ld must be a positive multiple of %d (got %lld)", mult, (long long)a->ld);
+  prefix_dims dims{};
+  for (int l = 0; l < a->L; ++l) {
+    const int32_t d = a->dims[l];
+    UR_REQUIRE(d > 0 && (d % mult) == 0 && d <= 2048, "ur_catalog_prefix_norms: dims[%d] must be a positive multiple of %d and <= 2048 (got %d)", l,
+               mult, d);
+    UR_REQUIRE((int64_t)d <= a->ld, "ur_catalog_prefix_norms: dims[%d] = %d exceeds ld = %lld", l, d, (long long)a->ld);
+    UR_REQUIRE(l == 0 || d > a->dims[l - 1], "ur_catalog_prefix_norms: dims must be strictly ascending (dims[%d] = %d after %d)", l, d,
+               a->dims[l - 1]);
+    dims.d[l] = d;
+  }
+  if (N == 0) return 0;
+  UR_REQUIRE(a->catalog && a->inv, "ur_catalog_prefix_norms: catalog / inv: null pointer");
+  UR_REQUIRE(UR_ALIGNED16(a->catalog), "ur_catalog_prefix_norms: catalog must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  return catalog_dispatch(bf16, a->catalog, [&](auto* cat) {
+    using CT = std::remove_const_t<std::remove_pointer_t<decltype(cat)>>;
+    hipLaunchKernelGGL(row_prefix_inv_norm_kernel<CT>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, cat, (long)a->ld, a->inv, (long)N, dims,
+                       (int)a->L);
+    UR_CHECK_LAUNCH("ur_catalog_prefix_norms");
+    return 0;
+  });
+}
+
+extern "C" int ur_catalog_funnel_select(ur_catalog_funnel_select_t* a, void* stream) {
+  UR_REQUIRE(a, "ur_catalog_funnel_select: null argument struct");
+  const catalog_call c{"ur_catalog_funnel_select", a->B, a->N, 8 /* dim has its own checks below */, a->E, a->chunk_rows, a->catalog_bf16, 0,
+                       a->gt_index, a->rank, a->exclude, a->user, a->catalog, a->cat_inv_norm, a->workspace, a->workspace_bytes};
+  if (const int rc = catalog_check_sizes(c, 8, 0, false)) return rc;
+  const int32_t B = a->B, dim = a->dim, K = a->K, E = a->E;
+  const int64_t N = a->N, cld = a->ld, ldu = a->ldu;
+  UR_REQUIRE(dim > 0 && (dim % 8) == 0 && dim <= 2048, "ur_catalog_funnel_select: dim must be a positive multiple of 8 and <= 2048 (got %d)", dim);
+  UR_REQUIRE(cld >= dim, "ur_catalog_funnel_select: ld must be at least dim = %d (got %lld)", dim, (long long)cld);
+  UR_REQUIRE(ldu >= dim, "ur_catalog_funnel_select: ldu must be at least dim = %d (got %lld)", dim, (long long)ldu);
+  UR_REQUIRE((cld % 8) == 0, "ur_catalog_funnel_select: ld must be a multiple of 8, every bf16 row 16-byte aligned (got %lld)", (long long)cld);
+  UR_REQUIRE((ldu % 4) == 0, "ur_catalog_funnel_select: ldu must be a multiple of 4, every f32 row 16-byte aligned (got %lld)", (long long)ldu);
+  UR_REQUIRE(K >= 1 && K <= UR_CATALOG_DEEP_TOPK_MAX, "ur_catalog_funnel_select: K must be 1 .. %d (got %d)", UR_CATALOG_DEEP_TOPK_MAX, K);
+  UR_REQUIRE(a->catalog_bf16 == 1, "ur_catalog_funnel_select: catalog_bf16 must be 1, the coarse scorer reads a bf16 catalogue only (got %d)",
+             a->catalog_bf16);
+  UR_REQUIRE(a->segments >= 0 && a->segments <= UR_CATALOG_DEEP_SEGMENTS_MAX, "ur_catalog_funnel_select: segments must be 0 .. %d (got %d)",
+             UR_CATALOG_DEEP_SEGMENTS_MAX, a->segments);
+  const coarse_deep_plan p = funnel_select_layout(B, N, dim, K, a->chunk_rows, a->segments);
+  if (!a->workspace) {
+    a->workspace_bytes = p.need;
+    return 0;
+  }
+  if (const int rc = catalog_check_buffers(c, p.need, false)) return rc;
+  if (B == 0) return 0;
+  UR_REQUIRE(a->topk_index && a->topk_score, "ur_catalog_funnel_select: topk_index / topk_score are null");
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)a->workspace;
+  bf16_t* ubf = (bf16_t*)(ws + p.user);
+  float* inv_u = (float*)(ws + p.inv_u);
+  float* ref = (float*)(ws + p.ref);
+  float* chunk = (float*)(ws + p.chunk);
+  float* list_score = (float*)(ws + p.list_score);
+  int* list_index = (int*)(ws + p.list_index);
+  int* count = (int*)(ws + p.count);
+  const bf16_t* cat = (const bf16_t*)a->catalog;
+  const long* gt = (const long*)a->gt_index;
+  const int G = deep_segments(a->segments, B, p.rows);             // <= p.gw, what the workspace holds
+  const int64_t tiles = p.rows / SEL_TILE;
+  const long seg_len = (long)((tiles + G - 1) / G) * SEL_TILE;
+  // the sequence of ur_catalog_coarse_deep_select: cast, norms, the diagonal launch, the chunks, the merge
+  const long pieces = (long)B * (dim >> 3);
+  hipLaunchKernelGGL(cast_prefix_kernel, dim3((unsigned)(pieces < 256L * 2048 ? (pieces + 255) / 256 : 2048)), dim3(256), 0, st, a->user, (long)ldu,
+                     ubf, (int)B, (int)dim);
+  hipLaunchKernelGGL(row_inv_norm_kernel<bf16_t>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, (const bf16_t*)ubf, inv_u, (long)B, (int)dim);
+  if (!a->cat_norm_ready && N > 0) launch_prefix_norm(cat, (long)cld, a->cat_inv_norm, (long)N, dim, st);
+  UR_CHECK_LAUNCH(c.who);
+  int rc = 0;
+  if (gt && N > 0) {
+    rc = launch_catalog_scores_bf16_prefix(ubf, inv_u, cat, (long)cld, a->cat_inv_norm, nullptr, 0, gt, ref, B, N, dim, st);
+    if (rc != 0) return rc;
+  }
+  rc = catalog_for_each_chunk(N, p.rows, [&](int64_t c0, int64_t len, int first) {
+    if (len > 0) {
+      const int rc = launch_catalog_scores_bf16_prefix(ubf, inv_u, cat + c0 * cld, (long)cld, a->cat_inv_norm + c0, chunk, (long)len, nullptr,
+                                                       nullptr, B, len, dim, st);
+      if (rc != 0) return rc;
+    }
+    hipLaunchKernelGGL(catalog_deep_sweep_kernel, dim3((unsigned)((int64_t)B * G)), dim3(256), 0, st, (const float*)chunk, (long)len, (int)c0,
+                       (int)len, (int)K, G, seg_len, list_score, list_index, count, gt, (const float*)ref, (const long*)a->exclude, (int)E, first);
+    UR_CHECK_LAUNCH(c.who);
+    return 0;
+  });
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(catalog_deep_merge_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)list_score, (const int*)list_index,
+                     (const int*)count, (int)K, G, a->topk_score, a->topk_index, a->rank);
+  UR_CHECK_LAUNCH(c.who);
+  return 0;
+}
+
+extern "C" int ur_catalog_funnel_rerank(ur_catalog_funnel_rerank_t* a, void* stream) {
+  UR_REQUIRE(a, "ur_catalog_funnel_rerank: null argument struct");
+  const int32_t B = a->B, dim = a->dim;
+  const int64_t N = a->N, cld = a->ld, ldu = a->ldu;
+  UR_REQUIRE(B >= 0, "ur_catalog_funnel_rerank: need B >= 0 (got %d)", B);
+  UR_REQUIRE(N >= 1 && N <= (int64_t)INT32_MAX, "ur_catalog_funnel_rerank: need 1 <= N <= INT32_MAX (got %lld)", (long long)N);
+  UR_REQUIRE(a->catalog_bf16 == 0 || a->catalog_bf16 == 1, "ur_catalog_funnel_rerank: catalog_bf16 must be 0 or 1 (got %d)", a->catalog_bf16);
+  const bool bf16 = a->catalog_bf16 == 1;
+  const int mult = bf16 ? 8 : 4;
+  UR_REQUIRE(dim > 0 && (dim % mult) == 0 && dim <= 2048, "ur_catalog_funnel_rerank: dim must be a positive multiple of %d and <= 2048 (got %d)",
+             mult, dim);
+  UR_REQUIRE(cld >= dim && (cld % mult) == 0, "ur_catalog_funnel_rerank: ld must be at least dim = %d and a multiple of %d (got %lld)", dim, mult,
+             (long long)cld);
+  UR_REQUIRE(ldu >= dim && (ldu % 4) == 0, "ur_catalog_funnel_rerank: ldu must be at least dim = %d and a multiple of 4 (got %lld)", dim,
+             (long long)ldu);
+  UR_REQUIRE(a->K_in >= 1 && a->K_in <= UR_CATALOG_DEEP_TOPK_MAX, "ur_catalog_funnel_rerank: K_in must be 1 .. %d (got %d)",
+             UR_CATALOG_DEEP_TOPK_MAX, a->K_in);
+  UR_REQUIRE(a->k >= 1 && a->k <= a->K_in, "ur_catalog_funnel_rerank: k must be 1 .. K_in = %d (got %d)", a->K_in, a->k);
+  const deep_rerank_plan p = funnel_rerank_layout(B, a->K_in);
+  if (!a->workspace) {
+    a->workspace_bytes = p.need;
+    return 0;
+  }
+  UR_REQUIRE(UR_ALIGNED16(a->workspace) && a->workspace_bytes >= p.need,
+             "ur_catalog_funnel_rerank: workspace must be 16-byte aligned and hold %lld bytes (got %lld)", (long long)p.need,
+             (long long)a->workspace_bytes);
+  if (B == 0) return 0;
+  UR_REQUIRE(a->index && a->topk_index && a->topk_score, "ur_catalog_funnel_rerank: index / topk_index / topk_score are null");
+  UR_REQUIRE(a->user && a->catalog && a->cat_inv_norm, "ur_catalog_funnel_rerank: user / catalog / cat_inv_norm: null pointer");
+  UR_REQUIRE(UR_ALIGNED16(a->user) && UR_ALIGNED16(a->catalog), "ur_catalog_funnel_rerank: user and catalog must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  float* inv_u = (float*)((char*)a->workspace + p.inv_u);
+  float* score = (float*)((char*)a->workspace + p.score);
+  const int K_in = a->K_in;
+  launch_prefix_norm(a->user, (long)ldu, inv_u, (long)B, dim, st);
+  return catalog_dispatch(bf16, a->catalog, [&](auto* cat) {
+    using CT = std::remove_const_t<std::remove_pointer_t<decltype(cat)>>;
+    if (!a->cat_norm_ready) launch_prefix_norm(cat, (long)cld, a->cat_inv_norm, (long)N, dim, st);
+    hipLaunchKernelGGL(catalog_funnel_rerank_score_kernel<CT>, dim3((unsigned)((K_in + 3) / 4), (unsigned)(B < DR_GRID_Y_MAX ? B : DR_GRID_Y_MAX)),
+                       dim3(256), 0, st, a->user, (long)ldu, (const float*)inv_u, cat, (long)cld, (const float*)a->cat_inv_norm, a->index, K_in,
+                       score, (int)B, (long)N, (int)dim);
+    hipLaunchKernelGGL(catalog_deep_rerank_sort_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)score, a->index, K_in, (int)a->k,
+                       a->topk_index, a->topk_score, (long)N);
+    UR_CHECK_LAUNCH("ur_catalog_funnel_rerank");
     return 0;
   });
 }

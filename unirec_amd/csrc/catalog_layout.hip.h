@@ -160,4 +160,11 @@ struct deep_rerank_plan {
   return p;
 }
 
+// ur_catalog_funnel_select / ur_catalog_funnel_rerank (include/unirec_hip_funnel.h): the two plans above at D = dim.  The staged user
+// prefix is a contiguous [B][dim] block and the catalogue is read in place, so the strides ld / ldu size nothing.
+[[maybe_unused]] static coarse_deep_plan funnel_select_layout(int32_t B, int64_t N, int32_t dim, int32_t K, int64_t chunk_rows, int32_t segments) {
+  return coarse_deep_layout(B, N, dim, K, chunk_rows, segments);
+}
+[[maybe_unused]] static deep_rerank_plan funnel_rerank_layout(int32_t B, int32_t K_in) { return deep_rerank_layout(B, K_in); }
+
 }  // namespace

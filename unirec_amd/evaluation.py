@@ -158,6 +158,7 @@ class CatalogEvaluator:
         self.catalog = torch.as_tensor(catalog).to(device, dtype).contiguous()    # [N,D], stays in HBM
         self.item_ids = None if item_ids is None else [str(i) for i in item_ids]
         self._inv = None                                                          # catalogue 1/||c||, computed once
+        self._prefix_inv = {}                                                     # prefix width -> 1/||c[:width]|| [N] (retrieve_funnel)
 
     def truncated(self, dim):
         """A new evaluator over the first `dim` components of every catalogue row, as a contiguous [N, dim] copy of the same dtype
@@ -270,4 +271,72 @@ class CatalogEvaluator:
             m = ranking_metrics(rank, ks).cpu().tolist()                                 # the one host read
             out.update(rank=rank, mrr=m[0], hit_at=dict(zip(ks, m[1:1 + len(ks)])), ndcg_at=dict(zip(ks, m[1 + len(ks):])),
                        rank_is_coarse=True)
+        return out
+
+    def _prefix_norms(self, dims):
+        """{d: the [N] inverse norms of the catalogue's first d components} for d in dims: one ``hip.catalog_prefix_norms`` call for the
+        widths not seen before.  The plane of the full width is ``self._inv`` (the same bits), shared with the other paths."""
+        D = self.catalog.shape[1]
+        missing = tuple(d for d in dims if d not in self._prefix_inv and not (d == D and self._inv is not None))
+        if missing:
+            planes = hip.catalog_prefix_norms(self.catalog, missing)
+            for d, plane in zip(missing, planes):
+                if d == D:
+                    self._inv = plane
+                else:
+                    self._prefix_inv[d] = plane
+        return {d: self._inv if d == D else self._prefix_inv[d] for d in dims}
+
+    def retrieve_funnel(self, user_embeddings, k=10, dims=None, shortlists=None, gt_index=None, exclude=None, ks=None, chunk_rows=None):
+        """Funnel retrieval for a Matryoshka-trained model (``matryoshka_dims``) on a bf16 catalogue: shortlist on the narrow prefix
+        dims[0], re-rank the survivors exactly on each wider prefix, the last one dims[-1].  Every stage reads its prefix of the resident
+        [N,D] catalogue in place: no truncated copy exists, and one norm plane per prefix is kept.
+        Stage 0: ``hip.catalog_funnel_select`` at dims[0] picks shortlists[0] items per user under the coarse bf16-MFMA scores of that
+        prefix; it carries gt_index, exclude and chunk_rows.  Stage i >= 1: ``hip.catalog_funnel_rerank`` at dims[i] scores the survivors
+        exactly and keeps shortlists[i]; the last stage keeps k.
+        dims: 2 to 8 ints, strictly ascending multiples of 8, the last at most D.  shortlists: len(dims) - 1 ints, non-increasing, each in
+        [k, 1024]; None means min(1024, max(128, 2 k)) at every stage: a default that leaves each re-rank twice the room the call
+        returns, NOT a tuned value -- choose them from the recall each prefix of the model gives.  k: an int in [1, 1024].
+        -> the dict of ``retrieve_two_stage``: topk_index int32 [B,k], topk_score f32 [B,k] with the exact scores at dims[-1] in the exact
+        order; with gt_index also rank / mrr / hit_at / ndcg_at from the COARSE scores at dims[0], rank_is_coarse=True and
+        rank_dim=dims[0].  A prefix of an embedding that was not trained for it is not a shortlist: the recall is the model's."""
+        if self.catalog.dtype != torch.bfloat16:
+            raise ValueError("retrieve: shortlist needs a bf16 catalogue (CatalogEvaluator(dtype=torch.bfloat16)), this one is "
+                             f"{self.catalog.dtype}")
+        top, D = hip.CATALOG_DEEP_TOPK_MAX, self.catalog.shape[1]
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= top:
+            raise ValueError(f"retrieve_funnel: k must be an int in [1, {top}], got {k!r}")
+        if dims is None:
+            raise ValueError("retrieve_funnel: dims must be given, the prefix widths of the stages")
+        dims = hip.mrl_dims(dims, "retrieve_funnel: dims")
+        if len(dims) < 2 or any(d % 8 for d in dims) or dims[-1] > D:
+            raise ValueError(f"retrieve_funnel: dims must hold 2 to {hip.MRL_MAX_DIMS} ascending multiples of 8, the last at most D = {D}, "
+                             f"got {dims}")
+        if shortlists is None:
+            shortlists = (min(top, max(hip.CATALOG_TOPK_MAX, 2 * k)),) * (len(dims) - 1)
+        try:
+            shortlists = tuple(shortlists)
+        except TypeError:
+            raise ValueError(f"retrieve_funnel: shortlists must be a sequence of {len(dims) - 1} ints, got {shortlists!r}") from None
+        if len(shortlists) != len(dims) - 1 or any(isinstance(s, bool) or not isinstance(s, int) for s in shortlists) or \
+                any(not k <= s <= top for s in shortlists) or any(b > a for a, b in zip(shortlists, shortlists[1:])):
+            raise ValueError(f"retrieve_funnel: shortlists must hold {len(dims) - 1} non-increasing ints in [k, {top}] (k = {k!r}), "
+                             f"got {shortlists!r}")
+        u = user_embeddings.detach().to(self.catalog.device, F32).contiguous()
+        ex = pack_exclude(exclude, u.shape[0])
+        if ex is not None:
+            ex = ex.to(u.device)
+        gt = None if gt_index is None else torch.as_tensor(gt_index).to(u.device, torch.int64)
+        inv = self._prefix_norms(dims)
+        idx, _, rank, _ = hip.catalog_funnel_select(u, self.catalog, dims[0], shortlists[0], inv[dims[0]], gt_index=gt, exclude=ex,
+                                                    chunk_rows=chunk_rows)
+        keep = shortlists[1:] + (k,)
+        for d, n in zip(dims[1:], keep):
+            idx, val, _ = hip.catalog_funnel_rerank(u, self.catalog, idx, d, n, inv[d])
+        out = {"topk_index": idx, "topk_score": val}
+        if rank is not None:
+            ks = (k,) if ks is None else tuple(int(x) for x in ks)
+            m = ranking_metrics(rank, ks).cpu().tolist()                                 # the one host read
+            out.update(rank=rank, mrr=m[0], hit_at=dict(zip(ks, m[1:1 + len(ks)])), ndcg_at=dict(zip(ks, m[1 + len(ks):])),
+                       rank_is_coarse=True, rank_dim=dims[0])
         return out

@@ -1507,6 +1507,89 @@ def catalog_deep_rerank(user, catalog, index, k=None, cat_inv_norm=None):
     return idx, val, cat_inv_norm
 
 
+def _funnel_operands(who, user, catalog, dim, cat_inv_norm):
+    """The operand checks of the funnel wrappers: user [B,Du] f32 and catalog [N,Dc] f32 or bf16, both taken whole -- only their first
+    `dim` components are read, with the row strides Du and Dc, and no copy is made -- and cat_inv_norm [N] f32, the plane of this prefix.
+    Returns (B, N, dim, ld, ldu, device, cat_inv_norm, cat_norm_ready)."""
+    if catalog.dtype not in (F32, BF16):
+        raise ValueError(f"{who}: catalog must be f32 or bf16, got {catalog.dtype}")
+    if isinstance(dim, bool) or not isinstance(dim, int):
+        raise ValueError(f"{who}: dim must be an int, got {dim!r}")
+    if user.dim() != 2 or catalog.dim() != 2 or not 0 < dim <= min(user.shape[1], catalog.shape[1]):
+        raise ValueError(f"{who}: user [B,Du] and catalog [N,Dc] must both hold the prefix dim = {dim}, got {tuple(user.shape)} and "
+                         f"{tuple(catalog.shape)}")
+    B, N = user.shape[0], catalog.shape[0]
+    cat_inv_norm, ready = _catalog_norm(cat_inv_norm, N, user.device, who)
+    _need(user, F32, f"{who}: user")
+    _need(catalog, catalog.dtype, f"{who}: catalog")
+    return B, N, dim, catalog.shape[1], user.shape[1], user.device, cat_inv_norm, ready
+
+
+def catalog_prefix_norms(catalog, dims):
+    """The inverse norms of len(dims) prefixes of every row of catalog [N,D] f32 or bf16 (ur_catalog_prefix_norms,
+    include/unirec_hip_funnel.h) -> inv f32 [L,N]: plane l holds, bit for bit, the cat_inv_norm the catalogue wrappers compute on the
+    contiguous slice catalog[:, :dims[l]].  The catalogue is read once, in place, for all planes.  dims: what mrl_dims accepts (1 to
+    MRL_MAX_DIMS ascending multiples of 4), multiples of 8 for a bf16 catalogue, the last at most D."""
+    who = "catalog_prefix_norms"
+    dims = mrl_dims(dims, "dims")
+    if catalog.dtype not in (F32, BF16):
+        raise ValueError(f"{who}: catalog must be f32 or bf16, got {catalog.dtype}")
+    if catalog.dim() != 2:
+        raise ValueError(f"{who}: catalog must be [N,D], got {tuple(catalog.shape)}")
+    if catalog.dtype == BF16 and any(d % 8 for d in dims):
+        raise ValueError(f"dims: every entry must be a multiple of 8 for a bf16 catalogue, got {dims}")
+    if dims[-1] > catalog.shape[1]:
+        raise ValueError(f"dims: the last entry must be at most the catalogue width {catalog.shape[1]}, got {dims}")
+    _need(catalog, catalog.dtype, f"{who}: catalog")
+    N, L = catalog.shape[0], len(dims)
+    inv = torch.empty((L, N), dtype=F32, device=catalog.device)
+    a = _lib.CatalogPrefixNorms()
+    a.catalog, a.catalog_bf16, a.N, a.ld, a.L, a.inv = catalog.data_ptr(), int(catalog.dtype == BF16), N, catalog.shape[1], L, inv.data_ptr()
+    a.dims[:L] = dims
+    check(_lib.load().ur_catalog_prefix_norms(ctypes.byref(a), _stream()), "ur_catalog_prefix_norms")
+    return inv
+
+
+def catalog_funnel_select(user, catalog, dim, K, cat_inv_norm=None, gt_index=None, exclude=None, chunk_rows=None, segments=None):
+    """catalog_coarse_deep_select on the first `dim` components of user [B,Du] f32 and of a bf16 catalog [N,Dc], read in place
+    (ur_catalog_funnel_select, include/unirec_hip_funnel.h): the tensors are taken whole and their row strides passed, no [N,dim] copy
+    exists.  Every output equals, in every bit, catalog_coarse_deep_select(user[:, :dim].contiguous(), catalog[:, :dim].contiguous(), K,
+    ...)'s: the APPROXIMATE coarse scores of the prefix, the lists, the rank and the norms.  cat_inv_norm is the [N] plane of THIS prefix
+    (a row of catalog_prefix_norms), in, or computed and returned.  dim: a multiple of 8.
+    segments: for tests, as in catalog_coarse_deep_select.
+    Returns (topk_index int32 [B,K], topk_score f32 [B,K], rank int32 [B] or None, cat_inv_norm)."""
+    if catalog.dtype != BF16:
+        raise ValueError("catalog_funnel_select: the coarse scorer reads a bf16 catalogue (CatalogEvaluator(dtype=torch.bfloat16)), "
+                         f"got {catalog.dtype}")
+    a = _lib.CatalogFunnelSelect()
+    a.B, a.N, a.dim, a.ld, a.ldu, dev, cat_inv_norm, a.cat_norm_ready = _funnel_operands("catalog_funnel_select", user, catalog, dim, cat_inv_norm)
+    a.user, a.catalog, a.cat_inv_norm, a.catalog_bf16 = user.data_ptr(), catalog.data_ptr(), cat_inv_norm.data_ptr(), 1
+    a.K, a.chunk_rows, a.segments = int(K), int(chunk_rows or 0), int(segments or 0)
+    idx, val = _catalog_lists(a, a.B, a.K, dev)
+    gt, rank = _catalog_filters("catalog_funnel_select", a, a.B, dev, gt_index, exclude)
+    _catalog_call("ur_catalog_funnel_select", a, dev, "catalog_funnel_select")
+    return idx, val, rank, cat_inv_norm
+
+
+def catalog_funnel_rerank(user, catalog, index, dim, k=None, cat_inv_norm=None):
+    """catalog_deep_rerank on the first `dim` components of user [B,Du] f32 and catalog [N,Dc] f32 or bf16, read in place
+    (ur_catalog_funnel_rerank, include/unirec_hip_funnel.h): index int32 [B,K'] with K' <= 1024, an entry outside [0,N) an empty slot; the
+    index and score bits are catalog_deep_rerank's on the contiguous slices, and with dim == Du == Dc that call's on the same tensors.
+    cat_inv_norm is the [N] plane of THIS prefix.  Returns (topk_index int32 [B,k], topk_score f32 [B,k], cat_inv_norm)."""
+    a = _lib.CatalogFunnelRerank()
+    a.B, a.N, a.dim, a.ld, a.ldu, dev, cat_inv_norm, a.cat_norm_ready = _funnel_operands("catalog_funnel_rerank", user, catalog, dim, cat_inv_norm)
+    a.user, a.catalog, a.cat_inv_norm = user.data_ptr(), catalog.data_ptr(), cat_inv_norm.data_ptr()
+    a.catalog_bf16 = int(catalog.dtype == BF16)
+    _need(index, torch.int32, "catalog_funnel_rerank: index")
+    if index.dim() != 2 or index.shape[0] != a.B:
+        raise ValueError(f"catalog_funnel_rerank: index must be [{a.B}, K'], got {tuple(index.shape)}")
+    a.index, a.K_in = index.data_ptr(), index.shape[1]
+    a.k = index.shape[1] if k is None else int(k)
+    idx, val = _catalog_lists(a, a.B, a.k, dev)
+    _catalog_call("ur_catalog_funnel_rerank", a, dev, "catalog_funnel_rerank")
+    return idx, val, cat_inv_norm
+
+
 def catalog_softmax(user, catalog, gt_index, temperature, cat_inv_norm=None, exclude=None, chunk_rows=None, scorer=None, grad_scale=1.0,
                     need_grad=True):
     """The softmax loss over the whole catalogue [N,D] f32 or bf16 (ur_catalog_softmax, include/unirec_hip_loss.h): cross-entropy of
