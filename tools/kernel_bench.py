@@ -10,6 +10,7 @@ shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
     python tools/kernel_bench.py catalog --funnel-dims 256 1024 --funnel-shortlists 1024 --K 1000 [--users 512 64] [--rounds 5]
     python tools/kernel_bench.py negatives --B 64 --P 1000 --N 1000000 --K 128 [--catalog-dtype f32|bf16] [--rounds 3]
     python tools/kernel_bench.py catalog_softmax --users 64 512 --dtypes f32 bf16 --N 1000000 [--D 1024] [--rounds 5]
+    python tools/kernel_bench.py catalog_mrl_softmax --users 64 512 --dtypes f32 bf16 --dims 64,128,256,512,1024 [--N 1000000] [--rounds 5]
     python tools/kernel_bench.py merge --B 64 --S 2048 [--layers 28] [--rank 16] [--rounds 5] [--iters 2]
     python tools/kernel_bench.py pool --B 64 --S 2048 [--D 1024] [--rounds 5] [--iters 20]
     python tools/kernel_bench.py mrl --B 64 --N 999 --D 1024 --dims 64,128,256,512,1024 [--rounds 5] [--iters 20]"""
@@ -722,6 +723,85 @@ def catalog_softmax(args):
         del cat
 
 
+def catalog_mrl_softmax(args):
+    """The Matryoshka catalogue softmax (hip.catalog_mrl_softmax, prefixes --dims of a [--N, --D] catalogue read in place) against the only
+    way to the same numbers without it, alternating --rounds times in this process (device events around --iters calls; medians), per
+    (--users, --dtypes) pair, every call with its norm planes ready, exclude [B,50]:
+      (a) hip.catalog_mrl_softmax, forward and forward + backward (and the forward with each scorer forced);
+      (b) K hip.catalog_softmax calls on contiguous slices, slices ready, and again with the slices made inside the timed region;
+      (c) one plain hip.catalog_softmax at --D;
+      (d) peak device allocation of one cold call of (a) against (b) with its slices (workspace included, the resident catalogue not)."""
+    N, D = args.N, args.D
+    dims = tuple(int(d) for d in args.dims.split(","))
+    tau = 0.07
+    g = torch.Generator(device="cuda").manual_seed(0)
+    cat32 = torch.randn(N, D, generator=g, device="cuda")
+
+    def peak(fn, tags):
+        for key in [k for k in hip._ws_cache if k[1] in tags]:
+            del hip._ws_cache[key]
+        torch.cuda.synchronize(); torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn(); torch.cuda.synchronize()
+        return torch.cuda.max_memory_allocated() - base
+
+    for dtype in (args.dtypes or [args.catalog_dtype]):
+        cat = cat32 if dtype == "f32" else cat32.to(torch.bfloat16)
+        planes = hip.catalog_prefix_norms(cat, dims)
+        for B in (args.users or [args.B]):
+            user = torch.randn(B, D, generator=g, device="cuda")
+            gt = torch.randint(0, N, (B,), generator=g, device="cuda")
+            seen = torch.sort(torch.randint(0, N, (B, 50), generator=g, device="cuda"), dim=1).values.contiguous()
+
+            def mrl_call(**kw):
+                return hip.catalog_mrl_softmax(user, cat, gt, dims, None, tau, planes, exclude=seen, **kw)
+
+            def sliced(ready=None, **kw):                                          # (slices made here live one at a time)
+                out = []
+                for k, d in enumerate(dims):
+                    u, c = ready[k] if ready else (user[:, :d].contiguous(), cat[:, :d].contiguous())
+                    out.append(hip.catalog_softmax(u, c, gt, tau, planes[k], exclude=seen, **kw)[:4])
+                return out
+
+            mem_a = peak(mrl_call, ("catalog_mrl_softmax",))
+            mem_b = peak(sliced, ("catalog_softmax",))
+            ready = [(user[:, :d].contiguous(), cat[:, :d].contiguous()) for d in dims]
+            slice_bytes = sum(c.numel() * c.element_size() for _, c in ready)
+            variants = [("(a) mrl forward", lambda: mrl_call(need_grad=False)),
+                        ("(a) mrl forward + backward", mrl_call),
+                        ("(a) mrl forward, vector scorer", lambda: mrl_call(need_grad=False, scorer="vector")),
+                        ("(a) mrl forward, mfma scorer", lambda: mrl_call(need_grad=False, scorer="mfma")),
+                        ("(b) K sliced forward, slices ready", lambda: sliced(ready, need_grad=False)),
+                        ("(b) K sliced forward + backward, slices ready", lambda: sliced(ready)),
+                        ("(b) K sliced forward + backward, slices made", sliced),
+                        ("(c) plain forward at D", lambda: hip.catalog_softmax(user, cat, gt, tau, planes[-1], exclude=seen, need_grad=False)),
+                        ("(c) plain forward + backward at D", lambda: hip.catalog_softmax(user, cat, gt, tau, planes[-1], exclude=seen))]
+            times = {name: [] for name, _ in variants}
+            for _, fn in variants:
+                fn(); fn()
+            torch.cuda.synchronize()
+            for _ in range(args.rounds):
+                for name, fn in variants:
+                    times[name].append(timeit(fn, args.iters))
+            loss = float(mrl_call(need_grad=False)[0])
+            want = sum(float(r[0]) for r in sliced(ready, need_grad=False))
+            med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+            print(f"catalog_mrl_softmax B={B} N={N} D={D} dims={dims} (sum d_k / D = {sum(dims) / D:.3f}) catalogue {dtype} "
+                  f"({cat.numel() * cat.element_size() / 2**30:.2f} GiB, slices {slice_bytes / 2**30:.2f} GiB), exclude [B,50], {args.rounds} alternating "
+                  f"rounds of {args.iters} calls; loss {loss:.6f} against {want:.6f} from the sliced calls")
+            for name, _ in variants:
+                t = sorted(times[name])
+                print(f"  {name:46s}: median {med[name]:9.3f} ms  min {t[0]:9.3f}  max {t[-1]:9.3f}")
+            for a, others in (("(a) mrl forward", ("(b) K sliced forward, slices ready", "(c) plain forward at D")),
+                              ("(a) mrl forward + backward", ("(b) K sliced forward + backward, slices ready", "(b) K sliced forward + backward, slices made",
+                                                              "(c) plain forward + backward at D"))):
+                for o in others:
+                    print(f"  {a} / {o}: {med[a] / med[o]:.3f}")
+            print(f"  (d) peak allocation of a cold call: (a) {mem_a / 2**20:.1f} MiB, (b) with its slices {mem_b / 2**20:.1f} MiB")
+            del user, ready
+        del cat, planes
+
+
 def merge(args):
     """Merged adapters (Qwen3LoRAModel.merge_adapter): the evaluation forward of the decoder (--layers of the 0.6B shape, rank --rank on all
     seven projections, B x S tokens, no_grad, eval mode) with the adapters merged and unmerged, alternating --rounds times in this process
@@ -879,7 +959,7 @@ def mrl(args):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog", "negatives", "catalog_softmax", "merge", "pool", "mrl"])
+    ap.add_argument("what", choices=["attn", "gemm", "lora", "rope", "dw", "xattn", "gemm_lora", "gemm_merge", "gemm_step", "rmslora", "swilora", "catalog", "negatives", "catalog_softmax", "catalog_mrl_softmax", "merge", "pool", "mrl"])
     ap.add_argument("--B", type=int, default=8)
     ap.add_argument("--S", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=5)
@@ -908,4 +988,4 @@ if __name__ == "__main__":
     ap.add_argument("--lib", action="store_true", help="gemm: also time torch.matmul on the same operands (reference point)")
     a = ap.parse_args()
     {"attn": attn, "gemm": gemm, "lora": lora, "rope": rope, "dw": dw, "xattn": xattn, "gemm_lora": gemm_lora, "gemm_merge": gemm_merge, "gemm_step": gemm_step, "rmslora": rmslora, "swilora": swilora,
-     "catalog": catalog, "negatives": negatives, "catalog_softmax": catalog_softmax, "merge": merge, "pool": pool, "mrl": mrl}[a.what](a)
+     "catalog": catalog, "negatives": negatives, "catalog_softmax": catalog_softmax, "catalog_mrl_softmax": catalog_mrl_softmax, "merge": merge, "pool": pool, "mrl": mrl}[a.what](a)

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -141,6 +141,19 @@ class MrlInfoNCE(ctypes.Structure):
                 ("B", c_int), ("N", c_int), ("D", c_int), ("K", c_int), ("dims", c_int * MRL_MAX_DIMS),
                 ("weights", c_float * MRL_MAX_DIMS), ("temperature", c_float), ("grad_scale", c_float),
                 ("scores", c_void_p), ("cand_inv_norm", c_void_p), ("plane_loss", c_void_p), ("loss", c_void_p), ("d_user", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_i64)]
+
+
+class CatalogMrlSoftmax(ctypes.Structure):
+    """Mirror of ur_catalog_mrl_softmax_t (include/unirec_hip_mrl_loss.h): CatalogSoftmax with K, dims, weights and plane_loss."""
+    _fields_ = [("user", c_void_p), ("catalog", c_void_p), ("catalog_bf16", c_int),
+                ("cat_inv_norm", c_void_p), ("cat_norm_ready", c_int),
+                ("gt_index", c_void_p), ("exclude", c_void_p), ("E", c_int),
+                ("temperature", c_float), ("grad_scale", c_float),
+                ("K", c_int), ("dims", c_int * MRL_MAX_DIMS), ("weights", c_float * MRL_MAX_DIMS),
+                ("plane_loss", c_void_p), ("loss", c_void_p), ("row_loss", c_void_p), ("lse", c_void_p), ("d_user", c_void_p),
+                ("B", c_int), ("N", c_i64), ("D", c_int),
+                ("chunk_rows", c_i64), ("scorer", c_int),
                 ("workspace", c_void_p), ("workspace_bytes", c_i64)]
 
 
@@ -402,6 +415,12 @@ FUNNEL_SIGNATURES = {
     "ur_catalog_funnel_rerank": (c_int, [ctypes.POINTER(CatalogFunnelRerank), c_void_p]),
 }
 
+# the Matryoshka loss family: every symbol include/unirec_hip_mrl_loss.h declares (tests/test_catalog_mrl_softmax_host.py holds this
+# table and the struct mirror above to that header and to the built library)
+MRL_LOSS_SIGNATURES = {
+    "ur_catalog_mrl_softmax": (c_int, [ctypes.POINTER(CatalogMrlSoftmax), c_void_p]),
+}
+
 _lib = None
 
 
@@ -425,7 +444,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(ADAPTER_SIGNATURES.items()) + \
             list(POOL_SIGNATURES.items()) + list(MRL_SIGNATURES.items()) + list(COARSE_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + \
-            list(COARSE_DEEP_SIGNATURES.items()) + list(FUNNEL_SIGNATURES.items()):
+            list(COARSE_DEEP_SIGNATURES.items()) + list(FUNNEL_SIGNATURES.items()) + list(MRL_LOSS_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

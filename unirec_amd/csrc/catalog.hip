@@ -19,9 +19,11 @@
 //                       (catalog_scores_mfma_kernel: the vector kernel's fmaf chains and sum tree, so the same score bits).
 //   ur_catalog_deep_select (include/unirec_hip_deep.h): the same streaming retrieval with lists of up to 1024 items.  The chunks are
 //                       scored by the launches of select mode; the selection kernels are those of catalog_deep.hip.h.
+#include <utility>
 #include "common.hip.h"
 #include "unirec_hip.h"
 #include "unirec_hip_loss.h"
+#include "unirec_hip_mrl_loss.h"
 #include "unirec_hip_deep.h"
 #include "catalog_select.hip.h"
 #include "catalog_deep.hip.h"
@@ -78,17 +80,19 @@ __global__ void gather_bytes_kernel(const uint8_t* __restrict__ src, const long*
 // (their vectors staged once in LDS) and walks catalogue rows, one row per wave per step: each lane holds 4-element
 // pieces of the row and accumulates 16 dot products, reduced across the wave at the end of the row.
 constexpr int CU_USERS = 16;
+// (the body: uld / cld = the row strides of user and cat in elements, D for the contiguous kernel; only the first D components of a
+// row are read, so with strides above D this is the kernel on a prefix of rows read in place -- catalog_scores_prefix_kernel)
 template <typename CT>
-__global__ __launch_bounds__(256) void catalog_scores_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
-                                                             const CT* __restrict__ cat, const float* __restrict__ inv_c,
-                                                             float* __restrict__ scores, int B, long N, int D, long rows_per_block) {
+__device__ __forceinline__ void catalog_scores_body(const float* __restrict__ user, long uld, const float* __restrict__ inv_u,
+                                                    const CT* __restrict__ cat, long cld, const float* __restrict__ inv_c,
+                                                    float* __restrict__ scores, int B, long N, int D, long rows_per_block) {
   extern __shared__ __attribute__((aligned(16))) float us[];      // [CU_USERS][D]
   const int b0 = blockIdx.y * CU_USERS;
   const int nb = min(CU_USERS, B - b0);
   for (int i = threadIdx.x * 4; i < CU_USERS * D; i += 256 * 4) {
     const int u = i / D, d = i - u * D;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (u < nb) v = *reinterpret_cast<const float4*>(user + (long)(b0 + u) * D + d);
+    if (u < nb) v = *reinterpret_cast<const float4*>(user + (long)(b0 + u) * uld + d);
     *reinterpret_cast<float4*>(us + i) = v;
   }
   __syncthreads();
@@ -98,7 +102,7 @@ __global__ __launch_bounds__(256) void catalog_scores_kernel(const float* __rest
     float acc[CU_USERS];
 #pragma unroll
     for (int u = 0; u < CU_USERS; ++u) acc[u] = 0.f;
-    const CT* cp = cat + n * D;
+    const CT* cp = cat + n * cld;
     for (int d = lane * 4; d < D; d += 256) {
       const float4 c = load4(cp + d);
 #pragma unroll
@@ -114,6 +118,18 @@ __global__ __launch_bounds__(256) void catalog_scores_kernel(const float* __rest
       if (lane == 0 && u < nb) scores[(long)(b0 + u) * N + n] = s * inv_u[b0 + u] * ic;
     }
   }
+}
+template <typename CT>
+__global__ __launch_bounds__(256) void catalog_scores_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
+                                                             const CT* __restrict__ cat, const float* __restrict__ inv_c,
+                                                             float* __restrict__ scores, int B, long N, int D, long rows_per_block) {
+  catalog_scores_body<CT>(user, (long)D, inv_u, cat, (long)D, inv_c, scores, B, N, D, rows_per_block);
+}
+template <typename CT>
+__global__ __launch_bounds__(256) void catalog_scores_prefix_kernel(const float* __restrict__ user, long uld, const float* __restrict__ inv_u,
+                                                                    const CT* __restrict__ cat, long cld, const float* __restrict__ inv_c,
+                                                                    float* __restrict__ scores, int B, long N, int D, long rows_per_block) {
+  catalog_scores_body<CT>(user, uld, inv_u, cat, cld, inv_c, scores, B, N, D, rows_per_block);
 }
 
 __global__ void rank_of_index_kernel(const float* __restrict__ scores, const long* __restrict__ gt, int* __restrict__ rank, long N) {
@@ -137,15 +153,15 @@ __global__ void rank_of_index_kernel(const float* __restrict__ scores, const lon
 // (the same lane -> element map, the same fmaf chain, the same wave_sum and the same two multiplies), so ref[b] has the bits that
 // kernel writes for that row.
 template <typename CT>
-__global__ __launch_bounds__(256) void catalog_gt_score_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
-                                                               const CT* __restrict__ cat, const float* __restrict__ inv_c,
-                                                               const long* __restrict__ gt, float* __restrict__ ref, int B, long N, int D) {
+__device__ __forceinline__ void catalog_gt_score_body(const float* __restrict__ user, long uld, const float* __restrict__ inv_u,
+                                                      const CT* __restrict__ cat, long cld, const float* __restrict__ inv_c,
+                                                      const long* __restrict__ gt, float* __restrict__ ref, int B, long N, int D) {
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
   const int lane = threadIdx.x & 63;
   const long g = min(max(gt[b], 0L), N - 1);
-  const CT* cp = cat + g * D;
-  const float* up = user + (long)b * D;
+  const CT* cp = cat + g * cld;
+  const float* up = user + (long)b * uld;
   float acc = 0.f;
   for (int d = lane * 4; d < D; d += 256) {
     const float4 c = load4(cp + d);
@@ -155,6 +171,19 @@ __global__ __launch_bounds__(256) void catalog_gt_score_kernel(const float* __re
   const float ic = inv_c[g];
   const float s = wave_sum(acc);
   if (lane == 0) ref[b] = s * inv_u[b] * ic;
+}
+template <typename CT>
+__global__ __launch_bounds__(256) void catalog_gt_score_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
+                                                               const CT* __restrict__ cat, const float* __restrict__ inv_c,
+                                                               const long* __restrict__ gt, float* __restrict__ ref, int B, long N, int D) {
+  catalog_gt_score_body<CT>(user, (long)D, inv_u, cat, (long)D, inv_c, gt, ref, B, N, D);
+}
+// (the same on the first D components of rows uld / cld elements apart)
+template <typename CT>
+__global__ __launch_bounds__(256) void catalog_gt_score_prefix_kernel(const float* __restrict__ user, long uld, const float* __restrict__ inv_u,
+                                                                      const CT* __restrict__ cat, long cld, const float* __restrict__ inv_c,
+                                                                      const long* __restrict__ gt, float* __restrict__ ref, int B, long N, int D) {
+  catalog_gt_score_body<CT>(user, uld, inv_u, cat, cld, inv_c, gt, ref, B, N, D);
 }
 
 // ---- f32-MFMA scorer ---------------------------------------------------------------------------------------------------------
@@ -198,10 +227,13 @@ template <> struct mf_row<bf16_t> {
 
 // WIDE: D > 1024 (16 users per workgroup, 8 pieces per chain at most).  FULL: D = 256 JMAX, so every chain has every piece and the
 // conditions below fold away; the code is one straight line per row group.
+// (the body: uld / cld = the row strides of user and cat, D for the contiguous kernel.  With strides above D it scores the first D
+// components of rows read in place -- catalog_scores_mfma_prefix_kernel: a piece at or past D is skipped by the conditions below, never
+// loaded as an operand, so what lies behind the prefix in a row reaches no result.)
 template <typename CT, bool WIDE, bool FULL>
-__global__ __launch_bounds__(256) void catalog_scores_mfma_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
-                                                                  const CT* __restrict__ cat, const float* __restrict__ inv_c,
-                                                                  float* __restrict__ scores, int B, long N, int D, long rows_per_block, int ub) {
+__device__ __forceinline__ void catalog_scores_mfma_body(const float* __restrict__ user, long uld, const float* __restrict__ inv_u,
+                                                         const CT* __restrict__ cat, long cld, const float* __restrict__ inv_c,
+                                                         float* __restrict__ scores, int B, long N, int D, long rows_per_block, int ub) {
   constexpr int UT = WIDE ? 1 : 2, RT = MF_TILES / UT, JMAX = WIDE ? 8 : 4;
   extern __shared__ __attribute__((aligned(16))) float us[];       // [64 chains][J][UT][k 4][user 16] | exchange [4 waves][MF_TILES][64] f32x4
   const int J = (D + 255) >> 8;
@@ -214,7 +246,7 @@ __global__ __launch_bounds__(256) void catalog_scores_mfma_kernel(const float* _
   for (int i = threadIdx.x; i < 16 * UT * D4; i += 256) {
     const int u = i / D4, d = (i - u * D4) * 4;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (u < nb) v = *reinterpret_cast<const float4*>(user + (long)(b0 + u) * D + d);
+    if (u < nb) v = *reinterpret_cast<const float4*>(user + (long)(b0 + u) * uld + d);
     float* q = us + (((((d & 255) >> 2) * J + (d >> 8)) * UT + (u >> 4)) << 6) + (u & 15);
     q[0] = v.w; q[16] = v.z; q[32] = v.y; q[48] = v.x;
   }
@@ -225,7 +257,7 @@ __global__ __launch_bounds__(256) void catalog_scores_mfma_kernel(const float* _
   for (long n0 = r0; n0 < r1; n0 += 16 * RT) {
     mf_row<CT> bp[RT];                           // a row past the end is read as the last one and never stored
 #pragma unroll
-    for (int r = 0; r < RT; ++r) bp[r] = mf_row<CT>(cat + min(n0 + r * 16 + col, N - 1) * D, k);
+    for (int r = 0; r < RT; ++r) bp[r] = mf_row<CT>(cat + min(n0 + r * 16 + col, N - 1) * cld, k);
     float bq[3][JMAX][RT];
     f32x4 st[5][MF_TILES];                       // st[s]: a finished subtree of 2^s chains waiting for its sibling
 #pragma unroll
@@ -281,6 +313,141 @@ __global__ __launch_bounds__(256) void catalog_scores_mfma_kernel(const float* _
       for (int e = 0; e < 4; ++e) {
         const int u = ut * 16 + k * 4 + e;
         if (u < nb) scores[(long)(b0 + u) * N + n] = v[e] * inv_u[b0 + u] * ic;
+      }
+    }
+  }
+}
+template <typename CT, bool WIDE, bool FULL>
+__global__ __launch_bounds__(256) void catalog_scores_mfma_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
+                                                                  const CT* __restrict__ cat, const float* __restrict__ inv_c,
+                                                                  float* __restrict__ scores, int B, long N, int D, long rows_per_block, int ub) {
+  catalog_scores_mfma_body<CT, WIDE, FULL>(user, (long)D, inv_u, cat, (long)D, inv_c, scores, B, N, D, rows_per_block, ub);
+}
+template <typename CT, bool WIDE, bool FULL>
+__global__ __launch_bounds__(256) void catalog_scores_mfma_prefix_kernel(const float* __restrict__ user, long uld, const float* __restrict__ inv_u,
+                                                                         const CT* __restrict__ cat, long cld, const float* __restrict__ inv_c,
+                                                                         float* __restrict__ scores, int B, long N, int D, long rows_per_block,
+                                                                         int ub) {
+  catalog_scores_mfma_body<CT, WIDE, FULL>(user, uld, inv_u, cat, cld, inv_c, scores, B, N, D, rows_per_block, ub);
+}
+
+// ---- one scoring pass for several prefixes (ur_catalog_mrl_softmax) -------------------------------------------------------------------
+// catalog_scores_mfma_kernel for up to MG_PLANES nested prefixes d_0 < .. < d_{NP-1} <= 1024 of the rows at once: plane p's scores, bit
+// for bit what that kernel writes at width d_p.  The chain of c runs over ascending pieces j as there; its value after the last piece
+// below d_p IS plane p's chain (a piece 4c + 256j lies wholly on one side of d_p), so at that point -- a wave-uniform condition -- the
+// accumulator enters plane p's own tree of pending subtrees, by the same counter in the same bit-reversed order; a chain with no piece
+// below d_p enters as +0, the idle lane of the vector kernel (a chain is never -0: it starts from +0).  So the MFMAs are those of ONE
+// pass at width d_{NP-1}, not of NP passes; what is paid per plane is the tree's adds and the epilogue.  NP trees do not fit beside
+// four output tiles: a wave keeps UT = 2 user tiles of ONE 16-row tile (2 f32x4 per pending subtree and plane), a workgroup steps 16
+// rows.  The last two tree levels go through the same LDS exchange, two planes per round: wave w finishes (plane w / 2, tile w % 2).
+// Three planes is what the register file takes: with four the trees spill to scratch (profiles/catalog_mrl_softmax_resource_usage.txt).
+constexpr int MG_PLANES = 3;
+// f(integral_constant<int, 0>), f(<1>), ... in order: a loop whose index is a compile-time constant of each iteration
+template <typename F, int... I>
+__device__ __forceinline__ void mf_steps(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+struct mf_group {
+  int d[MG_PLANES];                              // the prefixes, ascending; entries past NP unused
+};
+template <typename CT, int NP>
+__global__ __launch_bounds__(256) void catalog_scores_mfma_group_kernel(const float* __restrict__ user, long uld, const float* __restrict__ inv_u,
+                                                                        const CT* __restrict__ cat, long cld, const float* __restrict__ inv_c, long icld,
+                                                                        float* __restrict__ scores, long sld, int B, long N, mf_group g,
+                                                                        long rows_per_block, int ub) {
+  // plane p: user norms inv_u + p B, row norms inv_c + p icld, scores + p sld (each [B][N])
+  constexpr int UT = 2, JMAX = 4;
+  extern __shared__ __attribute__((aligned(16))) float us[];       // [64 chains][J][UT][k 4][user 16] | exchange [4 waves][MF_TILES][64] f32x4
+  const int D = g.d[NP - 1];
+  const int J = (D + 255) >> 8;
+  f32x4* ex = reinterpret_cast<f32x4*>(us + J * UT * 64 * 64);
+  const int ug = blockIdx.x % ub;
+  const long rb = blockIdx.x / ub;
+  const int b0 = ug * 16 * UT;
+  const int nb = min(16 * UT, B - b0);
+  const int D4 = D >> 2;
+  for (int i = threadIdx.x; i < 16 * UT * D4; i += 256) {
+    const int u = i / D4, d = (i - u * D4) * 4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (u < nb) v = *reinterpret_cast<const float4*>(user + (long)(b0 + u) * uld + d);
+    float* q = us + (((((d & 255) >> 2) * J + (d >> 8)) * UT + (u >> 4)) << 6) + (u & 15);
+    q[0] = v.w; q[16] = v.z; q[32] = v.y; q[48] = v.x;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, col = lane & 15, k = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long r0 = rb * rows_per_block, r1 = min(N, r0 + rows_per_block);
+  for (long n0 = r0; n0 < r1; n0 += 16) {
+    const mf_row<CT> bp(cat + min(n0 + col, N - 1) * cld, k);       // a row past the end is read as the last one and never stored
+    float bq[3][JMAX];
+    f32x4 st[NP][5][UT];                         // st[p][s]: plane p's finished subtree of 2^s chains waiting for its sibling
+    // step i - 2 of the 18: the loads of chain i, the products and the tree step of chain i - 2.  The step index is a template argument
+    // (mf_steps calls the 18 in order): the tree level of a chain is a constant of its step, in straight-line code.
+    const auto step = [&](auto index) __attribute__((always_inline)) {
+      constexpr int i = decltype(index)::value - 2;
+      if constexpr (i + 2 < 16) {
+        constexpr int t = mf_bitrev4(i + 2);
+#pragma unroll
+        for (int j = 0; j < JMAX; ++j) bq[(i + 2) % 3][j] = bp.at(4 * w + 16 * t + 256 * j < D ? 4 * w + 16 * t + 256 * j : 0);   // (a piece past D: unused)
+      }
+      if constexpr (i >= 0) {
+        const int c = w + 4 * mf_bitrev4(i);
+        constexpr int lvl = mf_trailing_ones(i);
+        f32x4 acc[UT], snap[NP][UT];             // snap[p]: the chain after its last piece below d_p; +0 without one
+#pragma unroll
+        for (int x = 0; x < UT; ++x) acc[x] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+          for (int x = 0; x < UT; ++x) snap[p][x] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < JMAX; ++j) {
+          if (4 * c + 256 * j < D) {
+            const float* ap = us + (((c * J + j) * UT) << 6) + lane;
+#pragma unroll
+            for (int x = 0; x < UT; ++x) acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[x * 64], bq[i % 3][j], acc[x], 0, 0, 0);
+#pragma unroll
+            for (int p = 0; p < NP - 1; ++p)
+              if (4 * c + 256 * j < g.d[p] && !(4 * c + 256 * (j + 1) < g.d[p])) {      // the chain's last piece below d_p (wave-uniform)
+#pragma unroll
+                for (int x = 0; x < UT; ++x) snap[p][x] = acc[x];
+              }
+          }
+        }
+#pragma unroll
+        for (int x = 0; x < UT; ++x) snap[NP - 1][x] = acc[x];      // (d_{NP-1} = D: every piece that was multiplied)
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+          for (int x = 0; x < UT; ++x) {
+            f32x4 v = snap[p][x];
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+              if (s < lvl) v = st[p][s][x] + v;
+            st[p][lvl][x] = v;
+          }
+      }
+    };
+    mf_steps(step, std::make_integer_sequence<int, 18>{});
+#pragma unroll
+    for (int p0 = 0; p0 < NP; p0 += 2) {
+      __syncthreads();                           // the previous exchange has been read
+#pragma unroll
+      for (int pp = 0; pp < 2; ++pp)
+        if (p0 + pp < NP) {
+#pragma unroll
+          for (int x = 0; x < UT; ++x) ex[(w * MF_TILES + pp * UT + x) * 64 + lane] = st[p0 + pp][4][x];
+        }
+      __syncthreads();
+      const int p = p0 + (w >> 1), ut = w & 1;   // wave w finishes item w of the round: (plane, user tile)
+      const long n = n0 + col;                   // C/D layout: column = lane & 15 (row of the catalogue), row = 4 (lane >> 4) + reg (user)
+      if (p < NP && n < N) {
+        const f32x4 v = (ex[(0 * MF_TILES + w) * 64 + lane] + ex[(2 * MF_TILES + w) * 64 + lane]) +
+                        (ex[(1 * MF_TILES + w) * 64 + lane] + ex[(3 * MF_TILES + w) * 64 + lane]);
+        const float ic = inv_c[p * icld + n];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int u = ut * 16 + k * 4 + e;
+          if (u < nb) scores[p * sld + (long)(b0 + u) * N + n] = v[e] * inv_u[(long)p * B + b0 + u] * ic;
+        }
       }
     }
   }
@@ -429,9 +596,12 @@ __global__ __launch_bounds__(256) void catalog_softmax_weight_kernel(float* __re
 // element depends on its own user and column only).  The slabs are accumulated across chunks by the stream's order: the first chunk
 // stores, later chunks add; a split without rows in a later (shorter) chunk leaves its slab alone.
 // (CSM_UT and CSM_USERS size the workspace: catalog_layout.hip.h)
+// (the body: cld = the row stride of cat in elements, D for the contiguous kernel.  With cld above D the product runs over the first D
+// columns of rows read in place -- catalog_softmax_grad_prefix_kernel: the slabs are [B,D], and the column clamp min(d, D - 4) keeps
+// every load below D, where the row's live data behind the prefix begins.)
 template <typename CT>
-__global__ __launch_bounds__(256) void catalog_softmax_grad_kernel(const float* __restrict__ wchunk, long ld, int len, const CT* __restrict__ cat,
-                                                                   float* __restrict__ slabs, int B, int D, int rps, int first) {
+__device__ __forceinline__ void catalog_softmax_grad_body(const float* __restrict__ wchunk, long ld, int len, const CT* __restrict__ cat, long cld,
+                                                          float* __restrict__ slabs, int B, int D, int rps, int first) {
   const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
   const int wave = threadIdx.x >> 6;
   const int b0 = blockIdx.x * CSM_USERS;
@@ -456,7 +626,7 @@ __global__ __launch_bounds__(256) void catalog_softmax_grad_kernel(const float* 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int n = n0 + 4 * q + j;
-      c[j] = load4(cp + (long)n * D);
+      c[j] = load4(cp + (long)n * cld);
 #pragma unroll
       for (int t = 0; t < CSM_UT; ++t) a[t][j] = wp[t][n];
     }
@@ -476,7 +646,7 @@ __global__ __launch_bounds__(256) void catalog_softmax_grad_kernel(const float* 
       const int n = n0 + 4 * q + j;
       const bool in = n < r1;
       const int ns = in ? n : r1 - 1;
-      float4 c = load4(cp + (long)ns * D);
+      float4 c = load4(cp + (long)ns * cld);
       if (!in) c = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int t = 0; t < CSM_UT; ++t) {
@@ -502,6 +672,16 @@ __global__ __launch_bounds__(256) void catalog_softmax_grad_kernel(const float* 
         *o = v;
       }
     }
+}
+template <typename CT>
+__global__ __launch_bounds__(256) void catalog_softmax_grad_kernel(const float* __restrict__ wchunk, long ld, int len, const CT* __restrict__ cat,
+                                                                   float* __restrict__ slabs, int B, int D, int rps, int first) {
+  catalog_softmax_grad_body<CT>(wchunk, ld, len, cat, (long)D, slabs, B, D, rps, first);
+}
+template <typename CT>
+__global__ __launch_bounds__(256) void catalog_softmax_grad_prefix_kernel(const float* __restrict__ wchunk, long ld, int len, const CT* __restrict__ cat,
+                                                                          long cld, float* __restrict__ slabs, int B, int D, int rps, int first) {
+  catalog_softmax_grad_body<CT>(wchunk, ld, len, cat, cld, slabs, B, D, rps, first);
 }
 
 // d_user[b] = gscale * iu_b * (sum_z slab[z][b] - u_b * iu_b * t_b), the slabs and the slots of t_b added in index order
@@ -645,6 +825,84 @@ static int launch_catalog_scores_mfma(const float* user, const float* user_inv_n
   }
   hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks_x * ub)), dim3(256), mf_lds_bytes(D, wide), st, user, user_inv_norm, catalog, cat_inv_norm,
                      scores, (int)B, (long)N, (int)D, (long)rpb, ub);
+  UR_CHECK_LAUNCH(who);
+  return 0;
+}
+
+// The two launches above on the first D components of rows read in place (user rows uld, catalogue rows cld elements apart): the grids,
+// the rows per workgroup and the LDS of the contiguous launch at width D, so a pair has the bits that launch gives on the contiguous
+// slices.  With both strides equal to D they ARE the contiguous launches.
+template <typename CT>
+static int launch_catalog_scores_prefix(const float* user, long uld, const float* user_inv_norm, const CT* catalog, long cld, const float* cat_inv_norm,
+                                        float* scores, int32_t B, int64_t N, int32_t D, hipStream_t st, const char* who) {
+  if (uld == D && cld == D) return launch_catalog_scores<CT>(user, user_inv_norm, catalog, cat_inv_norm, scores, B, N, D, st, who);
+  const int ub = ur_cdiv(B, CU_USERS);
+  long blocks_x = 2048 / ub;
+  if (blocks_x < 1) blocks_x = 1;
+  long rpb = (N + blocks_x - 1) / blocks_x;
+  rpb = (rpb + 3) / 4 * 4;
+  blocks_x = (N + rpb - 1) / rpb;
+  const size_t smem = (size_t)CU_USERS * D * sizeof(float);
+  static std::atomic<uint64_t> attr_set{0};   // per device
+  UR_ONCE_PER_DEVICE(attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&catalog_scores_prefix_kernel<CT>), hipFuncAttributeMaxDynamicSharedMemorySize, CU_USERS * 2048 * 4);
+    if (e != hipSuccess) UR_FAIL((int)e, "%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(catalog_scores_prefix_kernel<CT>, dim3((unsigned)blocks_x, (unsigned)ub), dim3(256), smem, st, user, uld, user_inv_norm, catalog,
+                     cld, cat_inv_norm, scores, (int)B, (long)N, (int)D, (long)rpb);
+  UR_CHECK_LAUNCH(who);
+  return 0;
+}
+template <typename CT>
+static int launch_catalog_scores_mfma_prefix(const float* user, long uld, const float* user_inv_norm, const CT* catalog, long cld,
+                                             const float* cat_inv_norm, float* scores, int32_t B, int64_t N, int32_t D, hipStream_t st, const char* who) {
+  if (uld == D && cld == D) return launch_catalog_scores_mfma<CT>(user, user_inv_norm, catalog, cat_inv_norm, scores, B, N, D, st, who);
+  const bool wide = D > 1024;
+  const int ub = ur_cdiv(B, wide ? 16 : 32);
+  const int group = wide ? 16 * MF_TILES : 16 * MF_TILES / 2;
+  long blocks_x = 1024 / ub;
+  if (blocks_x < 1) blocks_x = 1;
+  long rpb = (N + blocks_x - 1) / blocks_x;
+  rpb = (rpb + group - 1) / group * group;
+  blocks_x = (N + rpb - 1) / rpb;
+  void (*kernel)(const float*, long, const float*, const CT*, long, const float*, float*, int, long, int, long, int) =
+      wide ? catalog_scores_mfma_prefix_kernel<CT, true, false>                // (a prefix is narrower than its row: never 2048)
+           : (D == 1024 ? catalog_scores_mfma_prefix_kernel<CT, false, true> : catalog_scores_mfma_prefix_kernel<CT, false, false>);
+  static std::atomic<uint64_t> attr_set[3];   // per device, one per kernel
+  UR_ONCE_PER_DEVICE(attr_set[wide ? 2 : (D == 1024)]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf_lds_bytes(2048, true));
+    if (e != hipSuccess) UR_FAIL((int)e, "%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks_x * ub)), dim3(256), mf_lds_bytes(D, wide), st, user, uld, user_inv_norm, catalog, cld, cat_inv_norm,
+                     scores, (int)B, (long)N, (int)D, (long)rpb, ub);
+  UR_CHECK_LAUNCH(who);
+  return 0;
+}
+
+// one launch of the group scorer: np (2 .. MG_PLANES) prefixes d[0] < .. < d[np-1] <= 1024 of rows [0,N); plane p reads inv_u + p B and
+// inv_c + p icld and writes scores + p sld, leading dimension N
+template <typename CT>
+static int launch_catalog_scores_mfma_group(const float* user, long uld, const float* inv_u, const CT* catalog, long cld, const float* inv_c, long icld,
+                                            float* scores, long sld, int32_t B, int64_t N, const int* d, int np, hipStream_t st, const char* who) {
+  mf_group g{};
+  for (int p = 0; p < np; ++p) g.d[p] = d[p];
+  const int D = d[np - 1];
+  const int ub = ur_cdiv(B, 32);
+  long blocks_x = 1024 / ub;                                  // one workgroup per CU at a time (LDS): ~4 rounds
+  if (blocks_x < 1) blocks_x = 1;
+  long rpb = (N + blocks_x - 1) / blocks_x;
+  rpb = (rpb + 15) / 16 * 16;
+  blocks_x = (N + rpb - 1) / rpb;
+  void (*kernel)(const float*, long, const float*, const CT*, long, const float*, long, float*, long, int, long, mf_group, long, int) =
+      np == 2 ? catalog_scores_mfma_group_kernel<CT, 2> : catalog_scores_mfma_group_kernel<CT, 3>;
+  static_assert(MG_PLANES == 3, "one kernel per group size");
+  static std::atomic<uint64_t> attr_set[MG_PLANES + 1];   // per device, one per kernel
+  UR_ONCE_PER_DEVICE(attr_set[np]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mf_lds_bytes(1024, false));
+    if (e != hipSuccess) UR_FAIL((int)e, "%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks_x * ub)), dim3(256), mf_lds_bytes(D, false), st, user, uld, inv_u, catalog, cld, inv_c, icld, scores,
+                     sld, (int)B, (long)N, g, (long)rpb, ub);
   UR_CHECK_LAUNCH(who);
   return 0;
 }
@@ -848,6 +1106,187 @@ extern "C" int ur_catalog_softmax(ur_catalog_softmax_t* a, void* stream) {
   UR_REQUIRE(a->loss && a->row_loss && a->lse, "ur_catalog_softmax: loss / row_loss / lse: null pointer");
   UR_REQUIRE(!a->d_user || UR_ALIGNED16(a->d_user), "ur_catalog_softmax: d_user must be 16-byte aligned");
   return catalog_dispatch(c.catalog_bf16 == 1, a->catalog, [&](auto* cat) { return catalog_softmax_stream(c, a, cat, p, (hipStream_t)stream); });
+}
+
+// ---- ur_catalog_mrl_softmax (include/unirec_hip_mrl_loss.h) ------------------------------------------------------------------------
+// The stream above on K prefixes of the rows, read in place.  Every plane runs the launches of ur_catalog_softmax at width d_k with the
+// row stride D (the *_prefix kernels share their bodies with the contiguous ones; the fold, finish and weight kernels are the unchanged
+// ones on the plane's part of the chunk buffer, its norm plane and its slots), so plane k has the bits of that call on the contiguous
+// slices -- except that the MFMA scores of up to MG_PLANES planes come from one pass of catalog_scores_mfma_group_kernel.  What the
+// planes share besides: one read of the catalogue for all K norm planes, the chunk loop, and the last kernel.
+static_assert(CSM_MRL_MAX == UR_MRL_MAX_DIMS && UR_FUNNEL_MAX_DIMS == UR_MRL_MAX_DIMS, "one limit for the prefixes of every family");
+struct mrl_softmax_planes {
+  int d[UR_MRL_MAX_DIMS];
+  float w[UR_MRL_MAX_DIMS];
+  long slab[UR_MRL_MAX_DIMS];                  // plane k's slabs, as a float offset from the first plane's
+  int nslab[UR_MRL_MAX_DIMS];
+};
+
+namespace {
+// loss = sum_k w_k plane_loss[k]: fmaf from 0 in ascending k, a plane of weight 0 skipped.  One thread.
+__global__ void catalog_mrl_loss_kernel(const float* __restrict__ plane_loss, mrl_softmax_planes pl, int K, float* __restrict__ loss) {
+  float s = 0.f;
+  for (int k = 0; k < K; ++k)
+    if (pl.w[k] > 0.f) s = fmaf(pl.w[k], plane_loss[k], s);
+  loss[0] = s;
+}
+
+// d_user[b][d] = sum_{k : d < d_k} w_k g_k[b][d]: g_k is catalog_softmax_duser_kernel's expression on plane k's slabs [nslab_k][B][d_k],
+// slots t [k][B][CSM_SEGS] and user norm inv_u[k][b]; the sum is fmaf from 0 in ascending k, a plane of weight 0 skipped.
+__global__ __launch_bounds__(256) void catalog_mrl_duser_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
+                                                                const float* __restrict__ t_run, const float* __restrict__ slabs,
+                                                                float* __restrict__ d_user, int B, int D, mrl_softmax_planes pl, int K, float gscale) {
+  const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i >= (long)B * D) return;
+  const int b = (int)(i / D), d = (int)(i - (long)b * D);
+  const float4 u = *reinterpret_cast<const float4*>(user + i);
+  float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int p = 0; p < K; ++p) {
+    const int dk = pl.d[p];
+    if (d >= dk || !(pl.w[p] > 0.f)) continue;
+    const float* sl = slabs + pl.slab[p] + (long)b * dk + d;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int z = 0; z < pl.nslab[p]; ++z) {
+      const float4 q = *reinterpret_cast<const float4*>(sl + (long)z * B * dk);
+      s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w;
+    }
+    float t = 0.f;
+    for (int j = 0; j < CSM_SEGS; ++j) t += t_run[((long)p * B + b) * CSM_SEGS + j];
+    const float iu = inv_u[(long)p * B + b], k = iu * t, gs = gscale * iu;
+    const float4 g = make_float4(gs * (s.x - u.x * k), gs * (s.y - u.y * k), gs * (s.z - u.z * k), gs * (s.w - u.w * k));
+    const float w = pl.w[p];
+    out = make_float4(fmaf(w, g.x, out.x), fmaf(w, g.y, out.y), fmaf(w, g.z, out.z), fmaf(w, g.w, out.w));
+  }
+  *reinterpret_cast<float4*>(d_user + i) = out;
+}
+}  // namespace
+
+template <typename CT>
+static int catalog_mrl_softmax_stream(const catalog_call& c, const ur_catalog_mrl_softmax_t* a, const CT* catalog, const catalog_mrl_softmax_plan& p,
+                                      hipStream_t st) {
+  const int32_t B = a->B, D = a->D, E = a->E, K = a->K;
+  const int64_t N = a->N;
+  char* ws = (char*)a->workspace;
+  float* chunk = (float*)(ws + p.chunk);
+  float* inv_u = (float*)(ws + p.inv_u);
+  float* ref = (float*)(ws + p.ref);
+  float* m_run = (float*)(ws + p.m_run);
+  float* l_run = (float*)(ws + p.l_run);
+  float* t_run = (float*)(ws + p.t_run);
+  float* slabs = (float*)(ws + p.slabs[0]);
+  const long* gt = (const long*)a->gt_index;
+  const long* ex = (const long*)a->exclude;
+  const float* user = a->user;
+  float* inv_c = a->cat_inv_norm;
+  const float inv_tau = 1.0f / a->temperature;
+  const bool mfma = catalog_use_mfma(c);                        // by the call's (B, D), for every plane: the bits do not depend on it
+  prefix_dims dims{};
+  mrl_softmax_planes pl{};
+  for (int k = 0; k < K; ++k) {
+    dims.d[k] = pl.d[k] = a->dims[k];
+    pl.w[k] = a->weights[k];
+    pl.slab[k] = (long)((p.slabs[k] - p.slabs[0]) / 4);
+    pl.nslab[k] = p.nsplit[k];
+  }
+  // the norms of every prefix, users and catalogue, one read each; the ground-truth scores per plane
+  hipLaunchKernelGGL(row_prefix_inv_norm_kernel<float>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, (long)D, inv_u, (long)B, dims, (int)K);
+  if (!a->cat_norm_ready)
+    hipLaunchKernelGGL(row_prefix_inv_norm_kernel<CT>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, catalog, (long)D, inv_c, (long)N, dims, (int)K);
+  for (int k = 0; k < K; ++k)
+    hipLaunchKernelGGL(catalog_gt_score_prefix_kernel<CT>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, user, (long)D, (const float*)(inv_u + (long)k * B),
+                       catalog, (long)D, (const float*)(inv_c + (long)k * N), gt, ref + (long)k * B, (int)B, (long)N, (int)pl.d[k]);
+  UR_CHECK_LAUNCH(c.who);
+  // the scores of rows [c0, c0 + len) on every plane.  MFMA: runs of up to MG_PLANES planes no wider than 1024 take one pass of the group
+  // scorer; a plane left alone, or wider than 1024, takes the stride-aware single-plane launch.  Vector: one launch per plane.
+  const auto score_planes = [&](int64_t c0, int64_t len) {
+    for (int k = 0; k < K;) {
+      float* out = chunk + (long)k * B * p.rows;
+      const float* iu = inv_u + (long)k * B;
+      const float* ic = inv_c + (long)k * N + c0;
+      int np = 1;
+      while (mfma && k + np < K && np < MG_PLANES && pl.d[k + np] <= 1024) ++np;
+      const int rc = np > 1 ? launch_catalog_scores_mfma_group<CT>(user, (long)D, iu, catalog + c0 * D, (long)D, ic, (long)N, out, (long)B * p.rows, B, len,
+                                                                   pl.d + k, np, st, c.who)
+                     : mfma ? launch_catalog_scores_mfma_prefix<CT>(user, (long)D, iu, catalog + c0 * D, (long)D, ic, out, B, len, pl.d[k], st, c.who)
+                            : launch_catalog_scores_prefix<CT>(user, (long)D, iu, catalog + c0 * D, (long)D, ic, out, B, len, pl.d[k], st, c.who);
+      if (rc != 0) return rc;
+      k += np;
+    }
+    return 0;
+  };
+  const int folded = catalog_for_each_chunk(N, p.rows, [&](int64_t c0, int64_t len, int first) {
+    if (const int rc = score_planes(c0, len)) return rc;
+    for (int k = 0; k < K; ++k)
+      hipLaunchKernelGGL(catalog_softmax_fold_kernel, dim3((unsigned)B, CSM_SEGS), dim3(256), 0, st, (const float*)(chunk + (long)k * B * p.rows), (long)len,
+                         (int)c0, (int)len, p.seg, gt, ex, E, inv_tau, m_run + (long)k * B * CSM_SEGS, l_run + (long)k * B * CSM_SEGS, first);
+    UR_CHECK_LAUNCH(c.who);
+    return 0;
+  });
+  if (folded != 0) return folded;
+  for (int k = 0; k < K; ++k)
+    hipLaunchKernelGGL(catalog_softmax_finish_kernel, dim3(1), dim3(64), 0, st, (const float*)(m_run + (long)k * B * CSM_SEGS),
+                       (const float*)(l_run + (long)k * B * CSM_SEGS), (const float*)(ref + (long)k * B), inv_tau, a->lse + (long)k * B,
+                       a->row_loss + (long)k * B, a->plane_loss + k, (int)B);
+  hipLaunchKernelGGL(catalog_mrl_loss_kernel, dim3(1), dim3(1), 0, st, (const float*)a->plane_loss, pl, (int)K, a->loss);
+  UR_CHECK_LAUNCH(c.who);
+  if (!a->d_user) return 0;
+  const int weighted = catalog_for_each_chunk(N, p.rows, [&](int64_t c0, int64_t len, int first) {
+    if (const int rc = score_planes(c0, len)) return rc;
+    for (int k = 0; k < K; ++k) {
+      float* wk = chunk + (long)k * B * p.rows;
+      const int dk = pl.d[k];
+      hipLaunchKernelGGL(catalog_softmax_weight_kernel, dim3((unsigned)B, CSM_SEGS), dim3(256), 0, st, wk, (long)len, (int)c0, (int)len, p.seg,
+                         (const float*)(inv_c + (long)k * N), gt, ex, E, inv_tau, (const float*)(a->lse + (long)k * B), t_run + (long)k * B * CSM_SEGS,
+                         first);
+      const dim3 grid((unsigned)ur_cdiv(B, CSM_USERS), (unsigned)ur_cdiv(dk, 256), (unsigned)p.nsplit[k]);
+      if (dk == D)
+        hipLaunchKernelGGL(catalog_softmax_grad_kernel<CT>, grid, dim3(256), 0, st, (const float*)wk, (long)len, (int)len, catalog + c0 * D,
+                           slabs + pl.slab[k], (int)B, (int)D, p.rps[k], first);
+      else
+        hipLaunchKernelGGL(catalog_softmax_grad_prefix_kernel<CT>, grid, dim3(256), 0, st, (const float*)wk, (long)len, (int)len, catalog + c0 * D, (long)D,
+                           slabs + pl.slab[k], (int)B, dk, p.rps[k], first);
+    }
+    UR_CHECK_LAUNCH(c.who);
+    return 0;
+  });
+  if (weighted != 0) return weighted;
+  hipLaunchKernelGGL(catalog_mrl_duser_kernel, dim3((unsigned)(((long)B * D / 4 + 255) / 256)), dim3(256), 0, st, user, (const float*)inv_u,
+                     (const float*)t_run, (const float*)slabs, a->d_user, (int)B, (int)D, pl, (int)K, a->grad_scale / (float)B);
+  UR_CHECK_LAUNCH(c.who);
+  return 0;
+}
+
+extern "C" int ur_catalog_mrl_softmax(ur_catalog_mrl_softmax_t* a, void* stream) {
+  UR_REQUIRE(a, "ur_catalog_mrl_softmax: null argument struct");
+  const catalog_call c{"ur_catalog_mrl_softmax", a->B, a->N, a->D, a->E, a->chunk_rows, a->catalog_bf16, a->scorer, a->gt_index, nullptr,
+                       a->exclude, a->user, a->catalog, a->cat_inv_norm, a->workspace, a->workspace_bytes};
+  if (const int rc = catalog_check_sizes(c, 4, 1, true)) return rc;
+  const int32_t K = a->K;
+  UR_REQUIRE(K >= 1 && K <= UR_MRL_MAX_DIMS, "ur_catalog_mrl_softmax: K must be 1 .. %d (got %d)", UR_MRL_MAX_DIMS, K);
+  const int mult = a->catalog_bf16 == 1 ? 8 : 4;
+  bool any = false;
+  for (int k = 0; k < K; ++k) {
+    const int32_t d = a->dims[k];
+    UR_REQUIRE(d > 0 && (d % mult) == 0, "ur_catalog_mrl_softmax: dims[%d] must be a positive multiple of %d (got %d)", k, mult, d);
+    UR_REQUIRE(k == 0 || d > a->dims[k - 1], "ur_catalog_mrl_softmax: dims must be strictly ascending (dims[%d] = %d after %d)", k, d, a->dims[k - 1]);
+    const float w = a->weights[k];
+    UR_REQUIRE(w >= 0.f && w <= 3.0e38f, "ur_catalog_mrl_softmax: weights[%d] must be finite and >= 0 (got %g)", k, (double)w);
+    any = any || w > 0.f;
+  }
+  UR_REQUIRE(a->dims[K - 1] == a->D, "ur_catalog_mrl_softmax: the last of dims must equal D (got %d, D %d)", a->dims[K - 1], a->D);
+  UR_REQUIRE(any, "ur_catalog_mrl_softmax: weights must hold at least one positive entry");
+  UR_REQUIRE(a->temperature > 0.f && a->temperature <= 3.0e38f, "ur_catalog_mrl_softmax: temperature must be positive and finite (got %g)",
+             (double)a->temperature);
+  const catalog_mrl_softmax_plan p = catalog_mrl_softmax_layout(a->B, a->N, K, a->dims, a->chunk_rows, a->d_user != nullptr);
+  if (!a->workspace) {
+    a->workspace_bytes = p.need;
+    return 0;
+  }
+  if (const int rc = catalog_check_buffers(c, p.need, true)) return rc;
+  if (a->B == 0) return 0;
+  UR_REQUIRE(a->plane_loss && a->loss && a->row_loss && a->lse, "ur_catalog_mrl_softmax: plane_loss / loss / row_loss / lse: null pointer");
+  UR_REQUIRE(!a->d_user || UR_ALIGNED16(a->d_user), "ur_catalog_mrl_softmax: d_user must be 16-byte aligned");
+  return catalog_dispatch(c.catalog_bf16 == 1, a->catalog, [&](auto* cat) { return catalog_mrl_softmax_stream(c, a, cat, p, (hipStream_t)stream); });
 }
 
 extern "C" int ur_rank_of_index(const float* scores, const int64_t* gt_index, int32_t* rank, int32_t B, int64_t N, void* stream) {

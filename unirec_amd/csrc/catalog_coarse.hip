@@ -514,39 +514,8 @@ namespace {
 static_assert(UR_FUNNEL_MAX_DIMS == UR_MRL_MAX_DIMS, "a funnel takes the prefixes a Matryoshka head trains");
 static_assert(UR_FUNNEL_USER_GROUP == UR_COARSE_USER_GROUP, "the prefix scorer keeps the user groups of the contiguous one");
 
-// The row norms of L prefixes in one read.  row_inv_norm_kernel's chain: lane j adds the squares of its pieces at d = 4 j + 256 i in
-// ascending i.  The sum a lane holds after its last piece below dims[l] is that chain on the slice [:dims[l]] (dims are multiples of 4:
-// a piece lies wholly on one side of a boundary), so the lane keeps it as plane l's snapshot; a lane with no piece below the boundary
-// keeps 0, as the short loop does.  Each snapshot is folded by the same wave_sum and finished by the same expression.
-struct prefix_dims {
-  int d[UR_FUNNEL_MAX_DIMS];
-};
-template <typename CT>
-__global__ void row_prefix_inv_norm_kernel(const CT* __restrict__ x, long ld, float* __restrict__ inv, long rows, prefix_dims dims, int L) {
-  const long row = (long)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int lane = threadIdx.x & 63;
-  const CT* p = x + row * ld;
-  const int D = dims.d[L - 1];
-  float s = 0.f;
-  float snap[UR_FUNNEL_MAX_DIMS];
-#pragma unroll
-  for (int l = 0; l < UR_FUNNEL_MAX_DIMS; ++l) snap[l] = 0.f;
-  for (int d = lane * 4; d < D; d += 256) {
-    const float4 v = load4(p + d);
-    s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-#pragma unroll
-    for (int l = 0; l < UR_FUNNEL_MAX_DIMS; ++l)
-      if (l < L && d < dims.d[l]) snap[l] = s;
-  }
-#pragma unroll
-  for (int l = 0; l < UR_FUNNEL_MAX_DIMS; ++l) {
-    if (l < L) {                                                       // (uniform)
-      const float t = wave_sum(snap[l]);
-      if (lane == 0) inv[(long)l * rows + row] = 1.0f / fmaxf(sqrtf(t), 1e-12f);
-    }
-  }
-}
+// (the row norms of L prefixes in one read, row_prefix_inv_norm_kernel, are in catalog_select.hip.h: the Matryoshka softmax loss of
+// catalog.hip takes them too)
 
 // user [B, ldu] f32 -> out [B, dim] bf16, nearest even: the bits ur_cast_f32_to_bf16 gives on the contiguous copy user[:, :dim]
 __global__ void cast_prefix_kernel(const float* __restrict__ user, long ldu, bf16_t* __restrict__ out, int B, int dim) {

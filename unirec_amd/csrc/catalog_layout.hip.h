@@ -109,6 +109,40 @@ static catalog_softmax_plan catalog_softmax_layout(int32_t B, int64_t N, int32_t
   return p;
 }
 
+// ur_catalog_mrl_softmax (include/unirec_hip_mrl_loss.h): K planes of the plan above, plane k at width dims[k], sharing the chunk rows:
+// scores [K][B][rows] | inv_u [K][B] | ref [K][B] | m, l, t: [K][B][CSM_SEGS] each | per plane: slabs [nsplit_k][B][d_k] (with d_user only).
+// rows, left to the library: the K planes together near 64 MB.  seg is the one of the chunk rows and (nsplit_k, rps_k) are
+// catalog_softmax_splits(B, d_k, rows): what ur_catalog_softmax takes on the slice at the same chunk_rows.
+constexpr int CSM_MRL_MAX = 8;                 // = UR_MRL_MAX_DIMS (include/unirec_hip_mrl.h)
+static int64_t catalog_mrl_chunk_rows(int64_t chunk_rows, int32_t B, int64_t N, int32_t K) {
+  if (chunk_rows > 0) return catalog_chunk_rows(chunk_rows, B, N);
+  const int64_t r = ((int64_t)64 << 20) / (4 * (int64_t)(B > 0 ? B : 1) * (K > 0 ? K : 1)) / SEL_TILE * SEL_TILE;
+  return catalog_chunk_rows(r < SEL_TILE ? SEL_TILE : r, B, N);
+}
+struct catalog_mrl_softmax_plan {
+  int64_t rows, chunk, inv_u, ref, m_run, l_run, t_run, slabs[CSM_MRL_MAX], need;
+  int nsplit[CSM_MRL_MAX], rps[CSM_MRL_MAX], seg;
+};
+[[maybe_unused]] static catalog_mrl_softmax_plan catalog_mrl_softmax_layout(int32_t B, int64_t N, int32_t K, const int32_t* dims, int64_t chunk_rows,
+                                                                             bool grad) {
+  catalog_mrl_softmax_plan p{};
+  ws_carver c;
+  p.rows = catalog_mrl_chunk_rows(chunk_rows, B, N, K);
+  p.seg = (int)((p.rows + CSM_SEGS - 1) / CSM_SEGS);
+  p.chunk = c.take((int64_t)K * B * p.rows * 4);
+  p.inv_u = c.take((int64_t)K * B * 4);
+  p.ref = c.take((int64_t)K * B * 4);
+  p.m_run = c.take((int64_t)K * B * CSM_SEGS * 4);
+  p.l_run = c.take((int64_t)K * B * CSM_SEGS * 4);
+  p.t_run = c.take((int64_t)K * B * CSM_SEGS * 4);
+  for (int k = 0; k < K; ++k) {
+    catalog_softmax_splits(B, dims[k], p.rows, &p.nsplit[k], &p.rps[k]);
+    p.slabs[k] = c.take(grad ? (int64_t)p.nsplit[k] * B * dims[k] * 4 : 0);      // (no d_user: no pass 2, nothing reads the offsets)
+  }
+  p.need = c.need();
+  return p;
+}
+
 // ur_catalog_coarse_select: u~ [B][D] bf16 | iu~ [B] | ref [B] | chunk [B][rows] f32
 struct coarse_plan {
   int64_t rows, user, inv_u, ref, chunk, need;

@@ -1314,26 +1314,29 @@ def catalog_scorer_id(scorer):
 
 
 # What the five catalogue wrappers below share.  `who` is the wrapper's own name, in every message.
-def _catalog_norm(cat_inv_norm, N, dev, who):
-    """(cat_inv_norm, cat_norm_ready): the caller's inverse norms [N] f32, or a buffer for the library to fill"""
+def _catalog_norm(cat_inv_norm, N, dev, who, planes=None):
+    """(cat_inv_norm, cat_norm_ready): the caller's inverse norms [N] f32 ([planes,N] for a call on prefixes), or a buffer for the
+    library to fill"""
+    shape = (N,) if planes is None else (planes, N)
     if cat_inv_norm is None:
-        return torch.empty((N,), dtype=F32, device=dev), 0
-    if cat_inv_norm.dtype != F32 or cat_inv_norm.shape != (N,):
-        raise ValueError(f"{who}: cat_inv_norm must be f32 of shape [{N}], got {cat_inv_norm.dtype} {tuple(cat_inv_norm.shape)}")
+        return torch.empty(shape, dtype=F32, device=dev), 0
+    if cat_inv_norm.dtype != F32 or cat_inv_norm.shape != shape:
+        raise ValueError(f"{who}: cat_inv_norm must be f32 of shape {list(shape)}, got {cat_inv_norm.dtype} {tuple(cat_inv_norm.shape)}")
     _need(cat_inv_norm, F32, "cat_inv_norm")
     return cat_inv_norm, 1
 
 
-def _catalog_operands(who, user, catalog, cat_inv_norm):
-    """The operand checks: catalog's dtype, user [B,D] f32 and catalog [N,D] sharing D, cat_inv_norm [N] f32 -- the shapes first, as
-    ValueErrors, so that a call which would be read out of bounds is refused whatever else is wrong with it -- then device and contiguity.
+def _catalog_operands(who, user, catalog, cat_inv_norm, planes=None):
+    """The operand checks: catalog's dtype, user [B,D] f32 and catalog [N,D] sharing D, cat_inv_norm [N] f32 ([planes,N] when given) --
+    the shapes first, as ValueErrors, so that a call which would be read out of bounds is refused whatever else is wrong with it -- then
+    device and contiguity.
     Returns (B, N, D, device, cat_inv_norm, cat_norm_ready)."""
     if catalog.dtype not in (F32, BF16):
         raise ValueError(f"{who}: catalog must be f32 or bf16, got {catalog.dtype}")
     if user.dim() != 2 or catalog.dim() != 2 or catalog.shape[1] != user.shape[1]:
         raise ValueError(f"{who}: user [B,D] and catalog [N,D] must share D, got {tuple(user.shape)} and {tuple(catalog.shape)}")
     (B, D), N = user.shape, catalog.shape[0]
-    cat_inv_norm, ready = _catalog_norm(cat_inv_norm, N, user.device, who)
+    cat_inv_norm, ready = _catalog_norm(cat_inv_norm, N, user.device, who, planes)
     _need(user, F32, f"{who}: user")
     _need(catalog, catalog.dtype, f"{who}: catalog")
     return B, N, D, user.device, cat_inv_norm, ready
@@ -1612,6 +1615,44 @@ def catalog_softmax(user, catalog, gt_index, temperature, cat_inv_norm=None, exc
     a.loss, a.row_loss, a.lse, a.d_user = loss.data_ptr(), row_loss.data_ptr(), lse.data_ptr(), _p(d_user) or None
     _catalog_call("ur_catalog_softmax", a, dev, "catalog_softmax")
     return loss, row_loss, lse, d_user, cat_inv_norm
+
+
+def catalog_mrl_softmax(user, catalog, gt_index, dims, weights, temperature, cat_inv_norms=None, exclude=None, chunk_rows=None, scorer=None,
+                        grad_scale=1.0, need_grad=True):
+    """The Matryoshka form of catalog_softmax (ur_catalog_mrl_softmax, include/unirec_hip_mrl_loss.h): catalog_softmax on every prefix
+    dims[k] of user [B,D] f32 and catalog [N,D] f32 or bf16, both read in place -- no [N,d_k] copy -- and the weighted sum
+    loss = sum_k weights[k] * plane_loss[k] with its gradient.  dims: what mrl_dims accepts, the last one D, multiples of 8 for a bf16
+    catalogue; weights: None = all ones, a zero weight keeps the plane's outputs and leaves both sums.  At equal explicit chunk_rows plane
+    k's row_loss, lse, plane_loss and norms are, bit for bit, catalog_softmax's on the contiguous slices user[:, :d_k], catalog[:, :d_k].
+    cat_inv_norms: f32 [K,N], plane k the norms of prefix dims[k] (catalog_prefix_norms(catalog, dims)), in, or computed and returned.
+    gt_index, exclude, temperature, chunk_rows, scorer, grad_scale, need_grad: as for catalog_softmax, shared by all planes.
+    Returns (loss f32 [1], plane_loss f32 [K], row_loss f32 [K,B], lse f32 [K,B], d_user f32 [B,D] or None, cat_inv_norms)."""
+    who = "catalog_mrl_softmax"
+    scorer_id = catalog_scorer_id(scorer)
+    dims = mrl_dims(dims, "dims", user.shape[1] if user.dim() == 2 else None)      # (a user that is not [B,D] is refused below)
+    K = len(dims)
+    weights = mrl_weights(weights, K)
+    if catalog.dtype == BF16 and any(d % 8 for d in dims):
+        raise ValueError(f"dims: every entry must be a multiple of 8 for a bf16 catalogue, got {dims}")
+    a = _lib.CatalogMrlSoftmax()
+    a.B, a.N, a.D, dev, cat_inv_norms, a.cat_norm_ready = _catalog_operands(who, user, catalog, cat_inv_norms, planes=K)
+    a.user, a.catalog, a.cat_inv_norm = user.data_ptr(), catalog.data_ptr(), cat_inv_norms.data_ptr()
+    a.catalog_bf16, a.scorer = int(catalog.dtype == BF16), scorer_id
+    a.temperature, a.grad_scale, a.chunk_rows = float(temperature), float(grad_scale), int(chunk_rows or 0)
+    a.K = K
+    a.dims[:K] = dims
+    a.weights[:K] = weights
+    gt, _ = _catalog_filters(who, a, a.B, dev, gt_index, exclude, want_rank=False)
+    if gt is None:
+        raise ValueError(f"{who}: gt_index is needed")
+    loss = torch.empty((1,), dtype=F32, device=dev)
+    plane_loss = torch.empty((K,), dtype=F32, device=dev)
+    row_loss = torch.empty((K, a.B), dtype=F32, device=dev)
+    lse = torch.empty((K, a.B), dtype=F32, device=dev)
+    d_user = torch.empty((a.B, a.D), dtype=F32, device=dev) if need_grad else None
+    a.loss, a.plane_loss, a.row_loss, a.lse, a.d_user = loss.data_ptr(), plane_loss.data_ptr(), row_loss.data_ptr(), lse.data_ptr(), _p(d_user) or None
+    _catalog_call("ur_catalog_mrl_softmax", a, dev, who)
+    return loss, plane_loss, row_loss, lse, d_user, cat_inv_norms
 
 
 def rank_of_index(scores, gt_index):

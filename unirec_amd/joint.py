@@ -440,14 +440,38 @@ class _CatalogSoftmaxFn(torch.autograd.Function):
         return ctx.du * g, None, None, None
 
 
+class _CatalogMrlSoftmaxFn(torch.autograd.Function):
+    """The weighted sum of the catalogue softmax losses on the nested prefixes ``owner.matryoshka_dims``: one ``hip.catalog_mrl_softmax``
+    over the resident catalogue, read in place; the norm planes are the evaluator's, the ones ``retrieve_funnel`` searches with."""
+
+    @staticmethod
+    def forward(ctx, user, owner, gt, ex):
+        loss, plane_loss, row_loss, lse, du, _ = hip.catalog_mrl_softmax(user, owner.evaluator.catalog, gt, owner.matryoshka_dims,
+                                                                         owner.matryoshka_weights, owner.temperature, owner._norm_planes(),
+                                                                         exclude=ex, chunk_rows=owner.chunk_rows, scorer=owner.scorer,
+                                                                         grad_scale=1.0, need_grad=True)
+        owner.last_lse, owner.last_row_loss, owner.last_plane_loss = lse, row_loss, plane_loss
+        ctx.du = du
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.du * g, None, None, None
+
+
 class CatalogSoftmaxLoss(nn.Module):
     """Cross-entropy of each user's ground-truth item against EVERY row of a resident catalogue (cosine scores / temperature), streamed
     in chunks by ``hip.catalog_softmax``: no sampled negatives, no [B,P,D] tensor, nothing of size B x N.  The catalogue is frozen; the
-    gradient reaches the user embeddings only."""
+    gradient reaches the user embeddings only.
+    ``matryoshka_dims`` (ascending multiples of 4 -- 8 for a bf16 catalogue -- the last one the embedding width) makes it the Matryoshka
+    form, ``hip.catalog_mrl_softmax``: sum_k matryoshka_weights[k] * that loss on the first d_k components of the users and of every
+    catalogue row, each prefix renormalised, the catalogue read in place; weights all ones unless given, a zero weight keeps the plane's
+    loss in ``last_plane_loss`` and out of the sum and the gradient.  None is the plain loss: the same launches and bits as ever."""
 
-    def __init__(self, catalog, temperature: float = 0.07, scorer=None, chunk_rows=None):
+    def __init__(self, catalog, temperature: float = 0.07, scorer=None, chunk_rows=None, matryoshka_dims=None, matryoshka_weights=None):
         """catalog: a CatalogEvaluator (its catalogue and cached norms are used where they lie), or an [N,D] f32 / bf16 device tensor.
-        The catalogue's inverse norms are computed by the first call and kept.  scorer, chunk_rows: as for CatalogEvaluator.retrieve."""
+        The catalogue's inverse norms are computed by the first call and kept -- with matryoshka_dims one plane per width, in the
+        evaluator, where ``retrieve_funnel`` over the same widths finds them.  scorer, chunk_rows: as for CatalogEvaluator.retrieve."""
         super().__init__()
         from .evaluation import CatalogEvaluator
         hip.catalog_scorer_id(scorer)
@@ -459,21 +483,42 @@ class CatalogSoftmaxLoss(nn.Module):
         if not float(temperature) > 0:
             raise ValueError(f"CatalogSoftmaxLoss: temperature must be positive, got {temperature}")
         self.evaluator, self.temperature, self.scorer, self.chunk_rows = catalog, float(temperature), scorer, chunk_rows
-        self.last_lse = self.last_row_loss = None
+        if matryoshka_dims is None:
+            if matryoshka_weights is not None:
+                raise ValueError("matryoshka_weights needs matryoshka_dims")
+            self.matryoshka_dims = self.matryoshka_weights = None
+        else:
+            D = catalog.catalog.shape[1]
+            self.matryoshka_dims = hip.mrl_dims(matryoshka_dims, "matryoshka_dims", D)
+            self.matryoshka_weights = hip.mrl_weights(matryoshka_weights, len(self.matryoshka_dims), "matryoshka_weights")
+            if catalog.catalog.dtype == BF16 and any(d % 8 for d in self.matryoshka_dims):
+                raise ValueError(f"matryoshka_dims: every entry must be a multiple of 8 for a bf16 catalogue, got {self.matryoshka_dims}")
+        self.last_lse = self.last_row_loss = self.last_plane_loss = None
+        self._planes = None
 
     @property
     def catalog(self):
         return self.evaluator.catalog
 
+    def _norm_planes(self):
+        """[K,N]: the evaluator's norm plane of every width (computed there once, shared with retrieve_funnel), stacked once"""
+        if self._planes is None:
+            by_dim = self.evaluator._prefix_norms(self.matryoshka_dims)
+            self._planes = torch.stack([by_dim[d] for d in self.matryoshka_dims]).contiguous()
+        return self._planes
+
     def forward(self, user_embeddings, positive_item_index, exclude=None):
         """exclude: the items each user has seen (ragged lists or [B,E] padded with -1); they leave the softmax's sum, except the user's
-        own positive.  Keeps ``last_lse`` and ``last_row_loss`` [B] of the call."""
+        own positive.  Keeps ``last_lse`` and ``last_row_loss`` [B] of the call; with matryoshka_dims they are [K,B], and
+        ``last_plane_loss`` [K] holds the per-prefix losses."""
         from .evaluation import pack_exclude
         dev = self.catalog.device
         u = user_embeddings.contiguous().to(dev, F32)
         gt = torch.as_tensor(positive_item_index).to(dev, torch.int64)
         ex = pack_exclude(exclude, u.shape[0])
         ex = None if ex is None else ex.to(dev)
+        if self.matryoshka_dims is not None:
+            return _CatalogMrlSoftmaxFn.apply(u, self, gt, ex)
         return _CatalogSoftmaxFn.apply(u, self, gt, ex)
 
 
@@ -489,20 +534,19 @@ class MultiModalTrainer:
         """negatives: a ``negatives.CatalogCandidates``; needed by batches that carry ``positive_item_index`` instead of embeddings.
         loss: "infonce" (the reference's loss over one positive and the batch's negatives) or "catalog_softmax" (``CatalogSoftmaxLoss``
         over the whole catalogue of ``negatives``, which must then sample and mine nothing).
-        matryoshka_dims, matryoshka_weights: the Matryoshka form of InfoNCE (``InfoNCELoss``): the loss on every nested prefix of the
-        embeddings, for embedding batches and index batches alike.  Hard negatives are still mined with full-width scores: the mined
-        set is the one the plain loss would train on, and every prefix is trained against it."""
+        matryoshka_dims, matryoshka_weights: the Matryoshka form of the loss (``InfoNCELoss``, ``CatalogSoftmaxLoss``): the loss on every
+        nested prefix of the embeddings, for embedding batches and index batches alike.  Hard negatives are still mined with full-width
+        scores: the mined set is the one the plain loss would train on, and every prefix is trained against it."""
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
-        if loss == "catalog_softmax" and (matryoshka_dims is not None or matryoshka_weights is not None):
-            raise ValueError('loss="catalog_softmax" has no Matryoshka form: matryoshka_dims / matryoshka_weights need loss="infonce"')
         self.loss = loss
         self.infonce_loss = InfoNCELoss(temperature, matryoshka_dims, matryoshka_weights)
         self.negatives = negatives
         self.catalog_softmax_loss = None
         if loss == "catalog_softmax":
             if negatives is None:
-                raise ValueError('loss="catalog_softmax" needs the `negatives` argument (a negatives.CatalogCandidates over the resident '
+                form = "" if matryoshka_dims is None else " with matryoshka_dims"
+                raise ValueError(f'loss="catalog_softmax"{form} needs the `negatives` argument (a negatives.CatalogCandidates over the resident '
                                  "catalogue)")
             if negatives.num_random != 0 or negatives.num_hard != 0:
                 raise ValueError(f'loss="catalog_softmax" sums over the whole catalogue: negatives.num_random and negatives.num_hard must be 0 '
@@ -511,7 +555,8 @@ class MultiModalTrainer:
                 raise ValueError('loss="catalog_softmax" has no coarse form (its gradient would need its own definition): '
                                  "negatives.coarse must be False")
             self.catalog_softmax_loss = CatalogSoftmaxLoss(negatives.evaluator, temperature, scorer=negatives.scorer,
-                                                           chunk_rows=negatives.chunk_rows)
+                                                           chunk_rows=negatives.chunk_rows, matryoshka_dims=matryoshka_dims,
+                                                           matryoshka_weights=matryoshka_weights)
 
     def compute_loss(self, model, inputs, return_outputs=False, step=0, **kwargs):
         """A batch with ``positive_item_index`` [B] takes its candidates from the resident catalogue of ``negatives``: optional
@@ -630,8 +675,8 @@ class JointTrainer:
     ``negatives`` (a ``negatives.CatalogCandidates``) lets a batch name its candidates by index into a resident catalogue
     (``MultiModalTrainer.compute_loss``); the random negatives of such a batch are keyed on ``state.global_step``.
     ``loss="catalog_softmax"`` replaces InfoNCE by the softmax over that whole catalogue (``CatalogSoftmaxLoss``); gradient scale,
-    clipping and logging are the same.  ``matryoshka_dims`` / ``matryoshka_weights`` make the InfoNCE loss its Matryoshka form
-    (``InfoNCELoss``); the log records then carry ``plane_loss``, the per-prefix losses averaged over the logging window."""
+    clipping and logging are the same.  ``matryoshka_dims`` / ``matryoshka_weights`` make either loss its Matryoshka form
+    (``InfoNCELoss``, ``CatalogSoftmaxLoss``); the log records then carry ``plane_loss``, the per-prefix losses averaged over the logging window."""
 
     def __init__(self, model, args, num_training_steps=None, temperature: float = 0.07, negatives=None, loss: str = "infonce",
                  matryoshka_dims=None, matryoshka_weights=None):
@@ -693,7 +738,7 @@ class JointTrainer:
         self.state.global_step += 1
         loss = loss.detach()
         self._tr_loss = loss.clone() if self._tr_loss is None else self._tr_loss + loss
-        planes = self.loss_fn.infonce_loss.last_plane_loss if self.loss_fn.loss == "infonce" else None
+        planes = (self.loss_fn.infonce_loss if self.loss_fn.loss == "infonce" else self.loss_fn.catalog_softmax_loss).last_plane_loss
         if planes is not None:
             self._tr_planes = planes.clone() if self._tr_planes is None else self._tr_planes + planes
         self._since_log += 1
