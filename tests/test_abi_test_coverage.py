@@ -1,13 +1,20 @@
-"""CPU: every entry point declared in include/unirec_hip.h is either listed in a COVERS table -- naming the primitive-level test(s)
+"""CPU: every entry point declared in include/unirec_hip.h or in one of the family headers include/unirec_hip_*.h is either listed in a COVERS table -- naming the primitive-level test(s)
 that hold it against a reference -- or exempt below with a reason.  A new entry point without such a test fails here."""
 import ast
 import functools
+import glob
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COVERS_MODULES = ("tests/test_gpu_primitives.py", "tests/test_gpu_head_primitives.py", "tests/test_gpu_attention_f64.py", "tests/test_gpu_norm_f64.py",
-                  "tests/test_gpu_lora_f64.py", "tests/test_gpu_gemm_f64.py", "tests/test_gpu_elementwise_f64.py", "tests/test_gpu_dw_f64.py")
+                  "tests/test_gpu_lora_f64.py", "tests/test_gpu_gemm_f64.py", "tests/test_gpu_elementwise_f64.py", "tests/test_gpu_dw_f64.py",
+                  # the family headers: catalogue retrieval and losses, Matryoshka, pooling, LoRA merge
+                  "tests/test_gpu_catalog_deep.py", "tests/test_gpu_catalog_coarse.py", "tests/test_gpu_catalog_coarse_deep.py",
+                  "tests/test_gpu_catalog_funnel.py", "tests/test_gpu_catalog_softmax.py", "tests/test_gpu_catalog_mrl_softmax.py",
+                  "tests/test_gpu_mrl_f64.py", "tests/test_gpu_pool_f64.py", "tests/test_gpu_lora_merge.py",
+                  # where the catalogue calls read and write: the weakest alignments, guards, poisoned workspaces; rows past 4 GiB
+                  "tests/test_gpu_catalog_memory.py", "tests/test_gpu_catalog_4gib.py")
 
 EXEMPT = {
     "ur_version": "ABI handshake; asserted at every library load (unirec_amd/_lib.py) and in tests/test_cabi.py",
@@ -40,13 +47,23 @@ EXEMPT = {
 }
 
 
+def _headers():
+    """include/unirec_hip.h first, then the family headers in name order"""
+    first = os.path.join(ROOT, "include", "unirec_hip.h")
+    rest = sorted(p for p in glob.glob(os.path.join(ROOT, "include", "unirec_hip*.h")) if p != first)
+    return [first] + rest
+
+
 def _declared_entry_points():
-    with open(os.path.join(ROOT, "include", "unirec_hip.h")) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    """every ur_* function of every header, once: a family header may declare again what it builds on (ur_last_error, ur_catalog_scores,
+    ur_catalog_rerank), and a name counts where it first appears"""
     names = []
-    for n in re.findall(r"\b(ur_[a-z0-9_]+)\s*\(", text):
-        if n not in names:
-            names.append(n)
+    for path in _headers():
+        with open(path) as f:
+            text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+        for n in re.findall(r"\b(ur_[a-z0-9_]+)\s*\(", text):
+            if n not in names:
+                names.append(n)
     return names
 
 
@@ -75,7 +92,7 @@ def _problems(declared, tables, tests_of):
         for entry, names in covers.items():
             listed.setdefault(entry, []).append(path)
             if entry not in declared:
-                out.append(f"{path}: COVERS lists {entry}, which include/unirec_hip.h does not declare")
+                out.append(f"{path}: COVERS lists {entry}, which no header under include/ declares")
             if not names:
                 out.append(f"{path}: COVERS[{entry!r}] names no test")
             for name in names:
@@ -90,7 +107,7 @@ def _problems(declared, tables, tests_of):
             out.append(f"{entry} has no primitive-level test: add one and list it in a COVERS table, or exempt it with a reason")
     for entry in EXEMPT:
         if entry not in declared:
-            out.append(f"EXEMPT lists {entry}, which include/unirec_hip.h does not declare")
+            out.append(f"EXEMPT lists {entry}, which no header under include/ declares")
     return out
 
 
@@ -105,7 +122,9 @@ def _tables():
 
 def test_every_entry_point_has_a_primitive_level_test_or_a_reason():
     declared = _declared_entry_points()
-    assert len(declared) >= 81 and "ur_gemm" in declared and "ur_comm_destroy" in declared
+    assert len(_headers()) >= 10 and len(declared) == len(set(declared))
+    assert len(declared) >= 100 and "ur_gemm" in declared and "ur_comm_destroy" in declared
+    assert "ur_catalog_deep_select" in declared and "ur_lora_merge" in declared and "ur_catalog_mrl_softmax" in declared
     assert all(reason.strip() for reason in EXEMPT.values())
     problems = _problems(declared, _tables(), lambda p: _covers_and_tests(p)[1])
     assert not problems, "\n".join(problems)
