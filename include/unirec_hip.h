@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 29      /* 29: the Matryoshka catalogue softmax of unirec_hip_mrl_loss.h (ur_catalog_mrl_softmax; nothing in this header changed); 28: the funnel retrieval family of unirec_hip_funnel.h (ur_catalog_prefix_norms, ur_catalog_funnel_select, ur_catalog_funnel_rerank; nothing in this header changed); 27: the long two-stage retrieval family of unirec_hip_coarse_deep.h (ur_catalog_coarse_deep_select, ur_catalog_deep_rerank; nothing in this header changed); 26: the long-list retrieval family of unirec_hip_deep.h (ur_catalog_deep_select; nothing in this header changed); 25: the two-stage retrieval family of unirec_hip_coarse.h (ur_catalog_coarse_select, ur_catalog_rerank; nothing in this header changed); 24: the Matryoshka family of unirec_hip_mrl.h (ur_mrl_scores, ur_mrl_infonce; nothing in this header changed); 23: ur_lora_plan (the LoRA selection query; no existing declaration changed); 18: ur_gemm_plan; 19: ur_rmsnorm_lora_fwd takes 1 to 3 adapters; 20: the loss family of
+#define UR_ABI_VERSION 30      /* 30: the FP8 e4m3 catalogue family of unirec_fp8.h (ur_catalog_fp8_quantize, ur_catalog_fp8_select, ur_catalog_fp8_rerank; nothing in this header changed); 29: the Matryoshka catalogue softmax of unirec_hip_mrl_loss.h (ur_catalog_mrl_softmax; nothing in this header changed); 28: the funnel retrieval family of unirec_hip_funnel.h (ur_catalog_prefix_norms, ur_catalog_funnel_select, ur_catalog_funnel_rerank; nothing in this header changed); 27: the long two-stage retrieval family of unirec_hip_coarse_deep.h (ur_catalog_coarse_deep_select, ur_catalog_deep_rerank; nothing in this header changed); 26: the long-list retrieval family of unirec_hip_deep.h (ur_catalog_deep_select; nothing in this header changed); 25: the two-stage retrieval family of unirec_hip_coarse.h (ur_catalog_coarse_select, ur_catalog_rerank; nothing in this header changed); 24: the Matryoshka family of unirec_hip_mrl.h (ur_mrl_scores, ur_mrl_infonce; nothing in this header changed); 23: ur_lora_plan (the LoRA selection query; no existing declaration changed); 18: ur_gemm_plan; 19: ur_rmsnorm_lora_fwd takes 1 to 3 adapters; 20: the loss family of
                                   unirec_hip_loss.h (the full-catalogue softmax loss; nothing in this header changed); 21: the adapter
                                   family of unirec_hip_adapter.h (ur_lora_merge; nothing in this header changed); 22: the pooling family of
                                   unirec_hip_pool.h (ur_pool_norm_*; nothing in this header changed) */

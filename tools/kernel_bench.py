@@ -8,6 +8,7 @@ shapes; used under rocprofv3 (--kernel-trace / --pmc) when tuning.  Usage:
     python tools/kernel_bench.py catalog --shortlist 128 --catalog-dtype bf16 [--N 1000000] [--D 1024] [--rounds 3]
     python tools/kernel_bench.py catalog --two-stage-shortlist 1024 --K 1000 --catalog-dtype bf16 [--users 512 64] [--rounds 5]
     python tools/kernel_bench.py catalog --funnel-dims 256 1024 --funnel-shortlists 1024 --K 1000 [--users 512 64] [--rounds 5]
+    python tools/kernel_bench.py catalog --fp8 --K 1000 --two-stage-shortlist 1024 [--users 512 64] [--rounds 5]
     python tools/kernel_bench.py negatives --B 64 --P 1000 --N 1000000 --K 128 [--catalog-dtype f32|bf16] [--rounds 3]
     python tools/kernel_bench.py catalog_softmax --users 64 512 --dtypes f32 bf16 --N 1000000 [--D 1024] [--rounds 5]
     python tools/kernel_bench.py catalog_mrl_softmax --users 64 512 --dtypes f32 bf16 --dims 64,128,256,512,1024 [--N 1000000] [--rounds 5]
@@ -271,6 +272,8 @@ def catalog(args):
     from unirec_amd.evaluation import CatalogEvaluator
     if args.funnel_dims:
         return catalog_funnel(args)
+    if args.fp8:
+        return catalog_fp8(args)
     if args.two_stage_shortlist:
         return catalog_two_stage(args)
     if args.shortlist:
@@ -517,6 +520,93 @@ def catalog_two_stage(args):
             spread = max(max(times[a]) - min(times[a]), max(times[two_name]) - min(times[two_name]))
             print(f"  {a.strip()} / two-stage = {med[a] / med[two_name]:.2f}x  (difference {gap:.2f} ms against a spread of {spread:.2f} ms: "
                   f"{'faster by more than the spread' if gap > spread else 'NOT faster by more than the spread'})")
+
+
+def catalog_fp8(args):
+    """Fp8CatalogEvaluator.retrieve_two_stage(k=--K, shortlist=--two-stage-shortlist) against CatalogEvaluator.retrieve_two_stage on the
+    bf16 catalogue it was quantised from, per user count (--users, default 512 and 64), alternating --rounds times in one process after
+    one call of each.  Wall time of the whole call, the stages timed on their own (the per-kernel split: hip.catalog_fp8_select /
+    hip.catalog_coarse_deep_select, hip.catalog_fp8_rerank / hip.catalog_deep_rerank), the resident bytes of either catalogue, the
+    workspaces the size queries report, the peak allocation of a call, and the recall@K of both lists against the exact bf16 retrieve(k)
+    on two synthetic catalogues: standard normal rows, and rows whose later components decay (_decaying_catalogue)."""
+    import ctypes
+    from unirec_amd import _lib
+    from unirec_amd.evaluation import CatalogEvaluator
+    N, D, K = args.N, args.D, args.K
+    S = args.two_stage_shortlist or min(1024, max(128, 2 * K))
+    g = torch.Generator(device="cuda").manual_seed(0)
+    ev = CatalogEvaluator(torch.randn(N, D, generator=g, device="cuda").to(torch.bfloat16), dtype=torch.bfloat16)
+    f8 = ev.quantized()
+    held = sum(t.numel() * t.element_size() for t in (f8.codes, f8.scale, f8.inv))
+    print(f"catalog --fp8 --K {K} --two-stage-shortlist {S}: N={N} D={D}; resident bytes: bf16 catalogue {N * D * 2 / 2**20:.0f} MiB + norms "
+          f"{N * 4 / 2**20:.1f} MiB, fp8 codes {f8.codes.numel() / 2**20:.0f} MiB + scale and inv {2 * N * 4 / 2**20:.1f} MiB "
+          f"(held: {held / 2**20:.1f} MiB); {args.rounds} alternating rounds")
+    for B in (args.users or [512, 64]):
+        user = torch.randn(B, D, generator=g, device="cuda")
+        gt = torch.randint(0, N, (B,), generator=g, device="cuda")
+        ev.retrieve(user[:1], k=1)                            # the bf16 catalogue's norms, outside every figure below
+        bf_name, f8_name = f"bf16 retrieve_two_stage(k={K}, shortlist={S})", f"fp8  retrieve_two_stage(k={K}, shortlist={S})"
+        short16 = hip.catalog_coarse_deep_select(user, ev.catalog, S, ev._inv, gt_index=gt)[0]
+        short8 = hip.catalog_fp8_select(user, f8.codes, S, f8.inv, gt_index=gt)[0]
+        variants = [(bf_name, lambda: ev.retrieve_two_stage(user, k=K, shortlist=S, gt_index=gt)),
+                    (f8_name, lambda: f8.retrieve_two_stage(user, k=K, shortlist=S, gt_index=gt)),
+                    ("  bf16 coarse-deep select alone", lambda: hip.catalog_coarse_deep_select(user, ev.catalog, S, ev._inv, gt_index=gt)),
+                    ("  fp8 select alone", lambda: hip.catalog_fp8_select(user, f8.codes, S, f8.inv, gt_index=gt)),
+                    ("  bf16 deep re-rank alone", lambda: hip.catalog_deep_rerank(user, ev.catalog, short16, K, ev._inv)),
+                    ("  fp8 re-rank alone", lambda: hip.catalog_fp8_rerank(user, f8.codes, short8, f8.inv, K))]
+        peaks = {}
+        for name, fn in variants[:2]:
+            fn()
+            hip._ws_cache.clear()
+            torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            fn()
+            torch.cuda.synchronize()
+            peaks[name] = torch.cuda.max_memory_allocated() - base
+        for name, fn in variants:                             # scratch of every variant warm again
+            fn()
+        q8, q16 = _lib.CatalogFp8Select(), _lib.CatalogCoarseDeep()
+        q8.B, q8.N, q8.D, q8.K = B, N, D, S
+        q16.B, q16.N, q16.D, q16.K, q16.catalog_bf16 = B, N, D, S, 1
+        _lib.check(_lib.load().ur_catalog_fp8_select(ctypes.byref(q8), None), "ur_catalog_fp8_select")
+        _lib.check(_lib.load().ur_catalog_coarse_deep_select(ctypes.byref(q16), None), "ur_catalog_coarse_deep_select")
+        times = {name: [] for name, _ in variants}
+        for _ in range(args.rounds):
+            for name, fn in variants:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                times[name].append((time.perf_counter() - t0) * 1e3)
+        print(f"B={B} K={K} shortlist={S}: select workspace (size queries) fp8 {q8.workspace_bytes / 2**20:.2f} MiB, bf16 "
+              f"{q16.workspace_bytes / 2**20:.2f} MiB; peak allocation of a call fp8 {peaks[f8_name] / 2**20:.2f} MiB, bf16 {peaks[bf_name] / 2**20:.2f} MiB")
+        med = {}
+        for name, _ in variants:
+            t = sorted(times[name])
+            med[name] = t[len(t) // 2]
+            print(f"  {name:52s}: median {med[name]:9.2f} ms  min {t[0]:9.2f}  max {t[-1]:9.2f}  (spread {t[-1] - t[0]:.2f} over {len(t)} alternating rounds)")
+        spread = max(max(times[n]) - min(times[n]) for n in (bf_name, f8_name))
+        print(f"  bf16 / fp8 = {med[bf_name] / med[f8_name]:.3f}x (difference {med[bf_name] - med[f8_name]:.2f} ms against a spread of {spread:.2f} ms)")
+    # recall of both two-stage lists against the exact bf16 retrieve(k), on the random catalogue and on one whose later components decay
+    del short16, short8
+    Bq = min(64, (args.users or [64])[-1])
+    for label in ("random", "decaying"):
+        if label == "decaying":
+            del ev, f8
+            cat, scale = _decaying_catalogue(N, D, (D // 4, D // 2, D), g)
+            ev = CatalogEvaluator(cat, dtype=torch.bfloat16)
+            del cat
+            f8 = ev.quantized()
+        u = torch.randn(Bq, D, generator=g, device="cuda")
+        if label == "decaying":
+            u = u * scale
+        exact = ev.retrieve(u, k=K)["topk_index"]
+        for name, e in (("bf16", ev), ("fp8", f8)):
+            got = e.retrieve_two_stage(u, k=K, shortlist=S)["topk_index"]
+            hit = (got[:, :, None] == exact[:, None, :]).any(2).float().mean().item()
+            same = (got == exact).all(1).float().mean().item()
+            print(f"  recall@{K} of the {name} two-stage list (shortlist {S}) against the exact bf16 retrieve(k), {label} catalogue, {Bq} users: "
+                  f"{hit:.6f}; users whose whole list is identical {same:.4f}")
 
 
 def _decaying_catalogue(N, D, dims, g):
@@ -973,6 +1063,9 @@ if __name__ == "__main__":
     ap.add_argument("--shortlist", type=int, default=0, help="catalog: time retrieve(shortlist=...) against the exact retrieve() at (512, 100) and (64, 10)")
     ap.add_argument("--two-stage-shortlist", type=int, default=0,
                     help="catalog: time retrieve_two_stage(k=--K, shortlist=...) against the exact retrieve(k=--K) per --users (default 512 and 64)")
+    ap.add_argument("--fp8", action="store_true",
+                    help="catalog: time Fp8CatalogEvaluator.retrieve_two_stage(k=--K, shortlist=--two-stage-shortlist) against the bf16 "
+                         "retrieve_two_stage per --users (default 512 and 64), with resident bytes, peak allocation and recall")
     ap.add_argument("--segments", type=int, nargs="+", help="catalog with --K above 128: also time the long-list call with each of these workgroup counts per user forced")
     ap.add_argument("--funnel-dims", type=int, nargs="+",
                     help="catalog: time retrieve_funnel(k=--K, dims=...) against retrieve_two_stage at the full width and against the hand "

@@ -1,6 +1,6 @@
 """ctypes binding of libunirec_hip.so (the C ABI declared in include/unirec_hip.h, include/unirec_hip_loss.h,
 include/unirec_hip_adapter.h, include/unirec_hip_pool.h, include/unirec_hip_mrl.h, include/unirec_hip_coarse.h,
-include/unirec_hip_deep.h, include/unirec_hip_coarse_deep.h and include/unirec_hip_funnel.h).
+include/unirec_hip_deep.h, include/unirec_hip_coarse_deep.h, include/unirec_hip_funnel.h and include/unirec_fp8.h).
 
 Fails loudly: there is no CPU / eager fallback for the product path.
 """
@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNIREC_HIP_LIB selects another build of the SAME library (kernel A/B experiments); there is still no fallback.
 LIB_PATH = os.environ.get("UNIREC_HIP_LIB") or os.path.join(_HERE, "lib", "libunirec_hip.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 c_void_p, c_int, c_i64, c_u64, c_float = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
 
@@ -247,6 +247,35 @@ class CatalogFunnelRerank(ctypes.Structure):
                 ("workspace", c_void_p), ("workspace_bytes", c_i64)]
 
 
+FP8_USER_GROUP = 64                 # UR_FP8_USER_GROUP
+
+
+class CatalogFp8Quantize(ctypes.Structure):
+    """Mirror of ur_catalog_fp8_quantize_t (include/unirec_fp8.h)."""
+    _fields_ = [("src", c_void_p), ("src_bf16", c_int), ("N", c_i64), ("D", c_int), ("ld", c_i64),
+                ("codes", c_void_p), ("scale", c_void_p), ("inv", c_void_p)]
+
+
+class CatalogFp8Select(ctypes.Structure):
+    """Mirror of ur_catalog_fp8_select_t (include/unirec_fp8.h): CatalogCoarseDeep over codes, cat_inv_norm always an input."""
+    _fields_ = [("user", c_void_p), ("codes", c_void_p), ("cat_inv_norm", c_void_p),
+                ("B", c_int), ("N", c_i64), ("D", c_int), ("K", c_int),
+                ("topk_index", c_void_p), ("topk_score", c_void_p),
+                ("gt_index", c_void_p), ("rank", c_void_p),
+                ("exclude", c_void_p), ("E", c_int),
+                ("chunk_rows", c_i64), ("segments", c_int),
+                ("workspace", c_void_p), ("workspace_bytes", c_i64)]
+
+
+class CatalogFp8Rerank(ctypes.Structure):
+    """Mirror of ur_catalog_fp8_rerank_t (include/unirec_fp8.h): CatalogDeepRerank over codes, cat_inv_norm always an input."""
+    _fields_ = [("user", c_void_p), ("codes", c_void_p), ("cat_inv_norm", c_void_p),
+                ("B", c_int), ("N", c_i64), ("D", c_int),
+                ("index", c_void_p), ("K_in", c_int), ("k", c_int),
+                ("topk_index", c_void_p), ("topk_score", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_i64)]
+
+
 class F32Range(ctypes.Structure):
     """Mirror of ur_f32_range."""
     _fields_ = [("ptr", c_void_p), ("n", c_i64)]
@@ -421,6 +450,14 @@ MRL_LOSS_SIGNATURES = {
     "ur_catalog_mrl_softmax": (c_int, [ctypes.POINTER(CatalogMrlSoftmax), c_void_p]),
 }
 
+# the FP8 catalogue family: every symbol include/unirec_fp8.h declares (tests/test_catalog_fp8_host.py holds this table and the three
+# struct mirrors above to that header and to the built library)
+FP8_SIGNATURES = {
+    "ur_catalog_fp8_quantize": (c_int, [ctypes.POINTER(CatalogFp8Quantize), c_void_p]),
+    "ur_catalog_fp8_select": (c_int, [ctypes.POINTER(CatalogFp8Select), c_void_p]),
+    "ur_catalog_fp8_rerank": (c_int, [ctypes.POINTER(CatalogFp8Rerank), c_void_p]),
+}
+
 _lib = None
 
 
@@ -444,7 +481,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(ADAPTER_SIGNATURES.items()) + \
             list(POOL_SIGNATURES.items()) + list(MRL_SIGNATURES.items()) + list(COARSE_SIGNATURES.items()) + list(DEEP_SIGNATURES.items()) + \
-            list(COARSE_DEEP_SIGNATURES.items()) + list(FUNNEL_SIGNATURES.items()) + list(MRL_LOSS_SIGNATURES.items()):
+            list(COARSE_DEEP_SIGNATURES.items()) + list(FUNNEL_SIGNATURES.items()) + list(MRL_LOSS_SIGNATURES.items()) + \
+            list(FP8_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -230,9 +230,8 @@ __global__ __launch_bounds__(256) void catalog_rerank_kernel(const float* __rest
 // Then one workgroup per user loads its K_in pairs into LDS (2 x 4 x 1024 = 8 KB), pads them to the next power of two with empty slots
 // and sorts them with the bitonic helper of catalog_deep.hip.h (one compare-exchange pair per thread and step); the first k leave.
 // Neither launch's result depends on its grid: a score is a function of its pair, a list of its user's pairs.
-constexpr int DR_SLOTS = UR_CATALOG_DEEP_TOPK_MAX;
-constexpr int DR_GRID_Y_MAX = 65535;
-static_assert((DR_SLOTS & (DR_SLOTS - 1)) == 0 && DR_SLOTS >= UR_CATALOG_TOPK_MAX, "the sort takes a power of two; the short lists are a subset");
+// (DR_SLOTS, DR_GRID_Y_MAX and the sorting kernel, catalog_deep_rerank_sort_kernel, are in catalog_deep.hip.h: ur_catalog_fp8_rerank of
+// catalog_fp8.hip runs the same sorting launch)
 template <typename CT>
 __global__ __launch_bounds__(256) void catalog_deep_rerank_score_kernel(const float* __restrict__ user, const float* __restrict__ inv_u,
                                                                         const CT* __restrict__ cat, const float* __restrict__ inv_c,
@@ -258,31 +257,6 @@ __global__ __launch_bounds__(256) void catalog_deep_rerank_score_kernel(const fl
       s = wave_sum(acc) * iu * ic;
     }
     if (lane == 0) score[(long)b * K_in + slot] = s;
-  }
-}
-
-__global__ __launch_bounds__(256) void catalog_deep_rerank_sort_kernel(const float* __restrict__ score, const int* __restrict__ index, int K_in,
-                                                                       int k, int* __restrict__ topk_index, float* __restrict__ topk_score,
-                                                                       long N) {
-  __shared__ float ks[DR_SLOTS];
-  __shared__ int ki[DR_SLOTS];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  int P = 2;
-  while (P < K_in) P <<= 1;                                              // <= DR_SLOTS: K_in <= UR_CATALOG_DEEP_TOPK_MAX is checked
-  for (int i = tid; i < P; i += 256) {
-    float s = -__builtin_inff();
-    int id = SEL_EMPTY;
-    if (i < K_in) {
-      const int g = index[(long)b * K_in + i];
-      if (g >= 0 && (long)g < N) { s = score[(long)b * K_in + i]; id = g; }
-    }
-    ks[i] = s; ki[i] = id;
-  }
-  __syncthreads();
-  deep_sort(ks, ki, P, tid);
-  for (int i = tid; i < k; i += 256) {
-    topk_score[(long)b * k + i] = ks[i];
-    topk_index[(long)b * k + i] = ki[i] == SEL_EMPTY ? -1 : ki[i];
   }
 }
 

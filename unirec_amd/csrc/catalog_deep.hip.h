@@ -175,4 +175,36 @@ int deep_segments(int32_t segments, int32_t B, int64_t rows) {
   return g < 1 ? 1 : (int)g;
 }
 
+// ---- the sorting launch of the long re-ranks (ur_catalog_deep_rerank, ur_catalog_funnel_rerank in catalog_coarse.hip; ur_catalog_fp8_rerank
+// in catalog_fp8.hip) ------------------------------------------------------------------------------------------------------------------
+// One workgroup per user loads its K_in (score, index) pairs into LDS, pads them to the next power of two with empty slots, sorts them
+// with deep_sort and writes the first k.  The scoring launches that feed it are described where they live.
+constexpr int DR_SLOTS = UR_CATALOG_DEEP_TOPK_MAX;
+constexpr int DR_GRID_Y_MAX = 65535;
+static_assert((DR_SLOTS & (DR_SLOTS - 1)) == 0 && DR_SLOTS >= UR_CATALOG_TOPK_MAX, "the sort takes a power of two; the short lists are a subset");
+__global__ __launch_bounds__(256) void catalog_deep_rerank_sort_kernel(const float* __restrict__ score, const int* __restrict__ index, int K_in,
+                                                                       int k, int* __restrict__ topk_index, float* __restrict__ topk_score,
+                                                                       long N) {
+  __shared__ float ks[DR_SLOTS];
+  __shared__ int ki[DR_SLOTS];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int P = 2;
+  while (P < K_in) P <<= 1;                                              // <= DR_SLOTS: K_in <= UR_CATALOG_DEEP_TOPK_MAX is checked
+  for (int i = tid; i < P; i += 256) {
+    float s = -__builtin_inff();
+    int id = SEL_EMPTY;
+    if (i < K_in) {
+      const int g = index[(long)b * K_in + i];
+      if (g >= 0 && (long)g < N) { s = score[(long)b * K_in + i]; id = g; }
+    }
+    ks[i] = s; ki[i] = id;
+  }
+  __syncthreads();
+  deep_sort(ks, ki, P, tid);
+  for (int i = tid; i < k; i += 256) {
+    topk_score[(long)b * k + i] = ks[i];
+    topk_index[(long)b * k + i] = ki[i] == SEL_EMPTY ? -1 : ki[i];
+  }
+}
+
 }  // namespace

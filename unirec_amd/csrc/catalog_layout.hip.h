@@ -201,4 +201,29 @@ struct deep_rerank_plan {
 }
 [[maybe_unused]] static deep_rerank_plan funnel_rerank_layout(int32_t B, int32_t K_in) { return deep_rerank_layout(B, K_in); }
 
+// ur_catalog_fp8_select (include/unirec_fp8.h): the quantised users, then the regions of the long coarse select:
+// q [B][D] bytes | iu8 [B] | user scales [B] | ref [B] | chunk [B][rows] f32 | list scores [B][gw][K] | list indices [B][gw][K] | counts [B][gw]
+struct fp8_select_plan {
+  int64_t rows, user, inv_u, scale_u, ref, chunk, list_score, list_index, count, need;
+  int gw;
+};
+[[maybe_unused]] static fp8_select_plan fp8_select_layout(int32_t B, int64_t N, int32_t D, int32_t K, int64_t chunk_rows, int32_t segments) {
+  fp8_select_plan p;
+  ws_carver c;
+  p.rows = catalog_chunk_rows(chunk_rows, B, N);
+  p.gw = deep_segments_cap(segments, B);
+  p.user = c.take((int64_t)B * D);
+  p.inv_u = c.take((int64_t)B * 4);
+  p.scale_u = c.take((int64_t)B * 4);
+  p.ref = c.take((int64_t)B * 4);
+  p.chunk = c.take((int64_t)B * p.rows * 4);
+  p.list_score = c.take((int64_t)B * p.gw * K * 4);
+  p.list_index = c.take((int64_t)B * p.gw * K * 4);
+  p.count = c.take((int64_t)B * p.gw * 4);
+  p.need = c.need();
+  return p;
+}
+// ur_catalog_fp8_rerank: the plan of ur_catalog_deep_rerank (the code rows are read in place)
+[[maybe_unused]] static deep_rerank_plan fp8_rerank_layout(int32_t B, int32_t K_in) { return deep_rerank_layout(B, K_in); }
+
 }  // namespace

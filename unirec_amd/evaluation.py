@@ -10,6 +10,8 @@
                                   ``retrieve`` is the catalogue-scale form: the scores are streamed in chunks through
                                   ``ur_catalog_scores``' select mode (top-K, rank and a per-user seen-item filter; no [B,N] tensor).
                                   The catalogue may stay bf16 (``dtype=torch.bfloat16``): ``retrieve`` reads it as it is.
+  * ``Fp8CatalogEvaluator``       the catalogue at one byte per element (OCP e4m3fn codes and a power-of-two scale per row,
+                                  include/unirec_fp8.h): a shortlist pass over the codes and an exact re-rank against the quantised rows.
 Tie rule: the positive's rank is 1 + #{strictly greater}; top-K lists the lowest index first.
 """
 import numpy as np
@@ -168,6 +170,11 @@ class CatalogEvaluator:
         if isinstance(dim, bool) or not isinstance(dim, int) or dim <= 0 or dim % 4 or dim > D:
             raise ValueError(f"CatalogEvaluator.truncated: dim must be a positive multiple of 4 and at most D = {D}, got {dim!r}")
         return CatalogEvaluator(self.catalog[:, :dim], item_ids=self.item_ids, device=self.catalog.device, dtype=self.catalog.dtype)
+
+    def quantized(self, block_rows=None):
+        """An ``Fp8CatalogEvaluator`` over this catalogue's rows, quantised on its device a block of rows at a time: one byte per
+        element beside this evaluator's own tensor, which stays as it is."""
+        return Fp8CatalogEvaluator(self.catalog, item_ids=self.item_ids, device=self.catalog.device, block_rows=block_rows)
 
     def scores(self, user_embeddings):
         if self.catalog.dtype != F32:
@@ -339,4 +346,108 @@ class CatalogEvaluator:
             m = ranking_metrics(rank, ks).cpu().tolist()                                 # the one host read
             out.update(rank=rank, mrr=m[0], hit_at=dict(zip(ks, m[1:1 + len(ks)])), ndcg_at=dict(zip(ks, m[1 + len(ks):])),
                        rank_is_coarse=True, rank_dim=dims[0])
+        return out
+
+
+class Fp8CatalogEvaluator:
+    """Two-stage retrieval over a catalogue held at ONE byte per element (include/unirec_fp8.h): ``codes`` uint8 [N,D] (OCP e4m3fn bit
+    patterns), ``scale`` f32 [N] (a power of two per row; ``codes.float() * scale[:, None]`` decodes exactly) and ``inv`` f32 [N] (the
+    inverse norms of the code rows).  No other tensor of size N x D is held."""
+
+    BLOCK_BYTES = 256 << 20      # full-precision bytes on the device at a time while a host catalogue streams in
+
+    def __init__(self, catalog, item_ids=None, device="cuda", block_rows=None):
+        """catalog: an f32 or bf16 tensor [N,D] (anything else is converted to f32), D a multiple of 16 and at most 2048, on the host
+        or on a device.  It is quantised by ``hip.catalog_fp8_quantize`` a block of `block_rows` rows at a time (None: blocks of 256 MB);
+        a host tensor is copied block by block, so no full-precision device copy is made."""
+        cat = torch.as_tensor(catalog)
+        if cat.dtype not in (F32, torch.bfloat16):
+            cat = cat.to(F32)
+        if cat.dim() != 2 or cat.shape[1] == 0 or cat.shape[1] % 16 or cat.shape[1] > 2048:
+            raise ValueError(f"Fp8CatalogEvaluator: catalog must be [N,D] with D a positive multiple of 16 and at most 2048, got {tuple(cat.shape)}")
+        N, D = cat.shape
+        if block_rows is None:
+            block_rows = max(1, self.BLOCK_BYTES // (D * cat.element_size()))
+        if isinstance(block_rows, bool) or not isinstance(block_rows, int) or block_rows < 1:
+            raise ValueError(f"Fp8CatalogEvaluator: block_rows must be a positive int or None, got {block_rows!r}")
+        dev = torch.device(device)
+        self.item_ids = None if item_ids is None else [str(i) for i in item_ids]
+        self.codes = torch.empty((N, D), dtype=hip.FP8_CODES, device=dev)
+        self.scale = torch.empty((N,), dtype=F32, device=dev)
+        self.inv = torch.empty((N,), dtype=F32, device=dev)
+        for r0 in range(0, N, block_rows):
+            r1 = min(N, r0 + block_rows)
+            block = cat[r0:r1].detach().to(dev).contiguous()
+            hip.catalog_fp8_quantize(block, out=(self.codes[r0:r1], self.scale[r0:r1], self.inv[r0:r1]))
+
+    @classmethod
+    def from_codes(cls, codes, scale, item_ids=None):
+        """An evaluator over codes uint8 (or float8_e4m3fn) [N,D] and scale f32 [N] that exist already, on their device; ``inv`` is
+        recomputed from the codes a block of rows at a time (``hip.catalog_prefix_norms`` on the widened block: the row-norm chain, hence
+        the bits ``hip.catalog_fp8_quantize`` writes)."""
+        if codes.dtype == torch.float8_e4m3fn:
+            codes = codes.view(hip.FP8_CODES)
+        if codes.dtype != hip.FP8_CODES or codes.dim() != 2 or codes.shape[1] == 0 or codes.shape[1] % 16 or codes.shape[1] > 2048:
+            raise ValueError("Fp8CatalogEvaluator.from_codes: codes must be uint8 or float8_e4m3fn [N,D] with D a positive multiple of 16 and at "
+                             f"most 2048, got {codes.dtype} {tuple(codes.shape)}")
+        if scale.dtype != F32 or scale.shape != (codes.shape[0],):
+            raise ValueError(f"Fp8CatalogEvaluator.from_codes: scale must be f32 of shape [{codes.shape[0]}], got {scale.dtype} {tuple(scale.shape)}")
+        ev = cls.__new__(cls)
+        ev.item_ids = None if item_ids is None else [str(i) for i in item_ids]
+        ev.codes = codes.contiguous()
+        ev.scale = scale.to(codes.device).contiguous()
+        N, D = codes.shape
+        ev.inv = torch.empty((N,), dtype=F32, device=codes.device)
+        rows = max(1, cls.BLOCK_BYTES // (4 * D))
+        for r0 in range(0, N, rows):
+            r1 = min(N, r0 + rows)
+            values = ev.codes[r0:r1].view(torch.float8_e4m3fn).to(F32)             # a block of f32 code values, freed after its norms
+            ev.inv[r0:r1] = hip.catalog_prefix_norms(values, (D,))[0]                # the row-norm chain, the bits of the quantiser's plane
+        return ev
+
+    def dequantized(self, index=None):
+        """f32 rows: codes.float() * scale[:, None], exact; all N rows, or those of `index` (a 1-D tensor or list of row numbers)."""
+        codes, scale = self.codes, self.scale
+        if index is not None:
+            index = torch.as_tensor(index).to(codes.device, torch.int64)
+            codes, scale = codes[index], scale[index]
+        return codes.view(torch.float8_e4m3fn).to(F32) * scale[:, None]
+
+    def retrieve_two_stage(self, user_embeddings, k=10, shortlist=None, gt_index=None, exclude=None, ks=None, chunk_rows=None, rerank_with=None):
+        """``CatalogEvaluator.retrieve_two_stage`` on the fp8 catalogue: ``hip.catalog_fp8_select`` picks `shortlist` items per user under
+        the fp8 scores (users and rows as e4m3 codes, the users quantised by the catalogue's rule; the selection kernels of ``hip.catalog_deep_select``), then
+        the shortlist is scored exactly and the best k are returned -- one path for 1 <= k <= shortlist <= 1024.
+        rerank_with=None: stage 2 is ``hip.catalog_fp8_rerank``, the exact scores of the QUANTISED catalogue -- the bits
+        ``hip.catalog_deep_rerank`` gives on ``dequantized()``.  rerank_with=a ``CatalogEvaluator`` over the same N items: stage 2 is
+        that evaluator's ``hip.catalog_deep_rerank``, for a caller that has the full-precision rows resident anyway.
+        -> the dict of ``CatalogEvaluator.retrieve_two_stage``: topk_index int32 [B,k], topk_score f32 [B,k] in the exact order of stage
+        2; with gt_index also rank / mrr / hit_at / ndcg_at from the COARSE fp8 scores; always rank_is_coarse=True and
+        catalog_dtype="fp8_e4m3".  exclude, ks and chunk_rows as in ``CatalogEvaluator.retrieve``.
+        shortlist=None means min(1024, max(128, 2 k)): a default that leaves the re-rank twice the room it returns, NOT a tuned value --
+        choose it from the recall the catalogue needs."""
+        top = hip.CATALOG_DEEP_TOPK_MAX
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= top:
+            raise ValueError(f"retrieve_two_stage: k must be an int in [1, {top}], got {k!r}")
+        if shortlist is None:
+            shortlist = min(top, max(hip.CATALOG_TOPK_MAX, 2 * k))
+        if isinstance(shortlist, bool) or not isinstance(shortlist, int) or not k <= shortlist <= top:
+            raise ValueError(f"retrieve_two_stage: shortlist must be an int in [k, {top}] (k = {k!r}), got {shortlist!r}")
+        if rerank_with is not None and (not isinstance(rerank_with, CatalogEvaluator) or rerank_with.catalog.shape != self.codes.shape):
+            got = tuple(rerank_with.catalog.shape) if isinstance(rerank_with, CatalogEvaluator) else type(rerank_with).__name__
+            raise ValueError(f"retrieve_two_stage: rerank_with must be a CatalogEvaluator over the same {list(self.codes.shape)} catalogue, got {got}")
+        u = user_embeddings.detach().to(self.codes.device, F32).contiguous()
+        ex = pack_exclude(exclude, u.shape[0])
+        if ex is not None:
+            ex = ex.to(u.device)
+        gt = None if gt_index is None else torch.as_tensor(gt_index).to(u.device, torch.int64)
+        short, _, rank = hip.catalog_fp8_select(u, self.codes, shortlist, self.inv, gt_index=gt, exclude=ex, chunk_rows=chunk_rows)
+        if rerank_with is None:
+            idx, val = hip.catalog_fp8_rerank(u, self.codes, short, self.inv, k)
+        else:
+            idx, val, rerank_with._inv = hip.catalog_deep_rerank(u, rerank_with.catalog, short, k, rerank_with._inv)
+        out = {"topk_index": idx, "topk_score": val, "rank_is_coarse": True, "catalog_dtype": "fp8_e4m3"}
+        if rank is not None:
+            ks = (k,) if ks is None else tuple(int(x) for x in ks)
+            m = ranking_metrics(rank, ks).cpu().tolist()                                 # the one host read
+            out.update(rank=rank, mrr=m[0], hit_at=dict(zip(ks, m[1:1 + len(ks)])), ndcg_at=dict(zip(ks, m[1 + len(ks):])))
         return out

@@ -1593,6 +1593,103 @@ def catalog_funnel_rerank(user, catalog, index, dim, k=None, cat_inv_norm=None):
     return idx, val, cat_inv_norm
 
 
+FP8_CODES = torch.uint8      # the codes of an fp8 catalogue: e4m3fn bit patterns (codes.view(torch.float8_e4m3fn) is torch's view of them)
+
+
+def _fp8_operands(who, user, codes, cat_inv_norm):
+    """The operand checks of the fp8 wrappers: user [B,D] f32 and codes [N,D] uint8 (or float8_e4m3fn, the same bytes) sharing D, D a
+    multiple of 16, cat_inv_norm [N] f32 -- always given: it is the plane catalog_fp8_quantize wrote.  Shapes first, as ValueErrors.
+    Returns (B, N, D, device, codes as uint8)."""
+    if codes.dtype == torch.float8_e4m3fn:
+        codes = codes.view(FP8_CODES)
+    if codes.dtype != FP8_CODES:
+        raise ValueError(f"{who}: codes must be uint8 or float8_e4m3fn (OCP e4m3fn bit patterns), got {codes.dtype}")
+    if user.dim() != 2 or codes.dim() != 2 or codes.shape[1] != user.shape[1]:
+        raise ValueError(f"{who}: user [B,D] and codes [N,D] must share D, got {tuple(user.shape)} and {tuple(codes.shape)}")
+    (B, D), N = user.shape, codes.shape[0]
+    if D % 16:
+        raise ValueError(f"{who}: D must be a multiple of 16, got {D}")
+    if cat_inv_norm is None or cat_inv_norm.dtype != F32 or cat_inv_norm.shape != (N,):
+        got = None if cat_inv_norm is None else (cat_inv_norm.dtype, tuple(cat_inv_norm.shape))
+        raise ValueError(f"{who}: cat_inv_norm must be f32 of shape [{N}] (the inv plane of catalog_fp8_quantize), got {got}")
+    _need(user, F32, f"{who}: user")
+    _need(codes, FP8_CODES, f"{who}: codes")
+    _need(cat_inv_norm, F32, f"{who}: cat_inv_norm")
+    return B, N, D, user.device, codes
+
+
+def catalog_fp8_quantize(src, out=None):
+    """Rows of src [N,D] f32 or bf16 -> an fp8 catalogue (ur_catalog_fp8_quantize, include/unirec_fp8.h): codes uint8 [N,D], one OCP
+    e4m3fn bit pattern per element; scale f32 [N], the power of two 2^-e of the row (e the largest exponent with max|x| 2^e <= 448);
+    inv f32 [N], the inverse norm of the row's code values with the bits the row-norm kernel gives codes.float().  Rounding is to
+    nearest even into the subnormals with signed zeros, the header's rule in integer arithmetic: the codes are those of
+    (src * 2^e).to(torch.float8_e4m3fn) on the CPU.  codes.float() * scale[:, None] decodes exactly.  src may be a view whose rows are
+    further apart than D (stride(1) == 1, a row stride that is a multiple of 4); D a multiple of 16, at most 2048.
+    out: (codes, scale, inv) to write into, for quantising a catalogue a block of rows at a time.  Returns (codes, scale, inv)."""
+    who = "catalog_fp8_quantize"
+    if src.dtype not in (F32, BF16):
+        raise ValueError(f"{who}: src must be f32 or bf16, got {src.dtype}")
+    if src.dim() != 2 or src.shape[1] == 0 or src.shape[1] % 16:
+        raise ValueError(f"{who}: src must be [N,D] with D a positive multiple of 16, got {tuple(src.shape)}")
+    N, D = src.shape
+    ld = src.stride(0) if N > 1 else D
+    if src.stride(1) != 1 or ld < D or ld % 4:
+        raise ValueError(f"{who}: src must have unit stride along D and a row stride >= D that is a multiple of 4, got strides {src.stride()}")
+    if not src.is_cuda:
+        raise _lib.UniRecHipError(f"{who}: src: expected a device tensor (the UniRec HIP path has no CPU fallback)")
+    dev = src.device
+    if out is None:
+        out = (torch.empty((N, D), dtype=FP8_CODES, device=dev), torch.empty((N,), dtype=F32, device=dev), torch.empty((N,), dtype=F32, device=dev))
+    codes, scale, inv = out
+    if codes.shape != (N, D) or scale.shape != (N,) or inv.shape != (N,):
+        raise ValueError(f"{who}: out must be (codes [{N},{D}], scale [{N}], inv [{N}]), got {tuple(codes.shape)}, {tuple(scale.shape)}, "
+                         f"{tuple(inv.shape)}")
+    _need(codes, FP8_CODES, f"{who}: codes")
+    _need(scale, F32, f"{who}: scale")
+    _need(inv, F32, f"{who}: inv")
+    a = _lib.CatalogFp8Quantize()
+    a.src, a.src_bf16, a.N, a.D, a.ld = src.data_ptr(), int(src.dtype == BF16), N, D, ld
+    a.codes, a.scale, a.inv = codes.data_ptr(), scale.data_ptr(), inv.data_ptr()
+    check(_lib.load().ur_catalog_fp8_quantize(ctypes.byref(a), _stream()), "ur_catalog_fp8_quantize")
+    return codes, scale, inv
+
+
+def catalog_fp8_select(user, codes, K, cat_inv_norm, gt_index=None, exclude=None, chunk_rows=None, segments=None):
+    """catalog_coarse_deep_select over an fp8 catalogue (ur_catalog_fp8_select, include/unirec_fp8.h): the K <= 1024 best items per user
+    of user [B,D] f32 under the APPROXIMATE score s8 -- the users are quantised by catalog_fp8_quantize's rule and the cosine of the two
+    code rows is summed in f32 by v_mfma_f32_16x16x32_bf16 on the codes widened in registers (exact products; the error is the order of
+    the sum; the fp8 MFMA truncates its products and is not used).  codes uint8 [N,D] and
+    cat_inv_norm [N] are catalog_fp8_quantize's codes and inv; the row scales play no part in a cosine.  Total order, gt_index / rank,
+    exclude, chunk_rows, segments and the (-1, -inf) tail are catalog_coarse_deep_select's (the same selection kernels).
+    Returns (topk_index int32 [B,K], topk_score f32 [B,K], rank int32 [B] or None)."""
+    a = _lib.CatalogFp8Select()
+    a.B, a.N, a.D, dev, codes = _fp8_operands("catalog_fp8_select", user, codes, cat_inv_norm)
+    a.user, a.codes, a.cat_inv_norm = user.data_ptr(), codes.data_ptr(), cat_inv_norm.data_ptr()
+    a.K, a.chunk_rows, a.segments = int(K), int(chunk_rows or 0), int(segments or 0)
+    idx, val = _catalog_lists(a, a.B, a.K, dev)
+    gt, rank = _catalog_filters("catalog_fp8_select", a, a.B, dev, gt_index, exclude)
+    _catalog_call("ur_catalog_fp8_select", a, dev, "catalog_fp8_select")
+    return idx, val, rank
+
+
+def catalog_fp8_rerank(user, codes, index, cat_inv_norm, k=None):
+    """catalog_deep_rerank over an fp8 catalogue (ur_catalog_fp8_rerank, include/unirec_fp8.h): index int32 [B,K'] with K' <= 1024 into
+    codes uint8 [N,D], an entry outside [0,N) an empty slot.  Every pair is scored EXACTLY against the quantised row -- the codes are
+    widened as they are read and meet the unrounded f32 user in catalog_scores' own chain -- so the index and score bits are those of
+    catalog_deep_rerank(user, codes.float(), index, k, cat_inv_norm).  Returns (topk_index int32 [B,k], topk_score f32 [B,k])."""
+    a = _lib.CatalogFp8Rerank()
+    a.B, a.N, a.D, dev, codes = _fp8_operands("catalog_fp8_rerank", user, codes, cat_inv_norm)
+    a.user, a.codes, a.cat_inv_norm = user.data_ptr(), codes.data_ptr(), cat_inv_norm.data_ptr()
+    _need(index, torch.int32, "catalog_fp8_rerank: index")
+    if index.dim() != 2 or index.shape[0] != a.B:
+        raise ValueError(f"catalog_fp8_rerank: index must be [{a.B}, K'], got {tuple(index.shape)}")
+    a.index, a.K_in = index.data_ptr(), index.shape[1]
+    a.k = index.shape[1] if k is None else int(k)
+    idx, val = _catalog_lists(a, a.B, a.k, dev)
+    _catalog_call("ur_catalog_fp8_rerank", a, dev, "catalog_fp8_rerank")
+    return idx, val
+
+
 def catalog_softmax(user, catalog, gt_index, temperature, cat_inv_norm=None, exclude=None, chunk_rows=None, scorer=None, grad_scale=1.0,
                     need_grad=True):
     """The softmax loss over the whole catalogue [N,D] f32 or bf16 (ur_catalog_softmax, include/unirec_hip_loss.h): cross-entropy of
