@@ -49,7 +49,13 @@ const char* ur_last_error(void);
  * split_k > 1: f32 output only, ldc == N (a padded output is rejected: the slabs are dense [M, N] images of C and the
  *   combine copies them whole), deterministic slab reduction in `workspace`.
  * Constraints: K,K2 % 8 == 0 unless both operands are K-strided; N, ldc % 4 == 0; leading dims
- * % 8 == 0; 16-byte aligned bases. */
+ * % 8 == 0; 16-byte aligned bases.
+ * Alignment of every pointer (a pointer below it is refused with a negative return that names it, before any launch):
+ *   16 bytes  R, S, R2, S2, C, bias (read in 16-byte pieces), drop_bits, the split_k workspace of ur_gemm / ur_gemm_grouped,
+ *             qkr_q, qkr_k, qkr_v, swp_act, qkr_qw, qkr_kw, qkr_cos, qkr_sin (the norm weights and table rows are read in 16-byte pieces)
+ *    8 bytes  residual, gelu_out, gelu_grad_aux, swiglu_gu, swiglu_dgu, swiglu_gate, swiglu_act, with leading dimensions % 4 == 0 (the
+ *             persistent kernel takes them at 16 bytes with leading dimensions % 8 == 0; anything less runs the generic kernel)
+ *    4 bytes  qkr_rstd (one f32 store per (token, head)) */
 typedef struct {
   const void* R; int64_t ldr; int32_t r_kcontig;
   const void* S; int64_t lds; int32_t s_kcontig;
@@ -186,7 +192,10 @@ int ur_gemm_plan(const ur_gemm_args* a, int32_t count, ur_gemm_plan_info* out);
  *       bit i (i<4) = element c+2i dropped, bit 4+i = element c+2i+1 dropped.  A pure function of (seed, p, row0 + m, c, a).
  * drop_bits == NULL: no dropout.  The 1/(1-p) scale is the caller's (alpha).
  * Constraints: rank in {8, 16, 32, 64} (any other: a negative return whose message names the set); column ranges and ldx
- * multiples of 8; X, U, V, G 16-byte aligned; P 8-byte aligned.  Rank 16 has LDS-DMA ring kernels for the launches described at
+ * multiples of 8; X, U, V, G 16-byte aligned; P 8-byte aligned; drop_bits 16-byte aligned with bits_ld and bits_stride multiples of
+ * 16; drop_bits_t 16-byte aligned for the ring kernel (anything less runs the register-staged one); the slab workspaces of
+ * ur_lora_reduce / ur_lora_bgrad 16-byte aligned (summed in 16-byte pieces); x, w, out of ur_rmsnorm_lora_fwd and gu, act of
+ * ur_swiglu_lora_fwd 16-byte aligned, rstd 4-byte aligned.  Rank 16 has LDS-DMA ring kernels for the launches described at
  * drop_bits_t and ur_lora_bgrad; every other rank runs the register-staged kernels (an adapter = 1, 2 or 4 blocks of 16 rank rows
  * over the same fragments of X and the adapter's one bit plane; rank 8 = a half-filled block).  A row of P does not depend on where
  * the row sits in the launch.  ur_rmsnorm_lora_fwd and ur_swiglu_lora_fwd are rank 16 only.  Which kernel, grid, token split and
@@ -331,7 +340,9 @@ int ur_rmsnorm_bwd(const void* dout, const void* x, const float* w, const float*
  *       GQA: kv head = q head / (nq / nkv).  Needs Sq == Sk, dropout_p == 0.
  * q [B,Sq,nq,hd], k/v [B,Sk,nkv,hd], o [B,Sq,nq,hd] bf16 with token strides ldq/ldk/ldv/ldo
  * (elements; lets q,k,v live in one fused projection buffer).  head_dim 64 or 128.
- * stats [B,nq,Sq,2] f32 = (row max, 1/row sum) saved for the backward. */
+ * stats [B,nq,Sq,2] f32 = (row max, 1/row sum) saved for the backward.
+ * Alignment: q, k, v, o 16 bytes (ldq, ldk, ldv % 8 == 0; ldo % 4 == 0 for the forward alone, % 8 == 0 once the backward reads o);
+ * stats 4 bytes (every access is one f32); key_mask none (its bytes are read one at a time). */
 typedef struct {
   const void* q; const void* k; const void* v; void* o; float* stats;
   int64_t ldq, ldk, ldv, ldo;
@@ -349,7 +360,11 @@ typedef struct {
  * kernel; untouched without dropout) and the work-queue words of the persistent dK/dV kernel (zeroed by the
  * call itself) -- the library keeps no mutable device state of its own, so calls on different streams never interfere as long
  * as each brings its own workspace.  `a` must be the forward's arguments (o and stats filled by ur_attn_fwd).
- * No floating-point atomics: results are bitwise reproducible. */
+ * No floating-point atomics: results are bitwise reproducible.
+ * Alignment: dout 16 bytes (lddo % 8 == 0); dq, dk, dv 8 bytes (row strides % 4 == 0); delta, stats, kv_colsum, kv_colsum_ws and
+ * rope_rstd 4 bytes (every access through them is one 32-bit word, the kernels' LDS-DMA fetches of the row constants included);
+ * rope_q_raw, rope_dq_raw, rope_k, rope_dk_raw, rope_q_weight, rope_k_weight, rope_cos, rope_sin 16 bytes.  A pointer below its
+ * alignment is refused with a negative return that names it, before any launch. */
 typedef struct {
   const void* dout; void* dq; void* dk; void* dv;
   int64_t lddo, lddq, lddk, lddv;
@@ -371,7 +386,8 @@ typedef struct {
   /* with rope_rstd, optional: the k heads as well.  rope_k = the ROPED, normed k (qkr_k: the k of ur_attn_args, row stride rope_ldk),
    * rope_k_weight its norm weight, 1 / rms of (token m, k head h) = rope_rstd[m * rope_rstd_ld + rope_rstd_hk0 + h]; rope_dk_raw
    * (row stride rope_lddkraw) receives the gradient of the RAW k projection.  The generated causal head_dim-128 dK/dV kernel applies it
-   * in its store (dk is then not written); other shapes write dk (dense [B*Sk, nkv*hd] required) and run ur_qknorm_rope_bwd_roped_k. */
+   * in its store (dk is then not written); other shapes write dk (dense [B*Sk, nkv*hd] and 16-byte aligned, both required and checked before
+   * anything is launched) and run ur_qknorm_rope_bwd_roped_k. */
   const void* rope_k; int64_t rope_ldk; const float* rope_k_weight; int32_t rope_rstd_hk0;
   void* rope_dk_raw; int64_t rope_lddkraw;
   /* kv_colsum != NULL: the call also writes the column sums over ALL keys of all batch rows of dK and dV, f32 [2][nq * head_dim]

@@ -1,4 +1,4 @@
-"""CPU: every entry point declared in include/unirec_hip.h or in one of the family headers include/unirec_hip_*.h is either listed in a COVERS table -- naming the primitive-level test(s)
+"""CPU: every entry point declared in include/unirec_hip.h or in one of the family headers include/unirec_*.h (include/unirec_fp8.h among them) is either listed in a COVERS table -- naming the primitive-level test(s)
 that hold it against a reference -- or exempt below with a reason.  A new entry point without such a test fails here."""
 import ast
 import functools
@@ -14,7 +14,11 @@ COVERS_MODULES = ("tests/test_gpu_primitives.py", "tests/test_gpu_head_primitive
                   "tests/test_gpu_catalog_funnel.py", "tests/test_gpu_catalog_softmax.py", "tests/test_gpu_catalog_mrl_softmax.py",
                   "tests/test_gpu_mrl_f64.py", "tests/test_gpu_pool_f64.py", "tests/test_gpu_lora_merge.py",
                   # where the catalogue calls read and write: the weakest alignments, guards, poisoned workspaces; rows past 4 GiB
-                  "tests/test_gpu_catalog_memory.py", "tests/test_gpu_catalog_4gib.py")
+                  "tests/test_gpu_catalog_memory.py", "tests/test_gpu_catalog_4gib.py",
+                  # the FP8 catalogues of include/unirec_fp8.h
+                  "tests/test_gpu_catalog_fp8.py", "tests/test_gpu_catalog_fp8_memory.py",
+                  # where the training hot path reads and writes: GEMM, attention, LoRA under the same memory contract
+                  "tests/test_gpu_gemm_memory.py", "tests/test_gpu_attention_memory.py", "tests/test_gpu_lora_memory.py")
 
 EXEMPT = {
     "ur_version": "ABI handshake; asserted at every library load (unirec_amd/_lib.py) and in tests/test_cabi.py",
@@ -50,7 +54,7 @@ EXEMPT = {
 def _headers():
     """include/unirec_hip.h first, then the family headers in name order"""
     first = os.path.join(ROOT, "include", "unirec_hip.h")
-    rest = sorted(p for p in glob.glob(os.path.join(ROOT, "include", "unirec_hip*.h")) if p != first)
+    rest = sorted(p for p in glob.glob(os.path.join(ROOT, "include", "unirec_*.h")) if p != first)
     return [first] + rest
 
 
@@ -122,9 +126,10 @@ def _tables():
 
 def test_every_entry_point_has_a_primitive_level_test_or_a_reason():
     declared = _declared_entry_points()
-    assert len(_headers()) >= 10 and len(declared) == len(set(declared))
+    assert len(_headers()) == 11 and len(declared) == len(set(declared))
     assert len(declared) >= 100 and "ur_gemm" in declared and "ur_comm_destroy" in declared
     assert "ur_catalog_deep_select" in declared and "ur_lora_merge" in declared and "ur_catalog_mrl_softmax" in declared
+    assert {"ur_catalog_fp8_quantize", "ur_catalog_fp8_select", "ur_catalog_fp8_rerank"} <= set(declared)
     assert all(reason.strip() for reason in EXEMPT.values())
     problems = _problems(declared, _tables(), lambda p: _covers_and_tests(p)[1])
     assert not problems, "\n".join(problems)

@@ -61,6 +61,36 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert lib.ur_comm_destroy(None) == 0
 
 
+def test_pointers_below_the_stated_alignment_are_refused_by_name_without_a_gpu():
+    """the alignments include/unirec_hip.h states for the f32 planes, scratch and workspaces of ur_attn_fwd / ur_attn_bwd, ur_gemm and
+    ur_rmsnorm_lora_fwd: a pointer below them is a negative return that names it, before any HIP call (fake addresses, never followed)"""
+    lib, P = _lib.load(), 1 << 20
+    a, g = _lib.AttnArgs(), _lib.AttnBwdArgs()
+    a.q, a.k, a.v, a.o, a.stats = P, 2 * P, 3 * P, 4 * P, 5 * P + 2
+    a.B, a.Sq, a.Sk, a.nq, a.nkv, a.head_dim, a.scale = 2, 33, 40, 2, 2, 64, 0.125
+    a.ldq = a.ldk = a.ldv = a.ldo = g.lddo = g.lddq = g.lddk = g.lddv = 128
+    assert lib.ur_attn_fwd(ctypes.byref(a), None) < 0 and b"stats must be 4-byte aligned" in lib.ur_last_error()
+    a.stats = 5 * P + 4
+    g.dout, g.dq, g.dk, g.dv, g.delta = 6 * P, 7 * P + 8, 8 * P + 8, 9 * P + 8, 10 * P + 2
+    assert lib.ur_attn_bwd(ctypes.byref(a), ctypes.byref(g), None) < 0 and b"delta must be 4-byte aligned" in lib.ur_last_error()
+    g.delta, g.kv_colsum, g.kv_colsum_ws = 10 * P + 4, 11 * P + 2, 12 * P + 4
+    assert lib.ur_attn_bwd(ctypes.byref(a), ctypes.byref(g), None) < 0 and b"kv_colsum and kv_colsum_ws must be 4-byte aligned" in lib.ur_last_error()
+    g.kv_colsum, g.kv_colsum_ws, g.rope_rstd = 0, 0, 13 * P + 2
+    assert lib.ur_attn_bwd(ctypes.byref(a), ctypes.byref(g), None) < 0 and b"rope_rstd must be 4-byte aligned" in lib.ur_last_error()
+    m = _lib.GemmArgs()
+    m.M, m.N, m.K, m.R, m.S, m.C = 136, 136, 136, P, 2 * P, 3 * P
+    m.ldr = m.lds = m.ldc = 136
+    m.c_f32, m.split_k, m.alpha = 1, 2, 1.0
+    need = lib.ur_gemm_workspace_bytes(ctypes.byref(m))
+    assert need == 2 * 136 * 136 * 4
+    assert lib.ur_gemm(ctypes.byref(m), 4 * P + 8, need, None) < 0 and b"workspace must be 16-byte aligned" in lib.ur_last_error()
+    assert lib.ur_gemm(ctypes.byref(m), 4 * P, need - 1, None) < 0 and b"workspace too small" in lib.ur_last_error()
+    assert lib.ur_gemm_grouped(ctypes.byref(m), 1, 4 * P + 8, need, None) < 0 and b"workspace must be 16-byte aligned" in lib.ur_last_error()
+    r = _lib.LoraArgs()
+    r.nad, r.rank, r.shared = 1, 16, 1
+    assert lib.ur_rmsnorm_lora_fwd(P, 2 * P, 3 * P, 4 * P + 2, 8, 1024, 1e-6, ctypes.byref(r), None) < 0 and b"rstd must be 4-byte aligned" in lib.ur_last_error()
+
+
 def test_product_path_has_no_oracle_import():
     """The oracle is test infrastructure: nothing under unirec_amd/ may import it."""
     pkg = os.path.join(ROOT, "unirec_amd")

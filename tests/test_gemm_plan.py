@@ -236,6 +236,11 @@ def test_empty_launches_select_nothing():
     ((2048, 4096, 256), dict(R=0), "null operand"),
     ((1024, 4096, 256), QKR, "q/k-norm \\+ RoPE epilogue is not available"),
     ((1024, 4096, 256), SWP, "paired SwiGLU forward epilogue is not available"),
+    # the epilogue's f32 operands below the alignment the header states: refused by name, not as "not available"
+    ((2048, 4096, 256), dict(QKR, qkr_cos=ADDR + 8), "qkr_qw, qkr_kw, qkr_cos and qkr_sin must be 16-byte aligned"),
+    ((2048, 4096, 256), dict(QKR, qkr_kw=ADDR + 4), "qkr_qw, qkr_kw, qkr_cos and qkr_sin must be 16-byte aligned"),
+    ((2048, 4096, 256), dict(QKR, qkr_rstd=ADDR + 2), "qkr_rstd must be 4-byte aligned"),
+    ((2048, 4096, 256), dict(bias=ADDR + 8), "bias must be 16-byte aligned"),
 ])
 def test_the_query_refuses_what_ur_gemm_refuses(args, kw, text):
     for mode in (0, 1):

@@ -304,6 +304,7 @@ def test_argument_checks_reject_without_launching():
     refused(_with(a, v=a.v + 4))
     refused(_with(a, q=0))
     refused(_with(a, stats=0))
+    refused(_with(a, stats=a.stats + 2))                       # the f32 planes: 4 bytes
     # the output of the forward: 16-byte base, ldo % 4, ldo >= heads * hd (the backward only reads o: 16-byte rows)
     refused(_with(a, o=a.o + 8))
     refused(_with(a, ldo=nq * hd + 2))
@@ -321,6 +322,10 @@ def test_argument_checks_reject_without_launching():
     refused(a, _with(g, lddv=nkv * hd + 6), fwd=False)
     refused(a, _with(g, dq=0), fwd=False)
     refused(a, _with(g, delta=0), fwd=False)
+    refused(a, _with(g, delta=g.delta + 2), fwd=False)
+    refused(a, _with(g, kv_colsum=keep["colsum"].data_ptr() + 2, kv_colsum_ws=keep["colsum_ws"].data_ptr()), fwd=False)
+    refused(a, _with(g, kv_colsum=keep["colsum"].data_ptr(), kv_colsum_ws=keep["colsum_ws"].data_ptr() + 2), fwd=False)
+    refused(a, _with(g, rope_rstd=keep["stats"].data_ptr() + 2), fwd=False)
     # kv_colsum where the few-query kernel does not run (40 keys), and without its scratch
     assert lib.ur_attn_bwd_kv_colsum_floats(ctypes.byref(a)) == 0
     refused(a, _with(g, kv_colsum=keep["colsum"].data_ptr(), kv_colsum_ws=keep["colsum_ws"].data_ptr()), fwd=False)

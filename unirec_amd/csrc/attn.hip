@@ -2774,6 +2774,7 @@ int launch(const char* name, dim3 grid, int threads, int max_lds, int lds, hipSt
 // with_ptrs = false (ur_attn_plan): the same checks without requiring, align-checking or reading any data pointer
 int fill(AttnP& p, const ur_attn_args* a, bool with_ptrs = true) {
   UR_REQUIRE(a && (!with_ptrs || (a->q && a->k && a->v && a->stats)), "ur_attn: null argument");
+  UR_REQUIRE(!with_ptrs || (((uintptr_t)a->stats) & 3) == 0, "ur_attn: stats must be 4-byte aligned");
   UR_REQUIRE(a->B >= 0 && a->Sq > 0 && a->Sk > 0 && a->nq > 0 && a->nkv > 0 && (a->nq % a->nkv) == 0, "ur_attn: bad sizes");
   UR_REQUIRE(a->head_dim == 64 || a->head_dim == 128, "ur_attn: head_dim must be 64 or 128 (got %d)", a->head_dim);
   UR_REQUIRE((a->ldq % 8) == 0 && (a->ldk % 8) == 0 && (a->ldv % 8) == 0 && (!with_ptrs || (UR_ALIGNED16(a->q) && UR_ALIGNED16(a->k) && UR_ALIGNED16(a->v))),
@@ -2997,6 +2998,10 @@ extern "C" int ur_attn_bwd(const ur_attn_args* a, const ur_attn_bwd_args* g, voi
   if (rc) return rc;
   if (a->B == 0) return 0;
   UR_REQUIRE(g && g->dout && (g->dq || g->rope_q_raw) && g->dk && g->dv && g->delta && a->o, "ur_attn_bwd: null argument");
+  // f32 planes and scratch: every access through them is one 32-bit word (the LDS-DMA fetches of the row constants included)
+  UR_REQUIRE((((uintptr_t)g->delta) & 3) == 0, "ur_attn_bwd: delta must be 4-byte aligned");
+  UR_REQUIRE((((uintptr_t)g->kv_colsum) & 3) == 0 && (((uintptr_t)g->kv_colsum_ws) & 3) == 0, "ur_attn_bwd: kv_colsum and kv_colsum_ws must be 4-byte aligned");
+  UR_REQUIRE((((uintptr_t)g->rope_rstd) & 3) == 0, "ur_attn_bwd: rope_rstd must be 4-byte aligned");
   if (g->rope_q_raw) {
     UR_REQUIRE(a->head_dim == 128 && a->causal && a->Sq == a->Sk, "ur_attn_bwd: the fused q-norm / RoPE backward is built for the causal head_dim-128 shape");
     UR_REQUIRE(g->rope_q_weight && g->rope_cos && g->rope_sin && g->rope_dq_raw && UR_ALIGNED16(g->rope_q_raw) && UR_ALIGNED16(g->rope_dq_raw) &&
@@ -3043,6 +3048,8 @@ extern "C" int ur_attn_bwd(const ur_attn_args* a, const ur_attn_bwd_args* g, voi
   if (rope_k && !rope_k_fused) {
     // (checked BEFORE anything is launched: a refused call leaves every output untouched)
     UR_REQUIRE(g->lddk == (int64_t)a->nkv * a->head_dim, "ur_attn_bwd: rope_k on this shape needs a dense dk [B*Sk, nkv*hd]");
+    // (ur_qknorm_rope_bwd_roped_k reads dk in 16-byte pieces and used to refuse an 8-byte aligned one AFTER dQ and dK/dV had run)
+    UR_REQUIRE(UR_ALIGNED16(g->dk), "ur_attn_bwd: rope_k on this shape needs a 16-byte aligned dk (the stand-alone k kernel reads it in 16-byte pieces)");
     p.rk_src = nullptr;
   }
   rc = launch_dq(p, pl, a->head_dim, a->causal != 0, st);

@@ -529,6 +529,12 @@ static int gemm_check(const ur_gemm_args* a) {
                (((uintptr_t)a->swiglu_gu) & 7) == 0 && (((uintptr_t)a->swiglu_dgu) & 7) == 0,
                "ur_gemm: SwiGLU backward epilogue: N must equal swiglu_I, gu / dgu rows of >= 2 I elements, 8-byte aligned");
   }
+  if (a->qkr_q) {
+    // the epilogue reads the norm weights and the table rows in 16-byte pieces and stores one f32 per (token, head)
+    UR_REQUIRE(UR_ALIGNED16(a->qkr_qw) && UR_ALIGNED16(a->qkr_kw) && UR_ALIGNED16(a->qkr_cos) && UR_ALIGNED16(a->qkr_sin),
+               "ur_gemm: qkr_qw, qkr_kw, qkr_cos and qkr_sin must be 16-byte aligned");
+    UR_REQUIRE((((uintptr_t)a->qkr_rstd) & 3) == 0, "ur_gemm: qkr_rstd must be 4-byte aligned");
+  }
   if (a->drop_bits) {
     UR_REQUIRE(a->K2 > 0 && ((a->drop_rank >= 8 && a->drop_rank <= 32 && (a->drop_rank % 8) == 0) || a->drop_rank == 64) && (a->K2 % a->drop_rank) == 0 &&
                a->K2 / a->drop_rank <= 4 && a->r_kcontig && a->s_kcontig && splits <= 1 && !a->c_f32,
@@ -566,8 +572,9 @@ extern "C" int ur_gemm(const ur_gemm_args* a, void* workspace, int64_t workspace
   if (pl.kernel == UR_GEMM_KERNEL_NONE) return 0;
   const int splits = pl.splits;
   if (splits > 1) {
-    UR_REQUIRE(workspace && workspace_bytes >= ur_gemm_workspace_bytes(a) && UR_ALIGNED16(workspace),
+    UR_REQUIRE(workspace && workspace_bytes >= ur_gemm_workspace_bytes(a),
                "ur_gemm: split_k workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)ur_gemm_workspace_bytes(a));
+    UR_REQUIRE(UR_ALIGNED16(workspace), "ur_gemm: the split_k workspace must be 16-byte aligned");
     p.ksplit_len = ur_cdiv(ur_cdiv(a->K, BK), splits) * BK;
     p.slab_stride = (long)a->M * a->ldc;
     p.C = workspace;
@@ -624,8 +631,11 @@ extern "C" int ur_gemm_grouped(const ur_gemm_args* a, int32_t count, void* works
   const GemmPlan pl = gemm_select_grouped(a, count);
   const int splits = pl.splits, BT = pl.tile;
   if (splits > 1)
-    UR_REQUIRE(workspace && UR_ALIGNED16(workspace) && workspace_bytes >= ur_gemm_grouped_workspace_bytes(a, count),
+  {
+    UR_REQUIRE(workspace && workspace_bytes >= ur_gemm_grouped_workspace_bytes(a, count),
                "ur_gemm_grouped: split_k workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)ur_gemm_grouped_workspace_bytes(a, count));
+    UR_REQUIRE(UR_ALIGNED16(workspace), "ur_gemm_grouped: the split_k workspace must be 16-byte aligned");
+  }
   GemmP p;
   fill_params(a, p);
   p.ksplit_len = ur_cdiv(ur_cdiv(a->K, BK), splits) * BK;

@@ -1447,6 +1447,7 @@ extern "C" int ur_rmsnorm_lora_fwd(const void* x, const float* w, void* out, flo
                                    const ur_lora_args* a, void* stream) {
   UR_REQUIRE(D == 1024, "ur_rmsnorm_lora_fwd: built for the hidden size 1024 (D=%d)", D);
   UR_REQUIRE(M >= 0 && x && w && out && rstd && UR_ALIGNED16(x) && UR_ALIGNED16(w) && UR_ALIGNED16(out), "ur_rmsnorm_lora_fwd: null / misaligned");
+  UR_REQUIRE((((uintptr_t)rstd) & 3) == 0, "ur_rmsnorm_lora_fwd: rstd must be 4-byte aligned");
   UR_REQUIRE(a && a->nad >= 1 && a->nad <= 3 && a->rank == 16 && a->shared == 1, "ur_rmsnorm_lora_fwd: 1 to 3 rank-16 adapters sharing the normalised input");
   UR_REQUIRE(a->P && (((uintptr_t)a->P) & 7) == 0 && (a->ldp % 4) == 0 && a->ldp >= 16 * a->nad, "ur_rmsnorm_lora_fwd: P must be 8-byte aligned, ldp %% 4 == 0, ldp >= 16 nad");
   UR_REQUIRE(!a->drop_bits || (UR_ALIGNED16(a->drop_bits) && (a->bits_ld % 16) == 0 && a->bits_ld >= D / 8 && (a->bits_stride % 16) == 0),
